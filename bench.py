@@ -17,12 +17,16 @@ into contiguous shards of 256/N per GPU (ffcnn_amd.dist.shard_range).  Weights
 are broadcast from rank 0 over RCCL once, before the timed region.
 
 Rank 0 prints ONE JSON line (see DESIGN.md "Measurement"):
-  value        whole-job frames/s
+  value        whole-job frames/s (ms_per_step: milliseconds of one timed step)
+A plain run sets up, warms up, times --steps steps and prints the line.  With --full
+the line also carries what takes runs of its own, among them:
   roofline     the depthwise 3x3 kernel on BASELINE config[1] (320x320x64, batch 64):
                algorithmic bytes / mean launch time measured with HIP events on
                the launch stream, against the 8 TB/s HBM3E peak
   cpu_baseline the reference conv-v6.c path (oracle/_ref, built with the
                reference's own flags) timed on this box's host cores, N=1 only
+--dump-outputs DIR writes the detection records of the last timed step as .npy files
+(the inputs are seeded: the same arguments give the same frames on every run).
 """
 import argparse
 import ctypes as C
@@ -327,6 +331,22 @@ def pw_roofline(torch, capi, stream):
             "workload": "pw1x1 256->512 20x20 batch 256 fp32 (BASELINE config[2])"}
 
 
+def dump_records(out_dir, rec):
+    """--dump-outputs: the detection records of one step (a DETS_DTYPE array, one record per frame) as two .npy files that two builds
+    can be compared by: dets_header (count, ncand, overflow, nfull per frame; float64) and dets_boxes (type, score, x1, y1, x2, y2 of
+    every box slot; float32, the slots past a frame's count zeroed so that stale slot contents never differ between runs)."""
+    os.makedirs(out_dir, exist_ok=True)
+    rec = np.array(rec, copy=True)
+    hdr = np.stack([rec[k].astype(np.float64) for k in ("count", "ncand", "overflow", "nfull")], axis=1)
+    box = rec["box"]
+    boxes = np.stack([box[k].astype(np.float32) for k in ("type", "score", "x1", "y1", "x2", "y2")], axis=-1)
+    nslot = boxes.shape[1]
+    boxes[np.arange(nslot)[None, :] >= np.clip(rec["count"], 0, nslot)[:, None]] = 0.0
+    np.save(os.path.join(out_dir, "dets_header.npy"), hdr)
+    np.save(os.path.join(out_dir, "dets_boxes.npy"), boxes)
+    return hdr.nbytes + boxes.nbytes
+
+
 def launch_plan(gpus, env, ndev, node=False):
     """How `bench.py --gpus N` runs, decided from the command line, the environment and the visible devices alone:
          ("inline", None)    this process is the job (N = 1), or one rank of a torchrun job whose WORLD_SIZE == N
@@ -473,6 +493,9 @@ def run_node(args):
     for d in range(N):
         torch.cuda.synchronize(d)
     dt = time.perf_counter() - t0
+    if args.dump_outputs and args.steps > 0:                    # recs = the last launch's records, MS steps of G frames in step order
+        q = (args.steps - 1) % MS
+        dump_records(args.dump_outputs, recs[q * G:(q + 1) * G])
     # frame 0 of the LAST step sits in slot (steps - 1) % D ... every slot's frame 0 is the test image
     ok = None
     if check is not None:
@@ -535,6 +558,14 @@ def main():
     ap.add_argument("--no-strong-extra", action="store_true", help="multi-GPU (or --force-gather) weak-scaling runs: skip the untimed strong_b256 extra (north_star's batch-256 job, "
                     "merged and one step per launch, on the same ranks)")
     ap.add_argument("--no-node-line", action="store_true", help="skip the extra c_node_api measurement (a child `bench.py --node` run by rank 0 after the timed job)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline value: the config[1] / config[2] rooflines, value_repeats, the single-chain and "
+                         "two-steps-per-launch extras, other nets, the CPU baseline, strong_b256 / strong_unmerged, the other input format and the "
+                         "c_node_api line (each still subject to its --no-* switch); a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the detection records of the last timed step (what the caller of the timed path "
+                         "receives) as DIR/*.npy: dets_header (frames x [count, ncand, overflow, nfull], float64) and dets_boxes "
+                         "(frames x MAX_DET x [type, score, x1, y1, x2, y2], float32; slots past count are zero)")
     args = ap.parse_args()
 
     import torch
@@ -550,9 +581,9 @@ def main():
         # `python bench.py --gpus N` with no launcher: become the launcher -- the same command line the driver uses for N > 1
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
                "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
-        print("bench.py: --gpus %d without a launcher: re-exec as %s" % (args.gpus, " ".join(cmd[1:9])), file=sys.stderr)
+        print("bench.py: --gpus %d without a launcher: running %s" % (args.gpus, " ".join(cmd[1:9])), file=sys.stderr)
         sys.stderr.flush()
-        os.execv(sys.executable, cmd)
+        raise SystemExit(subprocess.call(cmd))                  # a fresh child process: this one has already asked the runtime for its devices
 
     import torch.distributed as dist
     from ffcnn_amd import capi
@@ -785,12 +816,12 @@ def main():
         # comes out of them in its sustained clock / memory state.  After idle it needs ~10 ms of work to get there
         # (tools/short_run.py: 20 steps straight after a 50 ms pause run at 153 k frames/s, the same 20 steps back to back at
         # 182 k), which a 5-step warm-up (1.8 ms) does not provide; both measurements are independent of the net's.
-        if world == 1 and not args.no_kernel_roofline and with_roofline:
+        if world == 1 and args.full and not args.no_kernel_roofline and with_roofline:
             roof = kernel_roofline(torch, capi, stream)
             roof_pw = pw_roofline(torch, capi, stream)
             torch.cuda.synchronize()
         else:
-            # N > 1 (or --no-kernel-roofline): the same device state by other means -- ~40 ms of untimed forwards in front of the
+            # N > 1 (or a plain run, or --no-kernel-roofline): the same device state by other means -- ~40 ms of untimed forwards in front of the
             # W warm-up steps, on every rank.  Without them a short run at N > 1 is measured on a device that is still ramping
             # while the N = 1 run (which has just done its roofline launches) is not: 173 k against 184 k frames/s per GPU at 20
             # steps, a 6 % "scaling loss" that is measurement order and nothing else.
@@ -819,11 +850,21 @@ def main():
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
         assert [e.graph_captures for e in exs] == caps0, "a graph was captured inside the timed region"
+        # --dump-outputs: the records of the last timed step as rank 0 holds them, taken before anything else runs on these executors
+        last = None
+        if args.dump_outputs and rank == 0 and nl > 0:
+            q = (args.steps - 1) - (nl - 1) * MS                    # the last timed step inside the last launch
+            if host_dets:
+                last = np.array(exs[shipped["group"]].dets_host()[q * B:(q + 1) * B], copy=True)
+            else:                                               # every rank's shard of it, from the newest gathered slot, in rank order
+                sl = shipped["slot"]
+                last = np.concatenate([ffdist.unpack_records(host[shipped["group"]][r].numpy()[sl * pbytes:(sl + 1) * pbytes], capi.DETS_DTYPE)[q * B:(q + 1) * B]
+                                       for r in range(world)])
         # value_repeats: the SAME K-step region five more times, back to back behind the value (untimed extras, `value` is the first
         # region and nothing else).  A 20-step region is 6.5 ms; DESIGN.md section 7 found one region in ten 7 % slower because the chain that was
         # enqueued last falls out of lockstep in its first round -- on the odd repeats that chain is enqueued FIRST, which tests the explanation.
         reps = []
-        if world == 1 and not gather_mode and with_roofline:
+        if world == 1 and not gather_mode and with_roofline and args.full:
             for r in range(5):
                 fence()
                 t1 = time.perf_counter()
@@ -831,7 +872,7 @@ def main():
                     step(i, rev=bool(r & 1))
                 fence()
                 reps.append(time.perf_counter() - t1)
-        return dict(reps=reps, fwd=fwd, exs=exs, streams=streams, xs=xs, x=x, ex=ex, model_bytes=model_bytes, model_flops=model_flops, dt=dt, untimed=untimed, shipped=shipped, host=host, pbytes=pbytes, roof=roof, roof_pw=roof_pw, check=check, K_in=K_in, S=S, M=M, Bx=Bx, flags=flags, host_dets=host_dets, gather_mode=gather_mode)
+        return dict(last=last, reps=reps, fwd=fwd, exs=exs, streams=streams, xs=xs, x=x, ex=ex, model_bytes=model_bytes, model_flops=model_flops, dt=dt, untimed=untimed, shipped=shipped, host=host, pbytes=pbytes, roof=roof, roof_pw=roof_pw, check=check, K_in=K_in, S=S, M=M, Bx=Bx, flags=flags, host_dets=host_dets, gather_mode=gather_mode)
 
     J = job(MS, True)
     exs = J["exs"]
@@ -857,6 +898,8 @@ def main():
     flags = J["flags"]
     host_dets = J["host_dets"]
     gather_mode = J["gather_mode"]
+    if J["last"] is not None:
+        dump_records(args.dump_outputs, J["last"])
 
     out = None
     if rank == 0:
@@ -942,7 +985,7 @@ def main():
             out["roofline_pw"] = roof_pw
     # untimed extras (N = 1): one chain alone (latency of a batch), and the same job fed with u8 BGR frames (SURVEY 8(d) row 4:
     # "64 frames u8 BGR 320x320") through ffgpu_exec_forward_bgr_dev -- the letterbox / normalise kernel in front of the net
-    if rank == 0 and world == 1 and not gather_mode and not args.no_extras:
+    if rank == 0 and world == 1 and not gather_mode and args.full and not args.no_extras:
         torch.cuda.synchronize()
         nlat = 30
         for i in range(5):
@@ -974,7 +1017,7 @@ def main():
             for e in ex2:
                 e.close()
             del x2
-    if rank == 0 and world == 1 and not gather_mode and not args.no_extras:
+    if rank == 0 and world == 1 and not gather_mode and args.full and not args.no_extras:
         # SURVEY 8(f) rows 2 / 3 as throughput (untimed extras): another darknet cfg (yolov3-tiny-shaped, implicit-GEMM kernels) and the
         # reference CLI's geometry, batch 16 per step on four chains (tools/other_nets.py)
         try:
@@ -986,7 +1029,7 @@ def main():
             out["config"]["other_nets"] = other_nets.rows(torch, capi)
         except Exception as e:                                  # noqa: BLE001 -- an extra
             out["config"]["other_nets"] = {"error": repr(e)[:300]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         for e in exs:
             e.close()
         exs = []
@@ -995,7 +1038,7 @@ def main():
     for e in exs:
         e.close()
     exs = []
-    if (gather_mode or not args.no_extras) and not strong and not args.no_strong_extra and 256 % world == 0:
+    if args.full and (gather_mode or not args.no_extras) and not strong and not args.no_strong_extra and 256 % world == 0:
         # ONE driver command, both scaling answers: beside the weak-scaling headline (64 frames per GPU) the same ranks -- at N = 1
         # the one GPU, whose figure is the denominator of north_star's ">= 7.5 x at 8 GPUs vs 1 GPU on batch 256" -- run
         # north_star's strong-scaling job -- every step is the SAME 256 frames, rank r takes shard_range(256, r, N) -- merged (as many consecutive
@@ -1024,7 +1067,7 @@ def main():
         B, lo, G = keep
         if out is not None:
             out["strong_b256"] = sb
-    if world == 1 and not gather_mode and not args.no_extras:
+    if world == 1 and not gather_mode and args.full and not args.no_extras:
         # the same job from the OTHER input format, measured exactly like the value (own executors and inputs, same warm-up, K timed steps):
         # rounds 1-3 reported fp32-resident frames; since round 4 the value starts from the u8 images SURVEY 8(d) row 4 names
         xs = x = J = None
@@ -1038,7 +1081,7 @@ def main():
         for e in J2["exs"]:
             e.close()
         J2 = None
-    if strong and MS > 1:
+    if args.full and strong and MS > 1:
         # the same job with ONE step per launch (--merge-steps 1): what "batch 256 over N GPUs" gives when every launch carries exactly its
         # shard of one step.  Every rank takes part (the gather is collective); reported beside the merged headline, never instead of it.
         xs = x = J = None
@@ -1056,7 +1099,7 @@ def main():
     net.close()
     if world > 1 or args.force_gather:
         dist.destroy_process_group()
-    if out is not None and not args.no_node_line:
+    if out is not None and args.full and not args.no_node_line:
         # north_star's host path -- plain C over the C-ABI, one process for all GPUs -- measured beside the torchrun job: rank 0
         # (alone by now: the process group is gone, the other ranks are leaving) runs `bench.py --node` on the same N devices
         xs = x = J = None

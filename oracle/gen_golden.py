@@ -18,6 +18,8 @@ Fixtures are data (inputs + the reference's outputs); no reference source text.
   input_320.npz         net_input result checksum + samples
   cli.json              the reference CLI (oracle/_ref/ffcnn_ref_cli_v6 = build.sh's default link) on
                         data/test.bmp: printed detection lines and the sha256 of the out.bmp it writes
+  ref_pins.npz          tests/test_oracle_vs_ref.py's pins: sha256 of every layer output / input / weights, boxes,
+                        layer table, conv-v2.c on seeded layers, boxes of the candidate-capacity regimes
 """
 import json
 import os
@@ -98,6 +100,61 @@ def cli_golden():
     return res
 
 
+TABLE_FIELDS = ("type", "w", "h", "c", "fs", "fn", "stride", "pad", "groups", "batchnorm", "activation", "depend_num")
+V2_CASES = [(8, 9, 11, 1, 1, 1, 0, 12), (6, 8, 8, 6, 3, 1, 1, 6), (3, 10, 10, 1, 3, 2, 1, 8)]     # (ic, ih, iw, groups, fs, stride, pad, fn)
+CAP_REGIMES = (0, 700, 40)                                                                       # net->bbox_max (0 = the reference's own)
+
+
+def sha(a):
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def ref_pins():
+    """ref_pins.npz: what tests/test_oracle_vs_ref.py checks the oracle against, from the reference itself -- sha256 of every
+    layer's output, of net_input's result and of the weights, the boxes, the layer table, conv-v2.c on seeded single layers
+    and the boxes of the candidate-capacity regimes."""
+    bgr, bw, bh = orc.load_bmp()
+    pins = {}
+    r = orc.Ref("v0")
+    r.set_input_image(bgr, bw, bh)
+    pins["input_sha"] = np.array(sha(r.input))
+    pins["weights_sha"] = np.array(sha(np.ctypeslib.as_array(r.n.weight_buf, (r.n.weight_size,))))
+    outs = r.forward(keep_activations=True)
+    pins["layer_ids"] = np.array(sorted(outs), np.int32)
+    pins["layer_sha"] = np.array([sha(outs[i]) for i in sorted(outs)])
+    pins["boxes"] = np.frombuffer(r.boxes.tobytes(), np.uint8)
+    pins["layer_num"] = np.array(r.n.layer_num, np.int32)
+    pins["table"] = np.array([[getattr(r.layer(i), k) for k in TABLE_FIELDS] + list(r.layer(i).depend_list)
+                              for i in range(r.n.layer_num + 1)], np.int32)
+    r.close()
+    rng = np.random.default_rng(7)
+    r = orc.Ref("v2")
+    for k, (ic, ih, iw, g, fs, s, p, fn) in enumerate(V2_CASES):
+        K = fs * fs * ic // g
+        k4 = (K + 3) & ~3
+        x = rng.uniform(-1, 1, (ic, ih, iw)).astype(np.float32)
+        f = np.zeros((fn, k4 + 4), np.float32)
+        f[:, :K] = rng.uniform(-.5, .5, (fn, K))
+        f[:, k4] = 1.25
+        f[:, k4 + 1] = 0.03
+        pins["v2_%d_x" % k], pins["v2_%d_f" % k] = x, f
+        pins["v2_%d_out" % k] = r.groupconv(x, f, g, p, s, fs, 2)
+    r.close()
+    for bbox_max in CAP_REGIMES:
+        r = orc.Ref("v0")
+        for i in range(r.n.layer_num):
+            if r.layer(i).type == 7:
+                r.layer(i).ignore_thres = 0.0
+        if bbox_max:
+            r.n.bbox_max = bbox_max
+        r.set_input_image(bgr, bw, bh)
+        r.forward()
+        pins["cap_%d_boxes" % bbox_max] = np.frombuffer(r.boxes.tobytes(), np.uint8)
+        r.close()
+    np.savez_compressed(os.path.join(GOLD, "ref_pins.npz"), **pins)
+
+
 def main():
     orc.build()
     os.makedirs(GOLD, exist_ok=True)
@@ -160,6 +217,7 @@ def main():
     txt = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, check=True).stdout
     open(os.path.join(GOLD, "net_dump.txt"), "w").write(txt)
     cli_golden()
+    ref_pins()
     print("golden written to", GOLD)
     for fn_ in sorted(os.listdir(GOLD)):
         print("  %-24s %8d B" % (fn_, os.path.getsize(os.path.join(GOLD, fn_))))

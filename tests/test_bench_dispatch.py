@@ -60,3 +60,19 @@ def test_host_topology_counts_physical_cores():
         except OSError:
             sib.add(c)
     assert len(sib) == len(reps)
+
+
+def test_dump_records_writes_float_arrays(tmp_path):
+    """--dump-outputs: one step's records -> dets_header (float64) and dets_boxes (float32), the box slots past a frame's count zeroed"""
+    import numpy as np
+    from ffcnn_amd import capi
+    rec = np.zeros(3, capi.DETS_DTYPE)
+    rec["count"], rec["ncand"], rec["overflow"], rec["nfull"] = [2, 0, 1], [9, 4, 7], [0, 0, 1], [2, 0, 1]
+    rec["box"]["type"], rec["box"]["score"], rec["box"]["x1"], rec["box"]["y2"] = 3, 0.5, 1.25, -2.0     # stale contents in every slot
+    nbytes = _bench().dump_records(str(tmp_path / "out"), rec)
+    hdr, boxes = np.load(tmp_path / "out" / "dets_header.npy"), np.load(tmp_path / "out" / "dets_boxes.npy")
+    assert nbytes == hdr.nbytes + boxes.nbytes
+    assert hdr.dtype == np.float64 and hdr.tolist() == [[2, 9, 0, 2], [0, 4, 0, 0], [1, 7, 1, 1]]
+    assert boxes.dtype == np.float32 and boxes.shape == (3, capi.FFGPU.MAX_DET, 6)
+    assert boxes[0, :2].tolist() == [[3, 0.5, 1.25, 0, 0, -2.0]] * 2 and boxes[2, 0].tolist() == [3, 0.5, 1.25, 0, 0, -2.0]
+    assert not boxes[0, 2:].any() and not boxes[1].any() and not boxes[2, 1:].any()

@@ -11,6 +11,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COMMON = ["--steps", "8", "--warmup", "4", "--no-cpu-baseline", "--no-kernel-roofline", "--no-extras"]
 NO_NODE = ["--no-node-line"]
+FULL = ["--full"]                                              # the extras beside the value (c_node_api, strong_b256, strong_unmerged) run only with --full
 
 
 def run(cmd, port=None):
@@ -36,7 +37,7 @@ def check_line(d, scaling, frames):
 
 @pytest.mark.gpu
 def test_bench_default_step():
-    d = run([sys.executable, "bench.py"] + COMMON)
+    d = run([sys.executable, "bench.py"] + COMMON + FULL)
     check_line(d, "weak", 64)
     assert d["config"]["untimed_forwards_before_t0"] > 0
     # beside it: the same job through the C node API (a child `bench.py --node`), same metric, boxes checked there as well
@@ -62,7 +63,7 @@ def test_bench_node_mode():
 @pytest.mark.gpu
 def test_bench_gather_step_under_torchrun():
     d = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-             "--master-port", "29541", "bench.py", "--gpus", "1", "--force-gather"] + COMMON + NO_NODE)
+             "--master-port", "29541", "bench.py", "--gpus", "1", "--force-gather"] + COMMON + NO_NODE + FULL)
     check_line(d, "weak", 64)
     assert "RCCL gather" in d["config"]["gather"]
     # one command, both scaling answers: the weak-scaling line carries north_star's batch-256 job (merged and one step per launch) as an extra,
@@ -101,7 +102,7 @@ def test_bench_refuses_more_gpus_than_visible():
 def test_bench_strong_scaling_reports_both_schedules():
     """strong scaling with a shard of 32 frames (the per-GPU load of 256 frames over 8 GPUs): the headline merges 4 steps per launch,
     the one-step-per-launch figure stands beside it; the line names the size of the RCCL communicator it created"""
-    d = run([sys.executable, "bench.py", "--force-gather", "--global-batch", "32"] + COMMON + NO_NODE, port=29549)
+    d = run([sys.executable, "bench.py", "--force-gather", "--global-batch", "32"] + COMMON + NO_NODE + FULL, port=29549)
     check_line(d, "strong", 32)
     assert d["config"]["steps_per_launch"] == 4 and d["config"]["frames_per_launch"] == 128
     u = d["strong_unmerged"]
@@ -111,8 +112,31 @@ def test_bench_strong_scaling_reports_both_schedules():
 
 @pytest.mark.gpu
 def test_bench_default_line_has_strong_b256():
-    """the N = 1 line without --no-extras: the batch-256 job (the denominator of north_star's 8-vs-1 sentence) sits beside the value, as it does at N > 1"""
-    d = run([sys.executable, "bench.py", "--steps", "8", "--warmup", "4", "--no-cpu-baseline", "--no-kernel-roofline", "--no-node-line"])
+    """the N = 1 --full line without --no-extras: the batch-256 job (the denominator of north_star's 8-vs-1 sentence) sits beside the value, as it does at N > 1"""
+    d = run([sys.executable, "bench.py", "--steps", "8", "--warmup", "4", "--no-cpu-baseline", "--no-kernel-roofline", "--no-node-line"] + FULL)
     check_line(d, "weak", 64)
     sb = d["strong_b256"]
     assert sb["global_batch"] == 256 and sb["frames_per_gpu"] == 256 and sb["n_gpus"] == 1 and sb["merged"]["value"] > 0 and sb["merged"]["frames_per_launch"] == 256
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """the plain command (no --full) times the steps and prints the line without the extras; --dump-outputs writes the last timed step's
+    records as float .npy files, frame 0 (the test image) holding the reference's golden boxes"""
+    d = run([sys.executable, "bench.py", "--gpus", "1", "--steps", "8", "--warmup", "4", "--dump-outputs", str(tmp_path)])
+    check_line(d, "weak", 64)
+    for key in ("roofline", "roofline_pw", "value_repeats", "cpu_baseline", "strong_b256", "c_node_api"):
+        assert key not in d, key
+    assert "other_nets" not in d["config"] and "fp32_resident_input" not in d["config"]
+    import numpy as np
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["dets_boxes.npy", "dets_header.npy"], files
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 << 20
+    hdr, boxes = np.load(tmp_path / "dets_header.npy"), np.load(tmp_path / "dets_boxes.npy")
+    assert hdr.dtype == np.float64 and hdr.shape == (64, 4) and boxes.dtype == np.float32 and boxes.shape[0] == 64 and boxes.shape[2] == 6
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "boxes.json")))["net_320x320_v0"]["boxes"]
+    assert int(hdr[0, 0]) == len(want)
+    for got, w in zip(boxes[0], want):                           # u8 input: boxes in the 320-pixel frame, the golden ones in the 640-wide source
+        assert int(got[0]) == int(w["type"]) and abs(float(got[1]) - float(w["score"])) < 1e-4
+        assert max(abs(2.0 * float(got[2 + i]) - float(w[k])) for i, k in enumerate(("x1", "y1", "x2", "y2"))) < 0.05
+    assert not boxes[0, len(want):].any()
