@@ -48,8 +48,13 @@ class FrameDets(C.Structure):        # ffgpu_frame_dets
                 ("box", BBOX * FFGPU.MAX_DET)]
 
 
+class BgrFrame(C.Structure):         # ffgpu_bgr_frame (24 bytes): one u8 BGR frame of a mixed batch
+    _fields_ = [("bgr", C.c_void_p), ("w", C.c_int), ("h", C.c_int), ("pitch", C.c_int), ("reserved", C.c_int)]
+
+
 assert C.sizeof(LAYER) == 120 and C.sizeof(NET) == 104 and C.sizeof(BBOX) == 24
 assert C.sizeof(FrameDets) == 16 + 24 * FFGPU.MAX_DET
+assert C.sizeof(BgrFrame) == 24
 
 BOX_DTYPE = np.dtype([("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
 DETS_DTYPE = np.dtype([("count", "<i4"), ("ncand", "<i4"), ("overflow", "<i4"), ("nfull", "<i4"),
@@ -61,7 +66,7 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_net_weights_dev", "ffgpu_net_weights_commit",
            "ffgpu_exec_create", "ffgpu_exec_destroy", "ffgpu_exec_batch", "ffgpu_exec_arena_bytes",
            "ffgpu_exec_kernel_count", "ffgpu_exec_work_model", "ffgpu_exec_set_scale", "ffgpu_exec_forward_dev", "ffgpu_exec_forward_host",
-           "ffgpu_exec_forward_bgr_dev", "ffgpu_exec_dets_dev", "ffgpu_exec_dets_host", "ffgpu_exec_set_ring", "ffgpu_exec_set_ring_strided", "ffgpu_exec_read_dets", "ffgpu_exec_read_layer", "ffgpu_exec_hash_layers",
+           "ffgpu_exec_forward_bgr_dev", "ffgpu_exec_forward_bgr_frames_dev", "ffgpu_exec_dets_dev", "ffgpu_exec_dets_host", "ffgpu_exec_set_ring", "ffgpu_exec_set_ring_strided", "ffgpu_exec_read_dets", "ffgpu_exec_read_layer", "ffgpu_exec_hash_layers",
            "ffgpu_exec_read_boxes", "ffgpu_exec_cand_capacity", "ffgpu_exec_graph_captures",
            "ffgpu_exec_profile", "ffgpu_exec_profile_steps", "ffgpu_exec_step_model", "ffgpu_groupconv_dev", "ffgpu_groupconv_kernel_name", "ffgpu_groupconv_time_dev", "ffgpu_irb_dev", "ffgpu_dwpw_dev", "ffgpu_packed_records_bytes", "ffgpu_pack_records", "ffgpu_unpack_records",
            "ffgpu_shard_range", "ffgpu_node_create", "ffgpu_node_destroy", "ffgpu_node_ndev", "ffgpu_node_shard", "ffgpu_node_set_scale",
@@ -126,6 +131,7 @@ def lib():
     L.ffgpu_exec_forward_dev.argtypes = [vp, vp, vp]
     L.ffgpu_exec_forward_host.argtypes = [vp, f32p]
     L.ffgpu_exec_forward_bgr_dev.argtypes = [vp, vp, i, i, f32p, f32p, vp]
+    L.ffgpu_exec_forward_bgr_frames_dev.argtypes = [vp, C.POINTER(BgrFrame), i, f32p, f32p, vp]
     L.ffgpu_exec_dets_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
     L.ffgpu_exec_dets_host.restype = vp; L.ffgpu_exec_dets_host.argtypes = [vp]
     L.ffgpu_exec_set_ring.argtypes = [vp, vp, C.c_int]
@@ -389,6 +395,15 @@ class Executor:
         m, s = (C.c_float * 3)(*mean), (C.c_float * 3)(*norm)
         _check(lib().ffgpu_exec_forward_bgr_dev(self.h, dev_ptr, w, h, m, s, stream), "ffgpu_exec_forward_bgr_dev")
 
+    def forward_bgr_frames_dev(self, frames, mean=(0.0, 0.0, 0.0), norm=(1 / 255.0,) * 3, stream=None):
+        """one forward of mixed-size u8 BGR frames (ffgpu_exec_forward_bgr_frames_dev): frames is a sequence of (ptr, w, h, pitch) tuples
+        (pitch 0 = ALIGN(3 w, 4)) or torch.uint8 device tensors of shape (h, pitch) (w = pitch // 3) or (h, w, 3)"""
+        arr = (BgrFrame * max(1, len(frames)))()
+        for k, f in enumerate(frames):
+            arr[k] = BgrFrame(*bgr_frame_desc(f))
+        m, s = (C.c_float * 3)(*mean), (C.c_float * 3)(*norm)
+        _check(lib().ffgpu_exec_forward_bgr_frames_dev(self.h, arr, len(frames), m, s, stream), "ffgpu_exec_forward_bgr_frames_dev")
+
     def dets_dev(self):
         ptr, nbytes = C.c_void_p(), C.c_size_t()
         _check(lib().ffgpu_exec_dets_dev(self.h, C.byref(ptr), C.byref(nbytes)), "ffgpu_exec_dets_dev")
@@ -467,6 +482,30 @@ class Executor:
         us = (C.c_float * 8)()
         _check(lib().ffgpu_exec_profile(self.h, dev_ptr, us), "ffgpu_exec_profile")
         return list(us)
+
+
+def bgr_frame_desc(f):
+    """(ptr, w, h, pitch, 0) of one frame for ffgpu_exec_forward_bgr_frames_dev: a (ptr, w, h[, pitch]) tuple, or a torch.uint8 device
+    tensor of shape (h, w, 3) (rows may be strided) or (h, pitch) (w = pitch // 3)"""
+    if isinstance(f, (tuple, list)):
+        ptr, w, h = f[0], f[1], f[2]
+        return (ptr, w, h, f[3] if len(f) > 3 else 0, 0)
+    import torch
+    if f.dtype != torch.uint8:
+        raise TypeError("frames must be torch.uint8 tensors, not %s" % f.dtype)
+    if not f.is_cuda:
+        raise ValueError("frames must be device tensors (the kernels read them on the GPU), not %s ones" % f.device)
+    if f.dim() == 3:
+        h, w, c = f.shape
+        if c != 3 or f.stride(2) != 1 or f.stride(1) != 3:
+            raise ValueError("an (h, w, 3) frame needs contiguous pixels (strides (pitch, 3, 1))")
+        return (f.data_ptr(), w, h, f.stride(0) if h > 1 else 3 * w, 0)
+    if f.dim() == 2:
+        h, pitch = f.shape
+        if f.stride(1) != 1:
+            raise ValueError("an (h, pitch) frame needs contiguous rows")
+        return (f.data_ptr(), pitch // 3, h, f.stride(0) if h > 1 else pitch, 0)
+    raise ValueError("a frame is (h, w, 3) or (h, pitch)")
 
 
 def shard_range(total, rank, world):

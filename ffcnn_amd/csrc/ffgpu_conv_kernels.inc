@@ -1427,10 +1427,22 @@ bool ffgpu_front_ok(const ConvDesc &c, const IrbDesc &d)
 
 // u8: the frames of this forward are u8 BGR images described by the executor's parameter block (c.in_ind IS that block: its
 // first member is the fp32 frame pointer the other form reads)
-int ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, hipStream_t s, bool u8)
+// three columns per lane (54 of 64 lanes on a 160-pixel row instead of 40) where the row fits a wave that way; FFGPU_FRONT_NC=4: the round-1 form.
+// ONE form for u8 and fp32 frames: each form sits within tolerance of the reference, but the two are not bit-identical to each other, and the same frames
+// must give the same records whichever way they arrive (tests/test_gpu_round3.py::test_u8_frames_into_the_first_kernel)
+int ffgpu_front_nc(const IrbDesc &d)
+{
+    return env_int("FFGPU_FRONT_NC", 3) == 3 && d.W >= 6 && (d.W + 2) / 3 <= 64 ? 3 : 4;
+}
+
+// resize: u8 frames of any size described one by one by the parameter block's frames_tab (ffgpu_exec_forward_bgr_frames_dev).  Three columns per
+// lane only: the four-column form of the gather does not fit a wave's registers, so the executor stages those frames (ffgpu_front_nc == 4) instead.
+int ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, hipStream_t s, bool u8, bool resize)
 {
     if (!ffgpu_front_ok(c, d)) { ffgpu_set_error("front: unsupported layer pair"); return -1; }
-    if (u8 && !c.in_ind) { ffgpu_set_error("front: the u8 form needs the executor's parameter block"); return -1; }
+    if ((u8 || resize) && !c.in_ind) { ffgpu_set_error("front: the u8 form needs the executor's parameter block"); return -1; }
+    const int nc = ffgpu_front_nc(d);
+    if (resize && nc != 3) { ffgpu_set_error("front: the resizing form has three columns per lane only (plane width %d)", d.W); return -1; }
     auto slope = [](int act) { return act == 2 ? 0.1f : (act == 1 ? 0.f : 1.f); };
     FrontP p;
     p.in = c.in; p.in_ind = c.in_ind; p.prm = reinterpret_cast<const ExecParams *>(c.in_ind); p.out = d.out; p.f0 = c.filt; p.w1 = d.w1; p.wd = d.wd; p.w2 = d.w2;
@@ -1443,11 +1455,9 @@ int ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, hipStream_t s, bool 
     p.ntasks = d.N * p.nbands;
     p.act0 = slope(c.act); p.act1 = slope(d.act1); p.actd = slope(d.actd); p.act2 = slope(d.act2);
     const dim3 grid((unsigned)((p.ntasks + 3) / 4));
-    // three columns per lane (54 of 64 lanes on a 160-pixel row instead of 40) where the row fits a wave that way; FFGPU_FRONT_NC=4: the round-1 form.
-    // ONE form for u8 and fp32 frames: each form sits within tolerance of the reference, but the two are not bit-identical to each other, and the same frames
-    // must give the same records whichever way they arrive (tests/test_gpu_round3.py::test_u8_frames_into_the_first_kernel)
-    const int nc = env_int("FFGPU_FRONT_NC", 3) == 3 && d.W >= 6 && (d.W + 2) / 3 <= 64 ? 3 : 4;
-    if (nc == 3) {
+    if (resize) {
+        hipLaunchKernelGGL((k_front<4, true, 3, true>), grid, dim3(256), 0, s, p);
+    } else if (nc == 3) {
         if (u8) hipLaunchKernelGGL((k_front<4, true, 3>), grid, dim3(256), 0, s, p);
         else    hipLaunchKernelGGL((k_front<4, false, 3>), grid, dim3(256), 0, s, p);
     } else {

@@ -63,7 +63,8 @@ void   ffgpu_irb_plan(IrbDesc &d);                     // freezes what the packe
 int    ffgpu_irb_pack(const IrbDesc &d, float *pk, hipStream_t s);
 int    ffgpu_launch_irb(const IrbDesc &d, hipStream_t s);
 bool   ffgpu_front_ok(const ConvDesc &c, const IrbDesc &d);      // first layer (3x3 s2, 3 -> 8) + thin block as one streaming kernel
-int    ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, hipStream_t s, bool u8 = false);
+int    ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, hipStream_t s, bool u8 = false, bool resize = false);   // resize: u8 frames of the parameter block's frames_tab
+int    ffgpu_front_nc(const IrbDesc &d);                         // output columns per lane k_front uses for this block (3 or 4; the resizing form: 3 only)
 
 // depthwise K x K (stride 1, same padding) + pointwise 1 x 1 as one launch (ffgpu_dwpw.inc); dw.out == pw.in is never written
 bool   ffgpu_dwpw_ok(const ConvDesc &dw, const ConvDesc &pw);
@@ -74,6 +75,17 @@ int    ffgpu_launch_dwpw(const ConvDesc &dw, const ConvDesc &pw, const float *wp
 size_t ffgpu_pw_pack_floats(const ConvDesc &d);
 void   ffgpu_conv_plan(ConvDesc &d);                   // freezes kernel / nsplit / x3_mt for this layer NOW (the tuning environment is read once, here)
 int    ffgpu_pw_pack(const ConvDesc &d, float *pk, hipStream_t s);
+
+// One frame of ffgpu_exec_forward_bgr_frames_dev as the kernels read it: the caller's descriptor plus net_input's letterbox
+// arithmetic (ffcnn.c:267-273), computed once on the host.  The executor keeps a device table of `batch` of them.
+struct FrameDesc {
+    const unsigned char *bgr;     // row 0 of the frame (any byte alignment)
+    int w, h, pitch;              // pitch: bytes from one row to the next (>= 3 w)
+    int sw, sh, s1, s2;           // the frame fills the top-left sw x sh of the net's plane; source pixel of (x, y) = (x s1 / s2, y s1 / s2)
+    int pad_;
+};
+int  ffgpu_launch_set_frames(FrameDesc *d_tab, const FrameDesc *h_desc, int n, hipStream_t s);
+int  ffgpu_launch_input_frames(const FrameDesc *d_tab, float *out, int N, int W, int H, const float mean[3], const float norm[3], hipStream_t s);
 
 // Per-executor parameter block in device memory: what changes from one forward to the next without changing the
 // launch list.  A one-thread kernel (ffgpu_launch_set_params) rewrites it in stream order in front of the graph launch,
@@ -89,6 +101,9 @@ struct ExecParams {
     long  bgr_frame;          // bytes from one frame to the next
     int   bgr_pitch;          // bytes per image row (ALIGN(3 w, 4), ffcnn.c:262)
     float mean[3], norm[3];   // net_input's per-channel mean / norm (plane order R, G, B)
+    // ffgpu_exec_forward_bgr_frames_dev: this forward's per-frame table (N entries; k_nms takes each frame's s1 / s2 from it, the
+    // resizing k_front its source); NULL for every other entry point
+    const FrameDesc *frames_tab;
 };
 int  ffgpu_launch_set_params(ExecParams *d_prm, const ExecParams &v, hipStream_t s);
 bool ffgpu_conv_supports_ind(const ConvDesc &d);    // the kernel ffgpu_launch_conv would pick reads ConvDesc::in_ind

@@ -209,6 +209,14 @@ struct ffgpu_exec {
     const unsigned char *bgr = nullptr; long bgr_frame = 0; int bgr_pitch = 0; float bgr_mean[3] = {}, bgr_norm[3] = {};
     bool u8_mode = false;              // the forward being enqueued / captured reads `bgr`
     hipGraphExec_t graph_u8 = nullptr; // its graph (the u8 form of the first kernel is another kernel): captured on first use
+    // mixed u8 frames (ffgpu_exec_forward_bgr_frames_dev): the device table of per-frame descriptors (one entry per frame, what
+    // d_prm->frames_tab names during such a forward) and the resizing first kernel's graph (captured on first use)
+    FrameDesc *d_ftab = nullptr;       // owned by the executor that allocated it (a split executor's halves point into their parent's)
+    const FrameDesc *ftab = nullptr;   // the table the forward being enqueued reads (NULL: every other entry point)
+    std::vector<FrameDesc> ftab_sent; hipStream_t ftab_stream = nullptr;      // what d_ftab holds (or will, on ftab_stream)
+    bool rs_mode = false;              // the forward being enqueued / captured runs the resizing u8 form of the first kernel
+    bool rs_last = false;              // ... and the last forward pushed did (read_layer(-1): no fp32 input tensor exists)
+    hipGraphExec_t graph_rs = nullptr;
     float *h_stage = nullptr;          // ffgpu_exec_forward_host from caller memory: page-locked staging of one batch (on first use)
     ffgpu_frame_dets *ring = nullptr; int ring_slots = 0; int *d_ringctr = nullptr;   // ffgpu_exec_set_ring
     int ring_stride = 0;               // records per ring slot (the parent's batch for the halves of a split executor)
@@ -716,7 +724,7 @@ static int issue_step(ffgpu_exec *ex, const Step &st, const float *d_frames, hip
     case S_FRONT: {
         ConvDesc d = st.conv;
         if (st.in_is_input && !d.in_ind) d.in = d_frames;
-        return ffgpu_launch_front(d, st.irb, s, ex->u8_mode); }
+        return ffgpu_launch_front(d, st.irb, s, ex->u8_mode, ex->rs_mode); }
     case S_YOLO:
         return ffgpu_launch_yolo(st.head, ex->N, ex->in_w, ex->in_h, ex->d_cand, ex->d_cand_key, ex->d_ncand, ex->cand_cap,
                                  st.flag ? ex->d_ringctr : nullptr, s);          // forwards are counted whether or not a ring is attached
@@ -785,7 +793,8 @@ static int push_params(ffgpu_exec *ex, const float *d_frames, hipStream_t s)
             ch->s1 = ex->s1; ch->s2 = ex->s2; ch->bbox_max = ex->bbox_max; ch->last_stream = s;
             ch->u8_mode = ex->u8_mode; ch->bgr = ex->bgr ? ex->bgr + (long)c * ch->N * ex->bgr_frame : nullptr; ch->bgr_frame = ex->bgr_frame; ch->bgr_pitch = ex->bgr_pitch;
             memcpy(ch->bgr_mean, ex->bgr_mean, sizeof ch->bgr_mean); memcpy(ch->bgr_norm, ex->bgr_norm, sizeof ch->bgr_norm);
-            if (push_params(ch, ex->u8_mode ? nullptr : d_frames + c * part, s)) return -1;
+            ch->rs_mode = ex->rs_mode; ch->ftab = ex->ftab ? ex->ftab + (size_t)c * ch->N : nullptr;      // each half reads its own half of the table
+            if (push_params(ch, ex->u8_mode || ex->rs_mode ? nullptr : d_frames + c * part, s)) return -1;
         }
         return 0;
     }
@@ -793,10 +802,11 @@ static int push_params(ffgpu_exec *ex, const float *d_frames, hipStream_t s)
     ExecParams v;
     memset(&v, 0, sizeof v);
     v.frames = d_frames; v.s1 = ex->s1; v.s2 = ex->s2;
-    if (ex->u8_mode) {
-        v.bgr = ex->bgr; v.bgr_frame = ex->bgr_frame; v.bgr_pitch = ex->bgr_pitch;
+    if (ex->u8_mode) { v.bgr = ex->bgr; v.bgr_frame = ex->bgr_frame; v.bgr_pitch = ex->bgr_pitch; }
+    if (ex->u8_mode || ex->rs_mode)
         for (int k = 0; k < 3; k++) { v.mean[k] = ex->bgr_mean[k]; v.norm[k] = ex->bgr_norm[k]; }
-    }
+    ex->rs_last = ex->rs_mode;
+    v.frames_tab = ex->ftab;
     v.bbox_max = ex->bbox_max;
     v.ring = ex->ring; v.ring_slots = ex->ring_slots; v.ring_stride = ex->ring_stride ? ex->ring_stride : ex->N;
     if (ex->prm_valid && ex->prm_stream == s && memcmp(&v, &ex->prm_sent, sizeof v) == 0) return 0;
@@ -836,6 +846,7 @@ static void drop_graphs(ffgpu_exec *ex)                       // caller has sync
 {
     if (ex->graph1) { (void)hipGraphExecDestroy(ex->graph1); ex->graph1 = nullptr; }
     if (ex->graph_u8) { (void)hipGraphExecDestroy(ex->graph_u8); ex->graph_u8 = nullptr; }
+    if (ex->graph_rs) { (void)hipGraphExecDestroy(ex->graph_rs); ex->graph_rs = nullptr; }
     for (auto &g : ex->graphs) (void)hipGraphExecDestroy(g.g);
     ex->graphs.clear();
 }
@@ -857,7 +868,7 @@ static int forward_on(ffgpu_exec *ex, const float *d_frames, hipStream_t s)
     if (push_params(ex, d_frames, s)) return -1;
     if (ex->flags & FFGPU_NO_GRAPH) return ex->child[0] ? issue_split(ex, d_frames, s) : issue_all(ex, d_frames, s);
     if (graph_pointer_free(ex)) {                            // the usual case: one graph, whatever the input buffer / scale
-        hipGraphExec_t &g1 = ex->u8_mode ? ex->graph_u8 : ex->graph1;      // (+ one more when u8 frames go straight into the first kernel)
+        hipGraphExec_t &g1 = ex->rs_mode ? ex->graph_rs : ex->u8_mode ? ex->graph_u8 : ex->graph1;      // (+ one more per u8 form of the first kernel)
         if (!g1 && capture(ex, d_frames, &g1)) return -1;
         FFGPU_CHECK(hipGraphLaunch(g1, s));
         return 0;
@@ -1016,7 +1027,7 @@ extern "C" void ffgpu_exec_destroy(ffgpu_exec *ex)
     for (const Step &st : ex->steps) if (st.kind == S_TOCNHW) (void)hipFree(st.out);
     (void)hipFree(ex->arena); (void)hipFree(ex->d_input); (void)hipFree(ex->d_pack); (void)hipFree(ex->d_cand);
     (void)hipFree(ex->d_cand_key); (void)hipFree(ex->d_ncand); (void)hipFree(ex->d_dets);
-    (void)hipFree(ex->d_full); (void)hipFree(ex->d_prm); (void)hipFree(ex->d_nms_scratch);
+    (void)hipFree(ex->d_full); (void)hipFree(ex->d_prm); (void)hipFree(ex->d_nms_scratch); (void)hipFree(ex->d_ftab);
     if (ex->h_dets) (void)hipHostFree(ex->h_dets);
     if (ex->h_stage) (void)hipHostFree(ex->h_stage);
     (void)hipFree(ex->d_ringctr);
@@ -1146,6 +1157,19 @@ static bool front_reads_u8(const ffgpu_exec *ex)
     return false;
 }
 
+// ... and that kernel has the resizing form: three columns per lane (ffgpu_front_nc)
+static bool front_resizes(const ffgpu_exec *ex)
+{
+    if (!front_reads_u8(ex)) return false;
+    if (ex->child[0]) {
+        for (int c = 0; c < ex->nchild; c++) if (!front_resizes(ex->child[c])) return false;
+        return true;
+    }
+    for (const Step &st : ex->steps)
+        if (st.in_is_input) return st.kind == S_FRONT && ffgpu_front_nc(st.irb) == 3;
+    return false;
+}
+
 extern "C" int ffgpu_exec_forward_bgr_dev(ffgpu_exec *ex, const unsigned char *d_bgr, int w, int h,
                                           const float mean[3], const float norm[3], void *stream)
 {
@@ -1171,6 +1195,60 @@ extern "C" int ffgpu_exec_forward_bgr_dev(ffgpu_exec *ex, const unsigned char *d
     if (ensure_input(ex)) return -1;
     if (ffgpu_launch_input_bgr(d_bgr, ex->d_input, ex->N, w, h, W, H, sw, sh, s1, s2, mean, norm, s)) return -1;
     return forward_on(ex, ex->d_input, s);
+}
+
+// Mixed-size u8 frames: per frame net_input's letterbox arithmetic (ffcnn.c:262-273) on the host, the table written in stream order in
+// front of the forward (skipped when it holds these values already), then either the resizing k_front reads the bytes itself (plans that
+// start with k_front) or k_input_frames writes the fp32 batch the ordinary graph consumes.  The executor's own scale stays as it was:
+// k_nms takes each frame's s1 / s2 from the table.
+extern "C" int ffgpu_exec_forward_bgr_frames_dev(ffgpu_exec *ex, const ffgpu_bgr_frame *frames, int nframes,
+                                                 const float mean[3], const float norm[3], void *stream)
+{
+    int ndev = 0;
+    if (!ex && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)) {
+        (void)hipGetLastError();
+        ffgpu_set_error("forward_bgr_frames_dev: no HIP device visible: libffcnn_hip has no CPU fallback");
+        return -1;
+    }
+    if (!alive(ex, "forward_bgr_frames_dev")) return -1;
+    if (!frames || !mean || !norm) { ffgpu_set_error("forward_bgr_frames_dev: NULL argument"); return -1; }
+    if (nframes != ex->N) { ffgpu_set_error("forward_bgr_frames_dev: %d frames for an executor of batch %d", nframes, ex->N); return -1; }
+    if (ex->in_c != 3) { ffgpu_set_error("forward_bgr_frames_dev: the net's input has %d channels, not 3", ex->in_c); return -1; }
+    const int W = ex->in_w, H = ex->in_h;
+    std::vector<FrameDesc> tab((size_t)nframes);
+    for (int n = 0; n < nframes; n++) {
+        const ffgpu_bgr_frame &f = frames[n];
+        if (!f.bgr) { ffgpu_set_error("forward_bgr_frames_dev: frame %d: NULL bgr", n); return -1; }
+        if (f.w <= 0 || f.h <= 0 || 3L * f.w > 0x7fffffffL) { ffgpu_set_error("forward_bgr_frames_dev: frame %d: bad size %d x %d", n, f.w, f.h); return -1; }
+        if (f.reserved != 0) { ffgpu_set_error("forward_bgr_frames_dev: frame %d: reserved must be 0", n); return -1; }
+        const long pitch = f.pitch ? (long)f.pitch : ((3L * f.w + 3) & ~3L);
+        if (pitch < 3L * f.w || pitch > 0x7fffffffL) { ffgpu_set_error("forward_bgr_frames_dev: frame %d: pitch %d is below 3 w = %ld", n, f.pitch, 3L * f.w); return -1; }
+        FrameDesc &d = tab[n];
+        memset(&d, 0, sizeof d);
+        d.bgr = f.bgr; d.w = f.w; d.h = f.h; d.pitch = (int)pitch;
+        if ((long)f.w * H > (long)f.h * W) { d.sw = W; d.sh = (int)((long)d.sw * f.h / f.w); d.s1 = f.w; d.s2 = d.sw; }      // ffcnn.c:267-273
+        else                               { d.sh = H; d.sw = (int)((long)d.sh * f.w / f.h); d.s1 = f.h; d.s2 = d.sh; }
+    }
+    hipStream_t s = stream ? (hipStream_t)stream : ex->own_stream;
+    if (!ex->d_ftab) FFGPU_CHECK(hipMalloc(&ex->d_ftab, sizeof(FrameDesc) * (size_t)ex->N));
+    if (!(ex->ftab_stream == s && ex->ftab_sent.size() == tab.size() && memcmp(ex->ftab_sent.data(), tab.data(), sizeof(FrameDesc) * tab.size()) == 0)) {
+        ex->ftab_sent.clear();
+        if (ffgpu_launch_set_frames(ex->d_ftab, tab.data(), nframes, s)) return -1;
+        ex->ftab_sent = tab; ex->ftab_stream = s;
+    }
+    for (int k = 0; k < 3; k++) { ex->bgr_mean[k] = mean[k]; ex->bgr_norm[k] = norm[k]; }
+    ex->ftab = ex->d_ftab;
+    int rc;
+    if (!getenv("FFGPU_NO_U8_FRONT") && front_resizes(ex)) {         // the resizing first kernel reads the frames itself: no fp32 batch
+        ex->rs_mode = true;
+        rc = forward_on(ex, nullptr, s);
+        ex->rs_mode = false;
+    } else {                                                         // staged: the fp32 batch, then the ordinary graph
+        rc = -1;
+        if (!ensure_input(ex) && !ffgpu_launch_input_frames(ex->d_ftab, ex->d_input, ex->N, W, H, mean, norm, s)) rc = forward_on(ex, ex->d_input, s);
+    }
+    ex->ftab = nullptr;
+    return rc;
 }
 
 extern "C" int ffgpu_exec_dets_dev(ffgpu_exec *ex, void **dev_ptr, size_t *bytes)
@@ -1291,7 +1369,7 @@ extern "C" int ffgpu_exec_read_layer(ffgpu_exec *ex, int layer, int frame, float
     }
     if (layer == -1) {                                            // the network input as the first layer saw it (frame-major)
         const size_t fl = (size_t)ex->in_c * ex->in_h * ex->in_w;
-        if (!ex->last_frames && ex->bgr) { ffgpu_set_error("read_layer: the last forward's frames were u8 images converted by the first kernel -- no fp32 input tensor exists"); return -1; }
+        if (!ex->last_frames && (ex->bgr || ex->rs_last)) { ffgpu_set_error("read_layer: the last forward's frames were u8 images converted by the first kernel -- no fp32 input tensor exists"); return -1; }
         if (!ex->last_frames) { ffgpu_set_error("read_layer: no forward has run yet"); return -1; }
         if (fl > cap_floats) { ffgpu_set_error("read_layer: buffer too small"); return -1; }
         if (copy_d2h(host_out, ex->last_frames + (size_t)frame * fl, fl * sizeof(float))) return -1;

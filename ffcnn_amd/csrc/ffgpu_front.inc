@@ -31,10 +31,33 @@ struct FrontP {
 // (every instruction is a wave's), 75 registers less.  A width that is not a multiple of 3 lets the LAST lane slide left to end with the row (it overlaps its
 // neighbour by `sl` columns, computed twice, stored twice with the same values): no column outside the row is ever loaded, computed or stored; what changes is
 // which of the neighbour's registers the two lanes at the seam take as their left / right column (wave-uniform `sl`).
-template <int OC, bool U8, int NC = 4>
+// RS (U8 as well): the frames of ffgpu_exec_forward_bgr_frames_dev -- every frame its own u8 BGR source of any size, pitch and byte alignment,
+// letterboxed into the plane as net_input does (ffcnn.c:267-289).  The frame is wave-uniform (n = task / nbands), so its descriptor (the
+// parameter block's frames_tab[n]) comes in with scalar loads.  Per task a lane computes the source byte offsets of its 2 NC input columns
+// (x s1 / s2, 64-bit products as k_input_bgr4), per row the wave maps y to y s1 / s2; a pixel is two aligned dwords (the one holding its first
+// byte and the one holding its last: neither reaches past the frame's own bytes' dwords) and a byte align.  Columns x >= sw and rows
+// y >= sh are 0.0f, as the staged path writes them.  A frame of the net's own size whose rows are dword aligned takes the U8 form's
+// contiguous-dword loads instead (wave-uniform branch).  Everything behind the conversion is the U8 form's code.
+__device__ __forceinline__ unsigned front_muldiv(unsigned x, unsigned s1, unsigned s2)
+{
+    const unsigned long long t = (unsigned long long)x * s1;
+    return (t >> 32) ? (unsigned)(t / s2) : (unsigned)t / s2;
+}
+// (byte - mean) * norm with the reference's two roundings, as two plain VALU instructions: the resizing form's conversion is never paired into
+// packed fp32 instructions (tools/isa_lint.py: no new packed forms)
+__device__ __forceinline__ float front_cvt(unsigned byte, float m, float s)
+{
+    float t, v;
+    asm("v_sub_f32 %0, %1, %2" : "=v"(t) : "v"((float)byte), "v"(m));
+    asm("v_mul_f32 %0, %1, %2" : "=v"(v) : "v"(t), "v"(s));
+    return v;
+}
+
+template <int OC, bool U8, int NC = 4, bool RS = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k_front(FrontP p)
 {
     static_assert(NC == 4 || NC == 3, "columns per lane");
+    static_assert(!RS || (U8 && NC == 3), "the resizing form reads u8 frames, three columns per lane");
     constexpr int IC = 8, EC = 8, CP = EC / 2, RL1 = 12, RL2 = 12, OCP = (OC + 3) & ~3;
     // LDS tables: t0 [27 taps][4 oc pairs][2] + scale' pairs [4][2] + bias' pairs [4][2] of layer 0; then the block's
     // tables exactly as in k_irb_thin (t1 | td | t2 | sb2)
@@ -71,9 +94,34 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
     const unsigned lo = on ? (unsigned)min(lane * NC, p.W - NC) : 0, li = 2 * lo;      // idle lanes work on column 0; nothing of theirs is stored
     // (both inputs are named through the parameter block: global address space, not flat -- see ffgpu_kernels.hip)
     const gfp ip = U8 ? nullptr : to_global(p.in_ind ? *p.in_ind : p.in) + (long)n * p.in_ns;
-    const FFG unsigned char *bp = U8 ? (const FFG unsigned char *)p.prm->bgr + (long)n * p.prm->bgr_frame + ((3u * li) & ~3u) : nullptr;     // this lane's 6 NC bytes of a row, from the dword they start in
+    const FFG unsigned char *bp = U8 && !RS ? (const FFG unsigned char *)p.prm->bgr + (long)n * p.prm->bgr_frame + ((3u * li) & ~3u) : nullptr;     // this lane's 6 NC bytes of a row, from the dword they start in
     const unsigned bsh = (3u * li) & 3u;                             // ... and where in that dword (NC = 3: 18 bytes per lane start at 0 or 2)
-    const unsigned bpitch = U8 ? (unsigned)p.prm->bgr_pitch : 0u;
+    const unsigned bpitch = U8 && !RS ? (unsigned)p.prm->bgr_pitch : 0u;
+    // RS: the frame's source, the rows that hold pixels (ihv: min(IH, sh), none when sw == 0), the lane's column offsets / which of them hold pixels
+    const FFG unsigned char *fsrc = nullptr;
+    unsigned long fpitch = 0;
+    unsigned fs1 = 1, fs2 = 1, cmask = 0, coff[2 * NC];
+    int ihv = IH;
+    bool ffast = false;
+    if (RS) {
+        const FrameDesc *fd = p.prm->frames_tab + n;                // (the values are the wave's: said so, they live in scalar registers)
+        const uintptr_t a = reinterpret_cast<uintptr_t>(fd->bgr);
+        const unsigned alo = __builtin_amdgcn_readfirstlane((unsigned)a), ahi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+        fsrc = (const FFG unsigned char *)(((uintptr_t)ahi << 32) | alo);
+        fpitch = (unsigned)__builtin_amdgcn_readfirstlane(fd->pitch);
+        fs1 = (unsigned)__builtin_amdgcn_readfirstlane(fd->s1); fs2 = (unsigned)__builtin_amdgcn_readfirstlane(fd->s2);
+        const int sw = __builtin_amdgcn_readfirstlane(fd->sw), sh = __builtin_amdgcn_readfirstlane(fd->sh);
+        const int fw = __builtin_amdgcn_readfirstlane(fd->w), fh = __builtin_amdgcn_readfirstlane(fd->h);
+        ihv = sw > 0 ? min(IH, sh) : 0;
+        ffast = fw == IW && fh == IH && ((alo | (unsigned)fpitch) & 3u) == 0;      // (then s1 == s2, sw = IW, sh = IH)
+#pragma unroll
+        for (int i = 0; i < 2 * NC; i++) {
+            const unsigned x = li + i;
+            const bool in = (int)x < sw;
+            coff[i] = in ? 3u * front_muldiv(x, fs1, fs2) : 0u;         // (a column outside the frame reads pixel 0 of the row; its value is 0)
+            cmask |= in ? 1u << i : 0u;
+        }
+    }
     float cm[3] = { 0.f, 0.f, 0.f }, cn[3] = { 1.f, 1.f, 1.f };
     if (U8) {
 #pragma unroll
@@ -91,10 +139,42 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
     // (gfx9 global loads of 8 / 16 bytes need only dword alignment; the types must not promise the compiler more than that)
     typedef u4_t u4a4_t __attribute__((aligned(4)));
     typedef u2_t u2a4_t __attribute__((aligned(4)));
-    struct Row { v4f a[3], b[3]; u4_t q0; u2_t q1; };               // the lane's 2 NC input columns of three channels (a: 0-3, b: 4-..); U8: the raw dwords (NC = 3: q1.x only)
+    struct RowB { v4f a[3], b[3]; u4_t q0; u2_t q1; };              // the lane's 2 NC input columns of three channels (a: 0-3, b: 4-..); U8: the raw dwords (NC = 3: q1.x only)
+    struct RowG { v4f a[3], b[3]; u4_t q0; u2_t q1; unsigned g[4 * NC]; unsigned sh; };   // RS: two dwords per pixel (g[2 i], g[2 i + 1]) and the row's byte misalignment, or g[0..5] as q0 / q1
+    typedef std::conditional_t<RS, RowG, RowB> Row;
+
 #define ROWC(R, ci, i) ((i) < 4 ? (R).a[ci][(i) & 3] : (R).b[ci][((i) - 4) & 3])       /* column i (a compile-time index after unrolling) */
     // U8: the raw bytes of row `row` (nothing for a row outside the image) ...
-    auto load_irow_u8 = [&](int row, Row &R) {
+    auto load_irow_rs = [&](int row, Row &R) __attribute__((always_inline)) {
+        if constexpr (RS) {
+            if (row < 0 || row >= ihv) return;                        // wave-uniform; cvt_row makes the zeros
+            unsigned v[4 * NC], r3 = 0;                               // (both branches write every element: no store the compiler could merge into one through a selected address)
+            if (ffast) {
+                const FFG unsigned char *src = fsrc + (unsigned long)row * fpitch + ((3u * li) & ~3u);
+                const u4_t a = *(const FFG u4a4_t *)src;
+                v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+                if (NC == 4) { const u2_t b = *(const FFG u2a4_t *)(src + 16); v[4] = b.x; v[5] = b.y; }
+                else { v[4] = *(const FFG unsigned *)(src + 16); v[5] = 0u; }
+#pragma unroll
+                for (int k = 6; k < 4 * NC; k++) v[k] = 0u;
+            } else {
+                const FFG unsigned char *rb = fsrc + (unsigned long)front_muldiv((unsigned)row, fs1, fs2) * fpitch;     // uniform
+                r3 = (unsigned)reinterpret_cast<uintptr_t>(rb) & 3u;
+                const FFG unsigned *ra = (const FFG unsigned *)(rb - r3);
+#pragma unroll
+                for (int i = 0; i < 2 * NC; i++) {
+                    const unsigned o = r3 + coff[i];
+                    v[2 * i] = ra[o >> 2];                            // the dword holding the pixel's first byte ...
+                    v[2 * i + 1] = ra[(o + 2) >> 2];                  // ... and the one holding its last (the same one when o % 4 < 2)
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4 * NC; k++) R.g[k] = v[k];
+            R.sh = r3;
+        }
+    };
+    auto load_irow_u8 = [&](int row, Row &R) __attribute__((always_inline)) {
+        if constexpr (RS) { load_irow_rs(row, R); return; }
         if (row < 0 || row >= IH) return;                             // wave-uniform; cvt_row makes the zeros
         const FFG unsigned char *src = bp + (unsigned)row * bpitch;
         R.q0 = *(const FFG u4a4_t *)src;
@@ -102,13 +182,27 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
         else { R.q1.x = *(const FFG unsigned *)(src + 16); R.q1.y = 0u; }
     };
     // ... and their conversion into the three planes' eight columns, where the row is consumed
-    auto cvt_row = [&](int row, Row &R) {
-        if (row < 0 || row >= IH) {
+    auto cvt_row = [&](int row, Row &R) __attribute__((always_inline)) {
+        if (row < 0 || row >= (RS ? ihv : IH)) {
 #pragma unroll
             for (int ci = 0; ci < 3; ci++) { R.a[ci] = z4; R.b[ci] = z4; }
             return;
         }
+        if constexpr (RS) if (!ffast) {
+#pragma unroll
+            for (int i = 0; i < 2 * NC; i++) {
+                const unsigned px = __builtin_amdgcn_alignbyte(R.g[2 * i + 1], R.g[2 * i], (R.sh + coff[i]) & 3u);     // B G R in bytes 0 1 2
+                const bool in = (cmask >> i) & 1u;
+#pragma unroll
+                for (int ci = 0; ci < 3; ci++) {
+                    const float v = in ? front_cvt((px >> (8 * (2 - ci))) & 0xffu, cm[ci], cn[ci]) : 0.f;
+                    if (i < 4) R.a[ci][i & 3] = v; else R.b[ci][(i - 4) & 3] = v;
+                }
+            }
+            return;
+        }
         unsigned d[6] = { R.q0.x, R.q0.y, R.q0.z, R.q0.w, R.q1.x, R.q1.y };
+        if constexpr (RS) { d[0] = R.g[0]; d[1] = R.g[1]; d[2] = R.g[2]; d[3] = R.g[3]; d[4] = R.g[4]; d[5] = R.g[5]; }
         if (NC == 3) {                                                // the lane's 18 bytes start 0 or 2 bytes into the first dword
 #pragma unroll
             for (int i = 0; i < 5; i++) d[i] = __builtin_amdgcn_alignbyte(d[i + 1], d[i], bsh);
@@ -118,11 +212,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
 #pragma unroll
             for (int ci = 0; ci < 3; ci++) {
                 const int k = 3 * i + 2 - ci;                         // plane 0 = R (byte 2 of the pixel), 1 = G, 2 = B
-                const float v = ((float)((d[k >> 2] >> (8 * (k & 3))) & 0xffu) - cm[ci]) * cn[ci];
+                float v;
+                if constexpr (RS) v = front_cvt((d[k >> 2] >> (8 * (k & 3))) & 0xffu, cm[ci], cn[ci]);
+                else v = ((float)((d[k >> 2] >> (8 * (k & 3))) & 0xffu) - cm[ci]) * cn[ci];
                 if (i < 4) R.a[ci][i] = v; else R.b[ci][i - 4] = v;
             }
     };
-    auto load_irow = [&](int row, Row &R) {
+    auto load_irow = [&](int row, Row &R) __attribute__((always_inline)) {
         if (U8) { load_irow_u8(row, R); return; }
         if (row < 0 || row >= IH) {                                   // wave-uniform
 #pragma unroll

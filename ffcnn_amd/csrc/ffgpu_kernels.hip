@@ -17,6 +17,7 @@
 #include <mutex>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include "ffgpu_dev.hpp"
 
 #define WAVE 64
@@ -402,7 +403,8 @@ __global__ void __launch_bounds__(256) k_nms(const BBOX *cand, const int *cand_k
     int   *s_idx = reinterpret_cast<int *>(wb + (size_t)8 * cap_p2);
     unsigned char *s_alive = wb + (size_t)12 * cap_p2;
     const int n = blockIdx.x, tid = threadIdx.x;
-    const int s1 = prm->s1, s2 = prm->s2, bbox_max = prm->bbox_max;   // (in the parameter block: a graph replays with this forward's values)
+    const FrameDesc *const ftab = prm->frames_tab;              // mixed-size u8 frames: each frame's own box scale
+    const int s1 = ftab ? ftab[n].s1 : prm->s1, s2 = ftab ? ftab[n].s2 : prm->s2, bbox_max = prm->bbox_max;   // (in the parameter block: a graph replays with this forward's values)
     ffgpu_frame_dets *const ring = prm->ring;                   // (the ring travels in the parameter block too: attaching or
     const int ring_slots = prm->ring_slots, ring_stride = prm->ring_stride;   //  restarting it does not invalidate the graph)
     const int total = ncand[n];
@@ -515,6 +517,66 @@ __global__ void __launch_bounds__(256) k_nms(const BBOX *cand, const int *cand_k
 __global__ void k_set_params(ExecParams *prm, ExecParams v)
 {
     if (threadIdx.x == 0 && blockIdx.x == 0) *prm = v;
+}
+
+// the per-frame table of ffgpu_exec_forward_bgr_frames_dev: FRAMES_CHUNK descriptors travel by value as the kernel's argument (no pinned staging,
+// no host sync: the caller's array is free on return), one thread per descriptor: 2.5 KB of arguments, one launch for a batch of 64
+#define FRAMES_CHUNK 64
+struct FramesChunk { FrameDesc d[FRAMES_CHUNK]; int n; };
+__global__ void k_set_frames(FrameDesc *tab, FramesChunk c)
+{
+    if (threadIdx.x < (unsigned)c.n) tab[threadIdx.x] = c.d[threadIdx.x];
+}
+
+// batched net_input of MIXED frames (ffgpu_exec_forward_bgr_frames_dev, staged path): k_input_bgr4's arithmetic per frame with the
+// frame's own descriptor (blockIdx.y = frame, read once per block), any byte alignment of the source and any pitch.  A thread owns 4
+// consecutive output pixels of one row; W need not be a multiple of 4.  Frames of the net's size whose rows are dword aligned load
+// 12 contiguous bytes as three dwords; every other frame reads its pixels byte by byte.
+__global__ void __launch_bounds__(256) k_input_frames(const FrameDesc *tab, float *out, int W, int H, InputP p)
+{
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const unsigned wq = ((unsigned)W + 3) >> 2, t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= wq * (unsigned)H) return;
+    const int y = (int)(t / wq), x0 = (int)(t - (unsigned)y * wq) * 4, n = blockIdx.y;
+    const FrameDesc fd = tab[n];
+    f4 r = { 0.f, 0.f, 0.f, 0.f }, g = r, b = r;
+    if (y < fd.sh && x0 < fd.sw) {
+        const unsigned char *row = fd.bgr + (long)((long)y * fd.s1 / fd.s2) * fd.pitch;
+        unsigned char px[4][3];
+        if (fd.s1 == fd.s2 && x0 + 3 < fd.sw && ((reinterpret_cast<uintptr_t>(fd.bgr) | (unsigned)fd.pitch) & 3) == 0) {   // not resized, dword aligned rows (3 x0 % 4 == 0)
+            const unsigned *q = reinterpret_cast<const unsigned *>(row + 3 * x0);
+            const unsigned d0 = q[0], d1 = q[1], d2 = q[2];
+            const unsigned char by[12] = { (unsigned char)d0, (unsigned char)(d0 >> 8), (unsigned char)(d0 >> 16), (unsigned char)(d0 >> 24),
+                                           (unsigned char)d1, (unsigned char)(d1 >> 8), (unsigned char)(d1 >> 16), (unsigned char)(d1 >> 24),
+                                           (unsigned char)d2, (unsigned char)(d2 >> 8), (unsigned char)(d2 >> 16), (unsigned char)(d2 >> 24) };
+#pragma unroll
+            for (int i = 0; i < 4; i++) { px[i][0] = by[3 * i]; px[i][1] = by[3 * i + 1]; px[i][2] = by[3 * i + 2]; }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int x = min(x0 + i, fd.sw - 1);
+                const unsigned char *s = row + (long)((long)x * fd.s1 / fd.s2) * 3;
+                px[i][0] = s[0]; px[i][1] = s[1]; px[i][2] = s[2];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const bool in = x0 + i < fd.sw;
+            r[i] = in ? ((float)px[i][2] - p.mean[0]) * p.norm[0] : 0.f;
+            g[i] = in ? ((float)px[i][1] - p.mean[1]) * p.norm[1] : 0.f;
+            b[i] = in ? ((float)px[i][0] - p.mean[2]) * p.norm[2] : 0.f;
+        }
+    }
+    float *o = out + (long)n * 3 * H * W + (long)y * W + x0;
+    if ((W & 3) == 0) {
+        *reinterpret_cast<f4 *>(o) = r;
+        *reinterpret_cast<f4 *>(o + (long)H * W) = g;
+        *reinterpret_cast<f4 *>(o + 2L * H * W) = b;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            if (x0 + i < W) { o[i] = r[i]; o[i + (long)H * W] = g[i]; o[i + 2L * H * W] = b[i]; }
+    }
 }
 
 // start of a forward: no candidates yet; one more forward for the record ring
@@ -654,6 +716,30 @@ int ffgpu_launch_input_bgr(const unsigned char *bgr, float *out, int N, int w, i
     }
     hipLaunchKernelGGL(k_input_bgr, dim3(grid_for((long)N * H * W, 256)), dim3(256), 0, s, bgr, out, N, w, h, W, H, sw, sh, s1, s2, p);
     LAUNCH_OK("input_bgr");
+    return 0;
+}
+
+int ffgpu_launch_set_frames(FrameDesc *d_tab, const FrameDesc *h_desc, int n, hipStream_t s)
+{
+    for (int i0 = 0; i0 < n; i0 += FRAMES_CHUNK) {
+        FramesChunk c;
+        memset(&c, 0, sizeof c);
+        c.n = std::min(FRAMES_CHUNK, n - i0);
+        memcpy(c.d, h_desc + i0, sizeof(FrameDesc) * c.n);
+        hipLaunchKernelGGL(k_set_frames, dim3(1), dim3(FRAMES_CHUNK), 0, s, d_tab + i0, c);
+        LAUNCH_OK("set_frames");
+    }
+    return 0;
+}
+
+int ffgpu_launch_input_frames(const FrameDesc *d_tab, float *out, int N, int W, int H, const float mean[3], const float norm[3], hipStream_t s)
+{
+    InputP p;
+    for (int i = 0; i < 3; i++) { p.mean[i] = mean[i]; p.norm[i] = norm[i]; }
+    const long q = (long)((W + 3) / 4) * H;
+    if (N > 65535 || q >= (1L << 31)) { ffgpu_set_error("input_frames: %d frames of %d x %d is too large", N, W, H); return -1; }
+    hipLaunchKernelGGL(k_input_frames, dim3((unsigned)((q + 255) / 256), (unsigned)N), dim3(256), 0, s, d_tab, out, W, H, p);
+    LAUNCH_OK("input_frames");
     return 0;
 }
 

@@ -115,6 +115,22 @@ int ffgpu_exec_forward_host(ffgpu_exec *ex, const float *h_frames);
 int ffgpu_exec_forward_bgr_dev(ffgpu_exec *ex, const unsigned char *d_bgr, int w, int h,
                                const float mean[3], const float norm[3], void *stream);
 
+/* One u8 BGR frame of a mixed batch: its own device allocation, size and row pitch. */
+typedef struct {
+    const unsigned char *bgr;   /* device address of row 0 of this frame, B G R bytes per pixel, any byte alignment */
+    int w, h;                   /* pixels, >= 1 */
+    int pitch;                  /* bytes from one row to the next, >= 3 w; 0 = ALIGN(3 w, 4) as net_input (ffcnn.c:262) */
+    int reserved;               /* 0 */
+} ffgpu_bgr_frame;              /* 24 bytes */
+
+/* frames: HOST array of `nframes` (== ffgpu_exec_batch(ex)) descriptors; the array is free again on return, the pixels must stay
+ * valid until the forward completes.  Frame n = net_input(frames[n]) (ffcnn.c:259-289) with its own s1/s2, then the forward; records
+ * of frame n are rescaled by frame n's s1/s2.  Enqueued on `stream` without synchronising, like ffgpu_exec_forward_bgr_dev.
+ * On plans that start with the fused first kernel the letterbox resize runs inside it (no fp32 batch is written); the
+ * executor's own scale (ffgpu_exec_set_scale) is left as it was. */
+int ffgpu_exec_forward_bgr_frames_dev(ffgpu_exec *ex, const ffgpu_bgr_frame *frames, int nframes,
+                                      const float mean[3], const float norm[3], void *stream);
+
 /* Device address of the batch's ffgpu_frame_dets[batch] (valid after the
  * forward enqueued on the same stream completes). */
 int ffgpu_exec_dets_dev(ffgpu_exec *ex, void **dev_ptr, size_t *bytes);
