@@ -52,9 +52,16 @@ class BgrFrame(C.Structure):         # ffgpu_bgr_frame (24 bytes): one u8 BGR fr
     _fields_ = [("bgr", C.c_void_p), ("w", C.c_int), ("h", C.c_int), ("pitch", C.c_int), ("reserved", C.c_int)]
 
 
+class Nv12Frame(C.Structure):        # ffgpu_nv12_frame (40 bytes): one NV12 frame (Y plane + interleaved U V plane) of a mixed batch
+    _fields_ = [("y", C.c_void_p), ("uv", C.c_void_p), ("w", C.c_int), ("h", C.c_int), ("pitch_y", C.c_int), ("pitch_uv", C.c_int),
+                ("matrix", C.c_int), ("reserved", C.c_int)]
+
+
+YUV_BT601_LIMITED, YUV_BT601_FULL, YUV_BT709_LIMITED, YUV_BT709_FULL = 0, 1, 2, 3      # FFGPU_YUV_* (ffgpu_nv12_frame.matrix)
+
 assert C.sizeof(LAYER) == 120 and C.sizeof(NET) == 104 and C.sizeof(BBOX) == 24
 assert C.sizeof(FrameDets) == 16 + 24 * FFGPU.MAX_DET
-assert C.sizeof(BgrFrame) == 24
+assert C.sizeof(BgrFrame) == 24 and C.sizeof(Nv12Frame) == 40
 
 BOX_DTYPE = np.dtype([("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
 DETS_DTYPE = np.dtype([("count", "<i4"), ("ncand", "<i4"), ("overflow", "<i4"), ("nfull", "<i4"),
@@ -66,7 +73,7 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_net_weights_dev", "ffgpu_net_weights_commit",
            "ffgpu_exec_create", "ffgpu_exec_destroy", "ffgpu_exec_batch", "ffgpu_exec_arena_bytes",
            "ffgpu_exec_kernel_count", "ffgpu_exec_work_model", "ffgpu_exec_set_scale", "ffgpu_exec_forward_dev", "ffgpu_exec_forward_host",
-           "ffgpu_exec_forward_bgr_dev", "ffgpu_exec_forward_bgr_frames_dev", "ffgpu_exec_dets_dev", "ffgpu_exec_dets_host", "ffgpu_exec_set_ring", "ffgpu_exec_set_ring_strided", "ffgpu_exec_read_dets", "ffgpu_exec_read_layer", "ffgpu_exec_hash_layers",
+           "ffgpu_exec_forward_bgr_dev", "ffgpu_exec_forward_bgr_frames_dev", "ffgpu_exec_forward_nv12_frames_dev", "ffgpu_exec_dets_dev", "ffgpu_exec_dets_host", "ffgpu_exec_set_ring", "ffgpu_exec_set_ring_strided", "ffgpu_exec_read_dets", "ffgpu_exec_read_layer", "ffgpu_exec_hash_layers",
            "ffgpu_exec_read_boxes", "ffgpu_exec_cand_capacity", "ffgpu_exec_graph_captures",
            "ffgpu_exec_profile", "ffgpu_exec_profile_steps", "ffgpu_exec_step_model", "ffgpu_groupconv_dev", "ffgpu_groupconv_kernel_name", "ffgpu_groupconv_time_dev", "ffgpu_irb_dev", "ffgpu_dwpw_dev", "ffgpu_packed_records_bytes", "ffgpu_pack_records", "ffgpu_unpack_records",
            "ffgpu_shard_range", "ffgpu_node_create", "ffgpu_node_destroy", "ffgpu_node_ndev", "ffgpu_node_shard", "ffgpu_node_set_scale",
@@ -132,6 +139,7 @@ def lib():
     L.ffgpu_exec_forward_host.argtypes = [vp, f32p]
     L.ffgpu_exec_forward_bgr_dev.argtypes = [vp, vp, i, i, f32p, f32p, vp]
     L.ffgpu_exec_forward_bgr_frames_dev.argtypes = [vp, C.POINTER(BgrFrame), i, f32p, f32p, vp]
+    L.ffgpu_exec_forward_nv12_frames_dev.argtypes = [vp, C.POINTER(Nv12Frame), i, f32p, f32p, vp]
     L.ffgpu_exec_dets_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
     L.ffgpu_exec_dets_host.restype = vp; L.ffgpu_exec_dets_host.argtypes = [vp]
     L.ffgpu_exec_set_ring.argtypes = [vp, vp, C.c_int]
@@ -404,6 +412,16 @@ class Executor:
         m, s = (C.c_float * 3)(*mean), (C.c_float * 3)(*norm)
         _check(lib().ffgpu_exec_forward_bgr_frames_dev(self.h, arr, len(frames), m, s, stream), "ffgpu_exec_forward_bgr_frames_dev")
 
+    def forward_nv12_frames_dev(self, frames, mean=(0.0, 0.0, 0.0), norm=(1 / 255.0,) * 3, stream=None, matrix=0):
+        """one forward of mixed-size NV12 frames (ffgpu_exec_forward_nv12_frames_dev): frames is a sequence of (y_ptr, uv_ptr or 0, w, h[, pitch_y,
+        pitch_uv, matrix]) tuples or (Y, UV) pairs of torch.uint8 device tensors (Y: h x pitch_y, UV: ceil(h / 2) x pitch_uv); `matrix` (YUV_*) is
+        the matrix of every frame that names none"""
+        arr = (Nv12Frame * max(1, len(frames)))()
+        for k, f in enumerate(frames):
+            arr[k] = Nv12Frame(*nv12_frame_desc(f, matrix))
+        m, s = (C.c_float * 3)(*mean), (C.c_float * 3)(*norm)
+        _check(lib().ffgpu_exec_forward_nv12_frames_dev(self.h, arr, len(frames), m, s, stream), "ffgpu_exec_forward_nv12_frames_dev")
+
     def dets_dev(self):
         ptr, nbytes = C.c_void_p(), C.c_size_t()
         _check(lib().ffgpu_exec_dets_dev(self.h, C.byref(ptr), C.byref(nbytes)), "ffgpu_exec_dets_dev")
@@ -506,6 +524,32 @@ def bgr_frame_desc(f):
             raise ValueError("an (h, pitch) frame needs contiguous rows")
         return (f.data_ptr(), pitch // 3, h, f.stride(0) if h > 1 else pitch, 0)
     raise ValueError("a frame is (h, w, 3) or (h, pitch)")
+
+
+def nv12_frame_desc(f, matrix=0):
+    """(y, uv, w, h, pitch_y, pitch_uv, matrix, 0) of one frame for ffgpu_exec_forward_nv12_frames_dev: a (y_ptr, uv_ptr or 0, w, h[, pitch_y,
+    pitch_uv, matrix]) tuple (uv 0 = y + pitch_y h; pitches 0 = w and 2 ceil(w / 2)), or a (Y, UV) pair of torch.uint8 device tensors: Y of
+    shape (h, pitch_y) (w = pitch_y columns), UV of shape (ceil(h / 2), pitch_uv); rows may be strided"""
+    if not isinstance(f, (tuple, list)) or not (len(f) == 2 or 4 <= len(f) <= 7):
+        raise ValueError("a frame is (y_ptr, uv_ptr or 0, w, h[, pitch_y, pitch_uv, matrix]) or a (Y, UV) pair of torch.uint8 device tensors")
+    if len(f) == 2:
+        import torch
+        Y, UV = f
+        if not (isinstance(Y, torch.Tensor) and isinstance(UV, torch.Tensor)):
+            raise ValueError("a frame is (y_ptr, uv_ptr or 0, w, h[, pitch_y, pitch_uv, matrix]) or a (Y, UV) pair of torch.uint8 device tensors")
+        for t in (Y, UV):
+            if t.dtype != torch.uint8:
+                raise TypeError("frames must be torch.uint8 tensors, not %s" % t.dtype)
+            if not t.is_cuda:
+                raise ValueError("frames must be device tensors (the kernels read them on the GPU), not %s ones" % t.device)
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError("a plane is (rows, pitch) with contiguous rows")
+        h, w = Y.shape
+        if UV.shape[0] != (h + 1) // 2 or UV.shape[1] < 2 * ((w + 1) // 2):
+            raise ValueError("the UV plane of a %d x %d frame has %d rows of at least %d bytes, not %s" % (w, h, (h + 1) // 2, 2 * ((w + 1) // 2), tuple(UV.shape)))
+        return (Y.data_ptr(), UV.data_ptr(), w, h, Y.stride(0) if h > 1 else w, UV.stride(0) if UV.shape[0] > 1 else UV.shape[1] & ~1, matrix, 0)
+    y, uv, w, h = f[0], f[1], f[2], f[3]
+    return (y, uv or 0, w, h, f[4] if len(f) > 4 else 0, f[5] if len(f) > 5 else 0, f[6] if len(f) > 6 else matrix, 0)
 
 
 def shard_range(total, rank, world):

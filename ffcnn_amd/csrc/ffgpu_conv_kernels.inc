@@ -1437,7 +1437,14 @@ int ffgpu_front_nc(const IrbDesc &d)
 
 // resize: u8 frames of any size described one by one by the parameter block's frames_tab (ffgpu_exec_forward_bgr_frames_dev).  Three columns per
 // lane only: the four-column form of the gather does not fit a wave's registers, so the executor stages those frames (ffgpu_front_nc == 4) instead.
-int ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, hipStream_t s, bool u8, bool resize)
+// Which route NV12 frames take on plans that have the fused form: FFGPU_NV12_FRONT=1 the NV12 form of k_front, =0 staging (k_input_nv12_frames);
+// unset: FFGPU_NV12_FRONT_DEFAULT, the outcome of tools/nv12_frames_bench.py (DESIGN 5.15: fused only if it beats staging at four chains by more
+// than the spread of the repeats).  Read at every call: it selects between two graphs, it changes neither.
+#define FFGPU_NV12_FRONT_DEFAULT 0
+bool ffgpu_front_nv12_fused() { return env_int("FFGPU_NV12_FRONT", FFGPU_NV12_FRONT_DEFAULT) != 0; }
+
+// resize 2: the same for the NV12 frames of ffgpu_exec_forward_nv12_frames_dev
+int ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, hipStream_t s, bool u8, int resize)
 {
     if (!ffgpu_front_ok(c, d)) { ffgpu_set_error("front: unsupported layer pair"); return -1; }
     if ((u8 || resize) && !c.in_ind) { ffgpu_set_error("front: the u8 form needs the executor's parameter block"); return -1; }
@@ -1455,7 +1462,9 @@ int ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, hipStream_t s, bool 
     p.ntasks = d.N * p.nbands;
     p.act0 = slope(c.act); p.act1 = slope(d.act1); p.actd = slope(d.actd); p.act2 = slope(d.act2);
     const dim3 grid((unsigned)((p.ntasks + 3) / 4));
-    if (resize) {
+    if (resize == 2) {
+        hipLaunchKernelGGL((k_front<4, true, 3, true, true>), grid, dim3(256), 0, s, p);
+    } else if (resize) {
         hipLaunchKernelGGL((k_front<4, true, 3, true>), grid, dim3(256), 0, s, p);
     } else if (nc == 3) {
         if (u8) hipLaunchKernelGGL((k_front<4, true, 3>), grid, dim3(256), 0, s, p);

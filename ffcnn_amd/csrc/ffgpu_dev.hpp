@@ -63,7 +63,8 @@ void   ffgpu_irb_plan(IrbDesc &d);                     // freezes what the packe
 int    ffgpu_irb_pack(const IrbDesc &d, float *pk, hipStream_t s);
 int    ffgpu_launch_irb(const IrbDesc &d, hipStream_t s);
 bool   ffgpu_front_ok(const ConvDesc &c, const IrbDesc &d);      // first layer (3x3 s2, 3 -> 8) + thin block as one streaming kernel
-int    ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, hipStream_t s, bool u8 = false, bool resize = false);   // resize: u8 frames of the parameter block's frames_tab
+int    ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, hipStream_t s, bool u8 = false, int resize = 0);   // resize: u8 frames of the parameter block's frames_tab (1: BGR, 2: NV12)
+bool   ffgpu_front_nv12_fused();                                 // NV12 frames go into the NV12 form of k_front where the plan has it (FFGPU_NV12_FRONT, else the measured default)
 int    ffgpu_front_nc(const IrbDesc &d);                         // output columns per lane k_front uses for this block (3 or 4; the resizing form: 3 only)
 
 // depthwise K x K (stride 1, same padding) + pointwise 1 x 1 as one launch (ffgpu_dwpw.inc); dw.out == pw.in is never written
@@ -76,16 +77,24 @@ size_t ffgpu_pw_pack_floats(const ConvDesc &d);
 void   ffgpu_conv_plan(ConvDesc &d);                   // freezes kernel / nsplit / x3_mt for this layer NOW (the tuning environment is read once, here)
 int    ffgpu_pw_pack(const ConvDesc &d, float *pk, hipStream_t s);
 
-// One frame of ffgpu_exec_forward_bgr_frames_dev as the kernels read it: the caller's descriptor plus net_input's letterbox
-// arithmetic (ffcnn.c:267-273), computed once on the host.  The executor keeps a device table of `batch` of them.
+// One frame of ffgpu_exec_forward_bgr_frames_dev / ffgpu_exec_forward_nv12_frames_dev as the kernels read it: the caller's descriptor plus
+// net_input's letterbox arithmetic (ffcnn.c:267-273), computed once on the host.  The executor keeps a device table of `batch` of them.
+// fmt tells the two kinds of table apart (a BGR table never compares equal to an NV12 one: the executor's "table already sent" shortcut).
 struct FrameDesc {
-    const unsigned char *bgr;     // row 0 of the frame (any byte alignment)
-    int w, h, pitch;              // pitch: bytes from one row to the next (>= 3 w)
+    const unsigned char *bgr;     // row 0 of the frame (any byte alignment); NV12: row 0 of the Y plane
+    int w, h, pitch;              // pitch: bytes from one row to the next (>= 3 w; NV12: of the Y plane, >= w)
     int sw, sh, s1, s2;           // the frame fills the top-left sw x sh of the net's plane; source pixel of (x, y) = (x s1 / s2, y s1 / s2)
+    int fmt;                      // 0: u8 BGR; 1 + FFGPU_YUV_*: NV12 converted with that matrix
+    const unsigned char *uv;      // NV12: row 0 of the interleaved U V plane (2-byte aligned, never NULL here); BGR: NULL
+    int pitch_uv;                 // NV12: bytes from one U V row to the next (even)
     int pad_;
 };
+static_assert(sizeof(FrameDesc) == 56, "FrameDesc: 64 of them travel by value as k_set_frames' argument");
+// NV12 -> BGR in 32-bit integers (include/ffcnn_hip.h): { yoff, cy, crv, cgu, cgv, cbu } per FFGPU_YUV_* matrix
+#define FFGPU_YUV_MATRICES { { 16, 298, 409, 100, 208, 516 }, { 0, 256, 359, 88, 183, 454 }, { 16, 298, 459, 55, 136, 541 }, { 0, 256, 403, 48, 120, 475 } }
 int  ffgpu_launch_set_frames(FrameDesc *d_tab, const FrameDesc *h_desc, int n, hipStream_t s);
 int  ffgpu_launch_input_frames(const FrameDesc *d_tab, float *out, int N, int W, int H, const float mean[3], const float norm[3], hipStream_t s);
+int  ffgpu_launch_input_nv12_frames(const FrameDesc *d_tab, float *out, int N, int W, int H, const float mean[3], const float norm[3], hipStream_t s);
 
 // Per-executor parameter block in device memory: what changes from one forward to the next without changing the
 // launch list.  A one-thread kernel (ffgpu_launch_set_params) rewrites it in stream order in front of the graph launch,
@@ -101,7 +110,7 @@ struct ExecParams {
     long  bgr_frame;          // bytes from one frame to the next
     int   bgr_pitch;          // bytes per image row (ALIGN(3 w, 4), ffcnn.c:262)
     float mean[3], norm[3];   // net_input's per-channel mean / norm (plane order R, G, B)
-    // ffgpu_exec_forward_bgr_frames_dev: this forward's per-frame table (N entries; k_nms takes each frame's s1 / s2 from it, the
+    // ffgpu_exec_forward_bgr_frames_dev / _nv12_frames_dev: this forward's per-frame table (N entries; k_nms takes each frame's s1 / s2 from it, the
     // resizing k_front its source); NULL for every other entry point
     const FrameDesc *frames_tab;
 };

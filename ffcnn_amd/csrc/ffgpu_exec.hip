@@ -214,9 +214,9 @@ struct ffgpu_exec {
     FrameDesc *d_ftab = nullptr;       // owned by the executor that allocated it (a split executor's halves point into their parent's)
     const FrameDesc *ftab = nullptr;   // the table the forward being enqueued reads (NULL: every other entry point)
     std::vector<FrameDesc> ftab_sent; hipStream_t ftab_stream = nullptr;      // what d_ftab holds (or will, on ftab_stream)
-    bool rs_mode = false;              // the forward being enqueued / captured runs the resizing u8 form of the first kernel
+    int  rs_mode = 0;                  // the forward being enqueued / captured runs a resizing u8 form of the first kernel (1: BGR frames, 2: NV12 frames)
     bool rs_last = false;              // ... and the last forward pushed did (read_layer(-1): no fp32 input tensor exists)
-    hipGraphExec_t graph_rs = nullptr;
+    hipGraphExec_t graph_rs = nullptr, graph_nv = nullptr;      // (one per form, each captured on first use)
     float *h_stage = nullptr;          // ffgpu_exec_forward_host from caller memory: page-locked staging of one batch (on first use)
     ffgpu_frame_dets *ring = nullptr; int ring_slots = 0; int *d_ringctr = nullptr;   // ffgpu_exec_set_ring
     int ring_stride = 0;               // records per ring slot (the parent's batch for the halves of a split executor)
@@ -805,7 +805,7 @@ static int push_params(ffgpu_exec *ex, const float *d_frames, hipStream_t s)
     if (ex->u8_mode) { v.bgr = ex->bgr; v.bgr_frame = ex->bgr_frame; v.bgr_pitch = ex->bgr_pitch; }
     if (ex->u8_mode || ex->rs_mode)
         for (int k = 0; k < 3; k++) { v.mean[k] = ex->bgr_mean[k]; v.norm[k] = ex->bgr_norm[k]; }
-    ex->rs_last = ex->rs_mode;
+    ex->rs_last = ex->rs_mode != 0;
     v.frames_tab = ex->ftab;
     v.bbox_max = ex->bbox_max;
     v.ring = ex->ring; v.ring_slots = ex->ring_slots; v.ring_stride = ex->ring_stride ? ex->ring_stride : ex->N;
@@ -847,6 +847,7 @@ static void drop_graphs(ffgpu_exec *ex)                       // caller has sync
     if (ex->graph1) { (void)hipGraphExecDestroy(ex->graph1); ex->graph1 = nullptr; }
     if (ex->graph_u8) { (void)hipGraphExecDestroy(ex->graph_u8); ex->graph_u8 = nullptr; }
     if (ex->graph_rs) { (void)hipGraphExecDestroy(ex->graph_rs); ex->graph_rs = nullptr; }
+    if (ex->graph_nv) { (void)hipGraphExecDestroy(ex->graph_nv); ex->graph_nv = nullptr; }
     for (auto &g : ex->graphs) (void)hipGraphExecDestroy(g.g);
     ex->graphs.clear();
 }
@@ -868,7 +869,7 @@ static int forward_on(ffgpu_exec *ex, const float *d_frames, hipStream_t s)
     if (push_params(ex, d_frames, s)) return -1;
     if (ex->flags & FFGPU_NO_GRAPH) return ex->child[0] ? issue_split(ex, d_frames, s) : issue_all(ex, d_frames, s);
     if (graph_pointer_free(ex)) {                            // the usual case: one graph, whatever the input buffer / scale
-        hipGraphExec_t &g1 = ex->rs_mode ? ex->graph_rs : ex->u8_mode ? ex->graph_u8 : ex->graph1;      // (+ one more per u8 form of the first kernel)
+        hipGraphExec_t &g1 = ex->rs_mode == 2 ? ex->graph_nv : ex->rs_mode ? ex->graph_rs : ex->u8_mode ? ex->graph_u8 : ex->graph1;      // (+ one more per u8 form of the first kernel)
         if (!g1 && capture(ex, d_frames, &g1)) return -1;
         FFGPU_CHECK(hipGraphLaunch(g1, s));
         return 0;
@@ -1197,6 +1198,33 @@ extern "C" int ffgpu_exec_forward_bgr_dev(ffgpu_exec *ex, const unsigned char *d
     return forward_on(ex, ex->d_input, s);
 }
 
+// the common tail of the two frame-table entry points: the table written in stream order in front of the forward -- skipped when it holds
+// these values already; a BGR table and an NV12 one never compare equal (FrameDesc::fmt, uv) -- then the fused or the staged route
+static int forward_frames(ffgpu_exec *ex, const std::vector<FrameDesc> &tab, bool nv12, const float mean[3], const float norm[3], hipStream_t s)
+{
+    const int nframes = (int)tab.size();
+    if (!ex->d_ftab) FFGPU_CHECK(hipMalloc(&ex->d_ftab, sizeof(FrameDesc) * (size_t)ex->N));
+    if (!(ex->ftab_stream == s && ex->ftab_sent.size() == tab.size() && memcmp(ex->ftab_sent.data(), tab.data(), sizeof(FrameDesc) * tab.size()) == 0)) {
+        ex->ftab_sent.clear();
+        if (ffgpu_launch_set_frames(ex->d_ftab, tab.data(), nframes, s)) return -1;
+        ex->ftab_sent = tab; ex->ftab_stream = s;
+    }
+    for (int k = 0; k < 3; k++) { ex->bgr_mean[k] = mean[k]; ex->bgr_norm[k] = norm[k]; }
+    ex->ftab = ex->d_ftab;
+    int rc;
+    if (!getenv("FFGPU_NO_U8_FRONT") && front_resizes(ex) && (!nv12 || ffgpu_front_nv12_fused())) {      // the resizing first kernel reads the frames itself: no fp32 batch
+        ex->rs_mode = nv12 ? 2 : 1;
+        rc = forward_on(ex, nullptr, s);
+        ex->rs_mode = 0;
+    } else {                                                         // staged: the fp32 batch, then the ordinary graph
+        rc = -1;
+        if (!ensure_input(ex) && !(nv12 ? ffgpu_launch_input_nv12_frames : ffgpu_launch_input_frames)(ex->d_ftab, ex->d_input, ex->N, ex->in_w, ex->in_h, mean, norm, s))
+            rc = forward_on(ex, ex->d_input, s);
+    }
+    ex->ftab = nullptr;
+    return rc;
+}
+
 // Mixed-size u8 frames: per frame net_input's letterbox arithmetic (ffcnn.c:262-273) on the host, the table written in stream order in
 // front of the forward (skipped when it holds these values already), then either the resizing k_front reads the bytes itself (plans that
 // start with k_front) or k_input_frames writes the fp32 batch the ordinary graph consumes.  The executor's own scale stays as it was:
@@ -1229,26 +1257,43 @@ extern "C" int ffgpu_exec_forward_bgr_frames_dev(ffgpu_exec *ex, const ffgpu_bgr
         if ((long)f.w * H > (long)f.h * W) { d.sw = W; d.sh = (int)((long)d.sw * f.h / f.w); d.s1 = f.w; d.s2 = d.sw; }      // ffcnn.c:267-273
         else                               { d.sh = H; d.sw = (int)((long)d.sh * f.w / f.h); d.s1 = f.h; d.s2 = d.sh; }
     }
-    hipStream_t s = stream ? (hipStream_t)stream : ex->own_stream;
-    if (!ex->d_ftab) FFGPU_CHECK(hipMalloc(&ex->d_ftab, sizeof(FrameDesc) * (size_t)ex->N));
-    if (!(ex->ftab_stream == s && ex->ftab_sent.size() == tab.size() && memcmp(ex->ftab_sent.data(), tab.data(), sizeof(FrameDesc) * tab.size()) == 0)) {
-        ex->ftab_sent.clear();
-        if (ffgpu_launch_set_frames(ex->d_ftab, tab.data(), nframes, s)) return -1;
-        ex->ftab_sent = tab; ex->ftab_stream = s;
+    return forward_frames(ex, tab, false, mean, norm, stream ? (hipStream_t)stream : ex->own_stream);
+}
+
+// NV12 frames: the same table with the second plane, its pitch and the matrix (FrameDesc::fmt != 0); the pixel is converted where it is sampled
+extern "C" int ffgpu_exec_forward_nv12_frames_dev(ffgpu_exec *ex, const ffgpu_nv12_frame *frames, int nframes,
+                                                  const float mean[3], const float norm[3], void *stream)
+{
+    int ndev = 0;
+    if (!ex && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)) {
+        (void)hipGetLastError();
+        ffgpu_set_error("forward_nv12_frames_dev: no HIP device visible: libffcnn_hip has no CPU fallback");
+        return -1;
     }
-    for (int k = 0; k < 3; k++) { ex->bgr_mean[k] = mean[k]; ex->bgr_norm[k] = norm[k]; }
-    ex->ftab = ex->d_ftab;
-    int rc;
-    if (!getenv("FFGPU_NO_U8_FRONT") && front_resizes(ex)) {         // the resizing first kernel reads the frames itself: no fp32 batch
-        ex->rs_mode = true;
-        rc = forward_on(ex, nullptr, s);
-        ex->rs_mode = false;
-    } else {                                                         // staged: the fp32 batch, then the ordinary graph
-        rc = -1;
-        if (!ensure_input(ex) && !ffgpu_launch_input_frames(ex->d_ftab, ex->d_input, ex->N, W, H, mean, norm, s)) rc = forward_on(ex, ex->d_input, s);
+    if (!alive(ex, "forward_nv12_frames_dev")) return -1;
+    if (!frames || !mean || !norm) { ffgpu_set_error("forward_nv12_frames_dev: NULL argument"); return -1; }
+    if (nframes != ex->N) { ffgpu_set_error("forward_nv12_frames_dev: %d frames for an executor of batch %d", nframes, ex->N); return -1; }
+    if (ex->in_c != 3) { ffgpu_set_error("forward_nv12_frames_dev: the net's input has %d channels, not 3", ex->in_c); return -1; }
+    const int W = ex->in_w, H = ex->in_h;
+    std::vector<FrameDesc> tab((size_t)nframes);
+    for (int n = 0; n < nframes; n++) {
+        const ffgpu_nv12_frame &f = frames[n];
+        if (!f.y) { ffgpu_set_error("forward_nv12_frames_dev: frame %d: NULL y", n); return -1; }
+        if (f.w <= 0 || f.h <= 0 || f.w > 0x3fffffff || f.h > 0x3fffffff) { ffgpu_set_error("forward_nv12_frames_dev: frame %d: bad size %d x %d", n, f.w, f.h); return -1; }
+        if (f.reserved != 0) { ffgpu_set_error("forward_nv12_frames_dev: frame %d: reserved must be 0", n); return -1; }
+        if (f.matrix < 0 || f.matrix > 3) { ffgpu_set_error("forward_nv12_frames_dev: frame %d: matrix %d is none of FFGPU_YUV_* (0..3)", n, f.matrix); return -1; }
+        const int pitch_y = f.pitch_y ? f.pitch_y : f.w, min_uv = 2 * ((f.w + 1) / 2), pitch_uv = f.pitch_uv ? f.pitch_uv : min_uv;
+        if (pitch_y < f.w) { ffgpu_set_error("forward_nv12_frames_dev: frame %d: pitch_y %d is below w = %d", n, f.pitch_y, f.w); return -1; }
+        if (pitch_uv < min_uv || (pitch_uv & 1)) { ffgpu_set_error("forward_nv12_frames_dev: frame %d: pitch_uv %d is odd or below 2 ((w + 1) / 2) = %d", n, f.pitch_uv, min_uv); return -1; }
+        const unsigned char *uv = f.uv ? f.uv : f.y + (size_t)pitch_y * f.h;
+        if (reinterpret_cast<uintptr_t>(uv) & 1) { ffgpu_set_error("forward_nv12_frames_dev: frame %d: the uv plane's address %p is odd (U V pairs are read as aligned 16-bit values)", n, (const void *)uv); return -1; }
+        FrameDesc &d = tab[n];
+        memset(&d, 0, sizeof d);
+        d.bgr = f.y; d.uv = uv; d.w = f.w; d.h = f.h; d.pitch = pitch_y; d.pitch_uv = pitch_uv; d.fmt = 1 + f.matrix;
+        if ((long)f.w * H > (long)f.h * W) { d.sw = W; d.sh = (int)((long)d.sw * f.h / f.w); d.s1 = f.w; d.s2 = d.sw; }      // ffcnn.c:267-273
+        else                               { d.sh = H; d.sw = (int)((long)d.sh * f.w / f.h); d.s1 = f.h; d.s2 = d.sh; }
     }
-    ex->ftab = nullptr;
-    return rc;
+    return forward_frames(ex, tab, true, mean, norm, stream ? (hipStream_t)stream : ex->own_stream);
 }
 
 extern "C" int ffgpu_exec_dets_dev(ffgpu_exec *ex, void **dev_ptr, size_t *bytes)

@@ -53,11 +53,16 @@ __device__ __forceinline__ float front_cvt(unsigned byte, float m, float s)
     return v;
 }
 
-template <int OC, bool U8, int NC = 4, bool RS = false>
+// NV (RS as well): the frames of ffgpu_exec_forward_nv12_frames_dev.  The same gather with a pixel made of its Y byte (one byte load) and the U V pair
+// of its 2 x 2 block (one aligned 16-bit load: the chroma plane is 2-byte aligned, its pitch even): 12 raw dwords per lane and row in flight, as in RS.
+// A lane's column offsets serve both planes (x' in the Y row, x' & ~1 in the chroma row); per row the wave maps y -> y' = y s1 / s2 and the chroma row
+// y' >> 1.  The matrix is the frame's, hence the wave's: six scalar values.  Integer conversion (nv12_to_bgr) where cvt_row converts, then front_cvt.
+template <int OC, bool U8, int NC = 4, bool RS = false, bool NV = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k_front(FrontP p)
 {
     static_assert(NC == 4 || NC == 3, "columns per lane");
     static_assert(!RS || (U8 && NC == 3), "the resizing form reads u8 frames, three columns per lane");
+    static_assert(!NV || RS, "the NV12 form is a resizing form");
     constexpr int IC = 8, EC = 8, CP = EC / 2, RL1 = 12, RL2 = 12, OCP = (OC + 3) & ~3;
     // LDS tables: t0 [27 taps][4 oc pairs][2] + scale' pairs [4][2] + bias' pairs [4][2] of layer 0; then the block's
     // tables exactly as in k_irb_thin (t1 | td | t2 | sb2)
@@ -99,7 +104,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
     const unsigned bpitch = U8 && !RS ? (unsigned)p.prm->bgr_pitch : 0u;
     // RS: the frame's source, the rows that hold pixels (ihv: min(IH, sh), none when sw == 0), the lane's column offsets / which of them hold pixels
     const FFG unsigned char *fsrc = nullptr;
-    unsigned long fpitch = 0;
+    unsigned long fpitch = 0, fpitch_uv = 0;
+    const FFG unsigned char *fuv = nullptr;
+    YuvMat ym = { 0, 0, 0, 0, 0, 0 };
     unsigned fs1 = 1, fs2 = 1, cmask = 0, coff[2 * NC];
     int ihv = IH;
     bool ffast = false;
@@ -113,12 +120,21 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
         const int sw = __builtin_amdgcn_readfirstlane(fd->sw), sh = __builtin_amdgcn_readfirstlane(fd->sh);
         const int fw = __builtin_amdgcn_readfirstlane(fd->w), fh = __builtin_amdgcn_readfirstlane(fd->h);
         ihv = sw > 0 ? min(IH, sh) : 0;
-        ffast = fw == IW && fh == IH && ((alo | (unsigned)fpitch) & 3u) == 0;      // (then s1 == s2, sw = IW, sh = IH)
+        ffast = !NV && fw == IW && fh == IH && ((alo | (unsigned)fpitch) & 3u) == 0;      // (then s1 == s2, sw = IW, sh = IH)
+        if constexpr (NV) {
+            const uintptr_t c = reinterpret_cast<uintptr_t>(fd->uv);
+            const unsigned clo = __builtin_amdgcn_readfirstlane((unsigned)c), chi = __builtin_amdgcn_readfirstlane((unsigned)(c >> 32));
+            fuv = (const FFG unsigned char *)(((uintptr_t)chi << 32) | clo);
+            fpitch_uv = (unsigned)__builtin_amdgcn_readfirstlane(fd->pitch_uv);
+            const YuvMat m = yuv_mat(__builtin_amdgcn_readfirstlane(fd->fmt));
+            ym = YuvMat{ __builtin_amdgcn_readfirstlane(m.yoff), __builtin_amdgcn_readfirstlane(m.cy), __builtin_amdgcn_readfirstlane(m.crv),
+                         __builtin_amdgcn_readfirstlane(m.cgu), __builtin_amdgcn_readfirstlane(m.cgv), __builtin_amdgcn_readfirstlane(m.cbu) };
+        }
 #pragma unroll
         for (int i = 0; i < 2 * NC; i++) {
             const unsigned x = li + i;
             const bool in = (int)x < sw;
-            coff[i] = in ? 3u * front_muldiv(x, fs1, fs2) : 0u;         // (a column outside the frame reads pixel 0 of the row; its value is 0)
+            coff[i] = in ? (NV ? 1u : 3u) * front_muldiv(x, fs1, fs2) : 0u;         // (a column outside the frame reads pixel 0 of the row; its value is 0)
             cmask |= in ? 1u << i : 0u;
         }
     }
@@ -148,6 +164,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
     auto load_irow_rs = [&](int row, Row &R) __attribute__((always_inline)) {
         if constexpr (RS) {
             if (row < 0 || row >= ihv) return;                        // wave-uniform; cvt_row makes the zeros
+            if constexpr (NV) {
+                const unsigned ys = front_muldiv((unsigned)row, fs1, fs2);                                  // uniform, as the two row bases are
+                const FFG unsigned char *yr = fsrc + (unsigned long)ys * fpitch, *cr = fuv + (unsigned long)(ys >> 1) * fpitch_uv;
+#pragma unroll
+                for (int i = 0; i < 2 * NC; i++) {
+                    R.g[2 * i] = yr[coff[i]];
+                    R.g[2 * i + 1] = *(const FFG unsigned short *)(cr + (coff[i] & ~1u));
+                }
+                R.sh = 0u;
+                return;
+            }
             unsigned v[4 * NC], r3 = 0;                               // (both branches write every element: no store the compiler could merge into one through a selected address)
             if (ffast) {
                 const FFG unsigned char *src = fsrc + (unsigned long)row * fpitch + ((3u * li) & ~3u);
@@ -188,10 +215,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
             for (int ci = 0; ci < 3; ci++) { R.a[ci] = z4; R.b[ci] = z4; }
             return;
         }
-        if constexpr (RS) if (!ffast) {
+        if constexpr (RS) if (NV || !ffast) {
 #pragma unroll
             for (int i = 0; i < 2 * NC; i++) {
-                const unsigned px = __builtin_amdgcn_alignbyte(R.g[2 * i + 1], R.g[2 * i], (R.sh + coff[i]) & 3u);     // B G R in bytes 0 1 2
+                unsigned px;                                                                                            // B G R in bytes 0 1 2
+                if constexpr (NV) px = nv12_to_bgr((int)R.g[2 * i], (int)(R.g[2 * i + 1] & 0xffu), (int)(R.g[2 * i + 1] >> 8), ym);
+                else px = __builtin_amdgcn_alignbyte(R.g[2 * i + 1], R.g[2 * i], (R.sh + coff[i]) & 3u);
                 const bool in = (cmask >> i) & 1u;
 #pragma unroll
                 for (int ci = 0; ci < 3; ci++) {

@@ -519,10 +519,12 @@ __global__ void k_set_params(ExecParams *prm, ExecParams v)
     if (threadIdx.x == 0 && blockIdx.x == 0) *prm = v;
 }
 
-// the per-frame table of ffgpu_exec_forward_bgr_frames_dev: FRAMES_CHUNK descriptors travel by value as the kernel's argument (no pinned staging,
-// no host sync: the caller's array is free on return), one thread per descriptor: 2.5 KB of arguments, one launch for a batch of 64
+// the per-frame table of ffgpu_exec_forward_bgr_frames_dev / _nv12_frames_dev: FRAMES_CHUNK descriptors travel by value as the kernel's argument (no
+// pinned staging, no host sync: the caller's array is free on return), one thread per descriptor: 64 x 56 = 3 588 bytes of arguments with the count, one
+// launch for a batch of 64
 #define FRAMES_CHUNK 64
 struct FramesChunk { FrameDesc d[FRAMES_CHUNK]; int n; };
+static_assert(sizeof(FramesChunk) + sizeof(FrameDesc *) <= 4096 - 256, "k_set_frames: the chunk travels as a kernel argument (4 KB at most, the hidden arguments included)");
 __global__ void k_set_frames(FrameDesc *tab, FramesChunk c)
 {
     if (threadIdx.x < (unsigned)c.n) tab[threadIdx.x] = c.d[threadIdx.x];
@@ -565,6 +567,80 @@ __global__ void __launch_bounds__(256) k_input_frames(const FrameDesc *tab, floa
             r[i] = in ? ((float)px[i][2] - p.mean[0]) * p.norm[0] : 0.f;
             g[i] = in ? ((float)px[i][1] - p.mean[1]) * p.norm[1] : 0.f;
             b[i] = in ? ((float)px[i][0] - p.mean[2]) * p.norm[2] : 0.f;
+        }
+    }
+    float *o = out + (long)n * 3 * H * W + (long)y * W + x0;
+    if ((W & 3) == 0) {
+        *reinterpret_cast<f4 *>(o) = r;
+        *reinterpret_cast<f4 *>(o + (long)H * W) = g;
+        *reinterpret_cast<f4 *>(o + 2L * H * W) = b;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            if (x0 + i < W) { o[i] = r[i]; o[i + (long)H * W] = g[i]; o[i + 2L * H * W] = b[i]; }
+    }
+}
+
+// NV12 -> B G R (bytes 0 1 2 of the result) of one pixel, include/ffcnn_hip.h's integer formula: every product fits 24 signed bits, >> is
+// arithmetic, the clamp comes last.  m = { yoff, cy, crv, cgu, cgv, cbu } of the frame's matrix.
+__constant__ int c_yuv_mat[4][6] = FFGPU_YUV_MATRICES;
+struct YuvMat { int yoff, cy, crv, cgu, cgv, cbu; };
+__device__ __forceinline__ YuvMat yuv_mat(int fmt)
+{
+    const int *m = c_yuv_mat[(fmt - 1) & 3];
+    return YuvMat{ m[0], m[1], m[2], m[3], m[4], m[5] };
+}
+__device__ __forceinline__ int clamp255(int v) { return min(max(v, 0), 255); }
+__device__ __forceinline__ unsigned nv12_to_bgr(int Y, int U, int V, const YuvMat &m)
+{
+    // (every factor and every product fits 24 signed bits: __mul24 is exact and a full-rate v_mul_i32_i24 / v_mad_i32_i24, a plain int product is not)
+    const int c = __mul24(m.cy, Y - m.yoff) + 128, d = U - 128, e = V - 128;
+    const int r = clamp255((c + __mul24(m.crv, e)) >> 8), g = clamp255((c - __mul24(m.cgu, d) - __mul24(m.cgv, e)) >> 8), b = clamp255((c + __mul24(m.cbu, d)) >> 8);
+    return (unsigned)b | ((unsigned)g << 8) | ((unsigned)r << 16);
+}
+
+// batched net_input of MIXED NV12 frames (ffgpu_exec_forward_nv12_frames_dev, staged path): k_input_frames with the pixel made from the Y
+// plane's byte and the chroma pair of its 2 x 2 block (nearest chroma); converting only the sampled pixel is converting the whole image
+// first, because net_input samples nearest-neighbour.  Unresized frames read a thread's 4 Y bytes and 2 chroma pairs as one dword each
+// where the planes are dword aligned; every other frame reads a byte and an aligned 16-bit pair per pixel.
+__global__ void __launch_bounds__(256) k_input_nv12_frames(const FrameDesc *tab, float *out, int W, int H, InputP p)
+{
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const unsigned wq = ((unsigned)W + 3) >> 2, t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= wq * (unsigned)H) return;
+    const int y = (int)(t / wq), x0 = (int)(t - (unsigned)y * wq) * 4, n = blockIdx.y;
+    const FrameDesc fd = tab[n];
+    f4 r = { 0.f, 0.f, 0.f, 0.f }, g = r, b = r;
+    if (y < fd.sh && x0 < fd.sw) {
+        const YuvMat m = yuv_mat(fd.fmt);
+        const long ys = (long)y * fd.s1 / fd.s2;
+        const unsigned char *yrow = fd.bgr + ys * fd.pitch, *crow = fd.uv + (ys >> 1) * fd.pitch_uv;
+        unsigned px[4];
+        if (fd.s1 == fd.s2 && x0 + 3 < fd.sw && ((reinterpret_cast<uintptr_t>(fd.bgr) | (unsigned)fd.pitch) & 3) == 0) {   // not resized (sw == w), dword aligned Y rows
+            const unsigned yy = *reinterpret_cast<const unsigned *>(yrow + x0);
+            unsigned cc;                                               // the two chroma pairs of pixels x0, x0 + 1 | x0 + 2, x0 + 3: bytes x0 .. x0 + 3 of the row
+            if (((reinterpret_cast<uintptr_t>(fd.uv) | (unsigned)fd.pitch_uv) & 3) == 0) cc = *reinterpret_cast<const unsigned *>(crow + x0);
+            else cc = (unsigned)*reinterpret_cast<const unsigned short *>(crow + x0) | ((unsigned)*reinterpret_cast<const unsigned short *>(crow + x0 + 2) << 16);
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const unsigned pr = cc >> (16 * (i >> 1));
+                px[i] = nv12_to_bgr((int)((yy >> (8 * i)) & 0xffu), (int)(pr & 0xffu), (int)((pr >> 8) & 0xffu), m);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int x = min(x0 + i, fd.sw - 1);
+                const long xs = (long)x * fd.s1 / fd.s2;
+                const unsigned pr = *reinterpret_cast<const unsigned short *>(crow + (xs & ~1L));      // U V of the pixel's 2 x 2 block: 2-byte aligned
+                px[i] = nv12_to_bgr((int)yrow[xs], (int)(pr & 0xffu), (int)(pr >> 8), m);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const bool in = x0 + i < fd.sw;
+            r[i] = in ? ((float)((px[i] >> 16) & 0xffu) - p.mean[0]) * p.norm[0] : 0.f;
+            g[i] = in ? ((float)((px[i] >> 8) & 0xffu) - p.mean[1]) * p.norm[1] : 0.f;
+            b[i] = in ? ((float)(px[i] & 0xffu) - p.mean[2]) * p.norm[2] : 0.f;
         }
     }
     float *o = out + (long)n * 3 * H * W + (long)y * W + x0;
@@ -740,6 +816,17 @@ int ffgpu_launch_input_frames(const FrameDesc *d_tab, float *out, int N, int W, 
     if (N > 65535 || q >= (1L << 31)) { ffgpu_set_error("input_frames: %d frames of %d x %d is too large", N, W, H); return -1; }
     hipLaunchKernelGGL(k_input_frames, dim3((unsigned)((q + 255) / 256), (unsigned)N), dim3(256), 0, s, d_tab, out, W, H, p);
     LAUNCH_OK("input_frames");
+    return 0;
+}
+
+int ffgpu_launch_input_nv12_frames(const FrameDesc *d_tab, float *out, int N, int W, int H, const float mean[3], const float norm[3], hipStream_t s)
+{
+    InputP p;
+    for (int i = 0; i < 3; i++) { p.mean[i] = mean[i]; p.norm[i] = norm[i]; }
+    const long q = (long)((W + 3) / 4) * H;
+    if (N > 65535 || q >= (1L << 31)) { ffgpu_set_error("input_nv12_frames: %d frames of %d x %d is too large", N, W, H); return -1; }
+    hipLaunchKernelGGL(k_input_nv12_frames, dim3((unsigned)((q + 255) / 256), (unsigned)N), dim3(256), 0, s, d_tab, out, W, H, p);
+    LAUNCH_OK("input_nv12_frames");
     return 0;
 }
 

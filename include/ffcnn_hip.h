@@ -131,6 +131,42 @@ typedef struct {
 int ffgpu_exec_forward_bgr_frames_dev(ffgpu_exec *ex, const ffgpu_bgr_frame *frames, int nframes,
                                       const float mean[3], const float norm[3], void *stream);
 
+/* NV12 -> BGR matrices of ffgpu_nv12_frame::matrix.  In 32-bit integers, with c = Y - yoff, d = U - 128, e = V - 128:
+ *   R = clamp((cy c         + crv e + 128) >> 8, 0, 255)        (>> is arithmetic, the clamp comes last)
+ *   G = clamp((cy c - cgu d - cgv e + 128) >> 8, 0, 255)
+ *   B = clamp((cy c + cbu d         + 128) >> 8, 0, 255)
+ *                                     yoff   cy  crv  cgu  cgv  cbu */
+#define FFGPU_YUV_BT601_LIMITED 0   /*  16  298  409  100  208  516 */
+#define FFGPU_YUV_BT601_FULL    1   /*   0  256  359   88  183  454 */
+#define FFGPU_YUV_BT709_LIMITED 2   /*  16  298  459   55  136  541 */
+#define FFGPU_YUV_BT709_FULL    3   /*   0  256  403   48  120  475 */
+
+/* One NV12 frame of a mixed batch (what video decoders write): a full-resolution Y plane and a half-resolution plane of interleaved
+ * U V pairs, (h + 1) / 2 rows of (w + 1) / 2 pairs; odd sizes are legal. */
+typedef struct {
+    const unsigned char *y;     /* device address of row 0 of the Y plane, any byte alignment                           */
+    const unsigned char *uv;    /* device address of row 0 of the interleaved U V plane, 2-byte aligned;                */
+                                /* NULL = y + pitch_y * h (one contiguous surface)                                      */
+    int w, h;                   /* pixels, >= 1                                                                         */
+    int pitch_y;                /* bytes between Y rows, >= w; 0 = w                                                    */
+    int pitch_uv;               /* bytes between UV rows, even, >= 2 ((w + 1) / 2); 0 = that minimum                    */
+    int matrix;                 /* FFGPU_YUV_*                                                                          */
+    int reserved;               /* 0                                                                                    */
+} ffgpu_nv12_frame;             /* 40 bytes */
+
+/* ffgpu_exec_forward_bgr_frames_dev for NV12 frames: frame n = net_input (ffcnn.c:259-289) of the BGR image whose pixel (x, y) is the
+ * formula above applied to Y[y][x], U = UV[y >> 1][2 (x >> 1)], V = UV[y >> 1][2 (x >> 1) + 1] (nearest chroma), then the forward.
+ * net_input samples nearest-neighbour, so only the sampled pixels are converted, inside the kernel that samples them; no BGR image is
+ * ever written.  Default route: k_input_nv12_frames writes the fp32 batch in front of the ordinary graph (staged).  FFGPU_NV12_FRONT=1
+ * sends the frames into the NV12 form of the fused first kernel instead, on plans that start with it at three columns per lane (no fp32
+ * batch; same records, byte for byte); it is not the default because it has not beaten staging by the margin DESIGN 5.15 asks for.
+ * FFGPU_NO_U8_FRONT=1 forces staging whatever else is set.  Same contract: host array free on return, pixels valid until the forward completes, enqueued on
+ * `stream` without synchronising, nframes == batch, 3-channel nets, the executor's own scale untouched.  Rejected with the frame's
+ * index in the message: NULL y, w or h < 1, pitch_y < w, pitch_uv odd or below its minimum, an odd uv address, matrix outside 0..3,
+ * reserved != 0.  A failed call leaves the executor usable. */
+int ffgpu_exec_forward_nv12_frames_dev(ffgpu_exec *ex, const ffgpu_nv12_frame *frames, int nframes,
+                                       const float mean[3], const float norm[3], void *stream);
+
 /* Device address of the batch's ffgpu_frame_dets[batch] (valid after the
  * forward enqueued on the same stream completes). */
 int ffgpu_exec_dets_dev(ffgpu_exec *ex, void **dev_ptr, size_t *bytes);
