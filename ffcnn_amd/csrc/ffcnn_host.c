@@ -368,8 +368,7 @@ void net_input(NET *net, unsigned char *bgr, int w, int h, float *mean, float *n
     int sw, sh;
     memset(net->bbox_list, 0, sizeof(BBOX) * (size_t)net->bbox_num);
     net->bbox_num = 0;
-    if ((long)w * H > (long)h * W) { sw = W; sh = (int)((long)sw * h / w); net->s1 = w; net->s2 = sw; }
-    else                           { sh = H; sw = (int)((long)sh * w / h); net->s1 = h; net->s2 = sh; }
+    letterbox(w, h, W, H, &sw, &sh, &net->s1, &net->s2);
     const size_t pitch = (size_t)UP(w * 3, 4), plane = (size_t)W * H;
     float *dst = l0->data;
     for (int y = 0; y < sh; y++) {

@@ -1425,8 +1425,8 @@ bool ffgpu_front_ok(const ConvDesc &c, const IrbDesc &d)
            (long)c.N * c.oh * c.ow >= env_int("FFGPU_FRONT_MIN_PX", 262144) && !env_int("FFGPU_NO_FRONT", 0);
 }
 
-// u8: the frames of this forward are u8 BGR images described by the executor's parameter block (c.in_ind IS that block: its
-// first member is the fp32 frame pointer the other form reads)
+// form IN_U8: the frames of this forward are u8 BGR images described by the executor's parameter block (c.in_ind IS that block: its
+// first member is the fp32 frame pointer the IN_F32 form reads)
 // three columns per lane (54 of 64 lanes on a 160-pixel row instead of 40) where the row fits a wave that way; FFGPU_FRONT_NC=4: the round-1 form.
 // ONE form for u8 and fp32 frames: each form sits within tolerance of the reference, but the two are not bit-identical to each other, and the same frames
 // must give the same records whichever way they arrive (tests/test_gpu_round3.py::test_u8_frames_into_the_first_kernel)
@@ -1435,17 +1435,17 @@ int ffgpu_front_nc(const IrbDesc &d)
     return env_int("FFGPU_FRONT_NC", 3) == 3 && d.W >= 6 && (d.W + 2) / 3 <= 64 ? 3 : 4;
 }
 
-// resize: u8 frames of any size described one by one by the parameter block's frames_tab (ffgpu_exec_forward_bgr_frames_dev).  Three columns per
-// lane only: the four-column form of the gather does not fit a wave's registers, so the executor stages those frames (ffgpu_front_nc == 4) instead.
-// Which route NV12 frames take on plans that have the fused form: FFGPU_NV12_FRONT=1 the NV12 form of k_front, =0 staging (k_input_nv12_frames);
+// forms IN_BGR_FRAMES / IN_NV12_FRAMES (the resizing forms): u8 frames of any size described one by one by the parameter block's frames_tab.  Three
+// columns per lane only: the four-column form of the gather does not fit a wave's registers, so the executor stages those frames (ffgpu_front_nc == 4) instead.
+// Which route NV12 frames take on plans that have the fused form: FFGPU_NV12_FRONT=1 the NV12 form of k_front, =0 staging (k_input4, ffgpu_input.inc);
 // unset: FFGPU_NV12_FRONT_DEFAULT, the outcome of tools/nv12_frames_bench.py (DESIGN 5.15: fused only if it beats staging at four chains by more
 // than the spread of the repeats).  Read at every call: it selects between two graphs, it changes neither.
 #define FFGPU_NV12_FRONT_DEFAULT 0
 bool ffgpu_front_nv12_fused() { return env_int("FFGPU_NV12_FRONT", FFGPU_NV12_FRONT_DEFAULT) != 0; }
 
-// resize 2: the same for the NV12 frames of ffgpu_exec_forward_nv12_frames_dev
-int ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, hipStream_t s, bool u8, int resize)
+int ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, InputForm form, hipStream_t s)
 {
+    const bool u8 = form == IN_U8, resize = form == IN_BGR_FRAMES || form == IN_NV12_FRAMES;
     if (!ffgpu_front_ok(c, d)) { ffgpu_set_error("front: unsupported layer pair"); return -1; }
     if ((u8 || resize) && !c.in_ind) { ffgpu_set_error("front: the u8 form needs the executor's parameter block"); return -1; }
     const int nc = ffgpu_front_nc(d);
@@ -1462,7 +1462,7 @@ int ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, hipStream_t s, bool 
     p.ntasks = d.N * p.nbands;
     p.act0 = slope(c.act); p.act1 = slope(d.act1); p.actd = slope(d.actd); p.act2 = slope(d.act2);
     const dim3 grid((unsigned)((p.ntasks + 3) / 4));
-    if (resize == 2) {
+    if (form == IN_NV12_FRAMES) {
         hipLaunchKernelGGL((k_front<4, true, 3, true, true>), grid, dim3(256), 0, s, p);
     } else if (resize) {
         hipLaunchKernelGGL((k_front<4, true, 3, true>), grid, dim3(256), 0, s, p);

@@ -63,7 +63,11 @@ void   ffgpu_irb_plan(IrbDesc &d);                     // freezes what the packe
 int    ffgpu_irb_pack(const IrbDesc &d, float *pk, hipStream_t s);
 int    ffgpu_launch_irb(const IrbDesc &d, hipStream_t s);
 bool   ffgpu_front_ok(const ConvDesc &c, const IrbDesc &d);      // first layer (3x3 s2, 3 -> 8) + thin block as one streaming kernel
-int    ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, hipStream_t s, bool u8 = false, int resize = 0);   // resize: u8 frames of the parameter block's frames_tab (1: BGR, 2: NV12)
+// How a forward's batch arrives.  IN_F32: fp32 frames (ExecParams::frames; the staging kernels of ffgpu_input.inc write them for u8 sources the first
+// kernel cannot take).  The u8 forms are read by k_front itself: IN_U8 frames of the net's own geometry (ExecParams::bgr), IN_BGR_FRAMES / IN_NV12_FRAMES
+// frames of any size, one descriptor each in ExecParams::frames_tab.  An executor keeps one captured graph per form.
+enum InputForm { IN_F32, IN_U8, IN_BGR_FRAMES, IN_NV12_FRAMES, IN_FORMS };
+int    ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, InputForm form, hipStream_t s);
 bool   ffgpu_front_nv12_fused();                                 // NV12 frames go into the NV12 form of k_front where the plan has it (FFGPU_NV12_FRONT, else the measured default)
 int    ffgpu_front_nc(const IrbDesc &d);                         // output columns per lane k_front uses for this block (3 or 4; the resizing form: 3 only)
 
@@ -93,8 +97,8 @@ static_assert(sizeof(FrameDesc) == 56, "FrameDesc: 64 of them travel by value as
 // NV12 -> BGR in 32-bit integers (include/ffcnn_hip.h): { yoff, cy, crv, cgu, cgv, cbu } per FFGPU_YUV_* matrix
 #define FFGPU_YUV_MATRICES { { 16, 298, 409, 100, 208, 516 }, { 0, 256, 359, 88, 183, 454 }, { 16, 298, 459, 55, 136, 541 }, { 0, 256, 403, 48, 120, 475 } }
 int  ffgpu_launch_set_frames(FrameDesc *d_tab, const FrameDesc *h_desc, int n, hipStream_t s);
-int  ffgpu_launch_input_frames(const FrameDesc *d_tab, float *out, int N, int W, int H, const float mean[3], const float norm[3], hipStream_t s);
-int  ffgpu_launch_input_nv12_frames(const FrameDesc *d_tab, float *out, int N, int W, int H, const float mean[3], const float norm[3], hipStream_t s);
+// staging (ffgpu_input.inc): the table's frames (BGR, or NV12 converted where sampled) -> the fp32 batch the IN_F32 graph consumes
+int  ffgpu_launch_input_frames(const FrameDesc *d_tab, bool nv12, float *out, int N, int W, int H, const float mean[3], const float norm[3], hipStream_t s);
 
 // Per-executor parameter block in device memory: what changes from one forward to the next without changing the
 // launch list.  A one-thread kernel (ffgpu_launch_set_params) rewrites it in stream order in front of the graph launch,
@@ -105,13 +109,13 @@ struct ExecParams {
     ffgpu_frame_dets *ring;   // record ring of the multi-GPU gather (ffgpu_exec_set_ring), or NULL
     int ring_slots, ring_stride;
     int bbox_max;             // NET.bbox_max of this forward: the reference re-reads it on every net_forward (ffcnn.c:461-463)
-    // u8 BGR frames of the net's own geometry, converted by the first kernel itself (k_front<.., true>; NULL: fp32 frames)
+    // form IN_U8: u8 BGR frames of the net's own geometry, converted by the first kernel itself (k_front<.., true>; NULL: every other form)
     const unsigned char *bgr;
     long  bgr_frame;          // bytes from one frame to the next
     int   bgr_pitch;          // bytes per image row (ALIGN(3 w, 4), ffcnn.c:262)
-    float mean[3], norm[3];   // net_input's per-channel mean / norm (plane order R, G, B)
-    // ffgpu_exec_forward_bgr_frames_dev / _nv12_frames_dev: this forward's per-frame table (N entries; k_nms takes each frame's s1 / s2 from it, the
-    // resizing k_front its source); NULL for every other entry point
+    float mean[3], norm[3];   // the u8 forms: net_input's per-channel mean / norm (plane order R, G, B); IN_F32: zero
+    // ffgpu_exec_forward_bgr_frames_dev / _nv12_frames_dev, fused (IN_BGR_FRAMES / IN_NV12_FRAMES) or staged (IN_F32): this forward's per-frame table
+    // (N entries; k_nms takes each frame's s1 / s2 from it, the resizing k_front its source); NULL for every other entry point
     const FrameDesc *frames_tab;
 };
 int  ffgpu_launch_set_params(ExecParams *d_prm, const ExecParams &v, hipStream_t s);

@@ -181,6 +181,35 @@ struct ffgpu_netdev {
     ffgpu_exec *exec1 = nullptr;
 };
 
+// Where a forward's batch comes from: a value the entry points build and hand down (forward_on -> push_params / capture -> issue_*), never executor
+// state.  `form` says which form of the first kernel runs and so which graph slot serves the forward; the members beside it are what that form reads:
+// frames (IN_F32), bgr / bgr_frame / bgr_pitch (IN_U8), ftab (the two frame-table forms -- and the staged route of those entry points, which is
+// IN_F32 with the table beside it: k_nms takes each frame's box scale from it), mean / norm (every u8 form).
+struct InputSrc {
+    InputForm form;
+    const float *frames;
+    const unsigned char *bgr; long bgr_frame; int bgr_pitch;
+    const FrameDesc *ftab;
+    float mean[3], norm[3];
+    // the source of the c-th part of a split executor: part_frames frames of part_floats floats in all
+    InputSrc slice(int c, int part_frames, size_t part_floats) const
+    {
+        InputSrc p = *this;
+        if (frames) p.frames = frames + c * part_floats;
+        if (bgr) p.bgr = bgr + (long)c * part_frames * bgr_frame;
+        if (ftab) p.ftab = ftab + (size_t)c * part_frames;
+        return p;
+    }
+};
+static InputSrc fp32_src(const float *d_frames) { InputSrc in = {}; in.frames = d_frames; return in; }
+static InputSrc u8_src(InputForm form, const float mean[3], const float norm[3])
+{
+    InputSrc in = {};
+    in.form = form;
+    for (int k = 0; k < 3; k++) { in.mean[k] = mean[k]; in.norm[k] = norm[k]; }
+    return in;
+}
+
 struct ffgpu_exec {
     NET *net = nullptr;
     ffgpu_netdev *dev = nullptr;
@@ -202,21 +231,13 @@ struct ffgpu_exec {
     ExecParams *d_prm = nullptr;       // device parameter block: input pointer + box scale of the forward being enqueued
     bool   indirect = false;           // every launch that reads the batch input does so through d_prm->frames
     ExecParams prm_sent = {}; hipStream_t prm_stream = nullptr; bool prm_valid = false;      // what d_prm holds (or will, on prm_stream)
-    const float *last_frames = nullptr;   // input of the last forward (read_layer(-1))
+    InputSrc last = {};                // input of the last forward (read_layer(-1))
     ffgpu_frame_dets *d_dets = nullptr;
     ffgpu_frame_dets *h_dets = nullptr, *h_dets_dev = nullptr;   // FFGPU_HOST_DETS: pinned mirror and its device address
-    // u8 BGR frames converted by the first kernel itself (ffgpu_exec_forward_bgr_dev without resize on a plan that starts with k_front)
-    const unsigned char *bgr = nullptr; long bgr_frame = 0; int bgr_pitch = 0; float bgr_mean[3] = {}, bgr_norm[3] = {};
-    bool u8_mode = false;              // the forward being enqueued / captured reads `bgr`
-    hipGraphExec_t graph_u8 = nullptr; // its graph (the u8 form of the first kernel is another kernel): captured on first use
-    // mixed u8 frames (ffgpu_exec_forward_bgr_frames_dev): the device table of per-frame descriptors (one entry per frame, what
-    // d_prm->frames_tab names during such a forward) and the resizing first kernel's graph (captured on first use)
-    FrameDesc *d_ftab = nullptr;       // owned by the executor that allocated it (a split executor's halves point into their parent's)
-    const FrameDesc *ftab = nullptr;   // the table the forward being enqueued reads (NULL: every other entry point)
+    // the frame-table entry points: the device table of per-frame descriptors (one entry per frame, what d_prm->frames_tab names during such a
+    // forward; a split executor's halves read their parts of their parent's)
+    FrameDesc *d_ftab = nullptr;
     std::vector<FrameDesc> ftab_sent; hipStream_t ftab_stream = nullptr;      // what d_ftab holds (or will, on ftab_stream)
-    int  rs_mode = 0;                  // the forward being enqueued / captured runs a resizing u8 form of the first kernel (1: BGR frames, 2: NV12 frames)
-    bool rs_last = false;              // ... and the last forward pushed did (read_layer(-1): no fp32 input tensor exists)
-    hipGraphExec_t graph_rs = nullptr, graph_nv = nullptr;      // (one per form, each captured on first use)
     float *h_stage = nullptr;          // ffgpu_exec_forward_host from caller memory: page-locked staging of one batch (on first use)
     ffgpu_frame_dets *ring = nullptr; int ring_slots = 0; int *d_ringctr = nullptr;   // ffgpu_exec_set_ring
     int ring_stride = 0;               // records per ring slot (the parent's batch for the halves of a split executor)
@@ -230,10 +251,11 @@ struct ffgpu_exec {
     hipStream_t side_stream = nullptr;              // second graph branch
     hipEvent_t  ev_fork = nullptr, ev_join = nullptr;
     int side_lo = -1, side_hi = -1;                 // layers [side_lo, side_hi] form the side branch
-    // ONE instantiated graph per executor: the input pointer and the box scale reach the kernels through d_prm.  Only a
+    // ONE instantiated graph per input form: the input pointer and the box scale reach the kernels through d_prm, and the forms differ in
+    // the first kernel alone.  IN_F32's is captured when the executor is created, a u8 form's on its first use.  Only a
     // net whose first layer has no kernel that reads through the slot (indirect == false: e.g. a pool or a pointwise conv
     // straight on the input) falls back to graphs keyed by the input pointer, least recently used one evicted.
-    hipGraphExec_t graph1 = nullptr;
+    hipGraphExec_t graph[IN_FORMS] = {};
     struct Keyed { const float *in; hipGraphExec_t g; unsigned long stamp; };
     std::vector<Keyed> graphs;
     unsigned long graph_stamp = 0;
@@ -670,8 +692,9 @@ static int repack(ffgpu_exec *ex, hipStream_t s)
 }
 
 // -------------------------------------------------------------------------- running
-static int issue_step(ffgpu_exec *ex, const Step &st, const float *d_frames, hipStream_t s)
+static int issue_step(ffgpu_exec *ex, const Step &st, const InputSrc &in, hipStream_t s)
 {
+    const float *const d_frames = in.frames;
 #ifdef FFGPU_DIAG
     // tuning only (tools/ablate_layers.py): FFGPU_DBG_SKIP="lo:hi" drops the launches of layers lo..hi -- wrong results,
     // but the change in frames/s is what that stretch of the net costs with several batches in flight
@@ -724,7 +747,7 @@ static int issue_step(ffgpu_exec *ex, const Step &st, const float *d_frames, hip
     case S_FRONT: {
         ConvDesc d = st.conv;
         if (st.in_is_input && !d.in_ind) d.in = d_frames;
-        return ffgpu_launch_front(d, st.irb, s, ex->u8_mode, ex->rs_mode); }
+        return ffgpu_launch_front(d, st.irb, in.form, s); }
     case S_YOLO:
         return ffgpu_launch_yolo(st.head, ex->N, ex->in_w, ex->in_h, ex->d_cand, ex->d_cand_key, ex->d_ncand, ex->cand_cap,
                                  st.flag ? ex->d_ringctr : nullptr, s);          // forwards are counted whether or not a ring is attached
@@ -735,7 +758,7 @@ static int issue_step(ffgpu_exec *ex, const Step &st, const float *d_frames, hip
     return -1;
 }
 
-static int issue_all(ffgpu_exec *ex, const float *d_frames, hipStream_t s)
+static int issue_all(ffgpu_exec *ex, const InputSrc &in, hipStream_t s)
 {
     bool forked = false, joined = true;
     for (const Step &st : ex->steps) {
@@ -747,7 +770,7 @@ static int issue_all(ffgpu_exec *ex, const float *d_frames, hipStream_t s)
                 FFGPU_CHECK(hipStreamWaitEvent(ex->side_stream, ex->ev_fork, 0));
                 forked = true; joined = false;
             }
-            if (issue_step(ex, st, d_frames, ex->side_stream) != 0) return -1;
+            if (issue_step(ex, st, in, ex->side_stream) != 0) return -1;
             continue;
         }
         if (st.kind == S_NMS && !joined) {                   // join before the candidates are consumed
@@ -755,7 +778,7 @@ static int issue_all(ffgpu_exec *ex, const float *d_frames, hipStream_t s)
             FFGPU_CHECK(hipStreamWaitEvent(s, ex->ev_join, 0));
             joined = true;
         }
-        if (issue_step(ex, st, d_frames, s) != 0) return -1;
+        if (issue_step(ex, st, in, s) != 0) return -1;
     }
     if (!joined) {
         FFGPU_CHECK(hipEventRecord(ex->ev_join, ex->side_stream));
@@ -767,14 +790,14 @@ static int issue_all(ffgpu_exec *ex, const float *d_frames, hipStream_t s)
 // FFGPU_SPLIT2: the two halves of the batch are two independent chains of the same 40-odd launches; issued on two
 // streams they become two parallel branches of one graph.  Most of the launches are bound by a wave's serial chain and
 // a few microseconds of launch / first-load latency, not by a pipe: the second chain fills those gaps.
-static int issue_all(ffgpu_exec *ex, const float *d_frames, hipStream_t s);
-static int issue_split(ffgpu_exec *ex, const float *d_frames, hipStream_t s)
+static int issue_split(ffgpu_exec *ex, const InputSrc &in, hipStream_t s)
 {
-    const size_t part = (size_t)ex->child[0]->N * ex->in_c * ex->in_h * ex->in_w;
+    const int pn = ex->child[0]->N;
+    const size_t part = (size_t)pn * ex->in_c * ex->in_h * ex->in_w;
     FFGPU_CHECK(hipEventRecord(ex->ev_fork, s));
     for (int c = 1; c < ex->nchild; c++) FFGPU_CHECK(hipStreamWaitEvent(ex->part_stream[c], ex->ev_fork, 0));
     for (int c = 0; c < ex->nchild; c++)
-        if (issue_all(ex->child[c], d_frames + c * part, c ? ex->part_stream[c] : s) != 0) return -1;
+        if (issue_all(ex->child[c], in.slice(c, pn, part), c ? ex->part_stream[c] : s) != 0) return -1;
     for (int c = 1; c < ex->nchild; c++) {
         FFGPU_CHECK(hipEventRecord(ex->part_ev[c], ex->part_stream[c]));
         FFGPU_CHECK(hipStreamWaitEvent(s, ex->part_ev[c], 0));
@@ -784,29 +807,25 @@ static int issue_split(ffgpu_exec *ex, const float *d_frames, hipStream_t s)
 
 // the parameter block of this forward, written in stream order in front of the launches that read it; skipped when the
 // block already holds (or, on the same stream, will hold by then) the same values
-static int push_params(ffgpu_exec *ex, const float *d_frames, hipStream_t s)
+static int push_params(ffgpu_exec *ex, const InputSrc &in, hipStream_t s)
 {
     if (ex->child[0]) {
-        const size_t part = (size_t)ex->child[0]->N * ex->in_c * ex->in_h * ex->in_w;
+        const int pn = ex->child[0]->N;
+        const size_t part = (size_t)pn * ex->in_c * ex->in_h * ex->in_w;
         for (int c = 0; c < ex->nchild; c++) {
             ffgpu_exec *ch = ex->child[c];
             ch->s1 = ex->s1; ch->s2 = ex->s2; ch->bbox_max = ex->bbox_max; ch->last_stream = s;
-            ch->u8_mode = ex->u8_mode; ch->bgr = ex->bgr ? ex->bgr + (long)c * ch->N * ex->bgr_frame : nullptr; ch->bgr_frame = ex->bgr_frame; ch->bgr_pitch = ex->bgr_pitch;
-            memcpy(ch->bgr_mean, ex->bgr_mean, sizeof ch->bgr_mean); memcpy(ch->bgr_norm, ex->bgr_norm, sizeof ch->bgr_norm);
-            ch->rs_mode = ex->rs_mode; ch->ftab = ex->ftab ? ex->ftab + (size_t)c * ch->N : nullptr;      // each half reads its own half of the table
-            if (push_params(ch, ex->u8_mode || ex->rs_mode ? nullptr : d_frames + c * part, s)) return -1;
+            if (push_params(ch, in.slice(c, pn, part), s)) return -1;      // (each half reads its own half of the frames / the table)
         }
         return 0;
     }
-    ex->last_frames = d_frames;
+    ex->last = in;
     ExecParams v;
     memset(&v, 0, sizeof v);
-    v.frames = d_frames; v.s1 = ex->s1; v.s2 = ex->s2;
-    if (ex->u8_mode) { v.bgr = ex->bgr; v.bgr_frame = ex->bgr_frame; v.bgr_pitch = ex->bgr_pitch; }
-    if (ex->u8_mode || ex->rs_mode)
-        for (int k = 0; k < 3; k++) { v.mean[k] = ex->bgr_mean[k]; v.norm[k] = ex->bgr_norm[k]; }
-    ex->rs_last = ex->rs_mode != 0;
-    v.frames_tab = ex->ftab;
+    v.frames = in.frames; v.s1 = ex->s1; v.s2 = ex->s2;
+    v.bgr = in.bgr; v.bgr_frame = in.bgr_frame; v.bgr_pitch = in.bgr_pitch;
+    for (int k = 0; k < 3; k++) { v.mean[k] = in.mean[k]; v.norm[k] = in.norm[k]; }
+    v.frames_tab = in.ftab;
     v.bbox_max = ex->bbox_max;
     v.ring = ex->ring; v.ring_slots = ex->ring_slots; v.ring_stride = ex->ring_stride ? ex->ring_stride : ex->N;
     if (ex->prm_valid && ex->prm_stream == s && memcmp(&v, &ex->prm_sent, sizeof v) == 0) return 0;
@@ -822,7 +841,7 @@ static bool graph_pointer_free(const ffgpu_exec *ex)
     return true;
 }
 
-static int capture(ffgpu_exec *ex, const float *d_frames, hipGraphExec_t *out)
+static int capture(ffgpu_exec *ex, const InputSrc &in, hipGraphExec_t *out)
 {
     hipGraph_t graph = nullptr;
     hipGraphExec_t gexec = nullptr;
@@ -830,7 +849,7 @@ static int capture(ffgpu_exec *ex, const float *d_frames, hipGraphExec_t *out)
     // null stream, which cannot be captured); replay goes to the caller's stream
     hipStream_t cs = ex->own_stream;
     FFGPU_CHECK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-    const int rc = ex->child[0] ? issue_split(ex, d_frames, cs) : issue_all(ex, d_frames, cs);
+    const int rc = ex->child[0] ? issue_split(ex, in, cs) : issue_all(ex, in, cs);
     hipError_t e = hipStreamEndCapture(cs, &graph);
     if (rc != 0) { if (graph) (void)hipGraphDestroy(graph); return -1; }
     if (e != hipSuccess) { ffgpu_set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); return -1; }
@@ -844,10 +863,7 @@ static int capture(ffgpu_exec *ex, const float *d_frames, hipGraphExec_t *out)
 
 static void drop_graphs(ffgpu_exec *ex)                       // caller has synchronised the streams the graphs ran on
 {
-    if (ex->graph1) { (void)hipGraphExecDestroy(ex->graph1); ex->graph1 = nullptr; }
-    if (ex->graph_u8) { (void)hipGraphExecDestroy(ex->graph_u8); ex->graph_u8 = nullptr; }
-    if (ex->graph_rs) { (void)hipGraphExecDestroy(ex->graph_rs); ex->graph_rs = nullptr; }
-    if (ex->graph_nv) { (void)hipGraphExecDestroy(ex->graph_nv); ex->graph_nv = nullptr; }
+    for (hipGraphExec_t &g : ex->graph) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     for (auto &g : ex->graphs) (void)hipGraphExecDestroy(g.g);
     ex->graphs.clear();
 }
@@ -860,17 +876,18 @@ static void drop_graphs(ffgpu_exec *ex)                       // caller has sync
 static int capture_at_create(ffgpu_exec *ex)
 {
     if ((ex->flags & FFGPU_NO_GRAPH) || !graph_pointer_free(ex)) return 0;
-    return capture(ex, nullptr, &ex->graph1);
+    return capture(ex, fp32_src(nullptr), &ex->graph[IN_F32]);
 }
 
-static int forward_on(ffgpu_exec *ex, const float *d_frames, hipStream_t s)
+static int forward_on(ffgpu_exec *ex, const InputSrc &in, hipStream_t s)
 {
+    const float *const d_frames = in.frames;
     ex->last_stream = s;
-    if (push_params(ex, d_frames, s)) return -1;
-    if (ex->flags & FFGPU_NO_GRAPH) return ex->child[0] ? issue_split(ex, d_frames, s) : issue_all(ex, d_frames, s);
-    if (graph_pointer_free(ex)) {                            // the usual case: one graph, whatever the input buffer / scale
-        hipGraphExec_t &g1 = ex->rs_mode == 2 ? ex->graph_nv : ex->rs_mode ? ex->graph_rs : ex->u8_mode ? ex->graph_u8 : ex->graph1;      // (+ one more per u8 form of the first kernel)
-        if (!g1 && capture(ex, d_frames, &g1)) return -1;
+    if (push_params(ex, in, s)) return -1;
+    if (ex->flags & FFGPU_NO_GRAPH) return ex->child[0] ? issue_split(ex, in, s) : issue_all(ex, in, s);
+    if (graph_pointer_free(ex)) {                            // the usual case: the form's graph, whatever the input buffer / scale
+        hipGraphExec_t &g1 = ex->graph[in.form];
+        if (!g1 && capture(ex, in, &g1)) return -1;
         FFGPU_CHECK(hipGraphLaunch(g1, s));
         return 0;
     }
@@ -886,7 +903,7 @@ static int forward_on(ffgpu_exec *ex, const float *d_frames, hipStream_t s)
             ex->graphs.erase(ex->graphs.begin() + lru);
         }
         hipGraphExec_t g = nullptr;
-        if (capture(ex, d_frames, &g)) return -1;
+        if (capture(ex, in, &g)) return -1;
         ex->graphs.push_back({ d_frames, g, 0 });
         hit = &ex->graphs.back();
     }
@@ -1117,7 +1134,7 @@ extern "C" int ffgpu_exec_forward_dev(ffgpu_exec *ex, const float *d_frames, voi
 {
     if (!alive(ex, "forward_dev")) return -1;
     if (!d_frames) { ffgpu_set_error("forward_dev: NULL argument"); return -1; }
-    return forward_on(ex, d_frames, stream ? (hipStream_t)stream : ex->own_stream);
+    return forward_on(ex, fp32_src(d_frames), stream ? (hipStream_t)stream : ex->own_stream);
 }
 
 static int ensure_input(ffgpu_exec *ex)
@@ -1141,34 +1158,28 @@ extern "C" int ffgpu_exec_forward_host(ffgpu_exec *ex, const float *h_frames)
         memcpy(ex->h_stage, h_frames, bytes);                    // (the previous forward_host of this executor ended with a stream sync)
         FFGPU_CHECK(hipMemcpyAsync(ex->d_input, ex->h_stage, bytes, hipMemcpyHostToDevice, ex->own_stream));
     }
-    if (forward_on(ex, ex->d_input, ex->own_stream)) return -1;
+    if (forward_on(ex, fp32_src(ex->d_input), ex->own_stream)) return -1;
     FFGPU_CHECK(hipStreamSynchronize(ex->own_stream));
     return 0;
 }
 
-// the plan's first launch is k_front reading through the parameter block (every leaf of a split executor alike)
-static bool front_reads_u8(const ffgpu_exec *ex)
+// the plan's first launch is k_front reading through the parameter block (every leaf of a split executor alike) -- and, for the
+// resizing forms, that kernel has three columns per lane (ffgpu_front_nc)
+static bool front_fused(const ffgpu_exec *ex, bool resizing)
 {
     if (ex->child[0]) {
-        for (int c = 0; c < ex->nchild; c++) if (!front_reads_u8(ex->child[c])) return false;
+        for (int c = 0; c < ex->nchild; c++) if (!front_fused(ex->child[c], resizing)) return false;
         return true;
     }
     for (const Step &st : ex->steps)
-        if (st.in_is_input) return st.kind == S_FRONT && st.conv.in_ind != nullptr && ex->indirect;
+        if (st.in_is_input) return st.kind == S_FRONT && st.conv.in_ind != nullptr && ex->indirect && (!resizing || ffgpu_front_nc(st.irb) == 3);
     return false;
 }
 
-// ... and that kernel has the resizing form: three columns per lane (ffgpu_front_nc)
-static bool front_resizes(const ffgpu_exec *ex)
+// this forward may use the u8 form `form` of the first kernel: no fp32 batch in between.  FFGPU_NO_U8_FRONT (tuning / tests): always the two-kernel path
+static bool front_takes(const ffgpu_exec *ex, InputForm form)
 {
-    if (!front_reads_u8(ex)) return false;
-    if (ex->child[0]) {
-        for (int c = 0; c < ex->nchild; c++) if (!front_resizes(ex->child[c])) return false;
-        return true;
-    }
-    for (const Step &st : ex->steps)
-        if (st.in_is_input) return st.kind == S_FRONT && ffgpu_front_nc(st.irb) == 3;
-    return false;
+    return !getenv("FFGPU_NO_U8_FRONT") && front_fused(ex, form != IN_U8) && (form != IN_NV12_FRAMES || ffgpu_front_nv12_fused());
 }
 
 extern "C" int ffgpu_exec_forward_bgr_dev(ffgpu_exec *ex, const unsigned char *d_bgr, int w, int h,
@@ -1178,71 +1189,59 @@ extern "C" int ffgpu_exec_forward_bgr_dev(ffgpu_exec *ex, const unsigned char *d
     if (!d_bgr || w <= 0 || h <= 0 || ex->in_c != 3) { ffgpu_set_error("forward_bgr_dev: bad arguments"); return -1; }
     hipStream_t s = stream ? (hipStream_t)stream : ex->own_stream;
     const int W = ex->in_w, H = ex->in_h;
-    int sw, sh, s1, s2;                                          // ffcnn.c:267-273
-    if ((long)w * H > (long)h * W) { sw = W; sh = (int)((long)sw * h / w); s1 = w; s2 = sw; }
-    else                           { sh = H; sw = (int)((long)sh * w / h); s1 = h; s2 = sh; }
-    ex->s1 = s1; ex->s2 = s2;
-    const bool no_u8_front = getenv("FFGPU_NO_U8_FRONT") != nullptr;             // (tuning / tests: always the two-kernel path)
-    if (w == W && h == H && (reinterpret_cast<uintptr_t>(d_bgr) & 3) == 0 && !no_u8_front && front_reads_u8(ex)) {
-        // no resize (net_input copies pixel for pixel): the first kernel converts the bytes itself -- no fp32 batch in between
-        const int pitch = (w * 3 + 3) & ~3;
-        ex->bgr = d_bgr; ex->bgr_pitch = pitch; ex->bgr_frame = (long)pitch * h;
-        for (int k = 0; k < 3; k++) { ex->bgr_mean[k] = mean[k]; ex->bgr_norm[k] = norm[k]; }
-        ex->u8_mode = true;
-        const int rc = forward_on(ex, nullptr, s);
-        ex->u8_mode = false;
-        return rc;
+    int sw, sh;
+    letterbox(w, h, W, H, &sw, &sh, &ex->s1, &ex->s2);
+    if (w == W && h == H && (reinterpret_cast<uintptr_t>(d_bgr) & 3) == 0 && front_takes(ex, IN_U8)) {
+        // no resize (net_input copies pixel for pixel): the first kernel converts the bytes itself
+        InputSrc in = u8_src(IN_U8, mean, norm);
+        in.bgr = d_bgr; in.bgr_pitch = (w * 3 + 3) & ~3; in.bgr_frame = (long)in.bgr_pitch * h;
+        return forward_on(ex, in, s);
     }
     if (ensure_input(ex)) return -1;
-    if (ffgpu_launch_input_bgr(d_bgr, ex->d_input, ex->N, w, h, W, H, sw, sh, s1, s2, mean, norm, s)) return -1;
-    return forward_on(ex, ex->d_input, s);
+    if (ffgpu_launch_input_bgr(d_bgr, ex->d_input, ex->N, w, h, W, H, sw, sh, ex->s1, ex->s2, mean, norm, s)) return -1;
+    return forward_on(ex, fp32_src(ex->d_input), s);
 }
 
-// the common tail of the two frame-table entry points: the table written in stream order in front of the forward -- skipped when it holds
-// these values already; a BGR table and an NV12 one never compare equal (FrameDesc::fmt, uv) -- then the fused or the staged route
-static int forward_frames(ffgpu_exec *ex, const std::vector<FrameDesc> &tab, bool nv12, const float mean[3], const float norm[3], hipStream_t s)
-{
-    const int nframes = (int)tab.size();
-    if (!ex->d_ftab) FFGPU_CHECK(hipMalloc(&ex->d_ftab, sizeof(FrameDesc) * (size_t)ex->N));
-    if (!(ex->ftab_stream == s && ex->ftab_sent.size() == tab.size() && memcmp(ex->ftab_sent.data(), tab.data(), sizeof(FrameDesc) * tab.size()) == 0)) {
-        ex->ftab_sent.clear();
-        if (ffgpu_launch_set_frames(ex->d_ftab, tab.data(), nframes, s)) return -1;
-        ex->ftab_sent = tab; ex->ftab_stream = s;
-    }
-    for (int k = 0; k < 3; k++) { ex->bgr_mean[k] = mean[k]; ex->bgr_norm[k] = norm[k]; }
-    ex->ftab = ex->d_ftab;
-    int rc;
-    if (!getenv("FFGPU_NO_U8_FRONT") && front_resizes(ex) && (!nv12 || ffgpu_front_nv12_fused())) {      // the resizing first kernel reads the frames itself: no fp32 batch
-        ex->rs_mode = nv12 ? 2 : 1;
-        rc = forward_on(ex, nullptr, s);
-        ex->rs_mode = 0;
-    } else {                                                         // staged: the fp32 batch, then the ordinary graph
-        rc = -1;
-        if (!ensure_input(ex) && !(nv12 ? ffgpu_launch_input_nv12_frames : ffgpu_launch_input_frames)(ex->d_ftab, ex->d_input, ex->N, ex->in_w, ex->in_h, mean, norm, s))
-            rc = forward_on(ex, ex->d_input, s);
-    }
-    ex->ftab = nullptr;
-    return rc;
-}
-
-// Mixed-size u8 frames: per frame net_input's letterbox arithmetic (ffcnn.c:262-273) on the host, the table written in stream order in
-// front of the forward (skipped when it holds these values already), then either the resizing k_front reads the bytes itself (plans that
-// start with k_front) or k_input_frames writes the fp32 batch the ordinary graph consumes.  The executor's own scale stays as it was:
-// k_nms takes each frame's s1 / s2 from the table.
-extern "C" int ffgpu_exec_forward_bgr_frames_dev(ffgpu_exec *ex, const ffgpu_bgr_frame *frames, int nframes,
-                                                 const float mean[3], const float norm[3], void *stream)
+// The two frame-table entry points.  Per frame net_input's letterbox arithmetic on the host; the table written in stream order in front of the
+// forward -- skipped when it holds these values already; a BGR table and an NV12 one never compare equal (FrameDesc::fmt, uv) -- then either the
+// resizing k_front reads the bytes itself (plans that start with it) or k_input4 writes the fp32 batch the ordinary graph consumes.  The
+// executor's own scale stays as it was: k_nms takes each frame's s1 / s2 from the table.
+static bool frames_args_ok(ffgpu_exec *ex, const char *what, const void *frames, int nframes, const float *mean, const float *norm)
 {
     int ndev = 0;
     if (!ex && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)) {
         (void)hipGetLastError();
-        ffgpu_set_error("forward_bgr_frames_dev: no HIP device visible: libffcnn_hip has no CPU fallback");
-        return -1;
+        ffgpu_set_error("%s: no HIP device visible: libffcnn_hip has no CPU fallback", what);
+        return false;
     }
-    if (!alive(ex, "forward_bgr_frames_dev")) return -1;
-    if (!frames || !mean || !norm) { ffgpu_set_error("forward_bgr_frames_dev: NULL argument"); return -1; }
-    if (nframes != ex->N) { ffgpu_set_error("forward_bgr_frames_dev: %d frames for an executor of batch %d", nframes, ex->N); return -1; }
-    if (ex->in_c != 3) { ffgpu_set_error("forward_bgr_frames_dev: the net's input has %d channels, not 3", ex->in_c); return -1; }
-    const int W = ex->in_w, H = ex->in_h;
+    if (!alive(ex, what)) return false;
+    if (!frames || !mean || !norm) { ffgpu_set_error("%s: NULL argument", what); return false; }
+    if (nframes != ex->N) { ffgpu_set_error("%s: %d frames for an executor of batch %d", what, nframes, ex->N); return false; }
+    if (ex->in_c != 3) { ffgpu_set_error("%s: the net's input has %d channels, not 3", what, ex->in_c); return false; }
+    return true;
+}
+
+static int forward_frames(ffgpu_exec *ex, const std::vector<FrameDesc> &tab, InputForm form, const float mean[3], const float norm[3], hipStream_t s)
+{
+    if (!ex->d_ftab) FFGPU_CHECK(hipMalloc(&ex->d_ftab, sizeof(FrameDesc) * (size_t)ex->N));
+    if (!(ex->ftab_stream == s && ex->ftab_sent.size() == tab.size() && memcmp(ex->ftab_sent.data(), tab.data(), sizeof(FrameDesc) * tab.size()) == 0)) {
+        ex->ftab_sent.clear();
+        if (ffgpu_launch_set_frames(ex->d_ftab, tab.data(), (int)tab.size(), s)) return -1;
+        ex->ftab_sent = tab; ex->ftab_stream = s;
+    }
+    InputSrc in = u8_src(form, mean, norm);
+    if (!front_takes(ex, form)) {                                    // staged: the fp32 batch, then the ordinary graph
+        if (ensure_input(ex) || ffgpu_launch_input_frames(ex->d_ftab, form == IN_NV12_FRAMES, ex->d_input, ex->N, ex->in_w, ex->in_h, mean, norm, s)) return -1;
+        in = fp32_src(ex->d_input);
+    }
+    in.ftab = ex->d_ftab;
+    return forward_on(ex, in, s);
+}
+
+extern "C" int ffgpu_exec_forward_bgr_frames_dev(ffgpu_exec *ex, const ffgpu_bgr_frame *frames, int nframes,
+                                                 const float mean[3], const float norm[3], void *stream)
+{
+    if (!frames_args_ok(ex, "forward_bgr_frames_dev", frames, nframes, mean, norm)) return -1;
     std::vector<FrameDesc> tab((size_t)nframes);
     for (int n = 0; n < nframes; n++) {
         const ffgpu_bgr_frame &f = frames[n];
@@ -1254,27 +1253,16 @@ extern "C" int ffgpu_exec_forward_bgr_frames_dev(ffgpu_exec *ex, const ffgpu_bgr
         FrameDesc &d = tab[n];
         memset(&d, 0, sizeof d);
         d.bgr = f.bgr; d.w = f.w; d.h = f.h; d.pitch = (int)pitch;
-        if ((long)f.w * H > (long)f.h * W) { d.sw = W; d.sh = (int)((long)d.sw * f.h / f.w); d.s1 = f.w; d.s2 = d.sw; }      // ffcnn.c:267-273
-        else                               { d.sh = H; d.sw = (int)((long)d.sh * f.w / f.h); d.s1 = f.h; d.s2 = d.sh; }
+        letterbox(d.w, d.h, ex->in_w, ex->in_h, &d.sw, &d.sh, &d.s1, &d.s2);
     }
-    return forward_frames(ex, tab, false, mean, norm, stream ? (hipStream_t)stream : ex->own_stream);
+    return forward_frames(ex, tab, IN_BGR_FRAMES, mean, norm, stream ? (hipStream_t)stream : ex->own_stream);
 }
 
 // NV12 frames: the same table with the second plane, its pitch and the matrix (FrameDesc::fmt != 0); the pixel is converted where it is sampled
 extern "C" int ffgpu_exec_forward_nv12_frames_dev(ffgpu_exec *ex, const ffgpu_nv12_frame *frames, int nframes,
                                                   const float mean[3], const float norm[3], void *stream)
 {
-    int ndev = 0;
-    if (!ex && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)) {
-        (void)hipGetLastError();
-        ffgpu_set_error("forward_nv12_frames_dev: no HIP device visible: libffcnn_hip has no CPU fallback");
-        return -1;
-    }
-    if (!alive(ex, "forward_nv12_frames_dev")) return -1;
-    if (!frames || !mean || !norm) { ffgpu_set_error("forward_nv12_frames_dev: NULL argument"); return -1; }
-    if (nframes != ex->N) { ffgpu_set_error("forward_nv12_frames_dev: %d frames for an executor of batch %d", nframes, ex->N); return -1; }
-    if (ex->in_c != 3) { ffgpu_set_error("forward_nv12_frames_dev: the net's input has %d channels, not 3", ex->in_c); return -1; }
-    const int W = ex->in_w, H = ex->in_h;
+    if (!frames_args_ok(ex, "forward_nv12_frames_dev", frames, nframes, mean, norm)) return -1;
     std::vector<FrameDesc> tab((size_t)nframes);
     for (int n = 0; n < nframes; n++) {
         const ffgpu_nv12_frame &f = frames[n];
@@ -1290,10 +1278,9 @@ extern "C" int ffgpu_exec_forward_nv12_frames_dev(ffgpu_exec *ex, const ffgpu_nv
         FrameDesc &d = tab[n];
         memset(&d, 0, sizeof d);
         d.bgr = f.y; d.uv = uv; d.w = f.w; d.h = f.h; d.pitch = pitch_y; d.pitch_uv = pitch_uv; d.fmt = 1 + f.matrix;
-        if ((long)f.w * H > (long)f.h * W) { d.sw = W; d.sh = (int)((long)d.sw * f.h / f.w); d.s1 = f.w; d.s2 = d.sw; }      // ffcnn.c:267-273
-        else                               { d.sh = H; d.sw = (int)((long)d.sh * f.w / f.h); d.s1 = f.h; d.s2 = d.sh; }
+        letterbox(d.w, d.h, ex->in_w, ex->in_h, &d.sw, &d.sh, &d.s1, &d.s2);
     }
-    return forward_frames(ex, tab, true, mean, norm, stream ? (hipStream_t)stream : ex->own_stream);
+    return forward_frames(ex, tab, IN_NV12_FRAMES, mean, norm, stream ? (hipStream_t)stream : ex->own_stream);
 }
 
 extern "C" int ffgpu_exec_dets_dev(ffgpu_exec *ex, void **dev_ptr, size_t *bytes)
@@ -1414,10 +1401,10 @@ extern "C" int ffgpu_exec_read_layer(ffgpu_exec *ex, int layer, int frame, float
     }
     if (layer == -1) {                                            // the network input as the first layer saw it (frame-major)
         const size_t fl = (size_t)ex->in_c * ex->in_h * ex->in_w;
-        if (!ex->last_frames && (ex->bgr || ex->rs_last)) { ffgpu_set_error("read_layer: the last forward's frames were u8 images converted by the first kernel -- no fp32 input tensor exists"); return -1; }
-        if (!ex->last_frames) { ffgpu_set_error("read_layer: no forward has run yet"); return -1; }
+        if (ex->last.form != IN_F32) { ffgpu_set_error("read_layer: the last forward's frames were u8 images converted by the first kernel -- no fp32 input tensor exists"); return -1; }
+        if (!ex->last.frames) { ffgpu_set_error("read_layer: no forward has run yet"); return -1; }
         if (fl > cap_floats) { ffgpu_set_error("read_layer: buffer too small"); return -1; }
-        if (copy_d2h(host_out, ex->last_frames + (size_t)frame * fl, fl * sizeof(float))) return -1;
+        if (copy_d2h(host_out, ex->last.frames + (size_t)frame * fl, fl * sizeof(float))) return -1;
         return (int)fl;
     }
     if (!(ex->flags & FFGPU_KEEP_ALL)) { ffgpu_set_error("read_layer needs an FFGPU_KEEP_ALL executor"); return -1; }
@@ -1455,13 +1442,14 @@ extern "C" int ffgpu_exec_profile(ffgpu_exec *ex, const float *d_frames, float u
     if (!d_frames || !us_by_kind) { ffgpu_set_error("profile: NULL argument"); return -1; }
     if (ex->child[0]) { ffgpu_set_error("profile: not available on a split executor"); return -1; }
     hipStream_t s = ex->own_stream;
-    if (push_params(ex, d_frames, s)) return -1;
+    const InputSrc in = fp32_src(d_frames);
+    if (push_params(ex, in, s)) return -1;
     std::vector<hipEvent_t> ev(ex->steps.size() + 1);
     for (auto &e : ev) FFGPU_CHECK(hipEventCreate(&e));
-    if (issue_all(ex, d_frames, s)) return -1;                    // warm
+    if (issue_all(ex, in, s)) return -1;                    // warm
     FFGPU_CHECK(hipEventRecord(ev[0], s));
     for (size_t i = 0; i < ex->steps.size(); i++) {
-        if (issue_step(ex, ex->steps[i], d_frames, s)) return -1;
+        if (issue_step(ex, ex->steps[i], in, s)) return -1;
         FFGPU_CHECK(hipEventRecord(ev[i + 1], s));
     }
     FFGPU_CHECK(hipStreamSynchronize(s));
@@ -1483,17 +1471,18 @@ extern "C" int ffgpu_exec_profile_steps(ffgpu_exec *ex, const float *d_frames, i
     if (!d_frames || !layer_of || !us) { ffgpu_set_error("profile_steps: NULL argument"); return -1; }
     if (ex->child[0]) { ffgpu_set_error("profile_steps: not available on a split executor"); return -1; }
     hipStream_t s = ex->own_stream;
-    if (push_params(ex, d_frames, s)) return -1;
+    const InputSrc in = fp32_src(d_frames);
+    if (push_params(ex, in, s)) return -1;
     const int n = (int)std::min<size_t>(ex->steps.size(), (size_t)cap);
     std::vector<hipEvent_t> ev(ex->steps.size() + 1);
     for (auto &e : ev) FFGPU_CHECK(hipEventCreate(&e));
     std::vector<float> acc(ex->steps.size(), 0.f);
     const int reps = 5;
-    if (issue_all(ex, d_frames, s)) return -1;
+    if (issue_all(ex, in, s)) return -1;
     for (int r = 0; r < reps; r++) {
         FFGPU_CHECK(hipEventRecord(ev[0], s));
         for (size_t i = 0; i < ex->steps.size(); i++) {
-            if (issue_step(ex, ex->steps[i], d_frames, s)) return -1;
+            if (issue_step(ex, ex->steps[i], in, s)) return -1;
             FFGPU_CHECK(hipEventRecord(ev[i + 1], s));
         }
         FFGPU_CHECK(hipStreamSynchronize(s));

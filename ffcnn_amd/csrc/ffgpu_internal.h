@@ -30,6 +30,14 @@ static inline ffcnn_ext *ffcnn_ext_of(NET *net)
     return e->magic == FFCNN_EXT_MAGIC ? e : (ffcnn_ext *)0;
 }
 
+/* net_input's letterbox (ffcnn.c:267-273): a w x h image fills the top-left sw x sh of the net's W x H plane, aspect kept; the source
+ * pixel of (x, y) is (x s1 / s2, y s1 / s2), and s1 / s2 rescales the boxes */
+static inline void letterbox(int w, int h, int W, int H, int *sw, int *sh, int *s1, int *s2)
+{
+    if ((long)w * H > (long)h * W) { *sw = W; *sh = (int)((long)*sw * h / w); *s1 = w; *s2 = *sw; }
+    else                           { *sh = H; *sw = (int)((long)*sh * w / h); *s1 = h; *s2 = *sh; }
+}
+
 /* implemented in ffgpu_exec.hip */
 void *ffgpu_netdev_create(NET *net);              /* uploads weight_buf; NULL on failure */
 void  ffgpu_netdev_destroy(void *dev);

@@ -350,7 +350,7 @@ static int node_submit_step(ffgpu_node *nd, const float *h_frames, int s, bool *
             }
             FFGPU_CHECK(hipMemcpyAsync(k.d_in[s], src, bytes, hipMemcpyHostToDevice, k.st[s]));
         }
-        if (forward_on(k.ex[s], k.d_in[s], k.st[s])) return -1;
+        if (forward_on(k.ex[s], fp32_src(k.d_in[s]), k.st[s])) return -1;
         if (nd->direct) { FFGPU_CHECK(hipEventRecord(nd->ev_host[s], k.st[s])); return 0; }   // the records are on the host when the step ends
         FFGPU_CHECK(hipEventRecord(k.ev_done[s], k.st[s]));
         FFGPU_CHECK(hipStreamWaitEvent(k.comm_st, k.ev_done[s], 0));
