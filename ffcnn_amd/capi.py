@@ -16,6 +16,7 @@ f32p = C.POINTER(C.c_float)
 
 class FFGPU:
     MAX_DET = 128
+    MERGE_LDS_SLOTS = 1024               # FFGPU_MERGE_LDS_SLOTS: unions up to this many boxes are merged in LDS (ffgpu_merge_tiles_dev)
     KEEP_ALL, COMPAT_V6, NO_GRAPH, NO_FUSE, HOST_DETS, SPLIT2, CONCURRENT, BF16_PW = 1, 2, 4, 8, 16, 32, 64, 128
     K_AUTO, K_GENERIC, K_DW_STREAM, K_DW_LDS, K_PW_MFMA, K_PW_GEMM, _K6, K_DENSE_SMALL, K_IGEMM, K_PW_BF16, K_GROUP_THIN, K_PW_X3, K_CONV_X3, K_PW_X3T = range(14)
 
@@ -57,11 +58,19 @@ class Nv12Frame(C.Structure):        # ffgpu_nv12_frame (40 bytes): one NV12 fra
                 ("matrix", C.c_int), ("reserved", C.c_int)]
 
 
+class Tile(C.Structure):             # ffgpu_tile (16 bytes): batch entry t is a tile of picture `image` (-1: of none) with origin (x0, y0)
+    _fields_ = [("image", C.c_int), ("x0", C.c_int), ("y0", C.c_int), ("reserved", C.c_int)]
+
+
+class TileRect(C.Structure):         # ffgpu_tile_rect: one tile of a plan (ffgpu_tile_plan)
+    _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("w", C.c_int), ("h", C.c_int)]
+
+
 YUV_BT601_LIMITED, YUV_BT601_FULL, YUV_BT709_LIMITED, YUV_BT709_FULL = 0, 1, 2, 3      # FFGPU_YUV_* (ffgpu_nv12_frame.matrix)
 
 assert C.sizeof(LAYER) == 120 and C.sizeof(NET) == 104 and C.sizeof(BBOX) == 24
 assert C.sizeof(FrameDets) == 16 + 24 * FFGPU.MAX_DET
-assert C.sizeof(BgrFrame) == 24 and C.sizeof(Nv12Frame) == 40
+assert C.sizeof(BgrFrame) == 24 and C.sizeof(Nv12Frame) == 40 and C.sizeof(Tile) == 16 and C.sizeof(TileRect) == 16
 
 BOX_DTYPE = np.dtype([("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
 DETS_DTYPE = np.dtype([("count", "<i4"), ("ncand", "<i4"), ("overflow", "<i4"), ("nfull", "<i4"),
@@ -78,7 +87,9 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_exec_profile", "ffgpu_exec_profile_steps", "ffgpu_exec_step_model", "ffgpu_groupconv_dev", "ffgpu_groupconv_kernel_name", "ffgpu_groupconv_time_dev", "ffgpu_irb_dev", "ffgpu_dwpw_dev", "ffgpu_packed_records_bytes", "ffgpu_pack_records", "ffgpu_unpack_records",
            "ffgpu_shard_range", "ffgpu_node_create", "ffgpu_node_destroy", "ffgpu_node_ndev", "ffgpu_node_shard", "ffgpu_node_set_scale",
            "ffgpu_node_input_dev", "ffgpu_node_input_slot_dev", "ffgpu_node_depth", "ffgpu_node_rccl_ranks", "ffgpu_node_forward", "ffgpu_node_forward_host",
-           "ffgpu_node_submit", "ffgpu_node_wait", "ffgpu_node_run"]
+           "ffgpu_node_submit", "ffgpu_node_wait", "ffgpu_node_run",
+           "ffgpu_merge_tiles_scratch_bytes", "ffgpu_merge_tiles_dev", "ffgpu_exec_merge_tiles", "ffgpu_exec_merged_dev", "ffgpu_exec_read_merged",
+           "ffgpu_exec_read_merged_boxes", "ffgpu_tile_plan"]
 # include/ffcnn_hip_diag.h (libffcnn_hip_diag.so: lab equipment, its own library)
 DIAG_EXPORTS = ["ffgpu_membench", "ffgpu_pipe_probe", "ffgpu_pipe_probe2", "ffgpu_pipe_probe3", "ffgpu_mfma_floor", "ffgpu_diag_x3_term", "ffgpu_diag_xl_op", "ffgpu_clock_probe"]
 
@@ -188,6 +199,14 @@ def lib():
     L.ffgpu_unpack_records.argtypes = [vp, i, i, vp]
     L.ffgpu_node_forward.argtypes = [vp, vp]
     L.ffgpu_node_forward_host.argtypes = [vp, f32p, vp]
+    L.ffgpu_merge_tiles_scratch_bytes.restype = sz
+    L.ffgpu_merge_tiles_scratch_bytes.argtypes = [i, i]
+    L.ffgpu_merge_tiles_dev.argtypes = [vp, vp, i, C.POINTER(Tile), i, i, C.c_float, i, vp, vp, vp, sz, vp]
+    L.ffgpu_exec_merge_tiles.argtypes = [vp, C.POINTER(Tile), i, i, vp]
+    L.ffgpu_exec_merged_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
+    L.ffgpu_exec_read_merged.argtypes = [vp, vp, i]
+    L.ffgpu_exec_read_merged_boxes.argtypes = [vp, i, vp, i]
+    L.ffgpu_tile_plan.argtypes = [i] * 7 + [C.POINTER(TileRect), i]
     _lib = L
     return L
 
@@ -478,6 +497,28 @@ class Executor:
         n = _check(lib().ffgpu_exec_read_boxes(self.h, frame, out.ctypes.data, out.size), "ffgpu_exec_read_boxes")
         return out[:n].copy()
 
+    def merge_tiles(self, tiles, nimages, stream=None):
+        """enqueue the merge of the last forward's boxes per picture behind it (ffgpu_exec_merge_tiles): tiles is one (image, x0, y0) per batch
+        entry (image -1: the entry is no tile) or a Tile array"""
+        _check(lib().ffgpu_exec_merge_tiles(self.h, tile_table(tiles), len(tiles), nimages, stream), "ffgpu_exec_merge_tiles")
+        self._cap_merged = self.cand_capacity * len(tiles)
+
+    def merged_dev(self):
+        ptr, nbytes = C.c_void_p(), C.c_size_t()
+        _check(lib().ffgpu_exec_merged_dev(self.h, C.byref(ptr), C.byref(nbytes)), "ffgpu_exec_merged_dev")
+        return ptr.value, nbytes.value
+
+    def read_merged(self, nimages):
+        out = np.zeros(max(1, nimages), DETS_DTYPE)
+        n = _check(lib().ffgpu_exec_read_merged(self.h, out.ctypes.data, nimages), "ffgpu_exec_read_merged")
+        return out[:n]
+
+    def read_merged_boxes(self, image=0):
+        """every box of picture `image` that survived the merge (the merged record keeps the first FFGPU.MAX_DET)"""
+        out = np.zeros(max(1, getattr(self, "_cap_merged", 0)), BOX_DTYPE)
+        n = _check(lib().ffgpu_exec_read_merged_boxes(self.h, image, out.ctypes.data, out.size), "ffgpu_exec_read_merged_boxes")
+        return out[:n].copy()
+
     def read_candidates(self, frame=0):
         out = np.zeros(max(1, self.cand_capacity), BOX_DTYPE)
         n = _check(lib().ffgpu_exec_read_layer(self.h, -2, frame, out.ctypes.data_as(f32p), out.size * 6), "read candidates")
@@ -550,6 +591,40 @@ def nv12_frame_desc(f, matrix=0):
         return (Y.data_ptr(), UV.data_ptr(), w, h, Y.stride(0) if h > 1 else w, UV.stride(0) if UV.shape[0] > 1 else UV.shape[1] & ~1, matrix, 0)
     y, uv, w, h = f[0], f[1], f[2], f[3]
     return (y, uv or 0, w, h, f[4] if len(f) > 4 else 0, f[5] if len(f) > 5 else 0, f[6] if len(f) > 6 else matrix, 0)
+
+
+def tile_table(tiles):
+    """a Tile array from a sequence of (image, x0, y0) tuples (or Tile structures; a Tile array passes through)"""
+    if isinstance(tiles, C.Array):
+        return tiles
+    arr = (Tile * max(1, len(tiles)))()
+    for k, t in enumerate(tiles):
+        arr[k] = t if isinstance(t, Tile) else Tile(t[0], t[1], t[2], 0)
+    return arr
+
+
+def tile_plan(img_w, img_h, tile_w, tile_h, overlap_x=0, overlap_y=0, align=1):
+    """ffgpu_tile_plan: [(x0, y0, w, h)] of the tiles that cover an img_w x img_h picture, rows of tiles left to right, top to bottom"""
+    n = _check(lib().ffgpu_tile_plan(img_w, img_h, tile_w, tile_h, overlap_x, overlap_y, align, None, 0), "ffgpu_tile_plan")
+    out = (TileRect * n)()
+    _check(lib().ffgpu_tile_plan(img_w, img_h, tile_w, tile_h, overlap_x, overlap_y, align, out, n), "ffgpu_tile_plan")
+    return [(r.x0, r.y0, r.w, r.h) for r in out]
+
+
+def tiles_of(img, plan, image=0):
+    """(frames, tiles) for Executor.forward_bgr_frames_dev and Executor.merge_tiles: the plan's crops of an (h, w, 3) uint8 device tensor (views, no copy)"""
+    return [img[y0:y0 + h, x0:x0 + w] for x0, y0, w, h in plan], [(image, x0, y0) for x0, y0, w, h in plan]
+
+
+def merge_tiles_dev(d_records, d_lists, list_stride, tiles, nimages, d_out_records, d_out_lists=None, thresh=0.5, use_min=1,
+                    d_scratch=None, scratch_bytes=0, stream=None):
+    """ffgpu_merge_tiles_dev on device buffers: tiles as Executor.merge_tiles takes them"""
+    _check(lib().ffgpu_merge_tiles_dev(d_records, d_lists, list_stride, tile_table(tiles), len(tiles), nimages, thresh, use_min,
+                                       d_out_records, d_out_lists, d_scratch, scratch_bytes, stream), "ffgpu_merge_tiles_dev")
+
+
+def merge_tiles_scratch_bytes(ntiles, list_stride):
+    return int(lib().ffgpu_merge_tiles_scratch_bytes(ntiles, list_stride))
 
 
 def shard_range(total, rank, world):

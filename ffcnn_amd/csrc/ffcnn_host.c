@@ -443,3 +443,50 @@ void net_profile(NET *net)
     if (ext && ext->profile && ext->dev && getenv("FFCNN_PROFILE_US") && ffgpu_netdev_profile_us(ext->dev, us) == 0)
         for (int k = 0; k < LAYER_TYPE_TOTOAL; k++) printf("%8s: %9.1f us\n", kind_name(k), us[k]);
 }
+
+/* ---- tiled detection: the planner (include/ffcnn_hip.h).  Pure host code.
+ * One axis: a picture of `len` pixels, tiles of `tile`, neighbours overlapping by `overlap`, origins multiples of `align`.  The effective tile
+ * is min(tile, len), one pixel larger when align == 2 and the last origin len - size would be odd.  n tiles have the origins floor(i (len -
+ * size) / (n - 1)) rounded down to a multiple of align: with n - 1 >= (len - size) / (size - overlap) consecutive origins are at most size -
+ * overlap + (align - 1) apart, so neighbours overlap by at least overlap - (align - 1).  Only overlap 0 with align 2 can then leave a one-pixel
+ * gap (origins size + 1 apart); further tiles close it: from (len - size) / (size - 1) steps on the origins are at most `size` apart.  At most
+ * (len - size) / align steps: origins `align` apart, where a large overlap asks for steps below `align`. */
+static int tile_origin(int i, int n, int len, int size, int align)
+{
+    if (n < 2) return 0;
+    const int x = (int)((long long)i * (len - size) / (n - 1));
+    return x - x % align;
+}
+
+static int tile_axis(const char *axis, int len, int tile, int overlap, int align, int *size, int *n)
+{
+    if (len < 1 || tile < 1) { ffgpu_set_error("tile_plan: %s: picture %d, tile %d: sizes must be >= 1", axis, len, tile); return -1; }
+    if (overlap < 0 || overlap >= tile) { ffgpu_set_error("tile_plan: %s: overlap %d must be >= 0 and below the tile size %d", axis, overlap, tile); return -1; }
+    if (align == 2 && tile < 2 && len > tile) { ffgpu_set_error("tile_plan: %s: align 2 needs tiles of at least 2 pixels (even origins of 1-pixel tiles cannot cover a picture)", axis); return -1; }
+    int sz = tile < len ? tile : len;
+    if (align == 2 && ((len - sz) & 1)) sz++;
+    if (sz >= len) { *size = len; *n = 1; return 0; }
+    int cnt = (len - sz + (sz - overlap) - 1) / (sz - overlap) + 1;
+    for (int gap = overlap < align - 1; gap; cnt += gap) {
+        gap = 0;
+        for (int i = 1; i < cnt && !gap; i++) gap = tile_origin(i, cnt, len, sz, align) - tile_origin(i - 1, cnt, len, sz, align) > sz;
+    }
+    if (cnt > (len - sz) / align + 1) cnt = (len - sz) / align + 1;      /* (origins `align` apart are the densest plan: no origin twice) */
+    *size = sz; *n = cnt;
+    return 0;
+}
+
+int ffgpu_tile_plan(int img_w, int img_h, int tile_w, int tile_h, int overlap_x, int overlap_y, int align, ffgpu_tile_rect *out, int cap)
+{
+    int w = 0, h = 0, nx = 0, ny = 0;
+    if (align != 1 && align != 2) { ffgpu_set_error("tile_plan: align %d is neither 1 nor 2", align); return -1; }
+    if (tile_axis("x", img_w, tile_w, overlap_x, align, &w, &nx) || tile_axis("y", img_h, tile_h, overlap_y, align, &h, &ny)) return -1;
+    if ((long long)nx * ny > 0x7fffffffLL) { ffgpu_set_error("tile_plan: %d x %d tiles is too many", nx, ny); return -1; }
+    if (cap > 0 && !out) { ffgpu_set_error("tile_plan: NULL output"); return -1; }
+    for (int k = 0; k < nx * ny && k < cap; k++) {
+        out[k].x0 = tile_origin(k % nx, nx, img_w, w, align);
+        out[k].y0 = tile_origin(k / nx, ny, img_h, h, align);
+        out[k].w = w; out[k].h = h;
+    }
+    return nx * ny;
+}

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <vector>
 #include "ffgpu_internal.h"
 
 #define FFGPU_CHECK(expr)                                                                   \
@@ -152,3 +153,11 @@ int ffgpu_launch_nms(const BBOX *cand, const int *cand_key, int *ncand, int cap,
 #define FFGPU_NMS_LDS_CAP 8192
 bool ffgpu_nms_in_lds(int cap_pow2);      // the work arrays of cap_pow2 slots fit the CURRENT device's LDS (else: global scratch, 13 bytes per slot and frame)
 int ffgpu_launch_clear(int *ncand, int N, int *ring_ctr, hipStream_t s);
+
+// tiled detection (ffgpu_merge.inc): the caller's tile table as the CSR k_merge_tiles reads (checked entry by entry; off receives the pictures' offsets),
+// its upload in stream order (ints by value as kernel arguments), and the merge of the tiles' records / lists per picture
+int    ffgpu_merge_build_tab(const char *what, const ffgpu_tile *tiles, int ntiles, int nimages, std::vector<int> &tab, std::vector<int> *off);
+size_t ffgpu_merge_tab_bytes(int ntiles);
+int    ffgpu_launch_set_ints(int *d_dst, const int *h_src, int n, hipStream_t s);
+int    ffgpu_launch_merge_tiles(const int *d_tab, const std::vector<int> &tab, const ffgpu_frame_dets *recs, const BBOX *lists, int stride,
+                                float thresh, int use_min, ffgpu_frame_dets *out_recs, BBOX *out_lists, void *scratch, hipStream_t s);

@@ -239,6 +239,10 @@ struct ffgpu_exec {
     FrameDesc *d_ftab = nullptr;
     std::vector<FrameDesc> ftab_sent; hipStream_t ftab_stream = nullptr;      // what d_ftab holds (or will, on ftab_stream)
     float *h_stage = nullptr;          // ffgpu_exec_forward_host from caller memory: page-locked staging of one batch (on first use)
+    // ffgpu_exec_merge_tiles (allocated by the first call): merged records and full lists (picture g's list at cand_cap x mrg_off[g]), the work arrays
+    // of unions beyond LDS, and the device tile table with what it holds (or will, on mtab_stream)
+    ffgpu_frame_dets *d_merged = nullptr; BBOX *d_merged_full = nullptr; void *d_merge_scratch = nullptr; int *d_mtab = nullptr;
+    std::vector<int> mtab_sent, mrg_off; hipStream_t mtab_stream = nullptr;
     ffgpu_frame_dets *ring = nullptr; int ring_slots = 0; int *d_ringctr = nullptr;   // ffgpu_exec_set_ring
     int ring_stride = 0;               // records per ring slot (the parent's batch for the halves of a split executor)
     static constexpr int MAXPART = 8;
@@ -1046,6 +1050,7 @@ extern "C" void ffgpu_exec_destroy(ffgpu_exec *ex)
     (void)hipFree(ex->arena); (void)hipFree(ex->d_input); (void)hipFree(ex->d_pack); (void)hipFree(ex->d_cand);
     (void)hipFree(ex->d_cand_key); (void)hipFree(ex->d_ncand); (void)hipFree(ex->d_dets);
     (void)hipFree(ex->d_full); (void)hipFree(ex->d_prm); (void)hipFree(ex->d_nms_scratch); (void)hipFree(ex->d_ftab);
+    (void)hipFree(ex->d_merged); (void)hipFree(ex->d_merged_full); (void)hipFree(ex->d_merge_scratch); (void)hipFree(ex->d_mtab);
     if (ex->h_dets) (void)hipHostFree(ex->h_dets);
     if (ex->h_stage) (void)hipHostFree(ex->h_stage);
     (void)hipFree(ex->d_ringctr);
@@ -1346,6 +1351,82 @@ extern "C" int ffgpu_exec_read_boxes(ffgpu_exec *ex, int frame, BBOX *host_out, 
     if (copy_d2h(&nfull, &ex->d_dets[frame].nfull, sizeof(int))) return -1;
     const int n = std::min(nfull, cap);
     if (n > 0 && copy_d2h(host_out, ex->d_full + (size_t)frame * ex->cand_cap, sizeof(BBOX) * (size_t)n)) return -1;
+    return nfull;
+}
+
+// -------------------------------------------------------------------------- tiled detection (include/ffcnn_hip.h; kernel: ffgpu_merge.inc)
+// A post-pass behind the forward on the forward's stream: reads the records and full lists k_nms left (a split executor's parent owns both), writes
+// buffers of its own.  The table is uploaded in front of the merge unless the device table holds (or will hold, on this stream) these values already.
+extern "C" int ffgpu_exec_merge_tiles(ffgpu_exec *ex, const ffgpu_tile *tiles, int ntiles, int nimages, void *stream)
+{
+    int ndev = 0;
+    if (!ex && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)) {
+        (void)hipGetLastError();
+        ffgpu_set_error("merge_tiles: no HIP device visible: libffcnn_hip has no CPU fallback");
+        return -1;
+    }
+    if (!alive(ex, "merge_tiles")) return -1;
+    if (!tiles) { ffgpu_set_error("merge_tiles: NULL tile table"); return -1; }
+    if (ntiles != ex->N) { ffgpu_set_error("merge_tiles: %d tiles for an executor of batch %d", ntiles, ex->N); return -1; }
+    const hipStream_t s = stream ? (hipStream_t)stream : ex->own_stream;
+    if (s != ex->last_stream) { ffgpu_set_error("merge_tiles: the merge must be enqueued on the stream of the forward it follows"); return -1; }
+    std::vector<int> tab, off;
+    if (ffgpu_merge_build_tab("merge_tiles", tiles, ntiles, nimages, tab, &off)) return -1;
+    if (!ex->d_merged) {
+        const size_t n = (size_t)ex->N, cap = (size_t)ex->cand_cap;
+        const size_t work = ffgpu_merge_tiles_scratch_bytes(ex->N, ex->cand_cap) - ffgpu_merge_tab_bytes(ex->N);
+        if (hipMalloc(&ex->d_merged_full, sizeof(BBOX) * cap * n) != hipSuccess || hipMalloc(&ex->d_merge_scratch, work) != hipSuccess ||
+            hipMalloc(&ex->d_mtab, ffgpu_merge_tab_bytes(ex->N)) != hipSuccess || hipMalloc(&ex->d_merged, sizeof(ffgpu_frame_dets) * n) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(ex->d_merged_full); (void)hipFree(ex->d_merge_scratch); (void)hipFree(ex->d_mtab);
+            ex->d_merged_full = nullptr; ex->d_merge_scratch = nullptr; ex->d_mtab = nullptr; ex->d_merged = nullptr;
+            ffgpu_set_error("merge_tiles: out of device memory for the merge buffers");
+            return -1;
+        }
+    }
+    if (!(ex->mtab_stream == s && ex->mtab_sent == tab)) {
+        ex->mtab_sent.clear();
+        if (ffgpu_launch_set_ints(ex->d_mtab, tab.data(), (int)tab.size(), s)) return -1;
+        ex->mtab_sent = tab; ex->mtab_stream = s;
+    }
+    ex->mrg_off = off;
+    return ffgpu_launch_merge_tiles(ex->d_mtab, tab, ex->d_dets, ex->d_full, ex->cand_cap, 0.5f, 1, ex->d_merged, ex->d_merged_full, ex->d_merge_scratch, s);
+}
+
+static bool merged_ok(const ffgpu_exec *ex, const char *what)
+{
+    if (!ex) { ffgpu_set_error("%s: NULL executor", what); return false; }
+    if (!ex->d_merged || ex->mrg_off.empty()) { ffgpu_set_error("%s: no ffgpu_exec_merge_tiles has run on this executor", what); return false; }
+    return true;
+}
+
+extern "C" int ffgpu_exec_merged_dev(ffgpu_exec *ex, void **dev_ptr, size_t *bytes)
+{
+    if (!merged_ok(ex, "merged_dev")) return -1;
+    if (dev_ptr) *dev_ptr = ex->d_merged;
+    if (bytes) *bytes = sizeof(ffgpu_frame_dets) * (ex->mrg_off.size() - 1);
+    return 0;
+}
+
+extern "C" int ffgpu_exec_read_merged(ffgpu_exec *ex, ffgpu_frame_dets *host_out, int max_images)
+{
+    if (!merged_ok(ex, "read_merged")) return -1;
+    if (!host_out) { ffgpu_set_error("read_merged: NULL argument"); return -1; }
+    const int n = std::max(0, std::min(max_images, (int)ex->mrg_off.size() - 1));
+    FFGPU_CHECK(hipStreamSynchronize(ex->last_stream));
+    if (n > 0 && copy_d2h(host_out, ex->d_merged, sizeof(ffgpu_frame_dets) * (size_t)n)) return -1;
+    return n;
+}
+
+extern "C" int ffgpu_exec_read_merged_boxes(ffgpu_exec *ex, int image, BBOX *host_out, int cap)
+{
+    if (!merged_ok(ex, "read_merged_boxes")) return -1;
+    if (image < 0 || image >= (int)ex->mrg_off.size() - 1 || cap < 0 || (cap > 0 && !host_out)) { ffgpu_set_error("read_merged_boxes: bad arguments"); return -1; }
+    FFGPU_CHECK(hipStreamSynchronize(ex->last_stream));
+    int nfull = 0;
+    if (copy_d2h(&nfull, &ex->d_merged[image].nfull, sizeof(int))) return -1;
+    const int n = std::min(nfull, cap);
+    if (n > 0 && copy_d2h(host_out, ex->d_merged_full + (size_t)ex->cand_cap * ex->mrg_off[image], sizeof(BBOX) * (size_t)n)) return -1;
     return nfull;
 }
 

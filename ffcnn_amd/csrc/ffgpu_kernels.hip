@@ -670,3 +670,5 @@ extern "C" int ffgpu_pack_records(const void *d_records, int nslots, long slot_s
     return 0;
 }
 
+#include "ffgpu_merge.inc"
+

@@ -330,6 +330,71 @@ size_t ffgpu_packed_records_bytes(int batch, int cap);
 int    ffgpu_unpack_records(const void *block, int batch, int cap, ffgpu_frame_dets *out);
 int    ffgpu_pack_records(const void *d_records, int nslots, long slot_stride_records, int batch, int cap, void *d_out, void *stream);
 
+/* ---- tiled detection: the boxes of the tiles of a large picture merged on the device --------------------------------------------------
+ * The net sees 320x320; a 1080p or 4K picture letterboxed down to it loses every small object.  The remedy is to cut the picture into
+ * overlapping tiles and run the tiles as one batch: a tile is a frame descriptor (ffgpu_bgr_frame / ffgpu_nv12_frame) whose address is
+ * bgr + y0 * pitch + 3 * x0 with the picture's pitch -- no copy.  What follows moves the tiles' boxes back into picture coordinates and
+ * suppresses the duplicates the overlaps and the tile borders produce, without a host round trip.
+ *
+ * Batch entry t may be declared a tile of picture image[t] with origin (x0[t], y0[t]).  Its survivors are the forward's full post-NMS
+ * list (nfull boxes in score order, in the tile's source pixels: what ffgpu_exec_read_boxes returns).  The merged result of picture g:
+ *   1. every survivor of every tile of g is translated: x1 += (float)x0, x2 += (float)x0, y1 += (float)y0, y2 += (float)y0 (one fp32
+ *      addition per coordinate, no FMA contraction);
+ *   2. the union is ordered by score descending, then position of the tile in the caller's table ascending, then index in the tile's
+ *      list ascending (a total order: identical pixels under two tiles give exact score ties);
+ *   3. the greedy class-aware suppression of ffcnn.c:298-322 runs on it with the arithmetic of the forward's own NMS: area =
+ *      (x2 - x1) * (y2 - y1), a box goes when metric > thresh, a suppressed box never suppresses another;
+ *   4. the survivors are written in that order, not rescaled.
+ * The merged record is an ffgpu_frame_dets: count = min(nfull, FFGPU_MAX_DET), nfull = survivors of the merge, ncand = sum of the tiles'
+ * ncand, overflow bit 0 = OR of the tiles' bit 0, bit 2 = nfull > FFGPU_MAX_DET, unused box slots zero.
+ * This is TWO-STAGE NMS -- per tile, then across tiles -- and deliberately not NMS over the union of the raw candidates.  With the
+ * reference's metric (intersection / min area, ffcnn.c:316,519) a partial box cut off by a tile border lies inside the whole box the
+ * neighbouring tile sees and scores near 1 against it.  A picture with one tile at (0, 0) gives that entry's own record; listing a tile
+ * twice changes nothing; a picture without boxes (or without tiles) gives a zero record.  Boxes are not clipped to the picture. */
+typedef struct {
+    int image;                  /* 0 .. nimages-1, or -1: this batch entry is no tile (ignored) */
+    int x0, y0;                 /* tile origin in the picture, >= 0 */
+    int reserved;               /* 0 */
+} ffgpu_tile;                   /* 16 bytes */
+
+#define FFGPU_MERGE_LDS_SLOTS 1024   /* a picture whose tiles hold at most this many boxes together is merged in LDS (the normal case: tens); */
+                                     /* a larger union is merged in the global scratch buffer: correct, not fast                             */
+
+/* The operator, on device records and lists with no executor (like ffgpu_pack_records).  d_records: ntiles ffgpu_frame_dets; d_lists: tile
+ * t's nfull boxes at box t * list_stride (nfull <= list_stride), or NULL: the records' own box[0 .. count).  tiles: HOST array, free on
+ * return.  d_out_records: nimages records.  d_out_lists (may be NULL): the full list of picture g starts at box list_stride x (number of
+ * tiles of pictures < g) -- FFGPU_MAX_DET takes list_stride's place when d_lists is NULL -- and has room for all of its tiles' boxes.
+ * d_scratch (16-byte aligned, ffgpu_merge_tiles_scratch_bytes(ntiles, list_stride) bytes) may be NULL when no picture CAN exceed the LDS
+ * slots (tiles of the picture x list_stride <= FFGPU_MERGE_LDS_SLOTS) and the table has at most 220 tiles; otherwise the call fails, with
+ * a message, before anything is launched.  Enqueued on `stream` without synchronising.  Rejected with the entry's index in the message:
+ * image outside -1 .. nimages-1, a negative origin, reserved != 0; also nimages < 1 or > ntiles and a NULL table. */
+size_t ffgpu_merge_tiles_scratch_bytes(int ntiles, int list_stride);
+int    ffgpu_merge_tiles_dev(const void *d_records, const void *d_lists, int list_stride, const ffgpu_tile *tiles, int ntiles, int nimages,
+                             float thresh, int use_min, void *d_out_records, void *d_out_lists, void *d_scratch, size_t scratch_bytes, void *stream);
+
+/* On an executor: enqueues the merge of the last forward's records and full lists behind it on `stream` (NULL = the executor's own; it
+ * must be the stream of that forward), with the net's own setting (threshold 0.5, min-area metric).  ntiles == batch.  A post-pass: the
+ * captured graph, the per-entry records and their ring / host mirror are untouched.  The tile table reaches the device in stream order
+ * as a kernel argument, skipped while the table is unchanged on that stream: a steady tiling costs ONE extra launch per forward.  Buffers
+ * belong to the executor (allocated by the first call).  Works on FFGPU_SPLIT2 executors.  A rejected call leaves the executor usable. */
+int ffgpu_exec_merge_tiles(ffgpu_exec *ex, const ffgpu_tile *tiles, int ntiles, int nimages, void *stream);
+/* the merged records on the device: `nimages` of the last merge (valid once it has completed) */
+int ffgpu_exec_merged_dev(ffgpu_exec *ex, void **dev_ptr, size_t *bytes);
+/* synchronise like ffgpu_exec_read_dets / ffgpu_exec_read_boxes and copy: the merged records (returns how many), ALL merged boxes of one
+ * picture (copies min(nfull, cap), returns nfull) */
+int ffgpu_exec_read_merged(ffgpu_exec *ex, ffgpu_frame_dets *host_out, int max_images);
+int ffgpu_exec_read_merged_boxes(ffgpu_exec *ex, int image, BBOX *host_out, int cap);
+
+/* The planner: pure host code, usable without a device (like ffgpu_shard_range).  Cuts an img_w x img_h picture into a grid of equal
+ * tiles (rows of tiles, left to right, top to bottom) and returns their number -- also when `cap` is too small: the first `cap` are
+ * written -- or -1.  Every tile has the same effective size min(tile, image), one pixel larger where align == 2 needs it; every tile lies
+ * inside the picture, together they cover it, neighbours overlap by at least overlap - (align - 1) pixels, every origin is a multiple
+ * of `align` (use 2 for NV12, whose chroma phase cannot shift by one pixel), the first tile starts at 0 and the last ends at the picture's
+ * edge; the same arguments always give the same plan.  Rejected: sizes < 1, overlap < 0 or >= the tile size, align not 1 or 2, and align
+ * 2 with a tile 1 pixel wide (high) in a wider (higher) picture, which even origins cannot cover. */
+typedef struct { int x0, y0, w, h; } ffgpu_tile_rect;
+int ffgpu_tile_plan(int img_w, int img_h, int tile_w, int tile_h, int overlap_x, int overlap_y, int align, ffgpu_tile_rect *out, int cap);
+
 #ifdef __cplusplus
 }
 #endif
