@@ -150,6 +150,7 @@ struct Step {
     ConvDesc conv;           // S_CONV (in == nullptr: patched to the batch input at launch); S_DWPW: the depthwise layer
     ConvDesc conv2;          // S_DWPW: the pointwise layer behind it
     bool     in_is_input;    // S_CONV / S_POOL / S_UPSAMPLE / S_TOCNHW read the batch input
+    bool     b_is_input;     // S_ADD: the `from` side is the batch input
     const float *a, *b;      // generic sources
     float   *out;
     long     n;              // element count (ADD/COPY) or planes
@@ -307,7 +308,7 @@ static int plan(ffgpu_exec *ex)
         case LAYER_TYPE_DROPOUT: canon[i] = src_tensor(i - 1); break;
         case LAYER_TYPE_YOLO: canon[i] = -2; break;
         case LAYER_TYPE_ROUTE:
-            canon[i] = (ll[i].depend_num == 1 && src_tensor(ll[i].depend_list[0]) >= 0) ? src_tensor(ll[i].depend_list[0]) : i;
+            canon[i] = (ll[i].depend_num == 1 && src_tensor(ll[i].depend_list[0]) >= -1) ? src_tensor(ll[i].depend_list[0]) : i;     // (-1: an alias of the net input)
             break;
         default: canon[i] = i;
         }
@@ -561,20 +562,25 @@ static int plan(ffgpu_exec *ex)
             break; }
         case LAYER_TYPE_AVGPOOL: case LAYER_TYPE_MAXPOOL: case LAYER_TYPE_UPSAMPLE: case LAYER_TYPE_SHORTCUT: {
             const float *src = in_ptr(i, &from_input);
-            if (from_input && N > 1) {          // needs CNHW order: convert the input once
+            // a shortcut whose OTHER side is the net input (from = a dropout in front of every other layer)
+            const bool b_input = a.type == LAYER_TYPE_SHORTCUT && src_tensor(a.depend_list[0]) == -1;
+            if (a.type == LAYER_TYPE_SHORTCUT && src_tensor(a.depend_list[0]) < -1) { bad_chain = true; break; }
+            if ((from_input || b_input) && N > 1) {          // needs CNHW order: convert the input once
                 if (!cnhw_input) {
-                    if (hipMalloc(&cnhw_input, (size_t)a.w * a.h * a.c * N * sizeof(float)) != hipSuccess) { ffgpu_set_error("hipMalloc failed"); return -1; }
-                    Step cv{}; cv.kind = S_TOCNHW; cv.layer = -1; cv.ltype = a.type; cv.out = cnhw_input; cv.c = a.c; cv.w = a.w; cv.h = a.h; cv.in_is_input = true;
+                    const LAYER &l0 = ll[0];
+                    if (hipMalloc(&cnhw_input, (size_t)l0.w * l0.h * l0.c * N * sizeof(float)) != hipSuccess) { ffgpu_set_error("hipMalloc failed"); return -1; }
+                    Step cv{}; cv.kind = S_TOCNHW; cv.layer = -1; cv.ltype = a.type; cv.out = cnhw_input; cv.c = l0.c; cv.w = l0.w; cv.h = l0.h; cv.in_is_input = true;
                     S.push_back(cv);
                 }
-                src = cnhw_input; from_input = false;
+                if (from_input) { src = cnhw_input; from_input = false; }
             }
             st.in_is_input = from_input;
             st.a = src;
             if (a.type == LAYER_TYPE_SHORTCUT) {
                 if (canon[i - 1] == i) break;                       // absorbed by the producing conv
                 st.kind = S_ADD;
-                st.b = tensor_ptr(ex, src_tensor(a.depend_list[0]));
+                st.b = b_input ? cnhw_input : tensor_ptr(ex, src_tensor(a.depend_list[0]));      // (batch 1: patched to the frames at launch)
+                st.b_is_input = b_input && N == 1;
                 st.out = tensor_ptr(ex, canon[i]);
                 st.n = out_floats(i); st.flag = a.activation;
             } else {
@@ -676,7 +682,7 @@ static int plan(ffgpu_exec *ex)
     // of every darknet cfg: dense KxK from 3 channels): the captured graph is then independent of the input buffer
     ex->indirect = true;
     for (const Step &st : S)
-        if (st.in_is_input && !(st.kind == S_FRONT || (st.kind == S_CONV && ffgpu_conv_supports_ind(st.conv)))) ex->indirect = false;
+        if (st.b_is_input || (st.in_is_input && !(st.kind == S_FRONT || (st.kind == S_CONV && ffgpu_conv_supports_ind(st.conv))))) ex->indirect = false;
     if (getenv("FFGPU_NO_INDIRECT") && atoi(getenv("FFGPU_NO_INDIRECT"))) ex->indirect = false;      // tests: the keyed fallback
     if (ex->indirect)
         for (Step &st : S) if (st.in_is_input) st.conv.in_ind = reinterpret_cast<const float *const *>(ex->d_prm);   // &d_prm->frames
@@ -733,7 +739,7 @@ static int issue_step(ffgpu_exec *ex, const Step &st, const InputSrc &in, hipStr
     case S_UPSAMPLE:
         return ffgpu_launch_upsample(st.in_is_input ? d_frames : st.a, st.out, (long)ex->N * st.c, st.w, st.h, st.stride, s);
     case S_ADD:
-        return ffgpu_launch_add_act(st.in_is_input ? d_frames : st.a, st.b, st.out, st.n, st.flag, s);
+        return ffgpu_launch_add_act(st.in_is_input ? d_frames : st.a, st.b_is_input ? d_frames : st.b, st.out, st.n, st.flag, s);
     case S_COPY:
         return ffgpu_launch_copy(st.a, st.out, st.n, s);
     case S_TOCNHW: {

@@ -139,9 +139,11 @@ __global__ void __launch_bounds__(256) k_spp(SppP p)
     for (long pl0 = (long)blockIdx.x * NP; pl0 < p.planes; pl0 += (long)gridDim.x * NP) {
         const int np = (int)min((long)NP, p.planes - pl0);
         __syncthreads();
-        for (int i = threadIdx.x; i < np * hw; i += blockDim.x) cur[i] = p.in[pl0 * hw + i];
-        __syncthreads();
-        if (!p.cascade) {
+        int nan_seen = 0;
+        for (int i = threadIdx.x; i < np * hw; i += blockDim.x) { const float t = p.in[pl0 * hw + i]; cur[i] = t; nan_seen |= t != t; }
+        // the reference's scan (ffcnn.c:354-372) gives NaN exactly where the clipped window's FIRST element is NaN and skips every other
+        // NaN; the cascade below would leave a NaN where it was.  Planes that hold one take the scan itself (the same for the whole workgroup).
+        if (__syncthreads_or(nan_seen) || !p.cascade) {
             for (int i = threadIdx.x; i < np * hw; i += blockDim.x) {
                 const int q = i / hw, r = i - q * hw, oy = r / p.w, ox = r - oy * p.w;
                 for (int k = 0; k < p.n; k++) {
@@ -521,7 +523,9 @@ int ffgpu_launch_spp(const float *in, float *const out[3], const int fs[3], int 
     for (int k = 0; k < 3; k++) { p.out[k] = k < n ? out[k] : nullptr; p.fs[k] = k < n ? fs[k] : 1; }
     p.cascade = 1;
     for (int k = 0, prev = 1; k < n; prev = fs[k], k++) if (!(fs[k] & 1) || fs[k] <= prev) p.cascade = 0;
-    hipLaunchKernelGGL(k_spp, dim3((unsigned)std::min((planes + 1) / 2, 4096L)), dim3(256), (size_t)4 * w * h * sizeof(float), s, p);
+    const size_t lds = (size_t)4 * w * h * sizeof(float);           // two planes + the row-pass copy of both: up to 128 KB
+    if (lds_allow((const void *)k_spp, lds, "spp")) return -1;
+    hipLaunchKernelGGL(k_spp, dim3((unsigned)std::min((planes + 1) / 2, 4096L)), dim3(256), lds, s, p);
     LAUNCH_OK("spp");
     return 0;
 }
