@@ -18,10 +18,7 @@
 #include "ffgpu_dw_pair.inc"
 #include "ffgpu_conv_thin.inc"
 
-// Scratch for BARE single-layer calls of the kernels that want a packed weight image (tests, tools, the conv.h drop-in; executors
-// carry plan-time images): per host thread and per DEVICE -- one thread may drive several GPUs -- grown on demand.  The image is
-// rebuilt on the call's stream before the kernel; two bare calls of one thread on DIFFERENT streams are not ordered against
-// each other.
+// Scratch for the packed weight image of a BARE single-layer call (conv_image): per host thread and per DEVICE -- one thread may drive several GPUs -- grown on demand
 struct BareScratch {
     float *p = nullptr; size_t n = 0; int dev = -1;
     float *get(size_t need)
@@ -41,6 +38,41 @@ static int env_int(const char *name, int dflt)
 {
     const char *v = getenv(name);
     return v && *v ? atoi(v) : dflt;
+}
+
+// CUs of the current device (a node plans on every GPU of the box), asked once per device and process (ADVICE r05: no runtime query per launch); 256 if the runtime does not say
+static int device_cus()
+{
+    static int cu_of[64];
+    static std::mutex cu_mu;
+    int dev = 0, cus = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lk(cu_mu);
+    if (dev >= 0 && dev < 64) {
+        if (!cu_of[dev]) (void)hipDeviceGetAttribute(&cu_of[dev], hipDeviceAttributeMultiprocessorCount, dev);
+        cus = cu_of[dev];
+    } else (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return cus > 0 ? cus : 256;
+}
+
+// m with i / dv == __umulhi(i, m) for 32-bit i (exact while i * dv < 2^32): ceil(2^32 / dv), dv >= 1.  A divisor of 1 has no 32-bit m (2^32
+// wraps to 0, which the earlier copies reached with and without saying so): k_conv_igemm, k_conv_first and k_dw_lds read m == 0 as "divisor 1, the
+// quotient is i"; k_dw_pair multiplies unconditionally and never gets one (dw_pair_ok: every divisor is >= 2).
+static unsigned umulhi_magic(long dv) { return dv == 1 ? 0u : (unsigned)(((1ULL << 32) + (unsigned long long)dv - 1) / (unsigned long long)dv); }
+
+// Pixel tiles of the two tiled pointwise GEMMs (k_pw_gemm32, k_pw_x3t): main tiles of 128 pixels, then narrow ones of 64 over the rest.  The narrow
+// ones take over the partial last round: with `slots` workgroups resident, (tiles % slots) main tiles would run alone at the end.
+static void split_main_narrow(long P, int ntm, int slots, bool narrow_on, long *ntn_main, long *ntn_narrow)
+{
+    const long ntn_all = (P + 127) / 128, total_all = ntn_all * ntm;
+    long tail_tiles = total_all % slots;                           // main tiles of the partial round
+    if (total_all <= slots / 2) tail_tiles = total_all;            // a launch that never fills the chip: all narrow
+    else if (tail_tiles > slots * 5 / 8) tail_tiles = 0;           // a nearly full round: leave it
+    if (!narrow_on) tail_tiles = 0;
+    const long tail_ntn = (tail_tiles + ntm - 1) / ntm;            // pixel tiles handed to the narrow form
+    *ntn_main = ntn_all - tail_ntn;
+    const long npx_narrow = P - *ntn_main * 128;
+    *ntn_narrow = npx_narrow > 0 ? (npx_narrow + 63) / 64 : 0;
 }
 
 static bool conv_cnhw_contiguous(const ConvDesc &d)
@@ -139,7 +171,6 @@ static bool dw_pair_ok(const ConvDesc &d)
 static int launch_dw_pair(const ConvDesc &d, hipStream_t s)
 {
     constexpr int BR = 5;
-    auto magic = [](long dv) { return (unsigned)(((1ULL << 32) + (unsigned long long)dv - 1) / (unsigned long long)dv); };     // dv >= 2 (dw_pair_ok)
     DwPairP p;
     p.in = d.in; p.filt = d.filt; p.out = d.out;
     p.W = d.iw; p.H = d.ih; p.N = d.N; p.rowlen = conv_k4(d) + 4;
@@ -156,7 +187,7 @@ static int launch_dw_pair(const ConvDesc &d, hipStream_t s)
     const int nb = (d.N + NI - 1) / NI;
     NI = (d.N + nb - 1) / nb;
     p.NI = NI;
-    p.m_tpi = magic(p.TPI); p.m_quads = magic(p.quads); p.m_hwq = magic((long)p.H * p.WQ); p.m_wq = magic(p.WQ);
+    p.m_tpi = umulhi_magic(p.TPI); p.m_quads = umulhi_magic(p.quads); p.m_hwq = umulhi_magic((long)p.H * p.WQ); p.m_wq = umulhi_magic(p.WQ);      // every divisor >= 2 (dw_pair_ok)
     const size_t lds = (size_t)NI * plane2 * sizeof(float);
     const dim3 grid((unsigned)nb, (unsigned)(d.ic / 2));
     if (vec == 4) hipLaunchKernelGGL((k_dw_pair<5, BR, 4>), grid, dim3(256), lds, s, p);
@@ -220,21 +251,6 @@ static int igemm_split(const ConvDesc &d)
     while (S < 8 && tiles * (S + 1) <= env_int("FFGPU_IGEMM_SPLIT_SLOTS", 768) && nchunks / (S + 1) >= 4) S++;
     if (f >= 1 && f <= 16) S = std::min(f, std::max(1, nchunks));
     return S;
-}
-// (for the layers AUTO gives to k_conv_x3 the plan-frozen number is that kernel's MT: the packed image is laid out for it)
-static bool ig_x3_auto(const ConvDesc &d);
-static int  ig_x3_mt_plan(const ConvDesc &d);
-static int conv_pick(const ConvDesc &d, int variant);
-// Plan-time freeze (executors; ADVICE r04): the kernel AUTO picks NOW, and the two numbers that shape its packed image.  Everything that sizes, fills
-// or reads ConvDesc::wpack goes through conv_pick(d, AUTO), which returns d.kernel once it is set.
-void ffgpu_conv_plan(ConvDesc &d)
-{
-    d.kernel = 0; d.nsplit = 0; d.x3_mt = 0;
-    const int k = conv_pick(d, FFGPU_K_AUTO);
-    if (k == FFGPU_K_IGEMM) d.nsplit = igemm_split(d);
-    if (k == FFGPU_K_CONV_X3) d.x3_mt = ig_x3_mt_plan(d);
-    if (k == FFGPU_K_PW_X3T) d.x3_mt = pwx3t_rb_env();
-    d.kernel = k;
 }
 static size_t igemm_part_floats(const ConvDesc &d) { const int S = igemm_split(d); return S > 1 ? (size_t)S * d.oc * d.N * d.oh * d.ow : 0; }      // (every group's parts: the groups run in one grid)
 static void igemm_dims(const ConvDesc &d, int &WM, int &nchunks, int &ntm, int &img)
@@ -321,29 +337,16 @@ static int conv_pick(const ConvDesc &d, int variant)
     return FFGPU_K_GENERIC;
 }
 
-bool ffgpu_conv_supports_ind(const ConvDesc &d)
+// Plan-time freeze (executors; ADVICE r04): the kernel AUTO picks NOW, and the two numbers that shape its packed image (for k_conv_x3 and k_pw_x3t the
+// tile form the image is laid out for).  Everything that sizes, fills or reads ConvDesc::wpack goes through conv_pick(d, AUTO), which returns d.kernel once it is set.
+void ffgpu_conv_plan(ConvDesc &d)
 {
+    d.kernel = 0; d.nsplit = 0; d.x3_mt = 0;
     const int k = conv_pick(d, FFGPU_K_AUTO);
-    return k == FFGPU_K_GENERIC || k == FFGPU_K_DENSE_SMALL || k == FFGPU_K_IGEMM || k == FFGPU_K_GROUP_THIN;
-}
-
-const char *ffgpu_conv_kernel_name(const ConvDesc &d, int variant)
-{
-    switch (conv_pick(d, variant)) {
-    case FFGPU_K_GENERIC: return "conv_generic";
-    case FFGPU_K_DW_STREAM: return dw_stream_ok(d) ? "dw3_stream" : "unsupported";
-    case FFGPU_K_PW_MFMA: return pw_mfma_ok(d) ? "pw_mfma" : "unsupported";
-    case FFGPU_K_DW_LDS: return dw_lds_ok(d) ? "dw_lds" : "unsupported";
-    case FFGPU_K_PW_GEMM: return pw_gemm_ok(d) ? "pw_gemm" : "unsupported";
-    case FFGPU_K_PW_BF16: return pw_gemm_ok(d) ? "pw_bf16" : "unsupported";
-    case FFGPU_K_PW_X3: return pw_x3_ok(d) ? "pw_x3" : "unsupported";
-    case FFGPU_K_PW_X3T: return pw_x3t_ok(d) ? "pw_x3t" : "unsupported";
-    case FFGPU_K_DENSE_SMALL: return dense_small_ok(d) ? "conv_dense8" : "unsupported";
-    case FFGPU_K_IGEMM: return igemm_ok(d) ? "conv_igemm" : "unsupported";
-    case FFGPU_K_CONV_X3: return ig_x3_ok(d) ? (d.fs == 1 ? "pw_x3s" : "conv_x3") : "unsupported";
-    case FFGPU_K_GROUP_THIN: return group_thin_ok(d) ? "conv_thin" : "unsupported";
-    default: return "unsupported";
-    }
+    if (k == FFGPU_K_IGEMM) d.nsplit = igemm_split(d);
+    if (k == FFGPU_K_CONV_X3) d.x3_mt = ig_x3_mt_plan(d);
+    if (k == FFGPU_K_PW_X3T) d.x3_mt = pwx3t_rb_env();
+    d.kernel = k;
 }
 
 template <int NV, int U, bool NT>
@@ -354,7 +357,7 @@ static void dw_stream_launch(const DwStreamP &p, hipStream_t s)
     hipLaunchKernelGGL((k_dw3_stream<NV, U, NT>), dim3((unsigned)blocks), dim3(256), (size_t)lds, s, p);
 }
 
-static int launch_dw_stream(const ConvDesc &d, hipStream_t s)
+static int launch_dw_stream(const ConvDesc &d, const float *, hipStream_t s)
 {
     // defaults from the sweep in profiles/r01_dw3_tuning.txt: 4-row tasks walked in address order keep the
     // chip-wide access window compact (5.95 TB/s vs 4.95 TB/s for one long stream per wave)
@@ -424,14 +427,14 @@ static int pw_ot(int oc, long nstrips)
     return ot;
 }
 
-static int launch_pw_mfma(const ConvDesc &d, hipStream_t s)
+static int launch_pw_mfma(const ConvDesc &d, const float *image, hipStream_t s)
 {
     PwP p;
     p.in = d.in; p.filt = d.filt; p.out = d.out; p.residual = d.residual;
     p.P = (long)d.N * d.iw * d.ih; p.ic = d.ic; p.oc = d.oc; p.k4 = (d.ic + 3) & ~3;
     p.act = d.act; p.res_act = d.res_act;
     p.nstrips = (p.P + 63) / 64;
-    p.wpack = d.wpack;
+    p.wpack = image;                     // (none: the kernel builds its LDS image from the filter rows)
     const int OT = pw_ot(d.oc, p.nstrips), ocblocks = (d.oc + OT * 16 - 1) / (OT * 16);
     // still too few waves and a long K loop: let the 4 waves of a workgroup split K (the 10x10 tail)
     const bool ksplit = p.nstrips * ocblocks < env_int("FFGPU_PW_KS_WAVES", 1024) && p.k4 >= 32 && !env_int("FFGPU_PW_NOKS", 0);
@@ -464,12 +467,28 @@ __global__ void k_pw_pack(PwPackP p)
         p.pk[i] = v;
     }
 }
+static void pw_mfma_dims(const ConvDesc &d, int &k4, int &OT, int &ocblocks) { k4 = (d.ic + 3) & ~3; OT = pw_ot(d.oc, ((long)d.N * d.iw * d.ih + 63) / 64); ocblocks = (d.oc + OT * 16 - 1) / (OT * 16); }
+static size_t pw_mfma_img_dwords(const ConvDesc &d) { int k4, OT, ocblocks; pw_mfma_dims(d, k4, OT, ocblocks); return ((size_t)(k4 / 4) * OT * 64 + OT * 32) * ocblocks; }
+static int pw_mfma_pack(const ConvDesc &d, float *pk, hipStream_t s)
+{
+    PwPackP q;
+    q.filt = d.filt; q.pk = pk; q.ic = d.ic; q.oc = d.oc;
+    pw_mfma_dims(d, q.k4, q.OT, q.ocblocks);
+    const int total = ((q.k4 / 4) * q.OT * 64 + q.OT * 32) * q.ocblocks;
+    hipLaunchKernelGGL(k_pw_pack, dim3((total + 255) / 256), dim3(256), 0, s, q);
+    LAUNCH_OK("pw_pack");
+    return 0;
+}
 
 // waves per workgroup of the pointwise GEMM: 8 (256-channel tiles: the input chunk shared by twice as many waves) from 256 filters up
 static int pwg32_wm(const ConvDesc &d) { const int f = env_int("FFGPU_PWG_WM", 0); return f == 4 || f == 8 ? f : (d.oc >= 256 - 8 ? 8 : 4); }
 static void pwg32_dims(const ConvDesc &d, int &nchunks, int &ntm) { nchunks = (d.ic + PWG_KC - 1) / PWG_KC; ntm = (d.oc + 32 * pwg32_wm(d) - 1) / (32 * pwg32_wm(d)); }
 static int pwg32_img(const ConvDesc &d) { int nc, ntm; pwg32_dims(d, nc, ntm); return nc * 512 * pwg32_wm(d) + 64 * pwg32_wm(d); }
+static size_t pwg32_img_dwords(const ConvDesc &d) { int nc, ntm; pwg32_dims(d, nc, ntm); return (size_t)pwg32_img(d) * ntm; }
 
+// one image per group, behind each other (igemm_pack), rounded to 64 floats; then the split-K partial sums
+static size_t igemm_images_floats(const ConvDesc &d) { int WM, nchunks, ntm, img; igemm_dims(d, WM, nchunks, ntm, img); return ((size_t)img * ntm * d.groups + 63) & ~(size_t)63; }
+static size_t igemm_img_dwords(const ConvDesc &d) { return igemm_images_floats(d) + igemm_part_floats(d); }
 static int igemm_pack(const ConvDesc &d, float *pk, hipStream_t s)
 {
     IgemmPackP q;
@@ -488,6 +507,7 @@ static int igemm_pack(const ConvDesc &d, float *pk, hipStream_t s)
 }
 
 static void pwbf16_dims(const ConvDesc &d, int &nchunks, int &ntm) { nchunks = (d.ic + PWB_KC - 1) / PWB_KC; ntm = (d.oc + 127) / 128; }
+static size_t pwbf16_img_dwords(const ConvDesc &d) { int nchunks, ntm; pwbf16_dims(d, nchunks, ntm); return (size_t)(nchunks * 2048 + 256) * ntm; }
 static int pwbf16_pack(const ConvDesc &d, float *pk, hipStream_t s)
 {
     PwBf16PackP q;
@@ -497,33 +517,6 @@ static int pwbf16_pack(const ConvDesc &d, float *pk, hipStream_t s)
     hipLaunchKernelGGL(k_pw_bf16_pack, dim3((total + 255) / 256), dim3(256), 0, s, q);
     LAUNCH_OK("pw_bf16_pack");
     return 0;
-}
-
-// plan-time weight image of a conv launch (pointwise MFMA kernels, implicit GEMM); 0: the kernel reads the filter rows as they are
-size_t ffgpu_pw_pack_floats(const ConvDesc &d)
-{
-    if (conv_pick(d, FFGPU_K_AUTO) == FFGPU_K_PW_X3) return (pwx3_img_dwords(d) + 63) & ~(size_t)63;
-    if (conv_pick(d, FFGPU_K_AUTO) == FFGPU_K_PW_X3T) return (pwx3t_img_dwords(d) + 63) & ~(size_t)63;
-    if (conv_pick(d, FFGPU_K_AUTO) == FFGPU_K_CONV_X3) return (ig_x3_img_dwords(d) + 63) & ~(size_t)63;
-    if (conv_pick(d, FFGPU_K_AUTO) == FFGPU_K_PW_BF16) {
-        int nchunks, ntm;
-        pwbf16_dims(d, nchunks, ntm);
-        return ((size_t)(nchunks * 2048 + 256) * ntm + 63) & ~(size_t)63;
-    }
-    if (conv_pick(d, FFGPU_K_AUTO) == FFGPU_K_IGEMM) {
-        int WM, nchunks, ntm, img;
-        igemm_dims(d, WM, nchunks, ntm, img);
-        return (((size_t)img * ntm * d.groups + 63) & ~(size_t)63) + ((igemm_part_floats(d) + 63) & ~(size_t)63);     // one image per group, behind each other (igemm_pack); then the split-K partial sums
-    }
-    if (!pw_mfma_ok(d)) return 0;
-    if (conv_pick(d, FFGPU_K_AUTO) == FFGPU_K_PW_GEMM) {
-        int nchunks, ntm;
-        pwg32_dims(d, nchunks, ntm);
-        return ((size_t)pwg32_img(d) * ntm + 63) & ~(size_t)63;
-    }
-    const long nstrips = ((long)d.N * d.iw * d.ih + 63) / 64;
-    const int k4 = (d.ic + 3) & ~3, OT = conv_pick(d, FFGPU_K_AUTO) == FFGPU_K_PW_GEMM ? 4 : pw_ot(d.oc, nstrips), ocblocks = (d.oc + OT * 16 - 1) / (OT * 16);
-    return (((size_t)(k4 / 4) * OT * 64 + OT * 32) * ocblocks + 63) & ~(size_t)63;
 }
 
 static int pwg32_pack(const ConvDesc &d, float *pk, hipStream_t s)
@@ -538,21 +531,383 @@ static int pwg32_pack(const ConvDesc &d, float *pk, hipStream_t s)
     return 0;
 }
 
+static int launch_generic(const ConvDesc &d, const float *, hipStream_t s)
+{
+    const long total = (long)d.oc * d.N * d.oh * d.ow;
+    hipLaunchKernelGGL(k_conv_generic, dim3(grid_for(total, 256, 256 * 32)), dim3(256), 0, s, d);
+    LAUNCH_OK("conv_generic");
+    return 0;
+}
+
+static int launch_group_thin(const ConvDesc &d, const float *, hipStream_t s)
+{
+    ThinGP p;
+    p.in = d.in; p.in_ind = d.in_ind; p.filt = d.filt; p.out = d.out; p.residual = d.residual;
+    p.N = d.N; p.iw = d.iw; p.ih = d.ih; p.ow = d.ow; p.oh = d.oh; p.gic = d.ic / d.groups; p.goc = d.oc / d.groups; p.groups = d.groups;
+    p.fs = d.fs; p.stride = d.stride; p.pad = d.pad; p.act = d.act; p.res_act = d.res_act;
+    p.k4 = (d.fs * d.fs * p.gic + 3) & ~3; p.rl = p.k4 + 4;
+    p.in_cs = d.in_cs; p.in_ns = d.in_ns; p.out_cs = d.out_cs; p.out_ns = d.out_ns; p.res_cs = d.res_cs; p.res_ns = d.res_ns;
+    p.tiles = (int)(((long)d.oh * d.ow + 255) / 256);
+    const dim3 grid((unsigned)((long)p.tiles * d.N * d.groups));
+    // outputs per lane and pass: every loaded input value feeds that many FMAs
+#define THIN_LAUNCH(FS) do { \
+        if (p.goc >= 7)      hipLaunchKernelGGL((k_conv_thin<8, FS>), grid, dim3(256), 0, s, p); \
+        else if (p.goc >= 3) hipLaunchKernelGGL((k_conv_thin<4, FS>), grid, dim3(256), 0, s, p); \
+        else                 hipLaunchKernelGGL((k_conv_thin<2, FS>), grid, dim3(256), 0, s, p); } while (0)
+    if (d.fs == 3) THIN_LAUNCH(3); else if (d.fs == 5) THIN_LAUNCH(5); else THIN_LAUNCH(0);
+#undef THIN_LAUNCH
+    LAUNCH_OK("conv_thin");
+    return 0;
+}
+
+static int launch_pw_gemm(const ConvDesc &d, const float *image, hipStream_t s)
+{
+    PwG32P p;                                 // LDS-tiled 32x32x2 GEMM (ffgpu_pw_gemm32.inc); the A operand comes from the packed image
+    p.in = d.in; p.out = d.out; p.residual = d.residual;
+    p.P = (long)d.N * d.iw * d.ih; p.ic = d.ic; p.oc = d.oc; p.act = d.act; p.res_act = d.res_act;
+    pwg32_dims(d, p.nchunks, p.ntm);
+    p.wm = pwg32_wm(d);
+    p.img = pwg32_img(d);
+    p.wpack = image;
+    // resident workgroups per CU: 4 of the 4-wave form (LDS 33 KB, 16 waves), 3 of the 8-wave form (LDS 50 KB, 24 waves)
+    const int slots = (p.wm == 8 ? env_int("FFGPU_PWG_SLOTS8", 3) : 4) * device_cus();
+    long ntn_main, ntn_narrow;
+    split_main_narrow(p.P, p.ntm, slots, env_int("FFGPU_PWG_NARROW", 1) != 0, &ntn_main, &ntn_narrow);
+    p.ntn = ntn_main;
+    const long total = p.ntn * p.ntm;
+    p.per_xcd = (int)((total + 7) / 8);
+    p.dbg = env_int("FFGPU_PWG_DBG", 0);
+    const dim3 grid((unsigned)(8 * p.per_xcd + ntn_narrow * p.ntm));
+    if (p.wm == 8) hipLaunchKernelGGL(k_pw_gemm32<8>, grid, dim3(512), 0, s, p);
+    else           hipLaunchKernelGGL(k_pw_gemm32<4>, grid, dim3(256), 0, s, p);
+    LAUNCH_OK("pw_gemm32");
+    return 0;
+}
+
+static int launch_pw_x3(const ConvDesc &d, const float *image, hipStream_t s)
+{
+    PwX3P p;
+    p.in = d.in; p.out = d.out; p.residual = d.residual; p.filt = d.filt;
+    p.P = (long)d.N * d.iw * d.ih; p.ic = d.ic; p.oc = d.oc; p.k4 = (d.ic + 3) & ~3; p.act = d.act; p.res_act = d.res_act;
+    pwx3_dims(d, p.ksteps, p.nrb);
+    p.wpack = reinterpret_cast<const unsigned *>(image);
+    // M tile of 16 MT rows whose three-part image for all k-steps fits the LDS (3 KB per 16 rows and k-step)
+    int MT = pw_x3_mt(d);
+    while (MT > 1 && (size_t)p.ksteps * MT * 3072 > 144 * 1024) MT /= 2;
+    const size_t lds = (size_t)p.ksteps * MT * 3072 + (size_t)MT * 128;
+    if (lds > 160 * 1024 - 1024) { ffgpu_set_error("pw_x3: %d input channels are too many for the LDS-resident weight tile", d.ic); return -1; }
+    p.ntm = (p.nrb + MT - 1) / MT;
+    p.ntn = (p.P + 63) / 64;
+    const int cus = device_cus(), per_cu = lds <= 72 * 1024 ? 2 : 1;                 // workgroups (8 waves, 2 per SIMD at 256 VGPRs ... 1 per SIMD each when two share a CU)
+    long nslots = std::max(1L, (long)cus * per_cu / p.ntm);
+    nslots = std::min(nslots, (p.ntn + 7) / 8);
+    if (nslots >= 8) nslots &= ~7L;                               // a multiple of the XCD count: the channel tiles of a pixel range share an XCD's L2 (see the kernel)
+    if (env_int("FFGPU_PWX3_SLOTS", 0) > 0) nslots = env_int("FFGPU_PWX3_SLOTS", 0);
+    p.nslots = (int)nslots;
+    const dim3 grid((unsigned)(nslots * p.ntm));
+#define PWX3_LAUNCH(mt) do { if (lds_allow((const void *)k_pw_x3<mt>, lds, "pw_x3")) return -1; hipLaunchKernelGGL((k_pw_x3<mt>), grid, dim3(512), lds, s, p); } while (0)
+    if (MT == 4) PWX3_LAUNCH(4); else if (MT == 2) PWX3_LAUNCH(2); else PWX3_LAUNCH(1);
+#undef PWX3_LAUNCH
+    LAUNCH_OK("pw_x3");
+    return 0;
+}
+
+static int launch_pw_x3t(const ConvDesc &d, const float *image, hipStream_t s)
+{
+    PwX3tP p;
+    p.in = d.in; p.out = d.out; p.residual = d.residual;
+    p.P = (long)d.N * d.iw * d.ih; p.ic = d.ic; p.oc = d.oc; p.act = d.act; p.res_act = d.res_act;
+    pwx3t_dims(d, p.nchunks, p.ntm);
+    const int RBv = pwx3t_rb(d);
+    p.img = (long)p.nchunks * xt_ach(RBv) + 2 * xt_tm(RBv);
+    p.wpack = reinterpret_cast<const unsigned *>(image);
+    const int slots = (RBv == 2 ? 2 : 3) * device_cus();          // resident workgroups: two of the 256-channel form per CU, three of the 128-channel one
+    long ntn_main, ntn_narrow;
+    split_main_narrow(p.P, p.ntm, slots, env_int("FFGPU_PWXT_NARROW", 1) != 0, &ntn_main, &ntn_narrow);
+    p.ntn = ntn_main;
+    const long total = p.ntn * p.ntm;
+    p.per_xcd = (int)((total + 7) / 8);
+    p.nmain = 8 * p.per_xcd; p.tpw = 1;
+    if (env_int("FFGPU_PWXT_PERSIST", 0) && total > slots) {      // tuning: persistent workgroups over the main tiles (slots of them, a multiple of 8)
+        p.nmain = slots / 8 * 8;
+        p.tpw = (int)((8L * p.per_xcd + p.nmain - 1) / p.nmain);
+    }
+    p.dbg = env_int("FFGPU_PWXT_DBG", 0);
+    { const int nt = env_int("FFGPU_PWXT_NT", -1); p.nt = nt >= 0 ? (nt != 0) : ((long)d.oc * p.P * 4 >= (128L << 20)); }
+    const dim3 grid((unsigned)(p.nmain + ntn_narrow * p.ntm));
+    p.dbg_t = nullptr;
+#if XT_TRACE                                                        // lab builds: one traced launch, dumped as text (tile words) to FFGPU_PWXT_TRACE
+    if (const char *tf = getenv("FFGPU_PWXT_TRACE")) {
+        const size_t nw = (size_t)((p.P + 31) / 32 + 4) * p.ntm * 8;
+        unsigned long long *d_t = nullptr;
+        if (hipMalloc(&d_t, nw * 8) != hipSuccess) return -1;
+        (void)hipMemsetAsync(d_t, 0, nw * 8, s);
+        p.dbg_t = d_t;
+        if (RBv == 2) hipLaunchKernelGGL(k_pw_x3t<2>, grid, dim3(256), 0, s, p); else hipLaunchKernelGGL(k_pw_x3t<1>, grid, dim3(256), 0, s, p);
+        (void)hipStreamSynchronize(s);
+        std::vector<unsigned long long> h(nw);
+        (void)hipMemcpy(h.data(), d_t, nw * 8, hipMemcpyDeviceToHost);
+        (void)hipFree(d_t);
+        if (FILE *fp = fopen(tf, "w")) {
+            for (size_t i = 0; i < nw; i += 8) if (h[i]) fprintf(fp, "%llu %llu %llu %llu %llu %llu %llu\n", h[i], h[i + 1], h[i + 2], h[i + 3], h[i + 4], h[i + 5], h[i + 6]);
+            fclose(fp);
+        }
+        return 0;
+    }
+#endif
+    if (RBv == 2) hipLaunchKernelGGL(k_pw_x3t<2>, grid, dim3(256), 0, s, p);
+    else          hipLaunchKernelGGL(k_pw_x3t<1>, grid, dim3(256), 0, s, p);
+    LAUNCH_OK("pw_x3t");
+    return 0;
+}
+
+static int launch_pw_bf16(const ConvDesc &d, const float *image, hipStream_t s)
+{
+    PwBf16P p;
+    p.in = d.in; p.out = d.out; p.residual = d.residual;
+    p.P = (long)d.N * d.iw * d.ih; p.ic = d.ic; p.oc = d.oc; p.act = d.act; p.res_act = d.res_act;
+    pwbf16_dims(d, p.nchunks, p.ntm);
+    p.img = p.nchunks * 2048 + 256;
+    p.wpack = reinterpret_cast<const unsigned *>(image);
+    p.ntn = (p.P + 127) / 128;
+    p.per_xcd = (int)((p.ntn * p.ntm + 7) / 8);
+    hipLaunchKernelGGL(k_pw_bf16, dim3((unsigned)(8 * p.per_xcd)), dim3(256), 0, s, p);
+    LAUNCH_OK("pw_bf16");
+    return 0;
+}
+
+static int launch_conv_x3(const ConvDesc &d, const float *image, hipStream_t s)
+{
+    IgX3P p;
+    int MT;
+    p.in = d.in; p.out = d.out; p.residual = d.residual; p.filt = d.filt;
+    p.iw = d.iw; p.ih = d.ih; p.ow = d.ow; p.oh = d.oh; p.ic = d.ic; p.oc = d.oc; p.k4 = conv_k4(d); p.act = d.act; p.res_act = d.res_act;
+    p.in_cs = (unsigned)d.in_cs; p.in_ns = (unsigned)d.in_ns;
+    ig_x3_dims(d, MT, p.ngr, p.nrb, p.ntm);
+    p.nunits = d.fs * (d.ic / 8);
+    p.wpack = reinterpret_cast<const unsigned *>(image);
+    const int NW = ig_x3_nw(d);
+    p.owp = d.fs == 1 ? d.ow : (d.ow + 3) & ~3; p.P = (long)d.N * d.oh * d.ow; p.Pp = (long)d.N * d.oh * p.owp;
+    p.ntn = (p.Pp + 63) / 64; p.npg = (p.ntn + NW - 1) / NW;
+    const long nblk = 8 * (long)p.ntm * ((p.npg + 7) / 8);
+    if (nblk > (1L << 30)) { ffgpu_set_error("conv_x3: too many tiles"); return -1; }
+    const size_t lds = (size_t)2 * 3 * d.fs * MT * 1024 + (size_t)MT * 128;
+    const dim3 grid((unsigned)nblk);
+#define IGX3_LAUNCH(mt, nw, fs) do { if (lds_allow((const void *)k_conv_x3<mt, nw, fs>, lds, "conv_x3")) return -1; hipLaunchKernelGGL((k_conv_x3<mt, nw, fs>), grid, dim3(64 * nw), lds, s, p); } while (0)
+#define IGX3_LAUNCH2(mt, nw) do { if (d.fs == 1) IGX3_LAUNCH(mt, nw, 1); else IGX3_LAUNCH(mt, nw, 3); } while (0)
+    if (d.stride == 2) {
+#define IGX3_LAUNCH_S2(mt, nw) do { if (lds_allow((const void *)k_conv_x3<mt, nw, 3, 2>, lds, "conv_x3")) return -1; hipLaunchKernelGGL((k_conv_x3<mt, nw, 3, 2>), grid, dim3(64 * nw), lds, s, p); } while (0)
+        if (NW == 8) { if (MT == 2) IGX3_LAUNCH_S2(2, 8); else IGX3_LAUNCH_S2(1, 8); }
+        else         { if (MT == 2) IGX3_LAUNCH_S2(2, 4); else IGX3_LAUNCH_S2(1, 4); }
+#undef IGX3_LAUNCH_S2
+    } else
+    if (NW == 8) { if (MT == 4) IGX3_LAUNCH2(4, 8); else if (MT == 2) IGX3_LAUNCH2(2, 8); else IGX3_LAUNCH2(1, 8); }
+    else         { if (MT == 4) IGX3_LAUNCH2(4, 4); else if (MT == 2) IGX3_LAUNCH2(2, 4); else IGX3_LAUNCH2(1, 4); }
+#undef IGX3_LAUNCH2
+#undef IGX3_LAUNCH
+    LAUNCH_OK("conv_x3");
+    return 0;
+}
+
+static int launch_igemm(const ConvDesc &d, const float *image, hipStream_t s)
+{
+    IgemmP p;
+    int WM;
+    const int gic = d.ic / d.groups, goc = d.oc / d.groups;
+    p.in = d.in; p.in_ind = d.in_ind;
+    p.P = (long)d.N * d.oh * d.ow; p.in_cs = d.in_cs; p.in_ns = d.in_ns;
+    p.N = d.N; p.iw = d.iw; p.ih = d.ih; p.ic = gic; p.ow = d.ow; p.oh = d.oh; p.oc = goc; p.fs = d.fs; p.stride = d.stride; p.pad = d.pad;
+    p.K = d.fs * d.fs * gic; p.act = d.act; p.res_act = d.res_act;
+    igemm_dims(d, WM, p.nchunks, p.ntm, p.img);
+    p.m_ff = umulhi_magic((long)d.fs * d.fs); p.m_f = umulhi_magic(d.fs);      // (1x1: 0, the kernel then does not divide)
+    const size_t per_group = (size_t)p.img * p.ntm;
+    p.nsplit = igemm_split(d);
+    p.part = p.nsplit > 1 ? const_cast<float *>(image) + igemm_images_floats(d) : nullptr;      // (behind the images: [group][split][filter][pixel])
+    const int TN = WM == 2 ? 128 : 256;
+    p.owp = (d.ow + 3) & ~3; p.Pp = (long)d.N * d.oh * p.owp;
+    p.ntn = ((igemm_vec(d) ? p.Pp : p.P) + TN - 1) / TN;
+    const long total = p.ntn * p.ntm * p.nsplit * d.groups;        // conv-v0.c:46-51: every group's tiles in ONE grid
+    if (total > (1L << 28)) { ffgpu_set_error("conv_igemm: too many tiles"); return -1; }
+    p.per_xcd = (int)((total + 7) / 8);
+    p.groups = d.groups; p.in_off = 0; p.g_in = (long)gic * d.in_cs; p.g_out = (long)goc * d.out_cs; p.g_w = (long)per_group;
+    p.out = d.out; p.residual = d.residual; p.wpack = image;
+    const dim3 grid((unsigned)(8 * p.per_xcd));
+    if (igemm_vec(d)) {
+        if (WM == 2)        hipLaunchKernelGGL((k_conv_igemm<2, true>), grid, dim3(256), 0, s, p);
+        else if (goc <= 32) hipLaunchKernelGGL((k_conv_igemm<1, true, true>), grid, dim3(256), 0, s, p);
+        else                hipLaunchKernelGGL((k_conv_igemm<1, true>), grid, dim3(256), 0, s, p);
+    } else {
+        if (WM == 2)        hipLaunchKernelGGL((k_conv_igemm<2, false>), grid, dim3(256), 0, s, p);
+        else if (goc <= 32) hipLaunchKernelGGL((k_conv_igemm<1, false, true>), grid, dim3(256), 0, s, p);
+        else                hipLaunchKernelGGL((k_conv_igemm<1, false>), grid, dim3(256), 0, s, p);
+    }
+    if (p.nsplit > 1) {
+        IgemmRedP q;
+        const int K = d.fs * d.fs * gic, k4 = (K + 3) & ~3;
+        q.part = p.part; q.filt = d.filt; q.residual = d.residual; q.out = d.out; q.P = p.P; q.oc = d.oc; q.goc = goc;
+        q.nsplit = p.nsplit; q.rl = k4 + 4; q.k4 = k4; q.act = d.act; q.res_act = d.res_act;
+        hipLaunchKernelGGL(k_conv_igemm_reduce, dim3((unsigned)std::min(((long)d.oc * p.P + 255) / 256, 65536L)), dim3(256), 0, s, q);
+    }
+    LAUNCH_OK("conv_igemm");
+    return 0;
+}
+
+static int launch_dw_lds(const ConvDesc &d, const float *, hipStream_t s)
+{
+    if (dw_pair_ok(d)) return launch_dw_pair(d, s);
+    DwLdsP p;
+    p.in = d.in; p.filt = d.filt; p.out = d.out;
+    p.W = d.iw; p.H = d.ih; p.OW = d.ow; p.OH = d.oh; p.planes = d.ic * d.N; p.N = d.N;
+    p.fs = d.fs; p.stride = d.stride; p.pad = d.pad; p.act = d.act; p.flags = d.flags; p.rowlen = conv_k4(d) + 4;
+    // staged row: the padded input row plus the columns a trailing partial quad may touch, 16-byte pitch
+    p.LW = (((d.ow + 3) / 4 * 4 - 1) * d.stride + d.fs + 4 + 3) & ~3;
+    if (p.LW < d.iw + 2 * d.pad) p.LW = (d.iw + 2 * d.pad + 3) & ~3;
+    // band height: ~1024 outputs per plane-band, input window <= 32 KB
+    int BH = d.oh;
+    while (BH > 1 && ((long)BH * d.ow > 1024 || ((long)(BH - 1) * d.stride + d.fs) * p.LW * 4 > 32 * 1024)) BH = (BH + 1) / 2;
+    if (env_int("FFGPU_DWL_BH", 0) > 0) BH = std::min(env_int("FFGPU_DWL_BH", 0), d.oh);       // tuning only
+    p.BH = BH; p.nbands = (d.oh + BH - 1) / BH;
+    p.IH = (BH - 1) * d.stride + d.fs;
+    int NPL = 1;
+    // (tools/tune_dwl.py: the per-item skeleton -- staging, barriers, index arithmetic -- dominates on the small planes
+    //  of the heads, so items are as large as LDS allows while a few per CU remain)
+    while (NPL < 16 && (long)(NPL * 2) * BH * d.ow <= 4096 && (long)(NPL * 2) * p.IH * p.LW * 4 <= 32 * 1024 &&
+           (long)p.planes * p.nbands / (NPL * 2) >= 600) NPL *= 2;
+    if (env_int("FFGPU_DWL_NPL", 0) > 0) NPL = env_int("FFGPU_DWL_NPL", 0);                      // tuning only
+    p.NPL = NPL;
+    p.nitems = (((long)p.planes + NPL - 1) / NPL) * p.nbands;
+    const long ppl = (long)p.IH * p.LW, owq = (d.ow + 3) / 4, per = (long)BH * owq;
+    // exactness of umulhi(i, m): i * d < 2^32 with i < NPL * ppl (staging) resp. NPL * per (outputs)
+    if ((long)NPL * ppl * ppl >= (1L << 32) || (long)NPL * per * per >= (1L << 32) || (long)p.planes >= (1L << 31)) {
+        ffgpu_set_error("dw_lds: item too large for 32-bit index arithmetic"); return -1; }
+    p.m_ppl = umulhi_magic(ppl); p.m_lw = umulhi_magic(p.LW); p.m_per = umulhi_magic(per); p.m_owq = umulhi_magic(owq);
+    p.vec4 = d.ow % 4 == 0 && ((long)d.ow * d.oh) % 4 == 0;
+    const size_t lds = ((size_t)NPL * p.IH * p.LW + NPL * (d.fs * d.fs + 2) + 8) * sizeof(float);
+    const int grid = (int)(p.nitems < 256L * 16 ? p.nitems : 256L * 16);
+    if (d.fs == 3 && d.stride == 1)      hipLaunchKernelGGL((k_dw_lds<3, 1>), dim3(grid), dim3(256), lds, s, p);
+    else if (d.fs == 3)                  hipLaunchKernelGGL((k_dw_lds<3, 2>), dim3(grid), dim3(256), lds, s, p);
+    else if (d.stride == 1)              hipLaunchKernelGGL((k_dw_lds<5, 1>), dim3(grid), dim3(256), lds, s, p);
+    else                                 hipLaunchKernelGGL((k_dw_lds<5, 2>), dim3(grid), dim3(256), lds, s, p);
+    LAUNCH_OK("dw_lds");
+    return 0;
+}
+
+static int launch_dense_small(const ConvDesc &d, const float *, hipStream_t s)
+{
+    // the usual first layer (3x3 s2 p1, 3 input channels, even geometry, 16-byte aligned planes, leaky / relu / linear):
+    // four pixels per thread -- fewer issue slots, chosen when the batch is big enough for issue slots to be what counts
+    if (d.fs == 3 && (d.stride == 2 || d.stride == 1) && d.pad == 1 && d.ic == 3 && !d.residual && d.act != 3 && d.iw == d.stride * d.ow && d.ih == d.stride * d.oh &&
+        d.ow % 4 == 0 && d.in_cs % 4 == 0 && d.in_ns % 4 == 0 && d.out_cs % 4 == 0 && d.out_ns % 4 == 0 && d.in_ns < (1L << 30) &&
+        d.out_ns * d.N < (1L << 30) && (long)d.N * d.oh * d.ow >= env_int("FFGPU_CONV_FIRST_MIN_PX", 262144) && !env_int("FFGPU_NO_CONV_FIRST", 0)) {
+        const int owq = d.ow / 4, per = d.oh * owq;
+        const unsigned m = umulhi_magic(owq);
+        const dim3 grid((per + 255) / 256, d.N, (d.oc + 7) / 8);
+        if (d.stride == 2) hipLaunchKernelGGL((k_conv_first<3, 2>), grid, dim3(256), (size_t)(27 * 8 + 16) * sizeof(float), s, d, m);
+        else               hipLaunchKernelGGL((k_conv_first<3, 1>), grid, dim3(256), (size_t)(27 * 8 + 16) * sizeof(float), s, d, m);
+        LAUNCH_OK("conv_first");
+        return 0;
+    }
+    const long npx = (long)d.N * d.oh * d.ow;
+    const int ppt = npx >= 262144 ? 2 : 1;
+    const dim3 grid(grid_for((npx + ppt - 1) / ppt, 256, 256 * 16), (d.oc + 7) / 8);
+    const size_t lds = ((size_t)d.fs * d.fs * d.ic * 8 + 16) * sizeof(float);
+    if (d.fs == 3 && ppt == 2)      hipLaunchKernelGGL((k_conv_dense8<3, 2>), grid, dim3(256), lds, s, d);
+    else if (d.fs == 3)             hipLaunchKernelGGL((k_conv_dense8<3, 1>), grid, dim3(256), lds, s, d);
+    else if (ppt == 2)              hipLaunchKernelGGL((k_conv_dense8<5, 2>), grid, dim3(256), lds, s, d);
+    else                            hipLaunchKernelGGL((k_conv_dense8<5, 1>), grid, dim3(256), lds, s, d);
+    LAUNCH_OK("conv_dense8");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// THE table of convolution kernels: everything the dispatcher knows about an FFGPU_K_* id.  Adding a kernel is one entry here plus its place in
+// conv_pick's AUTO order.
+struct ConvKernel {
+    int         id;
+    const char *(*name)(const ConvDesc &);
+    bool        (*ok)(const ConvDesc &);                       // can run this shape
+    size_t      (*image_dwords)(const ConvDesc &);              // packed weight image; nullptr: reads the filter rows as they are
+    int         (*pack)(const ConvDesc &, float *, hipStream_t);
+    int         (*launch)(const ConvDesc &, const float *image, hipStream_t);
+    bool        reads_ind;                                      // honours ConvDesc::in_ind
+    bool        image_optional;                                 // without a plan-time image it runs from the filter rows: bare calls pack nothing
+};
+static bool any_shape_ok(const ConvDesc &) { return true; }
+static const char *name_generic(const ConvDesc &)     { return "conv_generic"; }
+static const char *name_dw_stream(const ConvDesc &)   { return "dw3_stream"; }
+static const char *name_dw_lds(const ConvDesc &)      { return "dw_lds"; }
+static const char *name_pw_mfma(const ConvDesc &)     { return "pw_mfma"; }
+static const char *name_pw_gemm(const ConvDesc &)     { return "pw_gemm"; }
+static const char *name_dense_small(const ConvDesc &) { return "conv_dense8"; }
+static const char *name_igemm(const ConvDesc &)       { return "conv_igemm"; }
+static const char *name_pw_bf16(const ConvDesc &)     { return "pw_bf16"; }
+static const char *name_group_thin(const ConvDesc &)  { return "conv_thin"; }
+static const char *name_pw_x3(const ConvDesc &)       { return "pw_x3"; }
+static const char *name_conv_x3(const ConvDesc &d)    { return d.fs == 1 ? "pw_x3s" : "conv_x3"; }
+static const char *name_pw_x3t(const ConvDesc &)      { return "pw_x3t"; }
+
+static const ConvKernel conv_kernels[] = {
+    //  id                   name              ok              image_dwords        pack          launch              reads_ind  image_optional
+    { FFGPU_K_GENERIC,     name_generic,     any_shape_ok,   nullptr,            nullptr,      launch_generic,     true,  false },
+    { FFGPU_K_DW_STREAM,   name_dw_stream,   dw_stream_ok,   nullptr,            nullptr,      launch_dw_stream,   false, false },
+    { FFGPU_K_DW_LDS,      name_dw_lds,      dw_lds_ok,      nullptr,            nullptr,      launch_dw_lds,      false, false },      // (pair-able 5x5 shapes: k_dw_pair)
+    { FFGPU_K_PW_MFMA,     name_pw_mfma,     pw_mfma_ok,     pw_mfma_img_dwords, pw_mfma_pack, launch_pw_mfma,     false, true  },
+    { FFGPU_K_PW_GEMM,     name_pw_gemm,     pw_gemm_ok,     pwg32_img_dwords,   pwg32_pack,   launch_pw_gemm,     false, false },
+    { FFGPU_K_DENSE_SMALL, name_dense_small, dense_small_ok, nullptr,            nullptr,      launch_dense_small, true,  false },      // (the usual first layer: k_conv_first)
+    { FFGPU_K_IGEMM,       name_igemm,       igemm_ok,       igemm_img_dwords,   igemm_pack,   launch_igemm,       true,  false },      // (image: the groups' images, then the split-K partial sums)
+    { FFGPU_K_PW_BF16,     name_pw_bf16,     pw_gemm_ok,     pwbf16_img_dwords,  pwbf16_pack,  launch_pw_bf16,     false, false },
+    { FFGPU_K_GROUP_THIN,  name_group_thin,  group_thin_ok,  nullptr,            nullptr,      launch_group_thin,  true,  false },
+    { FFGPU_K_PW_X3,       name_pw_x3,       pw_x3_ok,       pwx3_img_dwords,    pwx3_pack,    launch_pw_x3,       false, false },
+    { FFGPU_K_CONV_X3,     name_conv_x3,     ig_x3_ok,       ig_x3_img_dwords,   ig_x3_pack,   launch_conv_x3,     false, false },
+    { FFGPU_K_PW_X3T,      name_pw_x3t,      pw_x3t_ok,      pwx3t_img_dwords,   pwx3t_pack,   launch_pw_x3t,      false, false },
+};
+static const ConvKernel *conv_kernel(int id)
+{
+    for (const ConvKernel &k : conv_kernels) if (k.id == id) return &k;
+    return nullptr;
+}
+
+// THE rule for the image a launch of kernel k reads.  ConvDesc::wpack is the plan-time image, sized (ffgpu_pw_pack_floats) and filled (ffgpu_pw_pack) for
+// the kernel AUTO picks -- so it serves k only if k IS that kernel.  Every other launch (bare single-layer calls; an explicit variant next to somebody
+// else's image) packs into the calling thread's scratch on the launch's stream first.  One scratch per kernel id: two bare calls of different
+// kernels on one stream must not overwrite each other's image before the first has run.
+static int conv_image(const ConvDesc &d, const ConvKernel &k, hipStream_t s, const float **image)
+{
+    static thread_local BareScratch bare_scratch[FFGPU_K_PW_X3T + 1];
+    *image = nullptr;
+    if (!k.image_dwords) return 0;
+    if (d.wpack && conv_pick(d, FFGPU_K_AUTO) == k.id) { *image = d.wpack; return 0; }
+    if (k.image_optional) return 0;
+    float *sc = bare_scratch[k.id].get(k.image_dwords(d));
+    if (!sc) { ffgpu_set_error("%s: hipMalloc failed", k.name(d)); return -1; }
+    if (k.pack(d, sc, s)) return -1;
+    *image = sc;
+    return 0;
+}
+
+bool ffgpu_conv_supports_ind(const ConvDesc &d)
+{
+    const ConvKernel *k = conv_kernel(conv_pick(d, FFGPU_K_AUTO));
+    return k && k->reads_ind;
+}
+
+const char *ffgpu_conv_kernel_name(const ConvDesc &d, int variant)
+{
+    const ConvKernel *k = conv_kernel(conv_pick(d, variant));
+    return k && k->ok(d) ? k->name(d) : "unsupported";
+}
+
+// plan-time weight image of the kernel AUTO picks, in floats rounded up to 64; 0: that kernel reads the filter rows as they are
+size_t ffgpu_pw_pack_floats(const ConvDesc &d)
+{
+    const ConvKernel *k = conv_kernel(conv_pick(d, FFGPU_K_AUTO));
+    return k && k->image_dwords ? (k->image_dwords(d) + 63) & ~(size_t)63 : 0;
+}
+
 int ffgpu_pw_pack(const ConvDesc &d, float *pk, hipStream_t s)
 {
-    if (conv_pick(d, FFGPU_K_AUTO) == FFGPU_K_IGEMM) return igemm_pack(d, pk, s);
-    if (conv_pick(d, FFGPU_K_AUTO) == FFGPU_K_CONV_X3) return ig_x3_pack(d, pk, s);
-    if (conv_pick(d, FFGPU_K_AUTO) == FFGPU_K_PW_BF16) return pwbf16_pack(d, pk, s);
-    if (conv_pick(d, FFGPU_K_AUTO) == FFGPU_K_PW_X3) return pwx3_pack(d, pk, s);
-    if (conv_pick(d, FFGPU_K_AUTO) == FFGPU_K_PW_X3T) return pwx3t_pack(d, pk, s);
-    if (conv_pick(d, FFGPU_K_AUTO) == FFGPU_K_PW_GEMM) return pwg32_pack(d, pk, s);
-    PwPackP q;
-    q.filt = d.filt; q.pk = pk; q.ic = d.ic; q.oc = d.oc; q.k4 = (d.ic + 3) & ~3;
-    q.OT = conv_pick(d, FFGPU_K_AUTO) == FFGPU_K_PW_GEMM ? 4 : pw_ot(d.oc, ((long)d.N * d.iw * d.ih + 63) / 64); q.ocblocks = (d.oc + q.OT * 16 - 1) / (q.OT * 16);
-    const int total = ((q.k4 / 4) * q.OT * 64 + q.OT * 32) * q.ocblocks;
-    hipLaunchKernelGGL(k_pw_pack, dim3((total + 255) / 256), dim3(256), 0, s, q);
-    LAUNCH_OK("pw_pack");
-    return 0;
+    const ConvKernel *k = conv_kernel(conv_pick(d, FFGPU_K_AUTO));
+    return k && k->pack ? k->pack(d, pk, s) : 0;
 }
 
 int ffgpu_launch_conv(const ConvDesc &d, int variant, hipStream_t s)
@@ -561,369 +916,15 @@ int ffgpu_launch_conv(const ConvDesc &d, int variant, hipStream_t s)
         ffgpu_set_error("groupconv: bad geometry (ic=%d oc=%d groups=%d fs=%d stride=%d)", d.ic, d.oc, d.groups, d.fs, d.stride);
         return -1;
     }
-    const int k = conv_pick(d, variant);
-    switch (k) {
-    case FFGPU_K_GENERIC: {
-        const long total = (long)d.oc * d.N * d.oh * d.ow;
-        hipLaunchKernelGGL(k_conv_generic, dim3(grid_for(total, 256, 256 * 32)), dim3(256), 0, s, d);
-        LAUNCH_OK("conv_generic");
-        return 0; }
-    case FFGPU_K_GROUP_THIN: {
-        if (!group_thin_ok(d)) break;
-        ThinGP p;
-        p.in = d.in; p.in_ind = d.in_ind; p.filt = d.filt; p.out = d.out; p.residual = d.residual;
-        p.N = d.N; p.iw = d.iw; p.ih = d.ih; p.ow = d.ow; p.oh = d.oh; p.gic = d.ic / d.groups; p.goc = d.oc / d.groups; p.groups = d.groups;
-        p.fs = d.fs; p.stride = d.stride; p.pad = d.pad; p.act = d.act; p.res_act = d.res_act;
-        p.k4 = (d.fs * d.fs * p.gic + 3) & ~3; p.rl = p.k4 + 4;
-        p.in_cs = d.in_cs; p.in_ns = d.in_ns; p.out_cs = d.out_cs; p.out_ns = d.out_ns; p.res_cs = d.res_cs; p.res_ns = d.res_ns;
-        p.tiles = (int)(((long)d.oh * d.ow + 255) / 256);
-        const dim3 grid((unsigned)((long)p.tiles * d.N * d.groups));
-        // outputs per lane and pass: every loaded input value feeds that many FMAs
-#define THIN_LAUNCH(FS) do { \
-            if (p.goc >= 7)      hipLaunchKernelGGL((k_conv_thin<8, FS>), grid, dim3(256), 0, s, p); \
-            else if (p.goc >= 3) hipLaunchKernelGGL((k_conv_thin<4, FS>), grid, dim3(256), 0, s, p); \
-            else                 hipLaunchKernelGGL((k_conv_thin<2, FS>), grid, dim3(256), 0, s, p); } while (0)
-        if (d.fs == 3) THIN_LAUNCH(3); else if (d.fs == 5) THIN_LAUNCH(5); else THIN_LAUNCH(0);
-#undef THIN_LAUNCH
-        LAUNCH_OK("conv_thin");
-        return 0; }
-    case FFGPU_K_DW_STREAM:
-        if (!dw_stream_ok(d)) break;
-        return launch_dw_stream(d, s);
-    case FFGPU_K_PW_MFMA:
-        if (!pw_mfma_ok(d)) break;
-        return launch_pw_mfma(d, s);
-    case FFGPU_K_PW_GEMM: {
-        if (!pw_gemm_ok(d)) break;
-        // LDS-tiled 32x32x2 GEMM (ffgpu_pw_gemm32.inc); the A operand comes from a packed image: the executor / timing
-        // entry points provide one (d.wpack), a bare call packs into a per-thread scratch buffer first
-        static thread_local BareScratch scratch32;
-        PwG32P p;
-        p.in = d.in; p.out = d.out; p.residual = d.residual;
-        p.P = (long)d.N * d.iw * d.ih; p.ic = d.ic; p.oc = d.oc; p.act = d.act; p.res_act = d.res_act;
-        pwg32_dims(d, p.nchunks, p.ntm);
-        p.wm = pwg32_wm(d);
-        p.img = pwg32_img(d);
-        if (d.wpack) p.wpack = d.wpack;
-        else {
-            float *sc = scratch32.get((size_t)p.img * p.ntm);
-            if (!sc) { ffgpu_set_error("pw_gemm: hipMalloc failed"); return -1; }
-            if (pwg32_pack(d, sc, s)) return -1;
-            p.wpack = sc;
-        }
-        // tiles: ntn main pixel tiles of 128, then narrow ones of 64 over the rest.  The narrow ones take over the partial
-        // last round: with `slots` workgroups resident (4 per CU), total % slots main tiles would run alone at the end
-        int cur_dev = 0, cus = 0;                                      // (per current device: a node plans on every GPU of the box)
-        (void)hipGetDevice(&cur_dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cur_dev);
-        // resident workgroups per CU: 4 of the 4-wave form (LDS 33 KB, 16 waves), 3 of the 8-wave form (LDS 50 KB, 24 waves)
-        const int slots = (p.wm == 8 ? env_int("FFGPU_PWG_SLOTS8", 3) : 4) * (cus > 0 ? cus : 256);
-        const long ntn_all = (p.P + 127) / 128, total_all = ntn_all * p.ntm;
-        long tail_tiles = total_all % slots;                           // main tiles of the partial round
-        if (total_all <= slots / 2) tail_tiles = total_all;            // a launch that never fills the chip: all narrow
-        else if (tail_tiles > slots * 5 / 8) tail_tiles = 0;           // a nearly full round: leave it
-        if (env_int("FFGPU_PWG_NARROW", 1) == 0) tail_tiles = 0;
-        const long tail_ntn = (tail_tiles + p.ntm - 1) / p.ntm;        // pixel tiles handed to the narrow form
-        p.ntn = ntn_all - tail_ntn;
-        const long npx_narrow = p.P - p.ntn * 128, ntn_narrow = npx_narrow > 0 ? (npx_narrow + 63) / 64 : 0;
-        const long total = p.ntn * p.ntm;
-        p.per_xcd = (int)((total + 7) / 8);
-        p.dbg = env_int("FFGPU_PWG_DBG", 0);
-        const dim3 grid((unsigned)(8 * p.per_xcd + ntn_narrow * p.ntm));
-        if (p.wm == 8) hipLaunchKernelGGL(k_pw_gemm32<8>, grid, dim3(512), 0, s, p);
-        else           hipLaunchKernelGGL(k_pw_gemm32<4>, grid, dim3(256), 0, s, p);
-        LAUNCH_OK("pw_gemm32");
-        return 0;
-        }
-    case FFGPU_K_PW_X3: {
-        if (!pw_x3_ok(d)) break;
-        static thread_local BareScratch x3_scratch;
-        PwX3P p;
-        p.in = d.in; p.out = d.out; p.residual = d.residual; p.filt = d.filt;
-        p.P = (long)d.N * d.iw * d.ih; p.ic = d.ic; p.oc = d.oc; p.k4 = (d.ic + 3) & ~3; p.act = d.act; p.res_act = d.res_act;
-        pwx3_dims(d, p.ksteps, p.nrb);
-        if (d.wpack && conv_pick(d, FFGPU_K_AUTO) == FFGPU_K_PW_X3) p.wpack = reinterpret_cast<const unsigned *>(d.wpack);
-        else {
-            float *sc = x3_scratch.get(pwx3_img_dwords(d));
-            if (!sc) { ffgpu_set_error("pw_x3: hipMalloc failed"); return -1; }
-            if (pwx3_pack(d, sc, s)) return -1;
-            p.wpack = reinterpret_cast<const unsigned *>(sc);
-        }
-        // M tile of 16 MT rows whose three-part image for all k-steps fits the LDS (3 KB per 16 rows and k-step)
-        int MT = pw_x3_mt(d);
-        while (MT > 1 && (size_t)p.ksteps * MT * 3072 > 144 * 1024) MT /= 2;
-        const size_t lds = (size_t)p.ksteps * MT * 3072 + (size_t)MT * 128;
-        if (lds > 160 * 1024 - 1024) { ffgpu_set_error("pw_x3: %d input channels are too many for the LDS-resident weight tile", d.ic); return -1; }
-        p.ntm = (p.nrb + MT - 1) / MT;
-        p.ntn = (p.P + 63) / 64;
-        int cur_dev = 0, cus = 0;
-        (void)hipGetDevice(&cur_dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cur_dev);
-        if (cus <= 0) cus = 256;
-        const int per_cu = lds <= 72 * 1024 ? 2 : 1;                  // workgroups (8 waves, 2 per SIMD at 256 VGPRs ... 1 per SIMD each when two share a CU)
-        long nslots = std::max(1L, (long)cus * per_cu / p.ntm);
-        nslots = std::min(nslots, (p.ntn + 7) / 8);
-        if (nslots >= 8) nslots &= ~7L;                               // a multiple of the XCD count: the channel tiles of a pixel range share an XCD's L2 (see the kernel)
-        if (env_int("FFGPU_PWX3_SLOTS", 0) > 0) nslots = env_int("FFGPU_PWX3_SLOTS", 0);
-        p.nslots = (int)nslots;
-        const dim3 grid((unsigned)(nslots * p.ntm));
-#define PWX3_LAUNCH(mt) do { if (lds_allow((const void *)k_pw_x3<mt>, lds, "pw_x3")) return -1; hipLaunchKernelGGL((k_pw_x3<mt>), grid, dim3(512), lds, s, p); } while (0)
-        if (MT == 4) PWX3_LAUNCH(4); else if (MT == 2) PWX3_LAUNCH(2); else PWX3_LAUNCH(1);
-#undef PWX3_LAUNCH
-        LAUNCH_OK("pw_x3");
-        return 0; }
-    case FFGPU_K_PW_X3T: {
-        if (!pw_x3t_ok(d)) break;
-        static thread_local BareScratch x3t_scratch;
-        PwX3tP p;
-        p.in = d.in; p.out = d.out; p.residual = d.residual;
-        p.P = (long)d.N * d.iw * d.ih; p.ic = d.ic; p.oc = d.oc; p.act = d.act; p.res_act = d.res_act;
-        pwx3t_dims(d, p.nchunks, p.ntm);
-        const int RBv = pwx3t_rb(d);
-        p.img = (long)p.nchunks * xt_ach(RBv) + 2 * xt_tm(RBv);
-        if (d.wpack && conv_pick(d, FFGPU_K_AUTO) == FFGPU_K_PW_X3T) p.wpack = reinterpret_cast<const unsigned *>(d.wpack);
-        else {
-            float *sc = x3t_scratch.get(pwx3t_img_dwords(d));
-            if (!sc) { ffgpu_set_error("pw_x3t: hipMalloc failed"); return -1; }
-            if (pwx3t_pack(d, sc, s)) return -1;
-            p.wpack = reinterpret_cast<const unsigned *>(sc);
-        }
-        // main tiles of 128 pixels, then narrow ones of 64 over the partial last round (two workgroups resident per CU)
-        int cur_dev = 0, cus = 0;
-        (void)hipGetDevice(&cur_dev);
-        {   // CUs per device, asked once per device and process (ADVICE r05: not two runtime calls per launch)
-            static int cu_of[64];
-            static std::mutex cu_mu;
-            std::lock_guard<std::mutex> lk(cu_mu);
-            if (cur_dev >= 0 && cur_dev < 64) {
-                if (!cu_of[cur_dev]) (void)hipDeviceGetAttribute(&cu_of[cur_dev], hipDeviceAttributeMultiprocessorCount, cur_dev);
-                cus = cu_of[cur_dev];
-            } else (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cur_dev);
-        }
-        const int slots = (RBv == 2 ? 2 : 3) * (cus > 0 ? cus : 256);
-        const long ntn_all = (p.P + 127) / 128, total_all = ntn_all * p.ntm;
-        long tail_tiles = total_all % slots;                           // main tiles of the partial round
-        if (total_all <= slots / 2) tail_tiles = total_all;            // a launch that never fills the chip: all narrow
-        else if (tail_tiles > slots * 5 / 8) tail_tiles = 0;           // a nearly full round: leave it
-        if (env_int("FFGPU_PWXT_NARROW", 1) == 0) tail_tiles = 0;
-        const long tail_ntn = (tail_tiles + p.ntm - 1) / p.ntm;
-        p.ntn = ntn_all - tail_ntn;
-        const long npx_narrow = p.P - p.ntn * 128, ntn_narrow = npx_narrow > 0 ? (npx_narrow + 63) / 64 : 0;
-        const long total = p.ntn * p.ntm;
-        p.per_xcd = (int)((total + 7) / 8);
-        p.nmain = 8 * p.per_xcd; p.tpw = 1;
-        if (env_int("FFGPU_PWXT_PERSIST", 0) && total > slots) {      // tuning: persistent workgroups over the main tiles (slots of them, a multiple of 8)
-            p.nmain = slots / 8 * 8;
-            p.tpw = (int)((8L * p.per_xcd + p.nmain - 1) / p.nmain);
-        }
-        p.dbg = env_int("FFGPU_PWXT_DBG", 0);
-        { const int nt = env_int("FFGPU_PWXT_NT", -1); p.nt = nt >= 0 ? (nt != 0) : ((long)d.oc * p.P * 4 >= (128L << 20)); }
-        const dim3 grid((unsigned)(p.nmain + ntn_narrow * p.ntm));
-        p.dbg_t = nullptr;
-#if XT_TRACE                                                        // lab builds: one traced launch, dumped as text (tile words) to FFGPU_PWXT_TRACE
-        if (const char *tf = getenv("FFGPU_PWXT_TRACE")) {
-            const size_t nw = (size_t)((p.P + 31) / 32 + 4) * p.ntm * 8;
-            unsigned long long *d_t = nullptr;
-            if (hipMalloc(&d_t, nw * 8) != hipSuccess) return -1;
-            (void)hipMemsetAsync(d_t, 0, nw * 8, s);
-            p.dbg_t = d_t;
-            if (RBv == 2) hipLaunchKernelGGL(k_pw_x3t<2>, grid, dim3(256), 0, s, p); else hipLaunchKernelGGL(k_pw_x3t<1>, grid, dim3(256), 0, s, p);
-            (void)hipStreamSynchronize(s);
-            std::vector<unsigned long long> h(nw);
-            (void)hipMemcpy(h.data(), d_t, nw * 8, hipMemcpyDeviceToHost);
-            (void)hipFree(d_t);
-            if (FILE *fp = fopen(tf, "w")) {
-                for (size_t i = 0; i < nw; i += 8) if (h[i]) fprintf(fp, "%llu %llu %llu %llu %llu %llu %llu\n", h[i], h[i + 1], h[i + 2], h[i + 3], h[i + 4], h[i + 5], h[i + 6]);
-                fclose(fp);
-            }
-            return 0;
-        }
-#endif
-        if (RBv == 2) hipLaunchKernelGGL(k_pw_x3t<2>, grid, dim3(256), 0, s, p);
-        else          hipLaunchKernelGGL(k_pw_x3t<1>, grid, dim3(256), 0, s, p);
-        LAUNCH_OK("pw_x3t");
-        return 0; }
-    case FFGPU_K_PW_BF16: {
-        if (!pw_gemm_ok(d)) break;
-        static thread_local BareScratch bf_scratch;
-        PwBf16P p;
-        p.in = d.in; p.out = d.out; p.residual = d.residual;
-        p.P = (long)d.N * d.iw * d.ih; p.ic = d.ic; p.oc = d.oc; p.act = d.act; p.res_act = d.res_act;
-        pwbf16_dims(d, p.nchunks, p.ntm);
-        p.img = p.nchunks * 2048 + 256;
-        if (d.wpack && conv_pick(d, FFGPU_K_AUTO) == FFGPU_K_PW_BF16) p.wpack = reinterpret_cast<const unsigned *>(d.wpack);
-        else {
-            float *sc = bf_scratch.get((size_t)p.img * p.ntm);
-            if (!sc) { ffgpu_set_error("pw_bf16: hipMalloc failed"); return -1; }
-            if (pwbf16_pack(d, sc, s)) return -1;
-            p.wpack = reinterpret_cast<const unsigned *>(sc);
-        }
-        p.ntn = (p.P + 127) / 128;
-        p.per_xcd = (int)((p.ntn * p.ntm + 7) / 8);
-        hipLaunchKernelGGL(k_pw_bf16, dim3((unsigned)(8 * p.per_xcd)), dim3(256), 0, s, p);
-        LAUNCH_OK("pw_bf16");
-        return 0; }
-    case FFGPU_K_CONV_X3: {
-        if (!ig_x3_ok(d)) break;
-        static thread_local BareScratch igx_scratch;
-        IgX3P p;
-        int MT;
-        p.in = d.in; p.out = d.out; p.residual = d.residual; p.filt = d.filt;
-        p.iw = d.iw; p.ih = d.ih; p.ow = d.ow; p.oh = d.oh; p.ic = d.ic; p.oc = d.oc; p.k4 = conv_k4(d); p.act = d.act; p.res_act = d.res_act;
-        p.in_cs = (unsigned)d.in_cs; p.in_ns = (unsigned)d.in_ns;
-        ig_x3_dims(d, MT, p.ngr, p.nrb, p.ntm);
-        p.nunits = d.fs * (d.ic / 8);
-        if (d.wpack && conv_pick(d, FFGPU_K_AUTO) == FFGPU_K_CONV_X3) p.wpack = reinterpret_cast<const unsigned *>(d.wpack);
-        else {
-            float *sc = igx_scratch.get(ig_x3_img_dwords(d));
-            if (!sc) { ffgpu_set_error("conv_x3: hipMalloc failed"); return -1; }
-            if (ig_x3_pack(d, sc, s)) return -1;
-            p.wpack = reinterpret_cast<const unsigned *>(sc);
-        }
-        const int NW = ig_x3_nw(d);
-        p.owp = d.fs == 1 ? d.ow : (d.ow + 3) & ~3; p.P = (long)d.N * d.oh * d.ow; p.Pp = (long)d.N * d.oh * p.owp;
-        p.ntn = (p.Pp + 63) / 64; p.npg = (p.ntn + NW - 1) / NW;
-        const long nblk = 8 * (long)p.ntm * ((p.npg + 7) / 8);
-        if (nblk > (1L << 30)) { ffgpu_set_error("conv_x3: too many tiles"); return -1; }
-        const size_t lds = (size_t)2 * 3 * d.fs * MT * 1024 + (size_t)MT * 128;
-        const dim3 grid((unsigned)nblk);
-#define IGX3_LAUNCH(mt, nw, fs) do { if (lds_allow((const void *)k_conv_x3<mt, nw, fs>, lds, "conv_x3")) return -1; hipLaunchKernelGGL((k_conv_x3<mt, nw, fs>), grid, dim3(64 * nw), lds, s, p); } while (0)
-#define IGX3_LAUNCH2(mt, nw) do { if (d.fs == 1) IGX3_LAUNCH(mt, nw, 1); else IGX3_LAUNCH(mt, nw, 3); } while (0)
-        if (d.stride == 2) {
-#define IGX3_LAUNCH_S2(mt, nw) do { if (lds_allow((const void *)k_conv_x3<mt, nw, 3, 2>, lds, "conv_x3")) return -1; hipLaunchKernelGGL((k_conv_x3<mt, nw, 3, 2>), grid, dim3(64 * nw), lds, s, p); } while (0)
-            if (NW == 8) { if (MT == 2) IGX3_LAUNCH_S2(2, 8); else IGX3_LAUNCH_S2(1, 8); }
-            else         { if (MT == 2) IGX3_LAUNCH_S2(2, 4); else IGX3_LAUNCH_S2(1, 4); }
-#undef IGX3_LAUNCH_S2
-        } else
-        if (NW == 8) { if (MT == 4) IGX3_LAUNCH2(4, 8); else if (MT == 2) IGX3_LAUNCH2(2, 8); else IGX3_LAUNCH2(1, 8); }
-        else         { if (MT == 4) IGX3_LAUNCH2(4, 4); else if (MT == 2) IGX3_LAUNCH2(2, 4); else IGX3_LAUNCH2(1, 4); }
-#undef IGX3_LAUNCH2
-#undef IGX3_LAUNCH
-        LAUNCH_OK("conv_x3");
-        return 0; }
-    case FFGPU_K_IGEMM: {
-        if (!igemm_ok(d)) break;
-        static thread_local BareScratch ig_scratch;
-        IgemmP p;
-        int WM;
-        const int gic = d.ic / d.groups, goc = d.oc / d.groups;
-        p.in = d.in; p.in_ind = d.in_ind;
-        p.P = (long)d.N * d.oh * d.ow; p.in_cs = d.in_cs; p.in_ns = d.in_ns;
-        p.N = d.N; p.iw = d.iw; p.ih = d.ih; p.ic = gic; p.ow = d.ow; p.oh = d.oh; p.oc = goc; p.fs = d.fs; p.stride = d.stride; p.pad = d.pad;
-        p.K = d.fs * d.fs * gic; p.act = d.act; p.res_act = d.res_act;
-        igemm_dims(d, WM, p.nchunks, p.ntm, p.img);
-        auto magic = [](long dv) { return dv == 1 ? 0u : (unsigned)(((1ULL << 32) + (unsigned long long)dv - 1) / (unsigned long long)dv); };
-        p.m_ff = magic((long)d.fs * d.fs); p.m_f = magic(d.fs);
-        const size_t per_group = (size_t)p.img * p.ntm, img_all = (per_group * d.groups + 63) & ~(size_t)63;
-        p.nsplit = igemm_split(d);
-        const float *wp;
-        if (d.wpack && variant == FFGPU_K_AUTO && k == conv_pick(d, FFGPU_K_AUTO)) wp = d.wpack;          // (the plan-time image exists only for the kernel AUTO picks)
-        else {
-            float *sc = ig_scratch.get(img_all + igemm_part_floats(d));
-            if (!sc) { ffgpu_set_error("conv_igemm: hipMalloc failed"); return -1; }
-            if (igemm_pack(d, sc, s)) return -1;
-            wp = sc;
-        }
-        p.part = p.nsplit > 1 ? const_cast<float *>(wp) + img_all : nullptr;      // (behind the images: [group][split][filter][pixel])
-        const int TN = WM == 2 ? 128 : 256;
-        p.owp = (d.ow + 3) & ~3; p.Pp = (long)d.N * d.oh * p.owp;
-        p.ntn = ((igemm_vec(d) ? p.Pp : p.P) + TN - 1) / TN;
-        const long total = p.ntn * p.ntm * p.nsplit * d.groups;        // conv-v0.c:46-51: every group's tiles in ONE grid
-        if (total > (1L << 28)) { ffgpu_set_error("conv_igemm: too many tiles"); return -1; }
-        p.per_xcd = (int)((total + 7) / 8);
-        p.groups = d.groups; p.in_off = 0; p.g_in = (long)gic * d.in_cs; p.g_out = (long)goc * d.out_cs; p.g_w = (long)per_group;
-        p.out = d.out; p.residual = d.residual; p.wpack = wp;
-        {
-            const dim3 grid((unsigned)(8 * p.per_xcd));
-            if (igemm_vec(d)) {
-                if (WM == 2)        hipLaunchKernelGGL((k_conv_igemm<2, true>), grid, dim3(256), 0, s, p);
-                else if (goc <= 32) hipLaunchKernelGGL((k_conv_igemm<1, true, true>), grid, dim3(256), 0, s, p);
-                else                hipLaunchKernelGGL((k_conv_igemm<1, true>), grid, dim3(256), 0, s, p);
-            } else {
-                if (WM == 2)        hipLaunchKernelGGL((k_conv_igemm<2, false>), grid, dim3(256), 0, s, p);
-                else if (goc <= 32) hipLaunchKernelGGL((k_conv_igemm<1, false, true>), grid, dim3(256), 0, s, p);
-                else                hipLaunchKernelGGL((k_conv_igemm<1, false>), grid, dim3(256), 0, s, p);
-            }
-            if (p.nsplit > 1) {
-                IgemmRedP q;
-                const int K = d.fs * d.fs * gic, k4 = (K + 3) & ~3;
-                q.part = p.part; q.filt = d.filt; q.residual = d.residual; q.out = d.out; q.P = p.P; q.oc = d.oc; q.goc = goc;
-                q.nsplit = p.nsplit; q.rl = k4 + 4; q.k4 = k4; q.act = d.act; q.res_act = d.res_act;
-                hipLaunchKernelGGL(k_conv_igemm_reduce, dim3((unsigned)std::min(((long)d.oc * p.P + 255) / 256, 65536L)), dim3(256), 0, s, q);
-            }
-        }
-        LAUNCH_OK("conv_igemm");
-        return 0; }
-    case FFGPU_K_DW_LDS: {
-        if (!dw_lds_ok(d)) break;
-        if (dw_pair_ok(d)) return launch_dw_pair(d, s);
-        DwLdsP p;
-        p.in = d.in; p.filt = d.filt; p.out = d.out;
-        p.W = d.iw; p.H = d.ih; p.OW = d.ow; p.OH = d.oh; p.planes = d.ic * d.N; p.N = d.N;
-        p.fs = d.fs; p.stride = d.stride; p.pad = d.pad; p.act = d.act; p.flags = d.flags; p.rowlen = conv_k4(d) + 4;
-        // staged row: the padded input row plus the columns a trailing partial quad may touch, 16-byte pitch
-        p.LW = (((d.ow + 3) / 4 * 4 - 1) * d.stride + d.fs + 4 + 3) & ~3;
-        if (p.LW < d.iw + 2 * d.pad) p.LW = (d.iw + 2 * d.pad + 3) & ~3;
-        // band height: ~1024 outputs per plane-band, input window <= 32 KB
-        int BH = d.oh;
-        while (BH > 1 && ((long)BH * d.ow > 1024 || ((long)(BH - 1) * d.stride + d.fs) * p.LW * 4 > 32 * 1024)) BH = (BH + 1) / 2;
-        if (env_int("FFGPU_DWL_BH", 0) > 0) BH = std::min(env_int("FFGPU_DWL_BH", 0), d.oh);       // tuning only
-        p.BH = BH; p.nbands = (d.oh + BH - 1) / BH;
-        p.IH = (BH - 1) * d.stride + d.fs;
-        int NPL = 1;
-        // (tools/tune_dwl.py: the per-item skeleton -- staging, barriers, index arithmetic -- dominates on the small planes
-        //  of the heads, so items are as large as LDS allows while a few per CU remain)
-        while (NPL < 16 && (long)(NPL * 2) * BH * d.ow <= 4096 && (long)(NPL * 2) * p.IH * p.LW * 4 <= 32 * 1024 &&
-               (long)p.planes * p.nbands / (NPL * 2) >= 600) NPL *= 2;
-        if (env_int("FFGPU_DWL_NPL", 0) > 0) NPL = env_int("FFGPU_DWL_NPL", 0);                      // tuning only
-        p.NPL = NPL;
-        p.nitems = (((long)p.planes + NPL - 1) / NPL) * p.nbands;
-        {
-            auto magic = [](long dv) { return (unsigned)(((1ULL << 32) + (unsigned long long)dv - 1) / (unsigned long long)dv); };
-            const long ppl = (long)p.IH * p.LW, owq = (d.ow + 3) / 4, per = (long)BH * owq;
-            // exactness of umulhi(i, m): i * d < 2^32 with i < NPL * ppl (staging) resp. NPL * per (outputs)
-            if ((long)NPL * ppl * ppl >= (1L << 32) || (long)NPL * per * per >= (1L << 32) || (long)p.planes >= (1L << 31)) {
-                ffgpu_set_error("dw_lds: item too large for 32-bit index arithmetic"); return -1; }
-            p.m_ppl = magic(ppl); p.m_lw = magic(p.LW); p.m_per = magic(per); p.m_owq = magic(owq);
-            p.vec4 = d.ow % 4 == 0 && ((long)d.ow * d.oh) % 4 == 0;
-        }
-        const size_t lds = ((size_t)NPL * p.IH * p.LW + NPL * (d.fs * d.fs + 2) + 8) * sizeof(float);
-        const int grid = (int)(p.nitems < 256L * 16 ? p.nitems : 256L * 16);
-        if (d.fs == 3 && d.stride == 1)      hipLaunchKernelGGL((k_dw_lds<3, 1>), dim3(grid), dim3(256), lds, s, p);
-        else if (d.fs == 3)                  hipLaunchKernelGGL((k_dw_lds<3, 2>), dim3(grid), dim3(256), lds, s, p);
-        else if (d.stride == 1)              hipLaunchKernelGGL((k_dw_lds<5, 1>), dim3(grid), dim3(256), lds, s, p);
-        else                                 hipLaunchKernelGGL((k_dw_lds<5, 2>), dim3(grid), dim3(256), lds, s, p);
-        LAUNCH_OK("dw_lds");
-        return 0; }
-    case FFGPU_K_DENSE_SMALL: {
-        if (!dense_small_ok(d)) break;
-        // the usual first layer (3x3 s2 p1, 3 input channels, even geometry, 16-byte aligned planes, leaky / relu / linear):
-        // four pixels per thread -- fewer issue slots, chosen when the batch is big enough for issue slots to be what counts
-        if (d.fs == 3 && (d.stride == 2 || d.stride == 1) && d.pad == 1 && d.ic == 3 && !d.residual && d.act != 3 && d.iw == d.stride * d.ow && d.ih == d.stride * d.oh &&
-            d.ow % 4 == 0 && d.in_cs % 4 == 0 && d.in_ns % 4 == 0 && d.out_cs % 4 == 0 && d.out_ns % 4 == 0 && d.in_ns < (1L << 30) &&
-            d.out_ns * d.N < (1L << 30) && (long)d.N * d.oh * d.ow >= env_int("FFGPU_CONV_FIRST_MIN_PX", 262144) && !env_int("FFGPU_NO_CONV_FIRST", 0)) {
-            const int owq = d.ow / 4, per = d.oh * owq;
-            const unsigned m = owq == 1 ? 0u : (unsigned)(((1ULL << 32) + owq - 1) / owq);
-            const dim3 grid((per + 255) / 256, d.N, (d.oc + 7) / 8);
-            if (d.stride == 2) hipLaunchKernelGGL((k_conv_first<3, 2>), grid, dim3(256), (size_t)(27 * 8 + 16) * sizeof(float), s, d, m);
-            else               hipLaunchKernelGGL((k_conv_first<3, 1>), grid, dim3(256), (size_t)(27 * 8 + 16) * sizeof(float), s, d, m);
-            LAUNCH_OK("conv_first");
-            return 0;
-        }
-        const long npx = (long)d.N * d.oh * d.ow;
-        const int ppt = npx >= 262144 ? 2 : 1;
-        const dim3 grid(grid_for((npx + ppt - 1) / ppt, 256, 256 * 16), (d.oc + 7) / 8);
-        const size_t lds = ((size_t)d.fs * d.fs * d.ic * 8 + 16) * sizeof(float);
-        if (d.fs == 3 && ppt == 2)      hipLaunchKernelGGL((k_conv_dense8<3, 2>), grid, dim3(256), lds, s, d);
-        else if (d.fs == 3)             hipLaunchKernelGGL((k_conv_dense8<3, 1>), grid, dim3(256), lds, s, d);
-        else if (ppt == 2)              hipLaunchKernelGGL((k_conv_dense8<5, 2>), grid, dim3(256), lds, s, d);
-        else                            hipLaunchKernelGGL((k_conv_dense8<5, 1>), grid, dim3(256), lds, s, d);
-        LAUNCH_OK("conv_dense8");
-        return 0; }
-    default: break;
+    const int id = conv_pick(d, variant);
+    const ConvKernel *k = conv_kernel(id);
+    if (!k || !k->ok(d)) {
+        ffgpu_set_error("groupconv: kernel variant %d does not support this shape", id);
+        return -1;
     }
-    ffgpu_set_error("groupconv: kernel variant %d does not support this shape", k);
-    return -1;
+    const float *image;
+    if (conv_image(d, *k, s, &image)) return -1;
+    return k->launch(d, image, s);
 }
 
 // ---------------------------------------------------------------------------

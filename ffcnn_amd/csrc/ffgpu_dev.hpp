@@ -27,7 +27,7 @@ struct ConvDesc {
     const float *filt;     // fn rows of K4+4 floats (conv.h layout)
     float       *out;
     const float *residual; // optional: out = act2(conv_act(...) + residual), same layout as out (fused shortcut)
-    const float *wpack;    // optional: plan-time LDS image of the weights (ffgpu_pw_pack), pointwise layers only
+    const float *wpack;    // optional: plan-time weight image (ffgpu_pw_pack_floats / ffgpu_pw_pack) of the kernel AUTO picks; a launch of any other kernel ignores it
     int   N;
     int   iw, ih, ic;
     int   ow, oh, oc;

@@ -324,6 +324,15 @@ static int plan(ffgpu_exec *ex)
     // pass 1b: 1x1 expand -> depthwise 3x3 -> 1x1 project triples become ONE fused kernel (ffgpu_irb.inc);
     // the two expanded tensors are never materialised
     std::vector<int> irb_tail(L, -1);           // layer p+2 -> p
+    auto irb_desc = [&](int p0) {               // geometry, activations, flags and res_act of the block of layers p0 .. p0 + 2 (the step adds the pointers)
+        IrbDesc d{};
+        const LAYER &a = ll[p0], &b = ll[p0 + 1], &c = ll[p0 + 2];
+        d.N = N; d.H = a.h; d.W = a.w; d.OH = ll[p0 + 3].h; d.OW = ll[p0 + 3].w;
+        d.ic = a.c; d.ec = a.fn; d.oc = c.fn; d.stride = b.stride; d.flags = ex->flags & FFGPU_CONCURRENT;
+        d.act1 = a.activation; d.actd = b.activation; d.act2 = c.activation;
+        d.res_act = fused_into[p0 + 2] >= 0 ? ll[fused_into[p0 + 2]].activation : 0;
+        return d;
+    };
     static const bool no_irb = getenv("FFGPU_NO_IRB") && atoi(getenv("FFGPU_NO_IRB"));
     if (fuse && !no_irb) {
         for (int p0 = 0; p0 + 2 < L; p0++) {
@@ -334,11 +343,7 @@ static int plan(ffgpu_exec *ex)
             const bool pw_c = c.fs == 1 && c.stride == 1 && c.pad == 0 && c.groups == 1;
             if (!pw_a || !dw_b || !pw_c || nuses[p0] != 1 || nuses[p0 + 1] != 1 || src_tensor(p0 - 1) < 0) continue;
             if (canon[p0] != p0 || canon[p0 + 1] != p0 + 1) continue;
-            IrbDesc d{};
-            d.N = N; d.H = a.h; d.W = a.w; d.OH = ll[p0 + 3].h; d.OW = ll[p0 + 3].w;
-            d.ic = a.c; d.ec = a.fn; d.oc = c.fn; d.stride = b.stride; d.flags = ex->flags & FFGPU_CONCURRENT;
-            d.act1 = a.activation; d.actd = b.activation; d.act2 = c.activation;
-            d.res_act = fused_into[p0 + 2] >= 0 ? ll[fused_into[p0 + 2]].activation : 0;
+            const IrbDesc d = irb_desc(p0);
             static const int min_ec = getenv("FFGPU_IRB_MIN_EC") ? atoi(getenv("FFGPU_IRB_MIN_EC")) : 24;
             if ((d.ec < min_ec && !ffgpu_irb_is_thin(d)) || !ffgpu_irb_supported(d)) continue;   // thin blocks take the streaming fused kernel
             irb_tail[p0 + 2] = p0;
@@ -351,12 +356,12 @@ static int plan(ffgpu_exec *ex)
     // tools/dwpw_bench.py): correct but SLOWER than the two launches it replaces -- 61 vs 8 + 15 us on 20x20x120 at batch 64
     // (one workgroup per CU, a barrier chain of 15 short depthwise / MFMA phases with one wave per SIMD; 147.5 k frames/s
     // end to end against 182.7 k) -- so the planner leaves the pairs alone unless asked.
-    auto layer_desc = [&](int i) {
+    auto layer_desc = [&](int i, int flag_mask = FFGPU_COMPAT_V6) {
         ConvDesc d{};
         const LAYER &a = ll[i], &b = ll[i + 1];
         d.N = N; d.iw = a.w; d.ih = a.h; d.ic = a.c; d.ow = b.w; d.oh = b.h; d.oc = b.c;
         d.fs = a.fs; d.stride = a.stride; d.pad = a.pad; d.groups = a.groups; d.act = a.activation;
-        d.flags = ex->flags & FFGPU_COMPAT_V6;
+        d.flags = ex->flags & flag_mask;
         d.in_cs = (long)N * a.w * a.h; d.in_ns = (long)a.w * a.h;
         d.out_cs = (long)N * b.w * b.h; d.out_ns = (long)b.w * b.h;
         return d;
@@ -502,7 +507,7 @@ static int plan(ffgpu_exec *ex)
         return t >= 0 ? tensor_ptr(ex, t) : nullptr;
     };
     for (int i = 0; i < L; i++) {
-        const LAYER &a = ll[i], &b = ll[i + 1];
+        const LAYER &a = ll[i];
         Step st{};
         st.layer = i; st.ltype = a.type;
         bool from_input = false;
@@ -512,21 +517,14 @@ static int plan(ffgpu_exec *ex)
             if (irb_tail[i] >= 0) {
                 const int p0 = irb_tail[i];
                 const LAYER &la = ll[p0], &lb = ll[p0 + 1], &lc = ll[p0 + 2];
-                IrbDesc &d = st.irb;
+                IrbDesc &d = st.irb = irb_desc(p0);
                 st.kind = S_IRB;
                 d.in = tensor_ptr(ex, src_tensor(p0 - 1));
                 d.out = tensor_ptr(ex, canon[i]);
                 d.w1 = ex->dev->d_weights + (la.filter - net->weight_buf);
                 d.wd = ex->dev->d_weights + (lb.filter - net->weight_buf);
                 d.w2 = ex->dev->d_weights + (lc.filter - net->weight_buf);
-                d.N = N; d.H = la.h; d.W = la.w; d.OH = b.h; d.OW = b.w; d.flags = ex->flags & FFGPU_CONCURRENT;
-                d.ic = la.c; d.ec = la.fn; d.oc = lc.fn; d.stride = lb.stride;
-                d.act1 = la.activation; d.actd = lb.activation; d.act2 = lc.activation;
-                if (fused_into[i] >= 0) {
-                    const LAYER &sc = ll[fused_into[i]];
-                    d.residual = tensor_ptr(ex, src_tensor(sc.depend_list[0]));
-                    d.res_act = sc.activation;
-                }
+                if (fused_into[i] >= 0) d.residual = tensor_ptr(ex, src_tensor(ll[fused_into[i]].depend_list[0]));
                 S.push_back(st);
                 break;
             }
@@ -541,18 +539,13 @@ static int plan(ffgpu_exec *ex)
                 S.push_back(st);
                 break;
             }
-            ConvDesc &d = st.conv;
+            ConvDesc &d = st.conv = layer_desc(i, FFGPU_COMPAT_V6 | FFGPU_BF16_PW);
             st.kind = S_CONV;
             d.in = in_ptr(i, &from_input);
             st.in_is_input = from_input;
             d.filt = ex->dev->d_weights + (a.filter - net->weight_buf);
             d.out = tensor_ptr(ex, canon[i]);
-            d.N = N; d.iw = a.w; d.ih = a.h; d.ic = a.c; d.ow = b.w; d.oh = b.h; d.oc = b.c;
-            d.fs = a.fs; d.stride = a.stride; d.pad = a.pad; d.groups = a.groups; d.act = a.activation;
-            d.flags = ex->flags & (FFGPU_COMPAT_V6 | FFGPU_BF16_PW);
             if (from_input) { d.in_cs = (long)a.w * a.h; d.in_ns = (long)a.c * a.w * a.h; }     // frame-major batch input
-            else            { d.in_cs = (long)N * a.w * a.h; d.in_ns = (long)a.w * a.h; }
-            d.out_cs = (long)N * b.w * b.h; d.out_ns = (long)b.w * b.h;
             if (fused_into[i] >= 0) {
                 const LAYER &sc = ll[fused_into[i]];
                 d.residual = tensor_ptr(ex, src_tensor(sc.depend_list[0]));

@@ -535,6 +535,40 @@ def test_pw_bf16(env, orc, shape):
     assert capi.kernel_name(N, W, H, ic, 1, 0, 1, 1, oc) in ("pw_gemm", "pw_mfma", "pw_x3", "pw_x3s")
 
 
+PACKED_IMAGE_SHAPES = [  # (AUTO's kernel, (N, W, H, ic, groups, pad, stride, fs, oc)): the smallest shapes that select each kernel with a packed weight image
+    ("pw_mfma", (1, 8, 8, 8, 1, 0, 1, 1, 16)), ("pw_mfma", (2, 10, 10, 12, 1, 0, 1, 1, 40)),            # (three channel tiles, a partial last block)
+    ("pw_gemm", (1, 128, 128, 64, 1, 0, 1, 1, 128)), ("pw_x3t", (1, 256, 256, 128, 1, 0, 1, 1, 192)), ("pw_x3s", (1, 64, 128, 96, 1, 0, 1, 1, 64)),
+    ("conv_x3", (2, 104, 104, 16, 1, 1, 1, 3, 64)), ("conv_x3", (4, 208, 208, 16, 1, 1, 2, 3, 64)),
+    ("conv_igemm", (1, 13, 13, 256, 1, 1, 1, 3, 512)), ("conv_igemm", (2, 16, 16, 32, 2, 1, 1, 3, 32)),  # (split-K: partial sums behind the image; two groups)
+]
+
+
+@pytest.mark.parametrize("name,shape", PACKED_IMAGE_SHAPES)
+def test_plan_image_equals_bare_image(env, name, shape):
+    """One kernel, one set of operands, two homes of its packed weight image: the plan-time image handed over in ConvDesc::wpack (groupconv_time_dev,
+    as an executor does) and the calling thread's scratch (groupconv_dev).  No atomics, split-K sums added in a fixed order: the outputs are equal bit
+    for bit.  Both against the generic kernel with this file's tolerance."""
+    capi, torch = env
+    N, W, H, ic, groups, pad, stride, fs, oc = shape
+    assert capi.kernel_name(*shape) == name
+    ow, oh = (W + 2 * pad - fs) // stride + 1, (H + 2 * pad - fs) // stride + 1
+    K = fs * fs * (ic // groups)
+    rng = np.random.default_rng(sum(shape))
+    f = make_filter(rng, oc, K)
+    f[:, :K] *= 3.0 / np.sqrt(K)
+    dx = torch.from_numpy(rng.uniform(-1, 1, (ic * N, H, W)).astype(np.float32)).cuda()
+    df = torch.from_numpy(f).cuda()
+    out = [torch.full((oc * N, oh, ow), float("nan"), device="cuda") for _ in range(3)]
+    capi.groupconv_time_dev(dx.data_ptr(), df.data_ptr(), out[0].data_ptr(), *shape, act=2, variant=capi.FFGPU.K_AUTO, warmup=0, iters=1)
+    capi.groupconv_dev(dx.data_ptr(), df.data_ptr(), out[1].data_ptr(), *shape, act=2, variant=capi.FFGPU.K_AUTO)
+    capi.groupconv_dev(dx.data_ptr(), df.data_ptr(), out[2].data_ptr(), *shape, act=2, variant=capi.FFGPU.K_GENERIC)
+    torch.cuda.synchronize()
+    assert torch.equal(out[0], out[1]), "%s %s: plan-time image and scratch image give different outputs" % (name, shape)
+    ref = out[2].cpu().numpy()
+    check(out[0].cpu().numpy(), ref, "%s %s with the plan-time image vs generic" % (name, shape))
+    check(out[1].cpu().numpy(), ref, "%s %s with the scratch image vs generic" % (name, shape))
+
+
 def test_unsupported_variant_fails_loudly(env):
     capi, torch = env
     x = torch.zeros((4, 7, 7), device="cuda")          # W % 4 != 0: the stream kernel must refuse
