@@ -66,11 +66,17 @@ class TileRect(C.Structure):         # ffgpu_tile_rect: one tile of a plan (ffgp
     _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("w", C.c_int), ("h", C.c_int)]
 
 
+class DrawStyle(C.Structure):        # ffgpu_draw_style (24 bytes): colour or palette (HOST bytes, 4 per entry) and thickness of the outlines
+    _fields_ = [("color", C.c_ubyte * 4), ("palette", C.c_void_p), ("npalette", C.c_int), ("thickness", C.c_int)]
+
+
+DRAW_ENTRIES, DRAW_MERGED = 0, 1                                                       # FFGPU_DRAW_* (ffgpu_exec_draw_bgr / _nv12: which)
 YUV_BT601_LIMITED, YUV_BT601_FULL, YUV_BT709_LIMITED, YUV_BT709_FULL = 0, 1, 2, 3      # FFGPU_YUV_* (ffgpu_nv12_frame.matrix)
 
 assert C.sizeof(LAYER) == 120 and C.sizeof(NET) == 104 and C.sizeof(BBOX) == 24
 assert C.sizeof(FrameDets) == 16 + 24 * FFGPU.MAX_DET
 assert C.sizeof(BgrFrame) == 24 and C.sizeof(Nv12Frame) == 40 and C.sizeof(Tile) == 16 and C.sizeof(TileRect) == 16
+assert C.sizeof(DrawStyle) == 24
 
 BOX_DTYPE = np.dtype([("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
 DETS_DTYPE = np.dtype([("count", "<i4"), ("ncand", "<i4"), ("overflow", "<i4"), ("nfull", "<i4"),
@@ -89,7 +95,8 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_node_input_dev", "ffgpu_node_input_slot_dev", "ffgpu_node_depth", "ffgpu_node_rccl_ranks", "ffgpu_node_forward", "ffgpu_node_forward_host",
            "ffgpu_node_submit", "ffgpu_node_wait", "ffgpu_node_run",
            "ffgpu_merge_tiles_scratch_bytes", "ffgpu_merge_tiles_dev", "ffgpu_exec_merge_tiles", "ffgpu_exec_merged_dev", "ffgpu_exec_read_merged",
-           "ffgpu_exec_read_merged_boxes", "ffgpu_tile_plan"]
+           "ffgpu_exec_read_merged_boxes", "ffgpu_tile_plan",
+           "ffgpu_draw_boxes_bgr_dev", "ffgpu_draw_boxes_nv12_dev", "ffgpu_exec_draw_bgr", "ffgpu_exec_draw_nv12"]
 # include/ffcnn_hip_diag.h (libffcnn_hip_diag.so: lab equipment, its own library)
 DIAG_EXPORTS = ["ffgpu_membench", "ffgpu_pipe_probe", "ffgpu_pipe_probe2", "ffgpu_pipe_probe3", "ffgpu_mfma_floor", "ffgpu_diag_x3_term", "ffgpu_diag_xl_op", "ffgpu_clock_probe"]
 
@@ -207,6 +214,10 @@ def lib():
     L.ffgpu_exec_read_merged.argtypes = [vp, vp, i]
     L.ffgpu_exec_read_merged_boxes.argtypes = [vp, i, vp, i]
     L.ffgpu_tile_plan.argtypes = [i] * 7 + [C.POINTER(TileRect), i]
+    L.ffgpu_draw_boxes_bgr_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(BgrFrame), i, C.POINTER(DrawStyle), vp]
+    L.ffgpu_draw_boxes_nv12_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(Nv12Frame), i, C.POINTER(DrawStyle), vp]
+    L.ffgpu_exec_draw_bgr.argtypes = [vp, i, C.POINTER(BgrFrame), i, C.POINTER(DrawStyle), vp]
+    L.ffgpu_exec_draw_nv12.argtypes = [vp, i, C.POINTER(Nv12Frame), i, C.POINTER(DrawStyle), vp]
     _lib = L
     return L
 
@@ -519,6 +530,18 @@ class Executor:
         n = _check(lib().ffgpu_exec_read_merged_boxes(self.h, image, out.ctypes.data, out.size), "ffgpu_exec_read_merged_boxes")
         return out[:n].copy()
 
+    def draw_bgr(self, frames, which=0, color=(0, 255, 0), palette=None, thickness=1, stream=None):
+        """enqueue the outlines of the last forward's boxes (which = DRAW_ENTRIES: entry n into frames[n]) or of the last merge's (DRAW_MERGED:
+        picture g into frames[g]) behind it (ffgpu_exec_draw_bgr): frames as forward_bgr_frames_dev takes them (None, or a NULL address: skipped),
+        colours as B G R bytes (draw_style)"""
+        arr = bgr_frame_table(frames)
+        _check(lib().ffgpu_exec_draw_bgr(self.h, which, arr, len(frames), draw_style(color, palette, thickness), stream), "ffgpu_exec_draw_bgr")
+
+    def draw_nv12(self, frames, which=0, color=(0, 255, 0), palette=None, thickness=1, stream=None):
+        """the same into NV12 frames (ffgpu_exec_draw_nv12): frames as forward_nv12_frames_dev takes them, colours as Y U V bytes"""
+        arr = nv12_frame_table(frames)
+        _check(lib().ffgpu_exec_draw_nv12(self.h, which, arr, len(frames), draw_style(color, palette, thickness), stream), "ffgpu_exec_draw_nv12")
+
     def read_candidates(self, frame=0):
         out = np.zeros(max(1, self.cand_capacity), BOX_DTYPE)
         n = _check(lib().ffgpu_exec_read_layer(self.h, -2, frame, out.ctypes.data_as(f32p), out.size * 6), "read candidates")
@@ -591,6 +614,54 @@ def nv12_frame_desc(f, matrix=0):
         return (Y.data_ptr(), UV.data_ptr(), w, h, Y.stride(0) if h > 1 else w, UV.stride(0) if UV.shape[0] > 1 else UV.shape[1] & ~1, matrix, 0)
     y, uv, w, h = f[0], f[1], f[2], f[3]
     return (y, uv or 0, w, h, f[4] if len(f) > 4 else 0, f[5] if len(f) > 5 else 0, f[6] if len(f) > 6 else matrix, 0)
+
+
+def bgr_frame_table(frames):
+    """a BgrFrame array from what bgr_frame_desc accepts; None is a NULL address (a skipped draw target)"""
+    arr = (BgrFrame * max(1, len(frames)))()
+    for k, f in enumerate(frames):
+        arr[k] = BgrFrame(None, 1, 1, 0, 0) if f is None else BgrFrame(*bgr_frame_desc(f))
+    return arr
+
+
+def nv12_frame_table(frames, matrix=0):
+    """an Nv12Frame array from what nv12_frame_desc accepts; None is a NULL address (a skipped draw target)"""
+    arr = (Nv12Frame * max(1, len(frames)))()
+    for k, f in enumerate(frames):
+        arr[k] = Nv12Frame(None, None, 1, 1, 0, 0, 0, 0) if f is None else Nv12Frame(*nv12_frame_desc(f, matrix))
+    return arr
+
+
+def draw_style(color=(0, 255, 0), palette=None, thickness=1):
+    """a DrawStyle: one colour of three bytes (B G R for BGR targets, Y U V for NV12 ones), or a palette of 1..256 such colours (a sequence of
+    triples or an (n, 3 | 4) uint8 array) indexed by the box's class mod its length.  The structure keeps its palette bytes alive."""
+    st = DrawStyle()
+    st.color[:] = (int(color[0]), int(color[1]), int(color[2]), 0)
+    st.thickness = thickness
+    if palette is not None:
+        pal = np.zeros((len(palette), 4), np.uint8)
+        if len(palette):
+            pal[:, :3] = np.asarray(palette, np.uint8).reshape(len(palette), -1)[:, :3]
+        st._pal = pal                                           # (owned by the structure: the C side reads it during the call)
+        st.palette = pal.ctypes.data
+        st.npalette = len(palette)
+    return st
+
+
+def _draw_boxes_dev(fn, name, table, d_records, d_lists, list_stride, list_first, frames, style, stream):
+    first = None if list_first is None else (C.c_int * max(1, len(list_first)))(*[int(v) for v in list_first])
+    _check(fn(d_records, d_lists, list_stride, first, table(frames), len(frames), style if style is not None else draw_style(), stream), name)
+
+
+def draw_boxes_bgr_dev(d_records, d_lists, list_stride, frames, style=None, list_first=None, stream=None):
+    """ffgpu_draw_boxes_bgr_dev on device records / lists: record t outlined in frames[t] (what bgr_frame_desc accepts, or None: skipped);
+    d_lists None: the records' own boxes; list_first: the first box of each target's list (default t * list_stride)"""
+    _draw_boxes_dev(lib().ffgpu_draw_boxes_bgr_dev, "ffgpu_draw_boxes_bgr_dev", bgr_frame_table, d_records, d_lists, list_stride, list_first, frames, style, stream)
+
+
+def draw_boxes_nv12_dev(d_records, d_lists, list_stride, frames, style=None, list_first=None, stream=None):
+    """ffgpu_draw_boxes_nv12_dev: the same into NV12 frames (what nv12_frame_desc accepts, or None: skipped); colours are Y U V bytes"""
+    _draw_boxes_dev(lib().ffgpu_draw_boxes_nv12_dev, "ffgpu_draw_boxes_nv12_dev", nv12_frame_table, d_records, d_lists, list_stride, list_first, frames, style, stream)
 
 
 def tile_table(tiles):

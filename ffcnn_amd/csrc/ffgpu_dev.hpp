@@ -161,3 +161,17 @@ size_t ffgpu_merge_tab_bytes(int ntiles);
 int    ffgpu_launch_set_ints(int *d_dst, const int *h_src, int n, hipStream_t s);
 int    ffgpu_launch_merge_tiles(const int *d_tab, const std::vector<int> &tab, const ffgpu_frame_dets *recs, const BBOX *lists, int stride,
                                 float thresh, int use_min, ffgpu_frame_dets *out_recs, BBOX *out_lists, void *scratch, hipStream_t s);
+
+// the detections drawn into the frames (ffgpu_draw.inc).  One target as the kernel reads it: the caller's descriptor with its defaults resolved, and
+// the first box of its list (in boxes from the lists' base; unused when the records' own boxes are drawn).  p0 == NULL: a skipped target.
+struct DrawTarget {
+    unsigned char *p0;            // row 0 of the BGR pixels / of the Y plane
+    unsigned char *p1;            // NV12: row 0 of the interleaved U V plane (2-byte aligned); BGR: NULL
+    long long first;
+    int w, h, pitch, pitch_uv;
+};
+int ffgpu_draw_style_check(const char *what, const ffgpu_draw_style *st, unsigned pal[256], int *npal);
+int ffgpu_draw_targets_bgr(const char *what, const ffgpu_bgr_frame *f, int n, std::vector<DrawTarget> &out);
+int ffgpu_draw_targets_nv12(const char *what, const ffgpu_nv12_frame *f, int n, std::vector<DrawTarget> &out);
+int ffgpu_launch_draw(bool nv12, const ffgpu_frame_dets *recs, const BBOX *lists, int stride, const std::vector<DrawTarget> &targets,
+                      const unsigned pal[256], int npal, int thickness, hipStream_t s);

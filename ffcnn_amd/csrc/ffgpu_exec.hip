@@ -1429,6 +1429,56 @@ extern "C" int ffgpu_exec_read_merged_boxes(ffgpu_exec *ex, int image, BBOX *hos
     return nfull;
 }
 
+// -------------------------------------------------------------------------- the detections drawn into the frames (include/ffcnn_hip.h; kernel: ffgpu_draw.inc)
+// A post-pass like the merge, on the stream of the forward or merge it follows: reads the records and full lists (per entry, or the merged ones),
+// writes the caller's frames and nothing of the executor's.
+static int exec_draw(ffgpu_exec *ex, bool nv12, const char *what, int which, const void *targets, int ntargets, const ffgpu_draw_style *style, void *stream)
+{
+    int ndev = 0;
+    if (!ex && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)) {
+        (void)hipGetLastError();
+        ffgpu_set_error("%s: no HIP device visible: libffcnn_hip has no CPU fallback", what);
+        return -1;
+    }
+    if (!alive(ex, what)) return -1;
+    if (!targets) { ffgpu_set_error("%s: NULL targets", what); return -1; }
+    unsigned pal[256];
+    int npal = 0;
+    if (ffgpu_draw_style_check(what, style, pal, &npal)) return -1;
+    if (which != FFGPU_DRAW_ENTRIES && which != FFGPU_DRAW_MERGED) { ffgpu_set_error("%s: which = %d is neither FFGPU_DRAW_ENTRIES nor FFGPU_DRAW_MERGED", what, which); return -1; }
+    const bool merged = which == FFGPU_DRAW_MERGED;
+    if (merged && !merged_ok(ex, what)) return -1;
+    const int want = merged ? (int)ex->mrg_off.size() - 1 : ex->N;
+    if (ntargets != want) {
+        if (merged) ffgpu_set_error("%s: %d targets for a merge of %d pictures", what, ntargets, want);
+        else ffgpu_set_error("%s: %d targets for an executor of batch %d", what, ntargets, want);
+        return -1;
+    }
+    const hipStream_t s = stream ? (hipStream_t)stream : ex->own_stream;
+    if (s != ex->last_stream) { ffgpu_set_error("%s: the draw must be enqueued on the stream of the forward or merge it follows", what); return -1; }
+    std::vector<DrawTarget> tab;
+    if (nv12 ? ffgpu_draw_targets_nv12(what, (const ffgpu_nv12_frame *)targets, ntargets, tab)
+             : ffgpu_draw_targets_bgr(what, (const ffgpu_bgr_frame *)targets, ntargets, tab)) return -1;
+    // a merged list has room for cand_cap boxes per tile of its picture and k_merge_tiles never reports more: the longest room is the kernel's clamp
+    int most = 1;
+    for (int t = 0; t < ntargets; t++) {
+        tab[t].first = (long long)ex->cand_cap * (merged ? ex->mrg_off[t] : t);
+        if (merged) most = std::max(most, ex->mrg_off[t + 1] - ex->mrg_off[t]);
+    }
+    const int stride = (int)std::min((long long)ex->cand_cap * most, (long long)0x7fffffff);
+    return ffgpu_launch_draw(nv12, merged ? ex->d_merged : ex->d_dets, merged ? ex->d_merged_full : ex->d_full, stride, tab, pal, npal, style->thickness, s);
+}
+
+extern "C" int ffgpu_exec_draw_bgr(ffgpu_exec *ex, int which, const ffgpu_bgr_frame *targets, int ntargets, const ffgpu_draw_style *style, void *stream)
+{
+    return exec_draw(ex, false, "draw_bgr", which, targets, ntargets, style, stream);
+}
+
+extern "C" int ffgpu_exec_draw_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_frame *targets, int ntargets, const ffgpu_draw_style *style, void *stream)
+{
+    return exec_draw(ex, true, "draw_nv12", which, targets, ntargets, style, stream);
+}
+
 // FFGPU_KEEP_ALL executors: one 64-bit hash per materialised layer over the layer's WHOLE batch tensor (every bit of every frame), computed on the
 // device behind the last forward; 0 for layers this executor does not materialise.  What the concurrency soak compares round after round
 // (tests/test_gpu_round5.py): 8 bytes per layer cross the bus instead of the activations.

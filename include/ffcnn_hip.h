@@ -395,6 +395,58 @@ int ffgpu_exec_read_merged_boxes(ffgpu_exec *ex, int image, BBOX *host_out, int 
 typedef struct { int x0, y0, w, h; } ffgpu_tile_rect;
 int ffgpu_tile_plan(int img_w, int img_h, int tile_w, int tile_h, int overlap_x, int overlap_y, int align, ffgpu_tile_rect *out, int cap);
 
+/* ---- the detections drawn into the frames on the device ---------------------------------------------------------------------------------
+ * The reference's program ends by outlining its boxes in the picture (ffcnn.c:583-589, bmp_rectangle of bmpfile.c:145-156).  What follows does
+ * that where the frames and the records already lie, in HBM, for u8 BGR and NV12 surfaces: no frame crosses the bus.
+ *
+ * One box, as the reference draws it.  Its integer corners are (a, b, c, d) = ((int)x1, (int)y1, (int)x2, (int)y2): truncated toward zero,
+ * values outside int saturate, NaN gives 0 (what v_cvt_i32_f32 does; the C cast is undefined there, so this sentence is the definition).
+ * Rectangle (a, b, c, d) is the pixel set of bmp_rectangle: (x, b) and (x, d) for a <= x <= c, (a, y) and (c, y) for b <= y <= d; a pixel
+ * outside 0 <= x < w, 0 <= y < h of the target is dropped.  The quirks belong to the contract: with a > c and b <= d the two vertical lines
+ * are still drawn, a box wholly outside draws nothing.  thickness = T draws the T rectangles (a + i, b + i, c - i, d - i), i = 0 .. T-1,
+ * computed as if in 64-bit integers (no wrap-around); T = 1 is exactly the reference.
+ * A target's result is what drawing its boxes serially in list order would leave: a later box overwrites an earlier one.  Only outline
+ * pixels are written; every other byte of the target -- row padding, the pixels between the outlines, the memory before and behind it --
+ * stays as it was.  The result does not depend on the order in which the device executes anything: the same bytes on every run.
+ * BGR targets (ffgpu_bgr_frame): a drawn pixel becomes the three bytes B, G, R of the box's colour.
+ * NV12 targets (ffgpu_nv12_frame; `matrix` is ignored): the colour is Y, U, V bytes, nothing is converted.  A drawn pixel (x, y) sets
+ * Y[y][x] = Y and the chroma pair UV[y >> 1][x >> 1] = (U, V); the serial order holds per chroma sample too: the last box in list order
+ * that touches any of the sample's up to four luma pixels gives it its value.  Odd widths and heights are legal.
+ * A box of class `type` takes palette entry type mod npalette (the non-negative remainder), or `color` when there is no palette.
+ * Targets: a descriptor keeps the meaning and the checks it has for the forward (BGR heights above 2^30 - 1 are rejected here as well), except
+ * that a NULL pixel address (bgr, y) means "skip this target".  The descriptors' const pointers are WRITTEN THROUGH.  Targets of one call
+ * must not overlap in memory; where they do, each overlapping byte holds one of the values written to it, which one is unspecified. */
+typedef struct {
+    unsigned char color[4];         /* the colour when palette is NULL: B G R 0 (BGR targets) / Y U V 0 (NV12 targets)          */
+    const unsigned char *palette;   /* HOST array of npalette x 4 bytes (same byte order), or NULL                               */
+    int npalette;                   /* 0 with a NULL palette, else 1..256                                                        */
+    int thickness;                  /* 1..8                                                                                      */
+} ffgpu_draw_style;                 /* 24 bytes: color at 0, palette at 8, npalette at 16, thickness at 20                       */
+
+/* The operators, on device records and lists with no executor (like ffgpu_merge_tiles_dev).  Target t draws record t of d_records.
+ * d_lists == NULL: the record's own box[0 .. count), count clamped to [0, FFGPU_MAX_DET].  Otherwise nfull boxes, clamped to
+ * [0, list_stride], starting at box list_first[t] of d_lists, or at box t * list_stride when list_first is NULL; list_first is a HOST
+ * array (merged lists do not start at a uniform stride).  Whatever the records hold, nothing is read or written outside the buffers and
+ * the targets' w x h.  targets, list_first and style (with its palette) are HOST memory and free again on return.  Any ntargets >= 1;
+ * the tables travel as kernel arguments, 64 targets per launch.  Enqueued on `stream` without synchronising.  Rejected before anything is
+ * launched, with the target's index in the message where there is one: NULL records, targets or style, ntargets < 1, a bad list_stride, a
+ * negative list start, thickness outside 1..8, npalette outside its range or inconsistent with palette, a descriptor the forward would
+ * reject other than for a NULL address. */
+int ffgpu_draw_boxes_bgr_dev (const void *d_records, const void *d_lists, int list_stride, const int *list_first,
+                              const ffgpu_bgr_frame  *targets, int ntargets, const ffgpu_draw_style *style, void *stream);
+int ffgpu_draw_boxes_nv12_dev(const void *d_records, const void *d_lists, int list_stride, const int *list_first,
+                              const ffgpu_nv12_frame *targets, int ntargets, const ffgpu_draw_style *style, void *stream);
+
+#define FFGPU_DRAW_ENTRIES 0   /* entry n's full post-NMS list into targets[n]; ntargets == batch                                      */
+#define FFGPU_DRAW_MERGED  1   /* picture g's merged list (last ffgpu_exec_merge_tiles) into targets[g]; ntargets == its nimages        */
+/* On an executor: a post-pass like ffgpu_exec_merge_tiles, enqueued on `stream` (NULL = the executor's own; it must be the stream of the
+ * forward or merge it follows) without synchronising.  The captured graph, the records, the full lists, the ring and the host mirror are
+ * untouched.  FFGPU_DRAW_ENTRIES with the very array handed to the forward draws each frame's boxes into that frame; a tile descriptor
+ * draws the tile's boxes inside the tile.  Works on FFGPU_SPLIT2 executors.  Rejected like the operators, and: ntargets not as stated, a
+ * `which` that is neither, FFGPU_DRAW_MERGED when no merge has run, the wrong stream.  A rejected call leaves the executor usable. */
+int ffgpu_exec_draw_bgr (ffgpu_exec *ex, int which, const ffgpu_bgr_frame  *targets, int ntargets, const ffgpu_draw_style *style, void *stream);
+int ffgpu_exec_draw_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_frame *targets, int ntargets, const ffgpu_draw_style *style, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
