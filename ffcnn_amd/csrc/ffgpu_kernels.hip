@@ -262,8 +262,8 @@ __global__ void k_yolo(YoloHead hd, int N, int netw, int neth, BBOX *cand, int *
     // threshold (almost all of them) skip the 80-class scan.  0.1 % slack keeps the shortcut rounding-proof.
     const bool pass = gid < total && !(1.0f / (1.0f + __expf(-bs)) < hd.thresh * 0.999f);
     // class scan of a passing cell: the WAVE reads its scores (lane l -> classes l, l + 64, ...) and reduces to the
-    // first maximum (the reference's `if (best < v)` scan, ffcnn.c:452-456) -- one lane walking 80 strided loads
-    // alone set the run time of the whole kernel
+    // first maximum (the reference's `if (cs < val)` scan from class 0, ffcnn.c:446-450) -- one lane walking 80 strided
+    // loads alone set the run time of the whole kernel
     float cs_best = 0.f;
     int best = 0;
     for (unsigned long long todo = __ballot(pass); todo; todo &= todo - 1) {
@@ -271,9 +271,11 @@ __global__ void k_yolo(YoloHead hd, int N, int netw, int neth, BBOX *cand, int *
         const long g = gid - lane + src;                              // that lane's (frame, anchor, cell)
         const int c2 = (int)(g % cells), k2 = (int)((g / cells) % 3), n2 = (int)(g / (3L * cells));
         const float *q = hd.in + (long)k2 * (5 + hd.classes) * cs + (long)n2 * cells + c2;
-        float v = -3.0e38f;
+        // classes 1 .. : first maximum, NaNs skipped (`v < t` is false for them); class 0 is the reference's starting value, not a
+        // contender: a NaN there stays (conf is NaN, no candidate), and it keeps the index when nothing is greater (all -inf, ties)
+        float v = -INFINITY;
         int vi = 1 << 30;
-        for (int l = lane; l < hd.classes; l += 64) {
+        for (int l = lane ? lane : 64; l < hd.classes; l += 64) {
             const float t = q[(5 + l) * cs];
             if (v < t) { v = t; vi = l; }
         }
@@ -283,7 +285,8 @@ __global__ void k_yolo(YoloHead hd, int N, int netw, int neth, BBOX *cand, int *
             const int oi = __shfl_xor(vi, off);
             if (v < ov || (v == ov && oi < vi)) { v = ov; vi = oi; }
         }
-        if (lane == src) { cs_best = v; best = vi; }
+        const float c0 = q[5 * cs];                                   // (one address for the wave)
+        if (lane == src) { const bool up = c0 < v; cs_best = up ? v : c0; best = up ? vi : 0; }
     }
     if (!pass) return;
     const float conf = 1.0f / ((1.0f + (float)exp((double)-bs) * (1.0f + (float)exp((double)-cs_best))));
@@ -308,7 +311,8 @@ __global__ void k_yolo(YoloHead hd, int N, int netw, int neth, BBOX *cand, int *
 // NMS (ffcnn.c:298-335): one workgroup per frame.  Candidates are ordered by
 // (score desc, emission key asc) with a bitonic sort -- the key makes the
 // order total where qsort's is unspecified -- then suppressed greedily per class
-// with inter/min(area) (or IoU) > thresh, compacted and rescaled by s1/s2.
+// with inter/min(area) (or IoU) > thresh, compacted and rescaled by s1/s2.  A candidate of score exactly 0 is the reference's
+// dead box: it counts in ncand and in the first bbox_max of the emission order, never suppresses and is not kept.
 // Capacity: every anchor of every cell has a candidate slot (cap per frame), so nothing is dropped before the sort; the
 // reference's own limit -- it stops appending at net->bbox_max in EMISSION order (ffcnn.c:463) -- is reproduced by a
 // first sort on the emission key when a frame has more candidates than that (never with the default bbox_max = 51 200).
@@ -378,7 +382,7 @@ __global__ void __launch_bounds__(256) k_nms(const BBOX *cand, const int *cand_k
         __syncthreads();
     }
     sort(false);
-    for (int i = tid; i < m; i += blockDim.x) s_alive[i] = 1;
+    for (int i = tid; i < m; i += blockDim.x) s_alive[i] = s_score[i] != 0.f;      // score 0 is the reference's "dead" (ffcnn.c:305,324): never suppresses, not kept
     __syncthreads();
     for (int a = 0; a < m; a++) {
         if (!s_alive[a]) continue;                       // uniform: read after a barrier

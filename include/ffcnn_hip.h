@@ -33,7 +33,12 @@ extern "C" {
 /* Candidate capacity: the reference appends candidates to a buffer of net->bbox_max = 51 200 entries (ffcnn.c:243,463).
  * Here every anchor of every head cell owns a slot (3 * cells summed over the heads: 1 500 per frame at 320x320), so the
  * decode never drops one; if a frame ever has more than net->bbox_max candidates, the FIRST bbox_max in the reference's
- * emission order go into NMS, as in the reference.  ffgpu_exec_cand_capacity() returns the slots per frame. */
+ * emission order go into NMS, as in the reference.  ffgpu_exec_cand_capacity() returns the slots per frame.
+ * `ncand` and the candidate list (ffgpu_exec_read_layer, layer -2) are NOT cut at bbox_max: they hold every decoded candidate.
+ * A candidate whose score is exactly 0 (ignore_thresh <= 0) is dead in NMS as in the reference (ffcnn.c:305,324): counted in ncand,
+ * present among the candidates, never suppressing, in no list and no record.
+ * Boxes are the reference's bit for bit (tests/detect_tail), with one exception: a coordinate that is NaN there is NaN here, but the
+ * sign and payload of that NaN are unspecified (IEEE 754 leaves them to the implementation). */
 
 /* Per-frame detection record as it lies in device (and gathered host) memory.
  * This is the unit the multi-GPU gather moves: fixed size, 16 + 128*24 bytes. */
