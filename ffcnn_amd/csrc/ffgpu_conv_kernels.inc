@@ -1009,7 +1009,385 @@ int ffgpu_launch_dwpw(const ConvDesc &dw, const ConvDesc &pw, const float *wpack
 }
 
 // ---------------------------------------------------------------------------
-// fused inverted-residual block: tile selection, constant packing, launch
+// fused inverted-residual block: one plan per block, constant packing, launch.
+// ffgpu_irb_plan picks the family -- thin (k_irb_thin), wave (k_irbw / k_irbw2) or workgroup (k_irb) --, the instantiation, the tile, the layout of the
+// packed image and the launch shape, and writes them into IrbDesc::plan.  It is the only function of this section that reads a choice or layout switch
+// of the FFGPU_* environment: ffgpu_irb_pack_floats, ffgpu_irb_pack, ffgpu_launch_irb and the front kernel follow the plan, so a switch changed after
+// planning cannot pair one kernel with another kernel's image.  (Read at launch: the diagnostics FFGPU_IRB_TRACE, FFGPU_VERBOSE_IRB, FFGPU_IRB_SKIP.)
+static float act_slope(int act) { return act == 2 ? 0.1f : (act == 1 ? 0.f : 1.f); }
+
+// tuning only (make TRACE=1 / -DIRB_TRACE=1, FFGPU_IRB_TRACE=1): in-kernel timeline of wave 0 of each workgroup of one k_irbw / k_irb launch, printed per
+// launch.  Of a workgroup's 16 slots, 0 .. nd are consecutive timestamps (100 MHz; a zero one: the phase did not run) and 8 .. 8 + ns - 1 sums over phases.
+struct IrbTraceFmt { const char *what; int nd, ns; const char *dname[7], *sname[6]; };
+static const IrbTraceFmt irbw_trace = { "irbw", 5, 6, { "issue loads", "barrier", "groups", "reduce", "rows" }, { "expand mfma", "store", "dw0", "prj0", "dw1", "prj1" } };
+static const IrbTraceFmt irb_trace = { "irb", 7, 4, { "consts", "wait", "load", "chunks", "reduce", "epilogue", "other-tiles" }, { "bar1", "expand", "bar2", "dw+project" } };
+static const IrbTraceFmt &irb_trace_of(const IrbwP &) { return irbw_trace; }
+static const IrbTraceFmt &irb_trace_of(const IrbP &) { return irb_trace; }
+
+static unsigned long long *irb_trace_begin(hipStream_t s)
+{
+    static unsigned long long *d_t = nullptr;
+    if (!d_t && hipMalloc(&d_t, 4096 * 16 * sizeof(unsigned long long)) != hipSuccess) return d_t = nullptr;
+    (void)hipMemsetAsync(d_t, 0, 4096 * 16 * sizeof(unsigned long long), s);
+    return d_t;
+}
+
+template <typename P>
+static int irb_trace_end(const P &p, const unsigned long long *d_t, long nblocks, hipStream_t s)
+{
+    const IrbTraceFmt &f = irb_trace_of(p);
+    (void)hipStreamSynchronize(s);
+    const long nb = std::min(nblocks, 4096L);
+    std::vector<unsigned long long> h((size_t)nb * 16);
+    (void)hipMemcpy(h.data(), d_t, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    unsigned long long t0 = ~0ull, t1 = 0; double d[7] = { 0 }, sum[6] = { 0 }, late = 0;
+    for (long b = 0; b < nb; b++) t0 = std::min(t0, h[b * 16]);
+    for (long b = 0; b < nb; b++) {
+        unsigned long long prev = h[b * 16];
+        late = std::max(late, (double)(prev - t0) * 0.01);
+        for (int k = 0; k < f.nd; k++) { const unsigned long long t = h[b * 16 + k + 1] ? h[b * 16 + k + 1] : prev; d[k] += (double)(t - prev) / nb * 0.01; prev = t; }
+        t1 = std::max(t1, prev);
+        for (int k = 0; k < f.ns; k++) sum[k] += (double)h[b * 16 + 8 + k] / nb * 0.01;
+    }
+    fprintf(stderr, "  trace %s %dx%d %d->%d->%d: span %.2f us (first %ld blocks), last start +%.2f |", f.what, p.W, p.H, p.ic, p.ec, p.oc, (double)(t1 - t0) * 0.01, nb, late);
+    for (int k = 0; k < f.nd; k++) fprintf(stderr, " %s %.2f", f.dname[k], d[k]);
+    fprintf(stderr, " [");
+    for (int k = 0; k < f.ns; k++) fprintf(stderr, "%s%s %.2f", k ? " " : "", f.sname[k], sum[k]);
+    fprintf(stderr, "] (us, wave 0, mean per workgroup)\n");
+    return 0;
+}
+
+// every k_irbw / k_irbw2 / k_irb launch: the planned LDS allowed, the planned grid and block, the trace if asked for
+template <typename P, void (*K)(P)>
+static int irb_launch_t(const P &p, const IrbPlan &c, hipStream_t s)
+{
+    const char *const what = irb_trace_of(p).what;
+    if (lds_allow((const void *)K, (size_t)c.lds, what)) return -1;
+    if (env_int("FFGPU_IRB_TRACE", 0)) {
+        P q = p;
+        if (!(q.dbg_t = irb_trace_begin(s))) return -1;
+        hipLaunchKernelGGL(K, dim3((unsigned)c.grid), dim3(c.block), (size_t)c.lds, s, q);
+        return irb_trace_end(p, q.dbg_t, c.grid, s);
+    }
+    hipLaunchKernelGGL(K, dim3((unsigned)c.grid), dim3(c.block), (size_t)c.lds, s, p);
+    LAUNCH_OK(what);
+    return 0;
+}
+
+#define IRB_LDS_MAX (160 * 1024)                     // per workgroup on gfx950
+
+// ---- thin form (ffgpu_irb_thin.inc): 8 expanded channels, streaming; the kernel reads the filter rows directly
+static bool irb_thin_ok(const IrbDesc &d)
+{
+    return d.stride == 1 && d.ec == 8 && (d.ic == 4 || d.ic == 8) && (d.oc == 4 || d.oc == 8) && d.W % 4 == 0 && d.W / 4 <= 64 &&
+           8L * d.N * d.W * d.H < (1L << 30) &&          // 32-bit offsets inside a frame-major tensor
+           d.act1 != 3 && d.actd != 3 && d.act2 != 3 && d.res_act != 3 && !env_int("FFGPU_NO_THIN", 0);
+}
+
+// rows per wave of k_irb_thin and k_front: every band expands two extra rows, so long bands waste least -- but the launch wants ~1000 waves;
+// 16 rows at batch 64 (640 waves, 12 % extra expand work), 2 rows for a single frame (80 waves)
+static int thin_band(int N, int H)
+{
+    int band = 2;
+    while (band < 16 && (long)N * H >= 640L * band * 2) band *= 2;
+    return band;
+}
+
+static ThinP thin_params(const IrbDesc &d)
+{
+    ThinP p;
+    p.in = d.in; p.out = d.out; p.residual = d.residual; p.w1 = d.w1; p.wd = d.wd; p.w2 = d.w2;
+    p.W = d.W; p.H = d.H; p.N = d.N;
+    p.band = d.plan.band; p.nbands = (d.H + p.band - 1) / p.band;
+    p.act1 = act_slope(d.act1); p.actd = act_slope(d.actd); p.act2 = act_slope(d.act2); p.res_act = act_slope(d.res_act);
+    p.ntasks = (long)d.N * p.nbands;
+    return p;
+}
+
+template <int IC, int EC, int OC>
+static int irb_thin_launch(const ThinP &p, const IrbPlan &c, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_irb_thin<IC, EC, OC>), dim3((unsigned)c.grid), dim3(c.block), 0, s, p);
+    LAUNCH_OK("irb_thin");
+    return 0;
+}
+
+static int launch_irb_thin(const IrbDesc &d, hipStream_t s)
+{
+    const ThinP p = thin_params(d);
+    if (d.ic == 8 && d.oc == 4) return irb_thin_launch<8, 8, 4>(p, d.plan, s);
+    if (d.ic == 4 && d.oc == 4) return irb_thin_launch<4, 8, 4>(p, d.plan, s);
+    if (d.ic == 8 && d.oc == 8) return irb_thin_launch<8, 8, 8>(p, d.plan, s);
+    return irb_thin_launch<4, 8, 8>(p, d.plan, s);
+}
+
+// ---- wave-autonomous form (ffgpu_irb_wave.inc, ffgpu_irb_wave2.inc): every instantiation that exists, shape test, tile / split choice, launch shape
+typedef int (*IrbwLaunch)(const IrbwP &, const IrbPlan &, hipStream_t);
+// S: stride; NSI: input strips per wave; NSO: output strips per wave (2: k_irbw2); big: the 256-register budget; x3: expand GEMM as split-bf16 products;
+// xl: the split tile once per workgroup in LDS; gate: the switch that lets the planner consider the shape at all (NULL: always), with its default
+struct IrbwKernel { int KS1, OT, S, NSI, NSO; bool big, x3, xl; const char *gate; int gate_dflt; IrbwLaunch launch; };
+// (entries in the order the instantiations have always been named in, which is the order the compiler emits them in: listings of two builds compare line by line)
+#define IRBW_K(ks1, ot, st, nsi, gate, dflt) \
+    { ks1, ot, st, nsi, 1, true, false, false, gate, dflt, irb_launch_t<IrbwP, k_irbw<ks1, ot, st, nsi, true>> }, \
+    { ks1, ot, st, nsi, 1, false, false, false, gate, dflt, irb_launch_t<IrbwP, k_irbw<ks1, ot, st, nsi, false>> }
+static const IrbwKernel irbw_kernels[] = {
+    { 2, 1, 1, 3, 2, true, true, false, nullptr, 0, irb_launch_t<IrbwP, k_irbw2<2, 3, true>> }, { 4, 1, 1, 3, 2, true, true, false, nullptr, 0, irb_launch_t<IrbwP, k_irbw2<4, 3, true>> },
+    { 2, 1, 1, 3, 2, true, false, false, nullptr, 0, irb_launch_t<IrbwP, k_irbw2<2, 3, false>> }, { 4, 1, 1, 3, 2, true, false, false, nullptr, 0, irb_launch_t<IrbwP, k_irbw2<4, 3, false>> },
+    { 12, 3, 1, 2, 1, true, true, true, nullptr, 0, irb_launch_t<IrbwP, k_irbw<12, 3, 1, 2, true, true, true>> },
+    { 4, 2, 2, 4, 1, true, true, false, nullptr, 0, irb_launch_t<IrbwP, k_irbw<4, 2, 2, 4, true, true>> },
+    { 6, 2, 1, 2, 1, true, true, false, nullptr, 0, irb_launch_t<IrbwP, k_irbw<6, 2, 1, 2, true, true>> },
+    IRBW_K(1, 1, 1, 2, nullptr, 0), IRBW_K(2, 1, 1, 2, nullptr, 0), IRBW_K(4, 1, 1, 2, nullptr, 0), IRBW_K(2, 2, 1, 2, nullptr, 0), IRBW_K(4, 2, 1, 2, nullptr, 0),
+    IRBW_K(6, 2, 1, 2, nullptr, 0), IRBW_K(12, 3, 1, 2, nullptr, 0), IRBW_K(1, 1, 2, 3, nullptr, 0), IRBW_K(2, 1, 2, 3, nullptr, 0), IRBW_K(4, 2, 2, 4, nullptr, 0),
+    IRBW_K(6, 3, 2, 3, "FFGPU_IRBW_S2_633", 1),
+    IRBW_K(1, 1, 2, 4, "FFGPU_IRBW_S2_NSI4", 0), IRBW_K(2, 1, 2, 4, "FFGPU_IRBW_S2_NSI4", 0),     // four-strip halo for the thin stride-2 blocks (12 of 16 output quads instead of 8)
+};
+#undef IRBW_K
+static const int irbw_nkernels = (int)(sizeof irbw_kernels / sizeof irbw_kernels[0]);
+
+// a single-strip fp32 instantiation of the shape exists and its switch, if it has one, lets the planner take it
+static bool irbw_has_kernel(int KS1, int OT, int S, int NSI)
+{
+    for (const IrbwKernel &k : irbw_kernels)
+        if (k.KS1 == KS1 && k.OT == OT && k.S == S && k.NSI == NSI && k.NSO == 1 && !k.x3) return !k.gate || env_int(k.gate, k.gate_dflt) != 0;
+    return false;
+}
+
+static long irbw_ntiles(const IrbDesc &d, int TWq, int TH) { return (long)d.N * ((d.OW + 4 * TWq - 1) / (4 * TWq)) * ((d.OH + TH - 1) / TH); }
+
+static bool irbw_pick(const IrbDesc &d, IrbPlan &c)
+{
+    if (env_int("FFGPU_NO_IRBW", 0)) return false;
+    if (d.stride != 1 && d.stride != 2) return false;
+    if (d.act1 == 3 || d.actd == 3 || d.act2 == 3 || d.res_act == 3) return false;
+    if ((size_t)d.ic * d.N * d.H * d.W >= (1u << 30) || (size_t)d.oc * d.N * d.OH * d.OW >= (1u << 30)) return false;   // 32-bit byte offsets
+    const int S = d.stride;
+    c.KS1 = ((d.ic + 3) & ~3) / 4; c.OT = (d.oc + 15) / 16; c.ngroups = (d.ec + 15) / 16;
+    // output tile of TWq quads x TH rows (<= 16 quads) whose halo fits NSI strips: fewest expand strips over the plane
+    double best = 1e30;
+    for (int TWq = 1; TWq <= 8; TWq++) {
+        if (TWq > 1 && (TWq - 1) * 4 >= d.OW) break;
+        for (int TH = 1; TWq * TH <= 16 && TH <= d.OH + 1; TH++) {
+            const int EW = S == 1 ? 4 * TWq + 4 : 8 * TWq + 4, EH = S * (TH - 1) + 3;
+            int NSI = (EW * EH + 63) / 64;
+            if (NSI < 2) NSI = 2;
+            if (S == 2 && NSI < 3) NSI = 3;
+            if (NSI > 4 || !irbw_has_kernel(c.KS1, c.OT, S, NSI)) continue;
+            const long tiles = irbw_ntiles(d, TWq, TH) / d.N;
+            // cycles per group, roughly; wide halo rows (EW floats contiguous in memory) load and store better than
+            // tall narrow tiles with the same strip count (profiles/r01_g_irbw_sweep.txt: 20x3 beats 8x8 on 80x80 and 40x40)
+            const double cost = (double)tiles * (NSI * (c.KS1 * 128.0 + 500.0) + 4 * (220.0 + c.OT * 128.0)) * (1.0 + 12.0 / EW);
+            if (cost < best) { best = cost; c.TWq = TWq; c.TH = TH; c.EW = EW; c.EH = EH; c.NSI = NSI; }
+        }
+    }
+    if (best > 1e29) return false;
+    const int ft = env_int("FFGPU_IRBW_TWQ", 0), fh = env_int("FFGPU_IRBW_TH", 0);
+    if (ft > 0 && fh > 0 && ft * fh <= 16) {
+        const int EW = S == 1 ? 4 * ft + 4 : 8 * ft + 4, EH = S * (fh - 1) + 3;
+        if (EW * EH <= c.NSI * 64) { c.TWq = ft; c.TH = fh; c.EW = EW; c.EH = EH; }
+    }
+    const long ntiles = irbw_ntiles(d, c.TWq, c.TH);
+    const int regs = c.NSI * c.KS1 * 4 + c.OT * 16 + 2 * (c.KS1 + 4 * c.OT) + 76;                     // rough VGPR need
+    c.big = regs > 124;
+    // (the BIG instantiation of a shape whose second set of expand accumulators fits is the software-pipelined form;
+    //  it buys a lone wave nothing and costs the many-round launches occupancy, so it is not forced: FFGPU_IRBW_BIG=1)
+    if (env_int("FFGPU_IRBW_BIG", -1) >= 0) c.big = env_int("FFGPU_IRBW_BIG", -1) != 0;                 // tuning only
+    if (S == 2 && c.KS1 == 1 && env_int("FFGPU_IRBW_BIG_S2K1", -1) >= 0) c.big = env_int("FFGPU_IRBW_BIG_S2K1", -1) != 0;   // tuning only: the 160 -> 80 block alone (40 bytes of scratch at 128 registers)
+    // waves sharing a tile: one wave per tile when that already gives every SIMD a wave or more (tools/tune_irbw.py:
+    // the split only pays on the small planes), else the smallest split that does
+    // With several chains in flight (FFGPU_CONCURRENT) other launches fill the SIMDs, and what counts is the work per
+    // wave that a split repeats (input tile, constants, reduction): 4 waves on the 10x10 planes and 2 on the 20x20 ones
+    // instead of 8 and 4 -- 3.5 % more frames/s with four chains, 4 % fewer with one.
+    const bool conc = (d.flags & FFGPU_CONCURRENT) != 0;
+    const int gmax = std::min(8, c.ngroups);
+    int G = 1;
+    for (int g = 1; g <= gmax; g++) {
+        const size_t slot = (size_t)c.OT * 1024, ereg = (size_t)g * 16 * c.NSI * 64;
+        if (g > 1 && ereg / slot < (size_t)(g + 1) / 2) continue;                                      // reduction must fit the E slices
+        G = g;
+        if (ntiles * g >= env_int("FFGPU_IRBW_GWAVES", conc ? 500 : 1200)) break;
+    }
+    if (!conc && G > 1 && G < gmax && c.ngroups % G != 0 && (c.ngroups + G) / (G + 1) <= (c.ngroups + G - 1) / G) G++;   // same trips per wave, better balance
+    // measured exceptions (profiles/r01_g_irbw_sweep.txt, batch 64): four waves on the 20x20 blocks (3, 2, 2, 2 groups
+    // each) beat three by 8 %
+    if (d.stride == 1 && c.ngroups == 9 && ntiles >= 400 && ntiles < 512 && gmax >= 4 && !conc && !env_int("FFGPU_IRBW_NOEXC", 0)) G = 4;
+    if (ntiles >= 256 && ntiles < 1100 && env_int("FFGPU_IRBW_G_MID", 0) > 0) G = std::min(gmax, env_int("FFGPU_IRBW_G_MID", 0));
+    // the LDS-resident split tile (XL, 48 input channels) makes a wave's share of a tile cheaper: with several chains in flight seven waves
+    // (two groups each of the 10x10 blocks' fourteen) beat four by 1.3 % (profiles/r04: 193.8 k against 191.3 k frames/s, eight: 193.4 k)
+    const bool xl_ok = S == 1 && c.KS1 == 12 && c.OT == 3 && c.NSI == 2 && c.big && ((env_int("FFGPU_IRBW_X3", 30) >> 3) & 1) != 0;
+    if (xl_ok && conc && ntiles < 256) G = std::min(gmax, env_int("FFGPU_IRBW_G_XL", 7));
+    if (ntiles < 256 && env_int("FFGPU_IRBW_G_SMALL", 0) > 0) G = std::min(gmax, env_int("FFGPU_IRBW_G_SMALL", 0));          // tuning only (wins over the XL choice)
+    const int fg = env_int("FFGPU_IRBW_G", 0);                      // an explicit FFGPU_IRBW_G wins over everything
+    if (fg >= 1 && fg <= gmax) G = fg;
+    c.G = G;
+    c.NSO = 1;
+    // single-strip kernel, 24 input channels (the 20x20 blocks): expand GEMM as split-bf16 products (bit 2 of FFGPU_IRBW_X3)
+    c.x3 = S == 1 && c.KS1 == 6 && c.OT == 2 && c.NSI == 2 && c.big && ((env_int("FFGPU_IRBW_X3", 30) >> 2) & 1) != 0;
+    // ... the 40 -> 20 stride-2 block (16 input channels, four-strip halo), bit 4
+    if (S == 2 && c.KS1 == 4 && c.OT == 2 && c.NSI == 4 && c.big && ((env_int("FFGPU_IRBW_X3", 30) >> 4) & 1) != 0) c.x3 = true;
+    // ... and 48 input channels with the groups split over G waves (the 10x10 blocks): the split tile lives once per workgroup in LDS (bit 3)
+    c.xl = xl_ok && G > 1;
+    if (c.xl) c.x3 = true;
+    // two output strips per wave (ffgpu_irb_wave2.inc): one wave per tile, <= 16 output channels, stride 1 -- when a tile
+    // of up to 32 quads with a three-strip halo covers the plane with clearly fewer expand strips
+    if (G == 1 && S == 1 && c.OT == 1 && (c.KS1 == 2 || c.KS1 == 4) && env_int("FFGPU_IRBW_NSO", 2) == 2) {
+        double best2 = 1e30; int tw2 = 0, th2 = 0;
+        for (int TWq = 1; TWq <= 8; TWq++) {
+            if (TWq > 1 && (TWq - 1) * 4 >= d.OW) break;
+            for (int TH = 1; TWq * TH <= 32 && TH <= d.OH + 1; TH++) {
+                if (TWq * TH <= 16 || TWq * ((TH + 1) / 2) > 16) continue;                            // a lane owns a quad in each row of a row pair
+                const int EW = 4 * TWq + 4, EH = TH + 2;
+                if (EW * EH > 192) continue;                                                           // three strips
+                const long tiles = irbw_ntiles(d, TWq, TH) / d.N;
+                const double cost = (double)tiles * (3 * (c.KS1 * 128.0 + 500.0) + 2 * 4 * (220.0 + 128.0)) * (1.0 + 12.0 / EW);
+                if (cost < best2) { best2 = cost; tw2 = TWq; th2 = TH; }
+            }
+        }
+        const int f2t = env_int("FFGPU_IRBW2_TWQ", 0), f2h = env_int("FFGPU_IRBW2_TH", 0);
+        if (f2t > 0 && f2h > 0 && f2t * ((f2h + 1) / 2) <= 16 && (4 * f2t + 4) * (f2h + 2) <= 192) { tw2 = f2t; th2 = f2h; best2 = 0; }
+        const long nt2 = tw2 ? irbw_ntiles(d, tw2, th2) : 0;
+        if (tw2 && best2 < 0.93 * best && nt2 >= env_int("FFGPU_IRBW2_MIN_TILES", 768)) {
+            c.NSO = 2; c.TWq = tw2; c.TH = th2; c.EW = 4 * tw2 + 4; c.EH = th2 + 2; c.NSI = 3; c.big = true; c.WPB = 4; c.xl = false;
+            // the expand GEMM as exact split-bf16 products on the bf16 matrix cores (ffgpu_irb_wave.inc "X3"); FFGPU_IRBW_X3=0: fp32 MFMAs
+            c.x3 = irbw_x3_has(c.KS1) && ((env_int("FFGPU_IRBW_X3", 30) >> (c.KS1 == 2 ? 0 : 1)) & 1) != 0;   // (bit 0: 8 input channels, bit 1: 16)
+        }
+    }
+    // tiles per workgroup (G == 1): whichever of 4 / 8 waves lets more waves share a CU's 160 KB of LDS
+    {
+        const size_t cs = ((size_t)c.ngroups * 224 + c.OT * 32) * sizeof(float), slice = (size_t)16 * c.NSI * 64 * sizeof(float);
+        const int cap = c.big ? 12 : 16;                                                               // VGPR-limited waves per CU
+        const int w4 = std::min(cap, (int)(IRB_LDS_MAX / (cs + 4 * slice)) * 4), w8 = std::min(cap, (int)(IRB_LDS_MAX / (cs + 8 * slice)) * 8);
+        c.WPB = G > 1 ? G : (w4 >= w8 ? 4 : 8);                                                       // tie: the finer granule (1.3 % with four chains in flight)
+        const int fw = env_int("FFGPU_IRBW_WPB", 0);
+        if (G == 1 && fw >= 1 && fw <= 8) c.WPB = fw;
+    }
+    return true;
+}
+
+static void irbw_layout(const IrbPlan &c, int &o_w2, int &o_cs, int &cs_floats, int &total)
+{
+    o_w2 = c.x3 ? c.ngroups * irbw_x3_nm(c.KS1) * 256 : c.ngroups * c.KS1 * 64;
+    o_cs = o_w2 + c.ngroups * 4 * c.OT * 64;
+    cs_floats = c.ngroups * 16 * 14 + c.OT * 32;
+    total = o_cs + cs_floats;
+}
+
+// the parameter block of a planned k_irbw / k_irbw2 launch: arithmetic on the descriptor and the plan
+static IrbwP irbw_params(const IrbDesc &d)
+{
+    const IrbPlan &c = d.plan;
+    IrbwP p;
+    p.in = d.in; p.out = d.out; p.residual = d.residual; p.pk = d.pk;
+    p.N = d.N; p.H = d.H; p.W = d.W; p.OH = d.OH; p.OW = d.OW; p.ic = d.ic; p.ec = d.ec; p.oc = d.oc;
+    p.act1 = act_slope(d.act1); p.actd = act_slope(d.actd); p.act2 = act_slope(d.act2); p.res_act = act_slope(d.res_act);
+    p.TWq = c.TWq; p.TH = c.TH; p.EW = c.EW; p.EH = c.EH;
+    p.tiles_x = (d.OW + 4 * c.TWq - 1) / (4 * c.TWq); p.tiles_y = (d.OH + c.TH - 1) / c.TH;
+    p.ntiles = (long)d.N * p.tiles_x * p.tiles_y;
+    p.ngroups = c.ngroups; p.G = c.G; p.WPB = c.WPB;
+    p.half_last = c.half; p.xcd = c.xcd;
+    int total;
+    irbw_layout(c, p.o_w2, p.o_cs, p.cs_floats, total);
+    p.red_cap = c.region / (c.OT * 1024);
+    p.xl_off = p.cs_floats + c.region;
+    p.in_elems = (unsigned)((size_t)d.ic * d.N * d.H * d.W);
+    p.vec = d.OW % 4 == 0 ? 4 : (d.OW % 2 == 0 ? 2 : 1);
+    p.m_ew = (unsigned)(((1ULL << 32) + c.EW - 1) / c.EW);
+    p.m_tx = umulhi_magic(p.tiles_x); p.m_ty = umulhi_magic(p.tiles_y); p.m_twq = umulhi_magic(p.TWq);
+    p.dbg_t = nullptr;
+    return p;
+}
+
+static bool irb_plan_wave(IrbDesc &d)
+{
+    IrbPlan &c = d.plan;
+    if (!irbw_pick(d, c)) return false;
+    c.family = IRB_WAVE;
+    // a last group of at most 8 real channels in the single-strip kernel: packed into registers 0 / 1, the other half of its work skipped (ffgpu_irb_wave.inc irbw_chan)
+    const int r = d.ec & 15;
+    c.half = c.NSO == 1 && r >= 1 && r <= 8 && env_int("FFGPU_IRBW_HALF", 1) != 0;
+    { const int x = env_int("FFGPU_IRBW_XCD", 3); c.xcd = c.G > 1 ? (x >> 1) & 1 : x & 1; }        // bit 0: one wave per tile, bit 1: group-split launches
+    const IrbwP p = irbw_params(d);                                  // (the reduction region follows)
+    c.pack_floats = p.o_cs + p.cs_floats;
+    if (p.ntiles * std::max(p.tiles_x, p.tiles_y) >= (1L << 32) || p.ntiles >= (1L << 31)) { ffgpu_set_error("irbw: too many tiles for 32-bit index arithmetic"); return false; }
+    // floats behind the shared constants: the waves' E slices, later the partial sums of the group split -- room for all
+    // G of them when the launch leaves the CU's LDS to one workgroup anyway (no folding rounds: two barriers fewer)
+    const int waves = c.G > 1 ? c.G : c.WPB;
+    size_t region = (size_t)waves * 16 * c.NSI * 64;
+    if (c.G > 1 && !env_int("FFGPU_IRBW_FOLD", 0)) {
+        const size_t want = (size_t)c.G * c.OT * 1024;
+        if (want > region && (p.cs_floats + want) * sizeof(float) <= 150 * 1024 && p.ntiles <= 512) region = want;
+    }
+    c.region = (int)region;
+    c.lds = (int)(((size_t)p.cs_floats + region + (c.xl ? (size_t)c.NSI * 4 * 64 * IRBW_XL_DW : 0)) * sizeof(float));
+    c.grid = (int)(c.G > 1 ? p.ntiles : (p.ntiles + c.WPB - 1) / c.WPB);
+    c.block = waves * 64;
+    for (int i = 0; i < irbw_nkernels; i++) {
+        const IrbwKernel &k = irbw_kernels[i];
+        if (k.KS1 == c.KS1 && k.OT == c.OT && k.S == d.stride && k.NSI == c.NSI && k.NSO == c.NSO && k.big == (c.big != 0) && k.x3 == (c.x3 != 0) && k.xl == (c.xl != 0)) { c.inst = i; return true; }
+    }
+    ffgpu_set_error("irbw: no instantiation for KS1=%d OT=%d S=%d NSI=%d NSO=%d big=%d x3=%d xl=%d", c.KS1, c.OT, d.stride, c.NSI, c.NSO, c.big, c.x3, c.xl);
+    return false;
+}
+
+// ---- first layer + first thin block as one kernel (ffgpu_front.inc): the planner asks, then launches; the block's plan says that it is thin, and how many rows a wave takes
+bool ffgpu_front_ok(const ConvDesc &c, const IrbDesc &d)
+{
+    return c.fs == 3 && c.stride == 2 && c.pad == 1 && c.groups == 1 && c.ic == 3 && c.oc == 8 && !c.residual && c.act != 3 &&
+           c.iw == 2 * c.ow && c.ih == 2 * c.oh && c.ow % 4 == 0 && c.ow / 4 <= 64 && c.in_cs % 4 == 0 && c.in_ns % 4 == 0 &&
+           3 * c.in_cs < (1L << 30) && c.out == d.in && d.plan.family == IRB_THIN && d.ic == 8 && d.ec == 8 && d.oc == 4 && !d.residual &&
+           d.W == c.ow && d.H == c.oh && d.N == c.N &&
+           (long)c.N * c.oh * c.ow >= env_int("FFGPU_FRONT_MIN_PX", 262144) && !env_int("FFGPU_NO_FRONT", 0);
+}
+
+// form IN_U8: the frames of this forward are u8 BGR images described by the executor's parameter block (c.in_ind IS that block: its
+// first member is the fp32 frame pointer the IN_F32 form reads)
+// three columns per lane (54 of 64 lanes on a 160-pixel row instead of 40) where the row fits a wave that way; FFGPU_FRONT_NC=4: the round-1 form.
+// ONE form for u8 and fp32 frames: each form sits within tolerance of the reference, but the two are not bit-identical to each other, and the same frames
+// must give the same records whichever way they arrive (tests/test_gpu_round3.py::test_u8_frames_into_the_first_kernel)
+int ffgpu_front_nc(const IrbDesc &d)
+{
+    return env_int("FFGPU_FRONT_NC", 3) == 3 && d.W >= 6 && (d.W + 2) / 3 <= 64 ? 3 : 4;
+}
+
+// forms IN_BGR_FRAMES / IN_NV12_FRAMES (the resizing forms): u8 frames of any size described one by one by the parameter block's frames_tab.  Three
+// columns per lane only: the four-column form of the gather does not fit a wave's registers, so the executor stages those frames (ffgpu_front_nc == 4) instead.
+// Which route NV12 frames take on plans that have the fused form: FFGPU_NV12_FRONT=1 the NV12 form of k_front, =0 staging (k_input4, ffgpu_input.inc);
+// unset: FFGPU_NV12_FRONT_DEFAULT, the outcome of tools/nv12_frames_bench.py (DESIGN 5.15: fused only if it beats staging at four chains by more
+// than the spread of the repeats).  Read at every call: it selects between two graphs, it changes neither.
+#define FFGPU_NV12_FRONT_DEFAULT 0
+bool ffgpu_front_nv12_fused() { return env_int("FFGPU_NV12_FRONT", FFGPU_NV12_FRONT_DEFAULT) != 0; }
+
+int ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, InputForm form, hipStream_t s)
+{
+    const bool u8 = form == IN_U8, resize = form == IN_BGR_FRAMES || form == IN_NV12_FRAMES;
+    if (!ffgpu_front_ok(c, d)) { ffgpu_set_error("front: unsupported layer pair"); return -1; }
+    if ((u8 || resize) && !c.in_ind) { ffgpu_set_error("front: the u8 form needs the executor's parameter block"); return -1; }
+    const int nc = ffgpu_front_nc(d);
+    if (resize && nc != 3) { ffgpu_set_error("front: the resizing form has three columns per lane only (plane width %d)", d.W); return -1; }
+    FrontP p;
+    p.in = c.in; p.in_ind = c.in_ind; p.prm = reinterpret_cast<const ExecParams *>(c.in_ind); p.out = d.out; p.f0 = c.filt; p.w1 = d.w1; p.wd = d.wd; p.w2 = d.w2;
+    p.in_cs = c.in_cs; p.in_ns = c.in_ns;
+    p.W = d.W; p.H = d.H; p.N = d.N;
+    p.band = d.plan.front_band;
+    p.nbands = (d.H + p.band - 1) / p.band;
+    p.ntasks = d.N * p.nbands;
+    p.act0 = act_slope(c.act); p.act1 = act_slope(d.act1); p.actd = act_slope(d.actd); p.act2 = act_slope(d.act2);
+    const dim3 grid((unsigned)((p.ntasks + 3) / 4));
+    if (form == IN_NV12_FRAMES) {
+        hipLaunchKernelGGL((k_front<4, true, 3, true, true>), grid, dim3(256), 0, s, p);
+    } else if (resize) {
+        hipLaunchKernelGGL((k_front<4, true, 3, true>), grid, dim3(256), 0, s, p);
+    } else if (nc == 3) {
+        if (u8) hipLaunchKernelGGL((k_front<4, true, 3>), grid, dim3(256), 0, s, p);
+        else    hipLaunchKernelGGL((k_front<4, false, 3>), grid, dim3(256), 0, s, p);
+    } else {
+        if (u8) hipLaunchKernelGGL((k_front<4, true>), grid, dim3(256), 0, s, p);
+        else    hipLaunchKernelGGL((k_front<4, false>), grid, dim3(256), 0, s, p);   // (8 output channels would need 20 more registers than a wave has)
+    }
+    LAUNCH_OK("front");
+    return 0;
+}
+
+// ---- workgroup form (ffgpu_irb.inc): the fallback
 // expanded channels per chunk: 16 keeps the LDS footprint small (more workgroups per CU), 32 halves the chunk count
 static int irb_ech(const IrbDesc &d)
 {
@@ -1025,8 +1403,6 @@ static int irb_chunk_floats(int k4, int ECH, int OT)
 {
     return (k4 * ECH + ECH * OT * 16 + ECH * IRB_TAPP + ECH * 2 + 3) & ~3;
 }
-
-#define IRB_LDS_MAX (160 * 1024)                     // per workgroup on gfx950
 
 // wbufs = chunk-constant buffers in LDS: nchunks (resident), 2 (streamed through registers) or 1 (single chunk)
 static size_t irb_lds_floats(int k4, int ECH, int OT, int NPin, int wbufs)
@@ -1059,10 +1435,9 @@ static void irb_geometry(const IrbDesc &d, int TH, int TW, int NF, IrbP &p)
     p.tiles_x = (d.OW + TW - 1) / TW; p.tiles_y = (d.OH + TH - 1) / TH;
 }
 
-static bool irb_pick_tile(const IrbDesc &d, IrbP &best)
+static bool irb_pick_tile(const IrbDesc &d, int ECH, IrbP &best)
 {
     const int k4 = (d.ic + 3) & ~3, OT = (d.oc + 15) / 16;
-    const int ECH = irb_ech(d);
     const int nchunks = (d.ec + ECH - 1) / ECH;
     double best_score = -1.0;
     // measured preferences (tools/tune_irb.py, batch 64, profiles/r01_irb_tile_sweep.txt); the scored search
@@ -1121,493 +1496,155 @@ static bool irb_pick_tile(const IrbDesc &d, IrbP &best)
     return best_score > 0;
 }
 
-static bool irb_thin_ok(const IrbDesc &d)
+typedef int (*IrbLaunch)(const IrbP &, const IrbPlan &, hipStream_t);
+struct IrbKernel { int MT, OT, S, NW; IrbLaunch launch; };          // NW waves per workgroup: 8 with one pixel strip per wave, 4 with two
+#define IRB_K(mt, ot) { mt, ot, 1, 8, irb_launch_t<IrbP, k_irb<mt, ot, 1, 1, 8>> }, { mt, ot, 2, 8, irb_launch_t<IrbP, k_irb<mt, ot, 1, 2, 8>> }, \
+                      { mt, ot, 1, 4, irb_launch_t<IrbP, k_irb<mt, ot, 2, 1, 4>> }, { mt, ot, 2, 4, irb_launch_t<IrbP, k_irb<mt, ot, 2, 2, 4>> }
+static const IrbKernel irb_kernels[] = { IRB_K(1, 1), IRB_K(1, 2), IRB_K(1, 3), IRB_K(2, 1), IRB_K(2, 2), IRB_K(2, 3) };
+#undef IRB_K
+
+// the parameter block of a planned k_irb launch: arithmetic on the descriptor and the plan's tile, chunk size, KS, wbufs and red_off
+static IrbP irb_params(const IrbDesc &d)
 {
-    return d.stride == 1 && d.ec == 8 && (d.ic == 4 || d.ic == 8) && (d.oc == 4 || d.oc == 8) && d.W % 4 == 0 && d.W / 4 <= 64 &&
-           8L * d.N * d.W * d.H < (1L << 30) &&          // 32-bit offsets inside a frame-major tensor
-           d.act1 != 3 && d.actd != 3 && d.act2 != 3 && d.res_act != 3 && !env_int("FFGPU_NO_THIN", 0);
-}
-
-template <int IC, int EC, int OC>
-static int irb_thin_launch(const ThinP &p, hipStream_t s)
-{
-    hipLaunchKernelGGL((k_irb_thin<IC, EC, OC>), dim3((unsigned)((p.ntasks + 3) / 4)), dim3(256), 0, s, p);
-    LAUNCH_OK("irb_thin");
-    return 0;
-}
-
-static int launch_irb_thin(const IrbDesc &d, hipStream_t s)
-{
-    auto slope = [](int act) { return act == 2 ? 0.1f : (act == 1 ? 0.f : 1.f); };
-    ThinP p;
-    p.in = d.in; p.out = d.out; p.residual = d.residual; p.w1 = d.w1; p.wd = d.wd; p.w2 = d.w2;
-    p.W = d.W; p.H = d.H; p.N = d.N;
-    // rows per wave: every band expands two extra rows, so long bands waste least -- but the launch wants ~1000 waves;
-    // 16 rows at batch 64 (640 waves, 12 % extra expand work), 2 rows for a single frame (80 waves)
-    int band = 2;
-    while (band < 16 && (long)d.N * d.H >= 640L * band * 2) band *= 2;
-    p.band = env_int("FFGPU_THIN_BAND", band);
-    p.nbands = (d.H + p.band - 1) / p.band;
-    p.act1 = slope(d.act1); p.actd = slope(d.actd); p.act2 = slope(d.act2); p.res_act = slope(d.res_act);
-    p.ntasks = (long)d.N * p.nbands;
-    if (d.ic == 8 && d.oc == 4) return irb_thin_launch<8, 8, 4>(p, s);
-    if (d.ic == 4 && d.oc == 4) return irb_thin_launch<4, 8, 4>(p, s);
-    if (d.ic == 8 && d.oc == 8) return irb_thin_launch<8, 8, 8>(p, s);
-    return irb_thin_launch<4, 8, 8>(p, s);
-}
-
-
-// ---------------------------------------------------------------------------
-// wave-autonomous fused block (ffgpu_irb_wave.inc): shape test, tile / split choice, packing, launch
-struct IrbwCfg { int KS1, OT, NSI, TWq, TH, EW, EH, ngroups, G, WPB; bool big; int NSO; bool x3, xl; };
-
-static bool irbw_has_kernel(int KS1, int OT, int S, int NSI)
-{
-    if (S == 1) return NSI == 2 && ((KS1 == 2 && OT == 1) || (KS1 == 4 && OT == 1) || (KS1 == 6 && OT == 2) || (KS1 == 12 && OT == 3) ||
-                                    (KS1 == 1 && OT == 1) || (KS1 == 2 && OT == 2) || (KS1 == 4 && OT == 2));
-    if (NSI == 4 && OT == 1 && (KS1 == 1 || KS1 == 2)) return env_int("FFGPU_IRBW_S2_NSI4", 0) != 0;     // four-strip halo for the thin stride-2 blocks (12 of 16 output quads instead of 8)
-    return (NSI == 3 && ((KS1 == 1 && OT == 1) || (KS1 == 2 && OT == 1) || (KS1 == 6 && OT == 3 && env_int("FFGPU_IRBW_S2_633", 1)))) || (NSI == 4 && KS1 == 4 && OT == 2);
-}
-
-static bool irbw_pick(const IrbDesc &d, IrbwCfg &c)
-{
-    if (env_int("FFGPU_NO_IRBW", 0)) return false;
-    if (d.stride != 1 && d.stride != 2) return false;
-    if (d.act1 == 3 || d.actd == 3 || d.act2 == 3 || d.res_act == 3) return false;
-    if ((size_t)d.ic * d.N * d.H * d.W >= (1u << 30) || (size_t)d.oc * d.N * d.OH * d.OW >= (1u << 30)) return false;   // 32-bit byte offsets
-    const int S = d.stride;
-    c.KS1 = ((d.ic + 3) & ~3) / 4; c.OT = (d.oc + 15) / 16; c.ngroups = (d.ec + 15) / 16;
-    // output tile of TWq quads x TH rows (<= 16 quads) whose halo fits NSI strips: fewest expand strips over the plane
-    double best = 1e30;
-    for (int TWq = 1; TWq <= 8; TWq++) {
-        if (TWq > 1 && (TWq - 1) * 4 >= d.OW) break;
-        for (int TH = 1; TWq * TH <= 16 && TH <= d.OH + 1; TH++) {
-            const int EW = S == 1 ? 4 * TWq + 4 : 8 * TWq + 4, EH = S * (TH - 1) + 3;
-            int NSI = (EW * EH + 63) / 64;
-            if (NSI < 2) NSI = 2;
-            if (S == 2 && NSI < 3) NSI = 3;
-            if (NSI > 4 || !irbw_has_kernel(c.KS1, c.OT, S, NSI)) continue;
-            const long tiles = (long)((d.OW + 4 * TWq - 1) / (4 * TWq)) * ((d.OH + TH - 1) / TH);
-            // cycles per group, roughly; wide halo rows (EW floats contiguous in memory) load and store better than
-            // tall narrow tiles with the same strip count (profiles/r01_g_irbw_sweep.txt: 20x3 beats 8x8 on 80x80 and 40x40)
-            const double cost = (double)tiles * (NSI * (c.KS1 * 128.0 + 500.0) + 4 * (220.0 + c.OT * 128.0)) * (1.0 + 12.0 / EW);
-            if (cost < best) { best = cost; c.TWq = TWq; c.TH = TH; c.EW = EW; c.EH = EH; c.NSI = NSI; }
-        }
-    }
-    if (best > 1e29) return false;
-    const int ft = env_int("FFGPU_IRBW_TWQ", 0), fh = env_int("FFGPU_IRBW_TH", 0);
-    if (ft > 0 && fh > 0 && ft * fh <= 16) {
-        const int EW = S == 1 ? 4 * ft + 4 : 8 * ft + 4, EH = S * (fh - 1) + 3;
-        if (EW * EH <= c.NSI * 64) { c.TWq = ft; c.TH = fh; c.EW = EW; c.EH = EH; }
-    }
-    const long ntiles = (long)d.N * ((d.OW + 4 * c.TWq - 1) / (4 * c.TWq)) * ((d.OH + c.TH - 1) / c.TH);
-    const int regs = c.NSI * c.KS1 * 4 + c.OT * 16 + 2 * (c.KS1 + 4 * c.OT) + 76;                     // rough VGPR need
-    c.big = regs > 124;
-    // (the BIG instantiation of a shape whose second set of expand accumulators fits is the software-pipelined form;
-    //  it buys a lone wave nothing and costs the many-round launches occupancy, so it is not forced: FFGPU_IRBW_BIG=1)
-    if (env_int("FFGPU_IRBW_BIG", -1) >= 0) c.big = env_int("FFGPU_IRBW_BIG", -1) != 0;                 // tuning only
-    if (S == 2 && c.KS1 == 1 && env_int("FFGPU_IRBW_BIG_S2K1", -1) >= 0) c.big = env_int("FFGPU_IRBW_BIG_S2K1", -1) != 0;   // tuning only: the 160 -> 80 block alone (40 bytes of scratch at 128 registers)
-    // waves sharing a tile: one wave per tile when that already gives every SIMD a wave or more (tools/tune_irbw.py:
-    // the split only pays on the small planes), else the smallest split that does
-    // With several chains in flight (FFGPU_CONCURRENT) other launches fill the SIMDs, and what counts is the work per
-    // wave that a split repeats (input tile, constants, reduction): 4 waves on the 10x10 planes and 2 on the 20x20 ones
-    // instead of 8 and 4 -- 3.5 % more frames/s with four chains, 4 % fewer with one.
-    const bool conc = (d.flags & FFGPU_CONCURRENT) != 0;
-    const int gmax = std::min(8, c.ngroups);
-    int G = 1;
-    for (int g = 1; g <= gmax; g++) {
-        const size_t slot = (size_t)c.OT * 1024, ereg = (size_t)g * 16 * c.NSI * 64;
-        if (g > 1 && ereg / slot < (size_t)(g + 1) / 2) continue;                                      // reduction must fit the E slices
-        G = g;
-        if (ntiles * g >= env_int("FFGPU_IRBW_GWAVES", conc ? 500 : 1200)) break;
-    }
-    if (!conc && G > 1 && G < gmax && c.ngroups % G != 0 && (c.ngroups + G) / (G + 1) <= (c.ngroups + G - 1) / G) G++;   // same trips per wave, better balance
-    // measured exceptions (profiles/r01_g_irbw_sweep.txt, batch 64): four waves on the 20x20 blocks (3, 2, 2, 2 groups
-    // each) beat three by 8 %
-    if (d.stride == 1 && c.ngroups == 9 && ntiles >= 400 && ntiles < 512 && gmax >= 4 && !conc && !env_int("FFGPU_IRBW_NOEXC", 0)) G = 4;
-    if (ntiles >= 256 && ntiles < 1100 && env_int("FFGPU_IRBW_G_MID", 0) > 0) G = std::min(gmax, env_int("FFGPU_IRBW_G_MID", 0));
-    // the LDS-resident split tile (XL, 48 input channels) makes a wave's share of a tile cheaper: with several chains in flight seven waves
-    // (two groups each of the 10x10 blocks' fourteen) beat four by 1.3 % (profiles/r04: 193.8 k against 191.3 k frames/s, eight: 193.4 k)
-    const bool xl_ok = S == 1 && c.KS1 == 12 && c.OT == 3 && c.NSI == 2 && c.big && ((env_int("FFGPU_IRBW_X3", 30) >> 3) & 1) != 0;
-    if (xl_ok && conc && ntiles < 256) G = std::min(gmax, env_int("FFGPU_IRBW_G_XL", 7));
-    if (ntiles < 256 && env_int("FFGPU_IRBW_G_SMALL", 0) > 0) G = std::min(gmax, env_int("FFGPU_IRBW_G_SMALL", 0));          // tuning only (wins over the XL choice)
-    const int fg = env_int("FFGPU_IRBW_G", 0);                      // an explicit FFGPU_IRBW_G wins over everything
-    if (fg >= 1 && fg <= gmax) G = fg;
-    c.G = G;
-    c.NSO = 1;
-    // single-strip kernel, 24 input channels (the 20x20 blocks): expand GEMM as split-bf16 products (bit 2 of FFGPU_IRBW_X3)
-    c.x3 = S == 1 && c.KS1 == 6 && c.OT == 2 && c.NSI == 2 && c.big && ((env_int("FFGPU_IRBW_X3", 30) >> 2) & 1) != 0;
-    // ... the 40 -> 20 stride-2 block (16 input channels, four-strip halo), bit 4
-    if (S == 2 && c.KS1 == 4 && c.OT == 2 && c.NSI == 4 && c.big && ((env_int("FFGPU_IRBW_X3", 30) >> 4) & 1) != 0) c.x3 = true;
-    // ... and 48 input channels with the groups split over G waves (the 10x10 blocks): the split tile lives once per workgroup in LDS (bit 3)
-    c.xl = xl_ok && G > 1;
-    if (c.xl) c.x3 = true;
-    // two output strips per wave (ffgpu_irb_wave2.inc): one wave per tile, <= 16 output channels, stride 1 -- when a tile
-    // of up to 32 quads with a three-strip halo covers the plane with clearly fewer expand strips
-    if (G == 1 && S == 1 && c.OT == 1 && (c.KS1 == 2 || c.KS1 == 4) && env_int("FFGPU_IRBW_NSO", 2) == 2) {
-        double best2 = 1e30; int tw2 = 0, th2 = 0;
-        for (int TWq = 1; TWq <= 8; TWq++) {
-            if (TWq > 1 && (TWq - 1) * 4 >= d.OW) break;
-            for (int TH = 1; TWq * TH <= 32 && TH <= d.OH + 1; TH++) {
-                if (TWq * TH <= 16 || TWq * ((TH + 1) / 2) > 16) continue;                            // a lane owns a quad in each row of a row pair
-                const int EW = 4 * TWq + 4, EH = TH + 2;
-                if (EW * EH > 192) continue;                                                           // three strips
-                const long tiles = (long)((d.OW + 4 * TWq - 1) / (4 * TWq)) * ((d.OH + TH - 1) / TH);
-                const double cost = (double)tiles * (3 * (c.KS1 * 128.0 + 500.0) + 2 * 4 * (220.0 + 128.0)) * (1.0 + 12.0 / EW);
-                if (cost < best2) { best2 = cost; tw2 = TWq; th2 = TH; }
-            }
-        }
-        const int f2t = env_int("FFGPU_IRBW2_TWQ", 0), f2h = env_int("FFGPU_IRBW2_TH", 0);
-        if (f2t > 0 && f2h > 0 && f2t * ((f2h + 1) / 2) <= 16 && (4 * f2t + 4) * (f2h + 2) <= 192) { tw2 = f2t; th2 = f2h; best2 = 0; }
-        const long nt2 = tw2 ? (long)d.N * ((d.OW + 4 * tw2 - 1) / (4 * tw2)) * ((d.OH + th2 - 1) / th2) : 0;
-        if (tw2 && best2 < 0.93 * best && nt2 >= env_int("FFGPU_IRBW2_MIN_TILES", 768)) {
-            c.NSO = 2; c.TWq = tw2; c.TH = th2; c.EW = 4 * tw2 + 4; c.EH = th2 + 2; c.NSI = 3; c.big = true; c.WPB = 4; c.xl = false;
-            // the expand GEMM as exact split-bf16 products on the bf16 matrix cores (ffgpu_irb_wave.inc "X3"); FFGPU_IRBW_X3=0: fp32 MFMAs
-            c.x3 = irbw_x3_has(c.KS1) && ((env_int("FFGPU_IRBW_X3", 30) >> (c.KS1 == 2 ? 0 : 1)) & 1) != 0;   // (bit 0: 8 input channels, bit 1: 16)
-        }
-    }
-    // tiles per workgroup (G == 1): whichever of 4 / 8 waves lets more waves share a CU's 160 KB of LDS
-    {
-        const size_t cs = ((size_t)c.ngroups * 224 + c.OT * 32) * sizeof(float), slice = (size_t)16 * c.NSI * 64 * sizeof(float);
-        const int cap = c.big ? 12 : 16;                                                               // VGPR-limited waves per CU
-        const int w4 = std::min(cap, (int)(IRB_LDS_MAX / (cs + 4 * slice)) * 4), w8 = std::min(cap, (int)(IRB_LDS_MAX / (cs + 8 * slice)) * 8);
-        c.WPB = G > 1 ? G : (w4 >= w8 ? 4 : 8);                                                       // tie: the finer granule (1.3 % with four chains in flight)
-        const int fw = env_int("FFGPU_IRBW_WPB", 0);
-        if (G == 1 && fw >= 1 && fw <= 8) c.WPB = fw;
-    }
-    return true;
-}
-
-// a last group of at most 8 real channels in the single-strip kernel: packed into registers 0 / 1, the other half of its work skipped (ffgpu_irb_wave.inc irbw_chan)
-static int irbw_half(const IrbDesc &d, const IrbwCfg &c)
-{
-    const int r = d.ec & 15;
-    const bool on = d.half ? d.half == 2 : env_int("FFGPU_IRBW_HALF", 1) != 0;       // a planned block carries the decision (ffgpu_irb_plan): pack and launch cannot disagree
-    return c.NSO == 1 && r >= 1 && r <= 8 && on ? 1 : 0;
-}
-
-static void irbw_layout(const IrbwCfg &c, int &o_w2, int &o_cs, int &cs_floats, int &total)
-{
-    o_w2 = c.x3 ? c.ngroups * irbw_x3_nm(c.KS1) * 256 : c.ngroups * c.KS1 * 64;
-    o_cs = o_w2 + c.ngroups * 4 * c.OT * 64;
-    cs_floats = c.ngroups * 16 * 14 + c.OT * 32;
-    total = o_cs + cs_floats;
-}
-
-// tuning only (make TRACE=1 / -DIRB_TRACE=1, FFGPU_IRB_TRACE=1): in-kernel timeline of wave 0 of each workgroup of one k_irbw launch, printed per launch;
-// `launch(q)` launches the kernel with the parameter block that carries the timestamp buffer
-template <typename L>
-static int irbw_traced(const IrbwP &p, long nblocks, hipStream_t s, L launch)
-{
-    {
-        static unsigned long long *d_t = nullptr;
-        if (!d_t && hipMalloc(&d_t, 4096 * 16 * sizeof(unsigned long long)) != hipSuccess) return -1;
-        IrbwP q = p; q.dbg_t = d_t;
-        (void)hipMemsetAsync(d_t, 0, 4096 * 16 * sizeof(unsigned long long), s);
-        launch(q);
-        (void)hipStreamSynchronize(s);
-        const long nb = std::min(nblocks, 4096L);
-        std::vector<unsigned long long> h((size_t)nb * 16);
-        (void)hipMemcpy(h.data(), d_t, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-        unsigned long long t0 = ~0ull, t1 = 0; double d[5] = { 0 }, ex[6] = { 0 }; double late = 0;
-        for (long b = 0; b < nb; b++) { t0 = std::min(t0, h[b * 16]); t1 = std::max(t1, h[b * 16 + 5]); }
-        for (long b = 0; b < nb; b++) {
-            late = std::max(late, (double)(h[b * 16] - t0) * 0.01);
-            d[0] += (double)(h[b * 16 + 1] - h[b * 16]) / nb * 0.01; d[1] += (double)(h[b * 16 + 2] - h[b * 16 + 1]) / nb * 0.01;
-            d[2] += (double)(h[b * 16 + 3] - h[b * 16 + 2]) / nb * 0.01;
-            const unsigned long long t4 = h[b * 16 + 4] ? h[b * 16 + 4] : h[b * 16 + 3];
-            d[3] += (double)(t4 - h[b * 16 + 3]) / nb * 0.01; d[4] += (double)(h[b * 16 + 5] - t4) / nb * 0.01;
-            for (int k = 0; k < 6; k++) ex[k] += (double)h[b * 16 + 8 + k] / nb * 0.01;
-        }
-        fprintf(stderr, "  trace irbw %dx%d %d->%d->%d: span %.2f us (first %ld blocks), last start +%.2f | issue loads %.2f barrier %.2f groups %.2f [expand mfma %.2f store %.2f dw0 %.2f prj0 %.2f dw1 %.2f prj1 %.2f] reduce %.2f rows %.2f (us, wave 0, mean per workgroup)\n",
-                p.W, p.H, p.ic, p.ec, p.oc, (double)(t1 - t0) * 0.01, nb, late, d[0], d[1], d[2], ex[0], ex[1], ex[2], ex[3], ex[4], ex[5], d[3], d[4]);
-        return 0;
-    }
-}
-
-template <int KS1, int OT, int S, int NSI, bool BIG>
-static int irbw_launch_t(const IrbwP &p, size_t lds, long nblocks, int threads, hipStream_t s)
-{
-    if (lds_allow((const void *)k_irbw<KS1, OT, S, NSI, BIG>, lds, "irbw")) return -1;
-    if (env_int("FFGPU_IRB_TRACE", 0))
-        return irbw_traced(p, nblocks, s, [&](const IrbwP &q) { hipLaunchKernelGGL((k_irbw<KS1, OT, S, NSI, BIG>), dim3((unsigned)nblocks), dim3(threads), lds, s, q); });
-    hipLaunchKernelGGL((k_irbw<KS1, OT, S, NSI, BIG>), dim3((unsigned)nblocks), dim3(threads), lds, s, p);
-    LAUNCH_OK("irbw");
-    return 0;
-}
-
-static int launch_irbw(const IrbDesc &d, const IrbwCfg &c, hipStream_t s)
-{
-    auto slope = [](int act) { return act == 2 ? 0.1f : (act == 1 ? 0.f : 1.f); };
-    IrbwP p;
+    const IrbPlan &c = d.plan;
+    IrbP p;
+    irb_geometry(d, c.TH, c.TW, c.NF, p);
     p.in = d.in; p.out = d.out; p.residual = d.residual; p.pk = d.pk;
-    p.N = d.N; p.H = d.H; p.W = d.W; p.OH = d.OH; p.OW = d.OW; p.ic = d.ic; p.ec = d.ec; p.oc = d.oc;
-    p.act1 = slope(d.act1); p.actd = slope(d.actd); p.act2 = slope(d.act2); p.res_act = slope(d.res_act);
-    p.TWq = c.TWq; p.TH = c.TH; p.EW = c.EW; p.EH = c.EH;
-    p.tiles_x = (d.OW + 4 * c.TWq - 1) / (4 * c.TWq); p.tiles_y = (d.OH + c.TH - 1) / c.TH;
-    p.ntiles = (long)d.N * p.tiles_x * p.tiles_y;
-    p.ngroups = c.ngroups; p.G = c.G; p.WPB = c.WPB;
-    p.half_last = irbw_half(d, c);
-    { const int x = env_int("FFGPU_IRBW_XCD", 3); p.xcd = c.G > 1 ? (x >> 1) & 1 : x & 1; }        // bit 0: one wave per tile, bit 1: group-split launches
-    int total;
-    irbw_layout(c, p.o_w2, p.o_cs, p.cs_floats, total);
-    // floats behind the shared constants: the waves' E slices, later the partial sums of the group split -- room for all
-    // G of them when the launch leaves the CU's LDS to one workgroup anyway (no folding rounds: two barriers fewer)
-    size_t region = (size_t)(c.G > 1 ? c.G : c.WPB) * 16 * c.NSI * 64;
-    if (c.G > 1 && !env_int("FFGPU_IRBW_FOLD", 0)) {
-        const size_t want = (size_t)c.G * c.OT * 1024;
-        if (want > region && (p.cs_floats + want) * sizeof(float) <= 150 * 1024 && p.ntiles <= 512) region = want;
-    }
-    p.red_cap = (int)(region / ((size_t)c.OT * 1024));
-    p.in_elems = (unsigned)((size_t)d.ic * d.N * d.H * d.W);
-    p.vec = d.OW % 4 == 0 ? 4 : (d.OW % 2 == 0 ? 2 : 1);
-    p.m_ew = (unsigned)(((1ULL << 32) + c.EW - 1) / c.EW);
-    {
-        auto magic = [](long dv) { return dv <= 1 ? 0u : (unsigned)(((1ULL << 32) + (unsigned long long)dv - 1) / (unsigned long long)dv); };
-        if (p.ntiles * std::max(p.tiles_x, p.tiles_y) >= (1L << 32) || p.ntiles >= (1L << 31)) { ffgpu_set_error("irbw: too many tiles for 32-bit index arithmetic"); return -1; }
-        p.m_tx = magic(p.tiles_x); p.m_ty = magic(p.tiles_y); p.m_twq = magic(p.TWq);
-    }
-    p.dbg_t = nullptr;
-    const int waves = c.G > 1 ? c.G : c.WPB;
-    p.xl_off = (int)((size_t)p.cs_floats + region);
-    const size_t lds = ((size_t)p.cs_floats + region + (c.xl ? (size_t)c.NSI * 4 * 64 * IRBW_XL_DW : 0)) * sizeof(float);
-    const long nblocks = c.G > 1 ? p.ntiles : (p.ntiles + c.WPB - 1) / c.WPB;
-    if (env_int("FFGPU_VERBOSE_IRB", 0))
-        fprintf(stderr, "irbw %dx%d %d->%d->%d s%d: tile %dx%d halo %dx%d (%d strips, %d out), %d groups, G %d, %ld tiles, %ld blocks x %d waves, lds %zu B%s\n",
-                d.W, d.H, d.ic, d.ec, d.oc, d.stride, 4 * c.TWq, c.TH, c.EW, c.EH, c.NSI, c.NSO, c.ngroups, c.G, p.ntiles, nblocks, waves, lds, c.big ? ", 256 VGPR" : "");
-    if (c.NSO == 2) {
-        if (c.KS1 == 2 && c.x3)  { hipLaunchKernelGGL((k_irbw2<2, 3, true>), dim3((unsigned)nblocks), dim3(waves * 64), lds, s, p); LAUNCH_OK("irbw2"); return 0; }
-        if (c.KS1 == 4 && c.x3)  { hipLaunchKernelGGL((k_irbw2<4, 3, true>), dim3((unsigned)nblocks), dim3(waves * 64), lds, s, p); LAUNCH_OK("irbw2"); return 0; }
-        if (c.KS1 == 2) { hipLaunchKernelGGL((k_irbw2<2, 3, false>), dim3((unsigned)nblocks), dim3(waves * 64), lds, s, p); LAUNCH_OK("irbw2"); return 0; }
-        if (c.KS1 == 4) { hipLaunchKernelGGL((k_irbw2<4, 3, false>), dim3((unsigned)nblocks), dim3(waves * 64), lds, s, p); LAUNCH_OK("irbw2"); return 0; }
-    }
-    if (c.xl && c.NSO == 1) {
-        if (lds_allow((const void *)k_irbw<12, 3, 1, 2, true, true, true>, lds, "irbw")) return -1;
-        if (env_int("FFGPU_IRB_TRACE", 0))
-            return irbw_traced(p, nblocks, s, [&](const IrbwP &q) { hipLaunchKernelGGL((k_irbw<12, 3, 1, 2, true, true, true>), dim3((unsigned)nblocks), dim3(waves * 64), lds, s, q); });
-        hipLaunchKernelGGL((k_irbw<12, 3, 1, 2, true, true, true>), dim3((unsigned)nblocks), dim3(waves * 64), lds, s, p);
-        LAUNCH_OK("irbw");
-        return 0;
-    }
-    if (c.x3 && c.NSO == 1 && c.KS1 == 4 && c.OT == 2 && d.stride == 2 && c.NSI == 4) {
-        if (lds_allow((const void *)k_irbw<4, 2, 2, 4, true, true>, lds, "irbw")) return -1;
-        if (env_int("FFGPU_IRB_TRACE", 0))
-            return irbw_traced(p, nblocks, s, [&](const IrbwP &q) { hipLaunchKernelGGL((k_irbw<4, 2, 2, 4, true, true>), dim3((unsigned)nblocks), dim3(waves * 64), lds, s, q); });
-        hipLaunchKernelGGL((k_irbw<4, 2, 2, 4, true, true>), dim3((unsigned)nblocks), dim3(waves * 64), lds, s, p);
-        LAUNCH_OK("irbw");
-        return 0;
-    }
-    if (c.x3 && c.NSO == 1 && c.KS1 == 6 && c.OT == 2 && d.stride == 1 && c.NSI == 2) {
-        if (lds_allow((const void *)k_irbw<6, 2, 1, 2, true, true>, lds, "irbw")) return -1;
-        if (env_int("FFGPU_IRB_TRACE", 0))
-            return irbw_traced(p, nblocks, s, [&](const IrbwP &q) { hipLaunchKernelGGL((k_irbw<6, 2, 1, 2, true, true>), dim3((unsigned)nblocks), dim3(waves * 64), lds, s, q); });
-        hipLaunchKernelGGL((k_irbw<6, 2, 1, 2, true, true>), dim3((unsigned)nblocks), dim3(waves * 64), lds, s, p);
-        LAUNCH_OK("irbw");
-        return 0;
-    }
-#define IRBW_CASE(ks1, ot, st, nsi) if (c.KS1 == ks1 && c.OT == ot && d.stride == st && c.NSI == nsi) \
-        return c.big ? irbw_launch_t<ks1, ot, st, nsi, true>(p, lds, nblocks, waves * 64, s) : irbw_launch_t<ks1, ot, st, nsi, false>(p, lds, nblocks, waves * 64, s);
-    IRBW_CASE(1, 1, 1, 2); IRBW_CASE(2, 1, 1, 2); IRBW_CASE(4, 1, 1, 2); IRBW_CASE(2, 2, 1, 2); IRBW_CASE(4, 2, 1, 2); IRBW_CASE(6, 2, 1, 2); IRBW_CASE(12, 3, 1, 2);
-    IRBW_CASE(1, 1, 2, 3); IRBW_CASE(2, 1, 2, 3); IRBW_CASE(4, 2, 2, 4); IRBW_CASE(6, 3, 2, 3); IRBW_CASE(1, 1, 2, 4); IRBW_CASE(2, 1, 2, 4);
-#undef IRBW_CASE
-    ffgpu_set_error("irbw: no instantiation for KS1=%d OT=%d S=%d NSI=%d", c.KS1, c.OT, d.stride, c.NSI);
-    return -1;
+    p.N = d.N; p.H = d.H; p.W = d.W; p.OH = d.OH; p.OW = d.OW; p.ic = d.ic; p.ec = d.ec; p.oc = d.oc; p.stride = d.stride;
+    p.act1 = act_slope(d.act1); p.actd = act_slope(d.actd); p.act2 = act_slope(d.act2); p.res_act = act_slope(d.res_act);
+    p.k4 = (d.ic + 3) & ~3; p.ECH = c.ECH; p.nchunks = (d.ec + c.ECH - 1) / c.ECH; p.CH = irb_chunk_floats(p.k4, c.ECH, c.OT);
+    p.vec_store = (d.OW % 4 == 0) && (p.TW % 4 == 0);
+    p.dbg_skip = env_int("FFGPU_IRB_SKIP", 0); p.dbg_t = nullptr;
+    p.ntiles = p.tiles_x * p.tiles_y * ((d.N + p.NF - 1) / p.NF);
+    p.KS = c.KS; p.red_off = c.red_off;
+    p.resident = p.nchunks > 1 && c.wbufs == p.nchunks;
+    const int nsi = p.NPin / 64;
+    p.inv_nsi = (65536 + nsi - 1) / nsi;
+    return p;
 }
 
-bool ffgpu_irb_is_thin(const IrbDesc &d) { return irb_thin_ok(d); }
-
-// ---- first layer + first thin block as one kernel (ffgpu_front.inc): the planner asks, then launches
-bool ffgpu_front_ok(const ConvDesc &c, const IrbDesc &d)
+static bool irb_plan_wg(IrbDesc &d)
 {
-    return c.fs == 3 && c.stride == 2 && c.pad == 1 && c.groups == 1 && c.ic == 3 && c.oc == 8 && !c.residual && c.act != 3 &&
-           c.iw == 2 * c.ow && c.ih == 2 * c.oh && c.ow % 4 == 0 && c.ow / 4 <= 64 && c.in_cs % 4 == 0 && c.in_ns % 4 == 0 &&
-           3 * c.in_cs < (1L << 30) && c.out == d.in && irb_thin_ok(d) && d.ic == 8 && d.ec == 8 && d.oc == 4 && !d.residual &&
-           d.W == c.ow && d.H == c.oh && d.N == c.N &&
-           (long)c.N * c.oh * c.ow >= env_int("FFGPU_FRONT_MIN_PX", 262144) && !env_int("FFGPU_NO_FRONT", 0);
-}
-
-// form IN_U8: the frames of this forward are u8 BGR images described by the executor's parameter block (c.in_ind IS that block: its
-// first member is the fp32 frame pointer the IN_F32 form reads)
-// three columns per lane (54 of 64 lanes on a 160-pixel row instead of 40) where the row fits a wave that way; FFGPU_FRONT_NC=4: the round-1 form.
-// ONE form for u8 and fp32 frames: each form sits within tolerance of the reference, but the two are not bit-identical to each other, and the same frames
-// must give the same records whichever way they arrive (tests/test_gpu_round3.py::test_u8_frames_into_the_first_kernel)
-int ffgpu_front_nc(const IrbDesc &d)
-{
-    return env_int("FFGPU_FRONT_NC", 3) == 3 && d.W >= 6 && (d.W + 2) / 3 <= 64 ? 3 : 4;
-}
-
-// forms IN_BGR_FRAMES / IN_NV12_FRAMES (the resizing forms): u8 frames of any size described one by one by the parameter block's frames_tab.  Three
-// columns per lane only: the four-column form of the gather does not fit a wave's registers, so the executor stages those frames (ffgpu_front_nc == 4) instead.
-// Which route NV12 frames take on plans that have the fused form: FFGPU_NV12_FRONT=1 the NV12 form of k_front, =0 staging (k_input4, ffgpu_input.inc);
-// unset: FFGPU_NV12_FRONT_DEFAULT, the outcome of tools/nv12_frames_bench.py (DESIGN 5.15: fused only if it beats staging at four chains by more
-// than the spread of the repeats).  Read at every call: it selects between two graphs, it changes neither.
-#define FFGPU_NV12_FRONT_DEFAULT 0
-bool ffgpu_front_nv12_fused() { return env_int("FFGPU_NV12_FRONT", FFGPU_NV12_FRONT_DEFAULT) != 0; }
-
-int ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, InputForm form, hipStream_t s)
-{
-    const bool u8 = form == IN_U8, resize = form == IN_BGR_FRAMES || form == IN_NV12_FRAMES;
-    if (!ffgpu_front_ok(c, d)) { ffgpu_set_error("front: unsupported layer pair"); return -1; }
-    if ((u8 || resize) && !c.in_ind) { ffgpu_set_error("front: the u8 form needs the executor's parameter block"); return -1; }
-    const int nc = ffgpu_front_nc(d);
-    if (resize && nc != 3) { ffgpu_set_error("front: the resizing form has three columns per lane only (plane width %d)", d.W); return -1; }
-    auto slope = [](int act) { return act == 2 ? 0.1f : (act == 1 ? 0.f : 1.f); };
-    FrontP p;
-    p.in = c.in; p.in_ind = c.in_ind; p.prm = reinterpret_cast<const ExecParams *>(c.in_ind); p.out = d.out; p.f0 = c.filt; p.w1 = d.w1; p.wd = d.wd; p.w2 = d.w2;
-    p.in_cs = c.in_cs; p.in_ns = c.in_ns;
-    p.W = d.W; p.H = d.H; p.N = d.N;
-    int band = 2;
-    while (band < 16 && (long)d.N * d.H >= 640L * band * 2) band *= 2;
-    p.band = env_int("FFGPU_FRONT_BAND", band);
-    p.nbands = (d.H + p.band - 1) / p.band;
-    p.ntasks = d.N * p.nbands;
-    p.act0 = slope(c.act); p.act1 = slope(d.act1); p.actd = slope(d.actd); p.act2 = slope(d.act2);
-    const dim3 grid((unsigned)((p.ntasks + 3) / 4));
-    if (form == IN_NV12_FRAMES) {
-        hipLaunchKernelGGL((k_front<4, true, 3, true, true>), grid, dim3(256), 0, s, p);
-    } else if (resize) {
-        hipLaunchKernelGGL((k_front<4, true, 3, true>), grid, dim3(256), 0, s, p);
-    } else if (nc == 3) {
-        if (u8) hipLaunchKernelGGL((k_front<4, true, 3>), grid, dim3(256), 0, s, p);
-        else    hipLaunchKernelGGL((k_front<4, false, 3>), grid, dim3(256), 0, s, p);
-    } else {
-        if (u8) hipLaunchKernelGGL((k_front<4, true>), grid, dim3(256), 0, s, p);
-        else    hipLaunchKernelGGL((k_front<4, false>), grid, dim3(256), 0, s, p);   // (8 output channels would need 20 more registers than a wave has)
-    }
-    LAUNCH_OK("front");
-    return 0;
-}
-
-bool ffgpu_irb_supported(const IrbDesc &d)
-{
-    if (irb_thin_ok(d)) return true;
-    { IrbwCfg c; if (irbw_pick(d, c)) return true; }
+    IrbPlan &c = d.plan;
     if (d.stride != 1 && d.stride != 2) return false;
     if (d.oc > 48 || d.ic > 64 || d.ec < 1) return false;
     if (d.act1 == 3 || d.actd == 3 || d.act2 == 3 || d.res_act == 3) return false;
     if (((long)d.H * d.W) % 4 || ((long)d.OH * d.OW) % 4) return false;      // CNHW planes stay 16-byte aligned
     IrbP p;
-    return irb_pick_tile(d, p);
+    c.ECH = irb_ech(d); c.OT = (d.oc + 15) / 16;
+    if (!irb_pick_tile(d, c.ECH, p)) return false;
+    c.family = IRB_WG; c.TH = p.TH; c.TW = p.TW; c.NF = p.NF;
+    p = irb_params(d);                                               // (KS, wbufs and red_off follow)
+    c.pack_floats = (int)(((size_t)p.nchunks * p.CH + c.OT * 32 + 63) & ~(size_t)63);
+    const int nso = (p.NPout + 63) / 64, nsi = p.NPin / 64;
+    c.NW = env_int("FFGPU_IRB_NW", 8) == 4 ? 4 : 8;                  // waves per workgroup
+    c.KS = 1;
+    while (c.KS * 2 * nso <= c.NW && c.KS < 4) c.KS *= 2;            // idle waves take slices of the channel loop
+    if (env_int("FFGPU_IRB_NOKS", 0)) c.KS = 1;
+    c.wbufs = irb_wbufs(p.k4, p.ECH, c.OT, p.NPin, p.nchunks, p.ntiles);
+    for (int wi = 0; wi < p.k4 * nsi; wi++)
+        if (((wi * p.inv_nsi) >> 16) != wi / nsi) { ffgpu_set_error("irb: strip reciprocal inexact (k4 %d, %d strips)", p.k4, nsi); return false; }
+    size_t lds = irb_lds_floats(p.k4, p.ECH, c.OT, p.NPin, c.wbufs) * sizeof(float);
+    for (;; c.KS /= 2) {                                             // reduce-scatter scratch: alias In..E when it fits, else append
+        const size_t need = c.KS > 1 ? (size_t)c.KS * nso * c.OT * 1024 : 0;
+        // (a workgroup that runs a single tile is done with Msk and the chunk constants too by then)
+        const size_t alias_cap = (size_t)(p.k4 + p.ECH) * p.NPin + (p.ntiles <= 256 ? (size_t)p.NPin + (size_t)c.wbufs * p.CH : 0);
+        if (need <= alias_cap) break;
+        if (lds + need * sizeof(float) <= IRB_LDS_MAX) { c.red_off = (int)(lds / sizeof(float)); lds += need * sizeof(float); break; }
+    }
+    const int bpc = std::max(1, std::min(4, (int)(IRB_LDS_MAX / lds)));
+    c.lds = (int)lds; c.grid = (int)std::min(256L * bpc, (long)p.ntiles); c.block = c.NW * 64;
+    for (int i = 0; i < (int)(sizeof irb_kernels / sizeof irb_kernels[0]); i++)
+        if (irb_kernels[i].MT == c.ECH / 16 && irb_kernels[i].OT == c.OT && irb_kernels[i].S == d.stride && irb_kernels[i].NW == c.NW) { c.inst = i; return true; }
+    return false;                                                    // (unreachable: ECH is 16 or 32, OT <= 3)
 }
 
-static void irb_consts(const IrbDesc &d, int &k4, int &ECH, int &MT, int &OT, int &nchunks, int &CH)
+bool ffgpu_irb_plan(IrbDesc &d)
 {
-    k4 = (d.ic + 3) & ~3; OT = (d.oc + 15) / 16;
-    ECH = irb_ech(d); MT = ECH / 16;
-    nchunks = (d.ec + ECH - 1) / ECH;
-    CH = irb_chunk_floats(k4, ECH, OT);
+    IrbPlan &c = d.plan;
+    c = IrbPlan{};
+    if (irb_thin_ok(d)) {
+        const int band = thin_band(d.N, d.H);
+        c.family = IRB_THIN; c.pack_floats = 64;
+        c.band = env_int("FFGPU_THIN_BAND", band); c.front_band = env_int("FFGPU_FRONT_BAND", band);
+        c.grid = (int)((thin_params(d).ntasks + 3) / 4); c.block = 256;
+        return true;
+    }
+    if (irb_plan_wave(d)) return true;
+    c = IrbPlan{};
+    if (irb_plan_wg(d)) return true;
+    c = IrbPlan{};
+    return false;
 }
 
-size_t ffgpu_irb_pack_floats(const IrbDesc &d)
+static bool irb_planned(const IrbDesc &d, const char *who)
 {
-    if (irb_thin_ok(d)) return 64;                     // the streaming kernel reads the filter rows directly
-    { IrbwCfg c; if (irbw_pick(d, c)) { int a, b, cs, total; irbw_layout(c, a, b, cs, total); return (size_t)total; } }
-    int k4, ECH, MT, OT, nchunks, CH;
-    irb_consts(d, k4, ECH, MT, OT, nchunks, CH);
-    return ((size_t)nchunks * CH + OT * 32 + 63) & ~(size_t)63;
+    if (d.plan.family == IRB_NONE) ffgpu_set_error("%s: the block has no plan (ffgpu_irb_plan has not run on it, or refused it)", who);
+    return d.plan.family != IRB_NONE;
 }
 
-void ffgpu_irb_plan(IrbDesc &d) { d.half = env_int("FFGPU_IRBW_HALF", 1) != 0 ? 2 : 1; }
+size_t ffgpu_irb_pack_floats(const IrbDesc &d) { return irb_planned(d, "irb_pack_floats") ? (size_t)d.plan.pack_floats : 0; }
 
 int ffgpu_irb_pack(const IrbDesc &d, float *pk, hipStream_t s)
 {
-    if (irb_thin_ok(d)) return 0;
-    { IrbwCfg c;
-      if (irbw_pick(d, c)) {
-          int a, b, cs, total; irbw_layout(c, a, b, cs, total);
-          IrbwPackP q; q.w1 = d.w1; q.wd = d.wd; q.w2 = d.w2; q.pk = pk; q.ic = d.ic; q.ec = d.ec; q.oc = d.oc;
-          q.k4 = (d.ic + 3) & ~3; q.OT = c.OT; q.ngroups = c.ngroups; q.x3 = c.x3 ? 1 : 0; q.half = irbw_half(d, c);
-          hipLaunchKernelGGL(k_irbw_pack, dim3((total + 255) / 256), dim3(256), 0, s, q);
-          LAUNCH_OK("irbw_pack");
-          return 0;
-      } }
+    const IrbPlan &c = d.plan;
+    if (!irb_planned(d, "irb_pack")) return -1;
+    if (c.family == IRB_THIN) return 0;
+    if (c.family == IRB_WAVE) {
+        IrbwPackP q; q.w1 = d.w1; q.wd = d.wd; q.w2 = d.w2; q.pk = pk; q.ic = d.ic; q.ec = d.ec; q.oc = d.oc;
+        q.k4 = (d.ic + 3) & ~3; q.OT = c.OT; q.ngroups = c.ngroups; q.x3 = c.x3; q.half = c.half;
+        hipLaunchKernelGGL(k_irbw_pack, dim3((c.pack_floats + 255) / 256), dim3(256), 0, s, q);
+        LAUNCH_OK("irbw_pack");
+        return 0;
+    }
     IrbPackP q;
     q.w1 = d.w1; q.wd = d.wd; q.w2 = d.w2; q.pk = pk;
     q.ic = d.ic; q.ec = d.ec; q.oc = d.oc;
-    irb_consts(d, q.k4, q.ECH, q.MT, q.OT, q.nchunks, q.CH);
+    q.k4 = (d.ic + 3) & ~3; q.ECH = c.ECH; q.MT = c.ECH / 16; q.OT = c.OT; q.nchunks = (d.ec + c.ECH - 1) / c.ECH; q.CH = irb_chunk_floats(q.k4, c.ECH, c.OT);
     const int total = q.nchunks * q.CH + q.OT * 32;
     hipLaunchKernelGGL(k_irb_pack, dim3((total + 255) / 256), dim3(256), 0, s, q);
     LAUNCH_OK("irb_pack");
     return 0;
 }
 
-template <int MT, int OT, int S, int SPW, int NW>
-static int irb_launch_t(const IrbP &p, size_t lds, long nblocks, hipStream_t s)
+// One canonical line per planned block (the probe behind ffgpu_irb_plan_text, tests/test_irb_choice.py; FFGPU_VERBOSE_IRB prints it per launch): family and instantiation, every scalar of
+// the parameter block the launch would pass, the launch shape, `half` and the size of the packed image
+int ffgpu_irb_plan_line(const IrbDesc &d, char *buf, size_t cap)
 {
-    if (lds_allow((const void *)k_irb<MT, OT, SPW, S, NW>, lds, "irb")) return -1;
-    if (env_int("FFGPU_IRB_TRACE", 0)) {             // tuning only: in-kernel timeline, printed per launch
-        static unsigned long long *d_t = nullptr;
-        if (!d_t && hipMalloc(&d_t, 4096 * 16 * sizeof(unsigned long long)) != hipSuccess) return -1;
-        IrbP q = p; q.dbg_t = d_t;
-        (void)hipMemsetAsync(d_t, 0, 4096 * 16 * sizeof(unsigned long long), s);
-        hipLaunchKernelGGL((k_irb<MT, OT, SPW, S, NW>), dim3((unsigned)nblocks), dim3(NW * 64), lds, s, q);
-        (void)hipStreamSynchronize(s);
-        std::vector<unsigned long long> h((size_t)nblocks * 16);
-        (void)hipMemcpy(h.data(), d_t, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-        unsigned long long t0 = ~0ull, t1 = 0; double d[7] = { 0 }, ph[4] = { 0 };
-        for (long b = 0; b < nblocks; b++) {
-            t0 = std::min(t0, h[b * 16]); t1 = std::max(t1, h[b * 16 + 7]);
-            for (int k = 0; k < 7; k++) d[k] += (double)(h[b * 16 + k + 1] - h[b * 16 + k]) / nblocks * 0.01;
-            for (int k = 0; k < 4; k++) ph[k] += (double)h[b * 16 + 8 + k] / nblocks * 0.01;
-        }
-        double late = 0; for (long b = 0; b < nblocks; b++) late = std::max(late, (double)(h[b * 16] - t0) * 0.01);
-        fprintf(stderr, "  trace %dx%d %d->%d->%d: span %.2f us, last start +%.2f | consts %.2f wait %.2f load %.2f chunks %.2f [bar1 %.2f expand %.2f bar2 %.2f dw+project %.2f] reduce %.2f epilogue %.2f other-tiles %.2f (us, mean per workgroup, first tile)\n",
-                p.W, p.H, p.ic, p.ec, p.oc, (double)(t1 - t0) * 0.01, late, d[0], d[1], d[2], d[3], ph[0], ph[1], ph[2], ph[3], d[4], d[5], d[6]);
-        return 0;
+    const IrbPlan &c = d.plan;
+    if (c.family == IRB_THIN) {
+        const ThinP p = thin_params(d);
+        return snprintf(buf, cap, "thin<%d,8,%d> W=%d H=%d N=%d band=%d nbands=%d act=%g,%g,%g,%g ntasks=%ld lds=%d grid=%d block=%d half=%d pack=%d",
+                        d.ic, d.oc, p.W, p.H, p.N, p.band, p.nbands, p.act1, p.actd, p.act2, p.res_act, p.ntasks, c.lds, c.grid, c.block, c.half, c.pack_floats);
     }
-    hipLaunchKernelGGL((k_irb<MT, OT, SPW, S, NW>), dim3((unsigned)nblocks), dim3(NW * 64), lds, s, p);
-    LAUNCH_OK("irb");
-    return 0;
+    if (c.family == IRB_WAVE) {
+        const IrbwP p = irbw_params(d);
+        const IrbwKernel &k = irbw_kernels[c.inst];
+        char key[48];
+        if (k.NSO == 2) snprintf(key, sizeof key, "irbw2<%d,%d%s>", k.KS1, k.NSI, k.x3 ? ",x3" : "");
+        else snprintf(key, sizeof key, "irbw<%d,%d,%d,%d%s%s%s>", k.KS1, k.OT, k.S, k.NSI, k.big ? ",big" : "", k.x3 ? ",x3" : "", k.xl ? ",xl" : "");
+        return snprintf(buf, cap, "%s N=%d H=%d W=%d OH=%d OW=%d ic=%d ec=%d oc=%d act=%g,%g,%g,%g tile=%d,%d,%d,%d tiles=%d,%d,%ld ngroups=%d G=%d WPB=%d o_w2=%d o_cs=%d cs_floats=%d "
+                        "xl_off=%d red_cap=%d in_elems=%u vec=%d half_last=%d m=%u,%u,%u,%u xcd=%d lds=%d grid=%d block=%d half=%d pack=%d",
+                        key, p.N, p.H, p.W, p.OH, p.OW, p.ic, p.ec, p.oc, p.act1, p.actd, p.act2, p.res_act, p.TWq, p.TH, p.EW, p.EH, p.tiles_x, p.tiles_y, p.ntiles, p.ngroups, p.G, p.WPB,
+                        p.o_w2, p.o_cs, p.cs_floats, p.xl_off, p.red_cap, p.in_elems, p.vec, p.half_last, p.m_ew, p.m_tx, p.m_ty, p.m_twq, p.xcd, c.lds, c.grid, c.block, c.half, c.pack_floats);
+    }
+    if (c.family == IRB_WG) {
+        const IrbP p = irb_params(d);
+        const IrbKernel &k = irb_kernels[c.inst];
+        return snprintf(buf, cap, "irb<%d,%d,%d,%d,%d> N=%d H=%d W=%d OH=%d OW=%d ic=%d ec=%d oc=%d stride=%d act=%g,%g,%g,%g tile=%d,%d,%d,%d,%d,%d NPin=%d NPout=%d tiles=%d,%d,%d "
+                        "k4=%d nchunks=%d ECH=%d CH=%d KS=%d red_off=%d vec_store=%d resident=%d inv_nsi=%d lds=%d grid=%d block=%d half=%d pack=%d",
+                        k.MT, k.OT, k.S, k.NW == 8 ? 1 : 2, k.NW, p.N, p.H, p.W, p.OH, p.OW, p.ic, p.ec, p.oc, p.stride, p.act1, p.actd, p.act2, p.res_act, p.TH, p.TW, p.TWq, p.NF, p.EH, p.EW,
+                        p.NPin, p.NPout, p.tiles_x, p.tiles_y, p.ntiles, p.k4, p.nchunks, p.ECH, p.CH, p.KS, p.red_off, p.vec_store, p.resident, p.inv_nsi, c.lds, c.grid, c.block, c.half, c.pack_floats);
+    }
+    return snprintf(buf, cap, "unsupported");
 }
 
 int ffgpu_launch_irb(const IrbDesc &d, hipStream_t s)
 {
-    if (irb_thin_ok(d)) return launch_irb_thin(d, s);
-    { IrbwCfg c; if (irbw_pick(d, c)) { if (!d.pk) { ffgpu_set_error("irbw: constants not packed"); return -1; } return launch_irbw(d, c, s); } }
-    IrbP p;
-    if (!d.pk || !ffgpu_irb_supported(d) || !irb_pick_tile(d, p)) { ffgpu_set_error("irb: unsupported block shape or constants not packed"); return -1; }
-    p.in = d.in; p.out = d.out; p.residual = d.residual; p.pk = d.pk;
-    p.N = d.N; p.H = d.H; p.W = d.W; p.OH = d.OH; p.OW = d.OW; p.ic = d.ic; p.ec = d.ec; p.oc = d.oc; p.stride = d.stride;
-    auto slope = [](int act) { return act == 2 ? 0.1f : (act == 1 ? 0.f : 1.f); };
-    p.act1 = slope(d.act1); p.actd = slope(d.actd); p.act2 = slope(d.act2); p.res_act = slope(d.res_act);
-    int MT, OT;
-    irb_consts(d, p.k4, p.ECH, MT, OT, p.nchunks, p.CH);
-    p.vec_store = (d.OW % 4 == 0) && (p.TW % 4 == 0);
-    p.dbg_skip = env_int("FFGPU_IRB_SKIP", 0); p.dbg_t = nullptr;
-    p.ntiles = p.tiles_x * p.tiles_y * ((d.N + p.NF - 1) / p.NF);
-    const int nso = (p.NPout + 63) / 64;
-    const int NW = env_int("FFGPU_IRB_NW", 8) == 4 ? 4 : 8;          // waves per workgroup
-    p.KS = 1;
-    while (p.KS * 2 * nso <= NW && p.KS < 4) p.KS *= 2;              // idle waves take slices of the channel loop
-    if (env_int("FFGPU_IRB_NOKS", 0)) p.KS = 1;
-    const int wbufs = irb_wbufs(p.k4, p.ECH, OT, p.NPin, p.nchunks, p.ntiles);
-    p.resident = p.nchunks > 1 && wbufs == p.nchunks;
-    const int nsi = p.NPin / 64;
-    p.inv_nsi = (65536 + nsi - 1) / nsi;
-    for (int wi = 0; wi < p.k4 * nsi; wi++)
-        if (((wi * p.inv_nsi) >> 16) != wi / nsi) { ffgpu_set_error("irb: strip reciprocal inexact (k4 %d, %d strips)", p.k4, nsi); return -1; }
-    size_t lds = irb_lds_floats(p.k4, p.ECH, OT, p.NPin, wbufs) * sizeof(float);
-    p.red_off = 0;
-    for (;; p.KS /= 2) {                                             // reduce-scatter scratch: alias In..E when it fits, else append
-        const size_t need = p.KS > 1 ? (size_t)p.KS * nso * OT * 1024 : 0;
-        // (a workgroup that runs a single tile is done with Msk and the chunk constants too by then)
-        const size_t alias_cap = (size_t)(p.k4 + p.ECH) * p.NPin + (p.ntiles <= 256 ? (size_t)p.NPin + (size_t)wbufs * p.CH : 0);
-        if (need <= alias_cap) break;
-        if (lds + need * sizeof(float) <= IRB_LDS_MAX) { p.red_off = (int)(lds / sizeof(float)); lds += need * sizeof(float); break; }
-    }
-    int bpc = (int)(IRB_LDS_MAX / lds);
-    if (bpc > 4) bpc = 4;
-    if (bpc < 1) bpc = 1;
-    long nblocks = 256L * bpc;
-    if (nblocks > p.ntiles) nblocks = p.ntiles;
-    if (env_int("FFGPU_VERBOSE_IRB", 0))
-        fprintf(stderr, "irb %dx%d %d->%d->%d s%d: tile %dx%d x%d frames, E %dx%d NPin %d NPout %d KS %d, lds %zu B, %d tiles on %ld blocks, ECH %d x %d chunks%s\n",
-                d.W, d.H, d.ic, d.ec, d.oc, d.stride, p.TW, p.TH, p.NF, p.EW, p.EH, p.NPin, p.NPout, p.KS, lds, p.ntiles, nblocks, p.ECH, p.nchunks, p.resident ? " (resident)" : "");
-#define IRB_CASE(mt, ot) if (MT == mt && OT == ot) { \
-        if (NW == 8) return d.stride == 1 ? irb_launch_t<mt, ot, 1, 1, 8>(p, lds, nblocks, s) : irb_launch_t<mt, ot, 2, 1, 8>(p, lds, nblocks, s); \
-        return d.stride == 1 ? irb_launch_t<mt, ot, 1, 2, 4>(p, lds, nblocks, s) : irb_launch_t<mt, ot, 2, 2, 4>(p, lds, nblocks, s); }
-    IRB_CASE(1, 1); IRB_CASE(1, 2); IRB_CASE(1, 3); IRB_CASE(2, 1); IRB_CASE(2, 2); IRB_CASE(2, 3);
-#undef IRB_CASE
-    ffgpu_set_error("irb: no instantiation for MT=%d OT=%d", MT, OT);
-    return -1;
+    const IrbPlan &c = d.plan;
+    if (!irb_planned(d, "irb")) return -1;
+    if (env_int("FFGPU_VERBOSE_IRB", 0)) { char line[1024]; ffgpu_irb_plan_line(d, line, sizeof line); fprintf(stderr, "%s\n", line); }
+    if (c.family == IRB_THIN) return launch_irb_thin(d, s);
+    if (!d.pk) { ffgpu_set_error("irb: constants not packed"); return -1; }
+    return c.family == IRB_WAVE ? irbw_kernels[c.inst].launch(irbw_params(d), c, s) : irb_kernels[c.inst].launch(irb_params(d), c, s);
 }

@@ -47,22 +47,37 @@ struct ConvDesc {
 
 static inline int conv_k4(const ConvDesc &d) { return (d.fs * d.fs * (d.ic / d.groups) + 3) & ~3; }
 
-// Fused 1x1 expand -> depthwise 3x3 -> 1x1 project [+ residual] on CNHW tensors (ffgpu_irb.inc)
+// Fused 1x1 expand -> depthwise 3x3 -> 1x1 project [+ residual] on CNHW tensors.
+// What ffgpu_irb_plan decided for one block, all of it: the kernel family and instantiation, the tile, the layout of the packed image and the launch
+// shape.  The FFGPU_* tuning environment is read once, there; packing and every launch follow the plan, so a switch changed later cannot pair one
+// kernel with another kernel's image.
+enum { IRB_NONE = 0, IRB_THIN, IRB_WAVE, IRB_WG };   // not planned / refused; k_irb_thin (8 expanded channels, streaming); k_irbw, k_irbw2 (a wave owns a tile); k_irb (fallback)
+struct IrbPlan {
+    int family;
+    int inst;                 // IRB_WAVE / IRB_WG: index into the family's table of instantiations (irbw_kernels[], irb_kernels[])
+    int half;                 // IRB_WAVE: the "half last group" form of image and kernel (FFGPU_IRBW_HALF)
+    int pack_floats;          // floats of the packed image
+    int lds, grid, block;     // dynamic LDS bytes, workgroups, threads per workgroup
+    int KS1, OT, NSI, NSO, TWq, TH, EW, EH, ngroups, G, WPB, big, x3, xl;   // IRB_WAVE: input-channel quads, 16-channel output tiles, input / output strips, tile and halo,
+                              // 16-channel groups, waves per tile, tiles per workgroup, register budget, split-bf16 expand, LDS-resident split tile (OT, TH: IRB_WG too)
+    int xcd, region;          // IRB_WAVE: tile order XCD by XCD; floats behind the shared constants (E slices, then the group split's partial sums)
+    int TW, NF, ECH, NW, KS, wbufs, red_off;   // IRB_WG: tile width, frames per tile, channels per chunk, waves, waves per strip, chunk buffers in LDS, offset of the reduce scratch
+    int band, front_band;     // IRB_THIN: rows per wave in k_irb_thin / in k_front
+};
 struct IrbDesc {
     const float *in; float *out; const float *residual;
     const float *w1, *wd, *w2;
     int N, H, W, OH, OW, ic, ec, oc, stride;
     int act1, actd, act2, res_act;
-    const float *pk;          // packed constants (ffgpu_irb_pack_floats floats, filled by ffgpu_irb_pack)
+    const float *pk;          // packed constants (plan.pack_floats floats, filled by ffgpu_irb_pack)
     int flags;                // FFGPU_CONCURRENT: tile splits chosen for several chains in flight
-    int half;                 // k_irbw's "half last group" form frozen with the plan (ffgpu_irb_plan): 0 = decided at every call (single-block calls), 1 = off, 2 = on
+    IrbPlan plan;             // ffgpu_irb_plan; a descriptor without one is refused by pack and launch
 };
-bool   ffgpu_irb_supported(const IrbDesc &d);
-bool   ffgpu_irb_is_thin(const IrbDesc &d);      // 8 expanded channels: streaming VALU kernel instead of the MFMA/LDS one
+bool   ffgpu_irb_plan(IrbDesc &d);                     // false: no fused kernel takes the block.  Reads geometry, activations and flags; the pointers may follow
 size_t ffgpu_irb_pack_floats(const IrbDesc &d);
-void   ffgpu_irb_plan(IrbDesc &d);                     // freezes what the packed image's layout depends on (FFGPU_IRBW_HALF is read once, here)
 int    ffgpu_irb_pack(const IrbDesc &d, float *pk, hipStream_t s);
 int    ffgpu_launch_irb(const IrbDesc &d, hipStream_t s);
+int    ffgpu_irb_plan_line(const IrbDesc &d, char *buf, size_t cap);   // the plan as one canonical line of text (ffgpu_irb_plan_text)
 bool   ffgpu_front_ok(const ConvDesc &c, const IrbDesc &d);      // first layer (3x3 s2, 3 -> 8) + thin block as one streaming kernel
 // How a forward's batch arrives.  IN_F32: fp32 frames (ExecParams::frames; the staging kernels of ffgpu_input.inc write them for u8 sources the first
 // kernel cannot take).  The u8 forms are read by k_front itself: IN_U8 frames of the net's own geometry (ExecParams::bgr), IN_BGR_FRAMES / IN_NV12_FRAMES

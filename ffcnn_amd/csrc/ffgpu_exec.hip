@@ -324,6 +324,7 @@ static int plan(ffgpu_exec *ex)
     // pass 1b: 1x1 expand -> depthwise 3x3 -> 1x1 project triples become ONE fused kernel (ffgpu_irb.inc);
     // the two expanded tensors are never materialised
     std::vector<int> irb_tail(L, -1);           // layer p+2 -> p
+    std::vector<IrbDesc> irb_planned(L);        // layer p+2 -> the block's planned descriptor
     auto irb_desc = [&](int p0) {               // geometry, activations, flags and res_act of the block of layers p0 .. p0 + 2 (the step adds the pointers)
         IrbDesc d{};
         const LAYER &a = ll[p0], &b = ll[p0 + 1], &c = ll[p0 + 2];
@@ -343,10 +344,10 @@ static int plan(ffgpu_exec *ex)
             const bool pw_c = c.fs == 1 && c.stride == 1 && c.pad == 0 && c.groups == 1;
             if (!pw_a || !dw_b || !pw_c || nuses[p0] != 1 || nuses[p0 + 1] != 1 || src_tensor(p0 - 1) < 0) continue;
             if (canon[p0] != p0 || canon[p0 + 1] != p0 + 1) continue;
-            const IrbDesc d = irb_desc(p0);
+            IrbDesc d = irb_desc(p0);
             static const int min_ec = getenv("FFGPU_IRB_MIN_EC") ? atoi(getenv("FFGPU_IRB_MIN_EC")) : 24;
-            if ((d.ec < min_ec && !ffgpu_irb_is_thin(d)) || !ffgpu_irb_supported(d)) continue;   // thin blocks take the streaming fused kernel
-            irb_tail[p0 + 2] = p0;
+            if (!ffgpu_irb_plan(d) || (d.ec < min_ec && d.plan.family != IRB_THIN)) continue;   // thin blocks take the streaming fused kernel
+            irb_tail[p0 + 2] = p0; irb_planned[p0 + 2] = d;
             canon[p0] = canon[p0 + 1] = -3;
             p0 += 2;
         }
@@ -517,7 +518,7 @@ static int plan(ffgpu_exec *ex)
             if (irb_tail[i] >= 0) {
                 const int p0 = irb_tail[i];
                 const LAYER &la = ll[p0], &lb = ll[p0 + 1], &lc = ll[p0 + 2];
-                IrbDesc &d = st.irb = irb_desc(p0);
+                IrbDesc &d = st.irb = irb_planned[i];
                 st.kind = S_IRB;
                 d.in = tensor_ptr(ex, src_tensor(p0 - 1));
                 d.out = tensor_ptr(ex, canon[i]);
@@ -629,7 +630,7 @@ static int plan(ffgpu_exec *ex)
     {   // constants of the fused blocks, packed once into their LDS image
         size_t tot = 0;
         for (Step &st : S) {
-            if (st.kind == S_IRB) { ffgpu_irb_plan(st.irb); tot += ffgpu_irb_pack_floats(st.irb); }
+            if (st.kind == S_IRB) tot += ffgpu_irb_pack_floats(st.irb);
             if (st.kind == S_CONV) {                              // kernel choice, split-K and k_conv_x3's MT frozen with the plan
                 if (st.in_is_input) st.conv.flags |= FFGPU_F_BATCH_INPUT;
                 ffgpu_conv_plan(st.conv);
@@ -872,10 +873,11 @@ static void drop_graphs(ffgpu_exec *ex)                       // caller has sync
 }
 
 // The launch list is captured into its graph when the executor is created (the input pointer travels through the parameter
-// block, so no buffer has to be known): kernel choices, tile splits and packed-constant layouts -- which the FFGPU_* tuning
-// switches influence -- are thereby frozen together with the plan; a switch changed between ffgpu_exec_create and the first
-// forward cannot make a launch disagree with the constants packed for it.  (Eager FFGPU_NO_GRAPH executors re-read the
-// switches per forward: they are a debugging mode.)
+// block, so no buffer has to be known).  That is a saving, not what keeps launches and packed constants together: plan() freezes
+// every kernel choice, tile split and image layout that the FFGPU_* tuning switches influence into the steps themselves
+// (ConvDesc::kernel / nsplit / x3_mt, IrbDesc::plan), and every later issue of a step -- the graphs captured on first use of a
+// u8 form or per input pointer, eager FFGPU_NO_GRAPH forwards, ffgpu_exec_profile and _profile_steps, the repack of
+// ffgpu_net_weights_commit -- reads them, never the environment.
 static int capture_at_create(ffgpu_exec *ex)
 {
     if ((ex->flags & FFGPU_NO_GRAPH) || !graph_pointer_free(ex)) return 0;
@@ -1820,6 +1822,24 @@ extern "C" float ffgpu_groupconv_time_dev(const float *d_in, const float *d_filt
     return ms * 1000.f / iters;
 }
 
+static void irb_fill(IrbDesc &d, int batch, int iw, int ih, int ic, int ec, int oc, int stride, int act1, int actd, int act2, int res_act)
+{
+    d.N = batch; d.H = ih; d.W = iw; d.OH = (ih + 2 - 3) / stride + 1; d.OW = (iw + 2 - 3) / stride + 1;
+    d.ic = ic; d.ec = ec; d.oc = oc; d.stride = stride;
+    d.act1 = act1; d.actd = actd; d.act2 = act2; d.res_act = res_act;
+}
+
+// pure host code: what ffgpu_irb_plan decides for the block, as one line of text
+extern "C" int ffgpu_irb_plan_text(int batch, int iw, int ih, int ic, int ec, int oc, int stride, int act1, int actd, int act2, int res_act, int flags, char *buf, int cap)
+{
+    if (!buf || cap < 1 || batch < 1 || iw < 1 || ih < 1 || stride < 1) { ffgpu_set_error("irb_plan_text: bad arguments"); return -1; }
+    IrbDesc d{};
+    irb_fill(d, batch, iw, ih, ic, ec, oc, stride, act1, actd, act2, res_act);
+    d.flags = flags & FFGPU_CONCURRENT;
+    (void)ffgpu_irb_plan(d);
+    return ffgpu_irb_plan_line(d, buf, (size_t)cap);
+}
+
 extern "C" float ffgpu_irb_dev(const float *d_in, const float *d_w1, const float *d_wd, const float *d_w2,
                                const float *d_res, float *d_out, int batch, int iw, int ih, int ic, int ec, int oc,
                                int stride, int act1, int actd, int act2, int res_act, int warmup, int iters, void *stream)
@@ -1827,10 +1847,8 @@ extern "C" float ffgpu_irb_dev(const float *d_in, const float *d_w1, const float
     hipStream_t s = (hipStream_t)stream;
     IrbDesc d{};
     d.in = d_in; d.out = d_out; d.residual = d_res; d.w1 = d_w1; d.wd = d_wd; d.w2 = d_w2;
-    d.N = batch; d.H = ih; d.W = iw; d.OH = (ih + 2 - 3) / stride + 1; d.OW = (iw + 2 - 3) / stride + 1;
-    d.ic = ic; d.ec = ec; d.oc = oc; d.stride = stride;
-    d.act1 = act1; d.actd = actd; d.act2 = act2; d.res_act = res_act;
-    if (!d_in || !d_out || !d_w1 || !d_wd || !d_w2 || !ffgpu_irb_supported(d)) { ffgpu_set_error("irb_dev: unsupported block shape"); return -1.f; }
+    irb_fill(d, batch, iw, ih, ic, ec, oc, stride, act1, actd, act2, res_act);
+    if (!d_in || !d_out || !d_w1 || !d_wd || !d_w2 || !ffgpu_irb_plan(d)) { ffgpu_set_error("irb_dev: unsupported block shape"); return -1.f; }     // planned once per call
     float *pk = nullptr;
     if (hipMalloc(&pk, ffgpu_irb_pack_floats(d) * sizeof(float)) != hipSuccess) { ffgpu_set_error("irb_dev: hipMalloc failed"); return -1.f; }
     d.pk = pk;

@@ -316,6 +316,12 @@ float ffgpu_irb_dev(const float *d_in, const float *d_w1, const float *d_wd, con
                     const float *d_res, float *d_out, int batch, int iw, int ih, int ic, int ec, int oc,
                     int stride, int act1, int actd, int act2, int res_act, int warmup, int iters, void *stream);
 
+/* What the planner decides for that block, as one line of text in buf (at most cap bytes; returns snprintf's count): the kernel
+ * family and instantiation, every scalar of the parameter block the launch would pass, LDS bytes, grid, block, `half`, the floats
+ * of the packed image -- or "unsupported".  flags: FFGPU_CONCURRENT or 0.  Pure host code (no device needed): for tests and logs. */
+int ffgpu_irb_plan_text(int batch, int iw, int ih, int ic, int ec, int oc, int stride, int act1, int actd, int act2, int res_act,
+                        int flags, char *buf, int cap);
+
 /* Fused pair: depthwise K x K (K = 3 | 5, stride 1, pad K / 2) -> pointwise 1x1, i.e. two consecutive groupconv calls of the
  * reference in one kernel (the depthwise tensor never leaves the CU).  CNHW device tensors; d_wd / d_wp are the two layers'
  * filter rows (conv.h layout).  iters > 0: returns mean microseconds per launch (HIP events on `stream`) instead of 0. */

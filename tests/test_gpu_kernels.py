@@ -711,3 +711,66 @@ def test_irb_wave_group_split(env, shape, G, monkeypatch):
     """wave-autonomous fused block with the channel groups of a tile split over G waves (fixed-order LDS reduction)"""
     monkeypatch.setenv("FFGPU_IRBW_G", str(G))
     test_irb_fused_block(env, shape)
+
+
+def test_irb_plan_is_frozen_at_create(orc, tmp_path, monkeypatch):
+    """A fused block's plan is frozen when the executor is created: a tuning switch changed afterwards reaches neither an eager issue of the steps
+    (profile_steps), nor the repack of the constants (weights_commit), nor a graph forward.  The net has one block that plans as the split-bf16 ("X3")
+    single-strip kernel: 24 -> 48 -> 24 channels on 16x16, i.e. KS1 6, OT 2, NSI 2.  After creation FFGPU_IRBW_X3=0 asks for the fp32 form.  Only this
+    switch, and only in this direction: the X3 image is the larger one (1280 against 384 dwords per group), so code that re-picked would read or write
+    the smaller layout inside the larger buffer -- wrong numbers, never an access out of bounds."""
+    from test_gpu_fuzz_nets import conv
+    from test_gpu_parity import _write_random_weights, close
+    from test_irb_choice import PLANNER_ENV
+    BATCH = 2
+    cfg_text = "[net]\nwidth=32\nheight=32\nchannels=3\n\n" + conv(24, 3, 2, "leaky") + \
+        conv(48, 1, 1, "leaky") + conv(48, 3, 1, "leaky", groups=48) + conv(24, 1, 1, "linear") + "[shortcut]\nfrom=-4\nactivation=linear\n\n" + \
+        conv(18, 1, 1, "linear", bn=0) + \
+        "[yolo]\nmask = 0,1,2\nanchors = 6,8, 10,14, 20,18, 30,40, 50,44, 70,80\nclasses=1\nignore_thresh = .55\nscale_x_y = 1.05\n\n"
+    import torch
+    from ffcnn_amd import capi as F
+    F.lib()
+    for v in PLANNER_ENV:
+        monkeypatch.delenv(v, raising=False)
+    assert F.irb_plan_text((BATCH, 16, 16, 24, 48, 24, 1, 2, 2, 0, 0)).startswith("irbw<6,2,1,2,big,x3> ")
+    cfg, wpath = str(tmp_path / "block.cfg"), str(tmp_path / "block.weights")
+    open(cfg, "w").write(cfg_text)
+    o = orc.Oracle(cfg=cfg, weights=None)
+    _write_random_weights(wpath, o, 31)
+    o.close()
+    o = orc.Oracle(cfg=cfg, weights=wpath)
+    frames = np.random.default_rng(32).uniform(0, 1, (BATCH, 3, 32, 32)).astype(np.float32)
+    acts = []
+    for f in range(BATCH):
+        o.input[...] = frames[f]
+        o.n.s1, o.n.s2 = 1, 1
+        o.forward(0)
+        acts.append({i: o.layer_out(i).copy() for i in range(o.nlayers) if o.layer_out(i) is not None})
+    o.close()
+    d_frames = torch.from_numpy(frames).cuda()
+
+    def check(ex, what):
+        seen = []
+        for i in sorted(acts[0]):
+            if n.layer(i).type == 4:
+                continue
+            try:
+                ex.read_layer(i, 0)
+            except RuntimeError as e:
+                assert "not materialised" in str(e)
+                continue
+            seen.append(i)
+            for f in range(BATCH):
+                close(ex.read_layer(i, f), acts[f][i], "%s: frame %d layer %d" % (what, f, i))
+        assert 0 in seen and 1 not in seen and 2 not in seen and len(seen) >= 3, seen       # the block is fused: its two expanded tensors do not exist
+
+    with F.Net(cfg, wpath) as n:
+        with n.executor(BATCH, F.FFGPU.KEEP_ALL) as ex:
+            ex.set_scale(1, 1)
+            monkeypatch.setenv("FFGPU_IRBW_X3", "0")
+            ex.profile_steps(d_frames.data_ptr())
+            check(ex, "eager issue (profile_steps)")
+            n.weights_commit()
+            check(ex, "repack (weights_commit)")
+            ex.forward_host(frames)
+            check(ex, "graph forward after the repack")
