@@ -90,7 +90,7 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_exec_kernel_count", "ffgpu_exec_work_model", "ffgpu_exec_set_scale", "ffgpu_exec_forward_dev", "ffgpu_exec_forward_host",
            "ffgpu_exec_forward_bgr_dev", "ffgpu_exec_forward_bgr_frames_dev", "ffgpu_exec_forward_nv12_frames_dev", "ffgpu_exec_dets_dev", "ffgpu_exec_dets_host", "ffgpu_exec_set_ring", "ffgpu_exec_set_ring_strided", "ffgpu_exec_read_dets", "ffgpu_exec_read_layer", "ffgpu_exec_hash_layers",
            "ffgpu_exec_read_boxes", "ffgpu_exec_cand_capacity", "ffgpu_exec_graph_captures",
-           "ffgpu_exec_profile", "ffgpu_exec_profile_steps", "ffgpu_exec_step_model", "ffgpu_groupconv_dev", "ffgpu_groupconv_kernel_name", "ffgpu_groupconv_time_dev", "ffgpu_irb_dev", "ffgpu_irb_plan_text", "ffgpu_dwpw_dev", "ffgpu_packed_records_bytes", "ffgpu_pack_records", "ffgpu_unpack_records",
+           "ffgpu_exec_profile", "ffgpu_exec_profile_steps", "ffgpu_exec_step_model", "ffgpu_groupconv_dev", "ffgpu_groupconv_kernel_name", "ffgpu_groupconv_time_dev", "ffgpu_irb_dev", "ffgpu_irb_plan_text", "ffgpu_irb_instantiations", "ffgpu_dwpw_dev", "ffgpu_packed_records_bytes", "ffgpu_pack_records", "ffgpu_unpack_records",
            "ffgpu_shard_range", "ffgpu_node_create", "ffgpu_node_destroy", "ffgpu_node_ndev", "ffgpu_node_shard", "ffgpu_node_set_scale",
            "ffgpu_node_input_dev", "ffgpu_node_input_slot_dev", "ffgpu_node_depth", "ffgpu_node_rccl_ranks", "ffgpu_node_forward", "ffgpu_node_forward_host",
            "ffgpu_node_submit", "ffgpu_node_wait", "ffgpu_node_run",
@@ -176,6 +176,7 @@ def lib():
     L.ffgpu_irb_dev.restype = C.c_float
     L.ffgpu_irb_dev.argtypes = [vp] * 6 + [i] * 13 + [vp]
     L.ffgpu_irb_plan_text.argtypes = [i] * 12 + [C.c_char_p, i]
+    L.ffgpu_irb_instantiations.argtypes = [C.c_char_p, i]
     L.ffgpu_exec_read_boxes.argtypes = [vp, i, vp, i]
     L.ffgpu_exec_cand_capacity.argtypes = [vp]
     L.ffgpu_exec_graph_captures.argtypes = [vp]
@@ -824,6 +825,15 @@ def irb_plan_text(shape, flags=0):
     if lib().ffgpu_irb_plan_text(*shape, flags, buf, len(buf)) < 0:
         raise RuntimeError("ffgpu_irb_plan_text failed: %s" % last_error())
     return buf.value.decode()
+
+
+def irb_instantiations():
+    """the key of every fused-block instantiation (the first word of irb_plan_text's line), in table order (no GPU needed)"""
+    buf = C.create_string_buffer(4096)
+    n = lib().ffgpu_irb_instantiations(buf, len(buf))
+    if n < 0 or n >= len(buf):
+        raise RuntimeError("ffgpu_irb_instantiations failed: %s" % (last_error() if n < 0 else "%d bytes" % n))
+    return buf.value.decode().split()
 
 
 def dwpw_dev(d_in, d_wd, d_wp, d_out, batch, iw, ih, c, oc, fs, actd=2, actp=0, warmup=0, iters=0, stream=None):

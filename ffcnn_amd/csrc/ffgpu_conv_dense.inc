@@ -159,7 +159,7 @@ __global__ void __launch_bounds__(256) k_conv_first(ConvDesc d, unsigned m_owq)
         // (four plain v_fma_f32 kept apart: hipcc otherwise packs them into v_pk_fma_f32 with sc / bi broadcast out of ONE register pair -- DESIGN.md 5.10, tools/isa_lint.py)
         v4f_cd v = pw_fma4_apart(acc[o].x, acc[o].y, acc[o].z, acc[o].w, sc, bi);
 #pragma unroll
-        for (int j = 0; j < 4; j++) v[j] = fmaxf(v[j], slope * v[j]);
+        for (int j = 0; j < 4; j++) v[j] = act_max(v[j], slope * v[j], act_floor(slope));
         *reinterpret_cast<v4f_cd *>(d.out + (long)(ob + o) * d.out_cs + po) = v;
     }
 }

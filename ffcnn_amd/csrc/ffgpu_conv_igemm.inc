@@ -261,7 +261,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k
         px = (long)rowi * p.ow + x;
     }
     const bool pair = two && !(p.P & 1) && !(p.ow & 1);               // 8-byte store: both pixels exist and every pair starts 8-byte aligned
-    auto act1 = [&](float t, int a, float sl) { return a == 3 ? 1.0f / (1.0f + (float)exp((double)-t)) : fmaxf(t, sl * t); };
+    auto act1 = [&](float t, int a, float sl) { return a == 3 ? 1.0f / (1.0f + (float)exp((double)-t)) : act_max(t, sl * t, act_floor(sl)); };
     if (p.nsplit > 1) {                                               // raw partial sums; scale', bias', activation and residual follow in the reduction
         float *part = p.part + ((size_t)grp * p.nsplit + ks) * p.oc * p.P;
 #pragma unroll
@@ -302,7 +302,7 @@ __global__ void __launch_bounds__(256) k_conv_igemm_reduce(IgemmRedP p)
     // (all groups at once: output channel o = goc g + ol of the contiguous oc x P tensor; part[g][s][ol][px])
     const long total = (long)p.oc * p.P, gsz = (long)p.goc * p.P;
     const float slope = p.act == 2 ? 0.1f : (p.act == 1 ? 0.f : 1.f), rslope = p.res_act == 2 ? 0.1f : (p.res_act == 1 ? 0.f : 1.f);
-    auto act1 = [&](float t, int a, float sl) { return a == 3 ? 1.0f / (1.0f + (float)exp((double)-t)) : fmaxf(t, sl * t); };
+    auto act1 = [&](float t, int a, float sl) { return a == 3 ? 1.0f / (1.0f + (float)exp((double)-t)) : act_max(t, sl * t, act_floor(sl)); };
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int o = (int)(i / p.P), g = o / p.goc;
         const float *part = p.part + (size_t)g * p.nsplit * gsz + (i - (long)g * gsz);

@@ -1112,13 +1112,17 @@ static int irb_thin_launch(const ThinP &p, const IrbPlan &c, hipStream_t s)
     return 0;
 }
 
+typedef int (*IrbThinLaunch)(const ThinP &, const IrbPlan &, hipStream_t);
+struct IrbThinKernel { int IC, OC; IrbThinLaunch launch; };
+static const IrbThinKernel irb_thin_kernels[] = { { 8, 4, irb_thin_launch<8, 8, 4> }, { 4, 4, irb_thin_launch<4, 8, 4> }, { 8, 8, irb_thin_launch<8, 8, 8> }, { 4, 8, irb_thin_launch<4, 8, 8> } };
+
 static int launch_irb_thin(const IrbDesc &d, hipStream_t s)
 {
     const ThinP p = thin_params(d);
-    if (d.ic == 8 && d.oc == 4) return irb_thin_launch<8, 8, 4>(p, d.plan, s);
-    if (d.ic == 4 && d.oc == 4) return irb_thin_launch<4, 8, 4>(p, d.plan, s);
-    if (d.ic == 8 && d.oc == 8) return irb_thin_launch<8, 8, 8>(p, d.plan, s);
-    return irb_thin_launch<4, 8, 8>(p, d.plan, s);
+    for (const IrbThinKernel &k : irb_thin_kernels)
+        if (k.IC == d.ic && k.OC == d.oc) return k.launch(p, d.plan, s);
+    ffgpu_set_error("irb_thin: no instantiation for %d -> 8 -> %d channels", d.ic, d.oc);
+    return -1;
 }
 
 // ---- wave-autonomous form (ffgpu_irb_wave.inc, ffgpu_irb_wave2.inc): every instantiation that exists, shape test, tile / split choice, launch shape
@@ -1609,20 +1613,41 @@ int ffgpu_irb_pack(const IrbDesc &d, float *pk, hipStream_t s)
 
 // One canonical line per planned block (the probe behind ffgpu_irb_plan_text, tests/test_irb_choice.py; FFGPU_VERBOSE_IRB prints it per launch): family and instantiation, every scalar of
 // the parameter block the launch would pass, the launch shape, `half` and the size of the packed image
+// the head of that line: one key per instantiation.  ffgpu_irb_keys walks the same three tables with the same three formatters, so a row added to a table is in the list
+static int irb_thin_key(int ic, int oc, char *key, size_t cap) { return snprintf(key, cap, "thin<%d,8,%d>", ic, oc); }
+static int irbw_key(const IrbwKernel &k, char *key, size_t cap)
+{
+    if (k.NSO == 2) return snprintf(key, cap, "irbw2<%d,%d%s>", k.KS1, k.NSI, k.x3 ? ",x3" : "");
+    return snprintf(key, cap, "irbw<%d,%d,%d,%d%s%s%s>", k.KS1, k.OT, k.S, k.NSI, k.big ? ",big" : "", k.x3 ? ",x3" : "", k.xl ? ",xl" : "");
+}
+static int irb_key(const IrbKernel &k, char *key, size_t cap) { return snprintf(key, cap, "irb<%d,%d,%d,%d,%d>", k.MT, k.OT, k.S, k.NW == 8 ? 1 : 2, k.NW); }
+
+// every instantiation the three families have, one key per line (ffgpu_irb_instantiations): thin, then irbw_kernels[], then irb_kernels[] (both wave counts are rows of it)
+int ffgpu_irb_keys(char *buf, size_t cap)
+{
+    size_t n = 0;
+    char key[48];
+    auto put = [&]() { n += (size_t)snprintf(n < cap ? buf + n : nullptr, n < cap ? cap - n : 0, "%s\n", key); };
+    for (const IrbThinKernel &k : irb_thin_kernels) { irb_thin_key(k.IC, k.OC, key, sizeof key); put(); }
+    for (const IrbwKernel &k : irbw_kernels) { irbw_key(k, key, sizeof key); put(); }
+    for (const IrbKernel &k : irb_kernels) { irb_key(k, key, sizeof key); put(); }
+    return (int)n;
+}
+
 int ffgpu_irb_plan_line(const IrbDesc &d, char *buf, size_t cap)
 {
     const IrbPlan &c = d.plan;
+    char key[48];
     if (c.family == IRB_THIN) {
         const ThinP p = thin_params(d);
-        return snprintf(buf, cap, "thin<%d,8,%d> W=%d H=%d N=%d band=%d nbands=%d act=%g,%g,%g,%g ntasks=%ld lds=%d grid=%d block=%d half=%d pack=%d",
-                        d.ic, d.oc, p.W, p.H, p.N, p.band, p.nbands, p.act1, p.actd, p.act2, p.res_act, p.ntasks, c.lds, c.grid, c.block, c.half, c.pack_floats);
+        irb_thin_key(d.ic, d.oc, key, sizeof key);
+        return snprintf(buf, cap, "%s W=%d H=%d N=%d band=%d nbands=%d act=%g,%g,%g,%g ntasks=%ld lds=%d grid=%d block=%d half=%d pack=%d",
+                        key, p.W, p.H, p.N, p.band, p.nbands, p.act1, p.actd, p.act2, p.res_act, p.ntasks, c.lds, c.grid, c.block, c.half, c.pack_floats);
     }
     if (c.family == IRB_WAVE) {
         const IrbwP p = irbw_params(d);
         const IrbwKernel &k = irbw_kernels[c.inst];
-        char key[48];
-        if (k.NSO == 2) snprintf(key, sizeof key, "irbw2<%d,%d%s>", k.KS1, k.NSI, k.x3 ? ",x3" : "");
-        else snprintf(key, sizeof key, "irbw<%d,%d,%d,%d%s%s%s>", k.KS1, k.OT, k.S, k.NSI, k.big ? ",big" : "", k.x3 ? ",x3" : "", k.xl ? ",xl" : "");
+        irbw_key(k, key, sizeof key);
         return snprintf(buf, cap, "%s N=%d H=%d W=%d OH=%d OW=%d ic=%d ec=%d oc=%d act=%g,%g,%g,%g tile=%d,%d,%d,%d tiles=%d,%d,%ld ngroups=%d G=%d WPB=%d o_w2=%d o_cs=%d cs_floats=%d "
                         "xl_off=%d red_cap=%d in_elems=%u vec=%d half_last=%d m=%u,%u,%u,%u xcd=%d lds=%d grid=%d block=%d half=%d pack=%d",
                         key, p.N, p.H, p.W, p.OH, p.OW, p.ic, p.ec, p.oc, p.act1, p.actd, p.act2, p.res_act, p.TWq, p.TH, p.EW, p.EH, p.tiles_x, p.tiles_y, p.ntiles, p.ngroups, p.G, p.WPB,
@@ -1631,9 +1656,10 @@ int ffgpu_irb_plan_line(const IrbDesc &d, char *buf, size_t cap)
     if (c.family == IRB_WG) {
         const IrbP p = irb_params(d);
         const IrbKernel &k = irb_kernels[c.inst];
-        return snprintf(buf, cap, "irb<%d,%d,%d,%d,%d> N=%d H=%d W=%d OH=%d OW=%d ic=%d ec=%d oc=%d stride=%d act=%g,%g,%g,%g tile=%d,%d,%d,%d,%d,%d NPin=%d NPout=%d tiles=%d,%d,%d "
+        irb_key(k, key, sizeof key);
+        return snprintf(buf, cap, "%s N=%d H=%d W=%d OH=%d OW=%d ic=%d ec=%d oc=%d stride=%d act=%g,%g,%g,%g tile=%d,%d,%d,%d,%d,%d NPin=%d NPout=%d tiles=%d,%d,%d "
                         "k4=%d nchunks=%d ECH=%d CH=%d KS=%d red_off=%d vec_store=%d resident=%d inv_nsi=%d lds=%d grid=%d block=%d half=%d pack=%d",
-                        k.MT, k.OT, k.S, k.NW == 8 ? 1 : 2, k.NW, p.N, p.H, p.W, p.OH, p.OW, p.ic, p.ec, p.oc, p.stride, p.act1, p.actd, p.act2, p.res_act, p.TH, p.TW, p.TWq, p.NF, p.EH, p.EW,
+                        key, p.N, p.H, p.W, p.OH, p.OW, p.ic, p.ec, p.oc, p.stride, p.act1, p.actd, p.act2, p.res_act, p.TH, p.TW, p.TWq, p.NF, p.EH, p.EW,
                         p.NPin, p.NPout, p.tiles_x, p.tiles_y, p.ntiles, p.k4, p.nchunks, p.ECH, p.CH, p.KS, p.red_off, p.vec_store, p.resident, p.inv_nsi, c.lds, c.grid, c.block, c.half, c.pack_floats);
     }
     return snprintf(buf, cap, "unsupported");

@@ -78,6 +78,7 @@ size_t ffgpu_irb_pack_floats(const IrbDesc &d);
 int    ffgpu_irb_pack(const IrbDesc &d, float *pk, hipStream_t s);
 int    ffgpu_launch_irb(const IrbDesc &d, hipStream_t s);
 int    ffgpu_irb_plan_line(const IrbDesc &d, char *buf, size_t cap);   // the plan as one canonical line of text (ffgpu_irb_plan_text)
+int    ffgpu_irb_keys(char *buf, size_t cap);                             // the key of every instantiation of the three families, one per line (ffgpu_irb_instantiations)
 bool   ffgpu_front_ok(const ConvDesc &c, const IrbDesc &d);      // first layer (3x3 s2, 3 -> 8) + thin block as one streaming kernel
 // How a forward's batch arrives.  IN_F32: fp32 frames (ExecParams::frames; the staging kernels of ffgpu_input.inc write them for u8 sources the first
 // kernel cannot take).  The u8 forms are read by k_front itself: IN_U8 frames of the net's own geometry (ExecParams::bgr), IN_BGR_FRAMES / IN_NV12_FRAMES

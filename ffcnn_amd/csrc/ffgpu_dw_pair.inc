@@ -107,7 +107,7 @@ __global__ void __launch_bounds__(256) k_dw_pair(DwPairP p)
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const v2f_dp t = acc[o][j] * sc + bi, u = t * p.slope;
-            v[j] = (v2f_dp){ fmaxf(t.x, u.x), fmaxf(t.y, u.y) };
+            v[j] = (v2f_dp){ act_max(t.x, u.x, act_floor(p.slope)), act_max(t.y, u.y, act_floor(p.slope)) };
         }
         const unsigned oo = (unsigned)i * HW + (unsigned)(y0 + o) * p.W + xq * 4;
         if (VEC == 4) {

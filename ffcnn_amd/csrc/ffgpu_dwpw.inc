@@ -144,7 +144,7 @@ __global__ void __launch_bounds__(256) k_dwpw(DwPwP p)
             const float sc = tp[FF], bi = tp[FF + 1];
 #pragma unroll
             for (int j = 0; j < SG; j++)
-                if (j < iseg) { const float v = fmaf(o[j], sc, bi); B[ich * p.TPS + iy * p.TW + ix0 + j] = fmaxf(v, p.slope_d * v); }
+                if (j < iseg) { const float v = fmaf(o[j], sc, bi); B[ich * p.TPS + iy * p.TW + ix0 + j] = act_max(v, p.slope_d * v, act_floor(p.slope_d)); }
         }
         __syncthreads();                                             // B tile of chunk c complete; everyone is done with the halo tile
         if (nct_w > 0) {
@@ -185,7 +185,7 @@ __global__ void __launch_bounds__(256) k_dwpw(DwPwP p)
                 const int ol = 16 * r + 4 * (lane >> 4) + i;
                 if (ol < p.OC) {
                     const float v = fmaf(acc[r][j][i], sb[2 * ol], sb[2 * ol + 1]);
-                    outb[(long)ol * cs + poff] = fmaxf(v, p.slope_p * v);
+                    outb[(long)ol * cs + poff] = act_max(v, p.slope_p * v, act_floor(p.slope_p));
                 }
             }
         }

@@ -1840,6 +1840,13 @@ extern "C" int ffgpu_irb_plan_text(int batch, int iw, int ih, int ic, int ec, in
     return ffgpu_irb_plan_line(d, buf, (size_t)cap);
 }
 
+// pure host code: the key of every fused-block instantiation, one per line, from the tables the planner dispatches through
+extern "C" int ffgpu_irb_instantiations(char *buf, int cap)
+{
+    if (!buf || cap < 1) { ffgpu_set_error("irb_instantiations: bad arguments"); return -1; }
+    return ffgpu_irb_keys(buf, (size_t)cap);
+}
+
 extern "C" float ffgpu_irb_dev(const float *d_in, const float *d_w1, const float *d_wd, const float *d_w2,
                                const float *d_res, float *d_out, int batch, int iw, int ih, int ic, int ec, int oc,
                                int stride, int act1, int actd, int act2, int res_act, int warmup, int iters, void *stream)

@@ -349,7 +349,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
 #pragma unroll
                 for (int j = 0; j < NC; j++) {
                     const v2f_t t = x[pr][j] * sc[pr] + bi[pr], u = t * p.act0;
-                    x[pr][j] = (v2f_t){ fmaxf(t.x, u.x), fmaxf(t.y, u.y) };
+                    x[pr][j] = (v2f_t){ act_max(t.x, u.x, act_floor(p.act0)), act_max(t.y, u.y, act_floor(p.act0)) };
                 }
         }
         // the next step's rows: 2r+1 becomes the carried one, 2r+2 and 2r+3 are fetched during the block's arithmetic
@@ -375,7 +375,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
                     for (int ci = 1; ci < IC; ci++) a += w1p(ci) * ((ci & 1) ? x[ci >> 1][j].y : x[ci >> 1][j].x);
                     a = a * w1p(IC) + w1p(IC + 1);
                     const v2f_t u = a * p.act1;
-                    win[1 + j] = (v2f_t){ fmaxf(a.x, u.x), fmaxf(a.y, u.y) };
+                    win[1 + j] = (v2f_t){ act_max(a.x, u.x, act_floor(p.act1)), act_max(a.y, u.y, act_floor(p.act1)) };
                 }
             } else {
 #pragma unroll
@@ -402,7 +402,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
                     d += wdp(6) * win[j]; d += wdp(7) * win[j + 1]; d += wdp(8) * win[j + 2];
                     d = d * wdp(9) + wdp(10);
                     const v2f_t u = d * p.actd;
-                    d = (v2f_t){ fmaxf(d.x, u.x), fmaxf(d.y, u.y) };
+                    d = (v2f_t){ act_max(d.x, u.x, act_floor(p.actd)), act_max(d.y, u.y, act_floor(p.actd)) };
 #pragma unroll
                     for (int k = 0; k < OCP / 2; k++) {
                         const v4f &wa = cd.w2[k >> 1], &wb = cd.w2[(OCP / 2 + k) >> 1];
@@ -445,7 +445,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
 #pragma unroll
                 for (int j = 0; j < NC; j++) {
                     const v2f_t t = o[k][j] * sc + bi, u = t * p.act2;
-                    v[j] = (v2f_t){ fmaxf(t.x, u.x), fmaxf(t.y, u.y) };
+                    v[j] = (v2f_t){ act_max(t.x, u.x, act_floor(p.act2)), act_max(t.y, u.y, act_floor(p.act2)) };
                 }
 #pragma unroll
                 for (int h = 0; h < 2; h++) {

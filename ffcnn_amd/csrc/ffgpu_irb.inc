@@ -71,7 +71,7 @@ template <class T> __device__ __forceinline__ void irb_st(void *base, unsigned b
 
 // linear / relu / leaky(0.1) (utils.h:15-23) as ONE branch-free form: act(x) = max(x, slope * x) with
 // slope 1, 0 or 0.1 -- two VALU ops and no wave-uniform branches in the inner loops
-__device__ __forceinline__ float irb_act(float x, float slope) { return fmaxf(x, slope * x); }
+__device__ __forceinline__ float irb_act(float x, float slope) { return act_max(x, slope * x, act_floor(slope)); }
 
 // ---- packed constants ------------------------------------------------------------------
 // chunk c at pk + c*CH:  [W1 frags ks1*MT*64][W2 frags (ECH/4)*OT*64][Wd ECH*12][Sb1 ECH*2]

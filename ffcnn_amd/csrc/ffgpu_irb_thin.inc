@@ -145,7 +145,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
                     for (int ci = 1; ci < IC; ci++) a += w1p(ci) * x[ci][j];
                     a = a * w1p(IC) + w1p(IC + 1);
                     const v2f_t u = a * p.act1;
-                    win[1 + j] = (v2f_t){ fmaxf(a.x, u.x), fmaxf(a.y, u.y) };
+                    win[1 + j] = (v2f_t){ act_max(a.x, u.x, act_floor(p.act1)), act_max(a.y, u.y, act_floor(p.act1)) };
                 }
             } else {                                               // the depthwise layer pads the EXPANDED tensor with zeros
 #pragma unroll
@@ -164,7 +164,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
                     d += wdp(6) * win[j]; d += wdp(7) * win[j + 1]; d += wdp(8) * win[j + 2];
                     d = d * wdp(9) + wdp(10);
                     const v2f_t u = d * p.actd;
-                    d = (v2f_t){ fmaxf(d.x, u.x), fmaxf(d.y, u.y) };
+                    d = (v2f_t){ act_max(d.x, u.x, act_floor(p.actd)), act_max(d.y, u.y, act_floor(p.actd)) };
                     // projection: output-channel pairs, expanded channel 2cp then 2cp+1 (the reference's order)
 #pragma unroll
                     for (int k = 0; k < OCP / 2; k++) {
@@ -210,14 +210,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     const v2f_t t = o[k][j] * sc + bi, u = t * p.act2;
-                    v[j] = (v2f_t){ fmaxf(t.x, u.x), fmaxf(t.y, u.y) };
+                    v[j] = (v2f_t){ act_max(t.x, u.x, act_floor(p.act2)), act_max(t.y, u.y, act_floor(p.act2)) };
                 }
 #pragma unroll
                 for (int h = 0; h < 2; h++) {
                     v4f q = { v[0][h], v[1][h], v[2][h], v[3][h] };
                     if (rp) {
                         q += res[2 * k + h];
-                        q.x = fmaxf(q.x, p.res_act * q.x); q.y = fmaxf(q.y, p.res_act * q.y); q.z = fmaxf(q.z, p.res_act * q.z); q.w = fmaxf(q.w, p.res_act * q.w);
+                        q.x = act_max(q.x, p.res_act * q.x, act_floor(p.res_act)); q.y = act_max(q.y, p.res_act * q.y, act_floor(p.res_act)); q.z = act_max(q.z, p.res_act * q.z, act_floor(p.res_act)); q.w = act_max(q.w, p.res_act * q.w, act_floor(p.res_act));
                     }
                     *reinterpret_cast<v4f *>(op + ((2 * k + h) * cs + (unsigned)(r - 1) * p.W + lo)) = q;
                 }

@@ -216,7 +216,7 @@ template <class T> __device__ __forceinline__ T irbw_ld(const void *base, unsign
 { return *reinterpret_cast<const T *>(reinterpret_cast<const char *>(base) + byte_off); }
 template <class T> __device__ __forceinline__ void irbw_st(void *base, unsigned byte_off, T v)
 { *reinterpret_cast<T *>(reinterpret_cast<char *>(base) + byte_off) = v; }
-__device__ __forceinline__ float irbw_act(float x, float slope) { return fmaxf(x, slope * x); }
+__device__ __forceinline__ float irbw_act(float x, float slope, float floor) { return act_max(x, slope * x, floor); }
 
 // KS1 = k-steps of the expand GEMM (ALIGN(ic,4)/4), OT = ceil(oc/16), S = stride, NSI = 64-pixel strips of the halo
 // tile, BIG = needs more than 128 VGPRs (two waves per SIMD instead of four)
@@ -238,6 +238,8 @@ __global__ void __launch_bounds__(512, BIG ? 2 : (KS1 == 1 && OT == 1 && S == 2 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int kq = lane >> 4, jq = lane & 15;
+    // the relu floors (act_floor), once and outside every lane condition: the scalar read is a convergent operation, and under a lane condition hipcc branches around it
+    const float fl_act1 = act_floor(p.act1), fl_actd = act_floor(p.actd), fl_act2 = act_floor(p.act2), fl_res = act_floor(p.res_act);
     constexpr int NPw = NSI * 64, NQ = NSI * 16;                 // pixels / pixel quads of the halo tile
     constexpr bool PIPE = !X3 && BIG && NSI * 16 + NSI * KS1 * 4 + OT * 16 + 2 * (KS1 + 4 * OT) <= 140;    // the pipelined form keeps a second set of expand accumulators
     const int ecp = p.ngroups * 16;
@@ -311,6 +313,13 @@ __global__ void __launch_bounds__(512, BIG ? 2 : (KS1 == 1 && OT == 1 && S == 2 
         }
         if (!XL) load_strip(si, xin[XL ? 0 : si]);
     }
+    // channels past ic (K is padded to 4 KS1) re-read the last channel's pixels (the clamp in load_strip).  Their weights are zero, but 0 * Inf is NaN where
+    // the reference has no term at all: they count as zero, like the padded k-units of the other split kernels
+    const bool kpad = 4 * (KS1 - 1) + kq >= p.ic;
+    if (!XL && kpad) {
+#pragma unroll
+        for (int si = 0; si < NSI; si++) xin[si][KS1 - 1] = z;
+    }
     // the exact three-way split of a value as the upper halves of three words (X3)
     auto split3 = [&](auto INF, float x, unsigned &u0, unsigned &u1, unsigned &u2) {
         const float r = x3_resid_t<decltype(INF)::value>(x);                          // exact (INF: 0 for +-Inf)
@@ -324,6 +333,7 @@ __global__ void __launch_bounds__(512, BIG ? 2 : (KS1 == 1 && OT == 1 && S == 2 
             const int si = item >> 1, qh = item & 1;
             v4f_w x[KS1];
             load_strip(si, x);
+            if (kpad) x[KS1 - 1] = z;
             float amax = 0.f;
 #pragma unroll
             for (int ks = 0; ks < KS1; ks++) amax = x3_amax3(x3_amax3(amax, x[ks].x, x[ks].y), x[ks].z, x[ks].w);
@@ -515,7 +525,7 @@ __global__ void __launch_bounds__(512, BIG ? 2 : (KS1 == 1 && OT == 1 && S == 2 
                 const v2f_w t = a * sc[rp] + bi[rp];
                 const v2f_w u = t * p.act1;
                 const bool in = (mb >> (si * 4 + q)) & 1u;        // the depthwise layer pads the EXPANDED tensor
-                y[q] = (v2f_w){ in ? fmaxf(t.x, u.x) : 0.f, in ? fmaxf(t.y, u.y) : 0.f };
+                y[q] = (v2f_w){ in ? act_max(t.x, u.x, fl_act1) : 0.f, in ? act_max(t.y, u.y, fl_act1) : 0.f };
             }
             // E slice layout: [pair][half of the pixel quad][quad][2 pixels][2 channels] -- each of the two stores below
             // puts 16 bytes per lane at a 16-byte lane stride (a [pair][pixel][2] layout made them 32-byte strided:
@@ -560,7 +570,7 @@ __global__ void __launch_bounds__(512, BIG ? 2 : (KS1 == 1 && OT == 1 && S == 2 
         for (int q = 0; q < 4; q++) {
             const v2f_w t = dv[q] * sd + bd;
             const v2f_w u = t * p.actd;
-            bq[q] = (v2f_w){ fmaxf(t.x, u.x), fmaxf(t.y, u.y) };
+            bq[q] = (v2f_w){ act_max(t.x, u.x, fl_actd), act_max(t.y, u.y, fl_actd) };
         }
     };
     auto project = [&](const float (&w2)[4 * OT], int m, const v2f_w (&bq)[4]) {
@@ -709,8 +719,8 @@ __global__ void __launch_bounds__(512, BIG ? 2 : (KS1 == 1 && OT == 1 && S == 2 
         } else {
 #pragma unroll
             for (int q = 0; q < 4; q++) {
-                v[q] = irbw_act(fmaf(v[q], sc, bi), p.act2);
-                if (p.residual) v[q] = irbw_act(v[q] + res[q], p.res_act);
+                v[q] = irbw_act(fmaf(v[q], sc, bi), p.act2, fl_act2);
+                if (p.residual) v[q] = irbw_act(v[q] + res[q], p.res_act, fl_res);
             }
         }
         const unsigned off = ((unsigned)oo * ocs + pbase) * 4u;

@@ -19,6 +19,8 @@ __global__ void __launch_bounds__(256, (X3 && KS1 == 2) ? IRBW2_X3_KS2_MINB : 2)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int kq = lane >> 4, jq = lane & 15;
+    // the relu floors (act_floor), once and outside every lane condition: the scalar read is a convergent operation, and under a lane condition hipcc branches around it
+    const float fl_act1 = act_floor(p.act1), fl_actd = act_floor(p.actd), fl_act2 = act_floor(p.act2), fl_res = act_floor(p.res_act);
     constexpr int NPw = NSI * 64, NQ = NSI * 16, NSO = 2;
     const int ecp = p.ngroups * 16;
     const float *Wd = smem, *Sb1 = smem + ecp * 12, *Sb2 = Sb1 + ecp * 2;
@@ -87,6 +89,10 @@ __global__ void __launch_bounds__(256, (X3 && KS1 == 2) ? IRBW2_X3_KS2_MINB : 2)
                 }
             }
         }
+    }
+    if (4 * (KS1 - 1) + kq >= p.ic) {                           // see k_irbw: padded input channels count as zero (0 * Inf)
+#pragma unroll
+        for (int si = 0; si < NSI; si++) xin[si][KS1 - 1] = z;
     }
     // X3: the tile's exact three-way split, packed as bf16 pairs of the lane's channels (2 pr, 2 pr + 1): xp[strip][pixel][part][pair]
     unsigned xp[X3 ? NSI : 1][4][3][X3 ? KS1 / 2 : 1];
@@ -207,7 +213,7 @@ __global__ void __launch_bounds__(256, (X3 && KS1 == 2) ? IRBW2_X3_KS2_MINB : 2)
                     const v2f_w t = a * sc[rp] + bi[rp];
                     const v2f_w u = t * p.act1;
                     const bool in = (mb >> (si * 4 + q)) & 1u;      // the depthwise layer pads the EXPANDED tensor
-                    y[q] = (v2f_w){ in ? fmaxf(t.x, u.x) : 0.f, in ? fmaxf(t.y, u.y) : 0.f };
+                    y[q] = (v2f_w){ in ? act_max(t.x, u.x, fl_act1) : 0.f, in ? act_max(t.y, u.y, fl_act1) : 0.f };
                 }
                 float *dst = Ew + ((2 * kq + rp) * 2 * NQ + si * 16 + jq) * 4;
                 *reinterpret_cast<v4f_w *>(dst) = (v4f_w){ y[0].x, y[0].y, y[1].x, y[1].y };
@@ -262,7 +268,7 @@ __global__ void __launch_bounds__(256, (X3 && KS1 == 2) ? IRBW2_X3_KS2_MINB : 2)
                 for (int q = 0; q < 4; q++) {
                     const v2f_w t = dv[so][q] * sd + bd;
                     const v2f_w u = t * p.actd;
-                    bq[q] = (v2f_w){ fmaxf(t.x, u.x), fmaxf(t.y, u.y) };
+                    bq[q] = (v2f_w){ act_max(t.x, u.x, fl_actd), act_max(t.y, u.y, fl_actd) };
                 }
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
@@ -320,8 +326,8 @@ __global__ void __launch_bounds__(256, (X3 && KS1 == 2) ? IRBW2_X3_KS2_MINB : 2)
                 if (M == 2) {
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
-                        v[q] = irbw_act(v[q], p.act2);
-                        if (p.residual) v[q] = irbw_act(v[q] + res[r][q], p.res_act);
+                        v[q] = irbw_act(v[q], p.act2, fl_act2);
+                        if (p.residual) v[q] = irbw_act(v[q] + res[r][q], p.res_act, fl_res);
                     }
                 }
                 const unsigned off = ((unsigned)oo * ocs + pbase[so]) * 4u;

@@ -42,6 +42,17 @@ __device__ __forceinline__ float act_apply(float x, int act)
     }
 }
 
+// linear / relu / leaky(0.1) in the kernels that carry the activation as a wave-uniform slope (1, 0, 0.1): act(x) = max(max(x, slope x), floor).
+// relu is x > 0 ? x : 0 for EVERY x (utils.h:18), so relu(NaN) = relu(-Inf) = 0 -- but 0 * -Inf and 0 * NaN are NaN, fmaxf drops a NaN operand, and
+// max(x, 0 x) alone hands -Inf and NaN through.  The floor is 0 for relu: it wins over -Inf and over two NaNs.  For leaky and linear max(x, slope x)
+// already is the reference's value for every x, NaN and +-Inf included, and the floor is a NaN, which fmaxf drops.  One scalar select per slope, and
+// v_max3_f32 where v_max_f32 stood.
+__device__ __forceinline__ float act_floor(float slope)            // (read as a scalar: left to itself hipcc keeps the select in a vector register per slope)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(slope == 0.f ? 0 : 0x7fc00000));
+}
+__device__ __forceinline__ float act_max(float x, float sx, float floor) { return fmaxf(fmaxf(x, sx), floor); }
+
 // ---------------------------------------------------------------------------
 // Generic grouped convolution: one thread per output element, taps accumulated
 // in the reference's order (channel, tap row, tap column; conv-v0.c:14-24).

@@ -137,7 +137,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
     const float slope = p.act == 2 ? 0.1f : (p.act == 1 ? 0.f : 1.f), rslope = p.res_act == 2 ? 0.1f : (p.res_act == 1 ? 0.f : 1.f);
     const long pxo = p0 + wn * 64 + 2 * (lane & 31);
     if (pxo >= p.P) return;
-    auto act1 = [&](float t, int a, float sl) { return a == 3 ? 1.0f / (1.0f + (float)exp((double)-t)) : fmaxf(t, sl * t); };
+    auto act1 = [&](float t, int a, float sl) { return a == 3 ? 1.0f / (1.0f + (float)exp((double)-t)) : act_max(t, sl * t, act_floor(sl)); };
 #pragma unroll
     for (int r = 0; r < 2; r++)
 #pragma unroll

@@ -204,7 +204,7 @@ __device__ __forceinline__ void pwg_tile(const PwG32P &p, float *smem, int mt, l
 #pragma unroll
             for (int j = 0; j < PXB; j++) {
                 const float t = fmaf(acc[j][e], sb.x, sb.y);
-                v[j] = (sig && p.act == 3) ? pwg_sigmoid(t) : fmaxf(t, slope * t);
+                v[j] = (sig && p.act == 3) ? pwg_sigmoid(t) : act_max(t, slope * t, act_floor(slope));
             }
             const size_t rowoff = ((size_t)(PWG_TM * mt + ou) * (size_t)p.P + (size_t)p0) * 4;      // uniform
             if (res) {
@@ -212,7 +212,7 @@ __device__ __forceinline__ void pwg_tile(const PwG32P &p, float *smem, int mt, l
 #pragma unroll
                 for (int j = 0; j < PXB; j++) {
                     const float t = v[j] + q[j];
-                    v[j] = (sig && p.res_act == 3) ? pwg_sigmoid(t) : fmaxf(t, rslope * t);
+                    v[j] = (sig && p.res_act == 3) ? pwg_sigmoid(t) : act_max(t, rslope * t, act_floor(rslope));
                 }
             }
             *reinterpret_cast<vB *>(reinterpret_cast<char *>(p.out) + rowoff + voff) = v;

@@ -46,7 +46,7 @@ __device__ __forceinline__ v4f_pw pw_act4(v4f_pw v, float slope, bool sigm)
 {
     if (sigm) return pw_sigmoid4(v);                     // wave-uniform
     v4f_pw r;
-    r.x = fmaxf(v.x, slope * v.x); r.y = fmaxf(v.y, slope * v.y); r.z = fmaxf(v.z, slope * v.z); r.w = fmaxf(v.w, slope * v.w);
+    r.x = act_max(v.x, slope * v.x, act_floor(slope)); r.y = act_max(v.y, slope * v.y, act_floor(slope)); r.z = act_max(v.z, slope * v.z, act_floor(slope)); r.w = act_max(v.w, slope * v.w, act_floor(slope));
     return r;
 }
 

@@ -312,10 +312,11 @@ __device__ __forceinline__ void xt_tile(const PwX3tP &p, unsigned *smem, int mt,
     // row block come with 8 ds_read_b128 up front (rows 8 g + 4 kg + 0 .. 3 are 32 consecutive bytes) -- round 5's listing had one ds_read_b64 per store with
     // `s_waitcnt lgkmcnt(0)` right behind it: 32 exposed LDS latencies per wave; (ii) max(t, slope t) as a bare v_max_f32: behind the opaque fma hipcc put a
     // canonicalising v_max_f32 v, v, v in front of every fmaxf (both operands come out of arithmetic: nothing to quiet).  18 -> 13 vector instructions per store.
-    auto max_raw = [](float a, float b) { float d; asm("v_max_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; };
+    // (with the floor of act_floor as third operand: relu(NaN) = relu(-Inf) = 0 as in the reference; the floor is wave-uniform, one scalar operand)
+    auto max_raw = [](float a, float b, float floor) { float d; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(floor)); return d; };
     auto epilogue = [&](auto FULL, auto RES, auto SIG, auto NT) {
         constexpr bool full = decltype(FULL)::value, res = decltype(RES)::value, sig = decltype(SIG)::value, nt = decltype(NT)::value;
-        auto act1 = [&](float t, int a, float sl) { return (sig && a == 3) ? pwg_sigmoid(t) : max_raw(t, sl * t); };
+        auto act1 = [&](float t, int a, float sl) { return (sig && a == 3) ? pwg_sigmoid(t) : max_raw(t, sl * t, act_floor(sl)); };
 #pragma unroll
         for (int r = 0; r < RB; r++) {
             typedef float v4 __attribute__((ext_vector_type(4)));

@@ -40,6 +40,10 @@ extern "C" {
  * Boxes are the reference's bit for bit (tests/detect_tail), with one exception: a coordinate that is NaN there is NaN here, but the
  * sign and payload of that NaN are unspecified (IEEE 754 leaves them to the implementation). */
 
+/* Activations on non-finite values are the reference's (utils.h:15-23) in EVERY kernel, whichever one a layer or block is planned onto:
+ * relu(x) is x > 0 ? x : 0, so relu(NaN) = 0 and relu(-Inf) = 0 (relu(+Inf) = +Inf); leaky(NaN) = NaN, leaky(-Inf) = -Inf; linear hands
+ * every value on.  A NaN or Inf that an activation does not remove propagates as in conv-v0.c:7-31 (w * Inf = +-Inf, 0 * Inf = NaN). */
+
 /* Per-frame detection record as it lies in device (and gathered host) memory.
  * This is the unit the multi-GPU gather moves: fixed size, 16 + 128*24 bytes. */
 typedef struct {
@@ -321,6 +325,11 @@ float ffgpu_irb_dev(const float *d_in, const float *d_w1, const float *d_wd, con
  * of the packed image -- or "unsupported".  flags: FFGPU_CONCURRENT or 0.  Pure host code (no device needed): for tests and logs. */
 int ffgpu_irb_plan_text(int batch, int iw, int ih, int ic, int ec, int oc, int stride, int act1, int actd, int act2, int res_act,
                         int flags, char *buf, int cap);
+
+/* The key of every instantiation the fused-block families have -- the first word of ffgpu_irb_plan_text's line -- one per line in buf
+ * (at most cap bytes; returns snprintf's count): the thin ones, then the wave ones, then the workgroup ones for both wave counts, read
+ * from the tables the planner dispatches through.  Pure host code: for tests that must reach every one of them. */
+int ffgpu_irb_instantiations(char *buf, int cap);
 
 /* Fused pair: depthwise K x K (K = 3 | 5, stride 1, pad K / 2) -> pointwise 1x1, i.e. two consecutive groupconv calls of the
  * reference in one kernel (the depthwise tensor never leaves the CU).  CNHW device tensors; d_wd / d_wp are the two layers'

@@ -91,3 +91,12 @@ def test_node_needs_a_net_with_device_state(capi):
     import ctypes as C
     assert not capi.lib().ffgpu_node_create(None, 1, None, 4, 0, 0)
     assert "NULL net" in capi.last_error()
+
+
+def test_irb_instantiations_lists_the_three_tables(capi):
+    """ffgpu_irb_instantiations: the keys of the 4 thin, 33 wave and 24 workgroup instantiations, each once, in the plan line's own spelling"""
+    keys = capi.irb_instantiations()
+    assert len(keys) == len(set(keys)) == 61, len(keys)
+    assert [k.split("<")[0] for k in keys] == ["thin"] * 4 + ["irbw2"] * 4 + ["irbw"] * 29 + ["irb"] * 24
+    assert {"thin<8,8,4>", "irbw<6,2,1,2,big,x3>", "irbw2<2,3,x3>", "irb<2,3,1,1,8>", "irb<2,3,2,2,4>", "irbw<12,3,1,2,big,x3,xl>"} <= set(keys)
+    assert capi.irb_plan_text((2, 16, 12, 8, 8, 4, 1, 2, 2, 0, 0)).split(" ")[0] in keys

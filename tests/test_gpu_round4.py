@@ -25,6 +25,10 @@ def env():
 
 # (ic, ec, oc, N, H, W): the three families that run the split expand GEMM by default + the two that can (FFGPU_IRBW_X3 bit 0)
 X3_BLOCKS = [(16, 96, 16, 24, 40, 40), (24, 136, 24, 24, 20, 20), (48, 224, 48, 24, 10, 10), (8, 48, 8, 24, 40, 40), (8, 32, 8, 8, 80, 80)]
+# the two-strip kernels the first and the last two shapes are here for take 768 tiles by default; these planes have fewer, and both modes would plan the same
+# single-strip fp32 kernel -- a kernel compared with itself.  With the tile floor lifted and one wave per tile: irbw2<4,3> against irbw2<4,3,x3>, irbw2<2,3> against irbw2<2,3,x3>
+X3_TWO_STRIP = {"FFGPU_IRBW2_MIN_TILES": "1", "FFGPU_IRBW_G": "1"}
+X3_SWITCHES = {(16, 96, 16, 24, 40, 40): X3_TWO_STRIP, (8, 48, 8, 24, 40, 40): X3_TWO_STRIP, (8, 32, 8, 8, 80, 80): X3_TWO_STRIP}
 
 
 @pytest.mark.gpu
@@ -37,14 +41,22 @@ def test_x3_fused_block_is_an_fp32_reorder(env, shape, monkeypatch):
     f1, fd, f2 = make_filter(rng, ec, ic), make_filter(rng, ec, 9), make_filter(rng, oc, ec)
     res = rng.uniform(-1, 1, (oc * N, H, W)).astype(np.float32)
     t = [torch.from_numpy(a).cuda() for a in (x, f1, fd, f2, res)]
-    outs = {}
+    outs, keys = {}, {}
+    from test_irb_choice import PLANNER_ENV
+    for v in PLANNER_ENV:
+        monkeypatch.delenv(v, raising=False)
+    for k, v in X3_SWITCHES.get(shape, {}).items():
+        monkeypatch.setenv(k, v)
     for mode in ("0", "15"):
         monkeypatch.setenv("FFGPU_IRBW_X3", mode)
+        keys[mode] = capi.irb_plan_text((N, W, H, ic, ec, oc, 1, 2, 2, 0, 0)).split(" ")[0]
         out = torch.full((oc * N, H, W), float("nan"), device="cuda")
         # 40 launches back to back, the last one's output is checked (a timing-dependent slip shows as a handful of wrong tiles)
         capi.irb_dev(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), t[4].data_ptr(), out.data_ptr(), N, W, H, ic, ec, oc, 1, warmup=0, iters=40)
         torch.cuda.synchronize()
         outs[mode] = out.cpu().numpy().reshape(oc, N, H, W)
+    # the two modes ran two kernels, and exactly one of them is a split-bf16 one
+    assert keys["0"] != keys["15"] and ",x3" not in keys["0"] and ",x3" in keys["15"], keys
     assert not np.isnan(outs["15"]).any()
     xf, rf = x.reshape(ic, N, H, W), res.reshape(oc, N, H, W)
     worst = {"0": 0.0, "15": 0.0}
