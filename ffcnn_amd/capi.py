@@ -70,17 +70,32 @@ class DrawStyle(C.Structure):        # ffgpu_draw_style (24 bytes): colour or pa
     _fields_ = [("color", C.c_ubyte * 4), ("palette", C.c_void_p), ("npalette", C.c_int), ("thickness", C.c_int)]
 
 
+class CropSpec(C.Structure):         # ffgpu_crop_spec (72 bytes): which boxes become crops, the slots' geometry and form
+    _fields_ = [("out_w", C.c_int), ("out_h", C.c_int), ("form", C.c_int), ("per_target", C.c_int), ("min_score", C.c_float), ("nclasses", C.c_int),
+                ("classes", C.c_void_p), ("margin_num", C.c_int), ("margin_den", C.c_int), ("mean", C.c_float * 3), ("norm", C.c_float * 3),
+                ("reserved", C.c_int)]
+
+
+class Crop(C.Structure):             # ffgpu_crop (48 bytes): one entry of the crop table
+    _fields_ = [("target", C.c_int), ("box", C.c_int), ("type", C.c_int), ("score", C.c_float), ("x0", C.c_int), ("y0", C.c_int), ("w", C.c_int),
+                ("h", C.c_int), ("sw", C.c_int), ("sh", C.c_int), ("s1", C.c_int), ("s2", C.c_int)]
+
+
+CROP_F32, CROP_U8 = 0, 1                                                               # FFGPU_CROP_* (ffgpu_crop_spec.form)
+CROP_ENTRIES, CROP_MERGED = 0, 1                                                       # FFGPU_CROP_* (ffgpu_exec_crop_bgr / _nv12: which)
 DRAW_ENTRIES, DRAW_MERGED = 0, 1                                                       # FFGPU_DRAW_* (ffgpu_exec_draw_bgr / _nv12: which)
 YUV_BT601_LIMITED, YUV_BT601_FULL, YUV_BT709_LIMITED, YUV_BT709_FULL = 0, 1, 2, 3      # FFGPU_YUV_* (ffgpu_nv12_frame.matrix)
 
 assert C.sizeof(LAYER) == 120 and C.sizeof(NET) == 104 and C.sizeof(BBOX) == 24
 assert C.sizeof(FrameDets) == 16 + 24 * FFGPU.MAX_DET
 assert C.sizeof(BgrFrame) == 24 and C.sizeof(Nv12Frame) == 40 and C.sizeof(Tile) == 16 and C.sizeof(TileRect) == 16
-assert C.sizeof(DrawStyle) == 24
+assert C.sizeof(DrawStyle) == 24 and C.sizeof(CropSpec) == 72 and C.sizeof(Crop) == 48
 
 BOX_DTYPE = np.dtype([("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
 DETS_DTYPE = np.dtype([("count", "<i4"), ("ncand", "<i4"), ("overflow", "<i4"), ("nfull", "<i4"),
                        ("box", BOX_DTYPE, (FFGPU.MAX_DET,))])
+CROP_DTYPE = np.dtype([("target", "<i4"), ("box", "<i4"), ("type", "<i4"), ("score", "<f4"), ("x0", "<i4"), ("y0", "<i4"), ("w", "<i4"), ("h", "<i4"),
+                       ("sw", "<i4"), ("sh", "<i4"), ("s1", "<i4"), ("s2", "<i4")])
 
 # every symbol include/*.h declares; tests check the built library exports all of them
 EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_profile", "groupconv",
@@ -96,7 +111,9 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_node_submit", "ffgpu_node_wait", "ffgpu_node_run",
            "ffgpu_merge_tiles_scratch_bytes", "ffgpu_merge_tiles_dev", "ffgpu_exec_merge_tiles", "ffgpu_exec_merged_dev", "ffgpu_exec_read_merged",
            "ffgpu_exec_read_merged_boxes", "ffgpu_tile_plan",
-           "ffgpu_draw_boxes_bgr_dev", "ffgpu_draw_boxes_nv12_dev", "ffgpu_exec_draw_bgr", "ffgpu_exec_draw_nv12"]
+           "ffgpu_draw_boxes_bgr_dev", "ffgpu_draw_boxes_nv12_dev", "ffgpu_exec_draw_bgr", "ffgpu_exec_draw_nv12",
+           "ffgpu_crop_table_bytes", "ffgpu_crop_slot_bytes", "ffgpu_crop_boxes_bgr_dev", "ffgpu_crop_boxes_nv12_dev", "ffgpu_exec_crop_bgr", "ffgpu_exec_crop_nv12",
+           "ffgpu_crops_to_source_dev"]
 # include/ffcnn_hip_diag.h (libffcnn_hip_diag.so: lab equipment, its own library)
 DIAG_EXPORTS = ["ffgpu_membench", "ffgpu_pipe_probe", "ffgpu_pipe_probe2", "ffgpu_pipe_probe3", "ffgpu_mfma_floor", "ffgpu_diag_x3_term", "ffgpu_diag_xl_op", "ffgpu_clock_probe"]
 
@@ -220,6 +237,15 @@ def lib():
     L.ffgpu_draw_boxes_nv12_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(Nv12Frame), i, C.POINTER(DrawStyle), vp]
     L.ffgpu_exec_draw_bgr.argtypes = [vp, i, C.POINTER(BgrFrame), i, C.POINTER(DrawStyle), vp]
     L.ffgpu_exec_draw_nv12.argtypes = [vp, i, C.POINTER(Nv12Frame), i, C.POINTER(DrawStyle), vp]
+    L.ffgpu_crop_table_bytes.restype = sz
+    L.ffgpu_crop_table_bytes.argtypes = [i]
+    L.ffgpu_crop_slot_bytes.restype = sz
+    L.ffgpu_crop_slot_bytes.argtypes = [i, i, i]
+    L.ffgpu_crop_boxes_bgr_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(BgrFrame), i, C.POINTER(CropSpec), vp, vp, i, vp]
+    L.ffgpu_crop_boxes_nv12_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(Nv12Frame), i, C.POINTER(CropSpec), vp, vp, i, vp]
+    L.ffgpu_exec_crop_bgr.argtypes = [vp, i, C.POINTER(BgrFrame), i, C.POINTER(CropSpec), vp, vp, i, vp]
+    L.ffgpu_exec_crop_nv12.argtypes = [vp, i, C.POINTER(Nv12Frame), i, C.POINTER(CropSpec), vp, vp, i, vp]
+    L.ffgpu_crops_to_source_dev.argtypes = [vp, i, vp, vp, i, vp, vp, vp]
     _lib = L
     return L
 
@@ -544,6 +570,16 @@ class Executor:
         arr = nv12_frame_table(frames)
         _check(lib().ffgpu_exec_draw_nv12(self.h, which, arr, len(frames), draw_style(color, palette, thickness), stream), "ffgpu_exec_draw_nv12")
 
+    def crop_bgr(self, frames, spec, d_out, d_table, capacity, which=0, stream=None):
+        """enqueue the cut of the last forward's boxes (which = CROP_ENTRIES: entry n out of frames[n]) or of the last merge's (CROP_MERGED: picture
+        g out of frames[g]) behind it (ffgpu_exec_crop_bgr): frames as forward_bgr_frames_dev takes them (None, or a NULL address: skipped), spec
+        from crop_spec, d_out / d_table the caller's device buffers of capacity slots (crop_slot_bytes) and crop_table_bytes(capacity) bytes"""
+        _check(lib().ffgpu_exec_crop_bgr(self.h, which, bgr_frame_table(frames), len(frames), spec, d_out, d_table, capacity, stream), "ffgpu_exec_crop_bgr")
+
+    def crop_nv12(self, frames, spec, d_out, d_table, capacity, which=0, stream=None, matrix=0):
+        """the same out of NV12 frames (ffgpu_exec_crop_nv12): frames as forward_nv12_frames_dev takes them"""
+        _check(lib().ffgpu_exec_crop_nv12(self.h, which, nv12_frame_table(frames, matrix), len(frames), spec, d_out, d_table, capacity, stream), "ffgpu_exec_crop_nv12")
+
     def read_candidates(self, frame=0):
         out = np.zeros(max(1, self.cand_capacity), BOX_DTYPE)
         n = _check(lib().ffgpu_exec_read_layer(self.h, -2, frame, out.ctypes.data_as(f32p), out.size * 6), "read candidates")
@@ -664,6 +700,59 @@ def draw_boxes_bgr_dev(d_records, d_lists, list_stride, frames, style=None, list
 def draw_boxes_nv12_dev(d_records, d_lists, list_stride, frames, style=None, list_first=None, stream=None):
     """ffgpu_draw_boxes_nv12_dev: the same into NV12 frames (what nv12_frame_desc accepts, or None: skipped); colours are Y U V bytes"""
     _draw_boxes_dev(lib().ffgpu_draw_boxes_nv12_dev, "ffgpu_draw_boxes_nv12_dev", nv12_frame_table, d_records, d_lists, list_stride, list_first, frames, style, stream)
+
+
+def crop_spec(out_w, out_h, form=CROP_F32, per_target=1, min_score=0.0, classes=None, margin=(0, 1), mean=(0.0, 0.0, 0.0), norm=(1 / 255.0,) * 3):
+    """a CropSpec: classes is None (every class) or a sequence of 1..256 flags indexed by the box's class; margin is (num, den).  The structure
+    keeps its class bytes alive."""
+    sp = CropSpec()
+    sp.out_w, sp.out_h, sp.form, sp.per_target, sp.min_score = out_w, out_h, form, per_target, min_score
+    sp.margin_num, sp.margin_den = margin
+    sp.mean[:], sp.norm[:] = [float(v) for v in mean], [float(v) for v in norm]
+    if classes is not None:
+        cls = np.ascontiguousarray(np.asarray(classes) != 0, np.uint8) if len(classes) else np.zeros(1, np.uint8)
+        sp._cls = cls                                           # (owned by the structure: the C side reads it during the call)
+        sp.classes = cls.ctypes.data
+        sp.nclasses = len(classes)
+    return sp
+
+
+def crop_table_bytes(capacity):
+    return lib().ffgpu_crop_table_bytes(capacity)
+
+
+def crop_slot_bytes(out_w, out_h, form=CROP_F32):
+    return lib().ffgpu_crop_slot_bytes(out_w, out_h, form)
+
+
+def crop_table(raw):
+    """(header dict, entries as a CROP_DTYPE array) of a crop table's bytes (a uint8 array of crop_table_bytes(capacity) bytes)"""
+    raw = np.ascontiguousarray(raw, np.uint8).reshape(-1)
+    hdr = raw[:16].view("<i4")
+    return dict(total=int(hdr[0]), taken=int(hdr[1]), empty=int(hdr[2]), capacity=int(hdr[3])), raw[16:].view(CROP_DTYPE)
+
+
+def _crop_boxes_dev(fn, name, table, d_records, d_lists, list_stride, list_first, frames, spec, d_out, d_table, capacity, stream):
+    first = None if list_first is None else (C.c_int * max(1, len(list_first)))(*[int(v) for v in list_first])
+    _check(fn(d_records, d_lists, list_stride, first, table(frames), len(frames), spec, d_out, d_table, capacity, stream), name)
+
+
+def crop_boxes_bgr_dev(d_records, d_lists, list_stride, frames, spec, d_out, d_table, capacity, list_first=None, stream=None):
+    """ffgpu_crop_boxes_bgr_dev on device records / lists: the selected boxes of record t cut out of frames[t] (what bgr_frame_desc accepts, or
+    None: skipped) into the slots at d_out, the table at d_table; d_lists None: the records' own boxes; list_first as draw_boxes_bgr_dev"""
+    _crop_boxes_dev(lib().ffgpu_crop_boxes_bgr_dev, "ffgpu_crop_boxes_bgr_dev", bgr_frame_table, d_records, d_lists, list_stride, list_first, frames, spec,
+                    d_out, d_table, capacity, stream)
+
+
+def crop_boxes_nv12_dev(d_records, d_lists, list_stride, frames, spec, d_out, d_table, capacity, list_first=None, stream=None):
+    """ffgpu_crop_boxes_nv12_dev: the same out of NV12 frames (what nv12_frame_desc accepts, or None: skipped)"""
+    _crop_boxes_dev(lib().ffgpu_crop_boxes_nv12_dev, "ffgpu_crop_boxes_nv12_dev", nv12_frame_table, d_records, d_lists, list_stride, list_first, frames, spec,
+                    d_out, d_table, capacity, stream)
+
+
+def crops_to_source_dev(d_table, capacity, d_records, d_lists, list_stride, d_out_records, d_out_lists=None, stream=None):
+    """ffgpu_crops_to_source_dev: the records (and full lists) of a forward over the slots back into the sources' coordinates; in place is legal"""
+    _check(lib().ffgpu_crops_to_source_dev(d_table, capacity, d_records, d_lists, list_stride, d_out_records, d_out_lists, stream), "ffgpu_crops_to_source_dev")
 
 
 def tile_table(tiles):

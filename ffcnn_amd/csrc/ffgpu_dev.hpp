@@ -191,3 +191,23 @@ int ffgpu_draw_targets_bgr(const char *what, const ffgpu_bgr_frame *f, int n, st
 int ffgpu_draw_targets_nv12(const char *what, const ffgpu_nv12_frame *f, int n, std::vector<DrawTarget> &out);
 int ffgpu_launch_draw(bool nv12, const ffgpu_frame_dets *recs, const BBOX *lists, int stride, const std::vector<DrawTarget> &targets,
                       const unsigned pal[256], int npal, int thickness, hipStream_t s);
+
+// the detections cut out of the frames (ffgpu_crop.inc).  One source as the kernels read it: a DrawTarget that is only read, with the NV12 matrix
+// (fmt as FrameDesc::fmt).  CropPlan: the caller's spec, checked, with the class filter's bytes copied.
+struct CropSrc {
+    const unsigned char *p0;      // row 0 of the BGR pixels / of the Y plane; NULL: a skipped source
+    const unsigned char *p1;      // NV12: row 0 of the interleaved U V plane (2-byte aligned); BGR: NULL
+    long long first;
+    int w, h, pitch, pitch_uv;
+    int fmt, pad_;
+};
+struct CropPlan {
+    int   out_w, out_h, form, per_target, nclasses, num, den;
+    float min_score, mean[3], norm[3];
+    unsigned char classes[256];
+};
+int ffgpu_crop_spec_check(const char *what, const ffgpu_crop_spec *sp, CropPlan &pl);
+int ffgpu_crop_sources(const char *what, bool nv12, const void *targets, int n, std::vector<CropSrc> &out);
+int ffgpu_crop_buffers_check(const char *what, const void *d_out, const void *d_table, int capacity);
+int ffgpu_launch_crop(bool nv12, const ffgpu_frame_dets *recs, const BBOX *lists, int stride, const std::vector<CropSrc> &sources, const CropPlan &pl,
+                      void *d_out, void *d_table, int capacity, hipStream_t s);

@@ -1481,6 +1481,56 @@ extern "C" int ffgpu_exec_draw_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_
     return exec_draw(ex, true, "draw_nv12", which, targets, ntargets, style, stream);
 }
 
+// -------------------------------------------------------------------------- the detections cut out of the frames (include/ffcnn_hip.h; kernels: ffgpu_crop.inc)
+// A post-pass like the draw, on the stream of the forward or merge it follows: reads the records and full lists (per entry, or the merged ones) and
+// the caller's frames, writes the caller's batch buffer and table and nothing of the executor's.
+static int exec_crop(ffgpu_exec *ex, bool nv12, const char *what, int which, const void *targets, int ntargets, const ffgpu_crop_spec *spec,
+                     void *d_out, void *d_table, int capacity, void *stream)
+{
+    int ndev = 0;
+    if (!ex && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)) {
+        (void)hipGetLastError();
+        ffgpu_set_error("%s: no HIP device visible: libffcnn_hip has no CPU fallback", what);
+        return -1;
+    }
+    if (!alive(ex, what)) return -1;
+    if (!targets) { ffgpu_set_error("%s: NULL targets", what); return -1; }
+    CropPlan pl;
+    if (ffgpu_crop_spec_check(what, spec, pl) || ffgpu_crop_buffers_check(what, d_out, d_table, capacity)) return -1;
+    if (which != FFGPU_CROP_ENTRIES && which != FFGPU_CROP_MERGED) { ffgpu_set_error("%s: which = %d is neither FFGPU_CROP_ENTRIES nor FFGPU_CROP_MERGED", what, which); return -1; }
+    const bool merged = which == FFGPU_CROP_MERGED;
+    if (merged && !merged_ok(ex, what)) return -1;
+    const int want = merged ? (int)ex->mrg_off.size() - 1 : ex->N;
+    if (ntargets != want) {
+        if (merged) ffgpu_set_error("%s: %d targets for a merge of %d pictures", what, ntargets, want);
+        else ffgpu_set_error("%s: %d targets for an executor of batch %d", what, ntargets, want);
+        return -1;
+    }
+    const hipStream_t s = stream ? (hipStream_t)stream : ex->own_stream;
+    if (s != ex->last_stream) { ffgpu_set_error("%s: the crop must be enqueued on the stream of the forward or merge it follows", what); return -1; }
+    std::vector<CropSrc> tab;
+    if (ffgpu_crop_sources(what, nv12, targets, ntargets, tab)) return -1;
+    int most = 1;                                                    // (the clamp of the list lengths: as exec_draw)
+    for (int t = 0; t < ntargets; t++) {
+        tab[t].first = (long long)ex->cand_cap * (merged ? ex->mrg_off[t] : t);
+        if (merged) most = std::max(most, ex->mrg_off[t + 1] - ex->mrg_off[t]);
+    }
+    const int stride = (int)std::min((long long)ex->cand_cap * most, (long long)0x7fffffff);
+    return ffgpu_launch_crop(nv12, merged ? ex->d_merged : ex->d_dets, merged ? ex->d_merged_full : ex->d_full, stride, tab, pl, d_out, d_table, capacity, s);
+}
+
+extern "C" int ffgpu_exec_crop_bgr(ffgpu_exec *ex, int which, const ffgpu_bgr_frame *sources, int ntargets, const ffgpu_crop_spec *spec,
+                                   void *d_out, void *d_table, int capacity, void *stream)
+{
+    return exec_crop(ex, false, "crop_bgr", which, sources, ntargets, spec, d_out, d_table, capacity, stream);
+}
+
+extern "C" int ffgpu_exec_crop_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_frame *sources, int ntargets, const ffgpu_crop_spec *spec,
+                                    void *d_out, void *d_table, int capacity, void *stream)
+{
+    return exec_crop(ex, true, "crop_nv12", which, sources, ntargets, spec, d_out, d_table, capacity, stream);
+}
+
 // FFGPU_KEEP_ALL executors: one 64-bit hash per materialised layer over the layer's WHOLE batch tensor (every bit of every frame), computed on the
 // device behind the last forward; 0 for layers this executor does not materialise.  What the concurrency soak compares round after round
 // (tests/test_gpu_round5.py): 8 bytes per layer cross the bus instead of the activations.

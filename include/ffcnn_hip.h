@@ -467,6 +467,93 @@ int ffgpu_draw_boxes_nv12_dev(const void *d_records, const void *d_lists, int li
 int ffgpu_exec_draw_bgr (ffgpu_exec *ex, int which, const ffgpu_bgr_frame  *targets, int ntargets, const ffgpu_draw_style *style, void *stream);
 int ffgpu_exec_draw_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_frame *targets, int ntargets, const ffgpu_draw_style *style, void *stream);
 
+/* ---- the detections cut out of the frames on the device, for a second stage ---------------------------------------------------------------
+ * A cascade looks again at each detected object -- with this net at full resolution, with another cfg, for a thumbnail.  What follows selects
+ * boxes, resamples each one's region of its source frame into one slot of a caller-owned batch buffer exactly as net_input (ffcnn.c:259-289)
+ * would if the region were an image of its own, and moves the boxes of a forward over those slots back into source coordinates; no record and
+ * no frame crosses the bus.
+ *
+ * Sources: descriptors as the draw contract takes them (ffgpu_bgr_frame / ffgpu_nv12_frame with the draw contract's checks, a NULL pixel
+ * address = "skip this source": none of its boxes take part); a w or h of 2^31 - 1 is rejected as well.  The sources are only read.
+ *
+ * Selection.  Sources are walked in ascending order, each one's list in list order.  A box QUALIFIES when score >= min_score (a NaN score never
+ * does) and its class is allowed: every type with classes == NULL, else 0 <= type < nclasses and classes[type] != 0.  Its integer corners
+ * (a, b, c, d) are the draw contract's (toward zero, saturating, NaN -> 0).  In 64-bit integers: mx = (c - a + 1) num / den,
+ * my = (d - b + 1) num / den, X0 = max(a - mx, 0), X1 = min(c + mx, w - 1), Y0 = max(b - my, 0), Y1 = min(d + my, h - 1).  A qualifying box
+ * with a > c or b > d, or with X0 > X1 or Y0 > Y1, is counted in `empty` (wherever it stands in its list) and takes nothing.  Every other
+ * qualifying box is SELECTED until its source has per_target selected boxes.  `total` counts the selected boxes; the first taken =
+ * min(total, capacity) of them, in that order, own slots 0 .. taken-1.
+ * The table, in the caller's device memory (16-byte aligned, ffgpu_crop_table_bytes(capacity) bytes): a header { int total, taken, empty,
+ * capacity } and `capacity` entries ffgpu_crop.  Entry n < taken: the source's index, the box's index in its list, its type and score, the
+ * region x0 = X0, y0 = Y0, w = X1 - X0 + 1, h = Y1 - Y0 + 1, and net_input's letterbox of a w x h image into out_w x out_h (ffcnn.c:267-273)
+ * as sw, sh, s1, s2.  Entries taken .. capacity-1: target = -1, s1 = s2 = 1, zero elsewhere.  No atomic decides an order: the table is the
+ * same byte for byte on every run and however many sources there are.
+ * Pixels.  Slot n < taken is net_input of the region: output pixel (x, y), x < sw, y < sh, is source pixel (x0 + x s1 / s2, y0 + y s1 / s2)
+ * (integer division, 64-bit product).  The source pixel is the frame's B G R bytes, or for NV12 the integer formula above with nearest
+ * chroma taken at the PICTURE's coordinates: odd origins are legal, no region is rounded.  FFGPU_CROP_F32: ((float)byte - mean) * norm, two
+ * roundings, planes R G B.  FFGPU_CROP_U8: the three bytes.  Every other pixel of the slot, all of slots taken .. capacity-1 and, in the U8
+ * form, every row's padding bytes are zero.  A call writes every byte of `capacity` slots and of the table and nothing before or behind them. */
+#define FFGPU_CROP_F32 0   /* slot n: three planes R, G, B of out_h x out_w fp32 = frame n of ffgpu_exec_forward_dev's batch                    */
+#define FFGPU_CROP_U8  1   /* slot n: out_h rows of ALIGN(3 out_w, 4) bytes B G R = frame n of ffgpu_exec_forward_bgr_dev's batch, or a picture */
+typedef struct {
+    int   out_w, out_h;             /* 1..4096: the second stage's geometry                                                       */
+    int   form;                     /* FFGPU_CROP_F32 | FFGPU_CROP_U8                                                             */
+    int   per_target;               /* 1..2^24: selected boxes per source at most                                                 */
+    float min_score;
+    int   nclasses;                 /* 0 with NULL classes, else 1..256                                                           */
+    const unsigned char *classes;   /* HOST array of nclasses bytes (non-zero: the class is allowed), or NULL: every class        */
+    int   margin_num, margin_den;   /* den 1..1024, num 0..4 den: the region is the box grown by num / den of its size each way   */
+    float mean[3], norm[3];         /* FFGPU_CROP_F32 only: net_input's per-channel mean / norm (plane order R, G, B)             */
+    int   reserved;                 /* 0                                                                                          */
+} ffgpu_crop_spec;                  /* 72 bytes: out_w 0, out_h 4, form 8, per_target 12, min_score 16, nclasses 20, classes 24,  */
+                                    /* margin_num 32, margin_den 36, mean 40, norm 52, reserved 64                                */
+typedef struct {
+    int   target, box, type;        /* the source's index, the box's index in its list, the box's class                           */
+    float score;
+    int   x0, y0, w, h;             /* the region in the source                                                                   */
+    int   sw, sh, s1, s2;           /* its letterbox: it fills the top-left sw x sh of the slot, source pixel = (x s1 / s2, ...)    */
+} ffgpu_crop;                       /* 48 bytes, behind the table's 16-byte header                                                */
+
+/* pure host code: the bytes of a table of `capacity` entries, and of one slot (0 for arguments outside their ranges) */
+size_t ffgpu_crop_table_bytes(int capacity);
+size_t ffgpu_crop_slot_bytes(int out_w, int out_h, int form);
+
+/* The operators, on device records and lists with no executor.  d_records, d_lists, list_stride and the HOST array list_first are the draw
+ * operators' and so are the clamps of the counts: whatever the records hold, nothing is read outside the buffers the host has sized or outside
+ * a source's w x h.  d_out: capacity x ffgpu_crop_slot_bytes bytes, 16-byte aligned.  sources, list_first, spec and spec->classes are HOST
+ * memory and free again on return; the tables travel as kernel arguments, 64 sources per launch, and the count of boxes selected so far
+ * travels in the table's header in stream order.  Enqueued on `stream` without synchronising.  Rejected before anything is launched, with the
+ * source's index ("target k") in the message where there is one: NULL records, sources, spec, output or table, ntargets < 1, capacity < 1
+ * (or above 2^24), a spec field outside its range, nclasses inconsistent with classes, reserved != 0, a bad list_stride, a negative list
+ * start, an output or table that is not 16-byte aligned, ntargets x list_stride above 2^31 - 1, a descriptor the forward would reject other
+ * than for a NULL address. */
+int ffgpu_crop_boxes_bgr_dev (const void *d_records, const void *d_lists, int list_stride, const int *list_first, const ffgpu_bgr_frame  *sources,
+                              int ntargets, const ffgpu_crop_spec *spec, void *d_out, void *d_table, int capacity, void *stream);
+int ffgpu_crop_boxes_nv12_dev(const void *d_records, const void *d_lists, int list_stride, const int *list_first, const ffgpu_nv12_frame *sources,
+                              int ntargets, const ffgpu_crop_spec *spec, void *d_out, void *d_table, int capacity, void *stream);
+
+#define FFGPU_CROP_ENTRIES 0   /* entry n's full post-NMS list out of sources[n]; ntargets == batch                                      */
+#define FFGPU_CROP_MERGED  1   /* picture g's merged list (last ffgpu_exec_merge_tiles) out of sources[g]; ntargets == its nimages        */
+/* On an executor: a post-pass like ffgpu_exec_draw_*, enqueued on `stream` (NULL = the executor's own; it must be the stream of the forward
+ * or merge it follows) without synchronising.  The captured graph, the records, the full lists, the ring and the host mirror are untouched;
+ * the output and the table are the caller's.  Works on FFGPU_SPLIT2 executors.  Rejected like the operators, and: ntargets not as stated, a
+ * `which` that is neither, FFGPU_CROP_MERGED when no merge has run, the wrong stream.  A rejected call leaves the executor usable. */
+int ffgpu_exec_crop_bgr (ffgpu_exec *ex, int which, const ffgpu_bgr_frame  *sources, int ntargets, const ffgpu_crop_spec *spec,
+                         void *d_out, void *d_table, int capacity, void *stream);
+int ffgpu_exec_crop_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_frame *sources, int ntargets, const ffgpu_crop_spec *spec,
+                         void *d_out, void *d_table, int capacity, void *stream);
+
+/* Map back: d_records holds `capacity` records of a forward over the slots (boxes in slot pixels rescaled by the SLOT's own s1 / s2 = 1, i.e.
+ * in the second net's pixels: run that forward with the default scale), d_lists (may be NULL) their full lists, list n at box n x list_stride.
+ * For slot n < taken every box of record n -- its own box[0 .. count), count clamped to [0, FFGPU_MAX_DET], and its nfull list boxes, clamped to
+ * [0, list_stride], when d_lists and d_out_lists are given -- becomes x * (float)s1 / (float)s2 + (float)x0, y likewise: fp32 multiply, then
+ * divide, then add, not contracted (k_nms's rescale followed by the merge's translation).  type, score and the four counters are copied,
+ * unused box slots of the record are zero; list boxes behind nfull are not written.  Slots taken .. capacity-1 give zero records (a net run on
+ * a zero frame may emit boxes: they do not leak).  In place (d_out_records == d_records, d_out_lists == d_lists) is legal.  Rejected: a NULL
+ * table or records, capacity < 1, a table that is not 16-byte aligned, a bad list_stride with d_lists given. */
+int ffgpu_crops_to_source_dev(const void *d_table, int capacity, const void *d_records, const void *d_lists, int list_stride,
+                              void *d_out_records, void *d_out_lists, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
