@@ -81,6 +81,19 @@ class Crop(C.Structure):             # ffgpu_crop (48 bytes): one entry of the c
                 ("h", C.c_int), ("sw", C.c_int), ("sh", C.c_int), ("s1", C.c_int), ("s2", C.c_int)]
 
 
+class TrackSpec(C.Structure):        # ffgpu_track_spec (32 bytes): the tracker's settings
+    _fields_ = [("capacity", C.c_int), ("max_missed", C.c_int), ("min_hits", C.c_int), ("iou_thresh", C.c_float), ("min_score", C.c_float),
+                ("birth_score", C.c_float), ("class_aware", C.c_int), ("reserved", C.c_int)]
+
+
+class Track(C.Structure):            # ffgpu_track (48 bytes): one slot of a stream's state
+    _fields_ = [("id", C.c_int), ("type", C.c_int), ("score", C.c_float), ("x1", C.c_float), ("y1", C.c_float), ("x2", C.c_float), ("y2", C.c_float),
+                ("hits", C.c_int), ("missed", C.c_int), ("born", C.c_int), ("det", C.c_int), ("reserved", C.c_int)]
+
+
+TRACK_DETS = 128                                                                       # FFGPU_TRACK_DETS
+TRACK_ENTRIES, TRACK_MERGED = 0, 1                                                     # FFGPU_TRACK_* (ffgpu_exec_track: which)
+TRACK_IDS_HEADER = ("considered", "matched", "born", "refused", "dropped", "freed", "live", "frame")   # the 8 ints in front of a row of ids
 CROP_F32, CROP_U8 = 0, 1                                                               # FFGPU_CROP_* (ffgpu_crop_spec.form)
 CROP_ENTRIES, CROP_MERGED = 0, 1                                                       # FFGPU_CROP_* (ffgpu_exec_crop_bgr / _nv12: which)
 DRAW_ENTRIES, DRAW_MERGED = 0, 1                                                       # FFGPU_DRAW_* (ffgpu_exec_draw_bgr / _nv12: which)
@@ -90,12 +103,15 @@ assert C.sizeof(LAYER) == 120 and C.sizeof(NET) == 104 and C.sizeof(BBOX) == 24
 assert C.sizeof(FrameDets) == 16 + 24 * FFGPU.MAX_DET
 assert C.sizeof(BgrFrame) == 24 and C.sizeof(Nv12Frame) == 40 and C.sizeof(Tile) == 16 and C.sizeof(TileRect) == 16
 assert C.sizeof(DrawStyle) == 24 and C.sizeof(CropSpec) == 72 and C.sizeof(Crop) == 48
+assert C.sizeof(TrackSpec) == 32 and C.sizeof(Track) == 48
 
 BOX_DTYPE = np.dtype([("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
 DETS_DTYPE = np.dtype([("count", "<i4"), ("ncand", "<i4"), ("overflow", "<i4"), ("nfull", "<i4"),
                        ("box", BOX_DTYPE, (FFGPU.MAX_DET,))])
 CROP_DTYPE = np.dtype([("target", "<i4"), ("box", "<i4"), ("type", "<i4"), ("score", "<f4"), ("x0", "<i4"), ("y0", "<i4"), ("w", "<i4"), ("h", "<i4"),
                        ("sw", "<i4"), ("sh", "<i4"), ("s1", "<i4"), ("s2", "<i4")])
+TRACK_DTYPE = np.dtype([("id", "<i4"), ("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"),
+                        ("hits", "<i4"), ("missed", "<i4"), ("born", "<i4"), ("det", "<i4"), ("reserved", "<i4")])
 
 # every symbol include/*.h declares; tests check the built library exports all of them
 EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_profile", "groupconv",
@@ -113,7 +129,8 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_exec_read_merged_boxes", "ffgpu_tile_plan",
            "ffgpu_draw_boxes_bgr_dev", "ffgpu_draw_boxes_nv12_dev", "ffgpu_exec_draw_bgr", "ffgpu_exec_draw_nv12",
            "ffgpu_crop_table_bytes", "ffgpu_crop_slot_bytes", "ffgpu_crop_boxes_bgr_dev", "ffgpu_crop_boxes_nv12_dev", "ffgpu_exec_crop_bgr", "ffgpu_exec_crop_nv12",
-           "ffgpu_crops_to_source_dev"]
+           "ffgpu_crops_to_source_dev",
+           "ffgpu_track_state_bytes", "ffgpu_track_reset_dev", "ffgpu_track_boxes_dev", "ffgpu_exec_track"]
 # include/ffcnn_hip_diag.h (libffcnn_hip_diag.so: lab equipment, its own library)
 DIAG_EXPORTS = ["ffgpu_membench", "ffgpu_pipe_probe", "ffgpu_pipe_probe2", "ffgpu_pipe_probe3", "ffgpu_mfma_floor", "ffgpu_diag_x3_term", "ffgpu_diag_xl_op", "ffgpu_clock_probe"]
 
@@ -246,6 +263,11 @@ def lib():
     L.ffgpu_exec_crop_bgr.argtypes = [vp, i, C.POINTER(BgrFrame), i, C.POINTER(CropSpec), vp, vp, i, vp]
     L.ffgpu_exec_crop_nv12.argtypes = [vp, i, C.POINTER(Nv12Frame), i, C.POINTER(CropSpec), vp, vp, i, vp]
     L.ffgpu_crops_to_source_dev.argtypes = [vp, i, vp, vp, i, vp, vp, vp]
+    L.ffgpu_track_state_bytes.restype = sz
+    L.ffgpu_track_state_bytes.argtypes = [i, i]
+    L.ffgpu_track_reset_dev.argtypes = [vp, i, i, i, vp]
+    L.ffgpu_track_boxes_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(i), i, C.POINTER(TrackSpec), vp, i, vp, vp, vp, vp]
+    L.ffgpu_exec_track.argtypes = [vp, i, C.POINTER(i), i, C.POINTER(TrackSpec), vp, i, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -580,6 +602,13 @@ class Executor:
         """the same out of NV12 frames (ffgpu_exec_crop_nv12): frames as forward_nv12_frames_dev takes them"""
         _check(lib().ffgpu_exec_crop_nv12(self.h, which, nv12_frame_table(frames, matrix), len(frames), spec, d_out, d_table, capacity, stream), "ffgpu_exec_crop_nv12")
 
+    def track(self, streams, spec, d_state, nstreams, d_ids, d_out_records=None, d_out_lists=None, which=0, stream=None):
+        """enqueue the tracker on the last forward's boxes (which = TRACK_ENTRIES: entry n is record n of video stream streams[n], -1: ignored) or on
+        the last merge's (TRACK_MERGED: picture g) behind it (ffgpu_exec_track): spec from track_spec, d_state / d_ids / d_out_* the caller's device
+        buffers (track_state_bytes; rows of 8 + S ints; records; lists of S boxes, S as include/ffcnn_hip.h states it)"""
+        arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+        _check(lib().ffgpu_exec_track(self.h, which, arr, len(streams), spec, d_state, nstreams, d_ids, d_out_records, d_out_lists, stream), "ffgpu_exec_track")
+
     def read_candidates(self, frame=0):
         out = np.zeros(max(1, self.cand_capacity), BOX_DTYPE)
         n = _check(lib().ffgpu_exec_read_layer(self.h, -2, frame, out.ctypes.data_as(f32p), out.size * 6), "read candidates")
@@ -753,6 +782,40 @@ def crop_boxes_nv12_dev(d_records, d_lists, list_stride, frames, spec, d_out, d_
 def crops_to_source_dev(d_table, capacity, d_records, d_lists, list_stride, d_out_records, d_out_lists=None, stream=None):
     """ffgpu_crops_to_source_dev: the records (and full lists) of a forward over the slots back into the sources' coordinates; in place is legal"""
     _check(lib().ffgpu_crops_to_source_dev(d_table, capacity, d_records, d_lists, list_stride, d_out_records, d_out_lists, stream), "ffgpu_crops_to_source_dev")
+
+
+def track_spec(capacity, max_missed=0, min_hits=1, iou_thresh=0.3, min_score=0.0, birth_score=0.0, class_aware=1):
+    """a TrackSpec (ffgpu_track_spec)"""
+    sp = TrackSpec()
+    sp.capacity, sp.max_missed, sp.min_hits, sp.class_aware = capacity, max_missed, min_hits, int(class_aware)
+    sp.iou_thresh, sp.min_score, sp.birth_score = iou_thresh, min_score, birth_score
+    return sp
+
+
+def track_state_bytes(nstreams, capacity):
+    return lib().ffgpu_track_state_bytes(nstreams, capacity)
+
+
+def track_state(raw, nstreams, capacity):
+    """([header dict per stream], slots as a TRACK_DTYPE array of nstreams x capacity) of a state's bytes (a uint8 array of track_state_bytes bytes)"""
+    raw = np.ascontiguousarray(raw, np.uint8).reshape(nstreams, 16 + 48 * capacity)
+    hdr = [dict(zip(("issued", "frames", "live", "reserved"), (int(v) for v in r[:16].view("<i4")))) for r in raw]
+    return hdr, np.ascontiguousarray(raw[:, 16:]).view(TRACK_DTYPE).reshape(nstreams, capacity)
+
+
+def track_reset_dev(d_state, nstreams, capacity, which_stream=-1, stream=None):
+    """ffgpu_track_reset_dev: zero the state of one video stream, or of all (-1), in stream order"""
+    _check(lib().ffgpu_track_reset_dev(d_state, nstreams, capacity, which_stream, stream), "ffgpu_track_reset_dev")
+
+
+def track_boxes_dev(d_records, d_lists, list_stride, streams, spec, d_state, nstreams, d_ids, d_out_records=None, d_out_lists=None, list_first=None,
+                    stream=None):
+    """ffgpu_track_boxes_dev on device records / lists: record t is the next frame of video stream streams[t] (-1: ignored); d_lists None: the
+    records' own boxes; list_first as draw_boxes_bgr_dev"""
+    first = None if list_first is None else (C.c_int * max(1, len(list_first)))(*[int(v) for v in list_first])
+    arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+    _check(lib().ffgpu_track_boxes_dev(d_records, d_lists, list_stride, first, arr, len(streams), spec, d_state, nstreams, d_ids, d_out_records,
+                                       d_out_lists, stream), "ffgpu_track_boxes_dev")
 
 
 def tile_table(tiles):

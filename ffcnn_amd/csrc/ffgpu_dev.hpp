@@ -211,3 +211,10 @@ int ffgpu_crop_sources(const char *what, bool nv12, const void *targets, int n, 
 int ffgpu_crop_buffers_check(const char *what, const void *d_out, const void *d_table, int capacity);
 int ffgpu_launch_crop(bool nv12, const ffgpu_frame_dets *recs, const BBOX *lists, int stride, const std::vector<CropSrc> &sources, const CropPlan &pl,
                       void *d_out, void *d_table, int capacity, hipStream_t s);
+
+// the detections tracked across a stream's frames (ffgpu_track.inc): the checks both entry points share, and the launches (record t's list starts
+// at box first[t] of `lists`)
+int ffgpu_track_args_check(const char *what, const int *streams, int ntargets, const ffgpu_track_spec *spec, const void *d_state, int nstreams,
+                           const void *d_ids, const void *d_out_records, const void *d_out_lists);
+int ffgpu_launch_track(const ffgpu_frame_dets *recs, const BBOX *lists, int stride, const long long *first, const int *streams, int ntargets,
+                       const ffgpu_track_spec &spec, void *d_state, void *d_ids, void *d_out_records, void *d_out_lists, hipStream_t s);

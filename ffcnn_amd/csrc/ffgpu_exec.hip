@@ -1531,6 +1531,43 @@ extern "C" int ffgpu_exec_crop_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_
     return exec_crop(ex, true, "crop_nv12", which, sources, ntargets, spec, d_out, d_table, capacity, stream);
 }
 
+// -------------------------------------------------------------------------- the detections tracked across frames (include/ffcnn_hip.h; kernel: ffgpu_track.inc)
+// A post-pass like the crop, on the stream of the forward or merge it follows: reads the records and full lists (per entry, or the merged ones),
+// writes the caller's state, ids and tracked records and nothing of the executor's.
+extern "C" int ffgpu_exec_track(ffgpu_exec *ex, int which, const int *streams, int ntargets, const ffgpu_track_spec *spec, void *d_state, int nstreams,
+                                void *d_ids, void *d_out_records, void *d_out_lists, void *stream)
+{
+    const char *const what = "exec_track";
+    int ndev = 0;
+    if (!ex && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)) {
+        (void)hipGetLastError();
+        ffgpu_set_error("%s: no HIP device visible: libffcnn_hip has no CPU fallback", what);
+        return -1;
+    }
+    if (!alive(ex, what)) return -1;
+    if (ffgpu_track_args_check(what, streams, ntargets, spec, d_state, nstreams, d_ids, d_out_records, d_out_lists)) return -1;
+    if (which != FFGPU_TRACK_ENTRIES && which != FFGPU_TRACK_MERGED) { ffgpu_set_error("%s: which = %d is neither FFGPU_TRACK_ENTRIES nor FFGPU_TRACK_MERGED", what, which); return -1; }
+    const bool merged = which == FFGPU_TRACK_MERGED;
+    if (merged && !merged_ok(ex, what)) return -1;
+    const int want = merged ? (int)ex->mrg_off.size() - 1 : ex->N;
+    if (ntargets != want) {
+        if (merged) ffgpu_set_error("%s: %d targets for a merge of %d pictures", what, ntargets, want);
+        else ffgpu_set_error("%s: %d targets for an executor of batch %d", what, ntargets, want);
+        return -1;
+    }
+    const hipStream_t s = stream ? (hipStream_t)stream : ex->own_stream;
+    if (s != ex->last_stream) { ffgpu_set_error("%s: the tracker must be enqueued on the stream of the forward or merge it follows", what); return -1; }
+    std::vector<long long> first((size_t)ntargets, 0);
+    int most = 1;                                                    // (the clamp of the list lengths: as exec_draw)
+    for (int t = 0; t < ntargets; t++) {
+        first[t] = (long long)ex->cand_cap * (merged ? ex->mrg_off[t] : t);
+        if (merged) most = std::max(most, ex->mrg_off[t + 1] - ex->mrg_off[t]);
+    }
+    if ((long long)ex->cand_cap * most > (1 << 24)) { ffgpu_set_error("%s: lists of up to %lld boxes are too long", what, (long long)ex->cand_cap * most); return -1; }
+    return ffgpu_launch_track(merged ? ex->d_merged : ex->d_dets, merged ? ex->d_merged_full : ex->d_full, ex->cand_cap * most, first.data(), streams, ntargets,
+                              *spec, d_state, d_ids, d_out_records, d_out_lists, s);
+}
+
 // FFGPU_KEEP_ALL executors: one 64-bit hash per materialised layer over the layer's WHOLE batch tensor (every bit of every frame), computed on the
 // device behind the last forward; 0 for layers this executor does not materialise.  What the concurrency soak compares round after round
 // (tests/test_gpu_round5.py): 8 bytes per layer cross the bus instead of the activations.

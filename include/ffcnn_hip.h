@@ -554,6 +554,90 @@ int ffgpu_exec_crop_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_frame *sour
 int ffgpu_crops_to_source_dev(const void *d_table, int capacity, const void *d_records, const void *d_lists, int list_stride,
                               void *d_out_records, void *d_out_lists, void *stream);
 
+/* ---- the detections tracked across a stream's frames on the device ---------------------------------------------------------------------------
+ * Every step above treats a frame as if it were alone.  What follows associates the boxes of consecutive frames of one video stream -- "is this
+ * the car of the previous frame?" -- where the records lie, in HBM: a greedy, class-aware IoU tracker with "last box, no motion model".  Its
+ * result is a pure function of its inputs: the same bytes on every run, comparable byte for byte (tests/tracks/trackref.py restates it).
+ *
+ * Streams and order.  A call handles ntargets records.  streams[t] (a HOST int array) is the video stream of record t, 0 .. nstreams-1, or -1:
+ * the entry is ignored.  The records of one stream are consecutive in time in ascending t; across calls, order on the HIP stream is time order.
+ * Streams are independent of each other.
+ * State, in the caller's device memory (16-byte aligned, ffgpu_track_state_bytes(nstreams, capacity) bytes): per stream a 16-byte header
+ * { int issued, frames, live, reserved } and `capacity` entries ffgpu_track.  id == 0 is a free slot and a free slot is all zero; all-zero
+ * memory is the valid empty state, so hipMemsetAsync (or ffgpu_track_reset_dev) initialises it.  Ids are ++issued, a 32-bit counter: after
+ * 2^32 - 1 births of one stream it wraps (through 0 and the negative ids); this is not handled.
+ *
+ * One frame of one stream, in this order:
+ *   1. Detections.  The record's list is walked in list order (d_lists, list_stride, list_first and the clamps of the draw operators).  A box is
+ *      CONSIDERED when score >= min_score (a NaN score never is), until FFGPU_TRACK_DETS boxes are considered; further qualifying boxes are
+ *      counted in `dropped`.
+ *   2. IoU of track a (its last box) and considered detection j, with exactly the arithmetic of the merge with use_min == 0: area =
+ *      (x2 - x1) * (y2 - y1); xa = a.x1 > j.x1 ? a.x1 : j.x1, ya likewise, xb = a.x2 < j.x2 ? a.x2 : j.x2, yb likewise; inter =
+ *      (xb - xa) * (yb - ya) if xa < xb && ya < yb, else 0; iou = inter / (area_a + area_j - inter): fp32, not contracted, IEEE division.  A
+ *      pair is ELIGIBLE when iou >= iou_thresh (NaN never is) and, with class_aware, the types are equal.
+ *   3. Matching.  The eligible pairs are walked in the total order "iou descending (as fp32 values compare), then track slot ascending, then
+ *      detection index ascending"; a pair whose track and detection are both still unmatched is a match.  No atomic and no arrival order
+ *      decides anything.
+ *   4. A matched track takes the detection's type, score and box; hits += 1, missed = 0, det = the box's index in its list.
+ *   5. An unmatched track: missed += 1, det = -1; if missed > max_missed the slot is freed (zeroed).
+ *   6. Births, after the frees, in ascending detection index: an unmatched considered detection with score >= birth_score takes the lowest free
+ *      slot: id = ++issued, hits = 1, missed = 0, born = frames, det = its index.  With no free slot it is counted in `refused`.
+ *   7. frames += 1 and live = the number of occupied slots -- also for a frame without boxes.
+ *
+ * Outputs per record t; every byte is written, for streams[t] == -1 as zero.  S = list_stride, or FFGPU_MAX_DET when d_lists is NULL.
+ *   d_ids: row t of 8 + S ints: the header { considered, matched, born, refused, dropped, freed, live, frame } (frame: the stream's frame
+ *     number of this record = `frames` before step 7), then ids[k] for box k of the list: 0 when the box was not considered or was neither
+ *     matched nor born, else the id of its track when that track now has hits >= min_hits, else -id.  Entries behind the list are 0.
+ *   d_out_records / d_out_lists (may be NULL; list t at box t x S): the TRACKED RECORD: the n considered boxes whose track now has hits >=
+ *     min_hits, in list order, unchanged except that `type` is the track id.  count = min(n, FFGPU_MAX_DET), nfull = n, ncand and overflow
+ *     bit 0 copied, bit 2 = n > FFGPU_MAX_DET; unused box slots of the record and of the list are zero.  The outputs must not overlap the inputs.
+ * The tracked record is the composition point and needs no new code: the draw operators colour it per OBJECT (the palette entry is type mod
+ * npalette, and type is the track id), the crop operators put the track id into ffgpu_crop.type, so a cascade can look once per object. */
+#define FFGPU_TRACK_DETS 128   /* considered detections per frame at most; also the largest capacity */
+typedef struct {
+    int   capacity;                 /* 1..128: track slots per stream (as the state was sized)                                      */
+    int   max_missed;               /* 0..2^20: a track survives this many consecutive frames without a match                       */
+    int   min_hits;                 /* 1..2^20: a track is reported with its positive id from this many hits on                     */
+    float iou_thresh;               /* finite, in [0, 1]                                                                            */
+    float min_score;                /* finite, in [0, 1]: a detection is considered from this score on                              */
+    float birth_score;              /* finite, in [0, 1]: an unmatched detection starts a track from this score on                  */
+    int   class_aware;              /* 0 | 1: a pair needs equal types                                                              */
+    int   reserved;                 /* 0                                                                                            */
+} ffgpu_track_spec;                 /* 32 bytes: capacity 0, max_missed 4, min_hits 8, iou_thresh 12, min_score 16, birth_score 20, */
+                                    /* class_aware 24, reserved 28                                                                  */
+typedef struct {
+    int   id, type;                 /* id 0: a free slot (all zero); type, score and the box: the last matched detection's          */
+    float score, x1, y1, x2, y2;
+    int   hits, missed;             /* matched frames in all; consecutive frames without a match                                    */
+    int   born, det;                /* the stream's frame number of its birth; its box's index in the last frame's list, or -1      */
+    int   reserved;                 /* 0                                                                                            */
+} ffgpu_track;                      /* 48 bytes, behind each stream's 16-byte header { int issued, frames, live, reserved }         */
+
+/* pure host code: the bytes of the state of nstreams (1..65536) streams of capacity (1..128) slots; 0 for arguments outside their ranges */
+size_t ffgpu_track_state_bytes(int nstreams, int capacity);
+/* zeroes the state of one stream, or of all with which_stream == -1, in stream order (a memset; no kernel) */
+int ffgpu_track_reset_dev(void *d_state, int nstreams, int capacity, int which_stream, void *stream);
+
+/* The operator, on device records and lists with no executor.  d_records, d_lists, list_stride and the HOST array list_first are the draw
+ * operators'.  One workgroup per video stream walks that stream's records of the call serially, tracks and detections in LDS; streams,
+ * list_first and spec are HOST memory and free again on return; the tables travel as kernel arguments, 128 records per launch, the launches of
+ * one call in order on `stream`.  Enqueued without synchronising.  Rejected before anything is launched, with the entry's index in the message
+ * where there is one: NULL records, streams, spec, state or ids, ntargets < 1, nstreams outside 1..65536, a stream index outside
+ * -1..nstreams-1, a spec field outside its range or reserved != 0, a state that is not 16-byte aligned, a bad list_stride, a negative list
+ * start, d_out_lists without d_out_records.  A rejected call leaves the state as it was. */
+int ffgpu_track_boxes_dev(const void *d_records, const void *d_lists, int list_stride, const int *list_first, const int *streams, int ntargets,
+                          const ffgpu_track_spec *spec, void *d_state, int nstreams, void *d_ids, void *d_out_records, void *d_out_lists, void *stream);
+
+#define FFGPU_TRACK_ENTRIES 0   /* entry n's full post-NMS list is record n; ntargets == batch; S = ffgpu_exec_cand_capacity()                      */
+#define FFGPU_TRACK_MERGED  1   /* picture g's merged list (last ffgpu_exec_merge_tiles) is record g; ntargets == its nimages; S =                */
+                                /* ffgpu_exec_cand_capacity() x the most tiles any picture of that merge has                                     */
+/* On an executor: a post-pass like ffgpu_exec_crop_*, enqueued on `stream` (NULL = the executor's own; it must be the stream of the forward or
+ * merge it follows) without synchronising.  The captured graph, the records, the full lists, the ring and the host mirror are untouched; state,
+ * ids and the tracked records are the caller's.  Works on FFGPU_SPLIT2 executors.  Rejected like the operator, and: ntargets not as stated, a
+ * `which` that is neither, FFGPU_TRACK_MERGED when no merge has run, the wrong stream.  A rejected call leaves the state and the executor usable. */
+int ffgpu_exec_track(ffgpu_exec *ex, int which, const int *streams, int ntargets, const ffgpu_track_spec *spec, void *d_state, int nstreams,
+                     void *d_ids, void *d_out_records, void *d_out_lists, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
