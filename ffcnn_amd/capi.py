@@ -18,6 +18,11 @@ class FFGPU:
     MAX_DET = 128
     MERGE_LDS_SLOTS = 1024               # FFGPU_MERGE_LDS_SLOTS: unions up to this many boxes are merged in LDS (ffgpu_merge_tiles_dev)
     KEEP_ALL, COMPAT_V6, NO_GRAPH, NO_FUSE, HOST_DETS, SPLIT2, CONCURRENT, BF16_PW = 1, 2, 4, 8, 16, 32, 64, 128
+    FEAT_FLAT, FEAT_MEAN, FEAT_MAX = 0, 1, 2                 # FFGPU_FEAT_* (ffgpu_feature_spec.pool)
+    POST_NONE, POST_SOFTMAX, POST_L2 = 0, 1, 2               # FFGPU_POST_* (ffgpu_feature_spec.post)
+    TOPK_MAX = 16                                            # FFGPU_TOPK_MAX
+    RELABEL_KEEP_SCORE, RELABEL_LABEL_SCORE = 0, 1           # FFGPU_RELABEL_* (ffgpu_relabel_spec.score_mode)
+    RELABEL_ENTRIES, RELABEL_MERGED = 0, 1                   # FFGPU_RELABEL_* (ffgpu_exec_relabel: which)
     K_AUTO, K_GENERIC, K_DW_STREAM, K_DW_LDS, K_PW_MFMA, K_PW_GEMM, _K6, K_DENSE_SMALL, K_IGEMM, K_PW_BF16, K_GROUP_THIN, K_PW_X3, K_CONV_X3, K_PW_X3T = range(14)
 
 
@@ -91,6 +96,18 @@ class Track(C.Structure):            # ffgpu_track (48 bytes): one slot of a str
                 ("hits", C.c_int), ("missed", C.c_int), ("born", C.c_int), ("det", C.c_int), ("reserved", C.c_int)]
 
 
+class FeatureSpec(C.Structure):      # ffgpu_feature_spec (16 bytes): which tensor, how it becomes a row, what is applied to the row
+    _fields_ = [("layer", C.c_int), ("pool", C.c_int), ("post", C.c_int), ("reserved", C.c_int)]
+
+
+class Label(C.Structure):            # ffgpu_label (8 bytes): one entry of a top-k row
+    _fields_ = [("index", C.c_int), ("value", C.c_float)]
+
+
+class RelabelSpec(C.Structure):      # ffgpu_relabel_spec (16 bytes): which labels are applied, and how
+    _fields_ = [("min_value", C.c_float), ("type_base", C.c_int), ("score_mode", C.c_int), ("reserved", C.c_int)]
+
+
 TRACK_DETS = 128                                                                       # FFGPU_TRACK_DETS
 TRACK_ENTRIES, TRACK_MERGED = 0, 1                                                     # FFGPU_TRACK_* (ffgpu_exec_track: which)
 TRACK_IDS_HEADER = ("considered", "matched", "born", "refused", "dropped", "freed", "live", "frame")   # the 8 ints in front of a row of ids
@@ -104,6 +121,7 @@ assert C.sizeof(FrameDets) == 16 + 24 * FFGPU.MAX_DET
 assert C.sizeof(BgrFrame) == 24 and C.sizeof(Nv12Frame) == 40 and C.sizeof(Tile) == 16 and C.sizeof(TileRect) == 16
 assert C.sizeof(DrawStyle) == 24 and C.sizeof(CropSpec) == 72 and C.sizeof(Crop) == 48
 assert C.sizeof(TrackSpec) == 32 and C.sizeof(Track) == 48
+assert C.sizeof(FeatureSpec) == 16 and C.sizeof(Label) == 8 and C.sizeof(RelabelSpec) == 16
 
 BOX_DTYPE = np.dtype([("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
 DETS_DTYPE = np.dtype([("count", "<i4"), ("ncand", "<i4"), ("overflow", "<i4"), ("nfull", "<i4"),
@@ -112,6 +130,7 @@ CROP_DTYPE = np.dtype([("target", "<i4"), ("box", "<i4"), ("type", "<i4"), ("sco
                        ("sw", "<i4"), ("sh", "<i4"), ("s1", "<i4"), ("s2", "<i4")])
 TRACK_DTYPE = np.dtype([("id", "<i4"), ("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"),
                         ("hits", "<i4"), ("missed", "<i4"), ("born", "<i4"), ("det", "<i4"), ("reserved", "<i4")])
+LABEL_DTYPE = np.dtype([("index", "<i4"), ("value", "<f4")])
 
 # every symbol include/*.h declares; tests check the built library exports all of them
 EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_profile", "groupconv",
@@ -130,7 +149,9 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_draw_boxes_bgr_dev", "ffgpu_draw_boxes_nv12_dev", "ffgpu_exec_draw_bgr", "ffgpu_exec_draw_nv12",
            "ffgpu_crop_table_bytes", "ffgpu_crop_slot_bytes", "ffgpu_crop_boxes_bgr_dev", "ffgpu_crop_boxes_nv12_dev", "ffgpu_exec_crop_bgr", "ffgpu_exec_crop_nv12",
            "ffgpu_crops_to_source_dev",
-           "ffgpu_track_state_bytes", "ffgpu_track_reset_dev", "ffgpu_track_boxes_dev", "ffgpu_exec_track"]
+           "ffgpu_track_state_bytes", "ffgpu_track_reset_dev", "ffgpu_track_boxes_dev", "ffgpu_exec_track",
+           "ffgpu_feature_dim", "ffgpu_exec_feature_dim", "ffgpu_features_dev", "ffgpu_exec_features", "ffgpu_topk_dev", "ffgpu_crops_relabel_dev",
+           "ffgpu_exec_relabel"]
 # include/ffcnn_hip_diag.h (libffcnn_hip_diag.so: lab equipment, its own library)
 DIAG_EXPORTS = ["ffgpu_membench", "ffgpu_pipe_probe", "ffgpu_pipe_probe2", "ffgpu_pipe_probe3", "ffgpu_mfma_floor", "ffgpu_diag_x3_term", "ffgpu_diag_xl_op", "ffgpu_clock_probe"]
 
@@ -268,6 +289,13 @@ def lib():
     L.ffgpu_track_reset_dev.argtypes = [vp, i, i, i, vp]
     L.ffgpu_track_boxes_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(i), i, C.POINTER(TrackSpec), vp, i, vp, vp, vp, vp]
     L.ffgpu_exec_track.argtypes = [vp, i, C.POINTER(i), i, C.POINTER(TrackSpec), vp, i, vp, vp, vp, vp]
+    L.ffgpu_feature_dim.argtypes = [i, i, i, i]
+    L.ffgpu_exec_feature_dim.argtypes = [vp, C.POINTER(FeatureSpec)]
+    L.ffgpu_features_dev.argtypes = [vp, i, i, i, i, i, i, vp, C.c_long, vp]
+    L.ffgpu_exec_features.argtypes = [vp, C.POINTER(FeatureSpec), vp, C.c_long, vp]
+    L.ffgpu_topk_dev.argtypes = [vp, i, i, C.c_long, i, vp, vp]
+    L.ffgpu_crops_relabel_dev.argtypes = [vp, i, vp, i, vp, vp, i, C.POINTER(i), i, C.POINTER(RelabelSpec), vp, vp, vp]
+    L.ffgpu_exec_relabel.argtypes = [vp, i, vp, i, vp, i, i, C.POINTER(RelabelSpec), vp, vp, vp]
     _lib = L
     return L
 
@@ -609,6 +637,25 @@ class Executor:
         arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
         _check(lib().ffgpu_exec_track(self.h, which, arr, len(streams), spec, d_state, nstreams, d_ids, d_out_records, d_out_lists, stream), "ffgpu_exec_track")
 
+    def feature_dim(self, spec):
+        """D of the rows Executor.features writes for `spec` (a FeatureSpec from feature_spec); pure host code (ffgpu_exec_feature_dim)"""
+        return _check(lib().ffgpu_exec_feature_dim(self.h, spec), "ffgpu_exec_feature_dim")
+
+    def features(self, spec, d_out, out_stride=None, stream=None):
+        """enqueue the rows of the last forward's tensor behind it (ffgpu_exec_features): spec from feature_spec (layer -1: the tensor the last layer
+        leaves), d_out the caller's device buffer of batch rows, out_stride floats apart (default: D); returns D"""
+        d = self.feature_dim(spec)
+        _check(lib().ffgpu_exec_features(self.h, spec, d_out, d if out_stride is None else out_stride, stream), "ffgpu_exec_features")
+        return d
+
+    def relabel(self, d_table, capacity, d_labels, k, spec, d_out_records, d_out_lists=None, which=0, ntargets=None, stream=None):
+        """enqueue the relabelling of the last forward's records and lists (which = RELABEL_ENTRIES; ntargets = the batch) or of the last merge's
+        (RELABEL_MERGED; ntargets = its pictures) behind it (ffgpu_exec_relabel): d_table the crop table these records' crops were cut with, d_labels
+        its slots' top-k rows of k Label each, spec from relabel_spec, d_out_* the caller's device buffers (records; lists of S boxes, S as
+        include/ffcnn_hip.h states it)"""
+        n = self.batch if ntargets is None else ntargets
+        _check(lib().ffgpu_exec_relabel(self.h, which, d_table, capacity, d_labels, k, n, spec, d_out_records, d_out_lists, stream), "ffgpu_exec_relabel")
+
     def read_candidates(self, frame=0):
         out = np.zeros(max(1, self.cand_capacity), BOX_DTYPE)
         n = _check(lib().ffgpu_exec_read_layer(self.h, -2, frame, out.ctypes.data_as(f32p), out.size * 6), "read candidates")
@@ -816,6 +863,48 @@ def track_boxes_dev(d_records, d_lists, list_stride, streams, spec, d_state, nst
     arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
     _check(lib().ffgpu_track_boxes_dev(d_records, d_lists, list_stride, first, arr, len(streams), spec, d_state, nstreams, d_ids, d_out_records,
                                        d_out_lists, stream), "ffgpu_track_boxes_dev")
+
+
+def feature_spec(layer=-1, pool=FFGPU.FEAT_MEAN, post=FFGPU.POST_NONE):
+    """a FeatureSpec (ffgpu_feature_spec)"""
+    return FeatureSpec(layer, pool, post, 0)
+
+
+def feature_dim(c, h, w, pool):
+    """ffgpu_feature_dim: D of a c x h x w tensor under `pool`; 0 outside the ranges (no GPU needed)"""
+    return lib().ffgpu_feature_dim(c, h, w, pool)
+
+
+def features_dev(d_in, n, c, h, w, pool, post, d_out, out_stride=None, stream=None):
+    """ffgpu_features_dev on a device tensor in CNHW layout: n rows of D floats at d_out, out_stride floats apart (default: D); returns D"""
+    d = feature_dim(c, h, w, pool)
+    _check(lib().ffgpu_features_dev(d_in, n, c, h, w, pool, post, d_out, (d if out_stride is None else out_stride), stream), "ffgpu_features_dev")
+    return d
+
+
+def topk_dev(d_in, n, d, k, d_out, in_stride=None, stream=None):
+    """ffgpu_topk_dev: the k best (index, value) of each of n rows of d floats (in_stride floats apart, default d) as n x k Label at d_out"""
+    _check(lib().ffgpu_topk_dev(d_in, n, d, d if in_stride is None else in_stride, k, d_out, stream), "ffgpu_topk_dev")
+
+
+def relabel_spec(min_value=0.0, type_base=0, score_mode=FFGPU.RELABEL_KEEP_SCORE):
+    """a RelabelSpec (ffgpu_relabel_spec)"""
+    return RelabelSpec(min_value, type_base, score_mode, 0)
+
+
+def crops_relabel_dev(d_table, capacity, d_labels, k, d_records, d_lists, list_stride, ntargets, spec, d_out_records, d_out_lists=None, list_first=None,
+                      stream=None):
+    """ffgpu_crops_relabel_dev on device records / lists: the best label of every crop slot written into the box the crop was cut from; d_lists None:
+    the records' own boxes; list_first as draw_boxes_bgr_dev"""
+    first = None if list_first is None else (C.c_int * max(1, len(list_first)))(*[int(v) for v in list_first])
+    _check(lib().ffgpu_crops_relabel_dev(d_table, capacity, d_labels, k, d_records, d_lists, list_stride, first, ntargets, spec, d_out_records, d_out_lists,
+                                         stream), "ffgpu_crops_relabel_dev")
+
+
+# the operators as attributes of FFGPU as well (FFGPU.features_dev(...)), next to the constants they take
+for _f in (feature_spec, feature_dim, features_dev, topk_dev, relabel_spec, crops_relabel_dev):
+    setattr(FFGPU, _f.__name__, staticmethod(_f))
+del _f
 
 
 def tile_table(tiles):

@@ -218,3 +218,12 @@ int ffgpu_track_args_check(const char *what, const int *streams, int ntargets, c
                            const void *d_ids, const void *d_out_records, const void *d_out_lists);
 int ffgpu_launch_track(const ffgpu_frame_dets *recs, const BBOX *lists, int stride, const long long *first, const int *streams, int ntargets,
                        const ffgpu_track_spec &spec, void *d_state, void *d_ids, void *d_out_records, void *d_out_lists, hipStream_t s);
+
+// the crops classified (ffgpu_feature.inc): the checks both entry points share, and the launches.  Features: frame n of the tensor is frame n % pn of
+// parts[n / pn], a CNHW tensor of pn frames (a split executor has one part per chain; at most 8).  Relabel: record t's list starts at box first[t].
+int ffgpu_feature_args_check(const char *what, int n, int c, int h, int w, int pool, int post, const void *d_out, long out_stride);
+int ffgpu_launch_features(const float *const *parts, int nparts, int pn, int c, int h, int w, int pool, int post, float *d_out, long out_stride, hipStream_t s);
+int ffgpu_relabel_args_check(const char *what, const void *d_table, int capacity, const void *d_labels, int k, int ntargets, const ffgpu_relabel_spec *spec,
+                             const void *d_out_records);
+int ffgpu_launch_relabel(const void *d_table, int capacity, const void *d_labels, int k, const ffgpu_frame_dets *recs, const BBOX *lists, int stride,
+                         const long long *first, int ntargets, const ffgpu_relabel_spec &spec, void *d_out_records, void *d_out_lists, hipStream_t s);

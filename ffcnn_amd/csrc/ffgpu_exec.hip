@@ -1568,6 +1568,106 @@ extern "C" int ffgpu_exec_track(ffgpu_exec *ex, int which, const int *streams, i
                               *spec, d_state, d_ids, d_out_records, d_out_lists, s);
 }
 
+// -------------------------------------------------------------------------- the crops classified (include/ffcnn_hip.h; kernels: ffgpu_feature.inc)
+// The tensor a feature spec names on this plan: its id and the frame's c x h x w, or -1 with a message.  layer == -1 is the last layer's, aliases
+// resolved by canon[] (a trailing dropout or one-source route holds its source's tensor id).  Nothing takes that tensor's floats after the forward: the
+// first-fit allocator of plan() hands a range on only to a tensor whose first use lies BEHIND the range's last use, pass 3 extends a tensor's last use to
+// every layer that reads it -- a trailing route's index included -- and behind a trailing dropout (which touches nothing) no tensor is born at all.
+static int feature_tensor(const ffgpu_exec *ex, const char *what, const ffgpu_feature_spec *spec, int *c, int *h, int *w)
+{
+    if (!spec) { ffgpu_set_error("%s: NULL spec", what); return -1; }
+    if (spec->reserved != 0) { ffgpu_set_error("%s: spec: reserved must be 0", what); return -1; }
+    const ffgpu_exec *pl = ex->child[0] ? ex->child[0] : ex;        // (the parts of a split executor have one and the same plan)
+    const int L = ex->net->layer_num;
+    int layer = spec->layer;
+    if (layer < -1 || layer >= L) { ffgpu_set_error("%s: layer %d is outside -1 .. %d", what, layer, L - 1); return -1; }
+    if (layer >= 0 && !(ex->flags & FFGPU_KEEP_ALL)) { ffgpu_set_error("%s: layer %d needs an FFGPU_KEEP_ALL executor (layer -1, the last layer's tensor, is legal on every plan)", what, layer); return -1; }
+    if (layer < 0) layer = L - 1;
+    if (L < 1) { ffgpu_set_error("%s: the net has no layer", what); return -1; }
+    if (ex->net->layer_list[layer].type == LAYER_TYPE_YOLO) {
+        ffgpu_set_error("%s: layer %d is a [yolo] layer: it leaves no tensor (its product is the detection records)", what, layer);
+        return -1;
+    }
+    const int t = pl->canon[layer];
+    if (t == -1) { ffgpu_set_error("%s: layer %d is an alias of the net input, which is frame-major: no CNHW tensor", what, layer); return -1; }
+    if (t < 0 || !pl->readable[layer]) { ffgpu_set_error("%s: layer %d is not materialised by this executor (fused away or no tensor)", what, layer); return -1; }
+    const LAYER &o = ex->net->layer_list[layer + 1];
+    *c = o.c; *h = o.h; *w = o.w;
+    return t;
+}
+
+extern "C" int ffgpu_exec_feature_dim(const ffgpu_exec *ex, const ffgpu_feature_spec *spec)
+{
+    const char *const what = "exec_feature_dim";
+    if (!alive(ex, what)) return -1;
+    int c = 0, h = 0, w = 0;
+    if (feature_tensor(ex, what, spec, &c, &h, &w) < 0) return -1;
+    if (spec->pool < FFGPU_FEAT_FLAT || spec->pool > FFGPU_FEAT_MAX) { ffgpu_set_error("%s: pool %d is none of FFGPU_FEAT_FLAT, _MEAN, _MAX", what, spec->pool); return -1; }
+    const int d = ffgpu_feature_dim(c, h, w, spec->pool);
+    if (d < 1) { ffgpu_set_error("%s: %d x %d x %d gives a plane or a row of more than 2^24 values", what, c, h, w); return -1; }
+    return d;
+}
+
+// A post-pass like the crop, on the stream of the forward it follows: reads the tensor the forward left (each part's, on a split executor), writes the
+// caller's rows and nothing of the executor's.
+extern "C" int ffgpu_exec_features(ffgpu_exec *ex, const ffgpu_feature_spec *spec, float *d_out, long out_stride, void *stream)
+{
+    const char *const what = "exec_features";
+    int ndev = 0;
+    if (!ex && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)) {
+        (void)hipGetLastError();
+        ffgpu_set_error("%s: no HIP device visible: libffcnn_hip has no CPU fallback", what);
+        return -1;
+    }
+    if (!alive(ex, what)) return -1;
+    int c = 0, h = 0, w = 0;
+    const int t = feature_tensor(ex, what, spec, &c, &h, &w);
+    if (t < 0) return -1;
+    if (ffgpu_feature_args_check(what, ex->N, c, h, w, spec->pool, spec->post, d_out, out_stride)) return -1;
+    const hipStream_t s = stream ? (hipStream_t)stream : ex->own_stream;
+    if (s != ex->last_stream) { ffgpu_set_error("%s: the features must be enqueued on the stream of the forward they follow", what); return -1; }
+    const float *parts[ffgpu_exec::MAXPART] = {};
+    const int nparts = ex->child[0] ? ex->nchild : 1;
+    for (int k = 0; k < nparts; k++) parts[k] = tensor_ptr(ex->child[0] ? ex->child[k] : ex, t);
+    return ffgpu_launch_features(parts, nparts, ex->N / nparts, c, h, w, spec->pool, spec->post, d_out, out_stride, s);
+}
+
+// On the first stage's executor: reads its records and full lists (per entry, or the merged ones), the caller's table and labels; writes the caller's
+// relabelled records and lists and nothing of the executor's.
+extern "C" int ffgpu_exec_relabel(ffgpu_exec *ex, int which, const void *d_table, int capacity, const void *d_labels, int k, int ntargets,
+                                  const ffgpu_relabel_spec *spec, void *d_out_records, void *d_out_lists, void *stream)
+{
+    const char *const what = "exec_relabel";
+    int ndev = 0;
+    if (!ex && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)) {
+        (void)hipGetLastError();
+        ffgpu_set_error("%s: no HIP device visible: libffcnn_hip has no CPU fallback", what);
+        return -1;
+    }
+    if (!alive(ex, what)) return -1;
+    if (ffgpu_relabel_args_check(what, d_table, capacity, d_labels, k, ntargets, spec, d_out_records)) return -1;
+    if (which != FFGPU_RELABEL_ENTRIES && which != FFGPU_RELABEL_MERGED) { ffgpu_set_error("%s: which = %d is neither FFGPU_RELABEL_ENTRIES nor FFGPU_RELABEL_MERGED", what, which); return -1; }
+    const bool merged = which == FFGPU_RELABEL_MERGED;
+    if (merged && !merged_ok(ex, what)) return -1;
+    const int want = merged ? (int)ex->mrg_off.size() - 1 : ex->N;
+    if (ntargets != want) {
+        if (merged) ffgpu_set_error("%s: %d targets for a merge of %d pictures", what, ntargets, want);
+        else ffgpu_set_error("%s: %d targets for an executor of batch %d", what, ntargets, want);
+        return -1;
+    }
+    const hipStream_t s = stream ? (hipStream_t)stream : ex->own_stream;
+    if (s != ex->last_stream) { ffgpu_set_error("%s: the relabelling must be enqueued on the stream of the forward or merge it follows", what); return -1; }
+    std::vector<long long> first((size_t)ntargets, 0);
+    int most = 1;                                                    // (the clamp of the list lengths: as exec_draw)
+    for (int t = 0; t < ntargets; t++) {
+        first[t] = (long long)ex->cand_cap * (merged ? ex->mrg_off[t] : t);
+        if (merged) most = std::max(most, ex->mrg_off[t + 1] - ex->mrg_off[t]);
+    }
+    if ((long long)ex->cand_cap * most > (1 << 24)) { ffgpu_set_error("%s: lists of up to %lld boxes are too long", what, (long long)ex->cand_cap * most); return -1; }
+    return ffgpu_launch_relabel(d_table, capacity, d_labels, k, merged ? ex->d_merged : ex->d_dets, merged ? ex->d_merged_full : ex->d_full, ex->cand_cap * most,
+                                first.data(), ntargets, *spec, d_out_records, d_out_lists, s);
+}
+
 // FFGPU_KEEP_ALL executors: one 64-bit hash per materialised layer over the layer's WHOLE batch tensor (every bit of every frame), computed on the
 // device behind the last forward; 0 for layers this executor does not materialise.  What the concurrency soak compares round after round
 // (tests/test_gpu_round5.py): 8 bytes per layer cross the bus instead of the activations.

@@ -693,4 +693,5 @@ extern "C" int ffgpu_pack_records(const void *d_records, int nslots, long slot_s
 #include "ffgpu_draw.inc"
 #include "ffgpu_crop.inc"
 #include "ffgpu_track.inc"
+#include "ffgpu_feature.inc"
 

@@ -638,6 +638,107 @@ int ffgpu_track_boxes_dev(const void *d_records, const void *d_lists, int list_s
 int ffgpu_exec_track(ffgpu_exec *ex, int which, const int *streams, int ntargets, const ffgpu_track_spec *spec, void *d_state, int nstreams,
                      void *d_ids, void *d_out_records, void *d_out_lists, void *stream);
 
+/* ---- the crops classified on the device: features, top-k labels, relabelling ---------------------------------------------------------------------
+ * The crops above fill a batch "for a second stage".  Where that stage is a detector its records come back with ffgpu_crops_to_source_dev.  Where it is
+ * a classifier or an embedding net -- a cfg WITHOUT a [yolo] layer -- its product is the tensor its last layer leaves.  What follows turns that tensor
+ * into one fp32 row per frame, a row into its k best labels, and each crop's best label into the class of the first stage's box the crop was cut from,
+ * where the data lie, in HBM; nothing crosses the bus and nothing synchronises.  No atomic is used anywhere: every result is a pure function of its
+ * inputs, the same bytes on every run (tests/features/featref.py restates the contract in numpy).
+ *
+ * Headless executors.  ffgpu_exec_create accepts a cfg without a [yolo] layer, with every flag combination, and every ffgpu_exec_forward_* form runs it;
+ * its records come out with count = ncand = nfull = overflow = 0 and ffgpu_exec_cand_capacity() is 1.
+ *
+ * Features.  Input: a tensor in the device layout "CNHW": plane (c, n) at ((c*N + n)*H*W), fp32.  Output: N rows of D fp32, frame-major: row n starts at
+ * d_out + n * out_stride (in floats), out_stride >= D, in the caller's memory; every element of every row is written, nothing between or behind the rows.
+ * `pool` selects the row:
+ *   FFGPU_FEAT_FLAT: D = C*H*W.  The frame's tensor in the reference's CHW order, i.e. what ffgpu_exec_read_layer returns, bit for bit, NaN payloads
+ *     and -0 included.
+ *   FFGPU_FEAT_MEAN: D = C.  The fp32 sum of the plane divided by (float)(H*W) with IEEE division.  The summation order is the implementation's; it is
+ *     a FIXED order: no atomic, independent of n and N (and of the tensor's alignment): a frame's row is the same bytes wherever the frame stands.
+ *   FFGPU_FEAT_MAX: D = C.  The plane's maximum.  Any NaN in the plane gives the quiet NaN 0x7fc00000; zeros compare as -0 < +0, so the result is
+ *     order-free and exact.
+ * `post` is applied to the row after pooling:
+ *   FFGPU_POST_NONE: the pooled row as it is.
+ *   FFGPU_POST_SOFTMAX: m = max_i x_i; e_i = expf(x_i - m), the accurate expf, not the fast intrinsic; out_i = e_i / sum(e).  A row with any NaN or
+ *     +Inf, or with only -Inf, is all NaN (0x7fc00000).  A -Inf element in any other row gives 0.
+ *   FFGPU_POST_L2: r = sqrtf(sum(x_i * x_i)); out_i = x_i / r.  With r == 0 the row is all zeros.  Non-finite inputs give what IEEE arithmetic of that
+ *     formula gives.
+ * At most two launches per call (one without a `post`). */
+#define FFGPU_FEAT_FLAT    0
+#define FFGPU_FEAT_MEAN    1
+#define FFGPU_FEAT_MAX     2
+#define FFGPU_POST_NONE    0
+#define FFGPU_POST_SOFTMAX 1
+#define FFGPU_POST_L2      2
+typedef struct {
+    int layer;                      /* -1: the tensor the net's last layer leaves; >= 0: that layer's output (FFGPU_KEEP_ALL executors only)   */
+    int pool, post;                 /* FFGPU_FEAT_*, FFGPU_POST_*                                                                              */
+    int reserved;                   /* 0                                                                                                       */
+} ffgpu_feature_spec;               /* 16 bytes: layer 0, pool 4, post 8, reserved 12                                                          */
+
+/* pure host code: D for a tensor of c x h x w per frame; 0 for sizes below 1, a pool outside its range, a plane (h * w) or a row (D) above 2^24 */
+int ffgpu_feature_dim(int c, int h, int w, int pool);
+/* pure host code: D of `spec` on this executor, or -1 with a message where ffgpu_exec_features would reject the spec */
+int ffgpu_exec_feature_dim(const ffgpu_exec *ex, const ffgpu_feature_spec *spec);
+
+/* The operator, on any device tensor with no executor.  Enqueued on `stream` without synchronising.  Rejected before anything is launched: NULL
+ * pointers, sizes below 1, D (or a plane) above 2^24, out_stride < D, an enum outside its range, an input or output that is not 4-byte aligned. */
+int ffgpu_features_dev(const float *d_in, int n, int c, int h, int w, int pool, int post, float *d_out, long out_stride, void *stream);
+
+/* On an executor: a post-pass like ffgpu_exec_crop_*, enqueued on `stream` (NULL = the executor's own; it must be the stream of the forward it follows)
+ * without synchronising.  The captured graph, the records, the full lists, the ring and the host mirror are untouched; the rows are the caller's (N =
+ * ffgpu_exec_batch(ex)).  layer == -1 means the tensor the net's last layer leaves, aliases resolved: a trailing dropout or one-source route gives its
+ * source's tensor; it is legal on every plan (the arena reuses a range only for a tensor first used behind the range's last use, and none is; nothing overwrites it after the forward).  layer >= 0 is
+ * legal only on FFGPU_KEEP_ALL executors, for a materialised layer, exactly as ffgpu_exec_read_layer decides.  A [yolo] layer (it has no tensor), a layer
+ * fused away and an alias of the net input are rejected with a message.  Works on FFGPU_SPLIT2 executors: each part writes its frames' rows, in the same
+ * launches.  Rejected like the operator, and: a NULL spec, reserved != 0, the wrong stream.  A rejected call leaves the executor usable. */
+int ffgpu_exec_features(ffgpu_exec *ex, const ffgpu_feature_spec *spec, float *d_out, long out_stride, void *stream);
+
+/* Top-k.  Input: n rows of d fp32, row r at d_in + r * in_stride (in_stride >= d).  Output: row r of d_out holds k entries ffgpu_label, 8 bytes each
+ * (row r at byte 8 k r): the row's elements in this total order: value descending, as fp32 values compare; then index ascending -- so +0 and -0 tie and
+ * the lower index wins; NaN is never selected.  Missing entries are { -1, 0.0f }: d < k, or too few elements that are no NaN.  The result is exact given
+ * the row.  One launch per call.  Rejected before anything is launched: NULL pointers, n < 1, d outside 1..2^24, in_stride < d, k outside
+ * 1..FFGPU_TOPK_MAX, an input or output that is not 4-byte aligned. */
+#define FFGPU_TOPK_MAX 16
+typedef struct { int index; float value; } ffgpu_label;      /* 8 bytes */
+int ffgpu_topk_dev(const float *d_in, int n, int d, long in_stride, int k, void *d_out, void *stream);
+
+/* Relabel.  Inputs: a crop table exactly as ffgpu_crop_boxes_* leaves it (d_table, capacity); its slots' top-k rows (d_labels: `capacity` rows of k
+ * ffgpu_label; only entry 0 of each row is used, k is passed for the row pitch); the first stage's records and its lists if any: d_records, d_lists,
+ * list_stride, the HOST array list_first and the clamps of the counts are the draw operators'.
+ * Outputs, laid out like the tracked record's: d_out_records[t], and list t at box t x S of d_out_lists (may be NULL); S = list_stride, or FFGPU_MAX_DET
+ * with NULL lists (the list is then the record's own box[0 .. count)).  They are copies of record t and of its list: counters and boxes unchanged, unused
+ * slots zero.  For every table entry n < taken whose label has index >= 0 and value >= min_value (a NaN value never), box entry.box of target
+ * entry.target gets type = type_base + index, and with FFGPU_RELABEL_LABEL_SCORE also score = value.  The patch lands in the list, and in the record's
+ * box[] where entry.box < count.  Boxes no entry refers to, and boxes of rejected labels, stay as they were; an entry whose target is outside
+ * 0 .. ntargets-1 or whose box lies behind its list is ignored.  Every output byte is written.  The outputs must not overlap the inputs.  A table entry
+ * names one box at most once, so no order decides anything.  One launch per 256 targets.  The relabelled record is a composition point like the tracked
+ * record: ffgpu_draw_*, ffgpu_crop_* and ffgpu_track_* consume it unchanged. */
+#define FFGPU_RELABEL_KEEP_SCORE  0
+#define FFGPU_RELABEL_LABEL_SCORE 1
+typedef struct {
+    float min_value;                /* a label is applied from this value on                                                                   */
+    int   type_base;                /* the new type is type_base + index                                                                       */
+    int   score_mode;               /* FFGPU_RELABEL_*                                                                                         */
+    int   reserved;                 /* 0                                                                                                       */
+} ffgpu_relabel_spec;               /* 16 bytes: min_value 0, type_base 4, score_mode 8, reserved 12                                           */
+
+/* The operator, on device records and lists with no executor.  list_first and spec are HOST memory and free again on return.  Enqueued on `stream`
+ * without synchronising.  Rejected before anything is launched, with the target's index in the message where there is one: NULL table, labels, records,
+ * spec or output records, capacity < 1, k outside 1..FFGPU_TOPK_MAX, ntargets < 1, a score_mode outside its range, reserved != 0, a table that is not
+ * 16-byte aligned, labels or outputs that are not 4-byte aligned, a bad list_stride, a negative list start, outputs that are the inputs. */
+int ffgpu_crops_relabel_dev(const void *d_table, int capacity, const void *d_labels, int k, const void *d_records, const void *d_lists, int list_stride,
+                            const int *list_first, int ntargets, const ffgpu_relabel_spec *spec, void *d_out_records, void *d_out_lists, void *stream);
+
+#define FFGPU_RELABEL_ENTRIES 0   /* entry n's record and full post-NMS list; ntargets == batch; S = ffgpu_exec_cand_capacity()                        */
+#define FFGPU_RELABEL_MERGED  1   /* picture g's merged record and list (last ffgpu_exec_merge_tiles); ntargets == its nimages; S as FFGPU_TRACK_MERGED */
+/* On the FIRST stage's executor: a post-pass like ffgpu_exec_track, enqueued on `stream` (NULL = the executor's own; it must be the stream of the forward
+ * or merge it follows) without synchronising.  The captured graph, the records, the full lists, the ring and the host mirror are untouched; table, labels
+ * and the relabelled records are the caller's.  Works on FFGPU_SPLIT2 executors.  Rejected like the operator, and: ntargets not as stated, a `which` that
+ * is neither, FFGPU_RELABEL_MERGED when no merge has run, the wrong stream.  A rejected call leaves the executor usable. */
+int ffgpu_exec_relabel(ffgpu_exec *ex, int which, const void *d_table, int capacity, const void *d_labels, int k, int ntargets,
+                       const ffgpu_relabel_spec *spec, void *d_out_records, void *d_out_lists, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
