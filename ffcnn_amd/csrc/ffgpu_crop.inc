@@ -258,26 +258,6 @@ int ffgpu_crop_spec_check(const char *what, const ffgpu_crop_spec *sp, CropPlan 
     return 0;
 }
 
-// the draw contract's checks of the descriptors (a NULL address: a skipped source), and no side of 2^31 - 1
-int ffgpu_crop_sources(const char *what, bool nv12, const void *targets, int n, std::vector<CropSrc> &out)
-{
-    for (int k = 0; k < n; k++) {
-        const int w = nv12 ? ((const ffgpu_nv12_frame *)targets)[k].w : ((const ffgpu_bgr_frame *)targets)[k].w;
-        const int h = nv12 ? ((const ffgpu_nv12_frame *)targets)[k].h : ((const ffgpu_bgr_frame *)targets)[k].h;
-        if (w == 0x7fffffff || h == 0x7fffffff) { ffgpu_set_error("%s: target %d: bad size %d x %d", what, k, w, h); return -1; }
-    }
-    std::vector<DrawTarget> tab;
-    if (nv12 ? ffgpu_draw_targets_nv12(what, (const ffgpu_nv12_frame *)targets, n, tab) : ffgpu_draw_targets_bgr(what, (const ffgpu_bgr_frame *)targets, n, tab)) return -1;
-    out.assign((size_t)n, CropSrc());
-    for (int k = 0; k < n; k++) {
-        CropSrc &c = out[k];
-        memset(&c, 0, sizeof c);
-        c.p0 = tab[k].p0; c.p1 = tab[k].p1; c.w = tab[k].w; c.h = tab[k].h; c.pitch = tab[k].pitch; c.pitch_uv = tab[k].pitch_uv;
-        c.fmt = nv12 ? 1 + ((const ffgpu_nv12_frame *)targets)[k].matrix : 0;
-    }
-    return 0;
-}
-
 int ffgpu_crop_buffers_check(const char *what, const void *d_out, const void *d_table, int capacity)
 {
     if (!d_out) { ffgpu_set_error("%s: NULL output", what); return -1; }
@@ -287,21 +267,21 @@ int ffgpu_crop_buffers_check(const char *what, const void *d_out, const void *d_
     return 0;
 }
 
-// sources[t] (its `first` set by the caller) takes its boxes from record t; every byte of the table and of `capacity` slots is written
-int ffgpu_launch_crop(bool nv12, const ffgpu_frame_dets *recs, const BBOX *lists, int stride, const std::vector<CropSrc> &sources, const CropPlan &pl,
-                      void *d_out, void *d_table, int capacity, hipStream_t s)
+// sources[t] takes its boxes from record t of `src`; every byte of the table and of `capacity` slots is written
+int ffgpu_launch_crop(bool nv12, const DetSource &src, const std::vector<CropSrc> &sources, const CropPlan &pl, void *d_out, void *d_table, int capacity, hipStream_t s)
 {
-    const int n = (int)sources.size();
+    const int n = (int)sources.size(), stride = src.stride;
     if ((long long)n * stride > 0x7fffffffLL) { ffgpu_set_error("crop_boxes: %d targets of up to %d boxes is too large", n, stride); return -1; }
     for (int t0 = 0; t0 < n; t0 += CROP_ARG_TARGETS) {
         const int nt = std::min(CROP_ARG_TARGETS, n - t0);
         CropSelArgs a;
         memset(&a, 0, sizeof a);
         memcpy(a.t, sources.data() + t0, sizeof(CropSrc) * (size_t)nt);
+        for (int i = 0; i < nt; i++) a.t[i].first = src.first[t0 + i];
         memcpy(a.classes, pl.classes, sizeof a.classes);
         a.nt = nt; a.rec0 = t0; a.first = t0 == 0; a.last = t0 + nt == n;
         a.out_w = pl.out_w; a.out_h = pl.out_h; a.per_target = pl.per_target; a.nclasses = pl.nclasses; a.num = pl.num; a.den = pl.den; a.min_score = pl.min_score;
-        hipLaunchKernelGGL(k_crop_select, dim3(1), dim3(CROP_ARG_TARGETS * CROP_GROUP), 0, s, a, recs, lists, stride, (int *)d_table, capacity);
+        hipLaunchKernelGGL(k_crop_select, dim3(1), dim3(CROP_ARG_TARGETS * CROP_GROUP), 0, s, a, src.recs, src.lists, stride, (int *)d_table, capacity);
         LAUNCH_OK("crop_select");
     }
     const unsigned gx = (unsigned)(((long)((pl.out_w + 3) / 4) * pl.out_h + 255) / 256);
@@ -326,57 +306,44 @@ int ffgpu_launch_crop(bool nv12, const ffgpu_frame_dets *recs, const BBOX *lists
     return 0;
 }
 
-static bool crop_no_device(const char *what)
+template <class Frame>
+static int crop_boxes_dev(const char *what, const void *d_records, const void *d_lists, int list_stride, const int *list_first,
+                          const Frame *sources, int ntargets, const ffgpu_crop_spec *spec, void *d_out, void *d_table, int capacity, void *stream)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) return false;
-    (void)hipGetLastError();
-    ffgpu_set_error("%s: no HIP device visible: libffcnn_hip has no CPU fallback", what);
-    return true;
-}
-
-static int crop_boxes_dev(bool nv12, const char *what, const void *d_records, const void *d_lists, int list_stride, const int *list_first,
-                          const void *targets, int ntargets, const ffgpu_crop_spec *spec, void *d_out, void *d_table, int capacity, void *stream)
-{
-    if (crop_no_device(what)) return -1;
-    if (!d_records) { ffgpu_set_error("%s: NULL records", what); return -1; }
-    if (!targets) { ffgpu_set_error("%s: NULL targets", what); return -1; }
+    if (ffgpu_no_device(what)) return -1;
+    if (!sources) { ffgpu_set_error("%s: NULL targets", what); return -1; }
     CropPlan pl;
     if (ffgpu_crop_spec_check(what, spec, pl) || ffgpu_crop_buffers_check(what, d_out, d_table, capacity)) return -1;
     if (ntargets < 1 || ntargets > (1 << 24)) { ffgpu_set_error("%s: %d targets (ntargets >= 1)", what, ntargets); return -1; }
-    const int stride = d_lists ? list_stride : FFGPU_MAX_DET;
-    if (stride < 1 || stride > (1 << 24)) { ffgpu_set_error("%s: bad list_stride %d", what, list_stride); return -1; }
+    DetSource src;
+    if (ffgpu_source_dev(what, d_records, d_lists, list_stride, list_first, ntargets, src)) return -1;
     std::vector<CropSrc> tab;
-    if (ffgpu_crop_sources(what, nv12, targets, ntargets, tab)) return -1;
-    for (int t = 0; t < ntargets; t++) {
-        if (d_lists && list_first && list_first[t] < 0) { ffgpu_set_error("%s: target %d: negative list start %d", what, t, list_first[t]); return -1; }
-        tab[t].first = d_lists ? (list_first ? (long long)list_first[t] : (long long)t * stride) : 0;
-    }
-    return ffgpu_launch_crop(nv12, (const ffgpu_frame_dets *)d_records, (const BBOX *)d_lists, stride, tab, pl, d_out, d_table, capacity, (hipStream_t)stream);
+    if (ffgpu_frame_table(what, FRAME_DRAW, sources, ntargets, tab)) return -1;
+    return ffgpu_launch_crop(std::is_same<Frame, ffgpu_nv12_frame>::value, src, tab, pl, d_out, d_table, capacity, (hipStream_t)stream);
 }
 
 extern "C" int ffgpu_crop_boxes_bgr_dev(const void *d_records, const void *d_lists, int list_stride, const int *list_first, const ffgpu_bgr_frame *sources,
                                         int ntargets, const ffgpu_crop_spec *spec, void *d_out, void *d_table, int capacity, void *stream)
 {
-    return crop_boxes_dev(false, "crop_boxes_bgr_dev", d_records, d_lists, list_stride, list_first, sources, ntargets, spec, d_out, d_table, capacity, stream);
+    return crop_boxes_dev("crop_boxes_bgr_dev", d_records, d_lists, list_stride, list_first, sources, ntargets, spec, d_out, d_table, capacity, stream);
 }
 
 extern "C" int ffgpu_crop_boxes_nv12_dev(const void *d_records, const void *d_lists, int list_stride, const int *list_first, const ffgpu_nv12_frame *sources,
                                          int ntargets, const ffgpu_crop_spec *spec, void *d_out, void *d_table, int capacity, void *stream)
 {
-    return crop_boxes_dev(true, "crop_boxes_nv12_dev", d_records, d_lists, list_stride, list_first, sources, ntargets, spec, d_out, d_table, capacity, stream);
+    return crop_boxes_dev("crop_boxes_nv12_dev", d_records, d_lists, list_stride, list_first, sources, ntargets, spec, d_out, d_table, capacity, stream);
 }
 
 extern "C" int ffgpu_crops_to_source_dev(const void *d_table, int capacity, const void *d_records, const void *d_lists, int list_stride,
                                          void *d_out_records, void *d_out_lists, void *stream)
 {
     const char *const what = "crops_to_source_dev";
-    if (crop_no_device(what)) return -1;
+    if (ffgpu_no_device(what)) return -1;
     if (!d_table) { ffgpu_set_error("%s: NULL table", what); return -1; }
     if (!d_records || !d_out_records) { ffgpu_set_error("%s: NULL records", what); return -1; }
     if (capacity < 1 || capacity > (1 << 24)) { ffgpu_set_error("%s: capacity %d is outside 1..2^24", what, capacity); return -1; }
     if (reinterpret_cast<uintptr_t>(d_table) & 15) { ffgpu_set_error("%s: the table must be 16-byte aligned", what); return -1; }
-    if (d_lists && (list_stride < 1 || list_stride > (1 << 24))) { ffgpu_set_error("%s: bad list_stride %d", what, list_stride); return -1; }
+    if (ffgpu_list_stride(what, d_lists, list_stride) < 0) return -1;
     hipLaunchKernelGGL(k_crops_to_source, dim3((unsigned)capacity), dim3(FFGPU_MAX_DET), 0, (hipStream_t)stream, (const int *)d_table, capacity,
                        (const ffgpu_frame_dets *)d_records, (const BBOX *)d_lists, d_lists ? list_stride : 0, (ffgpu_frame_dets *)d_out_records, (BBOX *)d_out_lists);
     LAUNCH_OK("crops_to_source");

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <vector>
 #include "ffgpu_internal.h"
+#include "ffgpu_args.hpp"
 
 #define FFGPU_CHECK(expr)                                                                   \
     do {                                                                                    \
@@ -98,19 +99,7 @@ size_t ffgpu_pw_pack_floats(const ConvDesc &d);
 void   ffgpu_conv_plan(ConvDesc &d);                   // freezes kernel / nsplit / x3_mt for this layer NOW (the tuning environment is read once, here)
 int    ffgpu_pw_pack(const ConvDesc &d, float *pk, hipStream_t s);
 
-// One frame of ffgpu_exec_forward_bgr_frames_dev / ffgpu_exec_forward_nv12_frames_dev as the kernels read it: the caller's descriptor plus
-// net_input's letterbox arithmetic (ffcnn.c:267-273), computed once on the host.  The executor keeps a device table of `batch` of them.
-// fmt tells the two kinds of table apart (a BGR table never compares equal to an NV12 one: the executor's "table already sent" shortcut).
-struct FrameDesc {
-    const unsigned char *bgr;     // row 0 of the frame (any byte alignment); NV12: row 0 of the Y plane
-    int w, h, pitch;              // pitch: bytes from one row to the next (>= 3 w; NV12: of the Y plane, >= w)
-    int sw, sh, s1, s2;           // the frame fills the top-left sw x sh of the net's plane; source pixel of (x, y) = (x s1 / s2, y s1 / s2)
-    int fmt;                      // 0: u8 BGR; 1 + FFGPU_YUV_*: NV12 converted with that matrix
-    const unsigned char *uv;      // NV12: row 0 of the interleaved U V plane (2-byte aligned, never NULL here); BGR: NULL
-    int pitch_uv;                 // NV12: bytes from one U V row to the next (even)
-    int pad_;
-};
-static_assert(sizeof(FrameDesc) == 56, "FrameDesc: 64 of them travel by value as k_set_frames' argument");
+// the forward's frame table (FrameDesc: ffgpu_args.hpp)
 // NV12 -> BGR in 32-bit integers (include/ffcnn_hip.h): { yoff, cy, crv, cgu, cgv, cbu } per FFGPU_YUV_* matrix
 #define FFGPU_YUV_MATRICES { { 16, 298, 409, 100, 208, 516 }, { 0, 256, 359, 88, 183, 454 }, { 16, 298, 459, 55, 136, 541 }, { 0, 256, 403, 48, 120, 475 } }
 int  ffgpu_launch_set_frames(FrameDesc *d_tab, const FrameDesc *h_desc, int n, hipStream_t s);
@@ -137,6 +126,9 @@ struct ExecParams {
 };
 int  ffgpu_launch_set_params(ExecParams *d_prm, const ExecParams &v, hipStream_t s);
 bool ffgpu_conv_supports_ind(const ConvDesc &d);    // the kernel ffgpu_launch_conv would pick reads ConvDesc::in_ind
+
+// true, with "<what>: no HIP device visible ..." as the error: what every entry point that needs no executor asks first (ffgpu_exec.hip)
+bool ffgpu_no_device(const char *what);
 
 // kernels.hip
 int         ffgpu_launch_conv(const ConvDesc &d, int variant, hipStream_t s);
@@ -178,52 +170,30 @@ int    ffgpu_launch_set_ints(int *d_dst, const int *h_src, int n, hipStream_t s)
 int    ffgpu_launch_merge_tiles(const int *d_tab, const std::vector<int> &tab, const ffgpu_frame_dets *recs, const BBOX *lists, int stride,
                                 float thresh, int use_min, ffgpu_frame_dets *out_recs, BBOX *out_lists, void *scratch, hipStream_t s);
 
-// the detections drawn into the frames (ffgpu_draw.inc).  One target as the kernel reads it: the caller's descriptor with its defaults resolved, and
-// the first box of its list (in boxes from the lists' base; unused when the records' own boxes are drawn).  p0 == NULL: a skipped target.
-struct DrawTarget {
-    unsigned char *p0;            // row 0 of the BGR pixels / of the Y plane
-    unsigned char *p1;            // NV12: row 0 of the interleaved U V plane (2-byte aligned); BGR: NULL
-    long long first;
-    int w, h, pitch, pitch_uv;
-};
+// the detections drawn into the frames (ffgpu_draw.inc; DrawTarget: ffgpu_args.hpp).  targets[t] draws record t of `src`
 int ffgpu_draw_style_check(const char *what, const ffgpu_draw_style *st, unsigned pal[256], int *npal);
-int ffgpu_draw_targets_bgr(const char *what, const ffgpu_bgr_frame *f, int n, std::vector<DrawTarget> &out);
-int ffgpu_draw_targets_nv12(const char *what, const ffgpu_nv12_frame *f, int n, std::vector<DrawTarget> &out);
-int ffgpu_launch_draw(bool nv12, const ffgpu_frame_dets *recs, const BBOX *lists, int stride, const std::vector<DrawTarget> &targets,
-                      const unsigned pal[256], int npal, int thickness, hipStream_t s);
+int ffgpu_launch_draw(bool nv12, const DetSource &src, const std::vector<DrawTarget> &targets, const unsigned pal[256], int npal, int thickness, hipStream_t s);
 
-// the detections cut out of the frames (ffgpu_crop.inc).  One source as the kernels read it: a DrawTarget that is only read, with the NV12 matrix
-// (fmt as FrameDesc::fmt).  CropPlan: the caller's spec, checked, with the class filter's bytes copied.
-struct CropSrc {
-    const unsigned char *p0;      // row 0 of the BGR pixels / of the Y plane; NULL: a skipped source
-    const unsigned char *p1;      // NV12: row 0 of the interleaved U V plane (2-byte aligned); BGR: NULL
-    long long first;
-    int w, h, pitch, pitch_uv;
-    int fmt, pad_;
-};
+// the detections cut out of the frames (ffgpu_crop.inc; CropSrc: ffgpu_args.hpp).  CropPlan: the caller's spec, checked, with the class filter's bytes copied.
 struct CropPlan {
     int   out_w, out_h, form, per_target, nclasses, num, den;
     float min_score, mean[3], norm[3];
     unsigned char classes[256];
 };
 int ffgpu_crop_spec_check(const char *what, const ffgpu_crop_spec *sp, CropPlan &pl);
-int ffgpu_crop_sources(const char *what, bool nv12, const void *targets, int n, std::vector<CropSrc> &out);
 int ffgpu_crop_buffers_check(const char *what, const void *d_out, const void *d_table, int capacity);
-int ffgpu_launch_crop(bool nv12, const ffgpu_frame_dets *recs, const BBOX *lists, int stride, const std::vector<CropSrc> &sources, const CropPlan &pl,
-                      void *d_out, void *d_table, int capacity, hipStream_t s);
+int ffgpu_launch_crop(bool nv12, const DetSource &src, const std::vector<CropSrc> &sources, const CropPlan &pl, void *d_out, void *d_table, int capacity, hipStream_t s);
 
-// the detections tracked across a stream's frames (ffgpu_track.inc): the checks both entry points share, and the launches (record t's list starts
-// at box first[t] of `lists`)
+// the detections tracked across a stream's frames (ffgpu_track.inc): the checks both entry points share, and the launches
 int ffgpu_track_args_check(const char *what, const int *streams, int ntargets, const ffgpu_track_spec *spec, const void *d_state, int nstreams,
                            const void *d_ids, const void *d_out_records, const void *d_out_lists);
-int ffgpu_launch_track(const ffgpu_frame_dets *recs, const BBOX *lists, int stride, const long long *first, const int *streams, int ntargets,
-                       const ffgpu_track_spec &spec, void *d_state, void *d_ids, void *d_out_records, void *d_out_lists, hipStream_t s);
+int ffgpu_launch_track(const DetSource &src, const int *streams, int ntargets, const ffgpu_track_spec &spec, void *d_state, void *d_ids, void *d_out_records, void *d_out_lists, hipStream_t s);
 
 // the crops classified (ffgpu_feature.inc): the checks both entry points share, and the launches.  Features: frame n of the tensor is frame n % pn of
-// parts[n / pn], a CNHW tensor of pn frames (a split executor has one part per chain; at most 8).  Relabel: record t's list starts at box first[t].
+// parts[n / pn], a CNHW tensor of pn frames (a split executor has one part per chain; at most 8).
 int ffgpu_feature_args_check(const char *what, int n, int c, int h, int w, int pool, int post, const void *d_out, long out_stride);
 int ffgpu_launch_features(const float *const *parts, int nparts, int pn, int c, int h, int w, int pool, int post, float *d_out, long out_stride, hipStream_t s);
 int ffgpu_relabel_args_check(const char *what, const void *d_table, int capacity, const void *d_labels, int k, int ntargets, const ffgpu_relabel_spec *spec,
                              const void *d_out_records);
-int ffgpu_launch_relabel(const void *d_table, int capacity, const void *d_labels, int k, const ffgpu_frame_dets *recs, const BBOX *lists, int stride,
-                         const long long *first, int ntargets, const ffgpu_relabel_spec &spec, void *d_out_records, void *d_out_lists, hipStream_t s);
+int ffgpu_launch_relabel(const void *d_table, int capacity, const void *d_labels, int k, const DetSource &src, int ntargets, const ffgpu_relabel_spec &spec,
+                         void *d_out_records, void *d_out_lists, hipStream_t s);

@@ -121,7 +121,7 @@ __global__ void __launch_bounds__(256) k_draw_boxes(DrawArgs a, const ffgpu_fram
     }
 }
 
-// ---- host side: the caller's style and descriptors checked once for the operators and the executor forms; -1 with the target's index in the message
+// ---- host side: the caller's style checked once for the operators and the executor forms (the descriptors: ffgpu_frame_table, role FRAME_DRAW)
 int ffgpu_draw_style_check(const char *what, const ffgpu_draw_style *st, unsigned pal[256], int *npal)
 {
     if (!st) { ffgpu_set_error("%s: NULL style", what); return -1; }
@@ -137,46 +137,8 @@ int ffgpu_draw_style_check(const char *what, const ffgpu_draw_style *st, unsigne
     return 0;
 }
 
-// the checks of ffgpu_exec_forward_bgr_frames_dev, but a NULL address is a skipped target
-int ffgpu_draw_targets_bgr(const char *what, const ffgpu_bgr_frame *f, int n, std::vector<DrawTarget> &out)
-{
-    out.assign((size_t)n, DrawTarget());
-    for (int k = 0; k < n; k++, f++) {
-        if (f->w <= 0 || f->h <= 0 || 3L * f->w > 0x7fffffffL || f->h > 0x3fffffff) { ffgpu_set_error("%s: target %d: bad size %d x %d", what, k, f->w, f->h); return -1; }
-        if (f->reserved != 0) { ffgpu_set_error("%s: target %d: reserved must be 0", what, k); return -1; }
-        const long pitch = f->pitch ? (long)f->pitch : ((3L * f->w + 3) & ~3L);
-        if (pitch < 3L * f->w || pitch > 0x7fffffffL) { ffgpu_set_error("%s: target %d: pitch %d is below 3 w = %ld", what, k, f->pitch, 3L * f->w); return -1; }
-        DrawTarget &d = out[k];
-        memset(&d, 0, sizeof d);
-        d.p0 = const_cast<unsigned char *>(f->bgr); d.w = f->w; d.h = f->h; d.pitch = (int)pitch;
-    }
-    return 0;
-}
-
-// the checks of ffgpu_exec_forward_nv12_frames_dev, but a NULL y is a skipped target
-int ffgpu_draw_targets_nv12(const char *what, const ffgpu_nv12_frame *f, int n, std::vector<DrawTarget> &out)
-{
-    out.assign((size_t)n, DrawTarget());
-    for (int k = 0; k < n; k++, f++) {
-        if (f->w <= 0 || f->h <= 0 || f->w > 0x3fffffff || f->h > 0x3fffffff) { ffgpu_set_error("%s: target %d: bad size %d x %d", what, k, f->w, f->h); return -1; }
-        if (f->reserved != 0) { ffgpu_set_error("%s: target %d: reserved must be 0", what, k); return -1; }
-        if (f->matrix < 0 || f->matrix > 3) { ffgpu_set_error("%s: target %d: matrix %d is none of FFGPU_YUV_* (0..3)", what, k, f->matrix); return -1; }
-        const int pitch_y = f->pitch_y ? f->pitch_y : f->w, min_uv = 2 * ((f->w + 1) / 2), pitch_uv = f->pitch_uv ? f->pitch_uv : min_uv;
-        if (pitch_y < f->w) { ffgpu_set_error("%s: target %d: pitch_y %d is below w = %d", what, k, f->pitch_y, f->w); return -1; }
-        if (pitch_uv < min_uv || (pitch_uv & 1)) { ffgpu_set_error("%s: target %d: pitch_uv %d is odd or below 2 ((w + 1) / 2) = %d", what, k, f->pitch_uv, min_uv); return -1; }
-        DrawTarget &d = out[k];
-        memset(&d, 0, sizeof d);
-        if (!f->y) continue;
-        const unsigned char *uv = f->uv ? f->uv : f->y + (size_t)pitch_y * f->h;
-        if (reinterpret_cast<uintptr_t>(uv) & 1) { ffgpu_set_error("%s: target %d: the uv plane's address %p is odd (U V pairs are written as aligned 16-bit values)", what, k, (const void *)uv); return -1; }
-        d.p0 = const_cast<unsigned char *>(f->y); d.p1 = const_cast<unsigned char *>(uv); d.w = f->w; d.h = f->h; d.pitch = pitch_y; d.pitch_uv = pitch_uv;
-    }
-    return 0;
-}
-
-// targets[t] (its `first` set by the caller) draws record t; DRAW_ARG_TARGETS targets per launch
-int ffgpu_launch_draw(bool nv12, const ffgpu_frame_dets *recs, const BBOX *lists, int stride, const std::vector<DrawTarget> &targets,
-                      const unsigned pal[256], int npal, int thickness, hipStream_t s)
+// targets[t] draws record t of `src`; DRAW_ARG_TARGETS targets per launch
+int ffgpu_launch_draw(bool nv12, const DetSource &src, const std::vector<DrawTarget> &targets, const unsigned pal[256], int npal, int thickness, hipStream_t s)
 {
     const int n = (int)targets.size();
     for (int t0 = 0; t0 < n; t0 += DRAW_ARG_TARGETS) {
@@ -184,51 +146,42 @@ int ffgpu_launch_draw(bool nv12, const ffgpu_frame_dets *recs, const BBOX *lists
         DrawArgs a;
         memset(&a, 0, sizeof a);
         memcpy(a.t, targets.data() + t0, sizeof(DrawTarget) * (size_t)nt);
+        for (int i = 0; i < nt; i++) a.t[i].first = src.first[t0 + i];
         memcpy(a.pal, pal, sizeof a.pal);
         a.npal = npal; a.thickness = thickness; a.rec0 = t0;
-        const dim3 grid((unsigned)std::min(stride, DRAW_GROUPS), (unsigned)nt);
-        if (nv12) hipLaunchKernelGGL(k_draw_boxes<true>, grid, dim3(256), 0, s, a, recs, lists, stride);
-        else      hipLaunchKernelGGL(k_draw_boxes<false>, grid, dim3(256), 0, s, a, recs, lists, stride);
+        const dim3 grid((unsigned)std::min(src.stride, DRAW_GROUPS), (unsigned)nt);
+        if (nv12) hipLaunchKernelGGL(k_draw_boxes<true>, grid, dim3(256), 0, s, a, src.recs, src.lists, src.stride);
+        else      hipLaunchKernelGGL(k_draw_boxes<false>, grid, dim3(256), 0, s, a, src.recs, src.lists, src.stride);
         LAUNCH_OK("draw_boxes");
     }
     return 0;
 }
 
-static int draw_boxes_dev(bool nv12, const char *what, const void *d_records, const void *d_lists, int list_stride, const int *list_first,
-                          const void *targets, int ntargets, const ffgpu_draw_style *style, void *stream)
+template <class Frame>
+static int draw_boxes_dev(const char *what, const void *d_records, const void *d_lists, int list_stride, const int *list_first,
+                          const Frame *targets, int ntargets, const ffgpu_draw_style *style, void *stream)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        (void)hipGetLastError();
-        ffgpu_set_error("%s: no HIP device visible: libffcnn_hip has no CPU fallback", what);
-        return -1;
-    }
-    if (!d_records) { ffgpu_set_error("%s: NULL records", what); return -1; }
+    if (ffgpu_no_device(what)) return -1;
     if (!targets) { ffgpu_set_error("%s: NULL targets", what); return -1; }
     unsigned pal[256];
     int npal = 0;
     if (ffgpu_draw_style_check(what, style, pal, &npal)) return -1;
     if (ntargets < 1 || ntargets > (1 << 24)) { ffgpu_set_error("%s: %d targets (ntargets >= 1)", what, ntargets); return -1; }
-    const int stride = d_lists ? list_stride : FFGPU_MAX_DET;
-    if (stride < 1 || stride > (1 << 24)) { ffgpu_set_error("%s: bad list_stride %d", what, list_stride); return -1; }
+    DetSource src;
+    if (ffgpu_source_dev(what, d_records, d_lists, list_stride, list_first, ntargets, src)) return -1;
     std::vector<DrawTarget> tab;
-    if (nv12 ? ffgpu_draw_targets_nv12(what, (const ffgpu_nv12_frame *)targets, ntargets, tab)
-             : ffgpu_draw_targets_bgr(what, (const ffgpu_bgr_frame *)targets, ntargets, tab)) return -1;
-    for (int t = 0; t < ntargets; t++) {
-        if (d_lists && list_first && list_first[t] < 0) { ffgpu_set_error("%s: target %d: negative list start %d", what, t, list_first[t]); return -1; }
-        tab[t].first = d_lists ? (list_first ? (long long)list_first[t] : (long long)t * stride) : 0;
-    }
-    return ffgpu_launch_draw(nv12, (const ffgpu_frame_dets *)d_records, (const BBOX *)d_lists, stride, tab, pal, npal, style->thickness, (hipStream_t)stream);
+    if (ffgpu_frame_table(what, FRAME_DRAW, targets, ntargets, tab)) return -1;
+    return ffgpu_launch_draw(std::is_same<Frame, ffgpu_nv12_frame>::value, src, tab, pal, npal, style->thickness, (hipStream_t)stream);
 }
 
 extern "C" int ffgpu_draw_boxes_bgr_dev(const void *d_records, const void *d_lists, int list_stride, const int *list_first,
                                         const ffgpu_bgr_frame *targets, int ntargets, const ffgpu_draw_style *style, void *stream)
 {
-    return draw_boxes_dev(false, "draw_boxes_bgr_dev", d_records, d_lists, list_stride, list_first, targets, ntargets, style, stream);
+    return draw_boxes_dev("draw_boxes_bgr_dev", d_records, d_lists, list_stride, list_first, targets, ntargets, style, stream);
 }
 
 extern "C" int ffgpu_draw_boxes_nv12_dev(const void *d_records, const void *d_lists, int list_stride, const int *list_first,
                                          const ffgpu_nv12_frame *targets, int ntargets, const ffgpu_draw_style *style, void *stream)
 {
-    return draw_boxes_dev(true, "draw_boxes_nv12_dev", d_records, d_lists, list_stride, list_first, targets, ntargets, style, stream);
+    return draw_boxes_dev("draw_boxes_nv12_dev", d_records, d_lists, list_stride, list_first, targets, ntargets, style, stream);
 }

@@ -22,6 +22,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "ffgpu_dev.hpp"
@@ -55,6 +56,13 @@ extern "C" int ffgpu_device_count(void)
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return 0; }
     return n;
+}
+
+bool ffgpu_no_device(const char *what)
+{
+    if (ffgpu_device_count() > 0) return false;
+    ffgpu_set_error("%s: no HIP device visible: libffcnn_hip has no CPU fallback", what);
+    return true;
 }
 
 extern "C" int ffgpu_set_device(int ordinal)
@@ -927,6 +935,13 @@ static bool alive(const ffgpu_exec *ex, const char *what)
     return true;
 }
 
+// "is there an executor", for the entry points that can be the first call of a process: without one, the missing device is the better message
+static bool exec_ok(const ffgpu_exec *ex, const char *what)
+{
+    if (!ex && ffgpu_no_device(what)) return false;
+    return alive(ex, what);
+}
+
 static ffgpu_netdev *netdev_of(NET *net)
 {
     if (!net) { ffgpu_set_error("NULL net"); return nullptr; }
@@ -1214,13 +1229,7 @@ extern "C" int ffgpu_exec_forward_bgr_dev(ffgpu_exec *ex, const unsigned char *d
 // executor's own scale stays as it was: k_nms takes each frame's s1 / s2 from the table.
 static bool frames_args_ok(ffgpu_exec *ex, const char *what, const void *frames, int nframes, const float *mean, const float *norm)
 {
-    int ndev = 0;
-    if (!ex && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)) {
-        (void)hipGetLastError();
-        ffgpu_set_error("%s: no HIP device visible: libffcnn_hip has no CPU fallback", what);
-        return false;
-    }
-    if (!alive(ex, what)) return false;
+    if (!exec_ok(ex, what)) return false;
     if (!frames || !mean || !norm) { ffgpu_set_error("%s: NULL argument", what); return false; }
     if (nframes != ex->N) { ffgpu_set_error("%s: %d frames for an executor of batch %d", what, nframes, ex->N); return false; }
     if (ex->in_c != 3) { ffgpu_set_error("%s: the net's input has %d channels, not 3", what, ex->in_c); return false; }
@@ -1244,49 +1253,28 @@ static int forward_frames(ffgpu_exec *ex, const std::vector<FrameDesc> &tab, Inp
     return forward_on(ex, in, s);
 }
 
+// the caller's descriptors checked (role FRAME_FORWARD) into the table, each with its letterbox
+template <class Frame>
+static int forward_frames_dev(ffgpu_exec *ex, const char *what, InputForm form, const Frame *frames, int nframes, const float mean[3], const float norm[3], void *stream)
+{
+    if (!frames_args_ok(ex, what, frames, nframes, mean, norm)) return -1;
+    std::vector<FrameDesc> tab;
+    if (ffgpu_frame_table(what, FRAME_FORWARD, frames, nframes, tab)) return -1;
+    for (FrameDesc &d : tab) letterbox(d.w, d.h, ex->in_w, ex->in_h, &d.sw, &d.sh, &d.s1, &d.s2);
+    return forward_frames(ex, tab, form, mean, norm, stream ? (hipStream_t)stream : ex->own_stream);
+}
+
 extern "C" int ffgpu_exec_forward_bgr_frames_dev(ffgpu_exec *ex, const ffgpu_bgr_frame *frames, int nframes,
                                                  const float mean[3], const float norm[3], void *stream)
 {
-    if (!frames_args_ok(ex, "forward_bgr_frames_dev", frames, nframes, mean, norm)) return -1;
-    std::vector<FrameDesc> tab((size_t)nframes);
-    for (int n = 0; n < nframes; n++) {
-        const ffgpu_bgr_frame &f = frames[n];
-        if (!f.bgr) { ffgpu_set_error("forward_bgr_frames_dev: frame %d: NULL bgr", n); return -1; }
-        if (f.w <= 0 || f.h <= 0 || 3L * f.w > 0x7fffffffL) { ffgpu_set_error("forward_bgr_frames_dev: frame %d: bad size %d x %d", n, f.w, f.h); return -1; }
-        if (f.reserved != 0) { ffgpu_set_error("forward_bgr_frames_dev: frame %d: reserved must be 0", n); return -1; }
-        const long pitch = f.pitch ? (long)f.pitch : ((3L * f.w + 3) & ~3L);
-        if (pitch < 3L * f.w || pitch > 0x7fffffffL) { ffgpu_set_error("forward_bgr_frames_dev: frame %d: pitch %d is below 3 w = %ld", n, f.pitch, 3L * f.w); return -1; }
-        FrameDesc &d = tab[n];
-        memset(&d, 0, sizeof d);
-        d.bgr = f.bgr; d.w = f.w; d.h = f.h; d.pitch = (int)pitch;
-        letterbox(d.w, d.h, ex->in_w, ex->in_h, &d.sw, &d.sh, &d.s1, &d.s2);
-    }
-    return forward_frames(ex, tab, IN_BGR_FRAMES, mean, norm, stream ? (hipStream_t)stream : ex->own_stream);
+    return forward_frames_dev(ex, "forward_bgr_frames_dev", IN_BGR_FRAMES, frames, nframes, mean, norm, stream);
 }
 
 // NV12 frames: the same table with the second plane, its pitch and the matrix (FrameDesc::fmt != 0); the pixel is converted where it is sampled
 extern "C" int ffgpu_exec_forward_nv12_frames_dev(ffgpu_exec *ex, const ffgpu_nv12_frame *frames, int nframes,
                                                   const float mean[3], const float norm[3], void *stream)
 {
-    if (!frames_args_ok(ex, "forward_nv12_frames_dev", frames, nframes, mean, norm)) return -1;
-    std::vector<FrameDesc> tab((size_t)nframes);
-    for (int n = 0; n < nframes; n++) {
-        const ffgpu_nv12_frame &f = frames[n];
-        if (!f.y) { ffgpu_set_error("forward_nv12_frames_dev: frame %d: NULL y", n); return -1; }
-        if (f.w <= 0 || f.h <= 0 || f.w > 0x3fffffff || f.h > 0x3fffffff) { ffgpu_set_error("forward_nv12_frames_dev: frame %d: bad size %d x %d", n, f.w, f.h); return -1; }
-        if (f.reserved != 0) { ffgpu_set_error("forward_nv12_frames_dev: frame %d: reserved must be 0", n); return -1; }
-        if (f.matrix < 0 || f.matrix > 3) { ffgpu_set_error("forward_nv12_frames_dev: frame %d: matrix %d is none of FFGPU_YUV_* (0..3)", n, f.matrix); return -1; }
-        const int pitch_y = f.pitch_y ? f.pitch_y : f.w, min_uv = 2 * ((f.w + 1) / 2), pitch_uv = f.pitch_uv ? f.pitch_uv : min_uv;
-        if (pitch_y < f.w) { ffgpu_set_error("forward_nv12_frames_dev: frame %d: pitch_y %d is below w = %d", n, f.pitch_y, f.w); return -1; }
-        if (pitch_uv < min_uv || (pitch_uv & 1)) { ffgpu_set_error("forward_nv12_frames_dev: frame %d: pitch_uv %d is odd or below 2 ((w + 1) / 2) = %d", n, f.pitch_uv, min_uv); return -1; }
-        const unsigned char *uv = f.uv ? f.uv : f.y + (size_t)pitch_y * f.h;
-        if (reinterpret_cast<uintptr_t>(uv) & 1) { ffgpu_set_error("forward_nv12_frames_dev: frame %d: the uv plane's address %p is odd (U V pairs are read as aligned 16-bit values)", n, (const void *)uv); return -1; }
-        FrameDesc &d = tab[n];
-        memset(&d, 0, sizeof d);
-        d.bgr = f.y; d.uv = uv; d.w = f.w; d.h = f.h; d.pitch = pitch_y; d.pitch_uv = pitch_uv; d.fmt = 1 + f.matrix;
-        letterbox(d.w, d.h, ex->in_w, ex->in_h, &d.sw, &d.sh, &d.s1, &d.s2);
-    }
-    return forward_frames(ex, tab, IN_NV12_FRAMES, mean, norm, stream ? (hipStream_t)stream : ex->own_stream);
+    return forward_frames_dev(ex, "forward_nv12_frames_dev", IN_NV12_FRAMES, frames, nframes, mean, norm, stream);
 }
 
 extern "C" int ffgpu_exec_dets_dev(ffgpu_exec *ex, void **dev_ptr, size_t *bytes)
@@ -1360,13 +1348,7 @@ extern "C" int ffgpu_exec_read_boxes(ffgpu_exec *ex, int frame, BBOX *host_out, 
 // buffers of its own.  The table is uploaded in front of the merge unless the device table holds (or will hold, on this stream) these values already.
 extern "C" int ffgpu_exec_merge_tiles(ffgpu_exec *ex, const ffgpu_tile *tiles, int ntiles, int nimages, void *stream)
 {
-    int ndev = 0;
-    if (!ex && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)) {
-        (void)hipGetLastError();
-        ffgpu_set_error("merge_tiles: no HIP device visible: libffcnn_hip has no CPU fallback");
-        return -1;
-    }
-    if (!alive(ex, "merge_tiles")) return -1;
+    if (!exec_ok(ex, "merge_tiles")) return -1;
     if (!tiles) { ffgpu_set_error("merge_tiles: NULL tile table"); return -1; }
     if (ntiles != ex->N) { ffgpu_set_error("merge_tiles: %d tiles for an executor of batch %d", ntiles, ex->N); return -1; }
     const hipStream_t s = stream ? (hipStream_t)stream : ex->own_stream;
@@ -1431,104 +1413,79 @@ extern "C" int ffgpu_exec_read_merged_boxes(ffgpu_exec *ex, int image, BBOX *hos
     return nfull;
 }
 
+// -------------------------------------------------------------------------- post-passes that read the boxes: draw, crop, track, relabel
+// What the four post-passes that read boxes share: `which` as the executor's records and lists (ffgpu_source_exec) and the stream, which must be the
+// one the forward or merge ran on.  src.stride is the caller's to derive from src.longest.
+static int exec_source(ffgpu_exec *ex, const char *what, const char *family, const char *noun, int which, int ntargets, void *stream, DetSource &src, hipStream_t *s)
+{
+    if (ffgpu_source_exec(what, family, which, ntargets, ex->N, ex->cand_cap, ex->d_merged ? &ex->mrg_off : nullptr, src)) return -1;
+    *s = stream ? (hipStream_t)stream : ex->own_stream;
+    if (*s != ex->last_stream) { ffgpu_set_error("%s: the %s must be enqueued on the stream of the forward or merge it follows", what, noun); return -1; }
+    src.recs = which ? ex->d_merged : ex->d_dets;
+    src.lists = which ? ex->d_merged_full : ex->d_full;
+    return 0;
+}
+
 // -------------------------------------------------------------------------- the detections drawn into the frames (include/ffcnn_hip.h; kernel: ffgpu_draw.inc)
 // A post-pass like the merge, on the stream of the forward or merge it follows: reads the records and full lists (per entry, or the merged ones),
 // writes the caller's frames and nothing of the executor's.
-static int exec_draw(ffgpu_exec *ex, bool nv12, const char *what, int which, const void *targets, int ntargets, const ffgpu_draw_style *style, void *stream)
+template <class Frame>
+static int exec_draw(ffgpu_exec *ex, const char *what, int which, const Frame *targets, int ntargets, const ffgpu_draw_style *style, void *stream)
 {
-    int ndev = 0;
-    if (!ex && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)) {
-        (void)hipGetLastError();
-        ffgpu_set_error("%s: no HIP device visible: libffcnn_hip has no CPU fallback", what);
-        return -1;
-    }
-    if (!alive(ex, what)) return -1;
+    if (!exec_ok(ex, what)) return -1;
     if (!targets) { ffgpu_set_error("%s: NULL targets", what); return -1; }
     unsigned pal[256];
     int npal = 0;
     if (ffgpu_draw_style_check(what, style, pal, &npal)) return -1;
-    if (which != FFGPU_DRAW_ENTRIES && which != FFGPU_DRAW_MERGED) { ffgpu_set_error("%s: which = %d is neither FFGPU_DRAW_ENTRIES nor FFGPU_DRAW_MERGED", what, which); return -1; }
-    const bool merged = which == FFGPU_DRAW_MERGED;
-    if (merged && !merged_ok(ex, what)) return -1;
-    const int want = merged ? (int)ex->mrg_off.size() - 1 : ex->N;
-    if (ntargets != want) {
-        if (merged) ffgpu_set_error("%s: %d targets for a merge of %d pictures", what, ntargets, want);
-        else ffgpu_set_error("%s: %d targets for an executor of batch %d", what, ntargets, want);
-        return -1;
-    }
-    const hipStream_t s = stream ? (hipStream_t)stream : ex->own_stream;
-    if (s != ex->last_stream) { ffgpu_set_error("%s: the draw must be enqueued on the stream of the forward or merge it follows", what); return -1; }
+    DetSource src;
+    hipStream_t s;
+    if (exec_source(ex, what, "DRAW", "draw", which, ntargets, stream, src, &s)) return -1;
+    src.stride = (int)std::min(src.longest, (long long)0x7fffffff);  // a list too long for the kernel's int: clamped
     std::vector<DrawTarget> tab;
-    if (nv12 ? ffgpu_draw_targets_nv12(what, (const ffgpu_nv12_frame *)targets, ntargets, tab)
-             : ffgpu_draw_targets_bgr(what, (const ffgpu_bgr_frame *)targets, ntargets, tab)) return -1;
-    // a merged list has room for cand_cap boxes per tile of its picture and k_merge_tiles never reports more: the longest room is the kernel's clamp
-    int most = 1;
-    for (int t = 0; t < ntargets; t++) {
-        tab[t].first = (long long)ex->cand_cap * (merged ? ex->mrg_off[t] : t);
-        if (merged) most = std::max(most, ex->mrg_off[t + 1] - ex->mrg_off[t]);
-    }
-    const int stride = (int)std::min((long long)ex->cand_cap * most, (long long)0x7fffffff);
-    return ffgpu_launch_draw(nv12, merged ? ex->d_merged : ex->d_dets, merged ? ex->d_merged_full : ex->d_full, stride, tab, pal, npal, style->thickness, s);
+    if (ffgpu_frame_table(what, FRAME_DRAW, targets, ntargets, tab)) return -1;
+    return ffgpu_launch_draw(std::is_same<Frame, ffgpu_nv12_frame>::value, src, tab, pal, npal, style->thickness, s);
 }
 
 extern "C" int ffgpu_exec_draw_bgr(ffgpu_exec *ex, int which, const ffgpu_bgr_frame *targets, int ntargets, const ffgpu_draw_style *style, void *stream)
 {
-    return exec_draw(ex, false, "draw_bgr", which, targets, ntargets, style, stream);
+    return exec_draw(ex, "draw_bgr", which, targets, ntargets, style, stream);
 }
 
 extern "C" int ffgpu_exec_draw_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_frame *targets, int ntargets, const ffgpu_draw_style *style, void *stream)
 {
-    return exec_draw(ex, true, "draw_nv12", which, targets, ntargets, style, stream);
+    return exec_draw(ex, "draw_nv12", which, targets, ntargets, style, stream);
 }
 
 // -------------------------------------------------------------------------- the detections cut out of the frames (include/ffcnn_hip.h; kernels: ffgpu_crop.inc)
 // A post-pass like the draw, on the stream of the forward or merge it follows: reads the records and full lists (per entry, or the merged ones) and
 // the caller's frames, writes the caller's batch buffer and table and nothing of the executor's.
-static int exec_crop(ffgpu_exec *ex, bool nv12, const char *what, int which, const void *targets, int ntargets, const ffgpu_crop_spec *spec,
+template <class Frame>
+static int exec_crop(ffgpu_exec *ex, const char *what, int which, const Frame *sources, int ntargets, const ffgpu_crop_spec *spec,
                      void *d_out, void *d_table, int capacity, void *stream)
 {
-    int ndev = 0;
-    if (!ex && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)) {
-        (void)hipGetLastError();
-        ffgpu_set_error("%s: no HIP device visible: libffcnn_hip has no CPU fallback", what);
-        return -1;
-    }
-    if (!alive(ex, what)) return -1;
-    if (!targets) { ffgpu_set_error("%s: NULL targets", what); return -1; }
+    if (!exec_ok(ex, what)) return -1;
+    if (!sources) { ffgpu_set_error("%s: NULL targets", what); return -1; }
     CropPlan pl;
     if (ffgpu_crop_spec_check(what, spec, pl) || ffgpu_crop_buffers_check(what, d_out, d_table, capacity)) return -1;
-    if (which != FFGPU_CROP_ENTRIES && which != FFGPU_CROP_MERGED) { ffgpu_set_error("%s: which = %d is neither FFGPU_CROP_ENTRIES nor FFGPU_CROP_MERGED", what, which); return -1; }
-    const bool merged = which == FFGPU_CROP_MERGED;
-    if (merged && !merged_ok(ex, what)) return -1;
-    const int want = merged ? (int)ex->mrg_off.size() - 1 : ex->N;
-    if (ntargets != want) {
-        if (merged) ffgpu_set_error("%s: %d targets for a merge of %d pictures", what, ntargets, want);
-        else ffgpu_set_error("%s: %d targets for an executor of batch %d", what, ntargets, want);
-        return -1;
-    }
-    const hipStream_t s = stream ? (hipStream_t)stream : ex->own_stream;
-    if (s != ex->last_stream) { ffgpu_set_error("%s: the crop must be enqueued on the stream of the forward or merge it follows", what); return -1; }
+    DetSource src;
+    hipStream_t s;
+    if (exec_source(ex, what, "CROP", "crop", which, ntargets, stream, src, &s)) return -1;
+    src.stride = (int)std::min(src.longest, (long long)0x7fffffff);  // (clamped, as the draw)
     std::vector<CropSrc> tab;
-    if (ffgpu_crop_sources(what, nv12, targets, ntargets, tab)) return -1;
-    int most = 1;                                                    // (the clamp of the list lengths: as exec_draw)
-    for (int t = 0; t < ntargets; t++) {
-        tab[t].first = (long long)ex->cand_cap * (merged ? ex->mrg_off[t] : t);
-        if (merged) most = std::max(most, ex->mrg_off[t + 1] - ex->mrg_off[t]);
-    }
-    const int stride = (int)std::min((long long)ex->cand_cap * most, (long long)0x7fffffff);
-    return ffgpu_launch_crop(nv12, merged ? ex->d_merged : ex->d_dets, merged ? ex->d_merged_full : ex->d_full, stride, tab, pl, d_out, d_table, capacity, s);
+    if (ffgpu_frame_table(what, FRAME_DRAW, sources, ntargets, tab)) return -1;
+    return ffgpu_launch_crop(std::is_same<Frame, ffgpu_nv12_frame>::value, src, tab, pl, d_out, d_table, capacity, s);
 }
 
 extern "C" int ffgpu_exec_crop_bgr(ffgpu_exec *ex, int which, const ffgpu_bgr_frame *sources, int ntargets, const ffgpu_crop_spec *spec,
                                    void *d_out, void *d_table, int capacity, void *stream)
 {
-    return exec_crop(ex, false, "crop_bgr", which, sources, ntargets, spec, d_out, d_table, capacity, stream);
+    return exec_crop(ex, "crop_bgr", which, sources, ntargets, spec, d_out, d_table, capacity, stream);
 }
 
 extern "C" int ffgpu_exec_crop_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_frame *sources, int ntargets, const ffgpu_crop_spec *spec,
                                     void *d_out, void *d_table, int capacity, void *stream)
 {
-    return exec_crop(ex, true, "crop_nv12", which, sources, ntargets, spec, d_out, d_table, capacity, stream);
+    return exec_crop(ex, "crop_nv12", which, sources, ntargets, spec, d_out, d_table, capacity, stream);
 }
 
 // -------------------------------------------------------------------------- the detections tracked across frames (include/ffcnn_hip.h; kernel: ffgpu_track.inc)
@@ -1538,34 +1495,15 @@ extern "C" int ffgpu_exec_track(ffgpu_exec *ex, int which, const int *streams, i
                                 void *d_ids, void *d_out_records, void *d_out_lists, void *stream)
 {
     const char *const what = "exec_track";
-    int ndev = 0;
-    if (!ex && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)) {
-        (void)hipGetLastError();
-        ffgpu_set_error("%s: no HIP device visible: libffcnn_hip has no CPU fallback", what);
-        return -1;
-    }
-    if (!alive(ex, what)) return -1;
+    if (!exec_ok(ex, what)) return -1;
     if (ffgpu_track_args_check(what, streams, ntargets, spec, d_state, nstreams, d_ids, d_out_records, d_out_lists)) return -1;
-    if (which != FFGPU_TRACK_ENTRIES && which != FFGPU_TRACK_MERGED) { ffgpu_set_error("%s: which = %d is neither FFGPU_TRACK_ENTRIES nor FFGPU_TRACK_MERGED", what, which); return -1; }
-    const bool merged = which == FFGPU_TRACK_MERGED;
-    if (merged && !merged_ok(ex, what)) return -1;
-    const int want = merged ? (int)ex->mrg_off.size() - 1 : ex->N;
-    if (ntargets != want) {
-        if (merged) ffgpu_set_error("%s: %d targets for a merge of %d pictures", what, ntargets, want);
-        else ffgpu_set_error("%s: %d targets for an executor of batch %d", what, ntargets, want);
-        return -1;
-    }
-    const hipStream_t s = stream ? (hipStream_t)stream : ex->own_stream;
-    if (s != ex->last_stream) { ffgpu_set_error("%s: the tracker must be enqueued on the stream of the forward or merge it follows", what); return -1; }
-    std::vector<long long> first((size_t)ntargets, 0);
-    int most = 1;                                                    // (the clamp of the list lengths: as exec_draw)
-    for (int t = 0; t < ntargets; t++) {
-        first[t] = (long long)ex->cand_cap * (merged ? ex->mrg_off[t] : t);
-        if (merged) most = std::max(most, ex->mrg_off[t + 1] - ex->mrg_off[t]);
-    }
-    if ((long long)ex->cand_cap * most > (1 << 24)) { ffgpu_set_error("%s: lists of up to %lld boxes are too long", what, (long long)ex->cand_cap * most); return -1; }
-    return ffgpu_launch_track(merged ? ex->d_merged : ex->d_dets, merged ? ex->d_merged_full : ex->d_full, ex->cand_cap * most, first.data(), streams, ntargets,
-                              *spec, d_state, d_ids, d_out_records, d_out_lists, s);
+    DetSource src;
+    hipStream_t s;
+    if (exec_source(ex, what, "TRACK", "tracker", which, ntargets, stream, src, &s)) return -1;
+    // the stride is also the pitch of the caller's output lists: a list too long is refused, not clamped
+    if (src.longest > (1 << 24)) { ffgpu_set_error("%s: lists of up to %lld boxes are too long", what, src.longest); return -1; }
+    src.stride = (int)src.longest;
+    return ffgpu_launch_track(src, streams, ntargets, *spec, d_state, d_ids, d_out_records, d_out_lists, s);
 }
 
 // -------------------------------------------------------------------------- the crops classified (include/ffcnn_hip.h; kernels: ffgpu_feature.inc)
@@ -1613,13 +1551,7 @@ extern "C" int ffgpu_exec_feature_dim(const ffgpu_exec *ex, const ffgpu_feature_
 extern "C" int ffgpu_exec_features(ffgpu_exec *ex, const ffgpu_feature_spec *spec, float *d_out, long out_stride, void *stream)
 {
     const char *const what = "exec_features";
-    int ndev = 0;
-    if (!ex && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)) {
-        (void)hipGetLastError();
-        ffgpu_set_error("%s: no HIP device visible: libffcnn_hip has no CPU fallback", what);
-        return -1;
-    }
-    if (!alive(ex, what)) return -1;
+    if (!exec_ok(ex, what)) return -1;
     int c = 0, h = 0, w = 0;
     const int t = feature_tensor(ex, what, spec, &c, &h, &w);
     if (t < 0) return -1;
@@ -1638,34 +1570,14 @@ extern "C" int ffgpu_exec_relabel(ffgpu_exec *ex, int which, const void *d_table
                                   const ffgpu_relabel_spec *spec, void *d_out_records, void *d_out_lists, void *stream)
 {
     const char *const what = "exec_relabel";
-    int ndev = 0;
-    if (!ex && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)) {
-        (void)hipGetLastError();
-        ffgpu_set_error("%s: no HIP device visible: libffcnn_hip has no CPU fallback", what);
-        return -1;
-    }
-    if (!alive(ex, what)) return -1;
+    if (!exec_ok(ex, what)) return -1;
     if (ffgpu_relabel_args_check(what, d_table, capacity, d_labels, k, ntargets, spec, d_out_records)) return -1;
-    if (which != FFGPU_RELABEL_ENTRIES && which != FFGPU_RELABEL_MERGED) { ffgpu_set_error("%s: which = %d is neither FFGPU_RELABEL_ENTRIES nor FFGPU_RELABEL_MERGED", what, which); return -1; }
-    const bool merged = which == FFGPU_RELABEL_MERGED;
-    if (merged && !merged_ok(ex, what)) return -1;
-    const int want = merged ? (int)ex->mrg_off.size() - 1 : ex->N;
-    if (ntargets != want) {
-        if (merged) ffgpu_set_error("%s: %d targets for a merge of %d pictures", what, ntargets, want);
-        else ffgpu_set_error("%s: %d targets for an executor of batch %d", what, ntargets, want);
-        return -1;
-    }
-    const hipStream_t s = stream ? (hipStream_t)stream : ex->own_stream;
-    if (s != ex->last_stream) { ffgpu_set_error("%s: the relabelling must be enqueued on the stream of the forward or merge it follows", what); return -1; }
-    std::vector<long long> first((size_t)ntargets, 0);
-    int most = 1;                                                    // (the clamp of the list lengths: as exec_draw)
-    for (int t = 0; t < ntargets; t++) {
-        first[t] = (long long)ex->cand_cap * (merged ? ex->mrg_off[t] : t);
-        if (merged) most = std::max(most, ex->mrg_off[t + 1] - ex->mrg_off[t]);
-    }
-    if ((long long)ex->cand_cap * most > (1 << 24)) { ffgpu_set_error("%s: lists of up to %lld boxes are too long", what, (long long)ex->cand_cap * most); return -1; }
-    return ffgpu_launch_relabel(d_table, capacity, d_labels, k, merged ? ex->d_merged : ex->d_dets, merged ? ex->d_merged_full : ex->d_full, ex->cand_cap * most,
-                                first.data(), ntargets, *spec, d_out_records, d_out_lists, s);
+    DetSource src;
+    hipStream_t s;
+    if (exec_source(ex, what, "RELABEL", "relabelling", which, ntargets, stream, src, &s)) return -1;
+    if (src.longest > (1 << 24)) { ffgpu_set_error("%s: lists of up to %lld boxes are too long", what, src.longest); return -1; }   // (refused, as the tracker)
+    src.stride = (int)src.longest;
+    return ffgpu_launch_relabel(d_table, capacity, d_labels, k, src, ntargets, *spec, d_out_records, d_out_lists, s);
 }
 
 // FFGPU_KEEP_ALL executors: one 64-bit hash per materialised layer over the layer's WHOLE batch tensor (every bit of every frame), computed on the

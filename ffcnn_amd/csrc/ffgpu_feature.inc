@@ -238,15 +238,6 @@ __global__ void __launch_bounds__(256) k_relabel(RelabelArgs a, const int *table
 }
 
 // ---- host side
-static bool feat_no_device(const char *what)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) return false;
-    (void)hipGetLastError();
-    ffgpu_set_error("%s: no HIP device visible: libffcnn_hip has no CPU fallback", what);
-    return true;
-}
-
 extern "C" int ffgpu_feature_dim(int c, int h, int w, int pool)
 {
     if (c < 1 || h < 1 || w < 1 || pool < FFGPU_FEAT_FLAT || pool > FFGPU_FEAT_MAX) return 0;
@@ -292,7 +283,7 @@ int ffgpu_launch_features(const float *const *parts, int nparts, int pn, int c, 
 extern "C" int ffgpu_features_dev(const float *d_in, int n, int c, int h, int w, int pool, int post, float *d_out, long out_stride, void *stream)
 {
     const char *const what = "features_dev";
-    if (feat_no_device(what)) return -1;
+    if (ffgpu_no_device(what)) return -1;
     if (!d_in) { ffgpu_set_error("%s: NULL input", what); return -1; }
     if (ffgpu_feature_args_check(what, n, c, h, w, pool, post, d_out, out_stride)) return -1;
     if (reinterpret_cast<uintptr_t>(d_in) & 3) { ffgpu_set_error("%s: the input must be 4-byte aligned", what); return -1; }
@@ -302,7 +293,7 @@ extern "C" int ffgpu_features_dev(const float *d_in, int n, int c, int h, int w,
 extern "C" int ffgpu_topk_dev(const float *d_in, int n, int d, long in_stride, int k, void *d_out, void *stream)
 {
     const char *const what = "topk_dev";
-    if (feat_no_device(what)) return -1;
+    if (ffgpu_no_device(what)) return -1;
     if (!d_in) { ffgpu_set_error("%s: NULL input", what); return -1; }
     if (!d_out) { ffgpu_set_error("%s: NULL output", what); return -1; }
     if (n < 1 || n > (1 << 24)) { ffgpu_set_error("%s: %d rows (n >= 1)", what, n); return -1; }
@@ -336,18 +327,18 @@ int ffgpu_relabel_args_check(const char *what, const void *d_table, int capacity
     return 0;
 }
 
-// record t's list starts at box first[t] of `lists`; everything has been checked
-int ffgpu_launch_relabel(const void *d_table, int capacity, const void *d_labels, int k, const ffgpu_frame_dets *recs, const BBOX *lists, int stride,
-                         const long long *first, int ntargets, const ffgpu_relabel_spec &spec, void *d_out_records, void *d_out_lists, hipStream_t s)
+// everything has been checked
+int ffgpu_launch_relabel(const void *d_table, int capacity, const void *d_labels, int k, const DetSource &src, int ntargets, const ffgpu_relabel_spec &spec,
+                         void *d_out_records, void *d_out_lists, hipStream_t s)
 {
-    if ((const void *)recs == d_out_records || (lists && (const void *)lists == d_out_lists)) { ffgpu_set_error("relabel: the outputs must not overlap the inputs"); return -1; }
+    if ((const void *)src.recs == d_out_records || (src.lists && (const void *)src.lists == d_out_lists)) { ffgpu_set_error("relabel: the outputs must not overlap the inputs"); return -1; }
     for (int t0 = 0; t0 < ntargets; t0 += RELABEL_ARG_ENTRIES) {
         const int nt = std::min(RELABEL_ARG_ENTRIES, ntargets - t0);
         RelabelArgs a;
         memset(&a, 0, sizeof a);
         a.t0 = t0;
-        for (int i = 0; i < nt; i++) a.first[i] = first[t0 + i];
-        hipLaunchKernelGGL(k_relabel, dim3((unsigned)nt), dim3(256), 0, s, a, (const int *)d_table, capacity, (const int2 *)d_labels, k, recs, lists, stride,
+        for (int i = 0; i < nt; i++) a.first[i] = src.first[t0 + i];
+        hipLaunchKernelGGL(k_relabel, dim3((unsigned)nt), dim3(256), 0, s, a, (const int *)d_table, capacity, (const int2 *)d_labels, k, src.recs, src.lists, src.stride,
                            spec, (ffgpu_frame_dets *)d_out_records, (BBOX *)d_out_lists);
         LAUNCH_OK("crops_relabel");
     }
@@ -359,16 +350,9 @@ extern "C" int ffgpu_crops_relabel_dev(const void *d_table, int capacity, const 
                                        void *d_out_lists, void *stream)
 {
     const char *const what = "crops_relabel_dev";
-    if (feat_no_device(what)) return -1;
-    if (!d_records) { ffgpu_set_error("%s: NULL records", what); return -1; }
+    if (ffgpu_no_device(what)) return -1;
     if (ffgpu_relabel_args_check(what, d_table, capacity, d_labels, k, ntargets, spec, d_out_records)) return -1;
-    const int stride = d_lists ? list_stride : FFGPU_MAX_DET;
-    if (stride < 1 || stride > (1 << 24)) { ffgpu_set_error("%s: bad list_stride %d", what, list_stride); return -1; }
-    std::vector<long long> first((size_t)ntargets, 0);
-    for (int t = 0; t < ntargets; t++) {
-        if (d_lists && list_first && list_first[t] < 0) { ffgpu_set_error("%s: target %d: negative list start %d", what, t, list_first[t]); return -1; }
-        first[t] = d_lists ? (list_first ? (long long)list_first[t] : (long long)t * stride) : 0;
-    }
-    return ffgpu_launch_relabel(d_table, capacity, d_labels, k, (const ffgpu_frame_dets *)d_records, (const BBOX *)d_lists, stride, first.data(), ntargets, *spec,
-                                d_out_records, d_out_lists, (hipStream_t)stream);
+    DetSource src;
+    if (ffgpu_source_dev(what, d_records, d_lists, list_stride, list_first, ntargets, src)) return -1;
+    return ffgpu_launch_relabel(d_table, capacity, d_labels, k, src, ntargets, *spec, d_out_records, d_out_lists, (hipStream_t)stream);
 }

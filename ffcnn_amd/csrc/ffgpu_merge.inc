@@ -241,15 +241,10 @@ extern "C" size_t ffgpu_merge_tiles_scratch_bytes(int ntiles, int list_stride)
 extern "C" int ffgpu_merge_tiles_dev(const void *d_records, const void *d_lists, int list_stride, const ffgpu_tile *tiles, int ntiles, int nimages,
                                      float thresh, int use_min, void *d_out_records, void *d_out_lists, void *d_scratch, size_t scratch_bytes, void *stream)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        (void)hipGetLastError();
-        ffgpu_set_error("merge_tiles_dev: no HIP device visible: libffcnn_hip has no CPU fallback");
-        return -1;
-    }
+    if (ffgpu_no_device("merge_tiles_dev")) return -1;
     if (!d_records || !d_out_records) { ffgpu_set_error("merge_tiles_dev: NULL records"); return -1; }
-    const int stride = d_lists ? list_stride : FFGPU_MAX_DET;
-    if (stride < 1 || stride > (1 << 24)) { ffgpu_set_error("merge_tiles_dev: bad list_stride %d", list_stride); return -1; }
+    const int stride = ffgpu_list_stride("merge_tiles_dev", d_lists, list_stride);
+    if (stride < 0) return -1;
     std::vector<int> tab, off;
     if (ffgpu_merge_build_tab("merge_tiles_dev", tiles, ntiles, nimages, tab, &off)) return -1;
     // the scratch buffer is needed when a picture's union CAN exceed the LDS slots (the kernel then uses it for the pictures whose union does),

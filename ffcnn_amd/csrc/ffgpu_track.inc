@@ -237,15 +237,6 @@ __global__ void __launch_bounds__(256) k_track(TrackArgs a, const ffgpu_frame_de
 static_assert(FFGPU_MAX_DET == FFGPU_TRACK_DETS, "k_track: a tracked record holds every considered box");
 
 // ---- host side
-static bool track_no_device(const char *what)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) return false;
-    (void)hipGetLastError();
-    ffgpu_set_error("%s: no HIP device visible: libffcnn_hip has no CPU fallback", what);
-    return true;
-}
-
 extern "C" size_t ffgpu_track_state_bytes(int nstreams, int capacity)
 {
     if (nstreams < 1 || nstreams > 65536 || capacity < 1 || capacity > FFGPU_TRACK_DETS) return 0;
@@ -283,9 +274,8 @@ int ffgpu_track_args_check(const char *what, const int *streams, int ntargets, c
     return 0;
 }
 
-// record t's list starts at box first[t] of `lists`; everything has been checked
-int ffgpu_launch_track(const ffgpu_frame_dets *recs, const BBOX *lists, int stride, const long long *first, const int *streams, int ntargets,
-                       const ffgpu_track_spec &spec, void *d_state, void *d_ids, void *d_out_records, void *d_out_lists, hipStream_t s)
+// everything has been checked
+int ffgpu_launch_track(const DetSource &src, const int *streams, int ntargets, const ffgpu_track_spec &spec, void *d_state, void *d_ids, void *d_out_records, void *d_out_lists, hipStream_t s)
 {
     const size_t lds = sizeof(TrackLds);
     if (lds_allow((const void *)k_track, lds, "track_boxes")) return -1;
@@ -300,10 +290,10 @@ int ffgpu_launch_track(const ffgpu_frame_dets *recs, const BBOX *lists, int stri
         for (int i = 0; i < nt; i++) {
             const int t = order[i];
             if (i == 0 || streams[t] != streams[order[i - 1]]) { a.gstream[a.ngroups] = streams[t]; a.goff[a.ngroups] = i; a.ngroups++; }
-            a.rec[i] = t; a.first[i] = first[t];
+            a.rec[i] = t; a.first[i] = src.first[t];
         }
         a.goff[a.ngroups] = nt;
-        hipLaunchKernelGGL(k_track, dim3((unsigned)a.ngroups), dim3(256), lds, s, a, recs, lists, stride, (unsigned char *)d_state, (int *)d_ids,
+        hipLaunchKernelGGL(k_track, dim3((unsigned)a.ngroups), dim3(256), lds, s, a, src.recs, src.lists, src.stride, (unsigned char *)d_state, (int *)d_ids,
                            (ffgpu_frame_dets *)d_out_records, (BBOX *)d_out_lists);
         LAUNCH_OK("track_boxes");
     }
@@ -313,7 +303,7 @@ int ffgpu_launch_track(const ffgpu_frame_dets *recs, const BBOX *lists, int stri
 extern "C" int ffgpu_track_reset_dev(void *d_state, int nstreams, int capacity, int which_stream, void *stream)
 {
     const char *const what = "track_reset_dev";
-    if (track_no_device(what)) return -1;
+    if (ffgpu_no_device(what)) return -1;
     if (!d_state) { ffgpu_set_error("%s: NULL state", what); return -1; }
     const size_t all = ffgpu_track_state_bytes(nstreams, capacity);
     if (!all) { ffgpu_set_error("%s: %d streams of %d slots (nstreams 1..65536, capacity 1..%d)", what, nstreams, capacity, FFGPU_TRACK_DETS); return -1; }
@@ -333,16 +323,9 @@ extern "C" int ffgpu_track_boxes_dev(const void *d_records, const void *d_lists,
                                      const ffgpu_track_spec *spec, void *d_state, int nstreams, void *d_ids, void *d_out_records, void *d_out_lists, void *stream)
 {
     const char *const what = "track_boxes_dev";
-    if (track_no_device(what)) return -1;
-    if (!d_records) { ffgpu_set_error("%s: NULL records", what); return -1; }
+    if (ffgpu_no_device(what)) return -1;
     if (ffgpu_track_args_check(what, streams, ntargets, spec, d_state, nstreams, d_ids, d_out_records, d_out_lists)) return -1;
-    const int stride = d_lists ? list_stride : FFGPU_MAX_DET;
-    if (stride < 1 || stride > (1 << 24)) { ffgpu_set_error("%s: bad list_stride %d", what, list_stride); return -1; }
-    std::vector<long long> first((size_t)ntargets, 0);
-    for (int t = 0; t < ntargets; t++) {
-        if (d_lists && list_first && list_first[t] < 0) { ffgpu_set_error("%s: target %d: negative list start %d", what, t, list_first[t]); return -1; }
-        first[t] = d_lists ? (list_first ? (long long)list_first[t] : (long long)t * stride) : 0;
-    }
-    return ffgpu_launch_track((const ffgpu_frame_dets *)d_records, (const BBOX *)d_lists, stride, first.data(), streams, ntargets, *spec, d_state, d_ids,
-                              d_out_records, d_out_lists, (hipStream_t)stream);
+    DetSource src;
+    if (ffgpu_source_dev(what, d_records, d_lists, list_stride, list_first, ntargets, src)) return -1;
+    return ffgpu_launch_track(src, streams, ntargets, *spec, d_state, d_ids, d_out_records, d_out_lists, (hipStream_t)stream);
 }
