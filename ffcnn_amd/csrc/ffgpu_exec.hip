@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "ffgpu_dev.hpp"
+#include "ffgpu_plan.hpp"
 #include "conv.h"
 
 // --------------------------------------------------------------------------
@@ -170,15 +171,6 @@ struct Step {
     int      lane;           // 0: main stream, 1: side stream (a detection head that runs beside the rest of the net)
 };
 
-struct Tensor {
-    long size = 0;           // floats
-    int  first = 1 << 30, last = -1;
-    long off = -1;           // arena offset (roots only)
-    int  parent = -1;        // concat-in-place parent tensor
-    long parent_off = 0;
-    bool used = false;
-};
-
 struct ffgpu_netdev {
     NET   *net = nullptr;
     std::mutex mu;                     // guards execs (executors may be created / destroyed from several threads)
@@ -225,11 +217,8 @@ struct ffgpu_exec {
     int  N = 1, flags = 0, device = 0;
     int  in_c = 0, in_h = 0, in_w = 0;
     std::vector<Step>   steps;
-    std::vector<Tensor> tensors;       // index = layer id
-    std::vector<int>    canon;         // layer id -> tensor id holding its output (-1: the batch input, -2: none, -3: fused away)
-    std::vector<char>   readable;      // layer's own output value exists in memory after a forward
-    float *arena = nullptr;
-    size_t arena_floats = 0;
+    NetLayout layout;                  // tensors, aliases, lifetimes, side lane and arena offsets (ffgpu_plan.hpp)
+    float *arena = nullptr;            // layout.arena_floats floats
     float *d_input = nullptr;          // own staging buffer for host / bgr entry points
     float *d_pack = nullptr;           // packed constants of the fused blocks (derived from the weights)
     BBOX  *d_cand = nullptr;           // cand_cap candidate slots per frame: one per anchor of every head cell
@@ -263,7 +252,6 @@ struct ffgpu_exec {
     hipStream_t own_stream = nullptr, last_stream = nullptr;
     hipStream_t side_stream = nullptr;              // second graph branch
     hipEvent_t  ev_fork = nullptr, ev_join = nullptr;
-    int side_lo = -1, side_hi = -1;                 // layers [side_lo, side_hi] form the side branch
     // ONE instantiated graph per input form: the input pointer and the box scale reach the kernels through d_prm, and the forms differ in
     // the first kernel alone.  IN_F32's is captured when the executor is created, a u8 form's on its first use.  Only a
     // net whose first layer has no kernel that reads through the slot (indirect == false: e.g. a pool or a pointwise conv
@@ -276,244 +264,102 @@ struct ffgpu_exec {
     int kernel_count = 0;
 };
 
-static float *tensor_ptr(const ffgpu_exec *ex, int t)
-{
-    long off = 0;
-    while (ex->tensors[t].parent >= 0) { off += ex->tensors[t].parent_off; t = ex->tensors[t].parent; }
-    return ex->arena + ex->tensors[t].off + off;
-}
-
-static int root_of(const std::vector<Tensor> &ts, int t) { while (ts[t].parent >= 0) t = ts[t].parent; return t; }
+static float *tensor_ptr(const ffgpu_exec *ex, int t) { return ex->arena + ex->layout.offset_of(t); }
 
 // -------------------------------------------------------------------------- planning
-static int plan(ffgpu_exec *ex)
+// plan() = the layout (ffgpu_plan.hpp: pure host code), the arena, the step list built from the layout, the rewrites of that list, the packed
+// constants' places, and whether the captured graph is free of the input pointer.
+static bool env_on(const char *name) { const char *v = getenv(name); return v && atoi(v) != 0; }
+
+// the one place the planner's switches are read: the flags, and the environment -- FFGPU_NO_IRB and FFGPU_IRB_MIN_EC once per process, the rest per create
+static PlanOptions plan_options(const ffgpu_exec *ex)
 {
-    NET *net = ex->net;
-    const int L = net->layer_num, N = ex->N;
-    const bool keep_all = ex->flags & FFGPU_KEEP_ALL;
-    const bool fuse = !(ex->flags & FFGPU_NO_FUSE);
-    const LAYER *ll = net->layer_list;
-    std::vector<Tensor> &T = ex->tensors;
-    std::vector<int> &canon = ex->canon;
-    T.assign(L, Tensor());
-    canon.assign(L, -2);
-    auto out_floats = [&](int i) { return (long)ll[i + 1].w * ll[i + 1].h * ll[i + 1].c * N; };
-    auto src_tensor = [&](int i) { return i < 0 ? -1 : canon[i]; };          // tensor holding the output of layer i
+    static const bool no_irb = env_on("FFGPU_NO_IRB");
+    static const int min_ec = getenv("FFGPU_IRB_MIN_EC") ? atoi(getenv("FFGPU_IRB_MIN_EC")) : 24;
+    PlanOptions o;
+    o.batch = ex->N;
+    o.keep_all = ex->flags & FFGPU_KEEP_ALL;
+    o.fuse = !(ex->flags & FFGPU_NO_FUSE);
+    // The head branch is OPT-IN (FFGPU_BRANCH=1).  MEASURED (r01): 2 % faster than the single chain once the head kernels were latency-sized (0.766 vs
+    // 0.782 ms per 64-frame batch), slower in an FFGPU_CONCURRENT plan (0.489 vs 0.455 ms: the other chains fill those gaps).  A forked graph runs on
+    // internal streams of the runtime (ROCm 7.0), its fragile part (an arena's worth of memory kept per destroyed graph, one
+    // SIGSEGV inside hipGraphLaunch in 30 runs of 630 create / launch / destroy cycles): 2 % of ONE chain's latency is not worth a process.  Never
+    // inside the halves of a split executor: a fork nested in a forked stream crashes graph capture there.
+    o.branch = env_on("FFGPU_BRANCH") && !ex->is_child;
+    o.no_irb = no_irb; o.irb_min_ec = min_ec;
+    o.dwpw = env_on("FFGPU_DWPW");
+    return o;
+}
 
-    // pass 1: aliases and shortcut fusion targets
-    std::vector<int> fused_into(L, -1);         // conv p -> shortcut s whose add it absorbs
-    std::vector<int> nuses(L, 0);               // consumers per LAYER output (before aliasing)
-    for (int i = 0; i < L; i++) {
-        if (i > 0 && ll[i].type != LAYER_TYPE_ROUTE) nuses[i - 1]++;
-        for (int k = 0; k < ll[i].depend_num; k++) {
-            const int d = ll[i].depend_list[k];
-            if (d < 0 || d >= i) { ffgpu_set_error("layer %d depends on layer %d (not earlier)", i, d); return -1; }
-            nuses[d]++;
-        }
-    }
-    for (int i = 0; i < L; i++) {
-        switch (ll[i].type) {
-        case LAYER_TYPE_DROPOUT: canon[i] = src_tensor(i - 1); break;
-        case LAYER_TYPE_YOLO: canon[i] = -2; break;
-        case LAYER_TYPE_ROUTE:
-            canon[i] = (ll[i].depend_num == 1 && src_tensor(ll[i].depend_list[0]) >= -1) ? src_tensor(ll[i].depend_list[0]) : i;     // (-1: an alias of the net input)
-            break;
-        default: canon[i] = i;
-        }
-        if (fuse && ll[i].type == LAYER_TYPE_SHORTCUT && i > 0) {
-            // walk back over dropouts to the producer of our input
-            int p = i - 1;
-            while (p > 0 && ll[p].type == LAYER_TYPE_DROPOUT && nuses[p] == 1) p--;
-            bool chain_private = ll[p].type == LAYER_TYPE_CONV && nuses[p] == 1 && src_tensor(ll[i].depend_list[0]) >= 0;
-            for (int q = p + 1; q < i && chain_private; q++) chain_private = ll[q].type == LAYER_TYPE_DROPOUT && nuses[q] == 1;
-            if (chain_private) { fused_into[p] = i; for (int q = p; q < i; q++) canon[q] = i; }
-        }
-    }
-    // pass 1b: 1x1 expand -> depthwise 3x3 -> 1x1 project triples become ONE fused kernel (ffgpu_irb.inc);
-    // the two expanded tensors are never materialised
-    std::vector<int> irb_tail(L, -1);           // layer p+2 -> p
-    std::vector<IrbDesc> irb_planned(L);        // layer p+2 -> the block's planned descriptor
-    auto irb_desc = [&](int p0) {               // geometry, activations, flags and res_act of the block of layers p0 .. p0 + 2 (the step adds the pointers)
-        IrbDesc d{};
-        const LAYER &a = ll[p0], &b = ll[p0 + 1], &c = ll[p0 + 2];
-        d.N = N; d.H = a.h; d.W = a.w; d.OH = ll[p0 + 3].h; d.OW = ll[p0 + 3].w;
-        d.ic = a.c; d.ec = a.fn; d.oc = c.fn; d.stride = b.stride; d.flags = ex->flags & FFGPU_CONCURRENT;
-        d.act1 = a.activation; d.actd = b.activation; d.act2 = c.activation;
-        d.res_act = fused_into[p0 + 2] >= 0 ? ll[fused_into[p0 + 2]].activation : 0;
-        return d;
+static ConvDesc layer_desc(const ffgpu_exec *ex, int i, int flag_mask = FFGPU_COMPAT_V6)
+{
+    ConvDesc d{};
+    const LAYER &a = ex->net->layer_list[i], &b = ex->net->layer_list[i + 1];
+    const int N = ex->N;
+    d.N = N; d.iw = a.w; d.ih = a.h; d.ic = a.c; d.ow = b.w; d.oh = b.h; d.oc = b.c;
+    d.fs = a.fs; d.stride = a.stride; d.pad = a.pad; d.groups = a.groups; d.act = a.activation;
+    d.flags = ex->flags & flag_mask;
+    d.in_cs = (long)N * a.w * a.h; d.in_ns = (long)a.w * a.h;
+    d.out_cs = (long)N * b.w * b.h; d.out_ns = (long)b.w * b.h;
+    return d;
+}
+
+// geometry, activations, flags and res_act of the block of layers p0 .. p0 + 2 (the step adds the pointers)
+static IrbDesc irb_desc(const ffgpu_exec *ex, int p0)
+{
+    IrbDesc d{};
+    const LAYER *ll = ex->net->layer_list;
+    const LAYER &a = ll[p0], &b = ll[p0 + 1], &c = ll[p0 + 2];
+    const int sc = ex->layout.fused_into[p0 + 2];
+    d.N = ex->N; d.H = a.h; d.W = a.w; d.OH = ll[p0 + 3].h; d.OW = ll[p0 + 3].w;
+    d.ic = a.c; d.ec = a.fn; d.oc = c.fn; d.stride = b.stride; d.flags = ex->flags & FFGPU_CONCURRENT;
+    d.act1 = a.activation; d.actd = b.activation; d.act2 = c.activation;
+    d.res_act = sc >= 0 ? ll[sc].activation : 0;
+    return d;
+}
+
+// stage 1: the layout.  What the kernels say of a block decides with it; the planned descriptors stay for the step builder (layer p0 + 2 -> its block's).
+static int plan_layout(ffgpu_exec *ex, std::vector<IrbDesc> &irb_planned)
+{
+    const PlanOptions opt = plan_options(ex);
+    irb_planned.assign(ex->net->layer_num, IrbDesc{});
+    auto block_ok = [&](int p0) {
+        IrbDesc d = irb_desc(ex, p0);
+        if (!ffgpu_irb_plan(d) || (d.ec < opt.irb_min_ec && d.plan.family != IRB_THIN)) return false;   // thin blocks take the streaming fused kernel
+        irb_planned[p0 + 2] = d;
+        return true;
     };
-    static const bool no_irb = getenv("FFGPU_NO_IRB") && atoi(getenv("FFGPU_NO_IRB"));
-    if (fuse && !no_irb) {
-        for (int p0 = 0; p0 + 2 < L; p0++) {
-            const LAYER &a = ll[p0], &b = ll[p0 + 1], &c = ll[p0 + 2];
-            if (a.type != LAYER_TYPE_CONV || b.type != LAYER_TYPE_CONV || c.type != LAYER_TYPE_CONV) continue;
-            const bool pw_a = a.fs == 1 && a.stride == 1 && a.pad == 0 && a.groups == 1;
-            const bool dw_b = b.fs == 3 && b.pad == 1 && (b.stride == 1 || b.stride == 2) && b.groups == b.c && b.fn == b.c;
-            const bool pw_c = c.fs == 1 && c.stride == 1 && c.pad == 0 && c.groups == 1;
-            if (!pw_a || !dw_b || !pw_c || nuses[p0] != 1 || nuses[p0 + 1] != 1 || src_tensor(p0 - 1) < 0) continue;
-            if (canon[p0] != p0 || canon[p0 + 1] != p0 + 1) continue;
-            IrbDesc d = irb_desc(p0);
-            static const int min_ec = getenv("FFGPU_IRB_MIN_EC") ? atoi(getenv("FFGPU_IRB_MIN_EC")) : 24;
-            if (!ffgpu_irb_plan(d) || (d.ec < min_ec && d.plan.family != IRB_THIN)) continue;   // thin blocks take the streaming fused kernel
-            irb_tail[p0 + 2] = p0; irb_planned[p0 + 2] = d;
-            canon[p0] = canon[p0 + 1] = -3;
-            p0 += 2;
-        }
-    }
-    // pass 1c (opt-in, FFGPU_DWPW=1): depthwise K x K (stride 1) -> 1x1 pairs that no fused block claimed (the heads' 5x5 + 1x1
-    // of yolo-fastest) become one launch (ffgpu_dwpw.inc); the depthwise tensor is never materialised.  MEASURED (r02,
-    // tools/dwpw_bench.py): correct but SLOWER than the two launches it replaces -- 61 vs 8 + 15 us on 20x20x120 at batch 64
-    // (one workgroup per CU, a barrier chain of 15 short depthwise / MFMA phases with one wave per SIMD; 147.5 k frames/s
-    // end to end against 182.7 k) -- so the planner leaves the pairs alone unless asked.
-    auto layer_desc = [&](int i, int flag_mask = FFGPU_COMPAT_V6) {
-        ConvDesc d{};
-        const LAYER &a = ll[i], &b = ll[i + 1];
-        d.N = N; d.iw = a.w; d.ih = a.h; d.ic = a.c; d.ow = b.w; d.oh = b.h; d.oc = b.c;
-        d.fs = a.fs; d.stride = a.stride; d.pad = a.pad; d.groups = a.groups; d.act = a.activation;
-        d.flags = ex->flags & flag_mask;
-        d.in_cs = (long)N * a.w * a.h; d.in_ns = (long)a.w * a.h;
-        d.out_cs = (long)N * b.w * b.h; d.out_ns = (long)b.w * b.h;
-        return d;
-    };
-    std::vector<int> dwpw_tail(L, -1);          // layer p+1 -> p
-    if (fuse && getenv("FFGPU_DWPW") && atoi(getenv("FFGPU_DWPW"))) {
-        for (int p0 = 0; p0 + 1 < L; p0++) {
-            if (ll[p0].type != LAYER_TYPE_CONV || ll[p0 + 1].type != LAYER_TYPE_CONV) continue;
-            if (canon[p0] != p0 || canon[p0 + 1] != p0 + 1 || nuses[p0] != 1 || fused_into[p0] >= 0 || fused_into[p0 + 1] >= 0 || src_tensor(p0 - 1) < 0) continue;
-            if (!ffgpu_dwpw_ok(layer_desc(p0), layer_desc(p0 + 1))) continue;
-            dwpw_tail[p0 + 1] = p0;
-            canon[p0] = -3;
-            p0++;
-        }
-    }
-    for (int i = 0; i < L; i++) if (canon[i] == i) { T[i].used = true; T[i].size = out_floats(i); }
-    ex->readable.assign(L, 0);
-    for (int i = 0; i < L; i++) {
-        if (canon[i] == i) ex->readable[i] = 1;
-        else if (ll[i].type == LAYER_TYPE_DROPOUT && i > 0 && canon[i] >= 0 && canon[i] == canon[i - 1]) ex->readable[i] = ex->readable[i - 1];
-        else if (ll[i].type == LAYER_TYPE_ROUTE && ll[i].depend_num == 1 && canon[i] >= 0) ex->readable[i] = ex->readable[ll[i].depend_list[0]];
-    }
+    auto pair_ok = [&](int p0) { return ffgpu_dwpw_ok(layer_desc(ex, p0), layer_desc(ex, p0 + 1)); };
+    return ffgpu_net_layout(ex->net->layer_list, ex->net->layer_num, opt, block_ok, pair_ok, ex->layout);
+}
 
-    // pass 2: concat-in-place for multi-source routes
-    std::vector<char> route_inplace(L, 0);
-    if (fuse) {
-        for (int i = 0; i < L; i++) {
-            if (ll[i].type != LAYER_TYPE_ROUTE || canon[i] != i || ll[i].depend_num < 2) continue;
-            bool ok = true;
-            std::vector<int> kids;
-            for (int k = 0; k < ll[i].depend_num && ok; k++) {
-                const int t = src_tensor(ll[i].depend_list[k]);
-                ok = t >= 0 && T[t].parent < 0 && std::find(kids.begin(), kids.end(), t) == kids.end();
-                kids.push_back(t);
-            }
-            if (!ok) continue;
-            long off = 0;
-            for (int t : kids) { T[t].parent = i; T[t].parent_off = off; off += T[t].size; }
-            route_inplace[i] = 1;
-        }
-    }
+// stage 2
+static int plan_arena(ffgpu_exec *ex)
+{
+    const size_t bytes = ex->layout.arena_floats * sizeof(float);
+    if (hipMalloc(&ex->arena, bytes) != hipSuccess) { ffgpu_set_error("arena hipMalloc(%zu bytes) failed", bytes); return -1; }
+    return 0;
+}
 
-    // pass 3: lifetimes (in layer-index time), folded onto concat roots
-    auto touch = [&](int t, int when) { if (t >= 0) { T[t].first = std::min(T[t].first, when); T[t].last = std::max(T[t].last, when); } };
-    for (int i = 0; i < L; i++) {
-        if (ll[i].type == LAYER_TYPE_DROPOUT) continue;
-        if (canon[i] >= 0 && !(ll[i].type == LAYER_TYPE_ROUTE && canon[i] != i)) touch(canon[i], i);     // written at i
-        if (ll[i].type != LAYER_TYPE_ROUTE) touch(src_tensor(i - 1), i);                                  // chain input read at i
-        for (int k = 0; k < ll[i].depend_num; k++) touch(src_tensor(ll[i].depend_list[k]), i);
-        if (irb_tail[i] >= 0) touch(src_tensor(irb_tail[i] - 1), i);
-        if (dwpw_tail[i] >= 0) touch(src_tensor(dwpw_tail[i] - 1), i);
-        if (irb_tail[i] >= 0 && fused_into[i] >= 0) touch(src_tensor(ll[fused_into[i]].depend_list[0]), i);
-    }
-    for (int t = 0; t < L; t++) {
-        if (!T[t].used || T[t].parent < 0) continue;
-        const int r = root_of(T, t);
-        T[r].first = std::min(T[r].first, T[t].first);
-        T[r].last = std::max(T[r].last, T[t].last);
-    }
-
-    // pass 3b: the first detection head runs BESIDE the rest of the net.  In a yolo cfg the layer after a [yolo]
-    // is a [route] back to a tensor produced at layer r: layers r+1 .. yolo only feed that head, everything after the
-    // yolo only depends on layers <= r, so the two chains become parallel branches of the HIP graph (the head's
-    // 10x10 kernels are latency-bound and hide under the other branch).  Their tensors must then not share arena
-    // space: every tensor born after the fork stays live to the end.
-    ex->side_lo = ex->side_hi = -1;
-    // MEASURED (r01): 1.5 % slower than the single chain while the head kernels were slow, 2 % FASTER once they were
-    // latency-sized (0.766 vs 0.782 ms per 64-frame batch) -> on by default; FFGPU_BRANCH=0 turns it off.
-    // (not inside the halves of a split executor: a fork nested in a forked stream crashes graph capture on ROCm 7.0,
-    //  and the second half-batch chain already fills the gaps the head branch was meant to fill)
-    //  nor in an FFGPU_CONCURRENT plan: the other chains fill those gaps -- 0.489 vs 0.455 ms with the branch on)
-    //  Round 3: OPT-IN (FFGPU_BRANCH=1).  A graph with a forked branch makes the runtime (ROCm 7.0) run it on internal streams of
-    //  its own, and that part of the runtime is the fragile one: it kept an arena's worth of memory per destroyed graph until a
-    //  device-wide sync was put in front of hipGraphExecDestroy (ffgpu_exec_destroy), and the one host crash that survived the
-    //  round-3 transfer rework (SIGSEGV inside hipGraphLaunch of a freshly created executor, once in 30
-    //  runs of 630 create / launch / destroy cycles each) was in its walk over those streams.  2 % of ONE chain's latency is not
-    //  worth a process; throughput configurations (several chains, FFGPU_CONCURRENT) never used the branch.
-    const bool branch = (getenv("FFGPU_BRANCH") ? atoi(getenv("FFGPU_BRANCH")) != 0 : false) && !ex->is_child;
-    if (fuse && branch) {
-        for (int y = 0; y + 1 < L; y++) {
-            if (ll[y].type != LAYER_TYPE_YOLO || ll[y + 1].type != LAYER_TYPE_ROUTE || ll[y + 1].depend_num != 1) continue;
-            const int r = ll[y + 1].depend_list[0];
-            bool ok = r >= 0 && r < y;
-            // nothing after the yolo may read a tensor produced inside (r, y]
-            for (int i = y + 1; i < L && ok; i++)
-                for (int k = 0; k < ll[i].depend_num; k++) if (ll[i].depend_list[k] > r && ll[i].depend_list[k] <= y) ok = false;
-            // nothing inside (r, y] may be a fused block straddling the fork (its first layer must be > r)
-            for (int i = r + 1; i <= y && ok; i++) if ((irb_tail[i] >= 0 && irb_tail[i] <= r) || (dwpw_tail[i] >= 0 && dwpw_tail[i] <= r)) ok = false;
-            if (fused_into[r] > r) ok = false;       // the fork tensor's producer was absorbed by a later shortcut
-            if (!ok) continue;
-            ex->side_lo = r + 1; ex->side_hi = y;
-            for (int t = 0; t < L; t++) if (T[t].used && T[t].first > r) T[t].last = L + 1;
-            for (int i = r + 1; i <= y; i++) {       // ... and whatever the side branch READS (its kernels may run late)
-                if (ll[i].type != LAYER_TYPE_ROUTE && src_tensor(i - 1) >= 0) T[src_tensor(i - 1)].last = L + 1;
-                for (int k = 0; k < ll[i].depend_num; k++) if (src_tensor(ll[i].depend_list[k]) >= 0) T[src_tensor(ll[i].depend_list[k])].last = L + 1;
-                if (irb_tail[i] >= 0 && src_tensor(irb_tail[i] - 1) >= 0) T[src_tensor(irb_tail[i] - 1)].last = L + 1;
-                if (dwpw_tail[i] >= 0 && src_tensor(dwpw_tail[i] - 1) >= 0) T[src_tensor(dwpw_tail[i] - 1)].last = L + 1;
-            }
-            for (int t = 0; t < L; t++) {
-                if (!T[t].used || T[t].parent < 0) continue;
-                const int rt = root_of(T, t);
-                T[rt].last = std::max(T[rt].last, T[t].last);
-            }
-            break;
-        }
-    }
-
-    // pass 4: first-fit arena allocation of the roots, 256-byte granules
-    struct Live { long off, size; int last; };
-    std::vector<Live> live;
-    long high = 0;
-    std::vector<int> order;
-    for (int t = 0; t < L; t++) if (T[t].used && T[t].parent < 0) order.push_back(t);
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return T[a].first != T[b].first ? T[a].first < T[b].first : a < b; });
-    for (int t : order) {
-        const long need = (T[t].size + 63) & ~63L;
-        if (keep_all) { T[t].off = high; high += need; continue; }
-        live.erase(std::remove_if(live.begin(), live.end(), [&](const Live &l) { return l.last < T[t].first; }), live.end());
-        std::sort(live.begin(), live.end(), [](const Live &a, const Live &b) { return a.off < b.off; });
-        long at = 0;
-        for (const Live &l : live) { if (at + need <= l.off) break; at = std::max(at, l.off + l.size); }
-        T[t].off = at;
-        live.push_back({ at, need, T[t].last });
-        high = std::max(high, at + need);
-    }
-    ex->arena_floats = (size_t)std::max(high, 64L);
-    if (hipMalloc(&ex->arena, ex->arena_floats * sizeof(float)) != hipSuccess) {
-        ffgpu_set_error("arena hipMalloc(%zu bytes) failed", ex->arena_floats * sizeof(float));
-        return -1;
-    }
-
-    // pass 5: steps
+// stage 3: one pass over the layers, every tensor at arena + offset_of
+static int plan_steps(ffgpu_exec *ex, const std::vector<IrbDesc> &irb_planned)
+{
+    const NetLayout &nl = ex->layout;
+    const LAYER *ll = ex->net->layer_list;
+    const int L = ex->net->layer_num, N = ex->N;
     std::vector<Step> &S = ex->steps;
     S.clear();
     { Step c{}; c.kind = S_CLEAR; c.layer = -1; c.ltype = LAYER_TYPE_YOLO; S.push_back(c); }
-    int key_base = 0, nheads = 0;
+    int key_base = 0;
     float *cnhw_input = nullptr;     // set when the first layer cannot read the frame-major input directly
     bool bad_chain = false;
+    auto ptr = [&](int t) { return tensor_ptr(ex, t); };
+    auto weights = [&](int i) { return ex->dev->d_weights + (ll[i].filter - ex->net->weight_buf); };
     auto in_ptr = [&](int i, bool *is_input) -> const float * {
-        const int t = src_tensor(i - 1);
+        const int t = nl.src(i - 1);
         *is_input = t == -1;
         if (t < -1) bad_chain = true;            // e.g. a conv chained directly behind a yolo head
-        return t >= 0 ? tensor_ptr(ex, t) : nullptr;
+        return t >= 0 ? ptr(t) : nullptr;
     };
     for (int i = 0; i < L; i++) {
         const LAYER &a = ll[i];
@@ -522,51 +368,42 @@ static int plan(ffgpu_exec *ex)
         bool from_input = false;
         switch (a.type) {
         case LAYER_TYPE_CONV: {
-            if (canon[i] == -3) break;                              // expanded tensors of a fused block
-            if (irb_tail[i] >= 0) {
-                const int p0 = irb_tail[i];
-                const LAYER &la = ll[p0], &lb = ll[p0 + 1], &lc = ll[p0 + 2];
+            if (nl.canon[i] == -3) break;                           // expanded tensors of a fused block
+            if (nl.irb_tail[i] >= 0) {
+                const int p0 = nl.irb_tail[i];
                 IrbDesc &d = st.irb = irb_planned[i];
                 st.kind = S_IRB;
-                d.in = tensor_ptr(ex, src_tensor(p0 - 1));
-                d.out = tensor_ptr(ex, canon[i]);
-                d.w1 = ex->dev->d_weights + (la.filter - net->weight_buf);
-                d.wd = ex->dev->d_weights + (lb.filter - net->weight_buf);
-                d.w2 = ex->dev->d_weights + (lc.filter - net->weight_buf);
-                if (fused_into[i] >= 0) d.residual = tensor_ptr(ex, src_tensor(ll[fused_into[i]].depend_list[0]));
-                S.push_back(st);
-                break;
-            }
-            if (dwpw_tail[i] >= 0) {                                // depthwise (p0) + this pointwise layer: one launch
-                const int p0 = dwpw_tail[i];
+                d.in = ptr(nl.src(p0 - 1));
+                d.out = ptr(nl.canon[i]);
+                d.w1 = weights(p0); d.wd = weights(p0 + 1); d.w2 = weights(p0 + 2);
+                if (nl.fused_into[i] >= 0) d.residual = ptr(nl.src(ll[nl.fused_into[i]].depend_list[0]));
+            } else if (nl.dwpw_tail[i] >= 0) {                      // depthwise (p0) + this pointwise layer: one launch
+                const int p0 = nl.dwpw_tail[i];
                 st.kind = S_DWPW;
-                st.conv = layer_desc(p0); st.conv2 = layer_desc(i);
-                st.conv.in = tensor_ptr(ex, src_tensor(p0 - 1));
-                st.conv.filt = ex->dev->d_weights + (ll[p0].filter - net->weight_buf);
-                st.conv2.filt = ex->dev->d_weights + (a.filter - net->weight_buf);
-                st.conv2.out = tensor_ptr(ex, canon[i]);
-                S.push_back(st);
-                break;
-            }
-            ConvDesc &d = st.conv = layer_desc(i, FFGPU_COMPAT_V6 | FFGPU_BF16_PW);
-            st.kind = S_CONV;
-            d.in = in_ptr(i, &from_input);
-            st.in_is_input = from_input;
-            d.filt = ex->dev->d_weights + (a.filter - net->weight_buf);
-            d.out = tensor_ptr(ex, canon[i]);
-            if (from_input) { d.in_cs = (long)a.w * a.h; d.in_ns = (long)a.c * a.w * a.h; }     // frame-major batch input
-            if (fused_into[i] >= 0) {
-                const LAYER &sc = ll[fused_into[i]];
-                d.residual = tensor_ptr(ex, src_tensor(sc.depend_list[0]));
-                d.res_act = sc.activation; d.res_cs = d.out_cs; d.res_ns = d.out_ns;
+                st.conv = layer_desc(ex, p0); st.conv2 = layer_desc(ex, i);
+                st.conv.in = ptr(nl.src(p0 - 1));
+                st.conv.filt = weights(p0); st.conv2.filt = weights(i);
+                st.conv2.out = ptr(nl.canon[i]);
+            } else {
+                ConvDesc &d = st.conv = layer_desc(ex, i, FFGPU_COMPAT_V6 | FFGPU_BF16_PW);
+                st.kind = S_CONV;
+                d.in = in_ptr(i, &st.in_is_input);
+                d.filt = weights(i);
+                d.out = ptr(nl.canon[i]);
+                if (st.in_is_input) { d.in_cs = (long)a.w * a.h; d.in_ns = (long)a.c * a.w * a.h; }     // frame-major batch input
+                if (nl.fused_into[i] >= 0) {
+                    const LAYER &sc = ll[nl.fused_into[i]];
+                    d.residual = ptr(nl.src(sc.depend_list[0]));
+                    d.res_act = sc.activation; d.res_cs = d.out_cs; d.res_ns = d.out_ns;
+                }
             }
             S.push_back(st);
             break; }
         case LAYER_TYPE_AVGPOOL: case LAYER_TYPE_MAXPOOL: case LAYER_TYPE_UPSAMPLE: case LAYER_TYPE_SHORTCUT: {
             const float *src = in_ptr(i, &from_input);
             // a shortcut whose OTHER side is the net input (from = a dropout in front of every other layer)
-            const bool b_input = a.type == LAYER_TYPE_SHORTCUT && src_tensor(a.depend_list[0]) == -1;
-            if (a.type == LAYER_TYPE_SHORTCUT && src_tensor(a.depend_list[0]) < -1) { bad_chain = true; break; }
+            const bool b_input = a.type == LAYER_TYPE_SHORTCUT && nl.src(a.depend_list[0]) == -1;
+            if (a.type == LAYER_TYPE_SHORTCUT && nl.src(a.depend_list[0]) < -1) { bad_chain = true; break; }
             if ((from_input || b_input) && N > 1) {          // needs CNHW order: convert the input once
                 if (!cnhw_input) {
                     const LAYER &l0 = ll[0];
@@ -579,31 +416,31 @@ static int plan(ffgpu_exec *ex)
             st.in_is_input = from_input;
             st.a = src;
             if (a.type == LAYER_TYPE_SHORTCUT) {
-                if (canon[i - 1] == i) break;                       // absorbed by the producing conv
+                if (nl.canon[i - 1] == i) break;                    // absorbed by the producing conv
                 st.kind = S_ADD;
-                st.b = b_input ? cnhw_input : tensor_ptr(ex, src_tensor(a.depend_list[0]));      // (batch 1: patched to the frames at launch)
+                st.b = b_input ? cnhw_input : ptr(nl.src(a.depend_list[0]));      // (batch 1: patched to the frames at launch)
                 st.b_is_input = b_input && N == 1;
-                st.out = tensor_ptr(ex, canon[i]);
-                st.n = out_floats(i); st.flag = a.activation;
+                st.out = ptr(nl.canon[i]);
+                st.n = (long)ll[i + 1].w * ll[i + 1].h * ll[i + 1].c * N; st.flag = a.activation;
             } else {
                 st.kind = a.type == LAYER_TYPE_UPSAMPLE ? S_UPSAMPLE : S_POOL;
-                st.out = tensor_ptr(ex, canon[i]);
+                st.out = ptr(nl.canon[i]);
                 st.c = a.c; st.w = a.w; st.h = a.h; st.fs = a.fs; st.stride = a.stride;
                 st.flag = a.type == LAYER_TYPE_MAXPOOL;
             }
             S.push_back(st);
             break; }
         case LAYER_TYPE_ROUTE: {
-            if (canon[i] != i || route_inplace[i]) break;           // alias / concat in place
+            if (nl.canon[i] != i || nl.route_inplace[i]) break;     // alias / concat in place
             long off = 0;
             for (int k = 0; k < a.depend_num; k++) {
-                const int t = src_tensor(a.depend_list[k]);
+                const int t = nl.src(a.depend_list[k]);
                 if (t < 0) { ffgpu_set_error("route %d: unsupported source", i); return -1; }
-                const long cnt = (long)ll[a.depend_list[k] + 1].w * ll[a.depend_list[k] + 1].h * ll[a.depend_list[k] + 1].c * N;
+                const LAYER &o = ll[a.depend_list[k] + 1];
                 Step cp{}; cp.kind = S_COPY; cp.layer = i; cp.ltype = a.type;
-                cp.a = tensor_ptr(ex, t); cp.out = tensor_ptr(ex, i) + off; cp.n = cnt;
+                cp.a = ptr(t); cp.out = ptr(i) + off; cp.n = (long)o.w * o.h * o.c * N;
                 S.push_back(cp);
-                off += cnt;
+                off += cp.n;
             }
             break; }
         case LAYER_TYPE_YOLO: {
@@ -615,81 +452,117 @@ static int plan(ffgpu_exec *ex)
             memcpy(hd.anchors, a.anchor_list, sizeof hd.anchors);
             hd.thresh = a.ignore_thres; hd.scale_xy = a.scale_x_y; hd.key_base = key_base;
             key_base += a.w * a.h * 3;
-            nheads++;
             S.push_back(st);
             break; }
         default: break;                                             // dropout
         }
     }
-    // first layer + the thin block behind it -> one streaming kernel (ffgpu_front.inc): the 8-channel tensor between them
-    // is never written (its arena space stays reserved; read_layer refuses it like the inside of a fused block)
-    if (fuse) {
-        for (size_t k = 0; k + 1 < S.size(); k++) {
-            Step &c0 = S[k];
-            const Step &b0 = S[k + 1];
-            if (c0.kind != S_CONV || b0.kind != S_IRB || c0.layer < 0 || nuses[c0.layer] != 1) continue;
-            if (!ffgpu_front_ok(c0.conv, b0.irb)) continue;
-            c0.kind = S_FRONT; c0.irb = b0.irb;
-            ex->readable[c0.layer] = 0;
-            S.erase(S.begin() + k + 1);
-            break;
-        }
-    }
-    {   // constants of the fused blocks, packed once into their LDS image
-        size_t tot = 0;
-        for (Step &st : S) {
-            if (st.kind == S_IRB) tot += ffgpu_irb_pack_floats(st.irb);
-            if (st.kind == S_CONV) {                              // kernel choice, split-K and k_conv_x3's MT frozen with the plan
-                if (st.in_is_input) st.conv.flags |= FFGPU_F_BATCH_INPUT;
-                ffgpu_conv_plan(st.conv);
-                tot += ffgpu_pw_pack_floats(st.conv);
-            }
-            if (st.kind == S_DWPW) tot += ffgpu_dwpw_pack_floats(st.conv, st.conv2);
-        }
-        if (tot) {
-            if (hipMalloc(&ex->d_pack, tot * sizeof(float)) != hipSuccess) { ffgpu_set_error("hipMalloc(pack) failed"); return -1; }
-            size_t off = 0;
-            for (Step &st : S) {
-                if (st.kind == S_IRB) { st.irb.pk = ex->d_pack + off; off += ffgpu_irb_pack_floats(st.irb); }
-                if (st.kind == S_DWPW) { st.conv2.wpack = ex->d_pack + off; off += ffgpu_dwpw_pack_floats(st.conv, st.conv2); }
-                if (st.kind == S_CONV && ffgpu_pw_pack_floats(st.conv)) { st.conv.wpack = ex->d_pack + off; off += ffgpu_pw_pack_floats(st.conv); }
-            }
-        }
-    }
     if (bad_chain) { ffgpu_set_error("a layer consumes the (non-existent) output of a yolo head"); return -1; }
-    // stride-1 max pools of one tensor that follow each other (the routes between them are aliases: an SPP block)
-    // become one launch
-    if (fuse) {
-        for (size_t i = 0; i + 1 < S.size(); i++) {
-            Step &a = S[i];
-            if (a.kind != S_POOL || !a.flag || a.stride != 1 || a.in_is_input || (long)a.w * a.h > 8192) continue;
-            int k = 0;
-            while (k < 2 && i + 1 < S.size()) {
-                const Step &b = S[i + 1];
-                if (b.kind != S_POOL || !b.flag || b.stride != 1 || b.in_is_input || b.a != a.a || b.c != a.c || b.w != a.w || b.h != a.h) break;
-                a.out2[k] = b.out; a.fs2[k] = b.fs; k++;
-                S.erase(S.begin() + i + 1);
-            }
+    return 0;
+}
+
+// stage 4: the rewrites of the step list
+// first layer + the thin block behind it -> one streaming kernel (ffgpu_front.inc): the 8-channel tensor between them
+// is never written (its arena space stays reserved; read_layer refuses it like the inside of a fused block)
+static void fuse_front(ffgpu_exec *ex)
+{
+    std::vector<Step> &S = ex->steps;
+    for (size_t k = 0; k + 1 < S.size(); k++) {
+        Step &c0 = S[k];
+        const Step &b0 = S[k + 1];
+        if (c0.kind != S_CONV || b0.kind != S_IRB || c0.layer < 0 || ex->layout.nuses[c0.layer] != 1) continue;
+        if (!ffgpu_front_ok(c0.conv, b0.irb)) continue;
+        c0.kind = S_FRONT; c0.irb = b0.irb;
+        ex->layout.readable[c0.layer] = 0;
+        S.erase(S.begin() + k + 1);
+        break;
+    }
+}
+
+// stride-1 max pools of one tensor that follow each other (the routes between them are aliases: an SPP block) become one launch
+static void merge_spp(std::vector<Step> &S)
+{
+    for (size_t i = 0; i + 1 < S.size(); i++) {
+        Step &a = S[i];
+        if (a.kind != S_POOL || !a.flag || a.stride != 1 || a.in_is_input || (long)a.w * a.h > 8192) continue;
+        int k = 0;
+        while (k < 2 && i + 1 < S.size()) {
+            const Step &b = S[i + 1];
+            if (b.kind != S_POOL || !b.flag || b.stride != 1 || b.in_is_input || b.a != a.a || b.c != a.c || b.w != a.w || b.h != a.h) break;
+            a.out2[k] = b.out; a.fs2[k] = b.fs; k++;
+            S.erase(S.begin() + i + 1);
         }
     }
+}
+
+static void rewrite_steps(ffgpu_exec *ex)
+{
+    std::vector<Step> &S = ex->steps;
+    const bool fuse = !(ex->flags & FFGPU_NO_FUSE);
+    if (fuse) { fuse_front(ex); merge_spp(S); }
     // with a detection head in the net no clear launch is needed: k_nms zeroes the candidate counters it has consumed
     // (they start zeroed) and the first head counts the forward for the record ring
-    if (nheads > 0 && fuse) {
+    const auto head = std::find_if(S.begin(), S.end(), [](const Step &t) { return t.kind == S_YOLO; });
+    if (head != S.end() && fuse) {
+        head->flag = 1;
         S.erase(std::remove_if(S.begin(), S.end(), [](const Step &t) { return t.kind == S_CLEAR; }), S.end());
-        for (Step &t : S) if (t.kind == S_YOLO) { t.flag = 1; break; }
     }
     { Step nm{}; nm.kind = S_NMS; nm.layer = -1; nm.ltype = LAYER_TYPE_YOLO; S.push_back(nm); }
-    for (Step &st : S) st.lane = (ex->side_lo >= 0 && st.layer >= ex->side_lo && st.layer <= ex->side_hi) ? 1 : 0;
-    // launches that read the batch input take its address from the parameter block when their kernel can (the first conv
-    // of every darknet cfg: dense KxK from 3 channels): the captured graph is then independent of the input buffer
-    ex->indirect = true;
-    for (const Step &st : S)
+    const NetLayout &nl = ex->layout;
+    for (Step &st : S) st.lane = (nl.side_lo >= 0 && st.layer >= nl.side_lo && st.layer <= nl.side_hi) ? 1 : 0;
+}
+
+// stage 5: kernel choice frozen with the plan, and the constants of the fused blocks and packed pointwise layers placed in one image (repack fills it)
+static size_t pack_floats(const Step &st)
+{
+    if (st.kind == S_IRB) return ffgpu_irb_pack_floats(st.irb);
+    if (st.kind == S_DWPW) return ffgpu_dwpw_pack_floats(st.conv, st.conv2);
+    if (st.kind == S_CONV) return ffgpu_pw_pack_floats(st.conv);
+    return 0;
+}
+
+static int place_constants(ffgpu_exec *ex)
+{
+    size_t tot = 0;
+    for (Step &st : ex->steps) {
+        if (st.kind == S_CONV) {                              // kernel choice, split-K and k_conv_x3's MT
+            if (st.in_is_input) st.conv.flags |= FFGPU_F_BATCH_INPUT;
+            ffgpu_conv_plan(st.conv);
+        }
+        tot += pack_floats(st);
+    }
+    if (!tot) return 0;
+    if (hipMalloc(&ex->d_pack, tot * sizeof(float)) != hipSuccess) { ffgpu_set_error("hipMalloc(pack) failed"); return -1; }
+    size_t off = 0;
+    for (Step &st : ex->steps) {
+        const size_t n = pack_floats(st);
+        if (st.kind == S_IRB) st.irb.pk = ex->d_pack + off;
+        else if (st.kind == S_DWPW) st.conv2.wpack = ex->d_pack + off;
+        else if (st.kind == S_CONV && n) st.conv.wpack = ex->d_pack + off;
+        off += n;
+    }
+    return 0;
+}
+
+// stage 6: launches that read the batch input take its address from the parameter block when their kernel can (the first conv
+// of every darknet cfg: dense KxK from 3 channels): the captured graph is then independent of the input buffer
+static void decide_indirect(ffgpu_exec *ex)
+{
+    ex->indirect = !env_on("FFGPU_NO_INDIRECT");             // tests: the keyed fallback
+    for (const Step &st : ex->steps)
         if (st.b_is_input || (st.in_is_input && !(st.kind == S_FRONT || (st.kind == S_CONV && ffgpu_conv_supports_ind(st.conv))))) ex->indirect = false;
-    if (getenv("FFGPU_NO_INDIRECT") && atoi(getenv("FFGPU_NO_INDIRECT"))) ex->indirect = false;      // tests: the keyed fallback
     if (ex->indirect)
-        for (Step &st : S) if (st.in_is_input) st.conv.in_ind = reinterpret_cast<const float *const *>(ex->d_prm);   // &d_prm->frames
-    ex->kernel_count = (int)S.size();
-    (void)nheads;
+        for (Step &st : ex->steps) if (st.in_is_input) st.conv.in_ind = reinterpret_cast<const float *const *>(ex->d_prm);   // &d_prm->frames
+}
+
+static int plan(ffgpu_exec *ex)
+{
+    std::vector<IrbDesc> irb_planned;
+    if (plan_layout(ex, irb_planned) || plan_arena(ex) || plan_steps(ex, irb_planned)) return -1;
+    rewrite_steps(ex);
+    if (place_constants(ex)) return -1;
+    decide_indirect(ex);
+    ex->kernel_count = (int)ex->steps.size();
     return 0;
 }
 
@@ -1025,7 +898,7 @@ static ffgpu_exec *exec_create_on(ffgpu_netdev *dev, NET *net, int batch, int fl
             ch->h_dets_dev = ex->h_dets_dev ? ex->h_dets_dev + (size_t)c * (batch / K) : nullptr;
             ex->child[c] = ch; ex->nchild = c + 1;
             ex->kernel_count += ch->kernel_count;
-            ex->arena_floats += ch->arena_floats;
+            ex->layout.arena_floats += ch->layout.arena_floats;
             if (c && (hipStreamCreateWithFlags(&ex->part_stream[c], hipStreamNonBlocking) != hipSuccess ||
                       hipEventCreateWithFlags(&ex->part_ev[c], hipEventDisableTiming) != hipSuccess)) {
                 ffgpu_set_error("split executor: stream / event creation failed"); ffgpu_exec_destroy(ex); return nullptr; }
@@ -1079,7 +952,7 @@ extern "C" void ffgpu_exec_destroy(ffgpu_exec *ex)
 }
 
 extern "C" int ffgpu_exec_batch(const ffgpu_exec *ex) { return ex ? ex->N : 0; }
-extern "C" size_t ffgpu_exec_arena_bytes(const ffgpu_exec *ex) { return ex ? ex->arena_floats * sizeof(float) : 0; }
+extern "C" size_t ffgpu_exec_arena_bytes(const ffgpu_exec *ex) { return ex ? ex->layout.arena_floats * sizeof(float) : 0; }
 extern "C" int ffgpu_exec_kernel_count(const ffgpu_exec *ex) { return ex ? ex->kernel_count : 0; }
 
 // What one forward of this plan MUST move and compute: per launch the tensors it reads and writes once each (input,
@@ -1526,9 +1399,9 @@ static int feature_tensor(const ffgpu_exec *ex, const char *what, const ffgpu_fe
         ffgpu_set_error("%s: layer %d is a [yolo] layer: it leaves no tensor (its product is the detection records)", what, layer);
         return -1;
     }
-    const int t = pl->canon[layer];
+    const int t = pl->layout.canon[layer];
     if (t == -1) { ffgpu_set_error("%s: layer %d is an alias of the net input, which is frame-major: no CNHW tensor", what, layer); return -1; }
-    if (t < 0 || !pl->readable[layer]) { ffgpu_set_error("%s: layer %d is not materialised by this executor (fused away or no tensor)", what, layer); return -1; }
+    if (t < 0 || !pl->layout.readable[layer]) { ffgpu_set_error("%s: layer %d is not materialised by this executor (fused away or no tensor)", what, layer); return -1; }
     const LAYER &o = ex->net->layer_list[layer + 1];
     *c = o.c; *h = o.h; *w = o.w;
     return t;
@@ -1596,9 +1469,9 @@ extern "C" int ffgpu_exec_hash_layers(ffgpu_exec *ex, unsigned long long *host_o
     int rc = 0, nh = 0;
     if (hipMemsetAsync(d, 0, sizeof(unsigned long long) * L, s) != hipSuccess) rc = -1;
     for (int i = 0; i < L && !rc; i++) {
-        if (ex->canon[i] < 0 || !ex->readable[i]) continue;
+        if (ex->layout.canon[i] < 0 || !ex->layout.readable[i]) continue;
         const LAYER &o = ex->net->layer_list[i + 1];
-        if (ffgpu_launch_hash64(tensor_ptr(ex, ex->canon[i]), (long)o.c * ex->N * o.w * o.h, d + i, s)) rc = -1;
+        if (ffgpu_launch_hash64(tensor_ptr(ex, ex->layout.canon[i]), (long)o.c * ex->N * o.w * o.h, d + i, s)) rc = -1;
         nh++;
     }
     if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = -1;
@@ -1639,14 +1512,14 @@ extern "C" int ffgpu_exec_read_layer(ffgpu_exec *ex, int layer, int frame, float
         return (int)fl;
     }
     if (!(ex->flags & FFGPU_KEEP_ALL)) { ffgpu_set_error("read_layer needs an FFGPU_KEEP_ALL executor"); return -1; }
-    if (layer < 0 || layer >= ex->net->layer_num || ex->canon[layer] < 0 || !ex->readable[layer]) {
+    if (layer < 0 || layer >= ex->net->layer_num || ex->layout.canon[layer] < 0 || !ex->layout.readable[layer]) {
         ffgpu_set_error("read_layer: layer %d is not materialised by this executor (fused away or no tensor)", layer);
         return -1;
     }
     const LAYER &o = ex->net->layer_list[layer + 1];
     const size_t plane = (size_t)o.w * o.h;
     if (plane * o.c > cap_floats) { ffgpu_set_error("read_layer: buffer too small"); return -1; }
-    const float *src = tensor_ptr(ex, ex->canon[layer]) + (size_t)frame * plane;
+    const float *src = tensor_ptr(ex, ex->layout.canon[layer]) + (size_t)frame * plane;
     {   // the frame's planes (one per channel, N planes apart in CNHW) gathered into the bounce buffer, then into caller memory
         const size_t row = plane * sizeof(float), per = std::max<size_t>(1, BOUNCE_BYTES / row);
         if (row > BOUNCE_BYTES) {                                  // a plane larger than the staging buffer (> 2048 x 2048 floats): contiguous, chunked plane by plane
@@ -1667,32 +1540,52 @@ extern "C" int ffgpu_exec_read_layer(ffgpu_exec *ex, int layer, int frame, float
     return (int)(plane * o.c);
 }
 
+// The steps of one forward timed one by one on the executor's own stream: a warm-up pass, then `reps` passes with an event behind every step;
+// us[i] = mean time of step i.  The events are destroyed on every path.
+static int timed_issue(ffgpu_exec *ex, const float *d_frames, int reps, std::vector<float> &us)
+{
+    hipStream_t s = ex->own_stream;
+    const InputSrc in = fp32_src(d_frames);
+    if (push_params(ex, in, s)) return -1;
+    const size_t n = ex->steps.size();
+    std::vector<hipEvent_t> ev(n + 1, nullptr);
+    us.assign(n, 0.f);
+    auto run = [&]() -> int {
+        for (auto &e : ev) FFGPU_CHECK(hipEventCreate(&e));
+        if (issue_all(ex, in, s)) return -1;                    // warm
+        for (int r = 0; r < reps; r++) {
+            FFGPU_CHECK(hipEventRecord(ev[0], s));
+            for (size_t i = 0; i < n; i++) {
+                if (issue_step(ex, ex->steps[i], in, s)) return -1;
+                FFGPU_CHECK(hipEventRecord(ev[i + 1], s));
+            }
+            FFGPU_CHECK(hipStreamSynchronize(s));
+            for (size_t i = 0; i < n; i++) {
+                float ms = 0.f;
+                FFGPU_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+                us[i] += ms * 1000.f / reps;
+            }
+        }
+        return 0;
+    };
+    const int rc = run();
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    if (!rc) ex->last_stream = s;
+    return rc;
+}
+
 extern "C" int ffgpu_exec_profile(ffgpu_exec *ex, const float *d_frames, float us_by_kind[LAYER_TYPE_TOTOAL])
 {
     if (!alive(ex, "profile")) return -1;
     if (!d_frames || !us_by_kind) { ffgpu_set_error("profile: NULL argument"); return -1; }
     if (ex->child[0]) { ffgpu_set_error("profile: not available on a split executor"); return -1; }
-    hipStream_t s = ex->own_stream;
-    const InputSrc in = fp32_src(d_frames);
-    if (push_params(ex, in, s)) return -1;
-    std::vector<hipEvent_t> ev(ex->steps.size() + 1);
-    for (auto &e : ev) FFGPU_CHECK(hipEventCreate(&e));
-    if (issue_all(ex, in, s)) return -1;                    // warm
-    FFGPU_CHECK(hipEventRecord(ev[0], s));
-    for (size_t i = 0; i < ex->steps.size(); i++) {
-        if (issue_step(ex, ex->steps[i], in, s)) return -1;
-        FFGPU_CHECK(hipEventRecord(ev[i + 1], s));
-    }
-    FFGPU_CHECK(hipStreamSynchronize(s));
+    std::vector<float> us;
+    if (timed_issue(ex, d_frames, 1, us)) return -1;
     for (int k = 0; k < LAYER_TYPE_TOTOAL; k++) us_by_kind[k] = 0.f;
-    for (size_t i = 0; i < ex->steps.size(); i++) {
-        float ms = 0.f;
-        FFGPU_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+    for (size_t i = 0; i < us.size(); i++) {
         const int k = ex->steps[i].ltype;
-        if (k >= 0 && k < LAYER_TYPE_TOTOAL) us_by_kind[k] += ms * 1000.f;
+        if (k >= 0 && k < LAYER_TYPE_TOTOAL) us_by_kind[k] += us[i];
     }
-    for (auto &e : ev) (void)hipEventDestroy(e);
-    ex->last_stream = s;
     return 0;
 }
 
@@ -1701,31 +1594,10 @@ extern "C" int ffgpu_exec_profile_steps(ffgpu_exec *ex, const float *d_frames, i
     if (!alive(ex, "profile_steps")) return -1;
     if (!d_frames || !layer_of || !us) { ffgpu_set_error("profile_steps: NULL argument"); return -1; }
     if (ex->child[0]) { ffgpu_set_error("profile_steps: not available on a split executor"); return -1; }
-    hipStream_t s = ex->own_stream;
-    const InputSrc in = fp32_src(d_frames);
-    if (push_params(ex, in, s)) return -1;
-    const int n = (int)std::min<size_t>(ex->steps.size(), (size_t)cap);
-    std::vector<hipEvent_t> ev(ex->steps.size() + 1);
-    for (auto &e : ev) FFGPU_CHECK(hipEventCreate(&e));
-    std::vector<float> acc(ex->steps.size(), 0.f);
-    const int reps = 5;
-    if (issue_all(ex, in, s)) return -1;
-    for (int r = 0; r < reps; r++) {
-        FFGPU_CHECK(hipEventRecord(ev[0], s));
-        for (size_t i = 0; i < ex->steps.size(); i++) {
-            if (issue_step(ex, ex->steps[i], in, s)) return -1;
-            FFGPU_CHECK(hipEventRecord(ev[i + 1], s));
-        }
-        FFGPU_CHECK(hipStreamSynchronize(s));
-        for (size_t i = 0; i < ex->steps.size(); i++) {
-            float ms = 0.f;
-            FFGPU_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-            acc[i] += ms * 1000.f / reps;
-        }
-    }
+    std::vector<float> acc;
+    if (timed_issue(ex, d_frames, 5, acc)) return -1;
+    const int n = (int)std::min<size_t>(acc.size(), (size_t)cap);
     for (int i = 0; i < n; i++) { layer_of[i] = ex->steps[i].layer; us[i] = acc[i]; }
-    for (auto &e : ev) (void)hipEventDestroy(e);
-    ex->last_stream = s;
     return n;
 }
 

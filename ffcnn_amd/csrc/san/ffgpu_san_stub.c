@@ -6,9 +6,10 @@
  * own latent UB: ffcnn.c:478-479, 261-264).
  *
  * FFSAN_NODEV=1: ffgpu_netdev_create fails (net_load's error path: net_free of a half-built net).
- * Otherwise a dummy handle is returned, so net_load hands the parsed NET to the caller; the stub walks every LAYER the way the
- * planner's first pass does (dependency indices, filter rows inside weight_buf) so out-of-range results of the parser are
- * touched -- and caught -- here.
+ * Otherwise a dummy handle is returned, so net_load hands the parsed NET to the caller; the stub touches what the device side reads
+ * of it before any kernel exists (dependency indices, filter rows inside weight_buf) so out-of-range results of the parser are
+ * caught here.  The planner's real first pass -- ffgpu_layout_aliases and the rest of ffgpu_plan.hpp -- runs on that NET under the
+ * same sanitizers in san/plan_driver.cc (make plan).
  */
 #include <stdarg.h>
 #include <stdio.h>

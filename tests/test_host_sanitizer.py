@@ -114,8 +114,8 @@ def test_hostile_cfgs(san, tmp_path, name):
     assert "net_load:" in out
 
 
-def test_seeded_mutations_of_the_real_cfg(san, tmp_path):
-    """Byte- and line-level damage to yolo-fastest-1.1.cfg: numbers replaced by extremes, lines dropped / doubled / cut."""
+def mutated_cfgs():
+    """Byte- and line-level damage to yolo-fastest-1.1.cfg: numbers replaced by extremes, lines dropped / doubled / cut; the 40 texts, seeded."""
     rng = np.random.default_rng(606)
     lines = open(YCFG).read().splitlines()
     extremes = ["0", "-1", "2147483647", "-2147483648", "99999999999999999999", "1e9", "", "-", "7,7,7,7,7,7,7,7,7,7,7,7", "x"]
@@ -134,6 +134,11 @@ def test_seeded_mutations_of_the_real_cfg(san, tmp_path):
                 ls[i] = ls[i][:int(rng.integers(0, len(ls[i]) + 1))]
             else:
                 ls[i] = re.sub(r"-?\d+", lambda m: extremes[int(rng.integers(0, 5))], ls[i])
+        yield "\n".join(ls) + "\n"
+
+
+def test_seeded_mutations_of_the_real_cfg(san, tmp_path):
+    for it, text in enumerate(mutated_cfgs()):
         p = str(tmp_path / "m.cfg")
-        open(p, "w").write("\n".join(ls) + "\n")
+        open(p, "w").write(text)
         assert "net_load:" in san(p, YW), "mutation %d" % it
