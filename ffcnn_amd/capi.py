@@ -108,6 +108,10 @@ class RelabelSpec(C.Structure):      # ffgpu_relabel_spec (16 bytes): which labe
     _fields_ = [("min_value", C.c_float), ("type_base", C.c_int), ("score_mode", C.c_int), ("reserved", C.c_int)]
 
 
+class Gallery(C.Structure):          # ffgpu_gallery (40 bytes): a host struct of device pointers
+    _fields_ = [("d_rows", C.c_void_p), ("d_ids", C.c_void_p), ("d_head", C.c_void_p), ("row_stride", C.c_long), ("capacity", C.c_int), ("d", C.c_int)]
+
+
 TRACK_DETS = 128                                                                       # FFGPU_TRACK_DETS
 TRACK_ENTRIES, TRACK_MERGED = 0, 1                                                     # FFGPU_TRACK_* (ffgpu_exec_track: which)
 TRACK_IDS_HEADER = ("considered", "matched", "born", "refused", "dropped", "freed", "live", "frame")   # the 8 ints in front of a row of ids
@@ -122,6 +126,7 @@ assert C.sizeof(BgrFrame) == 24 and C.sizeof(Nv12Frame) == 40 and C.sizeof(Tile)
 assert C.sizeof(DrawStyle) == 24 and C.sizeof(CropSpec) == 72 and C.sizeof(Crop) == 48
 assert C.sizeof(TrackSpec) == 32 and C.sizeof(Track) == 48
 assert C.sizeof(FeatureSpec) == 16 and C.sizeof(Label) == 8 and C.sizeof(RelabelSpec) == 16
+assert C.sizeof(Gallery) == 40
 
 BOX_DTYPE = np.dtype([("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
 DETS_DTYPE = np.dtype([("count", "<i4"), ("ncand", "<i4"), ("overflow", "<i4"), ("nfull", "<i4"),
@@ -151,7 +156,8 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_crops_to_source_dev",
            "ffgpu_track_state_bytes", "ffgpu_track_reset_dev", "ffgpu_track_boxes_dev", "ffgpu_exec_track",
            "ffgpu_feature_dim", "ffgpu_exec_feature_dim", "ffgpu_features_dev", "ffgpu_exec_features", "ffgpu_topk_dev", "ffgpu_crops_relabel_dev",
-           "ffgpu_exec_relabel"]
+           "ffgpu_exec_relabel",
+           "ffgpu_match_workspace_bytes", "ffgpu_match_dev", "ffgpu_gallery_enroll_dev"]
 # include/ffcnn_hip_diag.h (libffcnn_hip_diag.so: lab equipment, its own library)
 DIAG_EXPORTS = ["ffgpu_membench", "ffgpu_pipe_probe", "ffgpu_pipe_probe2", "ffgpu_pipe_probe3", "ffgpu_mfma_floor", "ffgpu_diag_x3_term", "ffgpu_diag_xl_op", "ffgpu_clock_probe"]
 
@@ -296,6 +302,10 @@ def lib():
     L.ffgpu_topk_dev.argtypes = [vp, i, i, C.c_long, i, vp, vp]
     L.ffgpu_crops_relabel_dev.argtypes = [vp, i, vp, i, vp, vp, i, C.POINTER(i), i, C.POINTER(RelabelSpec), vp, vp, vp]
     L.ffgpu_exec_relabel.argtypes = [vp, i, vp, i, vp, i, i, C.POINTER(RelabelSpec), vp, vp, vp]
+    L.ffgpu_match_workspace_bytes.restype = sz
+    L.ffgpu_match_workspace_bytes.argtypes = [i, i, i]
+    L.ffgpu_match_dev.argtypes = [vp, i, C.c_long, C.POINTER(Gallery), i, vp, vp, C.c_long, vp, sz, vp]
+    L.ffgpu_gallery_enroll_dev.argtypes = [C.POINTER(Gallery), vp, i, C.c_long, vp, i, C.c_float, vp, vp]
     _lib = L
     return L
 
@@ -901,8 +911,32 @@ def crops_relabel_dev(d_table, capacity, d_labels, k, d_records, d_lists, list_s
                                          stream), "ffgpu_crops_relabel_dev")
 
 
+def gallery(d_rows, capacity, d, d_ids=None, d_head=None, row_stride=None):
+    """a Gallery (ffgpu_gallery): capacity rows of d floats at d_rows, row_stride floats apart (default d); d_ids / d_head as the header says"""
+    return Gallery(d_rows, d_ids, d_head, d if row_stride is None else row_stride, capacity, d)
+
+
+def match_workspace_bytes(nq, capacity, k):
+    """ffgpu_match_workspace_bytes: the scratch ffgpu_match_dev needs; 0 outside the ranges (no GPU needed)"""
+    return int(lib().ffgpu_match_workspace_bytes(nq, capacity, k))
+
+
+def match_dev(d_q, nq, g, k, d_out_labels, d_work, work_bytes, d_sim=None, sim_stride=None, q_stride=None, stream=None):
+    """ffgpu_match_dev: the k best gallery rows of each of nq query rows (q_stride floats apart, default g.d) as nq x k Label at d_out_labels; d_sim:
+    the nq x capacity matrix as well, sim_stride floats apart (default capacity)"""
+    _check(lib().ffgpu_match_dev(d_q, nq, g.d if q_stride is None else q_stride, g, k, d_out_labels, d_sim, g.capacity if sim_stride is None else sim_stride,
+                                 d_work, work_bytes, stream), "ffgpu_match_dev")
+
+
+def gallery_enroll_dev(g, d_q, nq, d_labels, k, min_value, d_out_labels, q_stride=None, stream=None):
+    """ffgpu_gallery_enroll_dev: the queries whose best label (entry 0 of each row of k) does not reach min_value appended to the gallery; nq Label at
+    d_out_labels"""
+    _check(lib().ffgpu_gallery_enroll_dev(g, d_q, nq, g.d if q_stride is None else q_stride, d_labels, k, min_value, d_out_labels, stream),
+           "ffgpu_gallery_enroll_dev")
+
+
 # the operators as attributes of FFGPU as well (FFGPU.features_dev(...)), next to the constants they take
-for _f in (feature_spec, feature_dim, features_dev, topk_dev, relabel_spec, crops_relabel_dev):
+for _f in (feature_spec, feature_dim, features_dev, topk_dev, relabel_spec, crops_relabel_dev, gallery, match_workspace_bytes, match_dev, gallery_enroll_dev):
     setattr(FFGPU, _f.__name__, staticmethod(_f))
 del _f
 

@@ -739,6 +739,62 @@ int ffgpu_crops_relabel_dev(const void *d_table, int capacity, const void *d_lab
 int ffgpu_exec_relabel(ffgpu_exec *ex, int which, const void *d_table, int capacity, const void *d_labels, int k, int ntargets,
                        const ffgpu_relabel_spec *spec, void *d_out_records, void *d_out_lists, void *stream);
 
+/* ---- re-identification on the device: embeddings matched against a gallery, new ones enrolled -----------------------------------------------------
+ * Where the second stage is an embedding net its rows (ffgpu_exec_features, usually FFGPU_FEAT_MEAN + FFGPU_POST_L2) mean something only next to other
+ * rows: "which known person, vehicle or product is this?".  What follows compares query rows with a gallery of rows that lives in HBM, leaves the k best
+ * gallery rows of every query as rows of ffgpu_label -- what ffgpu_crops_relabel_dev / ffgpu_exec_relabel consume, so the identity becomes the box's
+ * type and draw, crop and track take it from there -- and appends the queries nobody recognised to the gallery, all where the data lie and with no
+ * synchronisation.  There is no executor form: the operators work on caller-owned rows, as ffgpu_topk_dev does.  No atomic is used anywhere and nothing
+ * depends on an arrival order: the same bytes on every run (tests/gallery/matchref.py restates the contract in numpy).
+ *
+ * The gallery is a HOST struct of device pointers, free again on return.  `count` is read ON THE DEVICE when the kernels run: an enrolment earlier on
+ * the same stream grows the gallery for the match behind it with no host involvement.  A count outside 0 .. capacity is clamped. */
+typedef struct {
+    float *d_rows;                  /* capacity rows of d fp32, row g at d_rows + g * row_stride (floats), row_stride >= d                      */
+    int   *d_ids;                   /* may be NULL: capacity ints; the label's index is d_ids[g] (g itself with NULL); d_ids[g] < 0: row g is disabled */
+    int   *d_head;                  /* may be NULL: 16 bytes on the device { int count, issued, dropped, reserved }; rows g >= count are not there.
+                                       NULL: count = capacity.  All-zero = the valid empty gallery (hipMemsetAsync initialises it)               */
+    long   row_stride;
+    int    capacity;                /* 1 .. 2^20                                                                                               */
+    int    d;                       /* 1 .. 4096                                                                                               */
+} ffgpu_gallery;                    /* 40 bytes: d_rows 0, d_ids 8, d_head 16, row_stride 24, capacity 32, d 36                                */
+
+/* Match.  Queries: nq rows of g->d fp32, row q at d_q + q * q_stride (q_stride >= d).
+ *  1. sim(q, g) is the dot product of query row q and gallery row g, in fp32.  The summation order is the implementation's; it is a FIXED order,
+ *     independent of q, nq, g, capacity, count, the strides and every alignment: a pair of rows gives the same bits wherever it stands.
+ *  2. A row behind count, or a disabled row, has sim = 0x7fc00000.
+ *  3. Row q of d_out_labels holds k entries ffgpu_label (row q at byte 8 k q): the gallery rows in this total order: sim descending, as fp32 values
+ *     compare; then gallery row g ascending -- ffgpu_topk_dev's order; NaN is never selected.  Missing entries are { -1, 0.0f }.  index is d_ids[g],
+ *     or g when d_ids is NULL -- applied after the selection, so rows of one identity each take an entry; value is sim(q, g).
+ *  4. d_sim may be NULL.  Otherwise element (q, g) for every g < capacity is written at d_sim + q * sim_stride + g, sim_stride >= capacity, and
+ *     nothing else is written.  The labels are the same bytes with and without d_sim.
+ *  5. Every byte of d_out_labels is written.
+ *  6. nq is 1..4096, k is 1..FFGPU_TOPK_MAX.  Pointers need only 4-byte alignment (d_head: 16); wider loads are used only where the address permits,
+ *     with the same bits either way.
+ *  7. d_work is the caller's scratch of at least ffgpu_match_workspace_bytes(nq, capacity, k) bytes, free again when the call's work has run.
+ * No synchronisation; everything is enqueued on `stream`.  At most two launches per call.  Rejected before anything is launched, each with its own
+ * message: a NULL query, gallery, d_rows, labels or workspace; nq, k, capacity or d outside their ranges; q_stride or row_stride < d; sim_stride <
+ * capacity; work_bytes below ffgpu_match_workspace_bytes; a pointer that is not 4-byte aligned; a d_head that is not 16-byte aligned.  A rejected call
+ * launches nothing and leaves everything usable. */
+size_t ffgpu_match_workspace_bytes(int nq, int capacity, int k);   /* pure host code; 0 for arguments outside their ranges */
+int ffgpu_match_dev(const float *d_q, int nq, long q_stride, const ffgpu_gallery *g, int k, void *d_out_labels, float *d_sim, long sim_stride,
+                    void *d_work, size_t work_bytes, void *stream);
+
+/* Enrol: open-set re-identification with no host round trip -- whoever was not recognised becomes known.  d_ids and d_head are required.  d_labels:
+ * nq rows of k ffgpu_label as ffgpu_match_dev leaves them; only entry 0 of each row is used, k is passed for the row pitch.  For the queries in
+ * ascending r (every rank is a ballot's, no order of arrival decides anything):
+ *   query r is matched when index >= 0 and value >= min_value (a NaN value never): out[r] = its label;
+ *   otherwise, if every element of the row is finite and a slot is left, it is enrolled: the e-th enrolled row of the call takes slot count + e, its d
+ *     floats are copied there bit for bit, d_ids[slot] = issued + e + 1, and out[r] = { that id, min_value } -- the same threshold passes it through
+ *     ffgpu_crops_relabel_dev;
+ *   otherwise out[r] = { -1, 0.0f } and `dropped` counts it.
+ * Afterwards count and issued have grown by the number enrolled.  d_out_labels is nq entries of 8 bytes, every byte written; it must not overlap
+ * d_labels.  Two unknown queries of one call are two identities, even if their rows are equal: a call does not match its queries against each other.
+ * Ids are positive and never reused (issued < 2^31 is the caller's business).  No synchronisation; at most two launches per call: one workgroup that
+ * decides, then a grid that copies.  Rejected like ffgpu_match_dev, and: a NULL d_ids, d_head or output, overlapping labels. */
+int ffgpu_gallery_enroll_dev(const ffgpu_gallery *g, const float *d_q, int nq, long q_stride, const void *d_labels, int k, float min_value,
+                             void *d_out_labels, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
