@@ -8,10 +8,10 @@
 // Features, launch 1 (k_feat_pool): one WAVE per plane (c, n), a contiguous run of H*W floats.  Lane l owns the quads l, l + 64, ... of the plane and
 // takes each quad's elements in ascending order; a quad is one 16-byte load where H*W % 4 == 0 and the plane's address allows it, four 4-byte loads
 // otherwise -- the order of the additions is the same either way, so the sum does not depend on the alignment.  The 64 partial results meet in a
-// butterfly of cross-lane exchanges.  MAX compares the values' bits as ordered integers (-0 below +0, exact in any order) and carries "a NaN was seen"
+// butterfly of cross-lane exchanges (wave_sum, wave_max of ffgpu_block.inc).  MAX compares the values' bits as ordered integers (-0 below +0, exact in any order) and carries "a NaN was seen"
 // beside them.  FLAT moves the quads as integers.  Launch 2 (k_feat_post, only with a `post`): one workgroup per row; the row is staged in LDS when it
 // has at most FEAT_LDS_ROW floats, else the three passes (maximum, sum, write) read it from the output row itself, which the L2 holds.  A wave reduces by
-// cross-lane exchanges, the waves' results meet in LDS and every lane adds them up in wave order.
+// cross-lane exchanges, the waves' results meet in LDS and every lane adds them up in wave order (block_sum, block_max).
 #define FEAT_LDS_ROW   8192                      // floats of a row staged in LDS (32 KB)
 #define FEAT_MAX_PARTS 8                         // == ffgpu_exec::MAXPART
 #define FEAT_QNAN      0x7fc00000u
@@ -72,7 +72,7 @@ __global__ void __launch_bounds__(256) k_feat_pool(FeatSrc src, int N, int C, in
                 acc = acc + __uint_as_float(v.z);
                 acc = acc + __uint_as_float(v.w);
             }
-            for (int o = WAVE / 2; o > 0; o >>= 1) acc = acc + __shfl_xor(acc, o);
+            acc = wave_sum(acc);
             if (lane == 0) row[c] = acc / (float)hw;
         } else {
             int best = (int)0x80000000;                                           // (below every key of a value that is no NaN)
@@ -86,36 +86,11 @@ __global__ void __launch_bounds__(256) k_feat_pool(FeatSrc src, int N, int C, in
                     best = max(best, feat_key(e[k]));
                 }
             }
-            for (int o = WAVE / 2; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o));
+            best = wave_max(best);
             const bool any_nan = __ballot(nan) != 0ull;
             if (lane == 0) reinterpret_cast<unsigned *>(row)[c] = any_nan ? FEAT_QNAN : (unsigned)feat_key((unsigned)best);
         }
     }
-}
-
-// the waves' values in LDS, then every lane combines them in wave order (red: one slot per wave; free again on return)
-__device__ __forceinline__ float feat_block_sum(float v, float *red)
-{
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE, nw = blockDim.x / WAVE;
-    for (int o = WAVE / 2; o > 0; o >>= 1) v = v + __shfl_xor(v, o);
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    float t = red[0];
-    for (int w = 1; w < nw; w++) t = t + red[w];
-    __syncthreads();
-    return t;
-}
-__device__ __forceinline__ float feat_block_max(float v, float *red)
-{
-    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE, nw = blockDim.x / WAVE;
-    for (int o = WAVE / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    float t = red[0];
-    for (int w = 1; w < nw; w++) t = fmaxf(t, red[w]);
-    __syncthreads();
-    return t;
 }
 
 // grid = rows, 1024 lanes; in place on the output rows
@@ -139,7 +114,7 @@ __global__ void __launch_bounds__(1024) k_feat_post(float *out, long out_stride,
         float m = -INFINITY;
         bool nan = false;
         for (int i = tid; i < D; i += nt) { const float x = get(i); nan = nan || x != x; m = fmaxf(m, x); }
-        m = feat_block_max(m, s_red);
+        m = block_max(m, s_red, nt / WAVE);
         const bool bad = __syncthreads_or(nan) || m == INFINITY || m == -INFINITY;
         if (bad) {                                                                 // a NaN, a +Inf, or nothing but -Inf (uniform)
             for (int i = tid; i < D; i += nt) reinterpret_cast<unsigned *>(grow)[i] = FEAT_QNAN;
@@ -147,23 +122,23 @@ __global__ void __launch_bounds__(1024) k_feat_post(float *out, long out_stride,
         }
         float sum = 0.f;
         for (int i = tid; i < D; i += nt) { const float e = expf(get(i) - m); put(i, e); sum = sum + e; }
-        sum = feat_block_sum(sum, s_red);
+        sum = block_sum(sum, s_red, nt / WAVE);
         for (int i = tid; i < D; i += nt) grow[i] = get(i) / sum;
     } else {
         float ss = 0.f;
         for (int i = tid; i < D; i += nt) { const float x = get(i); float sq = x * x; asm volatile("" : "+v"(sq)); ss = ss + sq; }
-        const float r = sqrtf(feat_block_sum(ss, s_red));
+        const float r = sqrtf(block_sum(ss, s_red, nt / WAVE));
         for (int i = tid; i < D; i += nt) grow[i] = r == 0.f ? 0.f : get(i) / r;
     }
 }
 
 // ---- top-k: grid = rows, 256 lanes.  Round r finds the first element, in the contract's total order (value descending, index ascending, no NaN),
-// that comes behind round r - 1's: k <= 16 passes over a row that the L2 holds, no sort, nothing that depends on an arrival order.
+// that comes behind round r - 1's (pair_behind, block_first_pair): k <= 16 passes over a row that the L2 holds, no sort, nothing that depends on an arrival order.
 __global__ void __launch_bounds__(256) k_topk(const float *in, long in_stride, int D, int k, int2 *out)
 {
     __shared__ float s_v[256 / WAVE];
     __shared__ int s_i[256 / WAVE];
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const int tid = threadIdx.x;
     const float *row = in + (long)blockIdx.x * in_stride;
     int2 *o = out + (long)blockIdx.x * k;
     float pv = 0.f;
@@ -175,16 +150,10 @@ __global__ void __launch_bounds__(256) k_topk(const float *in, long in_stride, i
         for (int i = tid; i < D; i += 256) {                                       // (ascending i: of equal values a lane keeps the first)
             const float v = row[i];
             if (v != v) continue;
-            if (r > 0 && !(v < pv || (v == pv && i > pi))) continue;
+            if (!pair_behind(v, i, pv, pi, r == 0)) continue;
             if (bi < 0 || v > bv) { bv = v; bi = i; }
         }
-        auto take = [&](float ov, int oi) { if (oi >= 0 && (bi < 0 || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; } };
-        for (int s = WAVE / 2; s > 0; s >>= 1) { const float ov = __shfl_xor(bv, s); const int oi = __shfl_xor(bi, s); take(ov, oi); }
-        if (lane == 0) { s_v[wave] = bv; s_i[wave] = bi; }
-        __syncthreads();
-        bv = s_v[0]; bi = s_i[0];
-        for (int w = 1; w < 256 / WAVE; w++) take(s_v[w], s_i[w]);
-        __syncthreads();
+        block_first_pair(bv, bi, s_v, s_i, 256 / WAVE);
         if (bi < 0) break;                                                         // (uniform) the row has no further value
         if (tid == 0) o[r] = make_int2(bi, __float_as_int(bv));
         pv = bv; pi = bi;

@@ -247,6 +247,8 @@ __global__ void k_copy(const float *src, float *dst, long n)
     for (long i = (n4 << 2) + gid; i < n; i += gsz) dst[i] = src[i];
 }
 
+#include "ffgpu_block.inc"
+
 // ---------------------------------------------------------------------------
 // YOLO head decode (ffcnn.c:438-474).  One thread per (frame, cell, anchor);
 // lanes run along x so the 85 strided channel reads are coalesced.  exp() is
@@ -322,7 +324,7 @@ __global__ void k_yolo(YoloHead hd, int N, int netw, int neth, BBOX *cand, int *
 // NMS (ffcnn.c:298-335): one workgroup per frame.  Candidates are ordered by
 // (score desc, emission key asc) with a bitonic sort -- the key makes the
 // order total where qsort's is unspecified -- then suppressed greedily per class
-// with inter/min(area) (or IoU) > thresh, compacted and rescaled by s1/s2.  A candidate of score exactly 0 is the reference's
+// with inter/min(area) (or IoU) > thresh, compacted and rescaled by s1/s2 (sort, suppression and compaction are ffgpu_block.inc's).  A candidate of score exactly 0 is the reference's
 // dead box: it counts in ncand and in the first bbox_max of the emission order, never suppresses and is not kept.
 // Capacity: every anchor of every cell has a candidate slot (cap per frame), so nothing is dropped before the sort; the
 // reference's own limit -- it stops appending at net->bbox_max in EMISSION order (ffcnn.c:463) -- is reproduced by a
@@ -365,67 +367,24 @@ __global__ void __launch_bounds__(256) k_nms(const BBOX *cand, const int *cand_k
         s_idx[i] = i;
     }
     __syncthreads();
-    // BYKEY: ascending emission key only (the pass that reproduces the reference's truncation); else (score desc, key asc)
-    auto sort = [&](bool bykey) {
-        for (int k = 2; k <= pow2; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int i = tid; i < pow2; i += blockDim.x) {
-                    const int l = i ^ j;
-                    if (l > i) {
-                        const bool up = (i & k) == 0;
-                        // "a precedes b"
-                        const bool a_first = bykey ? s_key[i] < s_key[l]
-                                                   : (s_score[i] > s_score[l] || (s_score[i] == s_score[l] && s_key[i] < s_key[l]));
-                        if (a_first != up) {
-                            const float ts = s_score[i]; s_score[i] = s_score[l]; s_score[l] = ts;
-                            const int tk = s_key[i]; s_key[i] = s_key[l]; s_key[l] = tk;
-                            const int ti = s_idx[i]; s_idx[i] = s_idx[l]; s_idx[l] = ti;
-                        }
-                    }
-                }
-                __syncthreads();
-            }
+    // two orders: ascending emission key only (the pass that reproduces the reference's truncation), and (score desc, key asc)
+    auto swap = [&](int i, int l) {
+        const float ts = s_score[i]; s_score[i] = s_score[l]; s_score[l] = ts;
+        const int tk = s_key[i]; s_key[i] = s_key[l]; s_key[l] = tk;
+        const int ti = s_idx[i]; s_idx[i] = s_idx[l]; s_idx[l] = ti;
     };
     if (m > bbox_max) {                                   // uniform; keep the first bbox_max in emission order (ffcnn.c:463)
-        sort(true);
+        block_bitonic(pow2, [&](int i, int l) { return s_key[i] < s_key[l]; }, swap);
         for (int i = bbox_max + tid; i < pow2; i += blockDim.x) { s_score[i] = -1.f; s_key[i] = 0x7fffffff; }
         m = bbox_max;
         __syncthreads();
     }
-    sort(false);
+    block_bitonic(pow2, [&](int i, int l) { return s_score[i] > s_score[l] || (s_score[i] == s_score[l] && s_key[i] < s_key[l]); }, swap);
     for (int i = tid; i < m; i += blockDim.x) s_alive[i] = s_score[i] != 0.f;      // score 0 is the reference's "dead" (ffcnn.c:305,324): never suppresses, not kept
     __syncthreads();
-    for (int a = 0; a < m; a++) {
-        if (!s_alive[a]) continue;                       // uniform: read after a barrier
-        const BBOX ba = c[s_idx[a]];
-        // (width and height of a box are kept out of ONE register pair: hipcc otherwise forms v_pk_mul_f32 v[a:b], v[a:b], v[a:b] op_sel:[0,1] ..., the operand
-        //  pattern of the packed-math slip under concurrent bf16 MFMAs -- see pw_fma4_apart in ffgpu_pw_mfma.inc)
-        auto area = [](float x1, float y1, float x2, float y2) { float w = x2 - x1; asm volatile("" : "+v"(w)); return w * (y2 - y1); };
-        const float area_a = area(ba.x1, ba.y1, ba.x2, ba.y2);
-        for (int j = a + 1 + tid; j < m; j += blockDim.x) {
-            if (!s_alive[j]) continue;
-            const BBOX bj = c[s_idx[j]];
-            if (bj.type != ba.type) continue;
-            const float xa = ba.x1 > bj.x1 ? ba.x1 : bj.x1, ya = ba.y1 > bj.y1 ? ba.y1 : bj.y1;
-            const float xb = ba.x2 < bj.x2 ? ba.x2 : bj.x2, yb = ba.y2 < bj.y2 ? ba.y2 : bj.y2;
-            const float inter = (xa < xb && ya < yb) ? area(xa, ya, xb, yb) : 0.f;
-            const float area_j = area(bj.x1, bj.y1, bj.x2, bj.y2);
-            const float uni = area_a + area_j - inter;
-            const float metric = use_min ? inter / (area_a < area_j ? area_a : area_j) : inter / uni;
-            if (metric > thresh) s_alive[j] = 0;
-        }
-        __syncthreads();
-    }
-    // survivors in score order: one thread walks the list (the key array has served its purpose and becomes the list),
-    // every thread then writes slots
-    __shared__ int s_nkeep;
-    if (tid == 0) {
-        int keep = 0;
-        for (int i = 0; i < m; i++) if (s_alive[i]) s_key[keep++] = s_idx[i];
-        s_nkeep = keep;
-    }
-    __syncthreads();
-    const int nfull = s_nkeep, nrec = min(nfull, FFGPU_MAX_DET);
+    block_suppress(m, s_alive, [&](int i) { return c[s_idx[i]]; }, thresh, use_min);
+    // survivors in score order (the key array has served its purpose and becomes the list), every thread then writes slots
+    const int nfull = block_compact(m, s_alive, s_idx, s_key), nrec = min(nfull, FFGPU_MAX_DET);
     auto scaled = [&](int i) {
         const BBOX b = c[s_key[i]];
         BBOX r;

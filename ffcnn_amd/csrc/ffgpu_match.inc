@@ -11,12 +11,12 @@
 // four guarded 4-byte loads otherwise -- the same bits either way; everything behind D, behind nq and behind `count` is zero in LDS.  Wave w owns
 // queries 16 w .. 16 w + 15 against all MT_G gallery rows: four accumulator tiles of v_mfma_f32_16x16x4_f32 (A = queries, B = gallery; C/D: gallery
 // row = 16 t + (lane & 15), query = 4 (lane >> 4) + reg), so the 64 sims of one query lie in four registers of ONE 16-lane group and the selection
-// needs no LDS: round r finds, by four cross-lane exchanges, the first pair (sim, g) in the contract's order behind round r - 1's (k_topk's idea).
+// needs no LDS: round r finds, by four cross-lane exchanges, the first pair (sim, g) in the contract's order behind round r - 1's (pair_behind, pair_take of ffgpu_block.inc, as k_topk).
 // The k pairs of (query, tile) go to the workspace.  A tile behind `count` writes its NaNs into d_sim (if given) and ends.
-// Launch 2 (k_match_merge): one workgroup per query merges the live tiles' lists in the same order, k rounds, and applies d_ids.
+// Launch 2 (k_match_merge): one workgroup per query merges the live tiles' lists in the same order (block_first_pair), k rounds, and applies d_ids.
 //
 // Enrol, launch 1 (k_enroll_decide): ONE workgroup.  A wave per query decides matched / all finite; then the queries are ranked in ascending r by
-// ballots and prefix counts, ids and labels written, the head updated.  Launch 2 (k_enroll_copy): one workgroup per query; an enrolled query's slot
+// ballots and prefix counts (block_rank), ids and labels written, the head updated.  Launch 2 (k_enroll_copy): one workgroup per query; an enrolled query's slot
 // follows from its id and the new head, its row is copied as integers.
 #define MT_Q   64                                // queries per workgroup (16 per wave)
 #define MT_G   64                                // gallery rows per tile
@@ -47,12 +47,6 @@ __device__ __forceinline__ uint4 mt_quad(const unsigned *row, bool there, bool v
     if (k0 + 2 < D) v.z = row[k0 + 2];
     if (k0 + 3 < D) v.w = row[k0 + 3];
     return v;
-}
-
-// does (ov, og) precede (bv, bg) in "sim descending, then g ascending"?  g < 0: no pair
-__device__ __forceinline__ void mt_take(float &bv, int &bg, float ov, int og)
-{
-    if (og >= 0 && (bg < 0 || ov > bv || (ov == bv && og < bg))) { bv = ov; bg = og; }
 }
 
 __global__ void __launch_bounds__(256) k_match(MatchP p)
@@ -148,12 +142,12 @@ __global__ void __launch_bounds__(256) k_match(MatchP p)
 #pragma unroll
             for (int t = 0; t < 4; t++) {                                           // (ascending g: of equal values a lane keeps the first)
                 const float v = acc[t][e];
-                const bool ok = v == v && (r == 0 || v < pv[e] || (v == pv[e] && gi[t] > pg[e]));
+                const bool ok = v == v && pair_behind(v, gi[t], pv[e], pg[e], r == 0);
                 if (ok && (bg < 0 || v > bv)) { bv = v; bg = gi[t]; }
             }
             if (r > 0 && pg[e] < 0) bg = -1;                                       // the list ended in an earlier round
 #pragma unroll
-            for (int o = 1; o < 16; o <<= 1) { const float ov = __shfl_xor(bv, o); const int og = __shfl_xor(bg, o); mt_take(bv, bg, ov, og); }
+            for (int o = 1; o < 16; o <<= 1) { const float ov = __shfl_xor(bv, o); const int og = __shfl_xor(bg, o); pair_take(bv, bg, ov, og); }
             pv[e] = bv; pg[e] = bg;
             if (lc == 0 && qb + e < p.nq) {
                 int *w = p.work + (((long)(qb + e) * p.ntiles + tile) * p.k + r) * 2;
@@ -169,7 +163,7 @@ __global__ void __launch_bounds__(256) k_match_merge(MatchP p)
 {
     __shared__ float s_v[256 / WAVE];
     __shared__ int s_g[256 / WAVE];
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const int tid = threadIdx.x;
     const int q = blockIdx.x;
     const int count = mt_count(p.head, p.capacity);
     const int n = ((count + MT_G - 1) / MT_G) * p.k;                                // pairs of the tiles that wrote a list
@@ -185,15 +179,10 @@ __global__ void __launch_bounds__(256) k_match_merge(MatchP p)
             const int g = w[2 * i];
             const float v = __int_as_float(w[2 * i + 1]);
             if (g < 0) continue;
-            if (r > 0 && !(v < pv || (v == pv && g > pg))) continue;
-            mt_take(bv, bg, v, g);
+            if (!pair_behind(v, g, pv, pg, r == 0)) continue;
+            pair_take(bv, bg, v, g);
         }
-        for (int s = WAVE / 2; s > 0; s >>= 1) { const float ov = __shfl_xor(bv, s); const int og = __shfl_xor(bg, s); mt_take(bv, bg, ov, og); }
-        if (lane == 0) { s_v[wave] = bv; s_g[wave] = bg; }
-        __syncthreads();
-        bv = s_v[0]; bg = s_g[0];
-        for (int x = 1; x < 256 / WAVE; x++) mt_take(bv, bg, s_v[x], s_g[x]);
-        __syncthreads();
+        block_first_pair(bv, bg, s_v, s_g, 256 / WAVE);
         if (bg < 0) break;                                                         // (uniform) no further pair
         if (tid == 0) { o[2 * r] = p.ids ? p.ids[bg] : bg; o[2 * r + 1] = __float_as_int(bv); }
         pv = bv; pg = bg;
@@ -236,12 +225,8 @@ __global__ void __launch_bounds__(1024) k_enroll_decide(EnrollP p)
     for (int r0 = 0; r0 < p.nq; r0 += 1024) {
         const int r = r0 + tid;
         const int st = r < p.nq ? s_state[r] : EN_MATCHED;
-        const unsigned long long m = __ballot(st == EN_NEW);
-        if (lane == 0) s_cnt[wave] = __popcll(m);
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int x = 0; x < 1024 / WAVE; x++) { const int c = s_cnt[x]; before += x < wave ? c : 0; total += c; }
-        const int e = seen + before + __popcll(m & ((1ull << lane) - 1ull));        // this query's rank among the new ones
+        int total;
+        const int e = seen + block_rank(st == EN_NEW, s_cnt, 1024 / WAVE, total);   // this query's rank among the new ones
         const bool room = e < p.capacity - count;
         if (r < p.nq) {
             int2 o = make_int2(-1, 0);

@@ -2,7 +2,7 @@
 // A batch entry may be a tile of a larger picture (a frame descriptor is an address, a size and a pitch: a crop costs nothing); its survivors
 // are in the tile's own pixels.  Per picture: translate every tile's survivors by the tile's origin (one fp32 addition per coordinate), order
 // the union by (score desc, position of the tile in the caller's table asc, index in the tile's list asc), run the greedy class-aware
-// suppression of ffcnn.c:298-322 with k_nms's arithmetic, write the survivors in that order.  Two-stage NMS: per tile by k_nms, across tiles
+// suppression of ffcnn.c:298-322 with k_nms's arithmetic (block_suppress, ffgpu_block.inc), write the survivors in that order.  Two-stage NMS: per tile by k_nms, across tiles
 // here -- not NMS over the union of the raw candidates.
 //
 // The tile table as the kernel reads it, ints: [0] nimages | off[nimages + 1] | { t, x0, y0 } per selected table entry, the entries of picture g
@@ -29,66 +29,27 @@ struct MergeWork {
         : score(reinterpret_cast<float *>(b)), idx(reinterpret_cast<int *>(b + 4 * cap)), box(reinterpret_cast<BBOX *>(b + 8 * cap)), alive(reinterpret_cast<int *>(b + 32 * cap)) {}
 };
 
-// sort, suppress, write: steps 2 - 4 of the contract on the m gathered boxes of picture g (k_nms's sort-and-suppress idiom; the gather slot is the
-// tie-breaking key: slots are filled tile by tile in table order)
-template <bool GLB>
+// sort, suppress, write: steps 2 - 4 of the contract on the m gathered boxes of picture g, with the primitives of ffgpu_block.inc that k_nms uses (the
+// gather slot is the tie-breaking key: slots are filled tile by tile in table order).  Unlike k_nms, a box of score 0 starts alive.
 __device__ __forceinline__ void merge_sorted_out(MergeWork w, int m, float thresh, int use_min, int ncand, int ovf0,
                                                  ffgpu_frame_dets *out, BBOX *out_list)
 {
-#pragma clang fp contract(off)
-    __shared__ int s_nkeep;
     const int tid = threadIdx.x;
     int pow2 = 1;
     while (pow2 < m) pow2 <<= 1;
     for (int i = m + tid; i < pow2; i += blockDim.x) { w.score[i] = -1.f; w.idx[i] = 0x7fffffff; }
     __syncthreads();
-    for (int k = 2; k <= pow2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < pow2; i += blockDim.x) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const bool up = (i & k) == 0;
-                    const bool a_first = w.score[i] > w.score[l] || (w.score[i] == w.score[l] && w.idx[i] < w.idx[l]);      // "a precedes b"
-                    if (a_first != up) {
-                        const float ts = w.score[i]; w.score[i] = w.score[l]; w.score[l] = ts;
-                        const int ti = w.idx[i]; w.idx[i] = w.idx[l]; w.idx[l] = ti;
-                    }
-                }
-            }
-            __syncthreads();
-        }
+    block_bitonic(pow2, [&](int i, int l) { return w.score[i] > w.score[l] || (w.score[i] == w.score[l] && w.idx[i] < w.idx[l]); },
+                  [&](int i, int l) {
+                      const float ts = w.score[i]; w.score[i] = w.score[l]; w.score[l] = ts;
+                      const int ti = w.idx[i]; w.idx[i] = w.idx[l]; w.idx[l] = ti;
+                  });
     for (int i = tid; i < m; i += blockDim.x) w.alive[i] = 1;
     __syncthreads();
-    for (int a = 0; a < m; a++) {
-        if (!w.alive[a]) continue;                       // uniform: read after a barrier
-        const BBOX ba = w.box[w.idx[a]];
-        // (width and height of a box are kept out of ONE register pair: hipcc otherwise forms v_pk_mul_f32 v[a:b], v[a:b], v[a:b] op_sel:[0,1] ..., the operand
-        //  pattern of the packed-math slip under concurrent bf16 MFMAs -- see pw_fma4_apart in ffgpu_pw_mfma.inc)
-        auto area = [](float x1, float y1, float x2, float y2) { float bw = x2 - x1; asm volatile("" : "+v"(bw)); return bw * (y2 - y1); };
-        const float area_a = area(ba.x1, ba.y1, ba.x2, ba.y2);
-        for (int j = a + 1 + tid; j < m; j += blockDim.x) {
-            if (!w.alive[j]) continue;
-            const BBOX bj = w.box[w.idx[j]];
-            if (bj.type != ba.type) continue;
-            const float xa = ba.x1 > bj.x1 ? ba.x1 : bj.x1, ya = ba.y1 > bj.y1 ? ba.y1 : bj.y1;
-            const float xb = ba.x2 < bj.x2 ? ba.x2 : bj.x2, yb = ba.y2 < bj.y2 ? ba.y2 : bj.y2;
-            const float inter = (xa < xb && ya < yb) ? area(xa, ya, xb, yb) : 0.f;
-            const float area_j = area(bj.x1, bj.y1, bj.x2, bj.y2);
-            const float uni = area_a + area_j - inter;
-            const float metric = use_min ? inter / (area_a < area_j ? area_a : area_j) : inter / uni;
-            if (metric > thresh) w.alive[j] = 0;
-        }
-        __syncthreads();
-    }
-    // survivors in order: one thread walks the list (the score array has served its purpose and becomes the list), every thread then writes slots
+    block_suppress(m, w.alive, [&](int i) { return w.box[w.idx[i]]; }, thresh, use_min);
+    // survivors in order (the score array has served its purpose and becomes the list), every thread then writes slots
     int *const keep = reinterpret_cast<int *>(w.score);
-    if (tid == 0) {
-        int n = 0;
-        for (int i = 0; i < m; i++) if (w.alive[i]) keep[n++] = w.idx[i];
-        s_nkeep = n;
-    }
-    __syncthreads();
-    const int nfull = s_nkeep, nrec = min(nfull, FFGPU_MAX_DET);
+    const int nfull = block_compact(m, w.alive, w.idx, keep), nrec = min(nfull, FFGPU_MAX_DET);
     if (out_list) for (int i = tid; i < nfull; i += blockDim.x) out_list[i] = w.box[keep[i]];
     for (int i = tid; i < FFGPU_MAX_DET; i += blockDim.x) {
         BBOX r = { 0, 0.f, 0.f, 0.f, 0.f, 0.f };
@@ -164,8 +125,7 @@ __global__ void __launch_bounds__(256) k_merge_tiles(Tab tab, const ffgpu_frame_
         __syncthreads();                                                              // (the chunk's tables are rewritten by the next trip)
     }
     BBOX *const ol = out_lists ? out_lists + (size_t)stride * o0 : nullptr;
-    if (glb) merge_sorted_out<true>(w, m, thresh, use_min, ncand, ovf0, out_recs + g, ol);
-    else     merge_sorted_out<false>(w, m, thresh, use_min, ncand, ovf0, out_recs + g, ol);
+    merge_sorted_out(w, m, thresh, use_min, ncand, ovf0, out_recs + g, ol);
 }
 
 int ffgpu_launch_set_ints(int *d_dst, const int *h_src, int n, hipStream_t s)

@@ -4,11 +4,11 @@
 //
 // One workgroup per video stream and launch: it loads the stream's state into LDS once, walks the stream's records of the launch serially and writes
 // the state back once.  Per frame: the considered detections are compacted into LDS by ballots (list order kept), the IoU of every (slot, detection)
-// pair goes into an LDS matrix (-1: not eligible), and the greedy matching in the contract's total order is found without sorting: a pair that
+// pair goes into an LDS matrix (box_overlap and box_iou of ffgpu_block.inc; -1: not eligible), and the greedy matching in the contract's total order is found without sorting: a pair that
 // is the first of its row (iou desc, detection asc) AND the first of its column (iou desc, slot asc) among the unmatched precedes every other
 // remaining pair that shares its track or its detection, so the serial walk takes it; all such pairs are taken per round, and the first remaining
 // pair of the whole matrix is always one of them.  Rounds: a handful on real frames, at most min(tracks, detections).  Frees, births (ranks from
-// ballots: the r-th birth takes the r-th free slot) and the counters use no atomic.
+// ballots, block_rank: the r-th birth takes the r-th free slot) and the counters use no atomic.
 //
 // The entries of a launch (TRACK_ARG_ENTRIES records, sorted by video stream on the host, record order kept inside a stream) and the spec travel as
 // ONE by-value kernel argument; more records: more launches, in order on the one stream, the state carrying a stream from one to the next.
@@ -49,8 +49,7 @@ __global__ void __launch_bounds__(256) k_track(TrackArgs a, const ffgpu_frame_de
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) unsigned char s_track[];
     TrackLds &L = *reinterpret_cast<TrackLds *>(s_track);
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE, g = blockIdx.x;
-    const unsigned long long below = (1ull << lane) - 1ull;
+    const int tid = threadIdx.x, g = blockIdx.x;
     const int e0 = a.goff[g], e1 = a.goff[g + 1], vs = a.gstream[g], C = a.spec.capacity;
     const long rowlen = 8 + (long)stride;
     if (vs < 0) {                                                                     // the ignored entries: every output byte zero (uniform)
@@ -84,33 +83,25 @@ __global__ void __launch_bounds__(256) k_track(TrackArgs a, const ffgpu_frame_de
         for (int k0 = 0; k0 < n; k0 += 256) {
             const int k = k0 + tid;
             const bool q = k < n && list[k].score >= min_score;
-            const unsigned long long m = __ballot(q);
-            if (lane == 0) L.wsum[wave] = __popcll(m);
-            __syncthreads();
-            int off = 0, tot = 0;
-            for (int w = 0; w < 4; w++) { const int c = L.wsum[w]; if (w < wave) off += c; tot += c; }
-            const long ord = nq + off + __popcll(m & below);
+            int tot;
+            const long ord = nq + block_rank(q, L.wsum, 4, tot);
             if (q && ord < FFGPU_TRACK_DETS) { track_put(&L.det[ord], list[k].type, list[k]); L.didx[ord] = k; }
             nq += tot;
             __syncthreads();
         }
         const int nd = (int)min(nq, (long)FFGPU_TRACK_DETS), dropped = (int)min(nq - nd, 0x7fffffffL);
 
-        // 2. the matrix (hipcc keeps a box's width and height out of one register pair: see merge_sorted_out)
-        auto area = [](float x1, float y1, float x2, float y2) { float bw = x2 - x1; asm volatile("" : "+v"(bw)); return bw * (y2 - y1); };
+        // 2. the matrix
         for (int p = tid; p < C * nd; p += blockDim.x) {
             const int s = p / nd, j = p - s * nd;
             const ffgpu_track ba = trk[s];
             float v = -1.f;
             if (ba.id != 0) {
                 const BBOX bj = L.det[j];
-                const float area_a = area(ba.x1, ba.y1, ba.x2, ba.y2);
-                const float xa = ba.x1 > bj.x1 ? ba.x1 : bj.x1, ya = ba.y1 > bj.y1 ? ba.y1 : bj.y1;
-                const float xb = ba.x2 < bj.x2 ? ba.x2 : bj.x2, yb = ba.y2 < bj.y2 ? ba.y2 : bj.y2;
-                const float inter = (xa < xb && ya < yb) ? area(xa, ya, xb, yb) : 0.f;
-                const float area_j = area(bj.x1, bj.y1, bj.x2, bj.y2);
-                const float uni = area_a + area_j - inter;
-                const float iou = inter / uni;
+                const float area_a = box_area(ba.x1, ba.y1, ba.x2, ba.y2);
+                float inter, area_j;
+                box_overlap(ba, bj, inter, area_j);
+                const float iou = box_iou(inter, area_a, area_j);
                 if (iou >= thr && (!a.spec.class_aware || ba.type == bj.type)) v = iou;   // (thr >= 0: an eligible value is never below -0.0)
             }
             L.iou[s * TRACK_PITCH + j] = v;
@@ -172,15 +163,13 @@ __global__ void __launch_bounds__(256) k_track(TrackArgs a, const ffgpu_frame_de
         }
         const int nmatched = __syncthreads_count(matched), nfreed = __syncthreads_count(gone);
 
-        // 6. births: the r-th unmatched detection that may start a track takes the r-th free slot
+        // 6. births: the r-th unmatched detection that may start a track takes the r-th free slot (ranks within a wave pair: waves 0-1 the
+        // detections, waves 2-3 the slots)
         bool flag;
         if (tid < FFGPU_TRACK_DETS) flag = tid < nd && L.dmatch[tid] < 0 && L.det[tid].score >= birth_score;
         else                        flag = tid - FFGPU_TRACK_DETS < C && trk[tid - FFGPU_TRACK_DETS].id == 0;
         {
-            const unsigned long long m = __ballot(flag);
-            if (lane == 0) L.wsum[wave] = __popcll(m);
-            __syncthreads();
-            const int r = __popcll(m & below) + ((wave & 1) ? L.wsum[wave - 1] : 0);
+            const int r = block_rank(flag, L.wsum, 2);
             const int nwant = L.wsum[0] + L.wsum[1], nfree = L.wsum[2] + L.wsum[3];
             if (flag && tid >= FFGPU_TRACK_DETS) L.freeslot[r] = tid - FFGPU_TRACK_DETS;
             __syncthreads();
@@ -211,10 +200,7 @@ __global__ void __launch_bounds__(256) k_track(TrackArgs a, const ffgpu_frame_de
             row[8 + L.didx[tid]] = conf ? id : (int)(0u - (unsigned)id);               // (zeroed above, barriers in between)
         }
         {
-            const unsigned long long m = __ballot(conf);
-            if (lane == 0) L.wsum[wave] = __popcll(m);
-            __syncthreads();
-            const int ord = __popcll(m & below) + ((wave & 1) ? L.wsum[wave - 1] : 0), nt = L.wsum[0] + L.wsum[1];   // (nt <= nd <= n <= stride)
+            const int ord = block_rank(conf, L.wsum, 2), nt = L.wsum[0] + L.wsum[1];   // (nt <= nd <= n <= stride)
             if (out_recs) {
                 ffgpu_frame_dets *o = out_recs + t;
                 if (conf) track_put(&o->box[ord], id, L.det[tid]);
