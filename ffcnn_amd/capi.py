@@ -112,11 +112,19 @@ class Gallery(C.Structure):          # ffgpu_gallery (40 bytes): a host struct o
     _fields_ = [("d_rows", C.c_void_p), ("d_ids", C.c_void_p), ("d_head", C.c_void_p), ("row_stride", C.c_long), ("capacity", C.c_int), ("d", C.c_int)]
 
 
+class RedactSpec(C.Structure):       # ffgpu_redact_spec (40 bytes): which boxes' regions are redacted, and how
+    _fields_ = [("mode", C.c_int), ("cell", C.c_int), ("flags", C.c_int), ("nclasses", C.c_int), ("classes", C.c_void_p), ("min_score", C.c_float),
+                ("margin_num", C.c_int), ("margin_den", C.c_int), ("color", C.c_ubyte * 4)]
+
+
 TRACK_DETS = 128                                                                       # FFGPU_TRACK_DETS
 TRACK_ENTRIES, TRACK_MERGED = 0, 1                                                     # FFGPU_TRACK_* (ffgpu_exec_track: which)
 TRACK_IDS_HEADER = ("considered", "matched", "born", "refused", "dropped", "freed", "live", "frame")   # the 8 ints in front of a row of ids
 CROP_F32, CROP_U8 = 0, 1                                                               # FFGPU_CROP_* (ffgpu_crop_spec.form)
 CROP_ENTRIES, CROP_MERGED = 0, 1                                                       # FFGPU_CROP_* (ffgpu_exec_crop_bgr / _nv12: which)
+REDACT_FILL, REDACT_MOSAIC = 0, 1                                                     # FFGPU_REDACT_* (ffgpu_redact_spec.mode)
+REDACT_OUTSIDE = 1                                                                     # FFGPU_REDACT_OUTSIDE (ffgpu_redact_spec.flags)
+REDACT_ENTRIES, REDACT_MERGED = 0, 1                                                   # FFGPU_REDACT_* (ffgpu_exec_redact_bgr / _nv12: which)
 DRAW_ENTRIES, DRAW_MERGED = 0, 1                                                       # FFGPU_DRAW_* (ffgpu_exec_draw_bgr / _nv12: which)
 YUV_BT601_LIMITED, YUV_BT601_FULL, YUV_BT709_LIMITED, YUV_BT709_FULL = 0, 1, 2, 3      # FFGPU_YUV_* (ffgpu_nv12_frame.matrix)
 
@@ -126,7 +134,7 @@ assert C.sizeof(BgrFrame) == 24 and C.sizeof(Nv12Frame) == 40 and C.sizeof(Tile)
 assert C.sizeof(DrawStyle) == 24 and C.sizeof(CropSpec) == 72 and C.sizeof(Crop) == 48
 assert C.sizeof(TrackSpec) == 32 and C.sizeof(Track) == 48
 assert C.sizeof(FeatureSpec) == 16 and C.sizeof(Label) == 8 and C.sizeof(RelabelSpec) == 16
-assert C.sizeof(Gallery) == 40
+assert C.sizeof(Gallery) == 40 and C.sizeof(RedactSpec) == 40
 
 BOX_DTYPE = np.dtype([("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
 DETS_DTYPE = np.dtype([("count", "<i4"), ("ncand", "<i4"), ("overflow", "<i4"), ("nfull", "<i4"),
@@ -157,7 +165,8 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_track_state_bytes", "ffgpu_track_reset_dev", "ffgpu_track_boxes_dev", "ffgpu_exec_track",
            "ffgpu_feature_dim", "ffgpu_exec_feature_dim", "ffgpu_features_dev", "ffgpu_exec_features", "ffgpu_topk_dev", "ffgpu_crops_relabel_dev",
            "ffgpu_exec_relabel",
-           "ffgpu_match_workspace_bytes", "ffgpu_match_dev", "ffgpu_gallery_enroll_dev"]
+           "ffgpu_match_workspace_bytes", "ffgpu_match_dev", "ffgpu_gallery_enroll_dev",
+           "ffgpu_redact_boxes_bgr_dev", "ffgpu_redact_boxes_nv12_dev", "ffgpu_exec_redact_bgr", "ffgpu_exec_redact_nv12"]
 # include/ffcnn_hip_diag.h (libffcnn_hip_diag.so: lab equipment, its own library)
 DIAG_EXPORTS = ["ffgpu_membench", "ffgpu_pipe_probe", "ffgpu_pipe_probe2", "ffgpu_pipe_probe3", "ffgpu_mfma_floor", "ffgpu_diag_x3_term", "ffgpu_diag_xl_op", "ffgpu_clock_probe"]
 
@@ -281,6 +290,10 @@ def lib():
     L.ffgpu_draw_boxes_nv12_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(Nv12Frame), i, C.POINTER(DrawStyle), vp]
     L.ffgpu_exec_draw_bgr.argtypes = [vp, i, C.POINTER(BgrFrame), i, C.POINTER(DrawStyle), vp]
     L.ffgpu_exec_draw_nv12.argtypes = [vp, i, C.POINTER(Nv12Frame), i, C.POINTER(DrawStyle), vp]
+    L.ffgpu_redact_boxes_bgr_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(BgrFrame), i, C.POINTER(RedactSpec), vp]
+    L.ffgpu_redact_boxes_nv12_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(Nv12Frame), i, C.POINTER(RedactSpec), vp]
+    L.ffgpu_exec_redact_bgr.argtypes = [vp, i, C.POINTER(BgrFrame), i, C.POINTER(RedactSpec), vp]
+    L.ffgpu_exec_redact_nv12.argtypes = [vp, i, C.POINTER(Nv12Frame), i, C.POINTER(RedactSpec), vp]
     L.ffgpu_crop_table_bytes.restype = sz
     L.ffgpu_crop_table_bytes.argtypes = [i]
     L.ffgpu_crop_slot_bytes.restype = sz
@@ -630,6 +643,15 @@ class Executor:
         arr = nv12_frame_table(frames)
         _check(lib().ffgpu_exec_draw_nv12(self.h, which, arr, len(frames), draw_style(color, palette, thickness), stream), "ffgpu_exec_draw_nv12")
 
+    def redact_bgr(self, frames, spec, which=0, stream=None):
+        """enqueue the redaction of the last forward's boxes (which = REDACT_ENTRIES: entry n in frames[n]) or of the last merge's (REDACT_MERGED:
+        picture g in frames[g]) behind it (ffgpu_exec_redact_bgr): frames as draw_bgr takes them, spec from redact_spec.  Redact before draw."""
+        _check(lib().ffgpu_exec_redact_bgr(self.h, which, bgr_frame_table(frames), len(frames), spec, stream), "ffgpu_exec_redact_bgr")
+
+    def redact_nv12(self, frames, spec, which=0, stream=None):
+        """the same in NV12 frames (ffgpu_exec_redact_nv12): the spec's colour is Y U V bytes, its cell even"""
+        _check(lib().ffgpu_exec_redact_nv12(self.h, which, nv12_frame_table(frames), len(frames), spec, stream), "ffgpu_exec_redact_nv12")
+
     def crop_bgr(self, frames, spec, d_out, d_table, capacity, which=0, stream=None):
         """enqueue the cut of the last forward's boxes (which = CROP_ENTRIES: entry n out of frames[n]) or of the last merge's (CROP_MERGED: picture
         g out of frames[g]) behind it (ffgpu_exec_crop_bgr): frames as forward_bgr_frames_dev takes them (None, or a NULL address: skipped), spec
@@ -786,6 +808,37 @@ def draw_boxes_bgr_dev(d_records, d_lists, list_stride, frames, style=None, list
 def draw_boxes_nv12_dev(d_records, d_lists, list_stride, frames, style=None, list_first=None, stream=None):
     """ffgpu_draw_boxes_nv12_dev: the same into NV12 frames (what nv12_frame_desc accepts, or None: skipped); colours are Y U V bytes"""
     _draw_boxes_dev(lib().ffgpu_draw_boxes_nv12_dev, "ffgpu_draw_boxes_nv12_dev", nv12_frame_table, d_records, d_lists, list_stride, list_first, frames, style, stream)
+
+
+def redact_spec(mode, cell=0, outside=False, min_score=0.0, classes=None, margin=(0, 1), color=(0, 0, 0)):
+    """a RedactSpec: mode REDACT_FILL (cell 0, color = B G R or Y U V bytes) or REDACT_MOSAIC (cell 2..64, even for NV12 targets); outside: everything
+    BUT the regions; classes, min_score and margin as crop_spec.  The structure keeps its class bytes alive."""
+    sp = RedactSpec()
+    sp.mode, sp.cell, sp.flags, sp.min_score = mode, cell, REDACT_OUTSIDE if outside else 0, min_score
+    sp.margin_num, sp.margin_den = margin
+    sp.color[:] = (int(color[0]), int(color[1]), int(color[2]), 0)
+    if classes is not None:
+        cls = np.ascontiguousarray(np.asarray(classes) != 0, np.uint8) if len(classes) else np.zeros(1, np.uint8)
+        sp._cls = cls                                           # (owned by the structure: the C side reads it during the call)
+        sp.classes = cls.ctypes.data
+        sp.nclasses = len(classes)
+    return sp
+
+
+def _redact_boxes_dev(fn, name, table, d_records, d_lists, list_stride, list_first, frames, spec, stream):
+    first = None if list_first is None else (C.c_int * max(1, len(list_first)))(*[int(v) for v in list_first])
+    _check(fn(d_records, d_lists, list_stride, first, table(frames), len(frames), spec, stream), name)
+
+
+def redact_boxes_bgr_dev(d_records, d_lists, list_stride, frames, spec, list_first=None, stream=None):
+    """ffgpu_redact_boxes_bgr_dev on device records / lists: the regions of record t's qualifying boxes (or everything but them) redacted in
+    frames[t] (what bgr_frame_desc accepts, or None: skipped); d_lists None: the records' own boxes; list_first as draw_boxes_bgr_dev"""
+    _redact_boxes_dev(lib().ffgpu_redact_boxes_bgr_dev, "ffgpu_redact_boxes_bgr_dev", bgr_frame_table, d_records, d_lists, list_stride, list_first, frames, spec, stream)
+
+
+def redact_boxes_nv12_dev(d_records, d_lists, list_stride, frames, spec, list_first=None, stream=None):
+    """ffgpu_redact_boxes_nv12_dev: the same in NV12 frames (what nv12_frame_desc accepts, or None: skipped)"""
+    _redact_boxes_dev(lib().ffgpu_redact_boxes_nv12_dev, "ffgpu_redact_boxes_nv12_dev", nv12_frame_table, d_records, d_lists, list_stride, list_first, frames, spec, stream)
 
 
 def crop_spec(out_w, out_h, form=CROP_F32, per_target=1, min_score=0.0, classes=None, margin=(0, 1), mean=(0.0, 0.0, 0.0), norm=(1 / 255.0,) * 3):

@@ -25,7 +25,7 @@ struct FrameDesc {
 };
 static_assert(sizeof(FrameDesc) == 56, "FrameDesc: 64 of them travel by value as k_set_frames' argument");
 
-// the detections drawn into the frames (ffgpu_draw.inc).  One target as the kernel reads it: the caller's descriptor with its defaults resolved, and
+// the detections drawn into the frames (ffgpu_draw.inc) or redacted in them (ffgpu_redact.inc).  One target as the kernel reads it: the caller's descriptor with its defaults resolved, and
 // the first box of its list (in boxes from the lists' base; unused when the records' own boxes are drawn).  p0 == NULL: a skipped target.
 struct DrawTarget {
     unsigned char *p0;            // row 0 of the BGR pixels / of the Y plane
@@ -128,9 +128,9 @@ struct DetSource {
                                       // the executor forms derive it from `longest`, each family by its own rule
 };
 
-static_assert(FFGPU_DRAW_ENTRIES == 0 && FFGPU_CROP_ENTRIES == 0 && FFGPU_TRACK_ENTRIES == 0 && FFGPU_RELABEL_ENTRIES == 0 &&
-              FFGPU_DRAW_MERGED == 1 && FFGPU_CROP_MERGED == 1 && FFGPU_TRACK_MERGED == 1 && FFGPU_RELABEL_MERGED == 1,
-              "ffgpu_source_exec: one check of `which` serves the four families");
+static_assert(FFGPU_DRAW_ENTRIES == 0 && FFGPU_CROP_ENTRIES == 0 && FFGPU_TRACK_ENTRIES == 0 && FFGPU_RELABEL_ENTRIES == 0 && FFGPU_REDACT_ENTRIES == 0 &&
+              FFGPU_DRAW_MERGED == 1 && FFGPU_CROP_MERGED == 1 && FFGPU_TRACK_MERGED == 1 && FFGPU_RELABEL_MERGED == 1 && FFGPU_REDACT_MERGED == 1,
+              "ffgpu_source_exec: one check of `which` serves the five families");
 
 // the list stride of an operator form: the caller's with lists, FFGPU_MAX_DET without; -1 with a message outside 1 .. 2^24
 inline int ffgpu_list_stride(const char *what, const void *d_lists, int list_stride)

@@ -31,8 +31,10 @@ static_assert(sizeof(CropSrc) == 48 && sizeof(CropSelArgs) + 5 * 8 <= 4096 - 256
 static_assert(sizeof(ffgpu_crop) == 48 && sizeof(ffgpu_crop_spec) == 72, "include/ffcnn_hip.h states these sizes");
 
 // One box against the spec and its source's w x h: 0 = does not qualify, 1 = qualifies and is empty, 2 = qualifies, r = { X0, Y0, w, h }.
-// Corners as the draw contract (draw_f2i), everything behind them in 64-bit integers: (c - a + 1) num <= 2^32 x 4096.
-__device__ __forceinline__ int crop_region(const BBOX &b, const CropSelArgs &a, int w, int h, int4 &r)
+// Corners as the draw contract (draw_f2i), everything behind them in 64-bit integers: (c - a + 1) num <= 2^32 x 4096.  Sel: a kernel's argument struct
+// with the selection's fields min_score, nclasses, classes, num, den (CropSelArgs; RedactArgs of ffgpu_redact.inc).
+template <class Sel>
+__device__ __forceinline__ int crop_region(const BBOX &b, const Sel &a, int w, int h, int4 &r)
 {
     if (!(b.score >= a.min_score)) return 0;                                          // (a NaN score never qualifies)
     if (a.nclasses && !((unsigned)b.type < (unsigned)a.nclasses && a.classes[(unsigned)b.type & 255u])) return 0;
@@ -235,20 +237,27 @@ __global__ void __launch_bounds__(FFGPU_MAX_DET) k_crops_to_source(const int *ta
 }
 
 // ---- host side: the spec and the descriptors checked once for the operators and the executor forms; -1 with the target's index in the message
+// the selection's class table and margin, as the crop and the redact specs carry them
+int ffgpu_box_sel_check(const char *what, int nclasses, const unsigned char *classes, int margin_num, int margin_den)
+{
+    if (classes ? (nclasses < 1 || nclasses > 256) : nclasses != 0) {
+        ffgpu_set_error("%s: nclasses %d (0 with NULL classes, else 1..256)", what, nclasses);
+        return -1;
+    }
+    if (margin_den < 1 || margin_den > 1024 || margin_num < 0 || margin_num > 4 * margin_den) {
+        ffgpu_set_error("%s: margin %d / %d (den 1..1024, num 0..4 den)", what, margin_num, margin_den);
+        return -1;
+    }
+    return 0;
+}
+
 int ffgpu_crop_spec_check(const char *what, const ffgpu_crop_spec *sp, CropPlan &pl)
 {
     if (!sp) { ffgpu_set_error("%s: NULL spec", what); return -1; }
     if (sp->out_w < 1 || sp->out_w > 4096 || sp->out_h < 1 || sp->out_h > 4096) { ffgpu_set_error("%s: out size %d x %d is outside 1..4096", what, sp->out_w, sp->out_h); return -1; }
     if (sp->form != FFGPU_CROP_F32 && sp->form != FFGPU_CROP_U8) { ffgpu_set_error("%s: form %d is neither FFGPU_CROP_F32 nor FFGPU_CROP_U8", what, sp->form); return -1; }
     if (sp->per_target < 1 || sp->per_target > (1 << 24)) { ffgpu_set_error("%s: per_target %d is outside 1..2^24", what, sp->per_target); return -1; }
-    if (sp->classes ? (sp->nclasses < 1 || sp->nclasses > 256) : sp->nclasses != 0) {
-        ffgpu_set_error("%s: nclasses %d (0 with NULL classes, else 1..256)", what, sp->nclasses);
-        return -1;
-    }
-    if (sp->margin_den < 1 || sp->margin_den > 1024 || sp->margin_num < 0 || sp->margin_num > 4 * sp->margin_den) {
-        ffgpu_set_error("%s: margin %d / %d (den 1..1024, num 0..4 den)", what, sp->margin_num, sp->margin_den);
-        return -1;
-    }
+    if (ffgpu_box_sel_check(what, sp->nclasses, sp->classes, sp->margin_num, sp->margin_den)) return -1;
     if (sp->reserved != 0) { ffgpu_set_error("%s: spec: reserved must be 0", what); return -1; }
     memset(&pl, 0, sizeof pl);
     pl.out_w = sp->out_w; pl.out_h = sp->out_h; pl.form = sp->form; pl.per_target = sp->per_target; pl.min_score = sp->min_score;

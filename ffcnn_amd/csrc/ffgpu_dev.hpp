@@ -180,9 +180,21 @@ struct CropPlan {
     float min_score, mean[3], norm[3];
     unsigned char classes[256];
 };
+int ffgpu_box_sel_check(const char *what, int nclasses, const unsigned char *classes, int margin_num, int margin_den);
 int ffgpu_crop_spec_check(const char *what, const ffgpu_crop_spec *sp, CropPlan &pl);
 int ffgpu_crop_buffers_check(const char *what, const void *d_out, const void *d_table, int capacity);
 int ffgpu_launch_crop(bool nv12, const DetSource &src, const std::vector<CropSrc> &sources, const CropPlan &pl, void *d_out, void *d_table, int capacity, hipStream_t s);
+
+// the detections' regions redacted in the frames (ffgpu_redact.inc).  RedactPlan: the caller's spec, checked (nv12: the cell must be even), with the
+// class filter's bytes copied and the colour packed as the draw's palette entries are.  targets[t] is redacted by record t of `src`
+struct RedactPlan {
+    int   mode, cell, outside, nclasses, num, den;
+    float min_score;
+    unsigned colour;
+    unsigned char classes[256];
+};
+int ffgpu_redact_spec_check(const char *what, const ffgpu_redact_spec *sp, bool nv12, RedactPlan &pl);
+int ffgpu_launch_redact(const char *what, bool nv12, const DetSource &src, const std::vector<DrawTarget> &targets, const RedactPlan &pl, hipStream_t s);
 
 // the detections tracked across a stream's frames (ffgpu_track.inc): the checks both entry points share, and the launches
 int ffgpu_track_args_check(const char *what, const int *streams, int ntargets, const ffgpu_track_spec *spec, const void *d_state, int nstreams,

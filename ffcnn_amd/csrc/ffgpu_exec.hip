@@ -1286,8 +1286,8 @@ extern "C" int ffgpu_exec_read_merged_boxes(ffgpu_exec *ex, int image, BBOX *hos
     return nfull;
 }
 
-// -------------------------------------------------------------------------- post-passes that read the boxes: draw, crop, track, relabel
-// What the four post-passes that read boxes share: `which` as the executor's records and lists (ffgpu_source_exec) and the stream, which must be the
+// -------------------------------------------------------------------------- post-passes that read the boxes: draw, crop, track, relabel, redact
+// What the five post-passes that read boxes share: `which` as the executor's records and lists (ffgpu_source_exec) and the stream, which must be the
 // one the forward or merge ran on.  src.stride is the caller's to derive from src.longest.
 static int exec_source(ffgpu_exec *ex, const char *what, const char *family, const char *noun, int which, int ntargets, void *stream, DetSource &src, hipStream_t *s)
 {
@@ -1327,6 +1327,36 @@ extern "C" int ffgpu_exec_draw_bgr(ffgpu_exec *ex, int which, const ffgpu_bgr_fr
 extern "C" int ffgpu_exec_draw_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_frame *targets, int ntargets, const ffgpu_draw_style *style, void *stream)
 {
     return exec_draw(ex, "draw_nv12", which, targets, ntargets, style, stream);
+}
+
+// -------------------------------------------------------------------------- the detections redacted in the frames (include/ffcnn_hip.h; kernel: ffgpu_redact.inc)
+// A post-pass like the draw, on the stream of the forward or merge it follows: reads the records and full lists (per entry, or the merged ones),
+// reads and writes the caller's frames and nothing of the executor's.
+template <class Frame>
+static int exec_redact(ffgpu_exec *ex, const char *what, int which, const Frame *targets, int ntargets, const ffgpu_redact_spec *spec, void *stream)
+{
+    const bool nv12 = std::is_same<Frame, ffgpu_nv12_frame>::value;
+    if (!exec_ok(ex, what)) return -1;
+    if (!targets) { ffgpu_set_error("%s: NULL targets", what); return -1; }
+    RedactPlan pl;
+    if (ffgpu_redact_spec_check(what, spec, nv12, pl)) return -1;
+    DetSource src;
+    hipStream_t s;
+    if (exec_source(ex, what, "REDACT", "redaction", which, ntargets, stream, src, &s)) return -1;
+    src.stride = (int)std::min(src.longest, (long long)0x7fffffff);  // (clamped, as the draw)
+    std::vector<DrawTarget> tab;
+    if (ffgpu_frame_table(what, FRAME_DRAW, targets, ntargets, tab)) return -1;
+    return ffgpu_launch_redact(what, nv12, src, tab, pl, s);
+}
+
+extern "C" int ffgpu_exec_redact_bgr(ffgpu_exec *ex, int which, const ffgpu_bgr_frame *targets, int ntargets, const ffgpu_redact_spec *spec, void *stream)
+{
+    return exec_redact(ex, "redact_bgr", which, targets, ntargets, spec, stream);
+}
+
+extern "C" int ffgpu_exec_redact_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_frame *targets, int ntargets, const ffgpu_redact_spec *spec, void *stream)
+{
+    return exec_redact(ex, "redact_nv12", which, targets, ntargets, spec, stream);
 }
 
 // -------------------------------------------------------------------------- the detections cut out of the frames (include/ffcnn_hip.h; kernels: ffgpu_crop.inc)

@@ -795,6 +795,69 @@ int ffgpu_match_dev(const float *d_q, int nq, long q_stride, const ffgpu_gallery
 int ffgpu_gallery_enroll_dev(const ffgpu_gallery *g, const float *d_q, int nq, long q_stride, const void *d_labels, int k, float min_value,
                              void *d_out_labels, void *stream);
 
+/* ---- the detections redacted in the frames on the device ---------------------------------------------------------------------------------------
+ * Privacy masking: faces, plates or people blanked or pixelated before a frame is encoded, stored or shown -- or everything BUT them.  What follows
+ * replaces the pixels of the selected boxes' regions in u8 BGR and NV12 frames where they lie, in HBM, by a solid colour or a mosaic.  The result is
+ * a pure function of the frame's original bytes, the list and the spec: the same bytes on every run (tests/redact/redactref.py restates it in numpy).
+ *
+ * Covered set S of a target.  A box QUALIFIES by the crop contract's rule: score >= min_score (a NaN score never does) and its class is allowed:
+ * every type with classes == NULL, else 0 <= type < nclasses and classes[type] != 0.  Its region is the crop contract's [X0..X1] x [Y0..Y1]: the
+ * integer corners (a, b, c, d) of the draw contract (toward zero, saturating, NaN -> 0), grown in 64-bit integers by mx = (c - a + 1) num / den and
+ * my = (d - b + 1) num / den, clipped to the target's w x h.  A qualifying box with a > c, b > d, X0 > X1 or Y0 > Y1 contributes nothing.  U is the
+ * union of the qualifying boxes' regions; S = U, or with FFGPU_REDACT_OUTSIDE the target's w x h minus U (a list with no qualifying box then redacts
+ * the whole target).  Overlapping boxes and the order of the list do not matter.
+ * FFGPU_REDACT_FILL.  BGR targets: every pixel of S becomes color[0..2].  NV12 targets (`matrix` is ignored, nothing is converted): Y[y][x] =
+ * color[0] for the pixels of S, and chroma sample (i, j) becomes (color[1], color[2]) when ANY of its up to four luma pixels (2i..2i+1, 2j..2j+1)
+ * inside w x h is in S -- the draw contract's view of a sample; it errs toward redacting.
+ * FFGPU_REDACT_MOSAIC, cell side s.  The cell grid is anchored at the TARGET's pixel (0, 0), not at the boxes: the pattern does not crawl as a box
+ * moves from frame to frame.  Cell (i, j) is x in [i s, min((i + 1) s, w) - 1], y in [j s, min((j + 1) s, h) - 1].  For each channel of a cell
+ * m = (sum + n / 2) / n in integers, the sum taken over ALL n pixels of the clipped cell in the frame's ORIGINAL bytes, in S or not; every pixel of the
+ * cell that is in S becomes m.  A cell with no pixel in S is neither changed nor read.  NV12: luma is one channel of such cells; chroma cell (i, j)
+ * has side s / 2 in the ((w + 1) / 2) x ((h + 1) / 2) plane, U and V averaged separately over the clipped chroma cell with the same rounding, written
+ * to the samples the FILL rule covers.  s is even there, so the luma pixels of a sample lie in one luma cell.
+ * Untouched bytes.  Every byte outside S -- row padding, uncovered pixels and chroma samples, the memory before and behind the target -- stays as it
+ * was.  Nothing depends on the order in which the device executes anything: each byte of a target is read and written by exactly one workgroup, and
+ * a barrier stands between that workgroup's loads of a cell and its first store to it.  No atomic is used.
+ * Ordering.  Redact, then draw: the outlines come out on top (the other way round the outlines are redacted with the rest).  A tile descriptor as a
+ * target anchors the grid at the TILE; for tiled pictures use FFGPU_REDACT_MERGED on the whole picture.
+ * Targets: as the draw contract takes them (a NULL pixel address = "skip this target", the const pointers are WRITTEN THROUGH, targets of one call
+ * must not overlap in memory). */
+#define FFGPU_REDACT_FILL    0
+#define FFGPU_REDACT_MOSAIC  1
+#define FFGPU_REDACT_OUTSIDE 1      /* flags bit 0: redact everything EXCEPT the regions */
+typedef struct {
+    int   mode;                     /* FFGPU_REDACT_FILL | FFGPU_REDACT_MOSAIC                                                    */
+    int   cell;                     /* MOSAIC: 2..64, even for NV12 targets; FILL: 0                                              */
+    int   flags;                    /* 0 | FFGPU_REDACT_OUTSIDE; any other bit is rejected                                        */
+    int   nclasses;                 /* 0 with NULL classes, else 1..256                                                           */
+    const unsigned char *classes;   /* HOST array, as ffgpu_crop_spec                                                             */
+    float min_score;
+    int   margin_num, margin_den;   /* as ffgpu_crop_spec: den 1..1024, num 0..4 den                                              */
+    unsigned char color[4];         /* FILL: B G R 0 / Y U V 0                                                                    */
+} ffgpu_redact_spec;                /* 40 bytes: mode 0, cell 4, flags 8, nclasses 12, classes 16, min_score 24, margin_num 28,   */
+                                    /* margin_den 32, color 36                                                                    */
+
+/* The operators, on device records and lists with no executor.  d_records, d_lists, list_stride, the HOST array list_first, the clamps of the counts,
+ * ntargets >= 1 and the 64 targets per launch (one by-value kernel argument) are the draw operators'; target t is redacted by record t.  targets,
+ * list_first, spec and spec->classes are HOST memory and free again on return.  Enqueued on `stream` without synchronising.  Rejected before anything
+ * is launched, with the target's index in the message where there is one: NULL records, targets or spec, an unknown mode, unknown flag bits, a cell
+ * outside its range (a non-zero cell with FILL, an odd cell on NV12 targets), nclasses inconsistent with classes, a margin outside its range,
+ * everything the draw operators reject, and a target of more than 2^23 blocks (s (64 / s) pixels square; FILL: 64). */
+int ffgpu_redact_boxes_bgr_dev (const void *d_records, const void *d_lists, int list_stride, const int *list_first,
+                                const ffgpu_bgr_frame  *targets, int ntargets, const ffgpu_redact_spec *spec, void *stream);
+int ffgpu_redact_boxes_nv12_dev(const void *d_records, const void *d_lists, int list_stride, const int *list_first,
+                                const ffgpu_nv12_frame *targets, int ntargets, const ffgpu_redact_spec *spec, void *stream);
+
+#define FFGPU_REDACT_ENTRIES 0   /* entry n's full post-NMS list in targets[n]; ntargets == batch                                        */
+#define FFGPU_REDACT_MERGED  1   /* picture g's merged list (last ffgpu_exec_merge_tiles) in targets[g]; ntargets == its nimages          */
+/* On an executor: a post-pass like ffgpu_exec_draw_*, enqueued on `stream` (NULL = the executor's own; it must be the stream of the forward or merge
+ * it follows) without synchronising.  The captured graph, the records, the full lists, the ring and the host mirror are untouched.  A tracked or
+ * relabelled record redacts by object or identity through the operators above: "who" is the record's `type`.  Works on FFGPU_SPLIT2 executors.
+ * Rejected like the operators, and: ntargets not as stated, a `which` that is neither, FFGPU_REDACT_MERGED when no merge has run, the wrong stream.
+ * A rejected call leaves the executor usable. */
+int ffgpu_exec_redact_bgr (ffgpu_exec *ex, int which, const ffgpu_bgr_frame  *targets, int ntargets, const ffgpu_redact_spec *spec, void *stream);
+int ffgpu_exec_redact_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_frame *targets, int ntargets, const ffgpu_redact_spec *spec, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
