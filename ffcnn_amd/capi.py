@@ -153,7 +153,7 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_exec_kernel_count", "ffgpu_exec_work_model", "ffgpu_exec_set_scale", "ffgpu_exec_forward_dev", "ffgpu_exec_forward_host",
            "ffgpu_exec_forward_bgr_dev", "ffgpu_exec_forward_bgr_frames_dev", "ffgpu_exec_forward_nv12_frames_dev", "ffgpu_exec_dets_dev", "ffgpu_exec_dets_host", "ffgpu_exec_set_ring", "ffgpu_exec_set_ring_strided", "ffgpu_exec_read_dets", "ffgpu_exec_read_layer", "ffgpu_exec_hash_layers",
            "ffgpu_exec_read_boxes", "ffgpu_exec_cand_capacity", "ffgpu_exec_graph_captures",
-           "ffgpu_exec_profile", "ffgpu_exec_profile_steps", "ffgpu_exec_step_model", "ffgpu_groupconv_dev", "ffgpu_groupconv_kernel_name", "ffgpu_groupconv_time_dev", "ffgpu_irb_dev", "ffgpu_irb_plan_text", "ffgpu_irb_instantiations", "ffgpu_dwpw_dev", "ffgpu_packed_records_bytes", "ffgpu_pack_records", "ffgpu_unpack_records",
+           "ffgpu_exec_profile", "ffgpu_exec_profile_steps", "ffgpu_exec_step_model", "ffgpu_groupconv_dev", "ffgpu_groupconv_kernel_name", "ffgpu_groupconv_time_dev", "ffgpu_irb_dev", "ffgpu_irb_plan_text", "ffgpu_irb_instantiations", "ffgpu_knobs_text", "ffgpu_dwpw_dev", "ffgpu_packed_records_bytes", "ffgpu_pack_records", "ffgpu_unpack_records",
            "ffgpu_shard_range", "ffgpu_node_create", "ffgpu_node_destroy", "ffgpu_node_ndev", "ffgpu_node_shard", "ffgpu_node_set_scale",
            "ffgpu_node_input_dev", "ffgpu_node_input_slot_dev", "ffgpu_node_depth", "ffgpu_node_rccl_ranks", "ffgpu_node_forward", "ffgpu_node_forward_host",
            "ffgpu_node_submit", "ffgpu_node_wait", "ffgpu_node_run",
@@ -247,6 +247,7 @@ def lib():
     L.ffgpu_irb_dev.argtypes = [vp] * 6 + [i] * 13 + [vp]
     L.ffgpu_irb_plan_text.argtypes = [i] * 12 + [C.c_char_p, i]
     L.ffgpu_irb_instantiations.argtypes = [C.c_char_p, i]
+    L.ffgpu_knobs_text.argtypes = [C.c_char_p, i]
     L.ffgpu_exec_read_boxes.argtypes = [vp, i, vp, i]
     L.ffgpu_exec_cand_capacity.argtypes = [vp]
     L.ffgpu_exec_graph_captures.argtypes = [vp]
@@ -1162,6 +1163,20 @@ def irb_instantiations():
     if n < 0 or n >= len(buf):
         raise RuntimeError("ffgpu_irb_instantiations failed: %s" % (last_error() if n < 0 else "%d bytes" % n))
     return buf.value.decode().split()
+
+
+def knobs():
+    """every environment variable the library reads, in table order (no GPU needed): dicts of name, kind (INT / ON / SET / TEXT), default
+    (an int, "computed" or None), cls (product / tuning / test / lab), value (what a read returns now under os.environ, as text) and text"""
+    buf = C.create_string_buffer(1 << 16)
+    n = lib().ffgpu_knobs_text(buf, len(buf))
+    if n < 0 or n >= len(buf):
+        raise RuntimeError("ffgpu_knobs_text failed: %s" % (last_error() if n < 0 else "%d bytes" % n))
+    rows = []
+    for line in buf.value.decode().splitlines():
+        name, kind, dflt, cls, value, text = line.split(" ", 5)
+        rows.append({"name": name, "kind": kind, "default": None if dflt == "-" else dflt if dflt == "computed" else int(dflt), "cls": cls, "value": value, "text": text})
+    return rows
 
 
 def dwpw_dev(d_in, d_wd, d_wp, d_out, batch, iw, ih, c, oc, fs, actd=2, actp=0, warmup=0, iters=0, stream=None):

@@ -34,12 +34,6 @@ struct BareScratch {
     }
 };
 
-static int env_int(const char *name, int dflt)
-{
-    const char *v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
-}
-
 // CUs of the current device (a node plans on every GPU of the box), asked once per device and process (ADVICE r05: no runtime query per launch); 256 if the runtime does not say
 static int device_cus()
 {
@@ -97,7 +91,7 @@ static bool pw_mfma_ok(const ConvDesc &d)
 
 // split-bf16 pointwise kernel (ffgpu_pw_x3.inc): fp32-equivalent results on the bf16 matrix cores; worth it where the layer is a
 // real contraction (the expand / project layers inside fused blocks never get here)
-static int pw_x3_mt(const ConvDesc &d) { const int f = env_int("FFGPU_PWX3_MT", 0); return f == 4 || f == 2 || f == 1 ? f : 4; }
+static int pw_x3_mt(const ConvDesc &d) { const int f = knob(K_PWX3_MT); return f == 4 || f == 2 || f == 1 ? f : 4; }
 static bool pw_x3_ok(const ConvDesc &d)
 {
     const long P = (long)d.N * d.iw * d.ih;
@@ -109,8 +103,8 @@ static bool pw_x3_ok(const ConvDesc &d)
 static bool pw_x3_auto(const ConvDesc &d)
 {
     const long P = (long)d.N * d.iw * d.ih;
-    return pw_x3_ok(d) && d.ic >= env_int("FFGPU_PWX3_MIN_IC", 192) && d.oc >= env_int("FFGPU_PWX3_MIN_OC", 256) && P >= env_int("FFGPU_PWX3_MIN_P", 65536) &&
-           env_int("FFGPU_PW_X3", 1) != 0;
+    return pw_x3_ok(d) && d.ic >= knob(K_PWX3_MIN_IC) && d.oc >= knob(K_PWX3_MIN_OC) && P >= knob(K_PWX3_MIN_P) &&
+           knob(K_PW_X3) != 0;
 }
 // tiled split-bf16 GEMM (ffgpu_pw_x3t.inc): a workgroup splits every input value once per 256 output channels.  AUTO: real contractions with
 // enough pixels to fill the chip (BASELINE config[2]); FFGPU_PW_X3T=0: never.
@@ -122,12 +116,12 @@ static bool pw_x3t_ok(const ConvDesc &d)
 static bool pw_x3t_auto(const ConvDesc &d)
 {
     const long P = (long)d.N * d.iw * d.ih;
-    return pw_x3t_ok(d) && env_int("FFGPU_PW_X3T", 1) != 0 && d.ic >= env_int("FFGPU_PWX3T_MIN_IC", 128) && d.oc >= env_int("FFGPU_PWX3T_MIN_OC", 192) &&
-           P >= env_int("FFGPU_PWX3T_MIN_P", 65536);
+    return pw_x3t_ok(d) && knob(K_PW_X3T) != 0 && d.ic >= knob(K_PWX3T_MIN_IC) && d.oc >= knob(K_PWX3T_MIN_OC) &&
+           P >= knob(K_PWX3T_MIN_P);
 }
 // 32-row blocks per wave: workgroup tiles of 256 channels (default) or 128 (tuning, FFGPU_PWXT_TM=128).  Part of the packed image's layout: a planned layer carries it in
 // ConvDesc::x3_mt (ffgpu_conv_plan), pack and every launch read THAT -- the environment only decides for unplanned single-layer calls (ADVICE r05)
-static int  pwx3t_rb_env() { return env_int("FFGPU_PWXT_TM", 256) == 128 ? 1 : 2; }
+static int  pwx3t_rb_env() { return knob(K_PWXT_TM) == 128 ? 1 : 2; }
 static int  pwx3t_rb(const ConvDesc &d) { return (d.kernel == FFGPU_K_PW_X3T && (d.x3_mt == 1 || d.x3_mt == 2)) ? d.x3_mt : pwx3t_rb_env(); }
 static void pwx3t_dims(const ConvDesc &d, int &nchunks, int &ntm) { nchunks = ((d.ic + 2 * XT_KC - 1) / (2 * XT_KC)) * 2; ntm = (d.oc + xt_tm(pwx3t_rb(d)) - 1) / xt_tm(pwx3t_rb(d)); }     // chunks in pairs (zero weights behind ic)
 static size_t pwx3t_img_dwords(const ConvDesc &d) { int nc, ntm; pwx3t_dims(d, nc, ntm); return ((size_t)nc * xt_ach(pwx3t_rb(d)) + 2 * xt_tm(pwx3t_rb(d))) * ntm; }
@@ -165,7 +159,7 @@ static bool dw_lds_ok(const ConvDesc &d)
 static bool dw_pair_ok(const ConvDesc &d)
 {
     return dw_lds_ok(d) && d.fs == 5 && d.stride == 1 && d.pad == 2 && d.ic % 2 == 0 && d.iw % 2 == 0 && d.iw >= 6 && d.iw <= 40 && d.ih <= 40 &&
-           d.act != 3 && !(d.flags & FFGPU_COMPAT_V6) && (long)d.ic * d.N * d.iw * d.ih < (1L << 30) && !env_int("FFGPU_NO_DW_PAIR", 0);
+           d.act != 3 && !(d.flags & FFGPU_COMPAT_V6) && (long)d.ic * d.N * d.iw * d.ih < (1L << 30) && !knob(K_NO_DW_PAIR);
 }
 
 static int launch_dw_pair(const ConvDesc &d, hipStream_t s)
@@ -183,7 +177,7 @@ static int launch_dw_pair(const ConvDesc &d, hipStream_t s)
     const long plane2 = (long)p.LH * p.LW * 2;
     int NI = std::min(256 / p.TPI, (int)(64 * 1024 / 4 / plane2));
     NI = std::max(1, std::min(NI, d.N));
-    if (env_int("FFGPU_DWP_NI", 0) > 0) NI = std::min(env_int("FFGPU_DWP_NI", 0), NI);              // tuning only
+    if (const int f = knob(K_DWP_NI); f > 0) NI = std::min(f, NI);              // tuning only
     const int nb = (d.N + NI - 1) / NI;
     NI = (d.N + nb - 1) / nb;
     p.NI = NI;
@@ -231,7 +225,7 @@ static int igemm_wm(const ConvDesc &d) { return d.oc / d.groups > 64 ? 2 : 1; }
 static bool igemm_vec(const ConvDesc &d)
 {
     return d.fs == 3 && d.stride == 1 && d.pad == 1 && d.ow >= 4 && d.iw == d.ow && d.ih == d.oh &&
-           (long)d.N * d.oh * ((d.ow + 3) & ~3) < (1L << 31) && !env_int("FFGPU_IGEMM_NOVEC", 0);
+           (long)d.N * d.oh * ((d.ow + 3) & ~3) < (1L << 31) && !knob(K_IGEMM_NOVEC);
 }
 static int igemm_kc(const ConvDesc &d) { return igemm_vec(d) ? (igemm_wm(d) == 1 ? IG_KC3N : IG_KC3) : IG_KC; }
 // split-K: a layer whose tiles do not fill the chip (768 resident workgroups: 3 per CU) and whose K loop is long is cut along K
@@ -243,12 +237,13 @@ static int igemm_kc(const ConvDesc &d) { return igemm_vec(d) ? (igemm_wm(d) == 1
 static int igemm_split(const ConvDesc &d)
 {
     if (d.nsplit > 0) return d.nsplit;
-    const int f = env_int("FFGPU_IGEMM_SPLIT", 0);
+    const int f = knob(K_IGEMM_SPLIT);
     const int WM = d.oc / d.groups > 64 ? 2 : 1, TN = WM == 2 ? 128 : 256, kc = igemm_kc(d);
     const long P = (long)d.N * d.oh * (igemm_vec(d) ? (d.ow + 3) & ~3 : d.ow), tiles = ((P + TN - 1) / TN) * ((d.oc / d.groups + 64 * WM - 1) / (64 * WM)) * d.groups;      // (all groups in one grid)
     const int nchunks = (d.fs * d.fs * (d.ic / d.groups) + kc - 1) / kc;
     int S = 1;
-    while (S < 8 && tiles * (S + 1) <= env_int("FFGPU_IGEMM_SPLIT_SLOTS", 768) && nchunks / (S + 1) >= 4) S++;
+    const long slots = 768;                                         // the split stops where tiles x S would pass this many workgroups
+    while (S < 8 && tiles * (S + 1) <= slots && nchunks / (S + 1) >= 4) S++;
     if (f >= 1 && f <= 16) S = std::min(f, std::max(1, nchunks));
     return S;
 }
@@ -271,20 +266,20 @@ static bool ig_x3_ok(const ConvDesc &d)
         return d.stride == 1 && d.pad == 0 && conv_cnhw_contiguous(d) && ((long)d.N * d.ih * d.iw) % 4 == 0;
     if ((long)d.N * d.oh * ((d.ow + 3) & ~3) >= (1L << 31) - 64 || d.ow < 4) return false;
     if (d.fs == 3 && d.stride == 2 && d.pad == 1)      // the downsampling form: even planes
-        return d.iw == 2 * d.ow && d.ih == 2 * d.oh && env_int("FFGPU_IGX3_S2", 1) != 0;
+        return d.iw == 2 * d.ow && d.ih == 2 * d.oh && knob(K_IGX3_S2) != 0;
     return igemm_vec(d) && d.iw >= 4;
 }
 // waves per workgroup: 4 (two workgroups per CU, out of phase) measured ahead of 8 on every stride-1 layer; the stride-2 form (256 VGPRs, a few spills in its
 // 4-wave build) is level or ahead with 8
-static int ig_x3_nw(const ConvDesc &d) { const int f = env_int("FFGPU_IGX3_NW", 0); return f == 8 || f == 4 ? f : (d.stride == 2 ? 8 : 4); }
+static int ig_x3_nw(const ConvDesc &d) { const int f = knob(K_IGX3_NW); return f == 8 || f == 4 ? f : (d.stride == 2 ? 8 : 4); }
 static long ig_x3_npg(const ConvDesc &d) { const long ntn = ((long)d.N * d.oh * (d.fs == 1 ? d.ow : (d.ow + 3) & ~3) + 63) / 64; return (ntn + ig_x3_nw(d) - 1) / ig_x3_nw(d); }
 // 16-row blocks per wave: 4 (every split input value feeds 64 output channels) while that leaves enough workgroups, else 2
 static int ig_x3_mt_plan(const ConvDesc &d)
 {
-    const int f = env_int("FFGPU_IGX3_MT", 0);
+    const int f = knob(K_IGX3_MT);
     if (f == 4 || f == 2 || f == 1) return f;
     if (d.oc <= 32 || d.stride == 2) return d.oc <= 16 ? 1 : 2;     // (stride 2: nine input columns per lane -- no registers for four blocks)
-    return ig_x3_npg(d) * ((d.oc + 63) / 64) >= env_int("FFGPU_IGX3_MT4_WGS", 192) ? 4 : 2;
+    return ig_x3_npg(d) * ((d.oc + 63) / 64) >= knob(K_IGX3_MT4_WGS) ? 4 : 2;
 }
 static int ig_x3_mt(const ConvDesc &d) { const int m = d.x3_mt == 4 || d.x3_mt == 2 || d.x3_mt == 1 ? d.x3_mt : ig_x3_mt_plan(d); return d.stride == 2 && m > 2 ? 2 : m; }
 static void ig_x3_dims(const ConvDesc &d, int &MT, int &ngr, int &nrb, int &ntm) { MT = ig_x3_mt(d); ngr = (d.fs * (d.ic / 8) + 3) / 4; nrb = (d.oc + 15) / 16; ntm = (nrb + MT - 1) / MT; }
@@ -298,10 +293,10 @@ static bool ig_x3_auto(const ConvDesc &d)
     // pointwise form: the heads' layers of yolo-fastest (>= 96 channels either side) -- alone 15.6 -> 11.8 us (120 -> 120 on 20x20 x 64) and 24.9 -> 16.7 us
     // (120 -> 255), the 10x10 ones level; with four chains in flight the seven layers together: 193.9 k -> 202.3 k frames/s (same box, alternating).  FFGPU_PW_X3S=0: never
     if (d.fs == 1)
-        return env_int("FFGPU_PW_X3S", 1) != 0 && d.ic >= env_int("FFGPU_PWX3S_MIN_IC", 96) && d.oc >= env_int("FFGPU_PWX3S_MIN_OC", 64) &&
-               ig_x3_npg(d) * ntm >= env_int("FFGPU_PWX3S_MIN_WGS", 64);
-    if (env_int("FFGPU_IG_X3", 1) == 0) return false;
-    return d.ic >= env_int("FFGPU_IGX3_MIN_IC", 16) && ig_x3_npg(d) * ntm >= env_int("FFGPU_IGX3_MIN_WGS", 160);
+        return knob(K_PW_X3S) != 0 && d.ic >= knob(K_PWX3S_MIN_IC) && d.oc >= knob(K_PWX3S_MIN_OC) &&
+               ig_x3_npg(d) * ntm >= knob(K_PWX3S_MIN_WGS);
+    if (knob(K_IG_X3) == 0) return false;
+    return d.ic >= knob(K_IGX3_MIN_IC) && ig_x3_npg(d) * ntm >= knob(K_IGX3_MIN_WGS);
 }
 static int ig_x3_pack(const ConvDesc &d, float *pk, hipStream_t s)
 {
@@ -320,20 +315,20 @@ static int conv_pick(const ConvDesc &d, int variant)
 {
     if (variant != FFGPU_K_AUTO) return variant;
     if (d.kernel) return d.kernel;                       // frozen with the plan (ffgpu_conv_plan)
-    static const int force_generic = env_int("FFGPU_FORCE_GENERIC", 0);
-    if (force_generic) return FFGPU_K_GENERIC;
+    if (knob(K_FORCE_GENERIC)) return FFGPU_K_GENERIC;
     if (dw_stream_ok(d)) return FFGPU_K_DW_STREAM;
     if (!(d.flags & FFGPU_BF16_PW) && pw_x3t_auto(d)) return FFGPU_K_PW_X3T;                  // (config[2]: the tiled form, round 5)
     if (!(d.flags & FFGPU_BF16_PW) && d.fs == 1 && ig_x3_auto(d)) return FFGPU_K_CONV_X3;     // (ahead of k_pw_x3 wherever both apply: config[2] 171 against 199 us on one box)
     if (!(d.flags & FFGPU_BF16_PW) && pw_x3_auto(d)) return FFGPU_K_PW_X3;
     if ((d.flags & FFGPU_BF16_PW) && pw_gemm_ok(d) && d.oc >= 128 && d.ic >= 128 && (long)d.N * d.iw * d.ih >= 16384) return FFGPU_K_PW_BF16;   // opt-in only
-    if (pw_gemm_ok(d) && d.oc >= env_int("FFGPU_PWG_MIN_OC", 128) && d.ic >= env_int("FFGPU_PWG_MIN_IC", 64) && (long)d.N * d.iw * d.ih >= 16384 && !env_int("FFGPU_NO_PW_GEMM", 0)) return FFGPU_K_PW_GEMM;
+    if (pw_gemm_ok(d) && d.oc >= knob(K_PWG_MIN_OC) && d.ic >= knob(K_PWG_MIN_IC) && (long)d.N * d.iw * d.ih >= 16384 && !knob(K_NO_PW_GEMM)) return FFGPU_K_PW_GEMM;
     if (pw_mfma_ok(d)) return FFGPU_K_PW_MFMA;
     if (dw_lds_ok(d)) return FFGPU_K_DW_LDS;
     if (dense_small_ok(d)) return FFGPU_K_DENSE_SMALL;
-    if (ig_x3_auto(d) && !env_int("FFGPU_NO_IGEMM", 0)) return FFGPU_K_CONV_X3;
-    if (igemm_ok(d) && d.ic / d.groups >= 8 && !env_int("FFGPU_NO_IGEMM", 0)) return FFGPU_K_IGEMM;
-    if (group_thin_ok(d) && !env_int("FFGPU_NO_GROUP_THIN", 0)) return FFGPU_K_GROUP_THIN;
+    const bool igemm_on = !knob(K_NO_IGEMM);
+    if (igemm_on && ig_x3_auto(d)) return FFGPU_K_CONV_X3;
+    if (igemm_on && igemm_ok(d) && d.ic / d.groups >= 8) return FFGPU_K_IGEMM;
+    if (group_thin_ok(d) && !knob(K_NO_GROUP_THIN)) return FFGPU_K_GROUP_THIN;
     return FFGPU_K_GENERIC;
 }
 
@@ -353,8 +348,7 @@ template <int NV, int U, bool NT>
 static void dw_stream_launch(const DwStreamP &p, hipStream_t s)
 {
     const long blocks = (p.ntasks + 3) / 4;
-    const int lds = env_int("FFGPU_DW_LDS", 0);      // tuning only: dummy LDS to cap waves per CU
-    hipLaunchKernelGGL((k_dw3_stream<NV, U, NT>), dim3((unsigned)blocks), dim3(256), (size_t)lds, s, p);
+    hipLaunchKernelGGL((k_dw3_stream<NV, U, NT>), dim3((unsigned)blocks), dim3(256), 0, s, p);
 }
 
 static int launch_dw_stream(const ConvDesc &d, const float *, hipStream_t s)
@@ -362,8 +356,8 @@ static int launch_dw_stream(const ConvDesc &d, const float *, hipStream_t s)
     // defaults from the sweep in profiles/r01_dw3_tuning.txt: 4-row tasks walked in address order keep the
     // chip-wide access window compact (5.95 TB/s vs 4.95 TB/s for one long stream per wave)
     // NT: outputs of 128 MB and more are streamed past the caches (ffgpu_dw_stream.inc DW_NT_MASK; FFGPU_DW_NT=0 / 1 forces)
-    const int U = env_int("FFGPU_DW_U", 4), BAND = env_int("FFGPU_DW_BAND", 4);
-    const int nt_env = env_int("FFGPU_DW_NT", -1), NT = nt_env >= 0 ? nt_env : ((long)d.ic * d.N * d.iw * d.ih * 4 >= (128L << 20));
+    const int U = knob(K_DW_U), BAND = knob(K_DW_BAND);
+    const int nt_env = knob(K_DW_NT), NT = nt_env >= 0 ? nt_env : ((long)d.ic * d.N * d.iw * d.ih * 4 >= (128L << 20));
     DwStreamP p;
     p.in = d.in; p.filt = d.filt; p.out = d.out; p.residual = nullptr;
     p.W = d.iw; p.H = d.ih; p.planes = d.ic * d.N; p.N = d.N;
@@ -381,7 +375,7 @@ static int launch_dw_stream(const ConvDesc &d, const float *, hipStream_t s)
     p.rowlen = conv_k4(d) + 4; p.act = d.act; p.res_act = 0;
     p.ntasks = pgroups * p.nbands;
     p.nblocks = (p.ntasks + 3) / 4;
-    p.xcd_remap = env_int("FFGPU_DW_XCD", 0);
+    p.xcd_remap = knob(K_DW_XCD);
     if (NV == 1) {
         if (U == 1)      { if (NT) dw_stream_launch<1, 1, true>(p, s); else dw_stream_launch<1, 1, false>(p, s); }
         else if (U == 2) { if (NT) dw_stream_launch<1, 2, true>(p, s); else dw_stream_launch<1, 2, false>(p, s); }
@@ -412,7 +406,7 @@ static int pw_launch(const PwP &p, int ocblocks, hipStream_t s)
 {
     const size_t lds = ((size_t)p.k4 * OT * 16 + OT * 32 + (KSP > 1 ? (size_t)(KSP - 1) * OT * 16 * 64 : 0)) * sizeof(float);
     // a big weight image limits workgroups per CU: 8 waves share it so 4 waves per SIMD keep the MFMA pipe fed
-    if (KSP == 1 && lds > 40 * 1024 && !env_int("FFGPU_PW_NW4", 0)) return pw_launch_t<OT, KSP, 8>(p, ocblocks, lds, s);
+    if (KSP == 1 && lds > 40 * 1024) return pw_launch_t<OT, KSP, 8>(p, ocblocks, lds, s);
     return pw_launch_t<OT, KSP, 4>(p, ocblocks, lds, s);
 }
 
@@ -422,7 +416,7 @@ static int pw_launch(const PwP &p, int ocblocks, hipStream_t s)
 static int pw_ot(int oc, long nstrips)
 {
     int ot = oc <= 16 ? 1 : (oc <= 32 ? 2 : (oc <= 48 ? 3 : 4));
-    const long target = env_int("FFGPU_PW_WAVES", 1536);
+    const long target = 1536;                        // (the shape alone: pack and launch must agree on it)
     while (ot > 1 && nstrips * ((oc + ot * 16 - 1) / (ot * 16)) < target) ot = ot == 3 ? 2 : ot / 2;
     return ot;
 }
@@ -437,7 +431,8 @@ static int launch_pw_mfma(const ConvDesc &d, const float *image, hipStream_t s)
     p.wpack = image;                     // (none: the kernel builds its LDS image from the filter rows)
     const int OT = pw_ot(d.oc, p.nstrips), ocblocks = (d.oc + OT * 16 - 1) / (OT * 16);
     // still too few waves and a long K loop: let the 4 waves of a workgroup split K (the 10x10 tail)
-    const bool ksplit = p.nstrips * ocblocks < env_int("FFGPU_PW_KS_WAVES", 1024) && p.k4 >= 32 && !env_int("FFGPU_PW_NOKS", 0);
+    const long ks_waves = 1024;
+    const bool ksplit = p.nstrips * ocblocks < ks_waves && p.k4 >= 32;
     switch (OT) {
     case 1: return ksplit ? pw_launch<1, 4>(p, ocblocks, s) : pw_launch<1, 1>(p, ocblocks, s);
     case 2: return ksplit ? pw_launch<2, 4>(p, ocblocks, s) : pw_launch<2, 1>(p, ocblocks, s);
@@ -481,7 +476,7 @@ static int pw_mfma_pack(const ConvDesc &d, float *pk, hipStream_t s)
 }
 
 // waves per workgroup of the pointwise GEMM: 8 (256-channel tiles: the input chunk shared by twice as many waves) from 256 filters up
-static int pwg32_wm(const ConvDesc &d) { const int f = env_int("FFGPU_PWG_WM", 0); return f == 4 || f == 8 ? f : (d.oc >= 256 - 8 ? 8 : 4); }
+static int pwg32_wm(const ConvDesc &d) { const int f = knob(K_PWG_WM); return f == 4 || f == 8 ? f : (d.oc >= 256 - 8 ? 8 : 4); }
 static void pwg32_dims(const ConvDesc &d, int &nchunks, int &ntm) { nchunks = (d.ic + PWG_KC - 1) / PWG_KC; ntm = (d.oc + 32 * pwg32_wm(d) - 1) / (32 * pwg32_wm(d)); }
 static int pwg32_img(const ConvDesc &d) { int nc, ntm; pwg32_dims(d, nc, ntm); return nc * 512 * pwg32_wm(d) + 64 * pwg32_wm(d); }
 static size_t pwg32_img_dwords(const ConvDesc &d) { int nc, ntm; pwg32_dims(d, nc, ntm); return (size_t)pwg32_img(d) * ntm; }
@@ -570,13 +565,13 @@ static int launch_pw_gemm(const ConvDesc &d, const float *image, hipStream_t s)
     p.img = pwg32_img(d);
     p.wpack = image;
     // resident workgroups per CU: 4 of the 4-wave form (LDS 33 KB, 16 waves), 3 of the 8-wave form (LDS 50 KB, 24 waves)
-    const int slots = (p.wm == 8 ? env_int("FFGPU_PWG_SLOTS8", 3) : 4) * device_cus();
+    const int slots = (p.wm == 8 ? 3 : 4) * device_cus();
     long ntn_main, ntn_narrow;
-    split_main_narrow(p.P, p.ntm, slots, env_int("FFGPU_PWG_NARROW", 1) != 0, &ntn_main, &ntn_narrow);
+    split_main_narrow(p.P, p.ntm, slots, knob(K_PWG_NARROW) != 0, &ntn_main, &ntn_narrow);
     p.ntn = ntn_main;
     const long total = p.ntn * p.ntm;
     p.per_xcd = (int)((total + 7) / 8);
-    p.dbg = env_int("FFGPU_PWG_DBG", 0);
+    p.dbg = knob(K_PWG_DBG);
     const dim3 grid((unsigned)(8 * p.per_xcd + ntn_narrow * p.ntm));
     if (p.wm == 8) hipLaunchKernelGGL(k_pw_gemm32<8>, grid, dim3(512), 0, s, p);
     else           hipLaunchKernelGGL(k_pw_gemm32<4>, grid, dim3(256), 0, s, p);
@@ -602,7 +597,6 @@ static int launch_pw_x3(const ConvDesc &d, const float *image, hipStream_t s)
     long nslots = std::max(1L, (long)cus * per_cu / p.ntm);
     nslots = std::min(nslots, (p.ntn + 7) / 8);
     if (nslots >= 8) nslots &= ~7L;                               // a multiple of the XCD count: the channel tiles of a pixel range share an XCD's L2 (see the kernel)
-    if (env_int("FFGPU_PWX3_SLOTS", 0) > 0) nslots = env_int("FFGPU_PWX3_SLOTS", 0);
     p.nslots = (int)nslots;
     const dim3 grid((unsigned)(nslots * p.ntm));
 #define PWX3_LAUNCH(mt) do { if (lds_allow((const void *)k_pw_x3<mt>, lds, "pw_x3")) return -1; hipLaunchKernelGGL((k_pw_x3<mt>), grid, dim3(512), lds, s, p); } while (0)
@@ -623,21 +617,21 @@ static int launch_pw_x3t(const ConvDesc &d, const float *image, hipStream_t s)
     p.wpack = reinterpret_cast<const unsigned *>(image);
     const int slots = (RBv == 2 ? 2 : 3) * device_cus();          // resident workgroups: two of the 256-channel form per CU, three of the 128-channel one
     long ntn_main, ntn_narrow;
-    split_main_narrow(p.P, p.ntm, slots, env_int("FFGPU_PWXT_NARROW", 1) != 0, &ntn_main, &ntn_narrow);
+    split_main_narrow(p.P, p.ntm, slots, knob(K_PWXT_NARROW) != 0, &ntn_main, &ntn_narrow);
     p.ntn = ntn_main;
     const long total = p.ntn * p.ntm;
     p.per_xcd = (int)((total + 7) / 8);
     p.nmain = 8 * p.per_xcd; p.tpw = 1;
-    if (env_int("FFGPU_PWXT_PERSIST", 0) && total > slots) {      // tuning: persistent workgroups over the main tiles (slots of them, a multiple of 8)
+    if (knob(K_PWXT_PERSIST) && total > slots) {      // tuning: persistent workgroups over the main tiles (slots of them, a multiple of 8)
         p.nmain = slots / 8 * 8;
         p.tpw = (int)((8L * p.per_xcd + p.nmain - 1) / p.nmain);
     }
-    p.dbg = env_int("FFGPU_PWXT_DBG", 0);
-    { const int nt = env_int("FFGPU_PWXT_NT", -1); p.nt = nt >= 0 ? (nt != 0) : ((long)d.oc * p.P * 4 >= (128L << 20)); }
+    p.dbg = knob(K_PWXT_DBG);
+    { const int nt = knob(K_PWXT_NT); p.nt = nt >= 0 ? (nt != 0) : ((long)d.oc * p.P * 4 >= (128L << 20)); }
     const dim3 grid((unsigned)(p.nmain + ntn_narrow * p.ntm));
     p.dbg_t = nullptr;
 #if XT_TRACE                                                        // lab builds: one traced launch, dumped as text (tile words) to FFGPU_PWXT_TRACE
-    if (const char *tf = getenv("FFGPU_PWXT_TRACE")) {
+    if (const char *tf = knob_text(K_PWXT_TRACE)) {
         const size_t nw = (size_t)((p.P + 31) / 32 + 4) * p.ntm * 8;
         unsigned long long *d_t = nullptr;
         if (hipMalloc(&d_t, nw * 8) != hipSuccess) return -1;
@@ -765,7 +759,7 @@ static int launch_dw_lds(const ConvDesc &d, const float *, hipStream_t s)
     // band height: ~1024 outputs per plane-band, input window <= 32 KB
     int BH = d.oh;
     while (BH > 1 && ((long)BH * d.ow > 1024 || ((long)(BH - 1) * d.stride + d.fs) * p.LW * 4 > 32 * 1024)) BH = (BH + 1) / 2;
-    if (env_int("FFGPU_DWL_BH", 0) > 0) BH = std::min(env_int("FFGPU_DWL_BH", 0), d.oh);       // tuning only
+    if (const int f = knob(K_DWL_BH); f > 0) BH = std::min(f, d.oh);       // tuning only
     p.BH = BH; p.nbands = (d.oh + BH - 1) / BH;
     p.IH = (BH - 1) * d.stride + d.fs;
     int NPL = 1;
@@ -773,7 +767,7 @@ static int launch_dw_lds(const ConvDesc &d, const float *, hipStream_t s)
     //  of the heads, so items are as large as LDS allows while a few per CU remain)
     while (NPL < 16 && (long)(NPL * 2) * BH * d.ow <= 4096 && (long)(NPL * 2) * p.IH * p.LW * 4 <= 32 * 1024 &&
            (long)p.planes * p.nbands / (NPL * 2) >= 600) NPL *= 2;
-    if (env_int("FFGPU_DWL_NPL", 0) > 0) NPL = env_int("FFGPU_DWL_NPL", 0);                      // tuning only
+    if (const int f = knob(K_DWL_NPL); f > 0) NPL = f;                      // tuning only
     p.NPL = NPL;
     p.nitems = (((long)p.planes + NPL - 1) / NPL) * p.nbands;
     const long ppl = (long)p.IH * p.LW, owq = (d.ow + 3) / 4, per = (long)BH * owq;
@@ -798,7 +792,7 @@ static int launch_dense_small(const ConvDesc &d, const float *, hipStream_t s)
     // four pixels per thread -- fewer issue slots, chosen when the batch is big enough for issue slots to be what counts
     if (d.fs == 3 && (d.stride == 2 || d.stride == 1) && d.pad == 1 && d.ic == 3 && !d.residual && d.act != 3 && d.iw == d.stride * d.ow && d.ih == d.stride * d.oh &&
         d.ow % 4 == 0 && d.in_cs % 4 == 0 && d.in_ns % 4 == 0 && d.out_cs % 4 == 0 && d.out_ns % 4 == 0 && d.in_ns < (1L << 30) &&
-        d.out_ns * d.N < (1L << 30) && (long)d.N * d.oh * d.ow >= env_int("FFGPU_CONV_FIRST_MIN_PX", 262144) && !env_int("FFGPU_NO_CONV_FIRST", 0)) {
+        d.out_ns * d.N < (1L << 30) && (long)d.N * d.oh * d.ow >= knob(K_CONV_FIRST_MIN_PX) && !knob(K_NO_CONV_FIRST)) {
         const int owq = d.ow / 4, per = d.oh * owq;
         const unsigned m = umulhi_magic(owq);
         const dim3 grid((per + 255) / 256, d.N, (d.oc + 7) / 8);
@@ -1063,7 +1057,7 @@ static int irb_launch_t(const P &p, const IrbPlan &c, hipStream_t s)
 {
     const char *const what = irb_trace_of(p).what;
     if (lds_allow((const void *)K, (size_t)c.lds, what)) return -1;
-    if (env_int("FFGPU_IRB_TRACE", 0)) {
+    if (knob(K_IRB_TRACE)) {
         P q = p;
         if (!(q.dbg_t = irb_trace_begin(s))) return -1;
         hipLaunchKernelGGL(K, dim3((unsigned)c.grid), dim3(c.block), (size_t)c.lds, s, q);
@@ -1081,7 +1075,7 @@ static bool irb_thin_ok(const IrbDesc &d)
 {
     return d.stride == 1 && d.ec == 8 && (d.ic == 4 || d.ic == 8) && (d.oc == 4 || d.oc == 8) && d.W % 4 == 0 && d.W / 4 <= 64 &&
            8L * d.N * d.W * d.H < (1L << 30) &&          // 32-bit offsets inside a frame-major tensor
-           d.act1 != 3 && d.actd != 3 && d.act2 != 3 && d.res_act != 3 && !env_int("FFGPU_NO_THIN", 0);
+           d.act1 != 3 && d.actd != 3 && d.act2 != 3 && d.res_act != 3 && !knob(K_NO_THIN);
 }
 
 // rows per wave of k_irb_thin and k_front: every band expands two extra rows, so long bands waste least -- but the launch wants ~1000 waves;
@@ -1128,22 +1122,22 @@ static int launch_irb_thin(const IrbDesc &d, hipStream_t s)
 // ---- wave-autonomous form (ffgpu_irb_wave.inc, ffgpu_irb_wave2.inc): every instantiation that exists, shape test, tile / split choice, launch shape
 typedef int (*IrbwLaunch)(const IrbwP &, const IrbPlan &, hipStream_t);
 // S: stride; NSI: input strips per wave; NSO: output strips per wave (2: k_irbw2); big: the 256-register budget; x3: expand GEMM as split-bf16 products;
-// xl: the split tile once per workgroup in LDS; gate: the switch that lets the planner consider the shape at all (NULL: always), with its default
-struct IrbwKernel { int KS1, OT, S, NSI, NSO; bool big, x3, xl; const char *gate; int gate_dflt; IrbwLaunch launch; };
+// xl: the split tile once per workgroup in LDS; gate: the switch that lets the planner consider the shape at all (K_NONE: always)
+struct IrbwKernel { int KS1, OT, S, NSI, NSO; bool big, x3, xl; Knob gate; IrbwLaunch launch; };
 // (entries in the order the instantiations have always been named in, which is the order the compiler emits them in: listings of two builds compare line by line)
-#define IRBW_K(ks1, ot, st, nsi, gate, dflt) \
-    { ks1, ot, st, nsi, 1, true, false, false, gate, dflt, irb_launch_t<IrbwP, k_irbw<ks1, ot, st, nsi, true>> }, \
-    { ks1, ot, st, nsi, 1, false, false, false, gate, dflt, irb_launch_t<IrbwP, k_irbw<ks1, ot, st, nsi, false>> }
+#define IRBW_K(ks1, ot, st, nsi, gate) \
+    { ks1, ot, st, nsi, 1, true, false, false, gate, irb_launch_t<IrbwP, k_irbw<ks1, ot, st, nsi, true>> }, \
+    { ks1, ot, st, nsi, 1, false, false, false, gate, irb_launch_t<IrbwP, k_irbw<ks1, ot, st, nsi, false>> }
 static const IrbwKernel irbw_kernels[] = {
-    { 2, 1, 1, 3, 2, true, true, false, nullptr, 0, irb_launch_t<IrbwP, k_irbw2<2, 3, true>> }, { 4, 1, 1, 3, 2, true, true, false, nullptr, 0, irb_launch_t<IrbwP, k_irbw2<4, 3, true>> },
-    { 2, 1, 1, 3, 2, true, false, false, nullptr, 0, irb_launch_t<IrbwP, k_irbw2<2, 3, false>> }, { 4, 1, 1, 3, 2, true, false, false, nullptr, 0, irb_launch_t<IrbwP, k_irbw2<4, 3, false>> },
-    { 12, 3, 1, 2, 1, true, true, true, nullptr, 0, irb_launch_t<IrbwP, k_irbw<12, 3, 1, 2, true, true, true>> },
-    { 4, 2, 2, 4, 1, true, true, false, nullptr, 0, irb_launch_t<IrbwP, k_irbw<4, 2, 2, 4, true, true>> },
-    { 6, 2, 1, 2, 1, true, true, false, nullptr, 0, irb_launch_t<IrbwP, k_irbw<6, 2, 1, 2, true, true>> },
-    IRBW_K(1, 1, 1, 2, nullptr, 0), IRBW_K(2, 1, 1, 2, nullptr, 0), IRBW_K(4, 1, 1, 2, nullptr, 0), IRBW_K(2, 2, 1, 2, nullptr, 0), IRBW_K(4, 2, 1, 2, nullptr, 0),
-    IRBW_K(6, 2, 1, 2, nullptr, 0), IRBW_K(12, 3, 1, 2, nullptr, 0), IRBW_K(1, 1, 2, 3, nullptr, 0), IRBW_K(2, 1, 2, 3, nullptr, 0), IRBW_K(4, 2, 2, 4, nullptr, 0),
-    IRBW_K(6, 3, 2, 3, "FFGPU_IRBW_S2_633", 1),
-    IRBW_K(1, 1, 2, 4, "FFGPU_IRBW_S2_NSI4", 0), IRBW_K(2, 1, 2, 4, "FFGPU_IRBW_S2_NSI4", 0),     // four-strip halo for the thin stride-2 blocks (12 of 16 output quads instead of 8)
+    { 2, 1, 1, 3, 2, true, true, false, K_NONE, irb_launch_t<IrbwP, k_irbw2<2, 3, true>> }, { 4, 1, 1, 3, 2, true, true, false, K_NONE, irb_launch_t<IrbwP, k_irbw2<4, 3, true>> },
+    { 2, 1, 1, 3, 2, true, false, false, K_NONE, irb_launch_t<IrbwP, k_irbw2<2, 3, false>> }, { 4, 1, 1, 3, 2, true, false, false, K_NONE, irb_launch_t<IrbwP, k_irbw2<4, 3, false>> },
+    { 12, 3, 1, 2, 1, true, true, true, K_NONE, irb_launch_t<IrbwP, k_irbw<12, 3, 1, 2, true, true, true>> },
+    { 4, 2, 2, 4, 1, true, true, false, K_NONE, irb_launch_t<IrbwP, k_irbw<4, 2, 2, 4, true, true>> },
+    { 6, 2, 1, 2, 1, true, true, false, K_NONE, irb_launch_t<IrbwP, k_irbw<6, 2, 1, 2, true, true>> },
+    IRBW_K(1, 1, 1, 2, K_NONE), IRBW_K(2, 1, 1, 2, K_NONE), IRBW_K(4, 1, 1, 2, K_NONE), IRBW_K(2, 2, 1, 2, K_NONE), IRBW_K(4, 2, 1, 2, K_NONE),
+    IRBW_K(6, 2, 1, 2, K_NONE), IRBW_K(12, 3, 1, 2, K_NONE), IRBW_K(1, 1, 2, 3, K_NONE), IRBW_K(2, 1, 2, 3, K_NONE), IRBW_K(4, 2, 2, 4, K_NONE),
+    IRBW_K(6, 3, 2, 3, K_IRBW_S2_633),
+    IRBW_K(1, 1, 2, 4, K_IRBW_S2_NSI4), IRBW_K(2, 1, 2, 4, K_IRBW_S2_NSI4),     // four-strip halo for the thin stride-2 blocks (12 of 16 output quads instead of 8)
 };
 #undef IRBW_K
 static const int irbw_nkernels = (int)(sizeof irbw_kernels / sizeof irbw_kernels[0]);
@@ -1152,7 +1146,7 @@ static const int irbw_nkernels = (int)(sizeof irbw_kernels / sizeof irbw_kernels
 static bool irbw_has_kernel(int KS1, int OT, int S, int NSI)
 {
     for (const IrbwKernel &k : irbw_kernels)
-        if (k.KS1 == KS1 && k.OT == OT && k.S == S && k.NSI == NSI && k.NSO == 1 && !k.x3) return !k.gate || env_int(k.gate, k.gate_dflt) != 0;
+        if (k.KS1 == KS1 && k.OT == OT && k.S == S && k.NSI == NSI && k.NSO == 1 && !k.x3) return k.gate == K_NONE || knob(k.gate) != 0;
     return false;
 }
 
@@ -1160,7 +1154,7 @@ static long irbw_ntiles(const IrbDesc &d, int TWq, int TH) { return (long)d.N * 
 
 static bool irbw_pick(const IrbDesc &d, IrbPlan &c)
 {
-    if (env_int("FFGPU_NO_IRBW", 0)) return false;
+    if (knob(K_NO_IRBW)) return false;
     if (d.stride != 1 && d.stride != 2) return false;
     if (d.act1 == 3 || d.actd == 3 || d.act2 == 3 || d.res_act == 3) return false;
     if ((size_t)d.ic * d.N * d.H * d.W >= (1u << 30) || (size_t)d.oc * d.N * d.OH * d.OW >= (1u << 30)) return false;   // 32-bit byte offsets
@@ -1184,7 +1178,7 @@ static bool irbw_pick(const IrbDesc &d, IrbPlan &c)
         }
     }
     if (best > 1e29) return false;
-    const int ft = env_int("FFGPU_IRBW_TWQ", 0), fh = env_int("FFGPU_IRBW_TH", 0);
+    const int ft = knob(K_IRBW_TWQ), fh = knob(K_IRBW_TH);
     if (ft > 0 && fh > 0 && ft * fh <= 16) {
         const int EW = S == 1 ? 4 * ft + 4 : 8 * ft + 4, EH = S * (fh - 1) + 3;
         if (EW * EH <= c.NSI * 64) { c.TWq = ft; c.TH = fh; c.EW = EW; c.EH = EH; }
@@ -1194,46 +1188,47 @@ static bool irbw_pick(const IrbDesc &d, IrbPlan &c)
     c.big = regs > 124;
     // (the BIG instantiation of a shape whose second set of expand accumulators fits is the software-pipelined form;
     //  it buys a lone wave nothing and costs the many-round launches occupancy, so it is not forced: FFGPU_IRBW_BIG=1)
-    if (env_int("FFGPU_IRBW_BIG", -1) >= 0) c.big = env_int("FFGPU_IRBW_BIG", -1) != 0;                 // tuning only
-    if (S == 2 && c.KS1 == 1 && env_int("FFGPU_IRBW_BIG_S2K1", -1) >= 0) c.big = env_int("FFGPU_IRBW_BIG_S2K1", -1) != 0;   // tuning only: the 160 -> 80 block alone (40 bytes of scratch at 128 registers)
+    if (const int f = knob(K_IRBW_BIG); f >= 0) c.big = f != 0;                 // tuning only
+    if (const int f = S == 2 && c.KS1 == 1 ? knob(K_IRBW_BIG_S2K1) : -1; f >= 0) c.big = f != 0;   // tuning only: the 160 -> 80 block alone (40 bytes of scratch at 128 registers)
     // waves sharing a tile: one wave per tile when that already gives every SIMD a wave or more (tools/tune_irbw.py:
     // the split only pays on the small planes), else the smallest split that does
     // With several chains in flight (FFGPU_CONCURRENT) other launches fill the SIMDs, and what counts is the work per
     // wave that a split repeats (input tile, constants, reduction): 4 waves on the 10x10 planes and 2 on the 20x20 ones
     // instead of 8 and 4 -- 3.5 % more frames/s with four chains, 4 % fewer with one.
     const bool conc = (d.flags & FFGPU_CONCURRENT) != 0;
+    const int x3_mask = knob(K_IRBW_X3);                            // one bit per shape that has a split-bf16 expand
     const int gmax = std::min(8, c.ngroups);
     int G = 1;
     for (int g = 1; g <= gmax; g++) {
         const size_t slot = (size_t)c.OT * 1024, ereg = (size_t)g * 16 * c.NSI * 64;
         if (g > 1 && ereg / slot < (size_t)(g + 1) / 2) continue;                                      // reduction must fit the E slices
         G = g;
-        if (ntiles * g >= env_int("FFGPU_IRBW_GWAVES", conc ? 500 : 1200)) break;
+        if (ntiles * g >= knob_or(K_IRBW_GWAVES, conc ? 500 : 1200)) break;
     }
     if (!conc && G > 1 && G < gmax && c.ngroups % G != 0 && (c.ngroups + G) / (G + 1) <= (c.ngroups + G - 1) / G) G++;   // same trips per wave, better balance
     // measured exceptions (profiles/r01_g_irbw_sweep.txt, batch 64): four waves on the 20x20 blocks (3, 2, 2, 2 groups
     // each) beat three by 8 %
-    if (d.stride == 1 && c.ngroups == 9 && ntiles >= 400 && ntiles < 512 && gmax >= 4 && !conc && !env_int("FFGPU_IRBW_NOEXC", 0)) G = 4;
-    if (ntiles >= 256 && ntiles < 1100 && env_int("FFGPU_IRBW_G_MID", 0) > 0) G = std::min(gmax, env_int("FFGPU_IRBW_G_MID", 0));
+    if (d.stride == 1 && c.ngroups == 9 && ntiles >= 400 && ntiles < 512 && gmax >= 4 && !conc && !knob(K_IRBW_NOEXC)) G = 4;
+    if (const int f = ntiles >= 256 && ntiles < 1100 ? knob(K_IRBW_G_MID) : 0; f > 0) G = std::min(gmax, f);
     // the LDS-resident split tile (XL, 48 input channels) makes a wave's share of a tile cheaper: with several chains in flight seven waves
     // (two groups each of the 10x10 blocks' fourteen) beat four by 1.3 % (profiles/r04: 193.8 k against 191.3 k frames/s, eight: 193.4 k)
-    const bool xl_ok = S == 1 && c.KS1 == 12 && c.OT == 3 && c.NSI == 2 && c.big && ((env_int("FFGPU_IRBW_X3", 30) >> 3) & 1) != 0;
-    if (xl_ok && conc && ntiles < 256) G = std::min(gmax, env_int("FFGPU_IRBW_G_XL", 7));
-    if (ntiles < 256 && env_int("FFGPU_IRBW_G_SMALL", 0) > 0) G = std::min(gmax, env_int("FFGPU_IRBW_G_SMALL", 0));          // tuning only (wins over the XL choice)
-    const int fg = env_int("FFGPU_IRBW_G", 0);                      // an explicit FFGPU_IRBW_G wins over everything
+    const bool xl_ok = S == 1 && c.KS1 == 12 && c.OT == 3 && c.NSI == 2 && c.big && ((x3_mask >> 3) & 1) != 0;
+    if (xl_ok && conc && ntiles < 256) G = std::min(gmax, knob(K_IRBW_G_XL));
+    if (const int f = ntiles < 256 ? knob(K_IRBW_G_SMALL) : 0; f > 0) G = std::min(gmax, f);          // tuning only (wins over the XL choice)
+    const int fg = knob(K_IRBW_G);                      // an explicit FFGPU_IRBW_G wins over everything
     if (fg >= 1 && fg <= gmax) G = fg;
     c.G = G;
     c.NSO = 1;
     // single-strip kernel, 24 input channels (the 20x20 blocks): expand GEMM as split-bf16 products (bit 2 of FFGPU_IRBW_X3)
-    c.x3 = S == 1 && c.KS1 == 6 && c.OT == 2 && c.NSI == 2 && c.big && ((env_int("FFGPU_IRBW_X3", 30) >> 2) & 1) != 0;
+    c.x3 = S == 1 && c.KS1 == 6 && c.OT == 2 && c.NSI == 2 && c.big && ((x3_mask >> 2) & 1) != 0;
     // ... the 40 -> 20 stride-2 block (16 input channels, four-strip halo), bit 4
-    if (S == 2 && c.KS1 == 4 && c.OT == 2 && c.NSI == 4 && c.big && ((env_int("FFGPU_IRBW_X3", 30) >> 4) & 1) != 0) c.x3 = true;
+    if (S == 2 && c.KS1 == 4 && c.OT == 2 && c.NSI == 4 && c.big && ((x3_mask >> 4) & 1) != 0) c.x3 = true;
     // ... and 48 input channels with the groups split over G waves (the 10x10 blocks): the split tile lives once per workgroup in LDS (bit 3)
     c.xl = xl_ok && G > 1;
     if (c.xl) c.x3 = true;
     // two output strips per wave (ffgpu_irb_wave2.inc): one wave per tile, <= 16 output channels, stride 1 -- when a tile
     // of up to 32 quads with a three-strip halo covers the plane with clearly fewer expand strips
-    if (G == 1 && S == 1 && c.OT == 1 && (c.KS1 == 2 || c.KS1 == 4) && env_int("FFGPU_IRBW_NSO", 2) == 2) {
+    if (G == 1 && S == 1 && c.OT == 1 && (c.KS1 == 2 || c.KS1 == 4) && knob(K_IRBW_NSO) == 2) {
         double best2 = 1e30; int tw2 = 0, th2 = 0;
         for (int TWq = 1; TWq <= 8; TWq++) {
             if (TWq > 1 && (TWq - 1) * 4 >= d.OW) break;
@@ -1246,13 +1241,13 @@ static bool irbw_pick(const IrbDesc &d, IrbPlan &c)
                 if (cost < best2) { best2 = cost; tw2 = TWq; th2 = TH; }
             }
         }
-        const int f2t = env_int("FFGPU_IRBW2_TWQ", 0), f2h = env_int("FFGPU_IRBW2_TH", 0);
+        const int f2t = knob(K_IRBW2_TWQ), f2h = knob(K_IRBW2_TH);
         if (f2t > 0 && f2h > 0 && f2t * ((f2h + 1) / 2) <= 16 && (4 * f2t + 4) * (f2h + 2) <= 192) { tw2 = f2t; th2 = f2h; best2 = 0; }
         const long nt2 = tw2 ? irbw_ntiles(d, tw2, th2) : 0;
-        if (tw2 && best2 < 0.93 * best && nt2 >= env_int("FFGPU_IRBW2_MIN_TILES", 768)) {
+        if (tw2 && best2 < 0.93 * best && nt2 >= knob(K_IRBW2_MIN_TILES)) {
             c.NSO = 2; c.TWq = tw2; c.TH = th2; c.EW = 4 * tw2 + 4; c.EH = th2 + 2; c.NSI = 3; c.big = true; c.WPB = 4; c.xl = false;
             // the expand GEMM as exact split-bf16 products on the bf16 matrix cores (ffgpu_irb_wave.inc "X3"); FFGPU_IRBW_X3=0: fp32 MFMAs
-            c.x3 = irbw_x3_has(c.KS1) && ((env_int("FFGPU_IRBW_X3", 30) >> (c.KS1 == 2 ? 0 : 1)) & 1) != 0;   // (bit 0: 8 input channels, bit 1: 16)
+            c.x3 = irbw_x3_has(c.KS1) && ((x3_mask >> (c.KS1 == 2 ? 0 : 1)) & 1) != 0;   // (bit 0: 8 input channels, bit 1: 16)
         }
     }
     // tiles per workgroup (G == 1): whichever of 4 / 8 waves lets more waves share a CU's 160 KB of LDS
@@ -1261,7 +1256,7 @@ static bool irbw_pick(const IrbDesc &d, IrbPlan &c)
         const int cap = c.big ? 12 : 16;                                                               // VGPR-limited waves per CU
         const int w4 = std::min(cap, (int)(IRB_LDS_MAX / (cs + 4 * slice)) * 4), w8 = std::min(cap, (int)(IRB_LDS_MAX / (cs + 8 * slice)) * 8);
         c.WPB = G > 1 ? G : (w4 >= w8 ? 4 : 8);                                                       // tie: the finer granule (1.3 % with four chains in flight)
-        const int fw = env_int("FFGPU_IRBW_WPB", 0);
+        const int fw = knob(K_IRBW_WPB);
         if (G == 1 && fw >= 1 && fw <= 8) c.WPB = fw;
     }
     return true;
@@ -1307,8 +1302,8 @@ static bool irb_plan_wave(IrbDesc &d)
     c.family = IRB_WAVE;
     // a last group of at most 8 real channels in the single-strip kernel: packed into registers 0 / 1, the other half of its work skipped (ffgpu_irb_wave.inc irbw_chan)
     const int r = d.ec & 15;
-    c.half = c.NSO == 1 && r >= 1 && r <= 8 && env_int("FFGPU_IRBW_HALF", 1) != 0;
-    { const int x = env_int("FFGPU_IRBW_XCD", 3); c.xcd = c.G > 1 ? (x >> 1) & 1 : x & 1; }        // bit 0: one wave per tile, bit 1: group-split launches
+    c.half = c.NSO == 1 && r >= 1 && r <= 8 && knob(K_IRBW_HALF) != 0;
+    { const int x = knob(K_IRBW_XCD); c.xcd = c.G > 1 ? (x >> 1) & 1 : x & 1; }        // bit 0: one wave per tile, bit 1: group-split launches
     const IrbwP p = irbw_params(d);                                  // (the reduction region follows)
     c.pack_floats = p.o_cs + p.cs_floats;
     if (p.ntiles * std::max(p.tiles_x, p.tiles_y) >= (1L << 32) || p.ntiles >= (1L << 31)) { ffgpu_set_error("irbw: too many tiles for 32-bit index arithmetic"); return false; }
@@ -1316,7 +1311,7 @@ static bool irb_plan_wave(IrbDesc &d)
     // G of them when the launch leaves the CU's LDS to one workgroup anyway (no folding rounds: two barriers fewer)
     const int waves = c.G > 1 ? c.G : c.WPB;
     size_t region = (size_t)waves * 16 * c.NSI * 64;
-    if (c.G > 1 && !env_int("FFGPU_IRBW_FOLD", 0)) {
+    if (c.G > 1 && !knob(K_IRBW_FOLD)) {
         const size_t want = (size_t)c.G * c.OT * 1024;
         if (want > region && (p.cs_floats + want) * sizeof(float) <= 150 * 1024 && p.ntiles <= 512) region = want;
     }
@@ -1339,7 +1334,7 @@ bool ffgpu_front_ok(const ConvDesc &c, const IrbDesc &d)
            c.iw == 2 * c.ow && c.ih == 2 * c.oh && c.ow % 4 == 0 && c.ow / 4 <= 64 && c.in_cs % 4 == 0 && c.in_ns % 4 == 0 &&
            3 * c.in_cs < (1L << 30) && c.out == d.in && d.plan.family == IRB_THIN && d.ic == 8 && d.ec == 8 && d.oc == 4 && !d.residual &&
            d.W == c.ow && d.H == c.oh && d.N == c.N &&
-           (long)c.N * c.oh * c.ow >= env_int("FFGPU_FRONT_MIN_PX", 262144) && !env_int("FFGPU_NO_FRONT", 0);
+           (long)c.N * c.oh * c.ow >= knob(K_FRONT_MIN_PX) && !knob(K_NO_FRONT);
 }
 
 // form IN_U8: the frames of this forward are u8 BGR images described by the executor's parameter block (c.in_ind IS that block: its
@@ -1349,7 +1344,7 @@ bool ffgpu_front_ok(const ConvDesc &c, const IrbDesc &d)
 // must give the same records whichever way they arrive (tests/test_gpu_round3.py::test_u8_frames_into_the_first_kernel)
 int ffgpu_front_nc(const IrbDesc &d)
 {
-    return env_int("FFGPU_FRONT_NC", 3) == 3 && d.W >= 6 && (d.W + 2) / 3 <= 64 ? 3 : 4;
+    return knob(K_FRONT_NC) == 3 && d.W >= 6 && (d.W + 2) / 3 <= 64 ? 3 : 4;
 }
 
 // forms IN_BGR_FRAMES / IN_NV12_FRAMES (the resizing forms): u8 frames of any size described one by one by the parameter block's frames_tab.  Three
@@ -1358,7 +1353,7 @@ int ffgpu_front_nc(const IrbDesc &d)
 // unset: FFGPU_NV12_FRONT_DEFAULT, the outcome of tools/nv12_frames_bench.py (DESIGN 5.15: fused only if it beats staging at four chains by more
 // than the spread of the repeats).  Read at every call: it selects between two graphs, it changes neither.
 #define FFGPU_NV12_FRONT_DEFAULT 0
-bool ffgpu_front_nv12_fused() { return env_int("FFGPU_NV12_FRONT", FFGPU_NV12_FRONT_DEFAULT) != 0; }
+bool ffgpu_front_nv12_fused() { return knob_or(K_NV12_FRONT, FFGPU_NV12_FRONT_DEFAULT) != 0; }
 
 int ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, InputForm form, hipStream_t s)
 {
@@ -1395,7 +1390,7 @@ int ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, InputForm form, hipS
 // expanded channels per chunk: 16 keeps the LDS footprint small (more workgroups per CU), 32 halves the chunk count
 static int irb_ech(const IrbDesc &d)
 {
-    const int force = env_int("FFGPU_IRB_ECH", 0);
+    const int force = knob(K_IRB_ECH);
     if (force == 16 || force == 32) return d.ec <= 16 ? 16 : force;
     if (d.ec <= 16) return 16;
     // measured (profiles/r01_irb_tile_sweep.txt): short K loops gain more from the extra workgroups per CU
@@ -1419,12 +1414,13 @@ static size_t irb_lds_floats(int k4, int ECH, int OT, int NPin, int wbufs)
 static int irb_wbufs(int k4, int ECH, int OT, int NPin, int nchunks, long ntiles)
 {
     if (nchunks == 1) return 1;
-    if (env_int("FFGPU_IRB_RESIDENT", 1) == 0) return 2;
+    const int resident = knob(K_IRB_RESIDENT);
+    if (resident == 0) return 2;
     const size_t a = irb_lds_floats(k4, ECH, OT, NPin, 2) * sizeof(float), b = irb_lds_floats(k4, ECH, OT, NPin, nchunks) * sizeof(float);
     if (b > IRB_LDS_MAX - 8 * 1024) return 2;
     const int want = (int)std::min(4L, (ntiles + 255) / 256);      // workgroups per CU the launch can use at all
     const int bpa = std::min(want, (int)(IRB_LDS_MAX / a)), bpb = std::min(want, (int)(IRB_LDS_MAX / b));
-    return (bpb >= bpa || bpb >= 2 || env_int("FFGPU_IRB_RESIDENT", 1) == 2) ? nchunks : 2;
+    return (bpb >= bpa || bpb >= 2 || resident == 2) ? nchunks : 2;
 }
 
 static void irb_geometry(const IrbDesc &d, int TH, int TW, int NF, IrbP &p)
@@ -1443,6 +1439,7 @@ static bool irb_pick_tile(const IrbDesc &d, int ECH, IrbP &best)
 {
     const int k4 = (d.ic + 3) & ~3, OT = (d.oc + 15) / 16;
     const int nchunks = (d.ec + ECH - 1) / ECH;
+    const int force_tw = knob(K_IRB_TW);
     double best_score = -1.0;
     // measured preferences (tools/tune_irb.py, batch 64, profiles/r01_irb_tile_sweep.txt); the scored search
     // below is the fallback for shapes the table does not fit
@@ -1462,12 +1459,12 @@ static bool irb_pick_tile(const IrbDesc &d, int ECH, IrbP &best)
         IrbP p;
         irb_geometry(d, TH, TW, 1, p);
         const size_t lds = irb_lds_floats(k4, ECH, OT, p.NPin, nchunks > 1 ? 2 : 1) * sizeof(float);
-        if (!env_int("FFGPU_IRB_TW", 0) && !env_int("FFGPU_IRB_NOTABLE", 0) && TW <= d.OW && p.NPout <= 512 && p.NPin <= 1024 && lds <= 150 * 1024) {
+        if (!force_tw && !knob(K_IRB_NOTABLE) && TW <= d.OW && p.NPout <= 512 && p.NPin <= 1024 && lds <= 150 * 1024) {
             best = p;
             return true;
         }
     }
-    const int force_tw = env_int("FFGPU_IRB_TW", 0), force_th = env_int("FFGPU_IRB_TH", 0), force_nf = env_int("FFGPU_IRB_NF", 0);
+    const int force_th = knob(K_IRB_TH), force_nf = knob(K_IRB_NF);
     const int tws[4] = { d.OW <= 24 ? d.OW : 16, 32, 8, force_tw };
     for (int twi = 0; twi < 4; twi++) {
         const int TW = tws[twi];
@@ -1518,7 +1515,7 @@ static IrbP irb_params(const IrbDesc &d)
     p.act1 = act_slope(d.act1); p.actd = act_slope(d.actd); p.act2 = act_slope(d.act2); p.res_act = act_slope(d.res_act);
     p.k4 = (d.ic + 3) & ~3; p.ECH = c.ECH; p.nchunks = (d.ec + c.ECH - 1) / c.ECH; p.CH = irb_chunk_floats(p.k4, c.ECH, c.OT);
     p.vec_store = (d.OW % 4 == 0) && (p.TW % 4 == 0);
-    p.dbg_skip = env_int("FFGPU_IRB_SKIP", 0); p.dbg_t = nullptr;
+    p.dbg_skip = knob(K_IRB_SKIP); p.dbg_t = nullptr;
     p.ntiles = p.tiles_x * p.tiles_y * ((d.N + p.NF - 1) / p.NF);
     p.KS = c.KS; p.red_off = c.red_off;
     p.resident = p.nchunks > 1 && c.wbufs == p.nchunks;
@@ -1541,10 +1538,10 @@ static bool irb_plan_wg(IrbDesc &d)
     p = irb_params(d);                                               // (KS, wbufs and red_off follow)
     c.pack_floats = (int)(((size_t)p.nchunks * p.CH + c.OT * 32 + 63) & ~(size_t)63);
     const int nso = (p.NPout + 63) / 64, nsi = p.NPin / 64;
-    c.NW = env_int("FFGPU_IRB_NW", 8) == 4 ? 4 : 8;                  // waves per workgroup
+    c.NW = knob(K_IRB_NW) == 4 ? 4 : 8;                  // waves per workgroup
     c.KS = 1;
     while (c.KS * 2 * nso <= c.NW && c.KS < 4) c.KS *= 2;            // idle waves take slices of the channel loop
-    if (env_int("FFGPU_IRB_NOKS", 0)) c.KS = 1;
+    if (knob(K_IRB_NOKS)) c.KS = 1;
     c.wbufs = irb_wbufs(p.k4, p.ECH, c.OT, p.NPin, p.nchunks, p.ntiles);
     for (int wi = 0; wi < p.k4 * nsi; wi++)
         if (((wi * p.inv_nsi) >> 16) != wi / nsi) { ffgpu_set_error("irb: strip reciprocal inexact (k4 %d, %d strips)", p.k4, nsi); return false; }
@@ -1570,7 +1567,7 @@ bool ffgpu_irb_plan(IrbDesc &d)
     if (irb_thin_ok(d)) {
         const int band = thin_band(d.N, d.H);
         c.family = IRB_THIN; c.pack_floats = 64;
-        c.band = env_int("FFGPU_THIN_BAND", band); c.front_band = env_int("FFGPU_FRONT_BAND", band);
+        c.band = knob_or(K_THIN_BAND, band); c.front_band = knob_or(K_FRONT_BAND, band);
         c.grid = (int)((thin_params(d).ntasks + 3) / 4); c.block = 256;
         return true;
     }
@@ -1669,7 +1666,7 @@ int ffgpu_launch_irb(const IrbDesc &d, hipStream_t s)
 {
     const IrbPlan &c = d.plan;
     if (!irb_planned(d, "irb")) return -1;
-    if (env_int("FFGPU_VERBOSE_IRB", 0)) { char line[1024]; ffgpu_irb_plan_line(d, line, sizeof line); fprintf(stderr, "%s\n", line); }
+    if (knob(K_VERBOSE_IRB)) { char line[1024]; ffgpu_irb_plan_line(d, line, sizeof line); fprintf(stderr, "%s\n", line); }
     if (c.family == IRB_THIN) return launch_irb_thin(d, s);
     if (!d.pk) { ffgpu_set_error("irb: constants not packed"); return -1; }
     return c.family == IRB_WAVE ? irbw_kernels[c.inst].launch(irbw_params(d), c, s) : irb_kernels[c.inst].launch(irb_params(d), c, s);

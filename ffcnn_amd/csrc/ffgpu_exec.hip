@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "ffgpu_dev.hpp"
+#include "ffgpu_knobs.hpp"
 #include "ffgpu_plan.hpp"
 #include "conv.h"
 
@@ -38,7 +39,7 @@ extern "C" void ffgpu_set_error(const char *fmt, ...)
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof g_err, fmt, ap);
     va_end(ap);
-    if (getenv("FFGPU_VERBOSE")) fprintf(stderr, "ffgpu: %s\n", g_err);
+    if (knob_set(K_VERBOSE)) fprintf(stderr, "ffgpu: %s\n", g_err);
 }
 
 extern "C" const char *ffgpu_last_error(void) { return g_err; }
@@ -269,13 +270,9 @@ static float *tensor_ptr(const ffgpu_exec *ex, int t) { return ex->arena + ex->l
 // -------------------------------------------------------------------------- planning
 // plan() = the layout (ffgpu_plan.hpp: pure host code), the arena, the step list built from the layout, the rewrites of that list, the packed
 // constants' places, and whether the captured graph is free of the input pointer.
-static bool env_on(const char *name) { const char *v = getenv(name); return v && atoi(v) != 0; }
-
-// the one place the planner's switches are read: the flags, and the environment -- FFGPU_NO_IRB and FFGPU_IRB_MIN_EC once per process, the rest per create
+// the one place the planner's switches are read: the flags, and the environment at every create
 static PlanOptions plan_options(const ffgpu_exec *ex)
 {
-    static const bool no_irb = env_on("FFGPU_NO_IRB");
-    static const int min_ec = getenv("FFGPU_IRB_MIN_EC") ? atoi(getenv("FFGPU_IRB_MIN_EC")) : 24;
     PlanOptions o;
     o.batch = ex->N;
     o.keep_all = ex->flags & FFGPU_KEEP_ALL;
@@ -285,9 +282,9 @@ static PlanOptions plan_options(const ffgpu_exec *ex)
     // internal streams of the runtime (ROCm 7.0), its fragile part (an arena's worth of memory kept per destroyed graph, one
     // SIGSEGV inside hipGraphLaunch in 30 runs of 630 create / launch / destroy cycles): 2 % of ONE chain's latency is not worth a process.  Never
     // inside the halves of a split executor: a fork nested in a forked stream crashes graph capture there.
-    o.branch = env_on("FFGPU_BRANCH") && !ex->is_child;
-    o.no_irb = no_irb; o.irb_min_ec = min_ec;
-    o.dwpw = env_on("FFGPU_DWPW");
+    o.branch = knob(K_BRANCH) && !ex->is_child;
+    o.no_irb = knob(K_NO_IRB); o.irb_min_ec = knob(K_IRB_MIN_EC);
+    o.dwpw = knob(K_DWPW);
     return o;
 }
 
@@ -548,7 +545,7 @@ static int place_constants(ffgpu_exec *ex)
 // of every darknet cfg: dense KxK from 3 channels): the captured graph is then independent of the input buffer
 static void decide_indirect(ffgpu_exec *ex)
 {
-    ex->indirect = !env_on("FFGPU_NO_INDIRECT");             // tests: the keyed fallback
+    ex->indirect = !knob(K_NO_INDIRECT);             // tests: the keyed fallback
     for (const Step &st : ex->steps)
         if (st.b_is_input || (st.in_is_input && !(st.kind == S_FRONT || (st.kind == S_CONV && ffgpu_conv_supports_ind(st.conv))))) ex->indirect = false;
     if (ex->indirect)
@@ -584,15 +581,15 @@ static int issue_step(ffgpu_exec *ex, const Step &st, const InputSrc &in, hipStr
     // tuning only (tools/ablate_layers.py): FFGPU_DBG_SKIP="lo:hi" drops the launches of layers lo..hi -- wrong results,
     // but the change in frames/s is what that stretch of the net costs with several batches in flight
     // (FFGPU_DBG_KEEP="lo:hi" is the complement: only that stretch runs -- tools/saturate_layers.py)
-    if (getenv("FFGPU_DBG_SKIP") || getenv("FFGPU_DBG_KEEP")) {
+    if (knob_text(K_DBG_SKIP) || knob_text(K_DBG_KEEP)) {
         static bool warned = false;
         if (!warned) { warned = true; fprintf(stderr, "libffcnn_hip: FFGPU_DBG_SKIP / FFGPU_DBG_KEEP set -- launches are being dropped, RESULTS ARE WRONG (tuning only)\n"); }
     }
-    if (const char *sk = getenv("FFGPU_DBG_SKIP")) {
+    if (const char *sk = knob_text(K_DBG_SKIP)) {
         int lo = -1, hi = -1;
         if (sscanf(sk, "%d:%d", &lo, &hi) == 2 && st.layer >= lo && st.layer <= hi && st.kind != S_NMS) return 0;
     }
-    if (const char *sk = getenv("FFGPU_DBG_KEEP")) {
+    if (const char *sk = knob_text(K_DBG_KEEP)) {
         int lo = -1, hi = -1;
         if (sscanf(sk, "%d:%d", &lo, &hi) == 2 && (st.layer < lo || st.layer > hi) && st.kind != S_NMS) return 0;
     }
@@ -837,14 +834,10 @@ static ffgpu_exec *exec_create_on(ffgpu_netdev *dev, NET *net, int batch, int fl
 {
     if (batch < 1) { ffgpu_set_error("batch must be >= 1"); return nullptr; }
     if (hipSetDevice(dev->device) != hipSuccess) { ffgpu_set_error("hipSetDevice failed"); return nullptr; }
-    const char *env = getenv("FFCNN_COMPAT_V6");
-    if (env && atoi(env)) flags |= FFGPU_COMPAT_V6;
-    env = getenv("FFGPU_NO_GRAPH");
-    if (env && atoi(env)) flags |= FFGPU_NO_GRAPH;
-    env = getenv("FFGPU_BF16_PW");
-    if (env && atoi(env)) flags |= FFGPU_BF16_PW;
-    env = getenv("FFGPU_NO_FUSE");
-    if (env && atoi(env)) flags |= FFGPU_NO_FUSE;
+    if (knob(K_COMPAT_V6)) flags |= FFGPU_COMPAT_V6;
+    if (knob(K_NO_GRAPH)) flags |= FFGPU_NO_GRAPH;
+    if (knob(K_BF16_PW)) flags |= FFGPU_BF16_PW;
+    if (knob(K_NO_FUSE)) flags |= FFGPU_NO_FUSE;
     const bool split = (flags & FFGPU_SPLIT2) && batch >= 2 && batch % 2 == 0 && !(flags & FFGPU_KEEP_ALL);
     const bool as_child = (flags & FFGPU_INTERNAL_CHILD) != 0;
     flags &= ~(FFGPU_SPLIT2 | FFGPU_INTERNAL_CHILD);
@@ -887,8 +880,8 @@ static ffgpu_exec *exec_create_on(ffgpu_netdev *dev, NET *net, int batch, int fl
     if (split) {
         // the parent owns the records (and their mirror / ring); each part plans its own arena and writes its slice
         int K = 2;
-        const char *ek = getenv("FFGPU_SPLIT_PARTS");            // tuning: 2 (default), 4 or 8 parallel chains
-        if (ek && (atoi(ek) == 4 || atoi(ek) == 8) && batch % atoi(ek) == 0) K = atoi(ek);
+        const int parts = knob(K_SPLIT_PARTS);                   // tuning: 2 (default), 4 or 8 parallel chains
+        if ((parts == 4 || parts == 8) && batch % parts == 0) K = parts;
         for (int c = 0; c < K; c++) {
             ffgpu_exec *ch = exec_create_on(dev, net, batch / K, (flags & ~FFGPU_HOST_DETS) | FFGPU_INTERNAL_CHILD);
             if (!ch) { ffgpu_exec_destroy(ex); return nullptr; }
@@ -1073,7 +1066,7 @@ static bool front_fused(const ffgpu_exec *ex, bool resizing)
 // this forward may use the u8 form `form` of the first kernel: no fp32 batch in between.  FFGPU_NO_U8_FRONT (tuning / tests): always the two-kernel path
 static bool front_takes(const ffgpu_exec *ex, InputForm form)
 {
-    return !getenv("FFGPU_NO_U8_FRONT") && front_fused(ex, form != IN_U8) && (form != IN_NV12_FRAMES || ffgpu_front_nv12_fused());
+    return !knob_set(K_NO_U8_FRONT) && front_fused(ex, form != IN_U8) && (form != IN_NV12_FRAMES || ffgpu_front_nv12_fused());
 }
 
 extern "C" int ffgpu_exec_forward_bgr_dev(ffgpu_exec *ex, const unsigned char *d_bgr, int w, int h,
@@ -1848,6 +1841,13 @@ extern "C" int ffgpu_irb_instantiations(char *buf, int cap)
     return ffgpu_irb_keys(buf, (size_t)cap);
 }
 
+// pure host code: the table of ffgpu_knobs.hpp, one line per environment variable, with the value a read would return now
+extern "C" int ffgpu_knobs_text(char *buf, int cap)
+{
+    if (!buf || cap < 1) { ffgpu_set_error("knobs_text: bad arguments"); return -1; }
+    return ffgpu_knobs_lines(buf, (size_t)cap);
+}
+
 extern "C" float ffgpu_irb_dev(const float *d_in, const float *d_w1, const float *d_wd, const float *d_w2,
                                const float *d_res, float *d_out, int batch, int iw, int ih, int ic, int ec, int oc,
                                int stride, int act1, int actd, int act2, int res_act, int warmup, int iters, void *stream)
@@ -1939,8 +1939,7 @@ extern "C" void groupconv(float *in, float *filt, float *out,
     if (!in || !filt || !out || ig < 1 || ic % ig) { fprintf(stderr, "ffcnn groupconv: bad arguments\n"); return; }
     const size_t n_in = (size_t)iw * ih * ic, n_out = (size_t)ow * oh * oc;
     const size_t n_f = (size_t)fn * ((((size_t)fs * fs * (ic / ig) + 3) & ~(size_t)3) + 4);
-    const char *env = getenv("FFCNN_COMPAT_V6");
-    const int flags = (env && atoi(env)) ? FFGPU_COMPAT_V6 : 0;
+    const int flags = knob(K_COMPAT_V6) ? FFGPU_COMPAT_V6 : 0;
     int cur = 0;
     (void)hipGetDevice(&cur);
     if (sc.dev != cur) {                          // the thread moved to another GPU (ffgpu_set_device): the buffers stay behind

@@ -203,8 +203,8 @@ extern "C" ffgpu_node *ffgpu_node_create(NET *net, int ndev, const int *devices,
         k.d_pack.assign(depth, nullptr); k.h_in.assign(depth, nullptr);
         ffgpu_shard_range(global_batch, r, ndev, &k.lo, &k.hi);
         if (k.hi - k.lo > 1024) { ffgpu_set_error("node_create: a shard of %d frames (the packed records hold at most 1024)", k.hi - k.lo); ffgpu_node_destroy(nd); return nullptr; }
-        const char *pb = getenv("FFGPU_NODE_PACK_BOXES");          // (tests: force the "block too small" path)
-        k.pack_cap = std::max(1, pb && atoi(pb) > 0 ? atoi(pb) : FFGPU_NODE_PACK_BOXES) * (k.hi - k.lo);
+        const int pb = knob(K_NODE_PACK_BOXES);                    // (tests: force the "block too small" path)
+        k.pack_cap = std::max(1, pb > 0 ? pb : FFGPU_NODE_PACK_BOXES) * (k.hi - k.lo);
         k.pack_bytes = ffgpu_packed_records_bytes(k.hi - k.lo, k.pack_cap);
         k.pack_off = nd->gather_bytes;
         nd->gather_bytes += k.pack_bytes;

@@ -28,7 +28,7 @@ struct PlanOptions {
     bool fuse = true;        // !FFGPU_NO_FUSE: every rewrite below
     bool branch = false;     // FFGPU_BRANCH=1: the first detection head as a side lane
     bool no_irb = false;     // FFGPU_NO_IRB=1
-    int  irb_min_ec = 24;    // FFGPU_IRB_MIN_EC: for the executor's block callable (the layout itself does not read it)
+    int  irb_min_ec = 0;     // FFGPU_IRB_MIN_EC, filled in by the executor for its block callable (the layout itself does not read it)
     bool dwpw = false;       // FFGPU_DWPW=1
 };
 

@@ -331,6 +331,13 @@ int ffgpu_irb_plan_text(int batch, int iw, int ih, int ic, int ec, int oc, int s
  * from the tables the planner dispatches through.  Pure host code: for tests that must reach every one of them. */
 int ffgpu_irb_instantiations(char *buf, int cap);
 
+/* Every environment variable the library reads, one per line in buf (at most cap bytes; returns snprintf's count): name, kind of parse
+ * (INT: unset or empty gives the default, else atoi; ON: atoi != 0; SET: present at all; TEXT: the string), default (`computed`: it depends
+ * on the shape or the build; `-`: none), class (product, tuning, test, lab), the value a read would return now under the current
+ * environment (TEXT: set / unset; a computed default: the number in the environment, or `default`), then what the variable does.  Pure
+ * host code (no device needed).  INTEGRATION.md section 6 describes the variables; this is the table it is checked against. */
+int ffgpu_knobs_text(char *buf, int cap);
+
 /* Fused pair: depthwise K x K (K = 3 | 5, stride 1, pad K / 2) -> pointwise 1x1, i.e. two consecutive groupconv calls of the
  * reference in one kernel (the depthwise tensor never leaves the CU).  CNHW device tensors; d_wd / d_wp are the two layers'
  * filter rows (conv.h layout).  iters > 0: returns mean microseconds per launch (HIP events on `stream`) instead of 0. */

@@ -11,7 +11,7 @@ float64 -- and tests/irb_blocks/test_gpu_kernels.py runs every case on the devic
           on one expanded channel, zero weights on the +Inf channel (plant())
 
 A shape is (N, W, H, ic, ec, oc, stride); acts is (act1, actd, act2, res_act) in the numbering of utils.h (0 linear, 1 relu, 2 leaky); env holds the
-planner switches the case runs under -- every other planner switch is unset (test_irb_choice.PLANNER_ENV)."""
+planner switches the case runs under -- every other planner switch is unset (test_irb_choice.knob_names: the library's own table)."""
 import collections
 import functools
 
@@ -199,11 +199,12 @@ def fields(line):
 
 
 def set_switches(monkeypatch, case):
-    from test_irb_choice import PLANNER_ENV
-    for v in PLANNER_ENV:
+    from test_irb_choice import knob_names
+    names = knob_names()
+    for v in names:
         monkeypatch.delenv(v, raising=False)
     for k, v in case.env.items():
-        assert k in PLANNER_ENV, k
+        assert k in names, k
         monkeypatch.setenv(k, v)
 
 

@@ -721,7 +721,7 @@ def test_irb_plan_is_frozen_at_create(orc, tmp_path, monkeypatch):
     the smaller layout inside the larger buffer -- wrong numbers, never an access out of bounds."""
     from test_gpu_fuzz_nets import conv
     from test_gpu_parity import _write_random_weights, close
-    from test_irb_choice import PLANNER_ENV
+    from test_irb_choice import knob_names
     BATCH = 2
     cfg_text = "[net]\nwidth=32\nheight=32\nchannels=3\n\n" + conv(24, 3, 2, "leaky") + \
         conv(48, 1, 1, "leaky") + conv(48, 3, 1, "leaky", groups=48) + conv(24, 1, 1, "linear") + "[shortcut]\nfrom=-4\nactivation=linear\n\n" + \
@@ -730,7 +730,7 @@ def test_irb_plan_is_frozen_at_create(orc, tmp_path, monkeypatch):
     import torch
     from ffcnn_amd import capi as F
     F.lib()
-    for v in PLANNER_ENV:
+    for v in knob_names():
         monkeypatch.delenv(v, raising=False)
     assert F.irb_plan_text((BATCH, 16, 16, 24, 48, 24, 1, 2, 2, 0, 0)).startswith("irbw<6,2,1,2,big,x3> ")
     cfg, wpath = str(tmp_path / "block.cfg"), str(tmp_path / "block.weights")

@@ -42,8 +42,8 @@ def test_x3_fused_block_is_an_fp32_reorder(env, shape, monkeypatch):
     res = rng.uniform(-1, 1, (oc * N, H, W)).astype(np.float32)
     t = [torch.from_numpy(a).cuda() for a in (x, f1, fd, f2, res)]
     outs, keys = {}, {}
-    from test_irb_choice import PLANNER_ENV
-    for v in PLANNER_ENV:
+    from test_irb_choice import knob_names
+    for v in knob_names():
         monkeypatch.delenv(v, raising=False)
     for k, v in X3_SWITCHES.get(shape, {}).items():
         monkeypatch.setenv(k, v)

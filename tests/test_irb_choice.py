@@ -63,11 +63,6 @@ SWITCHES = [("FFGPU_NO_IRBW", "1"), ("FFGPU_NO_THIN", "1"), ("FFGPU_IRBW_X3", "0
             ("FFGPU_IRBW_S2_NSI4", "1"), ("FFGPU_IRBW_S2_633", "0"), ("FFGPU_IRB_ECH", "32")]
 COLUMNS = ["default", "flags=FFGPU_CONCURRENT"] + ["%s=%s" % kv for kv in SWITCHES]
 FLOOR = 10
-# every variable the planner reads: a developer's shell must not change the census
-PLANNER_ENV = ["FFGPU_NO_THIN", "FFGPU_THIN_BAND", "FFGPU_FRONT_BAND", "FFGPU_NO_IRBW", "FFGPU_IRBW_S2_NSI4", "FFGPU_IRBW_S2_633", "FFGPU_IRBW_TWQ", "FFGPU_IRBW_TH",
-               "FFGPU_IRBW_BIG", "FFGPU_IRBW_BIG_S2K1", "FFGPU_IRBW_GWAVES", "FFGPU_IRBW_NOEXC", "FFGPU_IRBW_G_MID", "FFGPU_IRBW_X3", "FFGPU_IRBW_G_XL", "FFGPU_IRBW_G_SMALL",
-               "FFGPU_IRBW_G", "FFGPU_IRBW_NSO", "FFGPU_IRBW2_TWQ", "FFGPU_IRBW2_TH", "FFGPU_IRBW2_MIN_TILES", "FFGPU_IRBW_WPB", "FFGPU_IRBW_HALF", "FFGPU_IRBW_XCD",
-               "FFGPU_IRBW_FOLD", "FFGPU_IRB_ECH", "FFGPU_IRB_RESIDENT", "FFGPU_IRB_TW", "FFGPU_IRB_TH", "FFGPU_IRB_NF", "FFGPU_IRB_NOTABLE", "FFGPU_IRB_NW", "FFGPU_IRB_NOKS"]
 # The instantiations a switch-free or single-switch run can reach (of 4 thin, 33 wave and 24 workgroup ones):
 #  - k_irbw, fp32 expand: `big` follows from the shape (registers = 4 NSI KS1 + 16 OT + 2 (KS1 + 4 OT) + 76 > 124) unless FFGPU_IRBW_BIG forces it, so one of
 #    each shape's two register budgets; <6,2,1,2,big> and <4,2,2,4,big> only with FFGPU_IRBW_X3=0, the two <.,1,2,4> only with FFGPU_IRBW_S2_NSI4=1
@@ -149,9 +144,15 @@ def probe_of(L):
     return probe
 
 
+def knob_names():
+    """every variable the library reads, from its own table: a developer's shell must not change the census"""
+    from ffcnn_amd import capi
+    return [k["name"] for k in capi.knobs()]
+
+
 def census(probe, geoms, setenv, delenv):
     """per geometry, the full line of every column"""
-    for v in PLANNER_ENV:
+    for v in knob_names():
         delenv(v)
     cols = [[probe(t) for t in geoms], [probe(t, CONCURRENT) for t in geoms]]
     for k, v in SWITCHES:

@@ -23,11 +23,6 @@ SWITCHES = [{"FFGPU_IG_X3": "0"}, {"FFGPU_PW_X3T": "0"}, {"FFGPU_PW_X3S": "0"}, 
 COLUMNS = ["auto"] + ["k%d" % k for k in EXPLICIT] + [",".join("%s=%s" % kv for kv in sorted(sw.items())) for sw in SWITCHES]
 FLOOR = 10
 DIGITS = "0123456789abcdefghijklmnopqrstuvwxyz"
-# every variable the dispatcher's choice reads: a developer's shell must not change the census
-TUNING_ENV = ["FFGPU_FORCE_GENERIC", "FFGPU_PW_X3", "FFGPU_PW_X3T", "FFGPU_PW_X3S", "FFGPU_IG_X3", "FFGPU_NO_PW_GEMM", "FFGPU_NO_IGEMM", "FFGPU_NO_GROUP_THIN",
-              "FFGPU_NO_DW_PAIR", "FFGPU_IGX3_S2", "FFGPU_IGX3_NW", "FFGPU_IGX3_MT", "FFGPU_IGX3_MT4_WGS", "FFGPU_IGX3_MIN_IC", "FFGPU_IGX3_MIN_WGS",
-              "FFGPU_IGEMM_NOVEC", "FFGPU_PWX3_MIN_IC", "FFGPU_PWX3_MIN_OC", "FFGPU_PWX3_MIN_P", "FFGPU_PWX3T_MIN_IC", "FFGPU_PWX3T_MIN_OC", "FFGPU_PWX3T_MIN_P",
-              "FFGPU_PWX3S_MIN_IC", "FFGPU_PWX3S_MIN_OC", "FFGPU_PWX3S_MIN_WGS", "FFGPU_PWG_MIN_OC", "FFGPU_PWG_MIN_IC"]
 
 
 def geometries():
@@ -87,8 +82,8 @@ def geometries():
 
 def census(capi, geoms, setenv, delenv):
     """one string of len(COLUMNS) name indices per geometry"""
-    for v in TUNING_ENV:
-        delenv(v)
+    for k in capi.knobs():                  # every variable the library reads (its own table): a developer's shell must not change the census
+        delenv(k["name"])
     cols = [[capi.kernel_name(*t)for t in geoms]]
     for k in EXPLICIT:
         cols.append([capi.kernel_name(*t, variant=k) for t in geoms])
