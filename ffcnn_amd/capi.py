@@ -117,6 +117,33 @@ class RedactSpec(C.Structure):       # ffgpu_redact_spec (40 bytes): which boxes
                 ("margin_num", C.c_int), ("margin_den", C.c_int), ("color", C.c_ubyte * 4)]
 
 
+class Zone(C.Structure):             # ffgpu_zone (96 bytes): one polygon of a scene
+    _fields_ = [("x", C.c_float * 8), ("y", C.c_float * 8), ("nverts", C.c_int), ("dwell_frames", C.c_int), ("classes", C.c_uint * 4), ("reserved", C.c_int * 2)]
+
+
+class Line(C.Structure):             # ffgpu_line (32 bytes): one directed segment A -> B of a scene
+    _fields_ = [("ax", C.c_float), ("ay", C.c_float), ("bx", C.c_float), ("by", C.c_float), ("classes", C.c_uint * 4)]
+
+
+class Scene(C.Structure):            # ffgpu_scene (1040 bytes): the zones and lines of one video stream
+    _fields_ = [("zone", Zone * 8), ("line", Line * 8), ("nzones", C.c_int), ("nlines", C.c_int), ("anchor", C.c_int), ("reserved", C.c_int)]
+
+
+class ZonesSpec(C.Structure):        # ffgpu_zones_spec (32 bytes): the zones pass's settings
+    _fields_ = [("capacity", C.c_int), ("max_missed", C.c_int), ("identity", C.c_int), ("flags", C.c_int), ("min_score", C.c_float),
+                ("gate_zone", C.c_uint), ("gate_line", C.c_uint), ("reserved", C.c_int)]
+
+
+class ZoneSlot(C.Structure):         # ffgpu_zone_slot (64 bytes): one slot of a stream's state
+    _fields_ = [("id", C.c_int), ("px", C.c_float), ("py", C.c_float), ("inside", C.c_int), ("last", C.c_int), ("reserved", C.c_int * 3), ("since", C.c_int * 8)]
+
+
+SCENE_ZONES, SCENE_LINES, ZONE_VERTS, ZONES_DETS, ZONES_ROW = 8, 8, 8, 128, 64          # FFGPU_SCENE_ZONES, _LINES, FFGPU_ZONE_VERTS, FFGPU_ZONES_DETS, _ROW
+ZONES_NONE, ZONES_TYPE, ZONES_IDS = 0, 1, 2                                            # FFGPU_ZONES_* (ffgpu_zones_spec.identity)
+ZONES_GATE_INVERT = 1                                                                  # FFGPU_ZONES_GATE_INVERT (ffgpu_zones_spec.flags)
+ZONES_ENTRIES, ZONES_MERGED = 0, 1                                                     # FFGPU_ZONES_* (ffgpu_exec_zones: which)
+ZONES_EVENTS_HEADER = ("considered", "known", "fresh", "refused", "duplicate", "anonymous", "dropped", "freed", "live", "frame")   # the first ints of an event row
+ZONES_STATE_HEADER = 144                                                               # bytes in front of a stream's slots
 TRACK_DETS = 128                                                                       # FFGPU_TRACK_DETS
 TRACK_ENTRIES, TRACK_MERGED = 0, 1                                                     # FFGPU_TRACK_* (ffgpu_exec_track: which)
 TRACK_IDS_HEADER = ("considered", "matched", "born", "refused", "dropped", "freed", "live", "frame")   # the 8 ints in front of a row of ids
@@ -135,6 +162,7 @@ assert C.sizeof(DrawStyle) == 24 and C.sizeof(CropSpec) == 72 and C.sizeof(Crop)
 assert C.sizeof(TrackSpec) == 32 and C.sizeof(Track) == 48
 assert C.sizeof(FeatureSpec) == 16 and C.sizeof(Label) == 8 and C.sizeof(RelabelSpec) == 16
 assert C.sizeof(Gallery) == 40 and C.sizeof(RedactSpec) == 40
+assert C.sizeof(Zone) == 96 and C.sizeof(Line) == 32 and C.sizeof(Scene) == 1040 and C.sizeof(ZonesSpec) == 32 and C.sizeof(ZoneSlot) == 64
 
 BOX_DTYPE = np.dtype([("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
 DETS_DTYPE = np.dtype([("count", "<i4"), ("ncand", "<i4"), ("overflow", "<i4"), ("nfull", "<i4"),
@@ -143,6 +171,7 @@ CROP_DTYPE = np.dtype([("target", "<i4"), ("box", "<i4"), ("type", "<i4"), ("sco
                        ("sw", "<i4"), ("sh", "<i4"), ("s1", "<i4"), ("s2", "<i4")])
 TRACK_DTYPE = np.dtype([("id", "<i4"), ("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"),
                         ("hits", "<i4"), ("missed", "<i4"), ("born", "<i4"), ("det", "<i4"), ("reserved", "<i4")])
+ZONE_SLOT_DTYPE = np.dtype([("id", "<i4"), ("px", "<f4"), ("py", "<f4"), ("inside", "<i4"), ("last", "<i4"), ("reserved", "<i4", (3,)), ("since", "<i4", (8,))])
 LABEL_DTYPE = np.dtype([("index", "<i4"), ("value", "<f4")])
 
 # every symbol include/*.h declares; tests check the built library exports all of them
@@ -166,7 +195,8 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_feature_dim", "ffgpu_exec_feature_dim", "ffgpu_features_dev", "ffgpu_exec_features", "ffgpu_topk_dev", "ffgpu_crops_relabel_dev",
            "ffgpu_exec_relabel",
            "ffgpu_match_workspace_bytes", "ffgpu_match_dev", "ffgpu_gallery_enroll_dev",
-           "ffgpu_redact_boxes_bgr_dev", "ffgpu_redact_boxes_nv12_dev", "ffgpu_exec_redact_bgr", "ffgpu_exec_redact_nv12"]
+           "ffgpu_redact_boxes_bgr_dev", "ffgpu_redact_boxes_nv12_dev", "ffgpu_exec_redact_bgr", "ffgpu_exec_redact_nv12",
+           "ffgpu_zones_state_bytes", "ffgpu_scene_check", "ffgpu_zones_reset_dev", "ffgpu_zones_boxes_dev", "ffgpu_exec_zones"]
 # include/ffcnn_hip_diag.h (libffcnn_hip_diag.so: lab equipment, its own library)
 DIAG_EXPORTS = ["ffgpu_membench", "ffgpu_pipe_probe", "ffgpu_pipe_probe2", "ffgpu_pipe_probe3", "ffgpu_mfma_floor", "ffgpu_diag_x3_term", "ffgpu_diag_xl_op", "ffgpu_clock_probe"]
 
@@ -309,6 +339,12 @@ def lib():
     L.ffgpu_track_reset_dev.argtypes = [vp, i, i, i, vp]
     L.ffgpu_track_boxes_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(i), i, C.POINTER(TrackSpec), vp, i, vp, vp, vp, vp]
     L.ffgpu_exec_track.argtypes = [vp, i, C.POINTER(i), i, C.POINTER(TrackSpec), vp, i, vp, vp, vp, vp]
+    L.ffgpu_zones_state_bytes.restype = sz
+    L.ffgpu_zones_state_bytes.argtypes = [i, i]
+    L.ffgpu_scene_check.argtypes = [C.POINTER(Scene), i]
+    L.ffgpu_zones_reset_dev.argtypes = [vp, i, i, i, vp]
+    L.ffgpu_zones_boxes_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(i), i, C.POINTER(ZonesSpec), vp, vp, i, vp, vp, vp, vp, vp]
+    L.ffgpu_exec_zones.argtypes = [vp, i, C.POINTER(i), i, C.POINTER(ZonesSpec), vp, vp, i, vp, vp, vp, vp, vp]
     L.ffgpu_feature_dim.argtypes = [i, i, i, i]
     L.ffgpu_exec_feature_dim.argtypes = [vp, C.POINTER(FeatureSpec)]
     L.ffgpu_features_dev.argtypes = [vp, i, i, i, i, i, i, vp, C.c_long, vp]
@@ -670,6 +706,15 @@ class Executor:
         arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
         _check(lib().ffgpu_exec_track(self.h, which, arr, len(streams), spec, d_state, nstreams, d_ids, d_out_records, d_out_lists, stream), "ffgpu_exec_track")
 
+    def zones(self, streams, spec, d_scenes, d_state, nstreams, d_events, d_ids=None, d_out_records=None, d_out_lists=None, which=0, stream=None):
+        """enqueue the zones pass on the last forward's boxes (which = ZONES_ENTRIES: entry n is record n of video stream streams[n], -1: ignored) or on
+        the last merge's (ZONES_MERGED: picture g) behind it (ffgpu_exec_zones): spec from zones_spec, d_scenes nstreams uploaded Scenes, d_state /
+        d_events / d_out_* the caller's device buffers (zones_state_bytes; rows of ZONES_ROW + 2 S ints; records; lists of S boxes), d_ids the rows
+        Executor.track wrote for the same `which` (with identity ZONES_IDS)"""
+        arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+        _check(lib().ffgpu_exec_zones(self.h, which, arr, len(streams), spec, d_scenes, d_state, nstreams, d_ids, d_events, d_out_records, d_out_lists, stream),
+               "ffgpu_exec_zones")
+
     def feature_dim(self, spec):
         """D of the rows Executor.features writes for `spec` (a FeatureSpec from feature_spec); pure host code (ffgpu_exec_feature_dim)"""
         return _check(lib().ffgpu_exec_feature_dim(self.h, spec), "ffgpu_exec_feature_dim")
@@ -927,6 +972,86 @@ def track_boxes_dev(d_records, d_lists, list_stride, streams, spec, d_state, nst
     arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
     _check(lib().ffgpu_track_boxes_dev(d_records, d_lists, list_stride, first, arr, len(streams), spec, d_state, nstreams, d_ids, d_out_records,
                                        d_out_lists, stream), "ffgpu_track_boxes_dev")
+
+
+def class_mask(classes=None):
+    """the four words of a zone's or a line's class mask: None (or nothing): every class, else a bit per class 0..127"""
+    m = [0, 0, 0, 0]
+    for c in classes or ():
+        if not 0 <= int(c) < 128:
+            raise ValueError("class %r is outside 0..127" % (c,))
+        m[int(c) >> 5] |= 1 << (int(c) & 31)
+    return m
+
+
+def scene(zones=(), lines=(), anchor=0):
+    """a Scene (ffgpu_scene): zones = [(vertices [(x, y), ...][, dwell_frames[, classes]]), ...], lines = [((ax, ay), (bx, by)[, classes]), ...],
+    anchor 0: the box's centre, 1: its bottom centre"""
+    if len(zones) > SCENE_ZONES or len(lines) > SCENE_LINES:
+        raise ValueError("a scene holds %d zones and %d lines at most" % (SCENE_ZONES, SCENE_LINES))
+    sc = Scene()
+    sc.nzones, sc.nlines, sc.anchor = len(zones), len(lines), anchor
+    for z, zn in enumerate(zones):
+        verts = zn[0]
+        if len(verts) > ZONE_VERTS:
+            raise ValueError("zone %d: %d vertices (%d at most)" % (z, len(verts), ZONE_VERTS))
+        sc.zone[z].nverts, sc.zone[z].dwell_frames = len(verts), zn[1] if len(zn) > 1 else 0
+        for k, (x, y) in enumerate(verts):
+            sc.zone[z].x[k], sc.zone[z].y[k] = x, y
+        sc.zone[z].classes[:] = class_mask(zn[2] if len(zn) > 2 else None)
+    for l, ln in enumerate(lines):
+        (sc.line[l].ax, sc.line[l].ay), (sc.line[l].bx, sc.line[l].by) = ln[0], ln[1]
+        sc.line[l].classes[:] = class_mask(ln[2] if len(ln) > 2 else None)
+    return sc
+
+
+def scene_check(scenes):
+    """ffgpu_scene_check on a list of Scenes (pure host code): raises with what is wrong with the first bad one"""
+    arr = (Scene * max(1, len(scenes)))(*scenes)
+    _check(lib().ffgpu_scene_check(arr, len(scenes)), "ffgpu_scene_check")
+
+
+def scenes_bytes(scenes):
+    """the bytes to upload as d_scenes: the Scenes one after the other"""
+    return b"".join(bytes(s) for s in scenes)
+
+
+def zones_spec(capacity, max_missed=0, identity=ZONES_IDS, min_score=0.0, gate_zone=0, gate_line=0, invert=False):
+    """a ZonesSpec (ffgpu_zones_spec)"""
+    sp = ZonesSpec()
+    sp.capacity, sp.max_missed, sp.identity, sp.flags = capacity, max_missed, identity, ZONES_GATE_INVERT if invert else 0
+    sp.min_score, sp.gate_zone, sp.gate_line = min_score, gate_zone, gate_line
+    return sp
+
+
+def zones_state_bytes(nstreams, capacity):
+    return lib().ffgpu_zones_state_bytes(nstreams, capacity)
+
+
+def zones_state(raw, nstreams, capacity):
+    """([header dict per stream], slots as a ZONE_SLOT_DTYPE array of nstreams x capacity) of a state's bytes (a uint8 array of zones_state_bytes bytes)"""
+    raw = np.ascontiguousarray(raw, np.uint8).reshape(nstreams, ZONES_STATE_HEADER + 64 * capacity)
+    hdr = []
+    for r in raw:
+        w = np.ascontiguousarray(r[:ZONES_STATE_HEADER]).view("<u4")
+        hdr.append(dict(frames=int(w[0]), live=int(w[1]), total_entered=[int(v) for v in w[4:12]], total_left=[int(v) for v in w[12:20]],
+                        total_fwd=[int(v) for v in w[20:28]], total_back=[int(v) for v in w[28:36]]))
+    return hdr, np.ascontiguousarray(raw[:, ZONES_STATE_HEADER:]).view(ZONE_SLOT_DTYPE).reshape(nstreams, capacity)
+
+
+def zones_reset_dev(d_state, nstreams, capacity, which_stream=-1, stream=None):
+    """ffgpu_zones_reset_dev: zero the state of one video stream, or of all (-1), in stream order"""
+    _check(lib().ffgpu_zones_reset_dev(d_state, nstreams, capacity, which_stream, stream), "ffgpu_zones_reset_dev")
+
+
+def zones_boxes_dev(d_records, d_lists, list_stride, streams, spec, d_scenes, d_state, nstreams, d_events, d_ids=None, d_out_records=None, d_out_lists=None,
+                    list_first=None, stream=None):
+    """ffgpu_zones_boxes_dev on device records / lists: record t is the next frame of video stream streams[t] (-1: ignored); d_lists None: the
+    records' own boxes; list_first as draw_boxes_bgr_dev; d_ids: the rows track_boxes_dev wrote (with identity ZONES_IDS)"""
+    first = None if list_first is None else (C.c_int * max(1, len(list_first)))(*[int(v) for v in list_first])
+    arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+    _check(lib().ffgpu_zones_boxes_dev(d_records, d_lists, list_stride, first, arr, len(streams), spec, d_scenes, d_state, nstreams, d_ids, d_events,
+                                       d_out_records, d_out_lists, stream), "ffgpu_zones_boxes_dev")
 
 
 def feature_spec(layer=-1, pool=FFGPU.FEAT_MEAN, post=FFGPU.POST_NONE):

@@ -6,6 +6,7 @@
 #include <vector>
 #include "ffgpu_internal.h"
 #include "ffgpu_args.hpp"
+#include "ffgpu_zones_host.hpp"
 
 #define FFGPU_CHECK(expr)                                                                   \
     do {                                                                                    \
@@ -200,6 +201,10 @@ int ffgpu_launch_redact(const char *what, bool nv12, const DetSource &src, const
 int ffgpu_track_args_check(const char *what, const int *streams, int ntargets, const ffgpu_track_spec *spec, const void *d_state, int nstreams,
                            const void *d_ids, const void *d_out_records, const void *d_out_lists);
 int ffgpu_launch_track(const DetSource &src, const int *streams, int ntargets, const ffgpu_track_spec &spec, void *d_state, void *d_ids, void *d_out_records, void *d_out_lists, hipStream_t s);
+
+// zones and lines (ffgpu_zones.inc): the launches; the checks both entry points share are host code with no HIP in it (ffgpu_zones_host.hpp)
+int ffgpu_launch_zones(const DetSource &src, const int *streams, int ntargets, const ffgpu_zones_spec &spec, const void *d_scenes, void *d_state, const void *d_ids,
+                       void *d_events, void *d_out_records, void *d_out_lists, hipStream_t s);
 
 // the crops classified (ffgpu_feature.inc): the checks both entry points share, and the launches.  Features: frame n of the tensor is frame n % pn of
 // parts[n / pn], a CNHW tensor of pn frames (a split executor has one part per chain; at most 8).

@@ -1402,6 +1402,24 @@ extern "C" int ffgpu_exec_track(ffgpu_exec *ex, int which, const int *streams, i
     return ffgpu_launch_track(src, streams, ntargets, *spec, d_state, d_ids, d_out_records, d_out_lists, s);
 }
 
+// -------------------------------------------------------------------------- zones and lines (include/ffcnn_hip.h; kernel: ffgpu_zones.inc)
+// A post-pass like the tracker, on the stream of the forward or merge it follows: reads the records and full lists (per entry, or the merged ones), the
+// caller's scenes and ids, writes the caller's state, events and gated records and nothing of the executor's.
+extern "C" int ffgpu_exec_zones(ffgpu_exec *ex, int which, const int *streams, int ntargets, const ffgpu_zones_spec *spec, const void *d_scenes, void *d_state,
+                                int nstreams, const void *d_ids, void *d_events, void *d_out_records, void *d_out_lists, void *stream)
+{
+    const char *const what = "exec_zones";
+    if (!exec_ok(ex, what)) return -1;
+    if (ffgpu_zones_args_check(what, streams, ntargets, spec, d_scenes, d_state, nstreams, d_ids, d_events, d_out_records, d_out_lists)) return -1;
+    DetSource src;
+    hipStream_t s;
+    if (exec_source(ex, what, "ZONES", "zones pass", which, ntargets, stream, src, &s)) return -1;
+    // the stride is also the pitch of the ids, the events and the caller's output lists: a list too long is refused, not clamped (as the tracker)
+    if (src.longest > (1 << 24)) { ffgpu_set_error("%s: lists of up to %lld boxes are too long", what, src.longest); return -1; }
+    src.stride = (int)src.longest;
+    return ffgpu_launch_zones(src, streams, ntargets, *spec, d_scenes, d_state, d_ids, d_events, d_out_records, d_out_lists, s);
+}
+
 // -------------------------------------------------------------------------- the crops classified (include/ffcnn_hip.h; kernels: ffgpu_feature.inc)
 // The tensor a feature spec names on this plan: its id and the frame's c x h x w, or -1 with a message.  layer == -1 is the last layer's, aliases
 // resolved by canon[] (a trailing dropout or one-source route holds its source's tensor id).  Nothing takes that tensor's floats after the forward: the

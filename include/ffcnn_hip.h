@@ -865,6 +865,145 @@ int ffgpu_redact_boxes_nv12_dev(const void *d_records, const void *d_lists, int 
 int ffgpu_exec_redact_bgr (ffgpu_exec *ex, int which, const ffgpu_bgr_frame  *targets, int ntargets, const ffgpu_redact_spec *spec, void *stream);
 int ffgpu_exec_redact_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_frame *targets, int ntargets, const ffgpu_redact_spec *spec, void *stream);
 
+/* ---- zones and lines: identified boxes counted, flagged and gated on the device ----------------------------------------------------------------
+ * What a deployment asks of a tracked stream: how many are in this region now, who entered or left it, how many crossed this line and which way,
+ * who has been standing here for 200 frames -- and "redact everybody outside the ticketed area", "crop only those who crossed".  What follows is a
+ * stateful, per-stream geometry pass over any record laid out like the tracked one; its products are an event row, two flag words per box and a
+ * GATED RECORD the draw, crop, redact and track operators take unchanged.  The result is a pure function of its inputs: the same bytes on every run
+ * (tests/zones/zoneref.py restates it in numpy).
+ *
+ * Scene: device memory, one ffgpu_scene per video stream: d_scenes[s] for stream s.  Coordinates are the records' own picture pixels.  `classes` is a
+ * bit per class 0..127 (class c: bit c % 32 of word c / 32); all four words zero: every class.  A box of KNOWN class c is ADMITTED by a mask when the
+ * mask is all zero or 0 <= c < 128 and its bit is set; a box of UNKNOWN class only by an all-zero mask.  anchor 0: the box's centre, anything else:
+ * its bottom centre.  The kernel is total over any bytes: nzones and nlines are clamped to 0..8, a zone with nverts outside 3..8 or with a NaN among
+ * its nverts vertices contains nothing, NaN compares false everywhere.  ffgpu_scene_check says what is wrong with a scene before it is uploaded.
+ *
+ * Arithmetic: fp32, not contracted, no division.
+ *   Anchor of a box: px = (x1 + x2) * 0.5f; py = anchor ? y2 : (y1 + y2) * 0.5f.
+ *   INSIDE a zone, by the even-odd rule: for every edge i -> j = (i + 1) % nverts with (yi > py) != (yj > py):
+ *     d = (xj - xi) * (py - yi) - (px - xi) * (yj - yi); the edge toggles the result when yj > yi ? d > 0 : d < 0.
+ *   Side of P of the directed line A -> B: side(P) = ((bx - ax) * (Py - ay) - (by - ay) * (Px - ax)) > 0.
+ *   An object with previous anchor P0 and current anchor P1 CROSSES the line A -> B when side(P0) != side(P1) with respect to A -> B and A and B
+ *   lie on different sides of P0 -> P1 by the same formula; FORWARD when side(P1) is true, else BACKWARD.
+ * On coordinates of an integer grid (or of eighths) every product is exact and a point on an edge shared by two zones is in exactly one of them.
+ *
+ * Identity (spec.identity): where an object's identity and class come from.  FFGPU_ZONES_NONE: no identity (geometry only), class = type.
+ * FFGPU_ZONES_TYPE: identity = the box's type (a tracked or relabelled record), class unknown.  FFGPU_ZONES_IDS: identity = d_ids row t, entry 8 + k
+ * for box k of the list (rows of 8 + S ints, exactly what ffgpu_track_boxes_dev writes, S this call's S), class = type.  An identity <= 0 is ANONYMOUS.
+ *
+ * State, in the caller's device memory (16-byte aligned, ffgpu_zones_state_bytes(nstreams, capacity) bytes; all-zero is the valid empty state, so
+ * hipMemsetAsync or ffgpu_zones_reset_dev initialises it): per stream a 144-byte header { int frames, live, reserved[2]; unsigned total_entered[8],
+ * total_left[8], total_fwd[8], total_back[8]; } and `capacity` slots ffgpu_zone_slot of 64 bytes.  id == 0 is a free slot and a free slot is all zero.
+ * Only bits 0..7 of a slot's `inside` are read.  Frame numbers and counters are 32-bit and wrap; differences of frame numbers are taken modulo 2^32
+ * and read as signed.
+ *
+ * One frame of one stream, in this order (streams, ntargets, time order and -1 entries: exactly as ffgpu_track_boxes_dev; frame = `frames` before 7):
+ *   1. Considered boxes.  The record's list is walked in list order (d_lists, list_stride, list_first and the clamps of the draw operators).  A box is
+ *      CONSIDERED when score >= min_score (a NaN score never is), until FFGPU_ZONES_DETS boxes are; further qualifying boxes are counted in `dropped`.
+ *   2. Geometry.  Every considered box gets its anchor and its `inside` mask: bit z for each zone z < nzones whose class mask admits it and that
+ *      contains the anchor.
+ *   3. Owners.  A considered box whose identity is > 0 OWNS it, unless an earlier considered box of the frame has the same identity: then it is a
+ *      DUPLICATE.  Anonymous, duplicate and (6.) refused boxes have their inside bits and count in the occupancy, but cause no event.
+ *   4. Known owners: the identity is the id of a slot (of the lowest such slot).  entered = inside & ~slot.inside, left = slot.inside & ~inside;
+ *      since[z] = frame for the entered zones; every line l < nlines whose class mask admits the box is tested with P0 = the slot's point and P1 = the
+ *      anchor; the box is LOITERING in every zone z it is inside with dwell_frames > 0 and frame - since[z] >= dwell_frames.  The slot then takes the
+ *      anchor and the mask, and last = frame.
+ *   5. Frees.  An occupied slot no owner of this frame named, with frame - last > max_missed, is zeroed; every zone in its mask counts one `left`.
+ *   6. Fresh owners (owners that are not known) take the lowest free slots in list order, after the frees: id = the identity, the anchor, the mask,
+ *      last = frame, since[z] = frame for the zones of the mask and 0 for the others; entered = inside; no line is tested.  An owner that finds no
+ *      free slot is REFUSED.
+ *   7. The header's totals grow by the frame's entered, left (frees included), fwd and back counts per zone / line; live = the occupied slots;
+ *      frames += 1 -- also for a frame without boxes.
+ *
+ * Outputs per record t; every byte is written, for streams[t] == -1 as zero.  S = list_stride, or FFGPU_MAX_DET when d_lists is NULL.
+ *   d_events: row t of FFGPU_ZONES_ROW + 2 S ints: 16 ints { considered, known, fresh, refused, duplicate, anonymous, dropped, freed, live, frame,
+ *     0 x 6 }; 8 groups { occupancy, entered, left, loitering }, one per zone (occupancy: the considered boxes inside); 8 groups { fwd, back }, one per
+ *     line; then two words per list box k (at FFGPU_ZONES_ROW + 2 k), zero for a box that was not considered.
+ *     Word 0: bit z: inside zone z; 8 + z: entered it this frame; 16 + z: left it this frame; 24 + z: loitering in it.
+ *     Word 1: bit l: crossed line l forward; 8 + l: backward; 16 known, 17 fresh, 18 refused, 19 duplicate, 20 anonymous.
+ *   d_out_records / d_out_lists (may be NULL; list t at box t x S): the GATED RECORD: the n considered boxes SELECTED by the gate, in list order and
+ *     unchanged.  A box is selected when (((word0 & gate_zone) | (word1 & gate_line)) != 0) != (flags & FFGPU_ZONES_GATE_INVERT).  It is laid out by
+ *     the tracked record's rules: count = min(n, FFGPU_MAX_DET), nfull = n, ncand and overflow bit 0 copied, bit 2 = n > FFGPU_MAX_DET; unused box
+ *     slots of the record and of the list are zero.  The outputs must not overlap the inputs.
+ * The gated record is the composition point and needs no new code: redact it (OUTSIDE off) to hide who is inside a zone, crop it to look once at who
+ * crossed, draw it, track it. */
+#define FFGPU_SCENE_ZONES 8
+#define FFGPU_SCENE_LINES 8
+#define FFGPU_ZONE_VERTS  8
+#define FFGPU_ZONES_DETS  128  /* considered boxes per frame at most; also the largest capacity */
+#define FFGPU_ZONES_ROW   64   /* ints of an event row in front of the boxes' words */
+typedef struct {
+    float x[FFGPU_ZONE_VERTS], y[FFGPU_ZONE_VERTS];   /* the polygon's vertices 0 .. nverts-1, either winding                             */
+    int   nverts;                   /* 3..8                                                                                         */
+    int   dwell_frames;             /* >= 0; 0: nobody loiters here                                                                 */
+    unsigned classes[4];            /* a bit per class 0..127; all zero: every class                                                */
+    int   reserved[2];              /* 0                                                                                            */
+} ffgpu_zone;                       /* 96 bytes: x 0, y 32, nverts 64, dwell_frames 68, classes 72, reserved 88                     */
+typedef struct {
+    float ax, ay, bx, by;           /* the directed segment A -> B                                                                  */
+    unsigned classes[4];
+} ffgpu_line;                       /* 32 bytes: ax 0, ay 4, bx 8, by 12, classes 16                                                */
+typedef struct {
+    ffgpu_zone zone[FFGPU_SCENE_ZONES];
+    ffgpu_line line[FFGPU_SCENE_LINES];
+    int   nzones, nlines;           /* 0..8 each                                                                                    */
+    int   anchor;                   /* 0: the box's centre; 1: its bottom centre                                                    */
+    int   reserved;                 /* 0                                                                                            */
+} ffgpu_scene;                      /* 1040 bytes: zone 0, line 768, nzones 1024, nlines 1028, anchor 1032, reserved 1036           */
+
+#define FFGPU_ZONES_NONE 0          /* identity: none (every box anonymous); class = type                                           */
+#define FFGPU_ZONES_TYPE 1          /* identity = the box's type; class unknown                                                     */
+#define FFGPU_ZONES_IDS  2          /* identity = d_ids; class = type                                                               */
+#define FFGPU_ZONES_GATE_INVERT 1   /* flags bit 0: the gated record holds the considered boxes the gate does NOT select            */
+typedef struct {
+    int   capacity;                 /* 1..128: slots per stream (as the state was sized)                                            */
+    int   max_missed;               /* 0..2^20: an object survives this many consecutive frames without being seen                  */
+    int   identity;                 /* FFGPU_ZONES_NONE | _TYPE | _IDS                                                              */
+    int   flags;                    /* 0 | FFGPU_ZONES_GATE_INVERT; any other bit is rejected                                       */
+    float min_score;                /* finite, in [0, 1]: a box is considered from this score on                                    */
+    unsigned gate_zone, gate_line;  /* the gate's masks over word 0 and word 1 of a box                                             */
+    int   reserved;                 /* 0                                                                                            */
+} ffgpu_zones_spec;                 /* 32 bytes: capacity 0, max_missed 4, identity 8, flags 12, min_score 16, gate_zone 20,        */
+                                    /* gate_line 24, reserved 28                                                                    */
+typedef struct {
+    int   id;                       /* 0: a free slot (all zero)                                                                    */
+    float px, py;                   /* the object's anchor when it was last seen                                                    */
+    int   inside;                   /* its zones then (bits 0..7)                                                                   */
+    int   last;                     /* the stream's frame number when it was last seen                                              */
+    int   reserved[3];              /* 0                                                                                            */
+    int   since[FFGPU_SCENE_ZONES]; /* the frame number at which it entered zone z                                                  */
+} ffgpu_zone_slot;                  /* 64 bytes, behind each stream's 144-byte header                                               */
+
+/* pure host code: the bytes of the state of nstreams (1..65536) streams of capacity (1..128) slots; 0 for arguments outside their ranges */
+size_t ffgpu_zones_state_bytes(int nstreams, int capacity);
+/* pure host code: n scenes in HOST memory checked before their upload; 0, or -1 with the message (ffgpu_last_error) naming the scene and what is
+ * wrong: nzones or nlines outside 0..8, a used zone's nverts outside 3..8, a non-finite coordinate of a used vertex or line, a used line with A
+ * equal to B, a negative dwell_frames, an anchor that is neither 0 nor 1, a reserved field that is not 0. */
+int ffgpu_scene_check(const ffgpu_scene *host_scenes, int n);
+/* zeroes the state of one stream, or of all with which_stream == -1, in stream order (a memset; no kernel) */
+int ffgpu_zones_reset_dev(void *d_state, int nstreams, int capacity, int which_stream, void *stream);
+
+/* The operator, on device records and lists with no executor.  d_records, d_lists, list_stride and the HOST array list_first are the draw operators'.
+ * One workgroup per video stream walks that stream's records of the call serially, scene and state in LDS; streams, list_first and spec are HOST memory
+ * and free again on return; the tables travel as kernel arguments, 128 records per launch, the launches of one call in order on `stream`.  Enqueued
+ * without synchronising.  Rejected before anything is launched, with the entry's index in the message where there is one: NULL records, streams, spec,
+ * scenes, state or events, ntargets < 1, nstreams outside 1..65536, a stream index outside -1..nstreams-1, a spec field outside its range, unknown flag
+ * bits or reserved != 0, a state that is not 16-byte aligned, a bad list_stride, a negative list start, d_out_lists without d_out_records, and d_ids:
+ * it is required exactly when identity == FFGPU_ZONES_IDS (NULL then, or given otherwise, is rejected).  A rejected call leaves the state as it was. */
+int ffgpu_zones_boxes_dev(const void *d_records, const void *d_lists, int list_stride, const int *list_first, const int *streams, int ntargets,
+                          const ffgpu_zones_spec *spec, const void *d_scenes, void *d_state, int nstreams, const void *d_ids, void *d_events,
+                          void *d_out_records, void *d_out_lists, void *stream);
+
+#define FFGPU_ZONES_ENTRIES 0   /* entry n's full post-NMS list is record n; ntargets == batch; S as FFGPU_TRACK_ENTRIES                          */
+#define FFGPU_ZONES_MERGED  1   /* picture g's merged list (last ffgpu_exec_merge_tiles) is record g; ntargets == its nimages; S as FFGPU_TRACK_MERGED */
+/* On an executor: a post-pass like ffgpu_exec_track, enqueued on `stream` (NULL = the executor's own; it must be the stream of the forward or merge it
+ * follows) without synchronising.  The captured graph, the records, the full lists, the ring and the host mirror are untouched; scenes, state, events and
+ * the gated records are the caller's, and d_ids is what ffgpu_exec_track wrote for the same `which`.  Works on FFGPU_SPLIT2 executors.  Rejected like the
+ * operator, and: ntargets not as stated, a `which` that is neither, FFGPU_ZONES_MERGED when no merge has run, the wrong stream.  A rejected call leaves
+ * the state and the executor usable. */
+int ffgpu_exec_zones(ffgpu_exec *ex, int which, const int *streams, int ntargets, const ffgpu_zones_spec *spec, const void *d_scenes, void *d_state,
+                     int nstreams, const void *d_ids, void *d_events, void *d_out_records, void *d_out_lists, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
