@@ -11,6 +11,7 @@
 #include "ffgpu_front.inc"
 #include "ffgpu_irb_wave.inc"
 #include "ffgpu_irb_wave2.inc"
+#include "ffgpu_irb_stage.inc"
 #include "ffgpu_pw_x3.inc"
 #include "ffgpu_pw_x3t.inc"
 #include "ffgpu_conv_x3.inc"
@@ -1670,4 +1671,69 @@ int ffgpu_launch_irb(const IrbDesc &d, hipStream_t s)
     if (c.family == IRB_THIN) return launch_irb_thin(d, s);
     if (!d.pk) { ffgpu_set_error("irb: constants not packed"); return -1; }
     return c.family == IRB_WAVE ? irbw_kernels[c.inst].launch(irbw_params(d), c, s) : irb_kernels[c.inst].launch(irb_params(d), c, s);
+}
+
+// ---- a run of blocks on one small plane as one launch (ffgpu_irb_stage.inc).  The run is described by its blocks' own descriptors: each keeps the plan
+// ffgpu_irb_plan gave it and the image ffgpu_irb_pack wrote for that plan, and the stage kernel reads those images.  It takes a run only where every
+// block's plan is the XL form with seven waves and unfolded partial sums -- the summation order the stage kernel reproduces bit for bit.
+static bool irb_stage_params(const IrbDesc *blocks, int B, IrbStageP &p, size_t &lds)
+{
+    if (B < 2 || B > IRBS_MAXB) return false;
+    const IrbDesc &d0 = blocks[0];
+    for (int b = 0; b < B; b++) {
+        const IrbDesc &d = blocks[b];
+        const IrbPlan &c = d.plan;
+        if (d.ic != 48 || d.ec != 224 || d.oc != 48 || d.stride != 1 || d.OH != d.H || d.OW != d.W) return false;
+        if (d.N != d0.N || d.H != d0.H || d.W != d0.W || d.act1 != d0.act1 || d.actd != d0.actd) return false;
+        if (act_slope(d.act2) != 1.f || act_slope(d.res_act) != 1.f) return false;
+        if (c.family != IRB_WAVE || !c.xl || !c.x3 || c.half || c.G != IRBS_WAVES || c.KS1 != 12 || c.OT != 3 || c.ngroups != 2 * IRBS_WAVES) return false;
+        if (c.region / (c.OT * 1024) < c.G) return false;                  // (k_irbw would fold the upper waves' sums onto the lower ones first)
+    }
+    const int plane = d0.H * d0.W, TWq = (d0.W + 3) / 4;
+    if (plane > 128 || TWq * d0.H > 32) return false;                      // two expand strips, two strips of output quads
+    p = IrbStageP{};
+    p.B = B; p.N = d0.N; p.H = d0.H; p.W = d0.W;
+    p.act1 = act_slope(d0.act1); p.actd = act_slope(d0.actd);
+    p.TWq = TWq; p.P = 4 * TWq + 2; p.EP = p.P * (d0.H + 2);
+    int total;
+    irbw_layout(d0.plan, p.o_w2, p.o_cs, p.cs_floats, total);
+    if (p.cs_floats > 2 * IRBS_WAVES * 64 * 4) return false;
+    p.e_off = p.cs_floats;
+    p.e_slice = std::max(16 * p.EP, 2048);                                 // 8 pair planes; a reduction pass parks 2 x 4 rows of 256 floats
+    p.xi_off = p.e_off + IRBS_WAVES * p.e_slice;
+    p.f_off = p.xi_off + 2 * 4 * 64 * IRBW_XL_DW;
+    lds = (size_t)(p.f_off + 48 * plane) * sizeof(float);
+    p.m_w = umulhi_magic(d0.W); p.m_twq = umulhi_magic(TWq); p.m_plane = umulhi_magic(plane);
+    return lds <= IRB_LDS_MAX;
+}
+
+bool ffgpu_irb_stage_ok(const IrbDesc *blocks, int B)
+{
+    IrbStageP p; size_t lds;
+    return irb_stage_params(blocks, B, p, lds);
+}
+
+// (the probe behind ffgpu_irb_stage_plan_text, tests/test_irb_stage_plan.py) wanted: the executor's own conditions hold
+int ffgpu_irb_stage_line(const IrbDesc *blocks, int B, bool wanted, char *buf, size_t cap)
+{
+    IrbStageP p; size_t lds;
+    if (!wanted || !irb_stage_params(blocks, B, p, lds)) return snprintf(buf, cap, "blocks B=%d launches=%d", B, B);
+    return snprintf(buf, cap, "stage B=%d launches=1 N=%d H=%d W=%d act=%g,%g TWq=%d P=%d EP=%d o_w2=%d o_cs=%d cs_floats=%d e_off=%d e_slice=%d xi_off=%d f_off=%d m=%u,%u,%u lds=%zu grid=%d block=%d",
+                    p.B, p.N, p.H, p.W, p.act1, p.actd, p.TWq, p.P, p.EP, p.o_w2, p.o_cs, p.cs_floats, p.e_off, p.e_slice, p.xi_off, p.f_off, p.m_w, p.m_twq, p.m_plane, lds, p.N, IRBS_WAVES * 64);
+}
+
+int ffgpu_launch_irb_stage(const IrbDesc *blocks, int B, hipStream_t s)
+{
+    IrbStageP p; size_t lds;
+    if (!irb_stage_params(blocks, B, p, lds)) { ffgpu_set_error("irb_stage: the run of %d blocks does not fit the stage kernel", B); return -1; }
+    p.in = blocks[0].in; p.out = blocks[B - 1].out;
+    for (int b = 0; b < B; b++) {
+        if (!blocks[b].pk) { ffgpu_set_error("irb_stage: constants not packed"); return -1; }
+        p.pk[b] = blocks[b].pk;
+    }
+    if (!p.in || !p.out) { ffgpu_set_error("irb_stage: no tensors"); return -1; }
+    if (lds_allow((const void *)k_irb_stage, lds, "irb_stage")) return -1;
+    hipLaunchKernelGGL(k_irb_stage, dim3((unsigned)p.N), dim3(IRBS_WAVES * 64), lds, s, p);
+    LAUNCH_OK("irb_stage");
+    return 0;
 }

@@ -81,6 +81,12 @@ int    ffgpu_irb_pack(const IrbDesc &d, float *pk, hipStream_t s);
 int    ffgpu_launch_irb(const IrbDesc &d, hipStream_t s);
 int    ffgpu_irb_plan_line(const IrbDesc &d, char *buf, size_t cap);   // the plan as one canonical line of text (ffgpu_irb_plan_text)
 int    ffgpu_irb_keys(char *buf, size_t cap);                             // the key of every instantiation of the three families, one per line (ffgpu_irb_instantiations)
+// a run of B >= 2 blocks on one small plane (48 -> 224 -> 48, stride 1, linear project and shortcut) as one launch, one frame per workgroup
+// (ffgpu_irb_stage.inc): the blocks' own planned descriptors, whose packed images the kernel reads; in = blocks[0].in, out = blocks[B - 1].out
+#define IRBS_MAXB 8              /* blocks in a run */
+bool   ffgpu_irb_stage_ok(const IrbDesc *blocks, int B);
+int    ffgpu_launch_irb_stage(const IrbDesc *blocks, int B, hipStream_t s);
+int    ffgpu_irb_stage_line(const IrbDesc *blocks, int B, bool wanted, char *buf, size_t cap);   // one launch ("stage ...") or B of them ("blocks ..."), as one line of text
 bool   ffgpu_front_ok(const ConvDesc &c, const IrbDesc &d);      // first layer (3x3 s2, 3 -> 8) + thin block as one streaming kernel
 // How a forward's batch arrives.  IN_F32: fp32 frames (ExecParams::frames; the staging kernels of ffgpu_input.inc write them for u8 sources the first
 // kernel cannot take).  The u8 forms are read by k_front itself: IN_U8 frames of the net's own geometry (ExecParams::bgr), IN_BGR_FRAMES / IN_NV12_FRAMES

@@ -151,7 +151,7 @@ static int copy_d2h(void *h_dst, const void *d_src, size_t bytes)
 // --------------------------------------------------------------------------
 #define FFGPU_INTERNAL_CHILD 0x40000000   /* executor flag used only inside this file: a half of a split executor */
 
-enum StepKind { S_CONV, S_POOL, S_UPSAMPLE, S_ADD, S_COPY, S_YOLO, S_NMS, S_CLEAR, S_TOCNHW, S_IRB, S_FRONT, S_DWPW };
+enum StepKind { S_CONV, S_POOL, S_UPSAMPLE, S_ADD, S_COPY, S_YOLO, S_NMS, S_CLEAR, S_TOCNHW, S_IRB, S_FRONT, S_DWPW, S_STAGE };
 
 struct Step {
     StepKind kind;
@@ -167,6 +167,7 @@ struct Step {
     int      w, h, c, fs, stride, flag;
     YoloHead head;
     IrbDesc  irb;            // S_IRB: fused expand -> depthwise -> project [+ shortcut]
+    std::vector<IrbDesc> run; // S_STAGE: the blocks of a run merged into one launch (ffgpu_irb_stage.inc), each with its own plan and packed image
     float   *out2[2];        // S_POOL: further stride-1 max pools of the same tensor merged into this launch (fs2[k] != 0)
     int      fs2[2];
     int      lane;           // 0: main stream, 1: side stream (a detection head that runs beside the rest of the net)
@@ -271,6 +272,13 @@ static float *tensor_ptr(const ffgpu_exec *ex, int t) { return ex->arena + ex->l
 // plan() = the layout (ffgpu_plan.hpp: pure host code), the arena, the step list built from the layout, the rewrites of that list, the packed
 // constants' places, and whether the captured graph is free of the input pointer.
 // the one place the planner's switches are read: the flags, and the environment at every create
+// runs of small-plane blocks merge into one launch (ffgpu_irb_stage.inc) only where that launch's one workgroup per frame has company: several chains
+// in flight and at least 32 frames each.  A single chain of 64 workgroups on 256 CUs would lose against the per-block launches' two tiles per frame.
+static bool stage_wanted(int N, int flags)
+{
+    return (flags & FFGPU_CONCURRENT) && !(flags & (FFGPU_KEEP_ALL | FFGPU_NO_FUSE)) && N >= 32 && knob(K_IRB_STAGE) != 0;
+}
+
 static PlanOptions plan_options(const ffgpu_exec *ex)
 {
     PlanOptions o;
@@ -285,6 +293,7 @@ static PlanOptions plan_options(const ffgpu_exec *ex)
     o.branch = knob(K_BRANCH) && !ex->is_child;
     o.no_irb = knob(K_NO_IRB); o.irb_min_ec = knob(K_IRB_MIN_EC);
     o.dwpw = knob(K_DWPW);
+    o.stage = stage_wanted(ex->N, ex->flags);
     return o;
 }
 
@@ -327,7 +336,13 @@ static int plan_layout(ffgpu_exec *ex, std::vector<IrbDesc> &irb_planned)
         return true;
     };
     auto pair_ok = [&](int p0) { return ffgpu_dwpw_ok(layer_desc(ex, p0), layer_desc(ex, p0 + 1)); };
-    return ffgpu_net_layout(ex->net->layer_list, ex->net->layer_num, opt, block_ok, pair_ok, ex->layout);
+    static_assert(FFGPU_STAGE_MAX_BLOCKS == IRBS_MAXB, "the layout's longest run is the stage kernel's");
+    auto run_ok = [&](const std::vector<int> &tails) {              // (the blocks' last layers: their planned descriptors are in irb_planned by now)
+        std::vector<IrbDesc> run;
+        for (int t : tails) run.push_back(irb_planned[t]);
+        return ffgpu_irb_stage_ok(run.data(), (int)run.size());
+    };
+    return ffgpu_net_layout(ex->net->layer_list, ex->net->layer_num, opt, block_ok, pair_ok, run_ok, ex->layout);
 }
 
 // stage 2
@@ -365,8 +380,18 @@ static int plan_steps(ffgpu_exec *ex, const std::vector<IrbDesc> &irb_planned)
         bool from_input = false;
         switch (a.type) {
         case LAYER_TYPE_CONV: {
-            if (nl.canon[i] == -3) break;                           // expanded tensors of a fused block
-            if (nl.irb_tail[i] >= 0) {
+            if (nl.canon[i] == -3) break;                           // expanded tensors of a fused block; blocks inside a merged run
+            if (nl.stage_first[i] >= 0) {                           // the last block of a merged run: the run's one launch
+                st.kind = S_STAGE;
+                for (int t = nl.stage_first[i] + 2; t <= i; t++) {
+                    if (nl.irb_tail[t] < 0) continue;
+                    IrbDesc d = irb_planned[t];
+                    d.w1 = weights(nl.irb_tail[t]); d.wd = weights(nl.irb_tail[t] + 1); d.w2 = weights(nl.irb_tail[t] + 2);
+                    st.run.push_back(d);
+                }
+                st.run.front().in = ptr(nl.src(nl.stage_first[i] - 1));
+                st.run.back().out = ptr(nl.canon[i]);
+            } else if (nl.irb_tail[i] >= 0) {
                 const int p0 = nl.irb_tail[i];
                 IrbDesc &d = st.irb = irb_planned[i];
                 st.kind = S_IRB;
@@ -397,6 +422,8 @@ static int plan_steps(ffgpu_exec *ex, const std::vector<IrbDesc> &irb_planned)
             S.push_back(st);
             break; }
         case LAYER_TYPE_AVGPOOL: case LAYER_TYPE_MAXPOOL: case LAYER_TYPE_UPSAMPLE: case LAYER_TYPE_SHORTCUT: {
+            if (nl.canon[i] == -3) break;                           // a shortcut inside a merged run: added on chip
+            if (a.type == LAYER_TYPE_SHORTCUT && i > 0 && nl.canon[i - 1] == i) break;     // absorbed by the producing conv (the last of a merged run: its other side has no tensor)
             const float *src = in_ptr(i, &from_input);
             // a shortcut whose OTHER side is the net input (from = a dropout in front of every other layer)
             const bool b_input = a.type == LAYER_TYPE_SHORTCUT && nl.src(a.depend_list[0]) == -1;
@@ -413,7 +440,6 @@ static int plan_steps(ffgpu_exec *ex, const std::vector<IrbDesc> &irb_planned)
             st.in_is_input = from_input;
             st.a = src;
             if (a.type == LAYER_TYPE_SHORTCUT) {
-                if (nl.canon[i - 1] == i) break;                    // absorbed by the producing conv
                 st.kind = S_ADD;
                 st.b = b_input ? cnhw_input : ptr(nl.src(a.depend_list[0]));      // (batch 1: patched to the frames at launch)
                 st.b_is_input = b_input && N == 1;
@@ -513,6 +539,7 @@ static void rewrite_steps(ffgpu_exec *ex)
 static size_t pack_floats(const Step &st)
 {
     if (st.kind == S_IRB) return ffgpu_irb_pack_floats(st.irb);
+    if (st.kind == S_STAGE) { size_t n = 0; for (const IrbDesc &d : st.run) n += ffgpu_irb_pack_floats(d); return n; }
     if (st.kind == S_DWPW) return ffgpu_dwpw_pack_floats(st.conv, st.conv2);
     if (st.kind == S_CONV) return ffgpu_pw_pack_floats(st.conv);
     return 0;
@@ -534,6 +561,7 @@ static int place_constants(ffgpu_exec *ex)
     for (Step &st : ex->steps) {
         const size_t n = pack_floats(st);
         if (st.kind == S_IRB) st.irb.pk = ex->d_pack + off;
+        else if (st.kind == S_STAGE) { size_t o = off; for (IrbDesc &d : st.run) { d.pk = ex->d_pack + o; o += ffgpu_irb_pack_floats(d); } }
         else if (st.kind == S_DWPW) st.conv2.wpack = ex->d_pack + off;
         else if (st.kind == S_CONV && n) st.conv.wpack = ex->d_pack + off;
         off += n;
@@ -567,6 +595,7 @@ static int repack(ffgpu_exec *ex, hipStream_t s)
 {
     for (const Step &st : ex->steps) {
         if (st.kind == S_IRB && ffgpu_irb_pack(st.irb, const_cast<float *>(st.irb.pk), s)) return -1;
+        if (st.kind == S_STAGE) for (const IrbDesc &d : st.run) if (ffgpu_irb_pack(d, const_cast<float *>(d.pk), s)) return -1;
         if (st.kind == S_DWPW && ffgpu_dwpw_pack(st.conv, st.conv2, const_cast<float *>(st.conv2.wpack), s)) return -1;
         if (st.kind == S_CONV && st.conv.wpack && ffgpu_pw_pack(st.conv, const_cast<float *>(st.conv.wpack), s)) return -1;
     }
@@ -624,6 +653,8 @@ static int issue_step(ffgpu_exec *ex, const Step &st, const InputSrc &in, hipStr
         return 0; }
     case S_IRB:
         return ffgpu_launch_irb(st.irb, s);
+    case S_STAGE:
+        return ffgpu_launch_irb_stage(st.run.data(), (int)st.run.size(), s);
     case S_DWPW:
         return ffgpu_launch_dwpw(st.conv, st.conv2, st.conv2.wpack, s);
     case S_FRONT: {
@@ -962,6 +993,8 @@ static double step_model_bytes(const ffgpu_exec *ex, const Step &st)
         return 4.0 * (N * d.ic * d.ih * d.iw + N * d.oc * d.oh * d.ow * (d.residual ? 2 : 1) + rows(d)); }
     case S_IRB: { const IrbDesc &d = st.irb;
         return 4.0 * (N * d.ic * d.H * d.W + N * d.oc * d.OH * d.OW * (d.residual ? 2 : 1) + (double)d.ec * (d.ic + 4 + 16) + (double)d.oc * (d.ec + 4)); }
+    case S_STAGE: { const IrbDesc &d = st.run.front();           // the frame in, the frame out, every block's filter rows; nothing in between leaves the chip
+        return 4.0 * (N * d.ic * d.H * d.W + N * d.oc * d.OH * d.OW + (double)st.run.size() * ((double)d.ec * (d.ic + 4 + 16) + (double)d.oc * (d.ec + 4))); }
     case S_DWPW: { const ConvDesc &a = st.conv, &b = st.conv2;
         return 4.0 * (N * a.ic * a.ih * a.iw + N * b.oc * b.oh * b.ow + rows(a) + rows(b)); }
     case S_FRONT: { const ConvDesc &c = st.conv; const IrbDesc &d = st.irb;
@@ -1850,6 +1883,19 @@ extern "C" int ffgpu_irb_plan_text(int batch, int iw, int ih, int ic, int ec, in
     d.flags = flags & FFGPU_CONCURRENT;
     (void)ffgpu_irb_plan(d);
     return ffgpu_irb_plan_line(d, buf, (size_t)cap);
+}
+
+// pure host code: what an executor of `batch` frames made with `flags` does with a run of `blocks` blocks 48 -> 224 -> 48 on an iw x ih plane
+extern "C" int ffgpu_irb_stage_plan_text(int batch, int iw, int ih, int blocks, int act1, int actd, int flags, char *buf, int cap)
+{
+    if (!buf || cap < 1 || batch < 1 || iw < 1 || ih < 1 || blocks < 1 || blocks > 64) { ffgpu_set_error("irb_stage_plan_text: bad arguments"); return -1; }
+    std::vector<IrbDesc> run((size_t)blocks, IrbDesc{});
+    for (IrbDesc &d : run) {
+        irb_fill(d, batch, iw, ih, 48, 224, 48, 1, act1, actd, 0, 0);
+        d.flags = flags & FFGPU_CONCURRENT;
+        if (!ffgpu_irb_plan(d)) return snprintf(buf, (size_t)cap, "unsupported");
+    }
+    return ffgpu_irb_stage_line(run.data(), blocks, stage_wanted(batch, flags), buf, (size_t)cap);
 }
 
 // pure host code: the key of every fused-block instantiation, one per line, from the tables the planner dispatches through

@@ -38,6 +38,7 @@ enum KnobClass { KNOB_PRODUCT, KNOB_TUNING, KNOB_TEST, KNOB_LAB };
     X(NODE_PACK_BOXES,   "FFGPU_NODE_PACK_BOXES",   INT,  0,             PRODUCT, "room per frame in a shard's packed record block; 0 or less: 16, the constant of the same name in ffgpu_node.inc") \
     X(NO_IRB,            "FFGPU_NO_IRB",            ON,   0,             TUNING,  "no fused inverted-residual blocks: their three layers as three kernels") \
     X(IRB_MIN_EC,        "FFGPU_IRB_MIN_EC",        INT,  24,            TUNING,  "fewest expanded channels of a block the planner fuses (thin blocks apart)") \
+    X(IRB_STAGE,         "FFGPU_IRB_STAGE",         INT,  1,             TUNING,  "runs of 48 -> 224 -> 48 blocks on a small plane as one launch in FFGPU_CONCURRENT executors of 32 frames or more (0: one launch per block)") \
     X(SPLIT_PARTS,       "FFGPU_SPLIT_PARTS",       INT,  2,             TUNING,  "parallel chains of an FFGPU_SPLIT2 executor: 2, 4 or 8 (where the batch divides)") \
     X(NO_INDIRECT,       "FFGPU_NO_INDIRECT",       ON,   0,             TEST,    "the first kernel takes the input address from its arguments, not the parameter block: graphs keyed by input pointer") \
     /* ---- which kernel AUTO takes for a convolution (conv_pick and its *_auto) */ \

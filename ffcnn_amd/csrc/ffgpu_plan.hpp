@@ -30,6 +30,7 @@ struct PlanOptions {
     bool no_irb = false;     // FFGPU_NO_IRB=1
     int  irb_min_ec = 0;     // FFGPU_IRB_MIN_EC, filled in by the executor for its block callable (the layout itself does not read it)
     bool dwpw = false;       // FFGPU_DWPW=1
+    bool stage = false;      // runs of small-plane fused blocks as one launch: an FFGPU_CONCURRENT executor of at least 32 frames, FFGPU_IRB_STAGE not 0
 };
 
 struct NetLayout {
@@ -41,6 +42,8 @@ struct NetLayout {
     std::vector<int>    fused_into;     // conv p -> shortcut s whose add it absorbs
     std::vector<int>    irb_tail;       // layer p + 2 -> p: 1x1 expand -> depthwise 3x3 -> 1x1 project as one fused block
     std::vector<int>    dwpw_tail;      // layer p + 1 -> p: depthwise + pointwise as one launch
+    std::vector<int>    stage_first;    // last layer of the LAST block of a merged run -> first layer of its first block: the run is one launch at that layer
+    std::vector<char>   stage_inner;    // last layer of every other block of a merged run: no launch, no tensor
     int    side_lo = -1, side_hi = -1;  // layers [side_lo, side_hi] form the side lane
     size_t arena_floats = 0;
 
@@ -62,6 +65,7 @@ void ffgpu_layer_reads(const LAYER *ll, const NetLayout &nl, int i, F f)
     for (int k = 0; k < ll[i].depend_num; k++) f(nl.src(ll[i].depend_list[k]));
     if (nl.irb_tail[i] >= 0) f(nl.src(nl.irb_tail[i] - 1));
     if (nl.dwpw_tail[i] >= 0) f(nl.src(nl.dwpw_tail[i] - 1));
+    if (nl.stage_first[i] >= 0) f(nl.src(nl.stage_first[i] - 1));
     if (nl.irb_tail[i] >= 0 && nl.fused_into[i] >= 0) f(nl.src(ll[nl.fused_into[i]].depend_list[0]));
 }
 
@@ -126,6 +130,56 @@ void ffgpu_layout_irb(const LAYER *ll, int L, NetLayout &nl, BlockOk &&block_ok)
         nl.irb_tail[p0 + 2] = p0;
         nl.canon[p0] = nl.canon[p0 + 1] = -3;
         p0 += 2;
+    }
+}
+
+// pass 1b': a maximal run of at least two consecutive fused blocks on one small plane -- 48 -> 224 -> 48 channels, stride 1, at most 128 pixels in at
+// most 32 quads of a row, linear projection, a linear shortcut from the block's own input -- becomes ONE launch that keeps the frame on chip
+// (ffgpu_irb_stage.inc) where run_ok(the blocks' last layers) takes it.  A block's output may feed the next block alone: any other reader ends the
+// run behind that block.  The tensors between the blocks are never materialised: they get no tensor, so no arena range, and cannot be read back.
+constexpr int FFGPU_STAGE_MAX_BLOCKS = 8;
+template <class RunOk>
+void ffgpu_layout_stage(const LAYER *ll, int L, NetLayout &nl, RunOk &&run_ok)
+{
+    auto linear = [](int act) { return act != 1 && act != 2 && act != 3; };
+    // the block that ends at layer t has the stage's shape; its output tensor is the shortcut's
+    auto shaped = [&](int t) {
+        const int p0 = nl.irb_tail[t], s = nl.fused_into[t];
+        if (p0 < 0 || s < 0 || nl.canon[t] != s) return false;
+        const LAYER &a = ll[p0], &b = ll[p0 + 1], &c = ll[p0 + 2];
+        return a.c == 48 && a.fn == 224 && c.fn == 48 && b.stride == 1 && a.w * a.h <= 128 && (a.w + 3) / 4 * a.h <= 32 &&
+               linear(c.activation) && linear(ll[s].activation) && nl.src(ll[s].depend_list[0]) >= 0 && nl.src(ll[s].depend_list[0]) == nl.src(p0 - 1);
+    };
+    // block tn follows block t: it reads t's output, and nothing outside block tn does
+    auto follows = [&](int t, int tn) {
+        const int out = nl.canon[t], p0n = nl.irb_tail[tn], sn = nl.fused_into[tn];
+        if (nl.src(p0n - 1) != out || ll[p0n].w != ll[nl.irb_tail[t]].w || ll[p0n].h != ll[nl.irb_tail[t]].h ||
+            ll[p0n].activation != ll[nl.irb_tail[t]].activation || ll[p0n + 1].activation != ll[nl.irb_tail[t] + 1].activation) return false;
+        for (int i = 0; i < L; i++) {
+            if (ll[i].type == LAYER_TYPE_DROPOUT || (i >= nl.irb_tail[t] && i <= out) || (i >= p0n && i <= sn)) continue;     // (the two blocks' own layers)
+            bool reads = false;
+            ffgpu_layer_reads(ll, nl, i, [&](int x) { reads = reads || x == out; });
+            if (reads) return false;
+        }
+        return true;
+    };
+    for (int t = 0; t < L; t++) {
+        if (nl.irb_tail[t] < 0 || !shaped(t)) continue;
+        std::vector<int> run(1, t);
+        for (int tn = run.back() + 1; tn < L && (int)run.size() < FFGPU_STAGE_MAX_BLOCKS; tn++) {
+            if (nl.irb_tail[tn] < 0) continue;
+            if (!shaped(tn) || !follows(run.back(), tn)) break;
+            run.push_back(tn);
+        }
+        if (run.size() >= 2 && run_ok(run)) {
+            nl.stage_first[run.back()] = nl.irb_tail[run.front()];
+            for (size_t k = 0; k + 1 < run.size(); k++) {
+                const int out = nl.canon[run[k]];
+                nl.stage_inner[run[k]] = 1;
+                for (int i = 0; i < L; i++) if (nl.canon[i] == out) nl.canon[i] = -3;
+            }
+        }
+        t = run.back();
     }
 }
 
@@ -251,8 +305,8 @@ inline void ffgpu_layout_arena(int L, const PlanOptions &opt, NetLayout &nl)
 }
 
 // The whole layout of the L layers at ll (L + 1 entries); -1 with a message when the dependency graph or a route is refused.
-template <class BlockOk, class PairOk>
-int ffgpu_net_layout(const LAYER *ll, int L, const PlanOptions &opt, BlockOk &&block_ok, PairOk &&pair_ok, NetLayout &nl)
+template <class BlockOk, class PairOk, class RunOk>
+int ffgpu_net_layout(const LAYER *ll, int L, const PlanOptions &opt, BlockOk &&block_ok, PairOk &&pair_ok, RunOk &&run_ok, NetLayout &nl)
 {
     nl = NetLayout();
     nl.tensors.assign(L, Tensor());
@@ -260,8 +314,10 @@ int ffgpu_net_layout(const LAYER *ll, int L, const PlanOptions &opt, BlockOk &&b
     nl.readable.assign(L, 0); nl.route_inplace.assign(L, 0);
     nl.nuses.assign(L, 0);
     nl.fused_into.assign(L, -1); nl.irb_tail.assign(L, -1); nl.dwpw_tail.assign(L, -1);
+    nl.stage_first.assign(L, -1); nl.stage_inner.assign(L, 0);
     if (ffgpu_layout_aliases(ll, L, opt, nl)) return -1;
     if (opt.fuse && !opt.no_irb) ffgpu_layout_irb(ll, L, nl, block_ok);
+    if (opt.fuse && !opt.no_irb && !opt.keep_all && opt.stage) ffgpu_layout_stage(ll, L, nl, run_ok);
     if (opt.fuse && opt.dwpw) ffgpu_layout_dwpw(ll, L, nl, pair_ok);
     if (ffgpu_layout_tensors(ll, L, opt, nl)) return -1;
     if (opt.fuse) ffgpu_layout_concat(ll, L, nl);
@@ -269,4 +325,11 @@ int ffgpu_net_layout(const LAYER *ll, int L, const PlanOptions &opt, BlockOk &&b
     if (opt.fuse && opt.branch) ffgpu_layout_side_lane(ll, L, nl);
     ffgpu_layout_arena(L, opt, nl);
     return 0;
+}
+
+// (without merged runs)
+template <class BlockOk, class PairOk>
+int ffgpu_net_layout(const LAYER *ll, int L, const PlanOptions &opt, BlockOk &&block_ok, PairOk &&pair_ok, NetLayout &nl)
+{
+    return ffgpu_net_layout(ll, L, opt, block_ok, pair_ok, [](const std::vector<int> &) { return false; }, nl);
 }

@@ -1,10 +1,12 @@
 // plan_driver.cc -- the planner's layout pass (ffgpu_plan.hpp) on the CPU under AddressSanitizer + UBSan (`make plan`; tests/test_plan_host.py):
-//     ffgpu_plan_san <cfg> <batch> <flags> <irb: none|all> <dwpw 0|1> <branch 0|1>
+//     ffgpu_plan_san <cfg> <batch> <flags> <irb: none|all> <dwpw 0|1> <branch 0|1> [stage 0|1]
 // net_load through the host parser and the stub device side (no GPU), then ffgpu_net_layout with callables that take every candidate block / pair
 // that passed the layout's own structural test (all) or none of them.  Prints one line per layer -- layer canon readable first last root offset size
 // ("-" where the layer has no tensor) --, then "side_lo side_hi arena_floats", then the counts of the rewrites, and checks the invariants I1 - I5
 //  itself.  Exit code 0 = the walk ended, whether net_load or the layout accepted or refused the net; 1 = an invariant is violated (named,
 // with the layers); a sanitizer report aborts with its own exit code.
+// With stage = 1 the layout may merge runs of small-plane blocks (PlanOptions::stage; the callable takes every run or none, like the others): one more
+// line per merged run behind the counts, "stage <first layer> <last layer> <blocks>", and invariant I6 on them.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -69,6 +71,13 @@ static void check(const LAYER *ll, int L, const PlanOptions &opt, const NetLayou
         if (T[t].parent < 0 && T[t].off % 64) VIOLATION("I4: tensor %d starts at %ld, no multiple of 64 floats", t, T[t].off);
     }
     for (int i = 0; i < L; i++) if (nl.readable[i] && nl.canon[i] < 0) VIOLATION("I4: layer %d is readable without a tensor", i);
+    // I6: a merged run is one launch at its last block: the blocks before it leave no tensor, and the run's input lives until that launch
+    for (int i = 0; i < L; i++) {
+        if (nl.stage_inner[i] && (nl.canon[i] != -3 || nl.irb_tail[i] < 0 || nl.fused_into[i] < 0 || T[nl.fused_into[i]].used)) VIOLATION("I6: layer %d ends a block inside a merged run and still has a tensor", i);
+        if (nl.stage_first[i] < 0) continue;
+        const int in = nl.src(nl.stage_first[i] - 1);
+        if (in < 0 || nl.canon[i] < 0 || T[in].last < i || !disjoint(nl, root_of(T, in), root_of(T, nl.canon[i]))) VIOLATION("I6: the run that ends at layer %d has no input of its own at its launch", i);
+    }
     // I5: the side lane's tensors are nobody's to reuse
     if (nl.side_lo >= 0) {
         std::vector<char> kept(L, 0);
@@ -82,20 +91,21 @@ static void check(const LAYER *ll, int L, const PlanOptions &opt, const NetLayou
 
 int main(int argc, char **argv)
 {
-    if (argc != 7) { fprintf(stderr, "usage: %s cfg batch flags none|all dwpw branch\n", argv[0]); return 2; }
+    if (argc != 7 && argc != 8) { fprintf(stderr, "usage: %s cfg batch flags none|all dwpw branch [stage]\n", argv[0]); return 2; }
     const int flags = atoi(argv[3]);
     const bool take = !strcmp(argv[4], "all");
     PlanOptions opt;
     opt.batch = atoi(argv[2]);
     opt.keep_all = flags & FFGPU_KEEP_ALL; opt.fuse = !(flags & FFGPU_NO_FUSE);
     opt.dwpw = atoi(argv[5]) != 0; opt.branch = atoi(argv[6]) != 0;
+    opt.stage = argc == 8 && atoi(argv[7]) != 0;
     if (opt.batch < 1) { fprintf(stderr, "batch must be >= 1\n"); return 2; }
     NET *net = net_load(argv[1], NULL, 0, 0);
     if (!net) { printf("net_load: NULL (%s)\n", ffgpu_last_error()); return 0; }
     const LAYER *ll = net->layer_list;
     const int L = net->layer_num;
     NetLayout nl;
-    if (ffgpu_net_layout(ll, L, opt, [&](int) { return take; }, [&](int) { return take; }, nl)) {
+    if (ffgpu_net_layout(ll, L, opt, [&](int) { return take; }, [&](int) { return take; }, [&](const std::vector<int> &) { return take; }, nl)) {
         printf("layout: refused (%s)\n", ffgpu_last_error());
         net_free(net);
         return 0;
@@ -109,6 +119,12 @@ int main(int argc, char **argv)
     }
     printf("%d %d %zu\n", nl.side_lo, nl.side_hi, nl.arena_floats);
     printf("fused_into %d irb %d dwpw %d inplace %d\n", nfused, nirb, ndwpw, ninplace);
+    for (int i = 0; i < L; i++) {
+        if (nl.stage_first[i] < 0) continue;
+        int blocks = 0;
+        for (int t = nl.stage_first[i] + 2; t <= i; t++) blocks += nl.irb_tail[t] >= 0;
+        printf("stage %d %d %d\n", nl.stage_first[i], i, blocks);
+    }
     check(ll, L, opt, nl);
     net_free(net);
     return g_bad;

@@ -326,6 +326,13 @@ float ffgpu_irb_dev(const float *d_in, const float *d_w1, const float *d_wd, con
 int ffgpu_irb_plan_text(int batch, int iw, int ih, int ic, int ec, int oc, int stride, int act1, int actd, int act2, int res_act,
                         int flags, char *buf, int cap);
 
+/* What an executor of `batch` frames created with `flags` does with a run of `blocks` consecutive blocks 48 -> 224 -> 48 (stride 1, linear
+ * projection and shortcut) on an iw x ih plane, as one line of text in buf (at most cap bytes; returns snprintf's count): "stage ..." with the
+ * merged launch's parameter block, LDS bytes, grid and block where the run becomes one launch (FFGPU_CONCURRENT, at least 32 frames,
+ * FFGPU_IRB_STAGE not 0, neither FFGPU_KEEP_ALL nor FFGPU_NO_FUSE, a plane the stage kernel holds), else "blocks ..." -- one launch per
+ * block -- or "unsupported".  Pure host code (no device needed): for tests and logs. */
+int ffgpu_irb_stage_plan_text(int batch, int iw, int ih, int blocks, int act1, int actd, int flags, char *buf, int cap);
+
 /* The key of every instantiation the fused-block families have -- the first word of ffgpu_irb_plan_text's line -- one per line in buf
  * (at most cap bytes; returns snprintf's count): the thin ones, then the wave ones, then the workgroup ones for both wave counts, read
  * from the tables the planner dispatches through.  Pure host code: for tests that must reach every one of them. */
