@@ -87,12 +87,20 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
         ra[0] = reinterpret_cast<const u4 *>(wimg + (size_t)c * ACH)[tid];
         ra[1] = reinterpret_cast<const u4 *>(wimg + (size_t)c * ACH)[tid + 256];
 #pragma unroll
-        for (int j = 0; j < 4; j++)        // channels beyond ic: the last valid row (their weights are zero in the image)
+        for (int j = 0; j < 4; j++)        // channels beyond ic: the last valid row, zeroed in lstore
             rb[j] = *reinterpret_cast<const v4 *>(bsrc + (long)min(PWB_KC * c + 4 * kg + j, p.ic - 1) * p.P);
     };
-    auto lstore = [&](int buf) {
+    // c: the chunk in the registers.  Channels beyond ic (the last chunk of a ragged ic) count as ZERO: their weights are zero in the image, but a re-read
+    // row would give 0 x Inf = NaN where the reference has no term (tests/conv_kernels/test_gpu_kernels.py::test_non_finite_inputs[pw_bf16-*])
+    const bool kragged = (p.ic & (PWB_KC - 1)) != 0;                  // uniform
+    auto lstore = [&](int buf, int c) {
         reinterpret_cast<u4 *>(sA[buf])[tid] = ra[0];
         reinterpret_cast<u4 *>(sA[buf])[tid + 256] = ra[1];
+        if (kragged && c == p.nchunks - 1) {
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (PWB_KC * c + 4 * kg + j >= p.ic) rb[j] = (v4){ 0.f, 0.f, 0.f, 0.f };
+        }
 #pragma unroll
         for (int i = 0; i < 4; i++) {                                 // pixel 4 pxg + i: k = 4 kg .. 4 kg + 3 -> two dwords
             const v2bf_pb lo = { (__bf16)rb[0][i], (__bf16)rb[1][i] }, hi = { (__bf16)rb[2][i], (__bf16)rb[3][i] };
@@ -109,7 +117,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
             for (int e = 0; e < 16; e++) acc[r][j][e] = 0.f;
 
     gload(0);
-    lstore(0);
+    lstore(0, 0);
     __syncthreads();
     for (int c = 0; c < p.nchunks; c++) {
         const int buf = c & 1;
@@ -129,7 +137,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
                 for (int j = 0; j < 2; j++)
                     acc[r][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[r], fb[j], acc[r][j], 0, 0, 0);
         }
-        if (c + 1 < p.nchunks) lstore(buf ^ 1);
+        if (c + 1 < p.nchunks) lstore(buf ^ 1, c + 1);
         __syncthreads();
     }
 

@@ -69,6 +69,11 @@ __global__ void k_pw_gemm32_pack(PwG32PackP p)
     }
 }
 
+// what a padded row of the last, ragged input chunk is loaded from (every lane the same 16 bytes): channels beyond ic count as ZERO.  Their weights are zero
+// in the image, but a re-read row of the input would give 0 x Inf = NaN where the reference has no term at all
+// (tests/conv_kernels/test_gpu_kernels.py::test_non_finite_inputs[pw_gemm-*])
+__device__ __attribute__((aligned(16))) const float pwg_zero_row[4] = { 0.f, 0.f, 0.f, 0.f };
+
 __device__ __noinline__ float pwg_sigmoid(float t) { return 1.0f / (1.0f + (float)exp((double)-t)); }
 
 // one tile of 128 channels x 32 PXB pixels: waves 4 (channels) x 1, a wave owns ONE 32-channel row block and PXB pixel blocks
@@ -123,11 +128,11 @@ __device__ __forceinline__ void pwg_tile(const PwG32P &p, float *smem, int mt, l
         for (int h = 0; h < 2; h++)
             __builtin_amdgcn_global_load_lds((glb_t)(aptr + (wid * 2 + h) * 256 + lane * 4), (lds_t)(&sA[buf][(wid * 2 + h) * 256]), 16, 0, 0);
         aptr += ACH;
-        const bool rag = kragged && c == p.nchunks - 1;               // channels beyond ic: the last valid row -- their weights are zero
+        const bool rag = kragged && c == p.nchunks - 1;               // channels beyond ic: the zero row
         if (bload) {
 #pragma unroll
             for (int j = 0; j < BP; j++) {
-                const float *src = rag ? gb[j] - (long)max(PWG_KC * c + gbk[j] - (p.ic - 1), 0) * p.P : gb[j];
+                const float *src = rag && PWG_KC * c + gbk[j] >= p.ic ? pwg_zero_row : gb[j];
                 __builtin_amdgcn_global_load_lds((glb_t)src, (lds_t)(&sB[buf][(wid * BP + j) * 256]), 16, 0, 0);
                 gb[j] += bstep;
             }

@@ -109,8 +109,10 @@ __global__ void __launch_bounds__(NW * 64) k_pw_mfma(PwP p)
         // of the MFMAs (register ring, statically indexed).  Loads are UNCONDITIONAL -- a load under a lane
         // predicate makes hipcc wait for it on the spot (s_waitcnt vmcnt(0) inside the branch), which serialises
         // the whole ring: out-of-range pixels are redirected to the strip's first quad (their columns are never
-        // stored), padded channels to channel ic-1 (their weights are zero) and past-the-end prefetches re-read
-        // the last k-step.
+        // stored), padded channels to channel ic-1 and past-the-end prefetches re-read the last k-step.  A padded
+        // channel's weights are zero, but 0 x Inf is NaN where the reference has no term at all: what a padded
+        // k-slot re-read counts as ZERO: a select on the B operand, true only for the padded lanes of the last
+        // k-step (tests/conv_kernels/test_gpu_kernels.py::test_non_finite_inputs[pw_mfma-*]).
 #ifndef PW_MFMA_PF
 #define PW_MFMA_PF 4
 #endif
@@ -127,8 +129,10 @@ __global__ void __launch_bounds__(NW * 64) k_pw_mfma(PwP p)
             const int ks = kfirst + min(i, nmine - 1) * KSP;
             return *reinterpret_cast<const v4f_pw *>(sbase + (long)ks * 4 * p.P + (ks == ksteps - 1 ? vo_last : vo_norm));
         };
-        auto mma = [&](int i, const v4f_pw &bc) {
+        const bool kpad = 4 * (ksteps - 1) + kq >= p.ic;   // this lane's channel of the LAST k-step is padding (ic % 4 != 0 only)
+        auto mma = [&](int i, v4f_pw bc) {
             const int ks = kfirst + i * KSP;
+            bc = (kpad & (ks == ksteps - 1)) ? z : bc;     // a select, no branch: loop and tail keep their shape (and with it the ring's waits)
 #pragma unroll
             for (int t = 0; t < OT; t++) {
                 const float a = wl[(ks * OT + t) * 64 + lane];

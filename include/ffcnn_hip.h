@@ -42,7 +42,16 @@ extern "C" {
 
 /* Activations on non-finite values are the reference's (utils.h:15-23) in EVERY kernel, whichever one a layer or block is planned onto:
  * relu(x) is x > 0 ? x : 0, so relu(NaN) = 0 and relu(-Inf) = 0 (relu(+Inf) = +Inf); leaky(NaN) = NaN, leaky(-Inf) = -Inf; linear hands
- * every value on.  A NaN or Inf that an activation does not remove propagates as in conv-v0.c:7-31 (w * Inf = +-Inf, 0 * Inf = NaN). */
+ * every value on; sigmoid(+Inf) = 1, sigmoid(-Inf) = 0, sigmoid(NaN) = NaN.  A NaN or Inf that an activation does not remove propagates as
+ * in conv-v0.c:7-31 (w * Inf = +-Inf, 0 * Inf = NaN).
+ *
+ * Non-finite INPUTS: this holds for every convolution kernel -- the plain fp32 ones (conv_generic, dw3_stream, dw_lds / dw_pair, pw_mfma,
+ * pw_gemm, conv_dense8 / conv_first, conv_igemm, conv_thin, the fused dwpw pair), the opt-in pw_bf16 and the split-bf16 ones alike, with or
+ * without a fused residual.  An output is non-finite exactly when its window (the taps INSIDE the plane, of its own group's channels) holds a
+ * non-finite input: +-Inf with the sign of w * Inf where one Inf meets non-zero weights, NaN where it meets a zero weight, an Inf of the
+ * opposite sign or a NaN.  Nothing else is touched: what a kernel reads only to fill a tile -- a padded k-slot that re-reads the last input
+ * channel, a tap outside the plane loaded from a clamped address, a pixel beyond the last one -- counts as zero before it is multiplied, never
+ * as 0 * x (tests/conv_kernels). */
 
 /* Per-frame detection record as it lies in device (and gathered host) memory.
  * This is the unit the multi-GPU gather moves: fixed size, 16 + 128*24 bytes. */

@@ -80,11 +80,24 @@ class Cfg:
     def dropout(self):
         return self._add("dropout", "[dropout]\nprobability=.5\n", self.out_shape(self.n - 1), self.tip())
 
-    def conv(self, filters, act="linear", src=None):
+    def conv(self, filters, act="linear", src=None, size=1, groups=1):
+        """1x1 by default; size > 1: stride 1 with "same" padding (pad=1 in a cfg: size / 2), so the plane keeps its shape"""
         self._goto(src)
         c, h, w = self.out_shape(self.n - 1)
-        i = self._add("conv", "[convolutional]\nfilters=%d\nsize=1\nstride=1\npad=0\nactivation=%s\n" % (filters, act), (filters, h, w))
+        assert size % 2 == 1 and c % groups == 0 and filters % groups == 0
+        i = self._add("conv", "[convolutional]\nfilters=%d\nsize=%d\nstride=1\npad=%d\n%sactivation=%s\n" % (
+            filters, size, 1 if size > 1 else 0, "groups=%d\n" % groups if groups > 1 else "", act), (filters, h, w))
         self._step(i)
+        return i
+
+    def absorbed_shortcut(self, frm, act="linear"):
+        """out = act(the conv right in front + layer `frm`), the form a fused plan absorbs into that conv's epilogue (ffgpu_plan.hpp: the conv is read by
+        nobody else and `frm` is a tensor of its own, not the net input): no launch of its own there, one k_add_act launch in an unfused plan.  Not an op
+        of verify(): tests/conv_kernels checks it against the float64 restatement of the conv."""
+        assert self.kind[self.n - 1] == "conv" and frm >= 0 and self.real[frm] >= 0
+        assert self.out_shape(self.n - 1) == self.out_shape(self.real[frm])
+        i = self._add("shortcut", "[shortcut]\nfrom=%d\nactivation=%s\n" % (frm - self.n, act), self.out_shape(self.n - 1))
+        self._step(i, fused=False)
         return i
 
     def pool(self, kind, size, stride, src=None, _merge=None):
