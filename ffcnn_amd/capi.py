@@ -138,6 +138,20 @@ class ZoneSlot(C.Structure):         # ffgpu_zone_slot (64 bytes): one slot of a
     _fields_ = [("id", C.c_int), ("px", C.c_float), ("py", C.c_float), ("inside", C.c_int), ("last", C.c_int), ("reserved", C.c_int * 3), ("since", C.c_int * 8)]
 
 
+class TextItem(C.Structure):         # ffgpu_text_item (64 bytes): one line of text of a target
+    _fields_ = [("x", C.c_int), ("y", C.c_int), ("fg", C.c_ubyte * 4), ("bg", C.c_ubyte * 4), ("scale", C.c_ubyte), ("flags", C.c_ubyte), ("len", C.c_ubyte),
+                ("reserved", C.c_ubyte), ("text", C.c_ubyte * 44)]
+
+
+class CaptionSpec(C.Structure):      # ffgpu_caption_spec (48 bytes): which boxes are captioned, with which parts, in which colours
+    _fields_ = [("min_score", C.c_float), ("flags", C.c_int), ("identity", C.c_int), ("scale", C.c_int), ("fg", C.c_ubyte * 4), ("color", C.c_ubyte * 4),
+                ("palette", C.c_void_p), ("npalette", C.c_int), ("nnames", C.c_int), ("d_names", C.c_void_p)]
+
+
+TEXT_MAX, TEXT_ITEMS, TEXT_OPAQUE = 44, 256, 1                                         # FFGPU_TEXT_MAX, _ITEMS, FFGPU_TEXT_OPAQUE (ffgpu_text_item.flags)
+CAPTION_DETS = 128                                                                     # FFGPU_CAPTION_DETS
+CAPTION_NAME, CAPTION_SCORE, CAPTION_ID, CAPTION_OPAQUE = 1, 2, 4, 8                   # FFGPU_CAPTION_* (ffgpu_caption_spec.flags)
+CAPTION_ENTRIES, CAPTION_MERGED = 0, 1                                                 # FFGPU_CAPTION_* (ffgpu_exec_caption_bgr / _nv12: which)
 SCENE_ZONES, SCENE_LINES, ZONE_VERTS, ZONES_DETS, ZONES_ROW = 8, 8, 8, 128, 64          # FFGPU_SCENE_ZONES, _LINES, FFGPU_ZONE_VERTS, FFGPU_ZONES_DETS, _ROW
 ZONES_NONE, ZONES_TYPE, ZONES_IDS = 0, 1, 2                                            # FFGPU_ZONES_* (ffgpu_zones_spec.identity)
 ZONES_GATE_INVERT = 1                                                                  # FFGPU_ZONES_GATE_INVERT (ffgpu_zones_spec.flags)
@@ -162,6 +176,7 @@ assert C.sizeof(DrawStyle) == 24 and C.sizeof(CropSpec) == 72 and C.sizeof(Crop)
 assert C.sizeof(TrackSpec) == 32 and C.sizeof(Track) == 48
 assert C.sizeof(FeatureSpec) == 16 and C.sizeof(Label) == 8 and C.sizeof(RelabelSpec) == 16
 assert C.sizeof(Gallery) == 40 and C.sizeof(RedactSpec) == 40
+assert C.sizeof(TextItem) == 64 and C.sizeof(CaptionSpec) == 48
 assert C.sizeof(Zone) == 96 and C.sizeof(Line) == 32 and C.sizeof(Scene) == 1040 and C.sizeof(ZonesSpec) == 32 and C.sizeof(ZoneSlot) == 64
 
 BOX_DTYPE = np.dtype([("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
@@ -173,6 +188,8 @@ TRACK_DTYPE = np.dtype([("id", "<i4"), ("type", "<i4"), ("score", "<f4"), ("x1",
                         ("hits", "<i4"), ("missed", "<i4"), ("born", "<i4"), ("det", "<i4"), ("reserved", "<i4")])
 ZONE_SLOT_DTYPE = np.dtype([("id", "<i4"), ("px", "<f4"), ("py", "<f4"), ("inside", "<i4"), ("last", "<i4"), ("reserved", "<i4", (3,)), ("since", "<i4", (8,))])
 LABEL_DTYPE = np.dtype([("index", "<i4"), ("value", "<f4")])
+TEXT_ITEM_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("fg", "u1", (4,)), ("bg", "u1", (4,)), ("scale", "u1"), ("flags", "u1"), ("len", "u1"), ("reserved", "u1"),
+                            ("text", "u1", (44,))])
 
 # every symbol include/*.h declares; tests check the built library exports all of them
 EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_profile", "groupconv",
@@ -196,7 +213,9 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_exec_relabel",
            "ffgpu_match_workspace_bytes", "ffgpu_match_dev", "ffgpu_gallery_enroll_dev",
            "ffgpu_redact_boxes_bgr_dev", "ffgpu_redact_boxes_nv12_dev", "ffgpu_exec_redact_bgr", "ffgpu_exec_redact_nv12",
-           "ffgpu_zones_state_bytes", "ffgpu_scene_check", "ffgpu_zones_reset_dev", "ffgpu_zones_boxes_dev", "ffgpu_exec_zones"]
+           "ffgpu_zones_state_bytes", "ffgpu_scene_check", "ffgpu_zones_reset_dev", "ffgpu_zones_boxes_dev", "ffgpu_exec_zones",
+           "ffgpu_font_builtin", "ffgpu_draw_text_bgr_dev", "ffgpu_draw_text_nv12_dev", "ffgpu_caption_boxes_dev", "ffgpu_exec_caption_bgr", "ffgpu_exec_caption_nv12",
+           "ffgpu_caption_scene_dev"]
 # include/ffcnn_hip_diag.h (libffcnn_hip_diag.so: lab equipment, its own library)
 DIAG_EXPORTS = ["ffgpu_membench", "ffgpu_pipe_probe", "ffgpu_pipe_probe2", "ffgpu_pipe_probe3", "ffgpu_mfma_floor", "ffgpu_diag_x3_term", "ffgpu_diag_xl_op", "ffgpu_clock_probe"]
 
@@ -346,6 +365,14 @@ def lib():
     L.ffgpu_zones_reset_dev.argtypes = [vp, i, i, i, vp]
     L.ffgpu_zones_boxes_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(i), i, C.POINTER(ZonesSpec), vp, vp, i, vp, vp, vp, vp, vp]
     L.ffgpu_exec_zones.argtypes = [vp, i, C.POINTER(i), i, C.POINTER(ZonesSpec), vp, vp, i, vp, vp, vp, vp, vp]
+    L.ffgpu_font_builtin.restype = None
+    L.ffgpu_font_builtin.argtypes = [vp]
+    L.ffgpu_draw_text_bgr_dev.argtypes = [vp, i, vp, C.POINTER(BgrFrame), i, vp]
+    L.ffgpu_draw_text_nv12_dev.argtypes = [vp, i, vp, C.POINTER(Nv12Frame), i, vp]
+    L.ffgpu_caption_boxes_dev.argtypes = [vp, vp, i, C.POINTER(i), i, C.POINTER(CaptionSpec), vp, vp, i, vp]
+    L.ffgpu_exec_caption_bgr.argtypes = [vp, i, C.POINTER(BgrFrame), i, C.POINTER(CaptionSpec), vp, vp, i, vp, vp]
+    L.ffgpu_exec_caption_nv12.argtypes = [vp, i, C.POINTER(Nv12Frame), i, C.POINTER(CaptionSpec), vp, vp, i, vp, vp]
+    L.ffgpu_caption_scene_dev.argtypes = [vp, vp, i, i, vp, i, C.POINTER(i), i, C.POINTER(CaptionSpec), vp, i, vp]
     L.ffgpu_feature_dim.argtypes = [i, i, i, i]
     L.ffgpu_exec_feature_dim.argtypes = [vp, C.POINTER(FeatureSpec)]
     L.ffgpu_features_dev.argtypes = [vp, i, i, i, i, i, i, vp, C.c_long, vp]
@@ -716,6 +743,19 @@ class Executor:
         _check(lib().ffgpu_exec_zones(self.h, which, arr, len(streams), spec, d_scenes, d_state, nstreams, d_ids, d_events, d_out_records, d_out_lists, stream),
                "ffgpu_exec_zones")
 
+    def caption_bgr(self, frames, spec, d_items, items_stride, d_ids=None, d_font=None, which=0, stream=None):
+        """enqueue the captions of the last forward's boxes (which = CAPTION_ENTRIES: entry n into frames[n]) or of the last merge's (CAPTION_MERGED:
+        picture g into frames[g]) behind it (ffgpu_exec_caption_bgr): frames as draw_bgr takes them, spec from caption_spec, d_items the caller's
+        device buffer of len(frames) x items_stride x 64 bytes (it holds the composed items afterwards), d_ids the rows Executor.track wrote for the
+        same `which` (with identity ZONES_IDS), d_font 2 048 device bytes or None: the built-in font.  Redact, then draw, then caption."""
+        _check(lib().ffgpu_exec_caption_bgr(self.h, which, bgr_frame_table(frames), len(frames), spec, d_ids, d_items, items_stride, d_font, stream),
+               "ffgpu_exec_caption_bgr")
+
+    def caption_nv12(self, frames, spec, d_items, items_stride, d_ids=None, d_font=None, which=0, stream=None):
+        """the same into NV12 frames (ffgpu_exec_caption_nv12): the spec's colours are Y U V bytes"""
+        _check(lib().ffgpu_exec_caption_nv12(self.h, which, nv12_frame_table(frames), len(frames), spec, d_ids, d_items, items_stride, d_font, stream),
+               "ffgpu_exec_caption_nv12")
+
     def feature_dim(self, spec):
         """D of the rows Executor.features writes for `spec` (a FeatureSpec from feature_spec); pure host code (ffgpu_exec_feature_dim)"""
         return _check(lib().ffgpu_exec_feature_dim(self.h, spec), "ffgpu_exec_feature_dim")
@@ -1053,6 +1093,87 @@ def zones_boxes_dev(d_records, d_lists, list_stride, streams, spec, d_scenes, d_
     arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
     _check(lib().ffgpu_zones_boxes_dev(d_records, d_lists, list_stride, first, arr, len(streams), spec, d_scenes, d_state, nstreams, d_ids, d_events,
                                        d_out_records, d_out_lists, stream), "ffgpu_zones_boxes_dev")
+
+
+def font_builtin():
+    """the built-in font's 2 048 bytes as a (256, 8) uint8 array: row r of glyph g, bit 7 - c = column c (ffgpu_font_builtin; pure host code)"""
+    out = np.zeros((256, 8), np.uint8)
+    lib().ffgpu_font_builtin(out.ctypes.data)
+    return out
+
+
+def text_items(items, stride=None):
+    """TEXT_ITEM_DTYPE rows for one target from (x, y, text[, fg, bg, scale, opaque]) tuples, text a str (its characters' codes) or bytes; padded with
+    unused slots (len 0) to `stride` rows"""
+    out = np.zeros(len(items) if stride is None else stride, TEXT_ITEM_DTYPE)
+    if len(items) > len(out):
+        raise ValueError("%d items for a stride of %d" % (len(items), len(out)))
+    for k, it in enumerate(items):
+        x, y, text = it[0], it[1], it[2]
+        fg, bg, scale, opaque = (tuple(it[3:]) + ((255, 255, 255), (0, 0, 0), 1, False)[len(it) - 3:])[:4]
+        raw = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+        if len(raw) > TEXT_MAX:
+            raise ValueError("a text item holds %d characters, not %d" % (TEXT_MAX, len(raw)))
+        out[k]["x"], out[k]["y"], out[k]["scale"], out[k]["flags"], out[k]["len"] = x, y, scale, TEXT_OPAQUE if opaque else 0, len(raw)
+        out[k]["fg"][:3], out[k]["bg"][:3] = fg[:3], bg[:3]
+        out[k]["text"][:len(raw)] = np.frombuffer(raw, np.uint8)
+    return out
+
+
+def caption_spec(name=True, score=True, ident=False, opaque=True, min_score=0.0, identity=ZONES_NONE, scale=1, fg=(255, 255, 255), color=(0, 0, 0), palette=None,
+                 d_names=None, nnames=0):
+    """a CaptionSpec: which parts a caption has, from which score on, where the id comes from (ZONES_NONE | _TYPE | _IDS), the ink `fg` and the paper:
+    one colour or a palette as draw_style takes it (B G R bytes for BGR targets, Y U V for NV12 ones); d_names: nnames rows of 16 device bytes.  The
+    structure keeps its palette bytes alive."""
+    sp = CaptionSpec()
+    sp.min_score, sp.identity, sp.scale = min_score, identity, scale
+    sp.flags = (CAPTION_NAME if name else 0) | (CAPTION_SCORE if score else 0) | (CAPTION_ID if ident else 0) | (CAPTION_OPAQUE if opaque else 0)
+    sp.fg[:] = (int(fg[0]), int(fg[1]), int(fg[2]), 0)
+    sp.color[:] = (int(color[0]), int(color[1]), int(color[2]), 0)
+    if palette is not None:
+        pal = np.zeros((len(palette), 4), np.uint8)
+        if len(palette):
+            pal[:, :3] = np.asarray(palette, np.uint8).reshape(len(palette), -1)[:, :3]
+        sp._pal = pal                                           # (owned by the structure: the C side reads it during the call)
+        sp.palette = pal.ctypes.data
+        sp.npalette = len(palette)
+    sp.d_names, sp.nnames = d_names, nnames
+    return sp
+
+
+def names_bytes(names):
+    """the rows of 16 bytes ffgpu_caption_spec.d_names points to, for the caller to upload: a NUL ends a name shorter than 16 bytes"""
+    out = np.zeros((len(names), 16), np.uint8)
+    for k, nm in enumerate(names):
+        raw = (nm.encode("latin-1") if isinstance(nm, str) else bytes(nm))[:16]
+        out[k, :len(raw)] = np.frombuffer(raw, np.uint8)
+    return out
+
+
+def draw_text_bgr_dev(d_items, items_stride, frames, d_font=None, stream=None):
+    """ffgpu_draw_text_bgr_dev: items t * items_stride ... of d_items rasterised into frames[t] (what bgr_frame_desc accepts, or None: skipped);
+    d_font 2 048 device bytes, or None: the built-in font"""
+    _check(lib().ffgpu_draw_text_bgr_dev(d_items, items_stride, d_font, bgr_frame_table(frames), len(frames), stream), "ffgpu_draw_text_bgr_dev")
+
+
+def draw_text_nv12_dev(d_items, items_stride, frames, d_font=None, stream=None):
+    """ffgpu_draw_text_nv12_dev: the same into NV12 frames (what nv12_frame_desc accepts, or None: skipped); colours are Y U V bytes"""
+    _check(lib().ffgpu_draw_text_nv12_dev(d_items, items_stride, d_font, nv12_frame_table(frames), len(frames), stream), "ffgpu_draw_text_nv12_dev")
+
+
+def caption_boxes_dev(d_records, d_lists, list_stride, ntargets, spec, d_items, items_stride, d_ids=None, list_first=None, stream=None):
+    """ffgpu_caption_boxes_dev on device records / lists: the captions of record t composed into items t * items_stride ... of d_items; spec from
+    caption_spec, d_ids the rows track_boxes_dev wrote (with identity ZONES_IDS); the other arguments as draw_boxes_bgr_dev takes them"""
+    first = None if list_first is None else (C.c_int * max(1, len(list_first)))(*[int(v) for v in list_first])
+    _check(lib().ffgpu_caption_boxes_dev(d_records, d_lists, list_stride, first, ntargets, spec, d_ids, d_items, items_stride, stream), "ffgpu_caption_boxes_dev")
+
+
+def caption_scene_dev(d_scenes, d_state, nstreams, capacity, d_events, events_stride, streams, spec, d_items, items_stride, stream=None):
+    """ffgpu_caption_scene_dev: the zones' occupancies (event row t) and the lines' totals (the state of stream streams[t]) as items t * items_stride ...
+    of d_items (items_stride 16..256); spec from caption_spec (its colours and scale); draw them with draw_text_*_dev"""
+    arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+    _check(lib().ffgpu_caption_scene_dev(d_scenes, d_state, nstreams, capacity, d_events, events_stride, arr, len(streams), spec, d_items, items_stride, stream),
+           "ffgpu_caption_scene_dev")
 
 
 def feature_spec(layer=-1, pool=FFGPU.FEAT_MEAN, post=FFGPU.POST_NONE):

@@ -129,8 +129,8 @@ struct DetSource {
 };
 
 static_assert(FFGPU_DRAW_ENTRIES == 0 && FFGPU_CROP_ENTRIES == 0 && FFGPU_TRACK_ENTRIES == 0 && FFGPU_RELABEL_ENTRIES == 0 && FFGPU_REDACT_ENTRIES == 0 &&
-              FFGPU_ZONES_ENTRIES == 0 && FFGPU_DRAW_MERGED == 1 && FFGPU_CROP_MERGED == 1 && FFGPU_TRACK_MERGED == 1 && FFGPU_RELABEL_MERGED == 1 &&
-              FFGPU_REDACT_MERGED == 1 && FFGPU_ZONES_MERGED == 1, "ffgpu_source_exec: one check of `which` serves the six families");
+              FFGPU_ZONES_ENTRIES == 0 && FFGPU_CAPTION_ENTRIES == 0 && FFGPU_CAPTION_MERGED == 1 && FFGPU_DRAW_MERGED == 1 && FFGPU_CROP_MERGED == 1 && FFGPU_TRACK_MERGED == 1 && FFGPU_RELABEL_MERGED == 1 &&
+              FFGPU_REDACT_MERGED == 1 && FFGPU_ZONES_MERGED == 1, "ffgpu_source_exec: one check of `which` serves the seven families");
 
 // the list stride of an operator form: the caller's with lists, FFGPU_MAX_DET without; -1 with a message outside 1 .. 2^24
 inline int ffgpu_list_stride(const char *what, const void *d_lists, int list_stride)

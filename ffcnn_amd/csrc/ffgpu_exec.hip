@@ -1453,6 +1453,41 @@ extern "C" int ffgpu_exec_zones(ffgpu_exec *ex, int which, const int *streams, i
     return ffgpu_launch_zones(src, streams, ntargets, *spec, d_scenes, d_state, d_ids, d_events, d_out_records, d_out_lists, s);
 }
 
+// -------------------------------------------------------------------------- captions (include/ffcnn_hip.h; kernels: ffgpu_text.inc)
+// A post-pass like the draw, on the stream of the forward or merge it follows, in two launches: the items composed from the records and full lists (per
+// entry, or the merged ones) into the caller's d_items, then rasterised into the caller's frames.  Nothing of the executor's is written.
+template <class Frame>
+static int exec_caption(ffgpu_exec *ex, const char *what, int which, const Frame *targets, int ntargets, const ffgpu_caption_spec *spec, const void *d_ids,
+                        void *d_items, int items_stride, const void *d_font, void *stream)
+{
+    if (!exec_ok(ex, what)) return -1;
+    if (!targets) { ffgpu_set_error("%s: NULL targets", what); return -1; }
+    CaptionPlan pl;
+    if (ffgpu_caption_boxes_args_check(what, spec, d_ids, d_items, items_stride, pl)) return -1;
+    DetSource src;
+    hipStream_t s;
+    if (exec_source(ex, what, "CAPTION", "caption", which, ntargets, stream, src, &s)) return -1;
+    // with ids the stride is also their pitch, the tracker's S: a list too long is refused as the tracker refuses it; without, clamped as the draw
+    if (d_ids && src.longest > (1 << 24)) { ffgpu_set_error("%s: lists of up to %lld boxes are too long", what, src.longest); return -1; }
+    src.stride = (int)std::min(src.longest, (long long)0x7fffffff);
+    std::vector<DrawTarget> tab;
+    if (ffgpu_frame_table(what, FRAME_DRAW, targets, ntargets, tab)) return -1;
+    if (ffgpu_launch_caption_boxes(src, ntargets, pl, d_ids, d_items, items_stride, s)) return -1;
+    return ffgpu_launch_draw_text(std::is_same<Frame, ffgpu_nv12_frame>::value, d_items, items_stride, d_font, tab, s);
+}
+
+extern "C" int ffgpu_exec_caption_bgr(ffgpu_exec *ex, int which, const ffgpu_bgr_frame *targets, int ntargets, const ffgpu_caption_spec *spec,
+                                      const void *d_ids, void *d_items, int items_stride, const void *d_font, void *stream)
+{
+    return exec_caption(ex, "caption_bgr", which, targets, ntargets, spec, d_ids, d_items, items_stride, d_font, stream);
+}
+
+extern "C" int ffgpu_exec_caption_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_frame *targets, int ntargets, const ffgpu_caption_spec *spec,
+                                       const void *d_ids, void *d_items, int items_stride, const void *d_font, void *stream)
+{
+    return exec_caption(ex, "caption_nv12", which, targets, ntargets, spec, d_ids, d_items, items_stride, d_font, stream);
+}
+
 // -------------------------------------------------------------------------- the crops classified (include/ffcnn_hip.h; kernels: ffgpu_feature.inc)
 // The tensor a feature spec names on this plan: its id and the frame's c x h x w, or -1 with a message.  layer == -1 is the last layer's, aliases
 // resolved by canon[] (a trailing dropout or one-source route holds its source's tensor id).  Nothing takes that tensor's floats after the forward: the

@@ -1020,6 +1020,129 @@ int ffgpu_zones_boxes_dev(const void *d_records, const void *d_lists, int list_s
 int ffgpu_exec_zones(ffgpu_exec *ex, int which, const int *streams, int ntargets, const ffgpu_zones_spec *spec, const void *d_scenes, void *d_state,
                      int nstreams, const void *d_ids, void *d_events, void *d_out_records, void *d_out_lists, void *stream);
 
+/* ---- captions: names, scores, ids and counters written into the frames on the device ----------------------------------------------------------
+ * After the forward a box has a class (or a relabelled class or identity), a score, a track id and zone flags, and the outline of the draw operators
+ * shows none of it.  What follows writes "person 93% #12" at the box where the frames and the records already lie: a TEXT PRIMITIVE that rasterises
+ * text items lying in device memory into u8 BGR and NV12 frames, a COMPOSER that writes such items from any record (plain, merged, tracked, relabelled,
+ * gated), and a composer for the zones' and lines' counters.  The reference program draws rectangles only: the contract is this text, to the bit
+ * (tests/captions/textref.py restates it in numpy).  Outlines of the zones' polygons and lines are not part of it.
+ *
+ * Font: 256 glyphs of 8 x 8 pixels, 2 048 bytes.  Byte g * 8 + r is row r of glyph g, row 0 at the top; bit 7 - c of that byte is column c, column 0
+ * at the left; a set bit is ink.  The operators take `d_font`, 2 048 bytes of DEVICE memory (any alignment); NULL selects the built-in font compiled
+ * into the library: codes 32..126 are ASCII, every other code is one "unknown" glyph, a hollow box.  Every ASCII glyph keeps column 7 and row 7 empty, so
+ * adjacent cells do not touch; space is empty and no other glyph is; the 95 ASCII glyphs are pairwise different.
+ *
+ * Text items: ffgpu_text_item, 64 bytes each, in device memory (4-byte aligned).  Target t draws items t * items_stride .. t * items_stride +
+ * items_stride - 1; items_stride lies in 1..256; unused slots have len == 0; there is no count to read.
+ * The pixel set of an item: with s = the clamped scale and n = the clamped len, the item's RECTANGLE is the set of pixels with 0 <= px - x < 8 s n
+ * and 0 <= py - y < 8 s, computed as if in 64-bit integers.  A pixel of the rectangle is INK when glyph text[(px - x) / (8 s)] has the bit for column
+ * ((px - x) / s) % 8, row (py - y) / s; otherwise it is PAPER.  The item WRITES its ink pixels (value fg) and, with FFGPU_TEXT_OPAQUE, its paper
+ * pixels too (value bg).  A pixel outside 0 <= px < w, 0 <= py < h of the target is dropped.
+ * A target's result is what drawing its items serially in slot order would leave: a later item overwrites an earlier one.  Only written pixels
+ * change; every other byte -- row padding, unwritten pixels, the memory in front of and behind the surface -- stays as it was.  The result does not
+ * depend on the order in which the device executes anything: the same bytes on every run.
+ * BGR targets: a written pixel becomes the three bytes 0, 1, 2 of fg or bg.  NV12 targets (`matrix` ignored, nothing converted): a written pixel sets
+ * Y[py][px] = byte 0; the chroma pair UV[py >> 1][px >> 1] takes its value from the LAST item in slot order that writes any of the sample's up to four
+ * luma pixels inside the target: that item's fg (U, V) = bytes 1, 2 if at least one of the luma pixels the item writes in this sample is ink,
+ * otherwise its bg (U, V).  Odd widths and heights are legal.
+ * The kernel is total over any item bytes: nothing is read outside d_items and the font, nothing is written outside the targets' w x h. */
+#define FFGPU_TEXT_MAX    44   /* characters of an item */
+#define FFGPU_TEXT_ITEMS  256  /* items per target at most (items_stride) */
+#define FFGPU_TEXT_OPAQUE 1    /* flags bit 0: the paper is drawn too */
+typedef struct {
+    int x, y;                  /* top-left pixel of the first cell, in target pixels; any value */
+    unsigned char fg[4];       /* ink:   B G R 0 (BGR targets) / Y U V 0 (NV12 targets) */
+    unsigned char bg[4];       /* paper: same byte order */
+    unsigned char scale;       /* 1..4: each font pixel is scale x scale target pixels; 0 reads as 1, above 4 as 4 */
+    unsigned char flags;       /* FFGPU_TEXT_OPAQUE; other bits ignored */
+    unsigned char len;         /* characters used; above FFGPU_TEXT_MAX reads as FFGPU_TEXT_MAX; 0: the item draws nothing */
+    unsigned char reserved;
+    unsigned char text[FFGPU_TEXT_MAX];  /* glyph codes */
+} ffgpu_text_item;             /* 64 bytes: x 0, y 4, fg 8, bg 12, scale 16, flags 17, len 18, text 20 */
+
+/* pure host code: the built-in font's 2 048 bytes */
+void ffgpu_font_builtin(unsigned char out[2048]);
+
+/* The rasteriser.  The descriptors, their checks, "a NULL pixel address skips the target" and the no-overlap rule are the draw operators', word for
+ * word; the tables travel as by-value kernel arguments, 64 targets per launch; enqueued on `stream` without synchronising.  targets is HOST memory
+ * and free again on return.  Rejected before anything is launched, with the target's index in the message where there is one: NULL items or targets,
+ * items that are not 4-byte aligned, ntargets < 1, items_stride outside 1..256, a descriptor the draw operators would reject. */
+int ffgpu_draw_text_bgr_dev (const void *d_items, int items_stride, const void *d_font,
+                             const ffgpu_bgr_frame  *targets, int ntargets, void *stream);
+int ffgpu_draw_text_nv12_dev(const void *d_items, int items_stride, const void *d_font,
+                             const ffgpu_nv12_frame *targets, int ntargets, void *stream);
+
+/* Box captions.  Records, lists, list_stride, the HOST array list_first and their clamps are the draw operators'; d_ids is what ffgpu_track_boxes_dev
+ * wrote (rows of 8 + S ints, S = list_stride, or FFGPU_MAX_DET when d_lists is NULL) and is required exactly when identity == FFGPU_ZONES_IDS.
+ * For target t the list is walked in list order; a box is CONSIDERED when score >= min_score (a NaN score never is), until
+ * min(FFGPU_CAPTION_DETS, items_stride) boxes are considered; further qualifying boxes get no caption.  The k-th considered box writes item k of the
+ * target; every other item of the target's items_stride slots is written as 64 zero bytes: every byte of d_items for the call's targets is written.
+ * The item: (a, b, c, d) are the draw contract's integer corners (toward zero, saturating, NaN -> 0).  x = a; y = b - 8 * scale when b >= 8 * scale,
+ * else y = b: the tag sits on the box, and where there is no room above, inside its top.  fg = the spec's; bg = palette entry type mod npalette (the
+ * non-negative remainder), or `color`: the colour the draw operator outlines that box with; byte 3 of both is written as 0.  scale = the spec's;
+ * flags = FFGPU_TEXT_OPAQUE iff FFGPU_CAPTION_OPAQUE is set; reserved and the text bytes behind len are 0.
+ * The text is the parts below that are present, in this order, joined by one space and cut to FFGPU_TEXT_MAX characters; no part: len = 0.
+ *   Name, with FFGPU_CAPTION_NAME and identity != FFGPU_ZONES_TYPE (with _TYPE the class is unknown, as in zones).  With 0 <= type < nnames: the bytes
+ *     of row `type` of d_names up to the first NUL, at most 16, verbatim as glyph codes; an empty row gives an empty part, which is dropped.
+ *     Otherwise: `type` in decimal, with - for negatives.
+ *   Score, with FFGPU_CAPTION_SCORE: p = (int)(score * 100.0f + 0.5f), in fp32, not contracted, converted as the corners are, then clamped to 0..999;
+ *     written in decimal, followed by %.
+ *   Id, with FFGPU_CAPTION_ID: v = the box's type under _TYPE; under _IDS entry 8 + k' of row t of d_ids, k' the box's index in its list; under _NONE
+ *     0.  v > 0: # and v in decimal.  v < 0: #, -v in decimal (taken in 64 bits) and ?: a track that has not reached min_hits.  v == 0: absent.
+ * One workgroup per target; spec (with its palette) and list_first are HOST memory and free again on return; the tables travel as kernel arguments,
+ * 128 targets per launch.  Rejected before anything is launched: the draw operators' reasons, NULL spec or items, items that are not 4-byte aligned,
+ * items_stride outside 1..256, a non-finite or out-of-range min_score, flags without a part or with unknown bits, identity outside 0..2, scale
+ * outside 1..4, npalette inconsistent with palette, nnames < 0 or inconsistent with d_names, d_ids given or missing against the identity rule. */
+#define FFGPU_CAPTION_DETS   128  /* captioned boxes per target at most */
+#define FFGPU_CAPTION_NAME   1
+#define FFGPU_CAPTION_SCORE  2
+#define FFGPU_CAPTION_ID     4
+#define FFGPU_CAPTION_OPAQUE 8
+typedef struct {
+    float min_score;               /* finite, in [0, 1] */
+    int   flags;                   /* at least one of NAME | SCORE | ID; unknown bits rejected */
+    int   identity;                /* FFGPU_ZONES_NONE | _TYPE | _IDS, with the zones contract's meaning */
+    int   scale;                   /* 1..4 */
+    unsigned char fg[4];           /* ink */
+    unsigned char color[4];        /* paper when palette is NULL */
+    const unsigned char *palette;  /* HOST, npalette x 4 bytes, or NULL: exactly ffgpu_draw_style's */
+    int   npalette;                /* 0 with a NULL palette, else 1..256 */
+    int   nnames;                  /* rows of d_names; 0 with NULL */
+    const void *d_names;           /* DEVICE, nnames rows of 16 bytes (a NUL ends a shorter name), or NULL */
+} ffgpu_caption_spec;              /* 48 bytes: min_score 0, flags 4, identity 8, scale 12, fg 16, color 20, palette 24, npalette 32, nnames 36, */
+                                   /* d_names 40 */
+int ffgpu_caption_boxes_dev(const void *d_records, const void *d_lists, int list_stride, const int *list_first, int ntargets,
+                            const ffgpu_caption_spec *spec, const void *d_ids, void *d_items, int items_stride, void *stream);
+
+#define FFGPU_CAPTION_ENTRIES 0   /* entry n's full post-NMS list captions targets[n]; ntargets == batch; S as FFGPU_TRACK_ENTRIES              */
+#define FFGPU_CAPTION_MERGED  1   /* picture g's merged list (last ffgpu_exec_merge_tiles) captions targets[g]; ntargets == its nimages         */
+/* On an executor: a compose plus a draw-text, two launches, enqueued on `stream` (NULL = the executor's own; it must be the stream of the forward or
+ * merge it follows) without synchronising.  d_items is the caller's scratch of ntargets x items_stride x 64 bytes and also the product: a caller may
+ * read it.  d_ids is what ffgpu_exec_track wrote for the same `which`.  The captured graph, the records, the full lists, the ring and the host mirror
+ * are untouched.  Redact, then draw, then caption: the tags lie on top.  Works on FFGPU_SPLIT2 executors.  Rejected like the operators, and: ntargets
+ * not as stated, a `which` that is neither, FFGPU_CAPTION_MERGED when no merge has run, the wrong stream.  A rejected call leaves the executor usable. */
+int ffgpu_exec_caption_bgr (ffgpu_exec *ex, int which, const ffgpu_bgr_frame  *targets, int ntargets, const ffgpu_caption_spec *spec,
+                            const void *d_ids, void *d_items, int items_stride, const void *d_font, void *stream);
+int ffgpu_exec_caption_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_frame *targets, int ntargets, const ffgpu_caption_spec *spec,
+                            const void *d_ids, void *d_items, int items_stride, const void *d_font, void *stream);
+
+/* Zone and line counters as text items, from the events and the state of ffgpu_zones_boxes_dev; the caller draws them with ffgpu_draw_text_*_dev (no
+ * executor form: scenes and state are the caller's).  items_stride lies in 16..256.  events_stride is the ints per event row, FFGPU_ZONES_ROW + 2 S of
+ * the zones call that wrote it.  Stream s = streams[t]; -1 gives the target all-zero items.
+ *   Item z (0..7) exists for z < nzones (clamped to 0..8 as the zones kernel clamps it) when the zone's nverts is in 3..8.  Its text is "Z<z> <occupancy>",
+ *     occupancy = int 16 + 4 z of event row t, read as unsigned decimal.  It sits at ((int)x[0], (int)y[0]) of the zone, by the draw contract's conversion.
+ *   Item 8 + l exists for l < nlines (clamped likewise).  Its text is "L<l> <total_fwd[l]>/<total_back[l]>", read from the 144-byte header of stream s of
+ *     d_state (the streams lie 144 + 64 x capacity bytes apart).  It sits at ((int)ax, (int)ay).  THE VALUES ARE THE STATE'S WHEN THE KERNEL RUNS: with
+ *     several records of one stream in one zones call, every target of that stream shows the final totals.
+ *   fg, scale and OPAQUE come from the spec; bg = palette entry z or 8 + l (mod npalette), or `color`.  Every other slot is zero.  The spec's min_score,
+ *   part flags, identity and names are ignored here.
+ * streams and spec are HOST memory and free again on return; 512 targets per launch.  Rejected before anything is launched: NULL scenes, state,
+ * events, streams, spec or items, scenes, state, events or items that are not 4-byte aligned, ntargets < 1, nstreams outside 1..65536, capacity
+ * outside 1..128, events_stride below FFGPU_ZONES_ROW, items_stride outside 16..256, a stream outside -1..nstreams-1, scale outside 1..4, npalette
+ * inconsistent with palette. */
+int ffgpu_caption_scene_dev(const void *d_scenes, const void *d_state, int nstreams, int capacity, const void *d_events, int events_stride,
+                            const int *streams, int ntargets, const ffgpu_caption_spec *spec, void *d_items, int items_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
