@@ -148,6 +148,18 @@ class CaptionSpec(C.Structure):      # ffgpu_caption_spec (48 bytes): which boxe
                 ("palette", C.c_void_p), ("npalette", C.c_int), ("nnames", C.c_int), ("d_names", C.c_void_p)]
 
 
+class SegItem(C.Structure):          # ffgpu_seg_item (32 bytes): one segment of a target
+    _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("x1", C.c_int), ("y1", C.c_int), ("color", C.c_ubyte * 4), ("thickness", C.c_ubyte), ("dash", C.c_ubyte),
+                ("flags", C.c_ubyte), ("reserved", C.c_ubyte), ("reserved2", C.c_int * 2)]
+
+
+class OutlineSpec(C.Structure):      # ffgpu_outline_spec (40 bytes): which parts of a scene are outlined, and how
+    _fields_ = [("flags", C.c_int), ("thickness", C.c_int), ("line_dash", C.c_int), ("marker", C.c_int), ("color", C.c_ubyte * 4), ("alarm", C.c_ubyte * 4),
+                ("palette", C.c_void_p), ("npalette", C.c_int), ("reserved", C.c_int)]
+
+
+SEG_ITEMS, SEG_LIMIT, OUTLINE_FIXED = 512, 1 << 20, 80                                 # FFGPU_SEG_ITEMS, _LIMIT, FFGPU_OUTLINE_FIXED
+OUTLINE_ZONES, OUTLINE_LINES, OUTLINE_TICKS, OUTLINE_MARKERS, OUTLINE_ALARM = 1, 2, 4, 8, 16   # FFGPU_OUTLINE_* (ffgpu_outline_spec.flags)
 TEXT_MAX, TEXT_ITEMS, TEXT_OPAQUE = 44, 256, 1                                         # FFGPU_TEXT_MAX, _ITEMS, FFGPU_TEXT_OPAQUE (ffgpu_text_item.flags)
 CAPTION_DETS = 128                                                                     # FFGPU_CAPTION_DETS
 CAPTION_NAME, CAPTION_SCORE, CAPTION_ID, CAPTION_OPAQUE = 1, 2, 4, 8                   # FFGPU_CAPTION_* (ffgpu_caption_spec.flags)
@@ -177,6 +189,7 @@ assert C.sizeof(TrackSpec) == 32 and C.sizeof(Track) == 48
 assert C.sizeof(FeatureSpec) == 16 and C.sizeof(Label) == 8 and C.sizeof(RelabelSpec) == 16
 assert C.sizeof(Gallery) == 40 and C.sizeof(RedactSpec) == 40
 assert C.sizeof(TextItem) == 64 and C.sizeof(CaptionSpec) == 48
+assert C.sizeof(SegItem) == 32 and C.sizeof(OutlineSpec) == 40
 assert C.sizeof(Zone) == 96 and C.sizeof(Line) == 32 and C.sizeof(Scene) == 1040 and C.sizeof(ZonesSpec) == 32 and C.sizeof(ZoneSlot) == 64
 
 BOX_DTYPE = np.dtype([("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
@@ -190,6 +203,8 @@ ZONE_SLOT_DTYPE = np.dtype([("id", "<i4"), ("px", "<f4"), ("py", "<f4"), ("insid
 LABEL_DTYPE = np.dtype([("index", "<i4"), ("value", "<f4")])
 TEXT_ITEM_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("fg", "u1", (4,)), ("bg", "u1", (4,)), ("scale", "u1"), ("flags", "u1"), ("len", "u1"), ("reserved", "u1"),
                             ("text", "u1", (44,))])
+SEG_ITEM_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("color", "u1", (4,)), ("thickness", "u1"), ("dash", "u1"), ("flags", "u1"),
+                           ("reserved", "u1"), ("reserved2", "<i4", (2,))])
 
 # every symbol include/*.h declares; tests check the built library exports all of them
 EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_profile", "groupconv",
@@ -215,7 +230,8 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_redact_boxes_bgr_dev", "ffgpu_redact_boxes_nv12_dev", "ffgpu_exec_redact_bgr", "ffgpu_exec_redact_nv12",
            "ffgpu_zones_state_bytes", "ffgpu_scene_check", "ffgpu_zones_reset_dev", "ffgpu_zones_boxes_dev", "ffgpu_exec_zones",
            "ffgpu_font_builtin", "ffgpu_draw_text_bgr_dev", "ffgpu_draw_text_nv12_dev", "ffgpu_caption_boxes_dev", "ffgpu_exec_caption_bgr", "ffgpu_exec_caption_nv12",
-           "ffgpu_caption_scene_dev"]
+           "ffgpu_caption_scene_dev",
+           "ffgpu_draw_segments_bgr_dev", "ffgpu_draw_segments_nv12_dev", "ffgpu_outline_spec_check", "ffgpu_outline_scene_dev"]
 # include/ffcnn_hip_diag.h (libffcnn_hip_diag.so: lab equipment, its own library)
 DIAG_EXPORTS = ["ffgpu_membench", "ffgpu_pipe_probe", "ffgpu_pipe_probe2", "ffgpu_pipe_probe3", "ffgpu_mfma_floor", "ffgpu_diag_x3_term", "ffgpu_diag_xl_op", "ffgpu_clock_probe"]
 
@@ -373,6 +389,10 @@ def lib():
     L.ffgpu_exec_caption_bgr.argtypes = [vp, i, C.POINTER(BgrFrame), i, C.POINTER(CaptionSpec), vp, vp, i, vp, vp]
     L.ffgpu_exec_caption_nv12.argtypes = [vp, i, C.POINTER(Nv12Frame), i, C.POINTER(CaptionSpec), vp, vp, i, vp, vp]
     L.ffgpu_caption_scene_dev.argtypes = [vp, vp, i, i, vp, i, C.POINTER(i), i, C.POINTER(CaptionSpec), vp, i, vp]
+    L.ffgpu_draw_segments_bgr_dev.argtypes = [vp, i, C.POINTER(BgrFrame), i, vp]
+    L.ffgpu_draw_segments_nv12_dev.argtypes = [vp, i, C.POINTER(Nv12Frame), i, vp]
+    L.ffgpu_outline_spec_check.argtypes = [C.POINTER(OutlineSpec)]
+    L.ffgpu_outline_scene_dev.argtypes = [vp, vp, i, i, vp, i, C.POINTER(i), i, C.POINTER(OutlineSpec), vp, i, vp]
     L.ffgpu_feature_dim.argtypes = [i, i, i, i]
     L.ffgpu_exec_feature_dim.argtypes = [vp, C.POINTER(FeatureSpec)]
     L.ffgpu_features_dev.argtypes = [vp, i, i, i, i, i, i, vp, C.c_long, vp]
@@ -1174,6 +1194,64 @@ def caption_scene_dev(d_scenes, d_state, nstreams, capacity, d_events, events_st
     arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
     _check(lib().ffgpu_caption_scene_dev(d_scenes, d_state, nstreams, capacity, d_events, events_stride, arr, len(streams), spec, d_items, items_stride, stream),
            "ffgpu_caption_scene_dev")
+
+
+def seg_items(items, stride=None):
+    """SEG_ITEM_DTYPE rows for one target from (x0, y0, x1, y1[, color, thickness, dash]) tuples; padded with unused slots (thickness 0) to `stride`
+    rows"""
+    out = np.zeros(len(items) if stride is None else stride, SEG_ITEM_DTYPE)
+    if len(items) > len(out):
+        raise ValueError("%d items for a stride of %d" % (len(items), len(out)))
+    for k, it in enumerate(items):
+        color, thickness, dash = (tuple(it[4:]) + ((255, 255, 255), 1, 0)[len(it) - 4:])[:3]
+        out[k]["x0"], out[k]["y0"], out[k]["x1"], out[k]["y1"], out[k]["thickness"], out[k]["dash"] = it[0], it[1], it[2], it[3], thickness, dash
+        out[k]["color"][:3] = color[:3]
+    return out
+
+
+def outline_spec(zones=True, lines=True, ticks=False, markers=False, alarm_on=False, thickness=1, line_dash=0, marker=0, color=(0, 0, 0), alarm=(0, 0, 255),
+                 palette=None):
+    """an OutlineSpec: which parts of a scene become segments (the zones' edges, the lines' shafts, their forward ticks, the anchors' crosses; alarm_on:
+    a loitered zone takes the colour `alarm`), how thick, the shafts' dash, the crosses' arm length, and the colours: one colour or a palette as
+    draw_style takes it (B G R bytes for BGR targets, Y U V for NV12 ones).  The structure keeps its palette bytes alive."""
+    sp = OutlineSpec()
+    sp.flags = ((OUTLINE_ZONES if zones else 0) | (OUTLINE_LINES if lines else 0) | (OUTLINE_TICKS if ticks else 0) | (OUTLINE_MARKERS if markers else 0) |
+                (OUTLINE_ALARM if alarm_on else 0))
+    sp.thickness, sp.line_dash, sp.marker = thickness, line_dash, marker
+    sp.color[:] = (int(color[0]), int(color[1]), int(color[2]), 0)
+    sp.alarm[:] = (int(alarm[0]), int(alarm[1]), int(alarm[2]), 0)
+    if palette is not None:
+        pal = np.zeros((len(palette), 4), np.uint8)
+        if len(palette):
+            pal[:, :3] = np.asarray(palette, np.uint8).reshape(len(palette), -1)[:, :3]
+        sp._pal = pal                                           # (owned by the structure: the C side reads it during the call)
+        sp.palette = pal.ctypes.data
+        sp.npalette = len(palette)
+    return sp
+
+
+def outline_spec_check(spec):
+    """ffgpu_outline_spec_check (pure host code): raises with what is wrong with the spec"""
+    _check(lib().ffgpu_outline_spec_check(spec), "ffgpu_outline_spec_check")
+
+
+def draw_segments_bgr_dev(d_items, items_stride, frames, stream=None):
+    """ffgpu_draw_segments_bgr_dev: items t * items_stride ... of d_items (SEG_ITEM_DTYPE rows) rasterised into frames[t] (what bgr_frame_desc accepts, or
+    None: skipped)"""
+    _check(lib().ffgpu_draw_segments_bgr_dev(d_items, items_stride, bgr_frame_table(frames), len(frames), stream), "ffgpu_draw_segments_bgr_dev")
+
+
+def draw_segments_nv12_dev(d_items, items_stride, frames, stream=None):
+    """ffgpu_draw_segments_nv12_dev: the same into NV12 frames (what nv12_frame_desc accepts, or None: skipped); colours are Y U V bytes"""
+    _check(lib().ffgpu_draw_segments_nv12_dev(d_items, items_stride, nv12_frame_table(frames), len(frames), stream), "ffgpu_draw_segments_nv12_dev")
+
+
+def outline_scene_dev(d_scenes, d_state, nstreams, capacity, d_events, events_stride, streams, spec, d_items, items_stride, stream=None):
+    """ffgpu_outline_scene_dev: the zones' edges, the lines' shafts and ticks and the anchors' crosses of stream streams[t] (scene, event row t, state)
+    as items t * items_stride ... of d_items (items_stride 80..512); spec from outline_spec; draw them with draw_segments_*_dev"""
+    arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+    _check(lib().ffgpu_outline_scene_dev(d_scenes, d_state, nstreams, capacity, d_events, events_stride, arr, len(streams), spec, d_items, items_stride, stream),
+           "ffgpu_outline_scene_dev")
 
 
 def feature_spec(layer=-1, pool=FFGPU.FEAT_MEAN, post=FFGPU.POST_NONE):

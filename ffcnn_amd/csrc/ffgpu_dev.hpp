@@ -8,6 +8,7 @@
 #include "ffgpu_args.hpp"
 #include "ffgpu_zones_host.hpp"
 #include "ffgpu_text_host.hpp"
+#include "ffgpu_lines_host.hpp"
 
 #define FFGPU_CHECK(expr)                                                                   \
     do {                                                                                    \
@@ -217,6 +218,9 @@ int ffgpu_launch_zones(const DetSource &src, const int *streams, int ntargets, c
 // items t * items_stride ... of d_items; target t's items are composed from record t of `src`
 int ffgpu_launch_draw_text(bool nv12, const void *d_items, int items_stride, const void *d_font, const std::vector<DrawTarget> &targets, hipStream_t s);
 int ffgpu_launch_caption_boxes(const DetSource &src, int ntargets, const CaptionPlan &pl, const void *d_ids, void *d_items, int items_stride, hipStream_t s);
+
+// outlines (ffgpu_lines.inc): the segment rasteriser's launches; the checks are host code with no HIP in it (ffgpu_lines_host.hpp)
+int ffgpu_launch_draw_segments(bool nv12, const void *d_items, int items_stride, const std::vector<DrawTarget> &targets, hipStream_t s);
 
 // the crops classified (ffgpu_feature.inc): the checks both entry points share, and the launches.  Features: frame n of the tensor is frame n % pn of
 // parts[n / pn], a CNHW tensor of pn frames (a split executor has one part per chain; at most 8).

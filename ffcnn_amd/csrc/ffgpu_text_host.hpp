@@ -102,16 +102,19 @@ inline int ffgpu_caption_boxes_args_check(const char *what, const ffgpu_caption_
     return 0;
 }
 
-inline int ffgpu_caption_scene_args_check(const char *what, const void *d_scenes, const void *d_state, int nstreams, int capacity, const void *d_events,
-                                          int events_stride, const int *streams, int ntargets, const ffgpu_caption_spec *spec, const void *d_items,
-                                          int items_stride, CaptionPlan &pl)
+// what a scene composer reads of the zones call (this one and ffgpu_outline_scene_dev, ffgpu_lines_host.hpp), in two halves: the pointers are looked at
+// before the spec and the items, the ranges behind them
+inline int ffgpu_scene_source_nulls_check(const char *what, const void *d_scenes, const void *d_state, const void *d_events, const int *streams)
 {
     if (!d_scenes) { ffgpu_set_error("%s: NULL scenes", what); return -1; }
     if (!d_state) { ffgpu_set_error("%s: NULL state", what); return -1; }
     if (!d_events) { ffgpu_set_error("%s: NULL events", what); return -1; }
     if (!streams) { ffgpu_set_error("%s: NULL streams", what); return -1; }
-    if (ffgpu_caption_spec_check(what, spec, false, pl)) return -1;
-    if (ffgpu_text_items_check(what, d_items, items_stride, 16)) return -1;
+    return 0;
+}
+inline int ffgpu_scene_source_ranges_check(const char *what, const void *d_scenes, const void *d_state, int nstreams, int capacity, const void *d_events,
+                                           int events_stride, const int *streams, int ntargets)
+{
     if (ffgpu_ntargets_check(what, ntargets)) return -1;
     if (nstreams < 1 || nstreams > 65536) { ffgpu_set_error("%s: nstreams %d is outside 1..65536", what, nstreams); return -1; }
     if (capacity < 1 || capacity > FFGPU_ZONES_DETS) { ffgpu_set_error("%s: capacity %d is outside 1..%d", what, capacity, FFGPU_ZONES_DETS); return -1; }
@@ -123,4 +126,14 @@ inline int ffgpu_caption_scene_args_check(const char *what, const void *d_scenes
     for (int t = 0; t < ntargets; t++)
         if (streams[t] < -1 || streams[t] >= nstreams) { ffgpu_set_error("%s: target %d: stream %d is outside -1 .. %d", what, t, streams[t], nstreams - 1); return -1; }
     return 0;
+}
+
+inline int ffgpu_caption_scene_args_check(const char *what, const void *d_scenes, const void *d_state, int nstreams, int capacity, const void *d_events,
+                                          int events_stride, const int *streams, int ntargets, const ffgpu_caption_spec *spec, const void *d_items,
+                                          int items_stride, CaptionPlan &pl)
+{
+    if (ffgpu_scene_source_nulls_check(what, d_scenes, d_state, d_events, streams)) return -1;
+    if (ffgpu_caption_spec_check(what, spec, false, pl)) return -1;
+    if (ffgpu_text_items_check(what, d_items, items_stride, 16)) return -1;
+    return ffgpu_scene_source_ranges_check(what, d_scenes, d_state, nstreams, capacity, d_events, events_stride, streams, ntargets);
 }

@@ -1143,6 +1143,99 @@ int ffgpu_exec_caption_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_frame *t
 int ffgpu_caption_scene_dev(const void *d_scenes, const void *d_state, int nstreams, int capacity, const void *d_events, int events_stride,
                             const int *streams, int ntargets, const ffgpu_caption_spec *spec, void *d_items, int items_stride, void *stream);
 
+/* ---- outlines: the zones' polygons, the lines, their forward side and the tested anchors drawn into the frames on the device --------------------
+ * The captions write "Z3 5" at a zone's first vertex and "L1 12/7" at a line's A; the polygon the five are inside, the line the twelve crossed, the
+ * side that counts as forward and the point of a box that is tested are what follows: a SEGMENT PRIMITIVE that rasterises segment items lying in
+ * device memory into u8 BGR and NV12 frames, and a SCENE COMPOSER that writes such items from the scenes, the event rows and the state of
+ * ffgpu_zones_boxes_dev.  The reference program draws rectangles only: the contract is this text, to the bit (tests/outlines/lineref.py restates it
+ * in numpy).
+ *
+ * Segment items: ffgpu_seg_item, 32 bytes each, in device memory (4-byte aligned).  Target t draws items t * items_stride .. t * items_stride +
+ * items_stride - 1; items_stride lies in 1..FFGPU_SEG_ITEMS; there is no count to read.  An item with thickness 0, or with any coordinate outside
+ * -FFGPU_SEG_LIMIT..FFGPU_SEG_LIMIT, draws nothing (every product below then fits 64 bits with room to spare).
+ * The pixel set of an item, all in 64-bit integers: dx = x1 - x0, dy = y1 - y0; the item is X-MAJOR when |dx| >= |dy|, otherwise y-major, and for a
+ * y-major item x and y exchange their roles in everything that follows.  S is the end point with the smaller major coordinate, E the other one (they have the same
+ * major coordinate only when the segment is a single point: then S == E): the set does not depend on the direction the segment was given in.  D = E.x - S.x >= 0, g = E.y - S.y, T = the clamped thickness, lo = (T - 1) / 2, hi = T / 2, d = the clamped
+ * dash.  Pixel (px, py) belongs to the item when, with m = px - S.x and r = py - S.y:
+ *     0 <= m <= D,  and  d == 0 or ((m >> d) & 1) == 0,  and
+ *     if D == 0:  -lo <= r <= hi;   otherwise, with e = 2 m g + D:  2 D (r - hi) <= e < 2 D (r + lo + 1).
+ * That is the column S.y + floor((2 m g + D) / (2 D)) of major step m with its lo pixels before and hi pixels behind, the floor taken toward
+ * -infinity: a DDA that rounds half up in the canonical direction, the thickness running along the minor axis.  A solid item contains both of its
+ * end points.  A pixel outside 0 <= px < w, 0 <= py < h of the target is dropped.
+ * A target's result is what drawing its items serially in slot order would leave: a later item overwrites an earlier one.  Only written pixels
+ * change; every other byte -- row padding, unwritten pixels, the memory in front of and behind the surface -- stays as it was.  The result does not
+ * depend on the order in which the device executes anything: the same bytes on every run.
+ * BGR targets: a written pixel becomes the three bytes 0, 1, 2 of `color`.  NV12 targets (`matrix` ignored, nothing converted): a written pixel sets
+ * Y[py][px] = byte 0; the chroma pair UV[py >> 1][px >> 1] takes bytes 1, 2 of the LAST item in slot order that writes any of the sample's up to
+ * four luma pixels inside the target.  Odd widths and heights are legal.
+ * The segment kernel is total over any item bytes: nothing is read outside d_items, nothing is written outside the targets' w x h. */
+#define FFGPU_SEG_ITEMS  512      /* items per target at most (items_stride) */
+#define FFGPU_SEG_LIMIT  1048576  /* 2^20: an item with a coordinate beyond +- this draws nothing */
+typedef struct {
+    int x0, y0, x1, y1;          /* 0, 4, 8, 12: the end points, target pixels, any value            */
+    unsigned char color[4];      /* 16: B G R 0 (BGR targets) / Y U V 0 (NV12 targets)               */
+    unsigned char thickness;     /* 20: 0: the item draws nothing; above 8 reads as 8                */
+    unsigned char dash;          /* 21: 0: solid; above 6 reads as 6                                 */
+    unsigned char flags;         /* 22: ignored                                                      */
+    unsigned char reserved;      /* 23                                                               */
+    int reserved2[2];            /* 24                                                               */
+} ffgpu_seg_item;                /* 32 bytes: x0 0, y0 4, x1 8, y1 12, color 16, thickness 20, dash 21, flags 22, reserved 23, reserved2 24 */
+
+/* The segment rasteriser.  The descriptors, their checks, "a NULL pixel address skips the target" and the no-overlap rule are the draw operators',
+ * word for word; the tables travel as by-value kernel arguments, 64 targets per launch; enqueued on `stream` without synchronising.  targets is HOST
+ * memory and free again on return.  Rejected before anything is launched, with the target's index in the message where there is one: NULL items or
+ * targets, items that are not 4-byte aligned, ntargets < 1, items_stride outside 1..512, a descriptor the draw operators would reject. */
+int ffgpu_draw_segments_bgr_dev (const void *d_items, int items_stride, const ffgpu_bgr_frame  *targets, int ntargets, void *stream);
+int ffgpu_draw_segments_nv12_dev(const void *d_items, int items_stride, const ffgpu_nv12_frame *targets, int ntargets, void *stream);
+
+/* The scene as segment items, from the scenes, the events and the state of ffgpu_zones_boxes_dev; the caller draws them with
+ * ffgpu_draw_segments_*_dev (no executor form: scenes and state are the caller's).  Its shape is ffgpu_caption_scene_dev's: stream s = streams[t];
+ * -1 gives the target all-zero items; events_stride is the ints per event row of the zones call that wrote it; the state's streams lie
+ * 144 + 64 x capacity bytes apart.  items_stride lies in FFGPU_OUTLINE_FIXED..512.  Every byte of d_items for the call's targets is written, so the
+ * buffer needs no clearing; it is also the product: a caller may add items of their own behind the fixed slots.  THE STATE'S VALUES ARE THE STATE'S
+ * WHEN THE KERNEL RUNS: with several records of one stream in one zones call, every target of that stream shows the anchors of the last one.
+ * Every coordinate is converted from float by the draw contract's rule (toward zero, saturating, NaN -> 0); anything computed from the converted
+ * integers is computed in 64 bits and saturated to int, so a far-off vertex yields items the primitive drops.  Byte 3 of a colour, `flags` and the
+ * reserved fields are written as 0.
+ *   Slot 8 z + i, with FFGPU_OUTLINE_ZONES: zone z's edge from vertex i to vertex (i + 1) % nverts.  It exists for z < nzones (clamped to 0..8 as
+ *     the zones kernel clamps it) and i < nverts, when the zone's nverts is in 3..8 and none of its used vertices is NaN (otherwise the zone contains
+ *     nothing and draws nothing).  thickness = the spec's, dash 0; colour = palette entry z mod npalette, or `color`; with FFGPU_OUTLINE_ALARM the
+ *     colour is `alarm` when the zone's loitering count, int 16 + 4 z + 3 of event row t, is not 0.
+ *   Slot 64 + 2 l, with FFGPU_OUTLINE_LINES: line l's shaft A -> B, for l < nlines (clamped likewise).  thickness = the spec's, dash = line_dash;
+ *     colour = palette entry (8 + l) mod npalette, or `color`.
+ *   Slot 64 + 2 l + 1, with FFGPU_OUTLINE_TICKS: the forward tick of line l, from M = ((ax + bx) >> 1, (ay + by) >> 1) to
+ *     M + (-(by - ay) / 8, (bx - ax) / 8), the shifts arithmetic and the divisions toward zero, on the converted integers.  Solid, thickness 1, the
+ *     shaft's colour.  It points to the side on which the zones contract's side(P) is true: where a crossing ends that counts as FORWARD.
+ *   Slots 80 + 2 k and 80 + 2 k + 1, with FFGPU_OUTLINE_MARKERS: slot q < capacity of the stream's state is SEEN when id != 0 and last == frames - 1
+ *     modulo 2^32, frames the header's.  The k-th seen slot in slot order writes a cross centred on the converted (px, py) = (cx, cy):
+ *     (cx - r, cy) -> (cx + r, cy) and (cx, cy - r) -> (cx, cy + r), r = marker; solid, thickness 1; colour = palette entry id mod npalette (the
+ *     non-negative remainder), or `color`.  It is written while 80 + 2 k + 1 < items_stride; further seen slots get none.
+ *   Every other slot is 32 zero bytes.
+ * One workgroup per target; streams and spec (with its palette) are HOST memory and free again on return; 512 targets per launch.  Rejected before
+ * anything is launched: ffgpu_caption_scene_dev's reasons, with items_stride outside 80..512 in place of its range, and a spec field outside the
+ * ranges below.  Redact, then draw, then outline, then caption: the tags lie on top. */
+#define FFGPU_OUTLINE_FIXED   80  /* the slots of the zones' edges (0..63) and of the lines' shafts and ticks (64..79) */
+#define FFGPU_OUTLINE_ZONES   1
+#define FFGPU_OUTLINE_LINES   2
+#define FFGPU_OUTLINE_TICKS   4   /* needs FFGPU_OUTLINE_LINES */
+#define FFGPU_OUTLINE_MARKERS 8
+#define FFGPU_OUTLINE_ALARM   16  /* needs FFGPU_OUTLINE_ZONES */
+typedef struct {
+    int flags;                     /* at least one of ZONES | LINES | MARKERS; unknown bits rejected */
+    int thickness;                 /* 1..8: zones and line shafts */
+    int line_dash;                 /* 0..6: the line shafts' dash */
+    int marker;                    /* 0..32: the anchor crosses' arm length; at least 1 with MARKERS */
+    unsigned char color[4];        /* the colour when palette is NULL */
+    unsigned char alarm[4];        /* the alarm colour */
+    const unsigned char *palette;  /* HOST, npalette x 4 bytes, or NULL: exactly ffgpu_draw_style's */
+    int npalette;                  /* 0 with a NULL palette, else 1..256 */
+    int reserved;                  /* 0 */
+} ffgpu_outline_spec;              /* 40 bytes: flags 0, thickness 4, line_dash 8, marker 12, color 16, alarm 20, palette 24, npalette 32, reserved 36 */
+/* pure host code: 0, or -1 with the message in ffgpu_last_error */
+int ffgpu_outline_spec_check(const ffgpu_outline_spec *spec);
+int ffgpu_outline_scene_dev(const void *d_scenes, const void *d_state, int nstreams, int capacity, const void *d_events, int events_stride,
+                            const int *streams, int ntargets, const ffgpu_outline_spec *spec, void *d_items, int items_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
