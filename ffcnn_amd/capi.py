@@ -117,6 +117,11 @@ class RedactSpec(C.Structure):       # ffgpu_redact_spec (40 bytes): which boxes
                 ("margin_num", C.c_int), ("margin_den", C.c_int), ("color", C.c_ubyte * 4)]
 
 
+class BlurSpec(C.Structure):         # ffgpu_blur_spec (40 bytes): which boxes' regions are blurred, and how far
+    _fields_ = [("radius", C.c_int), ("passes", C.c_int), ("flags", C.c_int), ("nclasses", C.c_int), ("classes", C.c_void_p), ("min_score", C.c_float),
+                ("margin_num", C.c_int), ("margin_den", C.c_int), ("reserved", C.c_int)]
+
+
 class Zone(C.Structure):             # ffgpu_zone (96 bytes): one polygon of a scene
     _fields_ = [("x", C.c_float * 8), ("y", C.c_float * 8), ("nverts", C.c_int), ("dwell_frames", C.c_int), ("classes", C.c_uint * 4), ("reserved", C.c_int * 2)]
 
@@ -178,6 +183,8 @@ CROP_ENTRIES, CROP_MERGED = 0, 1                                                
 REDACT_FILL, REDACT_MOSAIC = 0, 1                                                     # FFGPU_REDACT_* (ffgpu_redact_spec.mode)
 REDACT_OUTSIDE = 1                                                                     # FFGPU_REDACT_OUTSIDE (ffgpu_redact_spec.flags)
 REDACT_ENTRIES, REDACT_MERGED = 0, 1                                                   # FFGPU_REDACT_* (ffgpu_exec_redact_bgr / _nv12: which)
+BLUR_OUTSIDE = 1                                                                       # FFGPU_BLUR_OUTSIDE (ffgpu_blur_spec.flags)
+BLUR_ENTRIES, BLUR_MERGED = 0, 1                                                       # FFGPU_BLUR_* (ffgpu_exec_blur_bgr / _nv12: which)
 DRAW_ENTRIES, DRAW_MERGED = 0, 1                                                       # FFGPU_DRAW_* (ffgpu_exec_draw_bgr / _nv12: which)
 YUV_BT601_LIMITED, YUV_BT601_FULL, YUV_BT709_LIMITED, YUV_BT709_FULL = 0, 1, 2, 3      # FFGPU_YUV_* (ffgpu_nv12_frame.matrix)
 
@@ -187,7 +194,7 @@ assert C.sizeof(BgrFrame) == 24 and C.sizeof(Nv12Frame) == 40 and C.sizeof(Tile)
 assert C.sizeof(DrawStyle) == 24 and C.sizeof(CropSpec) == 72 and C.sizeof(Crop) == 48
 assert C.sizeof(TrackSpec) == 32 and C.sizeof(Track) == 48
 assert C.sizeof(FeatureSpec) == 16 and C.sizeof(Label) == 8 and C.sizeof(RelabelSpec) == 16
-assert C.sizeof(Gallery) == 40 and C.sizeof(RedactSpec) == 40
+assert C.sizeof(Gallery) == 40 and C.sizeof(RedactSpec) == 40 and C.sizeof(BlurSpec) == 40
 assert C.sizeof(TextItem) == 64 and C.sizeof(CaptionSpec) == 48
 assert C.sizeof(SegItem) == 32 and C.sizeof(OutlineSpec) == 40
 assert C.sizeof(Zone) == 96 and C.sizeof(Line) == 32 and C.sizeof(Scene) == 1040 and C.sizeof(ZonesSpec) == 32 and C.sizeof(ZoneSlot) == 64
@@ -228,6 +235,7 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_exec_relabel",
            "ffgpu_match_workspace_bytes", "ffgpu_match_dev", "ffgpu_gallery_enroll_dev",
            "ffgpu_redact_boxes_bgr_dev", "ffgpu_redact_boxes_nv12_dev", "ffgpu_exec_redact_bgr", "ffgpu_exec_redact_nv12",
+           "ffgpu_blur_boxes_bgr_dev", "ffgpu_blur_boxes_nv12_dev", "ffgpu_exec_blur_bgr", "ffgpu_exec_blur_nv12",
            "ffgpu_zones_state_bytes", "ffgpu_scene_check", "ffgpu_zones_reset_dev", "ffgpu_zones_boxes_dev", "ffgpu_exec_zones",
            "ffgpu_font_builtin", "ffgpu_draw_text_bgr_dev", "ffgpu_draw_text_nv12_dev", "ffgpu_caption_boxes_dev", "ffgpu_exec_caption_bgr", "ffgpu_exec_caption_nv12",
            "ffgpu_caption_scene_dev",
@@ -361,6 +369,10 @@ def lib():
     L.ffgpu_redact_boxes_nv12_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(Nv12Frame), i, C.POINTER(RedactSpec), vp]
     L.ffgpu_exec_redact_bgr.argtypes = [vp, i, C.POINTER(BgrFrame), i, C.POINTER(RedactSpec), vp]
     L.ffgpu_exec_redact_nv12.argtypes = [vp, i, C.POINTER(Nv12Frame), i, C.POINTER(RedactSpec), vp]
+    L.ffgpu_blur_boxes_bgr_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(BgrFrame), C.POINTER(BgrFrame), i, C.POINTER(BlurSpec), vp]
+    L.ffgpu_blur_boxes_nv12_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(Nv12Frame), C.POINTER(Nv12Frame), i, C.POINTER(BlurSpec), vp]
+    L.ffgpu_exec_blur_bgr.argtypes = [vp, i, C.POINTER(BgrFrame), C.POINTER(BgrFrame), i, C.POINTER(BlurSpec), vp]
+    L.ffgpu_exec_blur_nv12.argtypes = [vp, i, C.POINTER(Nv12Frame), C.POINTER(Nv12Frame), i, C.POINTER(BlurSpec), vp]
     L.ffgpu_crop_table_bytes.restype = sz
     L.ffgpu_crop_table_bytes.argtypes = [i]
     L.ffgpu_crop_slot_bytes.restype = sz
@@ -733,6 +745,20 @@ class Executor:
         picture g in frames[g]) behind it (ffgpu_exec_redact_bgr): frames as draw_bgr takes them, spec from redact_spec.  Redact before draw."""
         _check(lib().ffgpu_exec_redact_bgr(self.h, which, bgr_frame_table(frames), len(frames), spec, stream), "ffgpu_exec_redact_bgr")
 
+    def blur_bgr(self, frames, scratch, spec, which=0, stream=None):
+        """enqueue the blur of the last forward's boxes (which = BLUR_ENTRIES) or of the last merge's (BLUR_MERGED) behind it (ffgpu_exec_blur_bgr):
+        frames as redact_bgr takes them, scratch one surface of the same w x h per frame (None where the frame is), spec from blur_spec.  Blur
+        before draw."""
+        if len(scratch) != len(frames):
+            raise ValueError("blur_bgr: %d scratch surfaces for %d frames" % (len(scratch), len(frames)))
+        _check(lib().ffgpu_exec_blur_bgr(self.h, which, bgr_frame_table(frames), bgr_frame_table(scratch), len(frames), spec, stream), "ffgpu_exec_blur_bgr")
+
+    def blur_nv12(self, frames, scratch, spec, which=0, stream=None):
+        """the same in NV12 frames (ffgpu_exec_blur_nv12): chroma is blurred with radius (radius + 1) / 2"""
+        if len(scratch) != len(frames):
+            raise ValueError("blur_nv12: %d scratch surfaces for %d frames" % (len(scratch), len(frames)))
+        _check(lib().ffgpu_exec_blur_nv12(self.h, which, nv12_frame_table(frames), nv12_frame_table(scratch), len(frames), spec, stream), "ffgpu_exec_blur_nv12")
+
     def redact_nv12(self, frames, spec, which=0, stream=None):
         """the same in NV12 frames (ffgpu_exec_redact_nv12): the spec's colour is Y U V bytes, its cell even"""
         _check(lib().ffgpu_exec_redact_nv12(self.h, which, nv12_frame_table(frames), len(frames), spec, stream), "ffgpu_exec_redact_nv12")
@@ -946,6 +972,39 @@ def redact_boxes_bgr_dev(d_records, d_lists, list_stride, frames, spec, list_fir
 def redact_boxes_nv12_dev(d_records, d_lists, list_stride, frames, spec, list_first=None, stream=None):
     """ffgpu_redact_boxes_nv12_dev: the same in NV12 frames (what nv12_frame_desc accepts, or None: skipped)"""
     _redact_boxes_dev(lib().ffgpu_redact_boxes_nv12_dev, "ffgpu_redact_boxes_nv12_dev", nv12_frame_table, d_records, d_lists, list_stride, list_first, frames, spec, stream)
+
+
+def blur_spec(radius, passes=1, outside=False, min_score=0.0, classes=None, margin=(0, 1)):
+    """a BlurSpec: radius 1..31 (the box window is 2 radius + 1 pixels square, clipped to the frame), passes 1..3; outside: everything BUT the
+    regions; classes, min_score and margin as redact_spec.  The structure keeps its class bytes alive."""
+    sp = BlurSpec()
+    sp.radius, sp.passes, sp.flags, sp.min_score = radius, passes, BLUR_OUTSIDE if outside else 0, min_score
+    sp.margin_num, sp.margin_den = margin
+    if classes is not None:
+        cls = np.ascontiguousarray(np.asarray(classes) != 0, np.uint8) if len(classes) else np.zeros(1, np.uint8)
+        sp._cls = cls                                           # (owned by the structure: the C side reads it during the call)
+        sp.classes = cls.ctypes.data
+        sp.nclasses = len(classes)
+    return sp
+
+
+def _blur_boxes_dev(fn, name, table, d_records, d_lists, list_stride, list_first, frames, scratch, spec, stream):
+    if len(scratch) != len(frames):
+        raise ValueError("%s: %d scratch surfaces for %d frames" % (name, len(scratch), len(frames)))
+    first = None if list_first is None else (C.c_int * max(1, len(list_first)))(*[int(v) for v in list_first])
+    _check(fn(d_records, d_lists, list_stride, first, table(frames), table(scratch), len(frames), spec, stream), name)
+
+
+def blur_boxes_bgr_dev(d_records, d_lists, list_stride, frames, scratch, spec, list_first=None, stream=None):
+    """ffgpu_blur_boxes_bgr_dev on device records / lists: the regions of record t's qualifying boxes (or everything but them) box-blurred in
+    frames[t] through scratch[t] (both what bgr_frame_desc accepts, or None: skipped); d_lists None: the records' own boxes; list_first as
+    draw_boxes_bgr_dev"""
+    _blur_boxes_dev(lib().ffgpu_blur_boxes_bgr_dev, "ffgpu_blur_boxes_bgr_dev", bgr_frame_table, d_records, d_lists, list_stride, list_first, frames, scratch, spec, stream)
+
+
+def blur_boxes_nv12_dev(d_records, d_lists, list_stride, frames, scratch, spec, list_first=None, stream=None):
+    """ffgpu_blur_boxes_nv12_dev: the same in NV12 frames (what nv12_frame_desc accepts, or None: skipped)"""
+    _blur_boxes_dev(lib().ffgpu_blur_boxes_nv12_dev, "ffgpu_blur_boxes_nv12_dev", nv12_frame_table, d_records, d_lists, list_stride, list_first, frames, scratch, spec, stream)
 
 
 def crop_spec(out_w, out_h, form=CROP_F32, per_target=1, min_score=0.0, classes=None, margin=(0, 1), mean=(0.0, 0.0, 0.0), norm=(1 / 255.0,) * 3):

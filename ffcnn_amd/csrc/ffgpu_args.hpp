@@ -59,6 +59,7 @@ struct FrameRole {
     int bgr_max_h;
 };
 static const FrameRole FRAME_FORWARD = { "frame", true, "read", 0x7fffffff }, FRAME_DRAW = { "target", false, "written", 0x3fffffff };
+static const FrameRole FRAME_SCRATCH = { "scratch", false, "written", 0x3fffffff };     // the blur's second surface per target: a FRAME_DRAW by another name
 
 inline int ffgpu_frame_check(const char *what, const FrameRole &role, int k, const ffgpu_bgr_frame &f, FrameArgs &a)
 {
@@ -130,7 +131,7 @@ struct DetSource {
 
 static_assert(FFGPU_DRAW_ENTRIES == 0 && FFGPU_CROP_ENTRIES == 0 && FFGPU_TRACK_ENTRIES == 0 && FFGPU_RELABEL_ENTRIES == 0 && FFGPU_REDACT_ENTRIES == 0 &&
               FFGPU_ZONES_ENTRIES == 0 && FFGPU_CAPTION_ENTRIES == 0 && FFGPU_CAPTION_MERGED == 1 && FFGPU_DRAW_MERGED == 1 && FFGPU_CROP_MERGED == 1 && FFGPU_TRACK_MERGED == 1 && FFGPU_RELABEL_MERGED == 1 &&
-              FFGPU_REDACT_MERGED == 1 && FFGPU_ZONES_MERGED == 1, "ffgpu_source_exec: one check of `which` serves the seven families");
+              FFGPU_REDACT_MERGED == 1 && FFGPU_ZONES_MERGED == 1 && FFGPU_BLUR_ENTRIES == 0 && FFGPU_BLUR_MERGED == 1, "ffgpu_source_exec: one check of `which` serves the eight families");
 
 // the list stride of an operator form: the caller's with lists, FFGPU_MAX_DET without; -1 with a message outside 1 .. 2^24
 inline int ffgpu_list_stride(const char *what, const void *d_lists, int list_stride)

@@ -205,6 +205,18 @@ struct RedactPlan {
 int ffgpu_redact_spec_check(const char *what, const ffgpu_redact_spec *sp, bool nv12, RedactPlan &pl);
 int ffgpu_launch_redact(const char *what, bool nv12, const DetSource &src, const std::vector<DrawTarget> &targets, const RedactPlan &pl, hipStream_t s);
 
+// the detections' regions blurred in the frames through a scratch surface per target (ffgpu_blur.inc).  BlurPlan: the caller's spec, checked, with the
+// class filter's bytes copied.  targets[t] is blurred by record t of `src` through scratch[t]; ffgpu_launch_blur first holds the scratch table against
+// the targets (same w x h, NULL where the target is, no overlap) and launches nothing when it does not fit
+struct BlurPlan {
+    int   radius, passes, outside, nclasses, num, den;
+    float min_score;
+    unsigned char classes[256];
+};
+int ffgpu_blur_spec_check(const char *what, const ffgpu_blur_spec *sp, BlurPlan &pl);
+int ffgpu_launch_blur(const char *what, bool nv12, const DetSource &src, const std::vector<DrawTarget> &targets, const std::vector<DrawTarget> &scratch,
+                      const BlurPlan &pl, hipStream_t s);
+
 // the detections tracked across a stream's frames (ffgpu_track.inc): the checks both entry points share, and the launches
 int ffgpu_track_args_check(const char *what, const int *streams, int ntargets, const ffgpu_track_spec *spec, const void *d_state, int nstreams,
                            const void *d_ids, const void *d_out_records, const void *d_out_lists);

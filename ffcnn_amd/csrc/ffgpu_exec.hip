@@ -1385,6 +1385,39 @@ extern "C" int ffgpu_exec_redact_nv12(ffgpu_exec *ex, int which, const ffgpu_nv1
     return exec_redact(ex, "redact_nv12", which, targets, ntargets, spec, stream);
 }
 
+// -------------------------------------------------------------------------- the detections blurred in the frames (include/ffcnn_hip.h; kernel: ffgpu_blur.inc)
+// A post-pass like the redaction, with a scratch surface per target: reads the records and full lists, reads and writes the caller's frames and
+// scratch surfaces and nothing of the executor's.
+template <class Frame>
+static int exec_blur(ffgpu_exec *ex, const char *what, int which, const Frame *targets, const Frame *scratch, int ntargets, const ffgpu_blur_spec *spec, void *stream)
+{
+    const bool nv12 = std::is_same<Frame, ffgpu_nv12_frame>::value;
+    if (!exec_ok(ex, what)) return -1;
+    if (!targets) { ffgpu_set_error("%s: NULL targets", what); return -1; }
+    if (!scratch) { ffgpu_set_error("%s: NULL scratch", what); return -1; }
+    BlurPlan pl;
+    if (ffgpu_blur_spec_check(what, spec, pl)) return -1;
+    DetSource src;
+    hipStream_t s;
+    if (exec_source(ex, what, "BLUR", "blur", which, ntargets, stream, src, &s)) return -1;
+    src.stride = (int)std::min(src.longest, (long long)0x7fffffff);  // (clamped, as the draw)
+    std::vector<DrawTarget> tab, stab;
+    if (ffgpu_frame_table(what, FRAME_DRAW, targets, ntargets, tab) || ffgpu_frame_table(what, FRAME_SCRATCH, scratch, ntargets, stab)) return -1;
+    return ffgpu_launch_blur(what, nv12, src, tab, stab, pl, s);
+}
+
+extern "C" int ffgpu_exec_blur_bgr(ffgpu_exec *ex, int which, const ffgpu_bgr_frame *targets, const ffgpu_bgr_frame *scratch, int ntargets,
+                                   const ffgpu_blur_spec *spec, void *stream)
+{
+    return exec_blur(ex, "blur_bgr", which, targets, scratch, ntargets, spec, stream);
+}
+
+extern "C" int ffgpu_exec_blur_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_frame *targets, const ffgpu_nv12_frame *scratch, int ntargets,
+                                    const ffgpu_blur_spec *spec, void *stream)
+{
+    return exec_blur(ex, "blur_nv12", which, targets, scratch, ntargets, spec, stream);
+}
+
 // -------------------------------------------------------------------------- the detections cut out of the frames (include/ffcnn_hip.h; kernels: ffgpu_crop.inc)
 // A post-pass like the draw, on the stream of the forward or merge it follows: reads the records and full lists (per entry, or the merged ones) and
 // the caller's frames, writes the caller's batch buffer and table and nothing of the executor's.

@@ -653,6 +653,7 @@ extern "C" int ffgpu_pack_records(const void *d_records, int nslots, long slot_s
 #include "ffgpu_draw.inc"
 #include "ffgpu_crop.inc"
 #include "ffgpu_redact.inc"
+#include "ffgpu_blur.inc"
 #include "ffgpu_track.inc"
 #include "ffgpu_zones.inc"
 #include "ffgpu_text.inc"

@@ -65,29 +65,16 @@ __device__ __forceinline__ void redact_col_sum(const unsigned char *p, size_t pi
     for (; y < y1; y++) redact_col_rows<NC, 1>(p, pitch, y, m);
 }
 
-// grid (blocks of the launch's largest target, targets of this launch), 256 lanes.  Target blockIdx.y reads record rec0 + blockIdx.y as k_draw_boxes
-// does (counts clamped to [0, stride]); a workgroup beyond its target's own blocks leaves.  Every load and store lies inside the block, clipped to the
-// target's w x h.
-template <bool NV12>
-__global__ void __launch_bounds__(256) k_redact(RedactArgs a, const ffgpu_frame_dets *recs, const BBOX *lists, int stride)
+// S of one block (bx0, by0, bw x bh pixels of a w x h target) into s_cov, a 64-bit mask per pixel row (rows >= bh: 0): the first stage of k_redact
+// and of k_blur (ffgpu_blur.inc).  Args: the kernel's argument struct with crop_region's selection fields and `outside`.  The list is staged
+// REDACT_LDS_BOXES at a time; lane (wv, row) ORs the columns of boxes wv, wv + 4, .. of every trip into its own register.  Every lane of the 256
+// calls it; true in every lane when a bit is set.  The LDS arrays are the caller's: s_xm, s_ya, s_yb [REDACT_LDS_BOXES], s_part [4][WAVE], s_cov [WAVE].
+template <class Args>
+__device__ __forceinline__ bool redact_coverage(const Args &a, const BBOX *list, int n, int w, int h, int bx0, int by0, int bw, int bh,
+                                                unsigned long long *s_xm, int *s_ya, int *s_yb, unsigned long long (*s_part)[WAVE], unsigned long long *s_cov)
 {
     typedef unsigned long long u64;
-    __shared__ u64 s_xm[REDACT_LDS_BOXES];                // a staged box inside this block: its columns ...
-    __shared__ int s_ya[REDACT_LDS_BOXES], s_yb[REDACT_LDS_BOXES];   // ... and its rows (ya > yb: none)
-    __shared__ u64 s_part[4][WAVE], s_cov[WAVE];          // row y's covered columns: each wave's share of the boxes, then S itself
-    const DrawTarget &t = a.t[blockIdx.y];
-    if (!t.p0) return;                                                                // a skipped target (uniform)
-    const int w = t.w, h = t.h, side = REDACT_SIDE(a.cell);
-    const long long nbx = ((long long)w + side - 1) / side, nby = ((long long)h + side - 1) / side;
-    if ((long long)blockIdx.x >= nbx * nby) return;                                   // (uniform)
-    const int bx0 = (int)(blockIdx.x % nbx) * side, by0 = (int)(blockIdx.x / nbx) * side, bw = min(side, w - bx0), bh = min(side, h - by0);
-    const ffgpu_frame_dets *rec = recs + a.rec0 + blockIdx.y;
-    const int n = max(0, min(lists ? rec->nfull : rec->count, stride));
-    if (n == 0 && !a.outside) return;                                                 // (uniform)
-    const BBOX *list = lists ? lists + t.first : rec->box;
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
-
-    // ---- S of this block.  Lane (wv, row) ORs the columns of boxes wv, wv + 4, .. of every trip into its own register.
     u64 acc = 0;
     for (int c0 = 0; c0 < n; c0 += REDACT_LDS_BOXES) {
         u64 xm = 0;
@@ -112,7 +99,33 @@ __global__ void __launch_bounds__(256) k_redact(RedactArgs a, const ffgpu_frame_
         mine = tid < bh ? (a.outside ? ~u : u) & redact_bits(0, bw - 1) : 0;
         s_cov[tid] = mine;
     }
-    if (!__syncthreads_or(mine != 0)) return;                                         // nothing to write: no pixel is touched
+    return __syncthreads_or(mine != 0);
+}
+
+// grid (blocks of the launch's largest target, targets of this launch), 256 lanes.  Target blockIdx.y reads record rec0 + blockIdx.y as k_draw_boxes
+// does (counts clamped to [0, stride]); a workgroup beyond its target's own blocks leaves.  Every load and store lies inside the block, clipped to the
+// target's w x h.
+template <bool NV12>
+__global__ void __launch_bounds__(256) k_redact(RedactArgs a, const ffgpu_frame_dets *recs, const BBOX *lists, int stride)
+{
+    typedef unsigned long long u64;
+    __shared__ u64 s_xm[REDACT_LDS_BOXES];                // a staged box inside this block: its columns ...
+    __shared__ int s_ya[REDACT_LDS_BOXES], s_yb[REDACT_LDS_BOXES];   // ... and its rows (ya > yb: none)
+    __shared__ u64 s_part[4][WAVE], s_cov[WAVE];          // row y's covered columns: each wave's share of the boxes, then S itself
+    const DrawTarget &t = a.t[blockIdx.y];
+    if (!t.p0) return;                                                                // a skipped target (uniform)
+    const int w = t.w, h = t.h, side = REDACT_SIDE(a.cell);
+    const long long nbx = ((long long)w + side - 1) / side, nby = ((long long)h + side - 1) / side;
+    if ((long long)blockIdx.x >= nbx * nby) return;                                   // (uniform)
+    const int bx0 = (int)(blockIdx.x % nbx) * side, by0 = (int)(blockIdx.x / nbx) * side, bw = min(side, w - bx0), bh = min(side, h - by0);
+    const ffgpu_frame_dets *rec = recs + a.rec0 + blockIdx.y;
+    const int n = max(0, min(lists ? rec->nfull : rec->count, stride));
+    if (n == 0 && !a.outside) return;                                                 // (uniform)
+    const BBOX *list = lists ? lists + t.first : rec->box;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
+
+    // ---- S of this block
+    if (!redact_coverage(a, list, n, w, h, bx0, by0, bw, bh, s_xm, s_ya, s_yb, s_part, s_cov)) return;   // nothing to write: no pixel is touched
 
     const unsigned c0 = a.colour & 0xffu, c1 = (a.colour >> 8) & 0xffu, c2 = (a.colour >> 16) & 0xffu;
     unsigned char *const row0 = t.p0 + (size_t)by0 * (size_t)t.pitch + (NV12 ? 1 : 3) * (size_t)bx0;     // pixel (bx0, by0)

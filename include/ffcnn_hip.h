@@ -881,6 +881,73 @@ int ffgpu_redact_boxes_nv12_dev(const void *d_records, const void *d_lists, int 
 int ffgpu_exec_redact_bgr (ffgpu_exec *ex, int which, const ffgpu_bgr_frame  *targets, int ntargets, const ffgpu_redact_spec *spec, void *stream);
 int ffgpu_exec_redact_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_frame *targets, int ntargets, const ffgpu_redact_spec *spec, void *stream);
 
+/* ---- the detections blurred in the frames on the device ----------------------------------------------------------------------------------------
+ * The third form of privacy masking, and the one asked for first: the selected boxes' regions (or everything BUT them) box-blurred in u8 BGR and
+ * NV12 frames where they lie.  A blur window reaches into pixels that a neighbour rewrites, so it is not done on one surface: the caller supplies a
+ * SCRATCH surface per target, and a pass is two launches -- the first reads the target everywhere and writes the blurred values of the covered set
+ * into the scratch, the second copies them back into the target; stream order between the two is the barrier.  The result is a pure function of
+ * the frame's bytes, the list and the spec: the same bytes on every run (tests/blur/blurref.py restates it in numpy).
+ *
+ * Covered set S of a target: the redact contract's, word for word (qualifying boxes, regions, union, FFGPU_BLUR_OUTSIDE = the target's w x h minus
+ * the union; a list with no qualifying box then blurs the whole target).  S is computed once per call from the list: every pass covers the same set.
+ * One pass, BGR.  Let O be the target's bytes before the pass and r the radius.  For every pixel (x, y) of S and every channel, the window is
+ * W = [max(x - r, 0) .. min(x + r, w - 1)] x [max(y - r, 0) .. min(y + r, h - 1)]: it is clipped to the target's w x h, not padded.  With n = |W|
+ * the new byte is (sum of O over W + n / 2) / n in integers.  The window takes in pixels outside S: blur mixes, it does not mask.  Every byte outside
+ * S stays.
+ * Passes.  passes = p applies the pass p times, each reading the whole target as the previous one left it (three passes of a box approximate a
+ * Gaussian).
+ * NV12 (`matrix` is ignored, nothing is converted).  Luma is one channel with radius r.  The chroma plane is ((w + 1) / 2) x ((h + 1) / 2) samples
+ * with radius rc = (r + 1) / 2; U and V are averaged separately with the same rounding, the window clipped to the chroma plane.  The samples written
+ * are exactly those the redact FILL rule covers: a sample is written when ANY of its luma pixels inside w x h is in S.  No evenness is required of r.
+ * Scratch.  One descriptor per target, of the same type and the same w x h; its pitches are free; it is NULL exactly where the target is NULL.
+ * Scratch surfaces must not overlap each other or any target of the call in memory (a surface here is the bytes from the first to the last of each
+ * of its planes, row padding included); a host check rejects that with both indices in the message.  After the call the scratch bytes at the
+ * positions of S (chroma: of the covered samples) hold the target's final values, and every other scratch byte is unchanged: the scratch is
+ * comparable byte for byte too.
+ * Untouched bytes.  Every byte outside S -- row padding, uncovered pixels and samples, the memory before and behind the surfaces -- stays as it was,
+ * in the target and in the scratch.  Each byte has one owner per launch: a workgroup owns a 64 x 64 block of the launch's destination, anchored at
+ * pixel (0, 0); nobody writes a launch's source.  No atomic is used; every load lies inside the source's w x h, every store inside the destination's.
+ * Ordering.  Blur, then draw, outline and caption: the overlays lie on top.  A tile descriptor is a legal target, but tiles of one picture overlap:
+ * for tiled pictures use FFGPU_BLUR_MERGED on the whole picture, as redaction does.
+ * Targets: as the draw contract takes them (a NULL pixel address = "skip this target", the const pointers are WRITTEN THROUGH, targets of one call
+ * must not overlap in memory). */
+#define FFGPU_BLUR_OUTSIDE 1        /* flags bit 0: blur everything EXCEPT the regions */
+typedef struct {
+    int   radius;                   /* 1..31: the window is up to (2 radius + 1) pixels square                                    */
+    int   passes;                   /* 1..3                                                                                       */
+    int   flags;                    /* 0 | FFGPU_BLUR_OUTSIDE; any other bit is rejected                                          */
+    int   nclasses;                 /* 0 with NULL classes, else 1..256                                                           */
+    const unsigned char *classes;   /* HOST array, as ffgpu_redact_spec                                                           */
+    float min_score;
+    int   margin_num, margin_den;   /* as ffgpu_redact_spec: den 1..1024, num 0..4 den                                            */
+    int   reserved;                 /* must be 0                                                                                  */
+} ffgpu_blur_spec;                  /* 40 bytes: radius 0, passes 4, flags 8, nclasses 12, classes 16, min_score 24, margin_num   */
+                                    /* 28, margin_den 32, reserved 36                                                             */
+
+/* The operators, on device records and lists with no executor: d_records, d_lists, list_stride, the HOST array list_first, the clamps of the counts
+ * and ntargets >= 1 are the redact operators'; target t is blurred by record t through scratch[t].  targets, scratch, list_first, spec and
+ * spec->classes are HOST memory and free again on return.  Enqueued on `stream` without synchronising: 2 passes launches per group of targets -- 64
+ * BGR targets or 48 NV12 targets travel as one by-value kernel argument (an NV12 target and its scratch are four planes).  Rejected before anything
+ * is launched, with the target's index in the message where there is one: everything the redact operators reject (but there is no mode and no
+ * cell), and: a radius outside 1..31, passes outside 1..3, unknown flag bits, a non-zero reserved, NULL scratch, a bad scratch descriptor, a scratch
+ * whose w x h differs from its target's, a scratch NULL where the target is not or the reverse, the overlaps above, and a target of more than 2^23
+ * blocks of 64 x 64 pixels. */
+int ffgpu_blur_boxes_bgr_dev (const void *d_records, const void *d_lists, int list_stride, const int *list_first,
+                              const ffgpu_bgr_frame  *targets, const ffgpu_bgr_frame  *scratch, int ntargets, const ffgpu_blur_spec *spec, void *stream);
+int ffgpu_blur_boxes_nv12_dev(const void *d_records, const void *d_lists, int list_stride, const int *list_first,
+                              const ffgpu_nv12_frame *targets, const ffgpu_nv12_frame *scratch, int ntargets, const ffgpu_blur_spec *spec, void *stream);
+
+#define FFGPU_BLUR_ENTRIES 0     /* entry n's full post-NMS list in targets[n]; ntargets == batch                                        */
+#define FFGPU_BLUR_MERGED  1     /* picture g's merged list (last ffgpu_exec_merge_tiles) in targets[g]; ntargets == its nimages          */
+/* On an executor: a post-pass like ffgpu_exec_redact_*, enqueued on `stream` (NULL = the executor's own; it must be the stream of the forward or
+ * merge it follows) without synchronising.  The captured graph, the records, the full lists, the ring and the host mirror are untouched.  Works on
+ * FFGPU_SPLIT2 executors.  Rejected like the operators and like the redact forms: ntargets not as stated, a `which` that is neither,
+ * FFGPU_BLUR_MERGED when no merge has run, the wrong stream.  A rejected call launches nothing and leaves the executor usable. */
+int ffgpu_exec_blur_bgr (ffgpu_exec *ex, int which, const ffgpu_bgr_frame  *targets, const ffgpu_bgr_frame  *scratch, int ntargets,
+                         const ffgpu_blur_spec *spec, void *stream);
+int ffgpu_exec_blur_nv12(ffgpu_exec *ex, int which, const ffgpu_nv12_frame *targets, const ffgpu_nv12_frame *scratch, int ntargets,
+                         const ffgpu_blur_spec *spec, void *stream);
+
 /* ---- zones and lines: identified boxes counted, flagged and gated on the device ----------------------------------------------------------------
  * What a deployment asks of a tracked stream: how many are in this region now, who entered or left it, how many crossed this line and which way,
  * who has been standing here for 200 frames -- and "redact everybody outside the ticketed area", "crop only those who crossed".  What follows is a
