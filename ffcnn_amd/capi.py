@@ -163,6 +163,26 @@ class OutlineSpec(C.Structure):      # ffgpu_outline_spec (40 bytes): which part
                 ("palette", C.c_void_p), ("npalette", C.c_int), ("reserved", C.c_int)]
 
 
+class TrailPoint(C.Structure):       # ffgpu_trail_point (12 bytes): an anchor and the frame it was seen in
+    _fields_ = [("x", C.c_int), ("y", C.c_int), ("frame", C.c_int)]
+
+
+class TrailSlot(C.Structure):        # ffgpu_trail_slot (416 bytes): one slot of a stream's trails state
+    _fields_ = [("id", C.c_int), ("last", C.c_int), ("n", C.c_int), ("head", C.c_int), ("cx", C.c_int), ("cy", C.c_int), ("reserved", C.c_int * 2),
+                ("ring", TrailPoint * 32)]
+
+
+class TrailsSpec(C.Structure):       # ffgpu_trails_spec (64 bytes): the trails pass's settings
+    _fields_ = [("capacity", C.c_int), ("max_missed", C.c_int), ("identity", C.c_int), ("flags", C.c_int), ("min_score", C.c_float), ("anchor", C.c_int),
+                ("points", C.c_int), ("min_move", C.c_int), ("thickness", C.c_int), ("coast_dash", C.c_int), ("color", C.c_ubyte * 4), ("reserved0", C.c_int),
+                ("palette", C.c_void_p), ("npalette", C.c_int), ("reserved", C.c_int)]
+
+
+TRAIL_POINTS, TRAILS_DETS, TRAILS_ROW = 32, 128, 16                                    # FFGPU_TRAIL_POINTS, FFGPU_TRAILS_DETS, _ROW
+TRAILS_COAST, TRAILS_TAPER = 1, 2                                                      # FFGPU_TRAILS_* (ffgpu_trails_spec.flags)
+TRAILS_ENTRIES, TRAILS_MERGED = 0, 1                                                   # FFGPU_TRAILS_* (ffgpu_exec_trails: which)
+TRAILS_ROW_HEADER = ("considered", "known", "fresh", "refused", "duplicate", "anonymous", "dropped", "freed", "live", "frame", "appended", "drawn", "clipped")
+TRAILS_STATE_HEADER = 16                                                               # bytes in front of a stream's slots
 SEG_ITEMS, SEG_LIMIT, OUTLINE_FIXED = 512, 1 << 20, 80                                 # FFGPU_SEG_ITEMS, _LIMIT, FFGPU_OUTLINE_FIXED
 OUTLINE_ZONES, OUTLINE_LINES, OUTLINE_TICKS, OUTLINE_MARKERS, OUTLINE_ALARM = 1, 2, 4, 8, 16   # FFGPU_OUTLINE_* (ffgpu_outline_spec.flags)
 TEXT_MAX, TEXT_ITEMS, TEXT_OPAQUE = 44, 256, 1                                         # FFGPU_TEXT_MAX, _ITEMS, FFGPU_TEXT_OPAQUE (ffgpu_text_item.flags)
@@ -197,6 +217,7 @@ assert C.sizeof(FeatureSpec) == 16 and C.sizeof(Label) == 8 and C.sizeof(Relabel
 assert C.sizeof(Gallery) == 40 and C.sizeof(RedactSpec) == 40 and C.sizeof(BlurSpec) == 40
 assert C.sizeof(TextItem) == 64 and C.sizeof(CaptionSpec) == 48
 assert C.sizeof(SegItem) == 32 and C.sizeof(OutlineSpec) == 40
+assert C.sizeof(TrailPoint) == 12 and C.sizeof(TrailSlot) == 416 and C.sizeof(TrailsSpec) == 64
 assert C.sizeof(Zone) == 96 and C.sizeof(Line) == 32 and C.sizeof(Scene) == 1040 and C.sizeof(ZonesSpec) == 32 and C.sizeof(ZoneSlot) == 64
 
 BOX_DTYPE = np.dtype([("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
@@ -207,6 +228,9 @@ CROP_DTYPE = np.dtype([("target", "<i4"), ("box", "<i4"), ("type", "<i4"), ("sco
 TRACK_DTYPE = np.dtype([("id", "<i4"), ("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"),
                         ("hits", "<i4"), ("missed", "<i4"), ("born", "<i4"), ("det", "<i4"), ("reserved", "<i4")])
 ZONE_SLOT_DTYPE = np.dtype([("id", "<i4"), ("px", "<f4"), ("py", "<f4"), ("inside", "<i4"), ("last", "<i4"), ("reserved", "<i4", (3,)), ("since", "<i4", (8,))])
+TRAIL_POINT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("frame", "<i4")])
+TRAIL_SLOT_DTYPE = np.dtype([("id", "<i4"), ("last", "<i4"), ("n", "<i4"), ("head", "<i4"), ("cx", "<i4"), ("cy", "<i4"), ("reserved", "<i4", (2,)),
+                             ("ring", TRAIL_POINT_DTYPE, (32,))])
 LABEL_DTYPE = np.dtype([("index", "<i4"), ("value", "<f4")])
 TEXT_ITEM_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("fg", "u1", (4,)), ("bg", "u1", (4,)), ("scale", "u1"), ("flags", "u1"), ("len", "u1"), ("reserved", "u1"),
                             ("text", "u1", (44,))])
@@ -239,7 +263,8 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_zones_state_bytes", "ffgpu_scene_check", "ffgpu_zones_reset_dev", "ffgpu_zones_boxes_dev", "ffgpu_exec_zones",
            "ffgpu_font_builtin", "ffgpu_draw_text_bgr_dev", "ffgpu_draw_text_nv12_dev", "ffgpu_caption_boxes_dev", "ffgpu_exec_caption_bgr", "ffgpu_exec_caption_nv12",
            "ffgpu_caption_scene_dev",
-           "ffgpu_draw_segments_bgr_dev", "ffgpu_draw_segments_nv12_dev", "ffgpu_outline_spec_check", "ffgpu_outline_scene_dev"]
+           "ffgpu_draw_segments_bgr_dev", "ffgpu_draw_segments_nv12_dev", "ffgpu_outline_spec_check", "ffgpu_outline_scene_dev",
+           "ffgpu_trails_state_bytes", "ffgpu_trails_spec_check", "ffgpu_trails_reset_dev", "ffgpu_trails_boxes_dev", "ffgpu_exec_trails"]
 # include/ffcnn_hip_diag.h (libffcnn_hip_diag.so: lab equipment, its own library)
 DIAG_EXPORTS = ["ffgpu_membench", "ffgpu_pipe_probe", "ffgpu_pipe_probe2", "ffgpu_pipe_probe3", "ffgpu_mfma_floor", "ffgpu_diag_x3_term", "ffgpu_diag_xl_op", "ffgpu_clock_probe"]
 
@@ -404,6 +429,12 @@ def lib():
     L.ffgpu_draw_segments_bgr_dev.argtypes = [vp, i, C.POINTER(BgrFrame), i, vp]
     L.ffgpu_draw_segments_nv12_dev.argtypes = [vp, i, C.POINTER(Nv12Frame), i, vp]
     L.ffgpu_outline_spec_check.argtypes = [C.POINTER(OutlineSpec)]
+    L.ffgpu_trails_state_bytes.restype = sz
+    L.ffgpu_trails_state_bytes.argtypes = [i, i]
+    L.ffgpu_trails_spec_check.argtypes = [C.POINTER(TrailsSpec)]
+    L.ffgpu_trails_reset_dev.argtypes = [vp, i, i, i, vp]
+    L.ffgpu_trails_boxes_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(i), i, C.POINTER(TrailsSpec), vp, i, vp, vp, vp, i, i, i, vp]
+    L.ffgpu_exec_trails.argtypes = [vp, i, C.POINTER(i), i, C.POINTER(TrailsSpec), vp, i, vp, vp, vp, i, i, i, vp]
     L.ffgpu_outline_scene_dev.argtypes = [vp, vp, i, i, vp, i, C.POINTER(i), i, C.POINTER(OutlineSpec), vp, i, vp]
     L.ffgpu_feature_dim.argtypes = [i, i, i, i]
     L.ffgpu_exec_feature_dim.argtypes = [vp, C.POINTER(FeatureSpec)]
@@ -788,6 +819,15 @@ class Executor:
         arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
         _check(lib().ffgpu_exec_zones(self.h, which, arr, len(streams), spec, d_scenes, d_state, nstreams, d_ids, d_events, d_out_records, d_out_lists, stream),
                "ffgpu_exec_zones")
+
+    def trails(self, streams, spec, d_state, nstreams, d_rows, d_ids=None, d_items=None, items_stride=0, first_item=0, nitems=0, which=0, stream=None):
+        """enqueue the trails pass on the last forward's boxes (which = TRAILS_ENTRIES: entry n is record n of video stream streams[n], -1: ignored) or
+        on the last merge's (TRAILS_MERGED: picture g) behind it (ffgpu_exec_trails): spec from trails_spec, d_state / d_rows / d_items the caller's
+        device buffers (trails_state_bytes; rows of TRAILS_ROW + 4 S ints; rows of items_stride segment items), d_ids the rows Executor.track wrote for
+        the same `which` (with identity ZONES_IDS)"""
+        arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+        _check(lib().ffgpu_exec_trails(self.h, which, arr, len(streams), spec, d_state, nstreams, d_ids, d_rows, d_items, items_stride, first_item, nitems, stream),
+               "ffgpu_exec_trails")
 
     def caption_bgr(self, frames, spec, d_items, items_stride, d_ids=None, d_font=None, which=0, stream=None):
         """enqueue the captions of the last forward's boxes (which = CAPTION_ENTRIES: entry n into frames[n]) or of the last merge's (CAPTION_MERGED:
@@ -1311,6 +1351,57 @@ def outline_scene_dev(d_scenes, d_state, nstreams, capacity, d_events, events_st
     arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
     _check(lib().ffgpu_outline_scene_dev(d_scenes, d_state, nstreams, capacity, d_events, events_stride, arr, len(streams), spec, d_items, items_stride, stream),
            "ffgpu_outline_scene_dev")
+
+
+def trails_spec(capacity, max_missed=0, identity=ZONES_IDS, min_score=0.0, anchor=0, points=TRAIL_POINTS, min_move=0, thickness=1, coast=False, taper=False,
+                coast_dash=0, color=(0, 0, 0), palette=None):
+    """a TrailsSpec (ffgpu_trails_spec): slots per stream, how long an unseen object is kept, where the identity comes from (ZONES_TYPE | _IDS), the
+    anchor (0: centre, 1: bottom centre), the history kept per object, the distance from which a point is appended, and how the trail is drawn: one
+    colour or a palette as draw_style takes it.  The structure keeps its palette bytes alive."""
+    sp = TrailsSpec()
+    sp.capacity, sp.max_missed, sp.identity, sp.flags = capacity, max_missed, identity, (TRAILS_COAST if coast else 0) | (TRAILS_TAPER if taper else 0)
+    sp.min_score, sp.anchor, sp.points, sp.min_move, sp.thickness, sp.coast_dash = min_score, anchor, points, min_move, thickness, coast_dash
+    sp.color[:] = (int(color[0]), int(color[1]), int(color[2]), 0)
+    if palette is not None:
+        pal = np.zeros((len(palette), 4), np.uint8)
+        if len(palette):
+            pal[:, :3] = np.asarray(palette, np.uint8).reshape(len(palette), -1)[:, :3]
+        sp._pal = pal                                           # (owned by the structure: the C side reads it during the call)
+        sp.palette = pal.ctypes.data
+        sp.npalette = len(palette)
+    return sp
+
+
+def trails_spec_check(spec):
+    """ffgpu_trails_spec_check (pure host code): raises with what is wrong with the spec"""
+    _check(lib().ffgpu_trails_spec_check(spec), "ffgpu_trails_spec_check")
+
+
+def trails_state_bytes(nstreams, capacity):
+    return lib().ffgpu_trails_state_bytes(nstreams, capacity)
+
+
+def trails_state(raw, nstreams, capacity):
+    """(headers as an int array of nstreams x 4: frames, live, reserved x 2; slots as a TRAIL_SLOT_DTYPE array of nstreams x capacity) of a state's bytes"""
+    raw = np.ascontiguousarray(raw, np.uint8).reshape(nstreams, TRAILS_STATE_HEADER + 416 * capacity)
+    return (np.ascontiguousarray(raw[:, :TRAILS_STATE_HEADER]).view("<i4"),
+            np.ascontiguousarray(raw[:, TRAILS_STATE_HEADER:]).view(TRAIL_SLOT_DTYPE).reshape(nstreams, capacity))
+
+
+def trails_reset_dev(d_state, nstreams, capacity, which_stream=-1, stream=None):
+    """ffgpu_trails_reset_dev: zero the trails state of one video stream, or of all (-1), in stream order"""
+    _check(lib().ffgpu_trails_reset_dev(d_state, nstreams, capacity, which_stream, stream), "ffgpu_trails_reset_dev")
+
+
+def trails_boxes_dev(d_records, d_lists, list_stride, streams, spec, d_state, nstreams, d_rows, d_ids=None, d_items=None, items_stride=0, first_item=0, nitems=0,
+                     list_first=None, stream=None):
+    """ffgpu_trails_boxes_dev on device records / lists: record t is the next frame of video stream streams[t] (-1: ignored); d_lists None: the
+    records' own boxes; list_first as draw_boxes_bgr_dev; d_ids: the rows track_boxes_dev wrote (with identity ZONES_IDS); d_rows: rows of
+    TRAILS_ROW + 4 S ints; d_items: rows of items_stride SEG_ITEM_DTYPE items of which first_item .. first_item + nitems - 1 are written, or None"""
+    arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+    first = None if list_first is None else (C.c_int * max(1, len(list_first)))(*[int(v) for v in list_first])
+    _check(lib().ffgpu_trails_boxes_dev(d_records, d_lists, list_stride, first, arr, len(streams), spec, d_state, nstreams, d_ids, d_rows, d_items, items_stride,
+                                        first_item, nitems, stream), "ffgpu_trails_boxes_dev")
 
 
 def feature_spec(layer=-1, pool=FFGPU.FEAT_MEAN, post=FFGPU.POST_NONE):

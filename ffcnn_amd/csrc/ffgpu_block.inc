@@ -1,5 +1,5 @@
 // ffgpu_block.inc -- the workgroup primitives of the detection tail and the post-passes (k_nms, k_merge_tiles, k_track, k_feat_pool, k_feat_post,
-// k_topk, k_match, k_match_merge, k_enroll_decide).  Device code only.  Every one of those kernels is held byte for byte to a Python restatement, so
+// k_topk, k_match, k_match_merge, k_enroll_decide, k_zones, k_trails).  Device code only.  Every one of those kernels is held byte for byte to a Python restatement, so
 // the ordering rule of a sort, the tie rule of a selection and the rounding of an overlap are part of a contract: each is written HERE, once, and what
 // differs between two kernels (array layouts, padding values, which slots start dead, how a record is written) stays at the call site.
 //
@@ -129,6 +129,59 @@ __device__ __forceinline__ int block_rank(bool flag, int *wsum, int gw, int &tot
     return before + __popcll(m & ((1ull << lane) - 1ull));
 }
 __device__ __forceinline__ int block_rank(bool flag, int *wsum, int gw) { int total; return block_rank(flag, wsum, gw, total); }
+
+// ---- identified boxes against a stream's slots (k_zones, k_trails): a workgroup of 256 lanes, lanes 0..127 the boxes, lanes 128..255 the slots.
+// The qualifying entries of a list of n, compacted in list order: put(ord, k) for the ord-th qualifying entry k while ord < cap.  Returns how many
+// qualify (uniform).  wsum: 4 slots; ends in a barrier.
+template <class Qual, class Put>
+__device__ __forceinline__ long block_consider(int n, int cap, int *wsum, Qual qual, Put put)
+{
+    long nq = 0;
+    for (int k0 = 0; k0 < n; k0 += 256) {
+        const int k = k0 + threadIdx.x;
+        const bool q = k < n && qual(k);
+        int tot;
+        const long ord = nq + block_rank(q, wsum, 4, tot);
+        if (q && ord < cap) put((int)ord, k);
+        nq += tot;
+        __syncthreads();
+    }
+    return nq;
+}
+// an earlier box of the frame has box j's identity (no early exit: the loads do not wait for each other)
+__device__ __forceinline__ bool ident_duplicate(const int *ident, int j, int id)
+{
+    bool dup = false;
+    for (int i = 0; i < j; i++) dup |= ident[i] == id;
+    return dup;
+}
+// the lowest of C slots whose id is `id`, or -1; id_of(s) reads slot s (no early exit)
+template <class IdOf>
+__device__ __forceinline__ int slot_lowest(int C, int id, IdOf id_of)
+{
+    int sl = -1;
+    for (int s = C - 1; s >= 0; s--) if (id_of(s) == id) sl = s;
+    return sl;
+}
+// Fresh owners: the r-th flagged box lane takes the r-th flagged (= free) slot lane's slot sidx.  Ranks within a wave pair: waves 0-1 the boxes, waves
+// 2-3 the slots.  Returns the slot of a flagged box lane, -1 when there is none left for it (refused), and -2 in every other lane.  wsum: 4 slots,
+// freeslot: 128; one barrier inside, and the caller's next one frees both.
+__device__ __forceinline__ int block_take_free(bool flag, bool box_lane, int sidx, int *wsum, int *freeslot)
+{
+    const int r = block_rank(flag, wsum, 2);
+    const int nfree = wsum[2] + wsum[3];
+    if (flag && !box_lane) freeslot[r] = sidx;
+    __syncthreads();
+    if (!(flag && box_lane)) return -2;
+    return r < nfree ? freeslot[r] : -1;
+}
+// this wave's count of the flagged lanes for word i of a row of counts (cnt[w]: wave w's)
+template <int ROW>
+__device__ __forceinline__ void wave_count(int (*cnt)[ROW], int i, bool flag)
+{
+    const unsigned long long m = __ballot(flag);
+    if ((threadIdx.x & (WAVE - 1)) == 0) cnt[threadIdx.x / WAVE][i] = __popcll(m);
+}
 
 // ---- reductions in one fixed order: a wave butterfly; the waves' values in LDS, then every lane combines them in wave order (red: one slot per wave;
 // free again on return).  The order of the additions is written here and nowhere else; the one arithmetic operation, add_f32, carries the pragma.

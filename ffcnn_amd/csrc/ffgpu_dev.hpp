@@ -9,6 +9,7 @@
 #include "ffgpu_zones_host.hpp"
 #include "ffgpu_text_host.hpp"
 #include "ffgpu_lines_host.hpp"
+#include "ffgpu_trails_host.hpp"
 
 #define FFGPU_CHECK(expr)                                                                   \
     do {                                                                                    \
@@ -233,6 +234,10 @@ int ffgpu_launch_caption_boxes(const DetSource &src, int ntargets, const Caption
 
 // outlines (ffgpu_lines.inc): the segment rasteriser's launches; the checks are host code with no HIP in it (ffgpu_lines_host.hpp)
 int ffgpu_launch_draw_segments(bool nv12, const void *d_items, int items_stride, const std::vector<DrawTarget> &targets, hipStream_t s);
+
+// track trails (ffgpu_trails.inc): the launches; the checks both entry points share are host code with no HIP in it (ffgpu_trails_host.hpp)
+int ffgpu_launch_trails(const DetSource &src, const int *streams, int ntargets, const TrailsPlan &pl, void *d_state, const void *d_ids, void *d_rows, void *d_items,
+                        int items_stride, int first_item, int nitems, hipStream_t s);
 
 // the crops classified (ffgpu_feature.inc): the checks both entry points share, and the launches.  Features: frame n of the tensor is frame n % pn of
 // parts[n / pn], a CNHW tensor of pn frames (a split executor has one part per chain; at most 8).

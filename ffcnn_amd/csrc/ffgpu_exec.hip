@@ -1486,6 +1486,25 @@ extern "C" int ffgpu_exec_zones(ffgpu_exec *ex, int which, const int *streams, i
     return ffgpu_launch_zones(src, streams, ntargets, *spec, d_scenes, d_state, d_ids, d_events, d_out_records, d_out_lists, s);
 }
 
+// -------------------------------------------------------------------------- track trails (include/ffcnn_hip.h; kernel: ffgpu_trails.inc)
+// A post-pass like the zones pass, on the stream of the forward or merge it follows: reads the records and full lists (per entry, or the merged ones)
+// and the caller's ids, writes the caller's state, rows and items and nothing of the executor's.
+extern "C" int ffgpu_exec_trails(ffgpu_exec *ex, int which, const int *streams, int ntargets, const ffgpu_trails_spec *spec, void *d_state, int nstreams,
+                                 const void *d_ids, void *d_rows, void *d_items, int items_stride, int first_item, int nitems, void *stream)
+{
+    const char *const what = "exec_trails";
+    if (!exec_ok(ex, what)) return -1;
+    TrailsPlan pl;
+    if (ffgpu_trails_args_check(what, streams, ntargets, spec, d_state, nstreams, d_ids, d_rows, d_items, items_stride, first_item, nitems, pl)) return -1;
+    DetSource src;
+    hipStream_t s;
+    if (exec_source(ex, what, "TRAILS", "trails pass", which, ntargets, stream, src, &s)) return -1;
+    // the stride is also the pitch of the ids and the rows: a list too long is refused, not clamped (as the tracker)
+    if (src.longest > (1 << 24)) { ffgpu_set_error("%s: lists of up to %lld boxes are too long", what, src.longest); return -1; }
+    src.stride = (int)src.longest;
+    return ffgpu_launch_trails(src, streams, ntargets, pl, d_state, d_ids, d_rows, d_items, items_stride, first_item, nitems, s);
+}
+
 // -------------------------------------------------------------------------- captions (include/ffcnn_hip.h; kernels: ffgpu_text.inc)
 // A post-pass like the draw, on the stream of the forward or merge it follows, in two launches: the items composed from the records and full lists (per
 // entry, or the merged ones) into the caller's d_items, then rasterised into the caller's frames.  Nothing of the executor's is written.

@@ -73,11 +73,7 @@ __device__ __forceinline__ int zones_cross(const ffgpu_line &l, float p0x, float
     return s1 ? 1 : 2;
 }
 // this wave's count of the flagged lanes for word i of the event row
-__device__ __forceinline__ void zones_count(int (*cnt)[FFGPU_ZONES_ROW], int i, bool flag)
-{
-    const unsigned long long m = __ballot(flag);
-    if ((threadIdx.x & (WAVE - 1)) == 0) cnt[threadIdx.x / WAVE][i] = __popcll(m);
-}
+__device__ __forceinline__ void zones_count(int (*cnt)[FFGPU_ZONES_ROW], int i, bool flag) { wave_count(cnt, i, flag); }
 
 // grid = groups of the launch, 256 lanes.  Counts are clamped to [0, stride] as the draw kernel clamps them.
 __global__ void __launch_bounds__(256) k_zones(ZonesArgs a, const ffgpu_frame_dets *recs, const BBOX *lists, int stride, const unsigned char *scenes,
@@ -132,16 +128,8 @@ __global__ void __launch_bounds__(256) k_zones(ZonesArgs a, const ffgpu_frame_de
         if (tid < FFGPU_ZONES_DETS) L.named[tid] = 0;
 
         // 1. the considered boxes, in list order
-        long nq = 0;                                                                  // qualifying boxes so far (uniform)
-        for (int k0 = 0; k0 < n; k0 += 256) {
-            const int k = k0 + tid;
-            const bool q = k < n && list[k].score >= min_score;
-            int tot;
-            const long ord = nq + block_rank(q, L.wsum, 4, tot);
-            if (q && ord < FFGPU_ZONES_DETS) { track_put(&L.det[ord], list[k].type, list[k]); L.didx[ord] = k; }
-            nq += tot;
-            __syncthreads();
-        }
+        const long nq = block_consider(n, FFGPU_ZONES_DETS, L.wsum, [&](int k) { return list[k].score >= min_score; },      // the qualifying boxes (uniform)
+                                       [&](int ord, int k) { track_put(&L.det[ord], list[k].type, list[k]); L.didx[ord] = k; });
         const int nd = (int)min(nq, (long)FFGPU_ZONES_DETS), dropped = (int)min(nq - nd, 0x7fffffffL);
 
         // 2. geometry.  A lane owns its box: anchor, identity, the lines that admit it.  The inside mask is found by eight consecutive lanes per box,
@@ -177,13 +165,9 @@ __global__ void __launch_bounds__(256) k_zones(ZonesArgs a, const ffgpu_frame_de
         // 3. owners; 4. known owners: the lowest slot with the identity -- no other owner has it, so the lane updates the slot in place (no lane writes
         // an id before the next barrier)
         const bool anon = box && ident <= 0;
-        bool dup = false;
-        if (box && !anon)
-            for (int j = 0; j < tid; j++) dup |= L.ident[j] == ident;                 // (no early exit: the loads do not wait for each other)
+        const bool dup = box && !anon && ident_duplicate(L.ident, tid, ident);
         const bool owner = box && !anon && !dup;
-        int sl = -1;
-        if (owner)
-            for (int s = C - 1; s >= 0; s--) if (slot[s].id == ident) sl = s;         // (the lowest; no early exit)
+        const int sl = owner ? slot_lowest(C, ident, [&](int s) { return slot[s].id; }) : -1;
         const bool known = sl >= 0;
         int entered = 0, left = 0, loit = 0, fwd = 0, back = 0;
         if (known) {
@@ -222,13 +206,10 @@ __global__ void __launch_bounds__(256) k_zones(ZonesArgs a, const ffgpu_frame_de
         const bool flag = tid < FFGPU_ZONES_DETS ? owner && !known : slane && slot[sidx].id == 0;
         bool fresh = false, refused = false;
         {
-            const int r = block_rank(flag, L.wsum, 2);
-            const int nfree = L.wsum[2] + L.wsum[3];
-            if (flag && tid >= FFGPU_ZONES_DETS) L.freeslot[r] = sidx;
-            __syncthreads();
-            if (flag && tid < FFGPU_ZONES_DETS) {
-                if (r < nfree) {
-                    ffgpu_zone_slot &q = slot[L.freeslot[r]];
+            const int fs = block_take_free(flag, tid < FFGPU_ZONES_DETS, sidx, L.wsum, L.freeslot);
+            if (fs > -2) {
+                if (fs >= 0) {
+                    ffgpu_zone_slot &q = slot[fs];
                     q.id = ident; q.px = px; q.py = py; q.inside = ins; q.last = frames; q.reserved[0] = q.reserved[1] = q.reserved[2] = 0;
                     for (int z = 0; z < FFGPU_SCENE_ZONES; z++) q.since[z] = ((ins >> z) & 1) ? frames : 0;
                     fresh = true;

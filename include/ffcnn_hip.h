@@ -1303,6 +1303,122 @@ int ffgpu_outline_spec_check(const ffgpu_outline_spec *spec);
 int ffgpu_outline_scene_dev(const void *d_scenes, const void *d_state, int nstreams, int capacity, const void *d_events, int events_stride,
                             const int *streams, int ntargets, const ffgpu_outline_spec *spec, void *d_items, int items_stride, void *stream);
 
+/* ---- track trails: where an identified object has been, kept per stream on the device and composed into segment items -------------------------
+ * The zones state holds one anchor per slot, the last.  What follows keeps a HISTORY of anchors per identity and per video stream -- a ring of up to
+ * FFGPU_TRAIL_POINTS points behind every slot -- and has two products: TRAIL ITEMS, ffgpu_seg_items the segment primitive above draws, and a MOTION
+ * ROW per box (displacement and frame span over the kept history) from which speed and heading follow.  It is a stateful per-stream pass in the shape
+ * of ffgpu_zones_boxes_dev, and a pure function of its inputs: the same bytes on every run (tests/trails/trailref.py restates it in numpy).
+ *
+ * State, in the caller's device memory (16-byte aligned, ffgpu_trails_state_bytes(nstreams, capacity) bytes; all-zero is the valid empty state, so
+ * hipMemsetAsync or ffgpu_trails_reset_dev initialises it): per stream a 16-byte header { int frames, live, reserved[2]; } and `capacity` slots
+ * ffgpu_trail_slot of 416 bytes.  id == 0 is a free slot and a free slot is all zero, all 416 bytes.  The LIVE POINTS of a slot are ring[(head + j) % 32]
+ * for j = 0 .. n - 1, j = 0 the oldest and j = n - 1 the NEWEST; ring entries outside that window keep whatever they held.  Frame numbers are 32-bit
+ * and wrap; differences of frame numbers are taken modulo 2^32 and read as signed.  The kernel is total over any state bytes: wherever a slot's n and
+ * head are READ, n is clamped to 0..points and head is taken modulo 32 (the non-negative remainder); a known owner's slot gets the clamped values back.
+ *
+ * One frame of one stream, in this order (streams, ntargets, time order and -1 entries: exactly as ffgpu_zones_boxes_dev; frame = `frames` before 7):
+ *   1. Considered boxes.  The record's list is walked in list order (d_lists, list_stride, list_first and the clamps of the draw operators).  A box is
+ *      CONSIDERED when score >= min_score (a NaN score never is), until FFGPU_TRAILS_DETS boxes are; further qualifying boxes are counted in `dropped`.
+ *   2. Anchor.  In fp32, not contracted, as the zones contract: px = (x1 + x2) * 0.5f; py = anchor ? y2 : (y1 + y2) * 0.5f.  Each coordinate is then
+ *      converted to int by the draw contract's rule (toward zero, saturating, NaN -> 0): A = (A.x, A.y).  Everything behind this point is integer.
+ *   3. Owners.  The identity is the box's type (FFGPU_ZONES_TYPE) or d_ids row t, entry 8 + k for box k of the list (FFGPU_ZONES_IDS; rows of 8 + S
+ *      ints).  An identity <= 0 is ANONYMOUS.  A considered box whose identity is > 0 OWNS it, unless an earlier considered box of the frame has the
+ *      same identity: then it is a DUPLICATE.
+ *   4. Known owners: the identity is the id of a slot (of the lowest such slot).  With N the slot's newest live point, the anchor is APPENDED when
+ *      max(|A.x - N.x|, |A.y - N.y|) >= min_move, in 64-bit integers (min_move 0: always), and also when the slot has no live point (n == 0).
+ *      Append with n == points: head = (head + 1) % 32; otherwise n += 1; in both cases ring[(head + n - 1) % 32] = { A.x, A.y, frame }.
+ *      cx, cy = A and last = frame are set whether or not a point was appended.
+ *   5. Frees.  An occupied slot no owner of this frame named, with frame - last > max_missed, is zeroed, all 416 bytes.
+ *   6. Fresh owners (owners that are not known) take the lowest free slots (id == 0) in list order, after the frees: id = the identity, last = frame,
+ *      n = 1, head = 0, ring[0] = { A.x, A.y, frame }, cx, cy = A; every other byte of the slot is zero.  An owner that finds no free slot is REFUSED.
+ *   7. live = the occupied slots; frames += 1 -- also for a frame without boxes.
+ *
+ * Outputs per record t.  S = list_stride, or FFGPU_MAX_DET when d_lists is NULL.
+ *   d_rows (required): row t of FFGPU_TRAILS_ROW + 4 S ints, every byte written, for streams[t] == -1 as zero: 16 ints { considered, known, fresh,
+ *     refused, duplicate, anonymous, dropped, freed, live, frame, appended, drawn, clipped, 0, 0, 0 } (appended: the known owners of 4. that appended a
+ *     point), then four ints per list box k (at FFGPU_TRAILS_ROW + 4 k): the MOTION ROW { n, dx, dy, df } of a box that is a known or fresh owner, zero
+ *     for every other box.  n = the slot's live points after this frame; with O the slot's oldest live point, dx = cx - O.x and dy = cy - O.y, taken in
+ *     64 bits and saturated to int; df = frame - O.frame, modulo 2^32 as signed.
+ *   d_items (may be NULL: then items_stride, first_item and nitems must be 0): ffgpu_seg_items, 4-byte aligned, row t of items_stride items
+ *     (1..FFGPU_SEG_ITEMS).  The call writes exactly the slots first_item .. first_item + nitems - 1 of row t (first_item >= 0, nitems >= 1,
+ *     first_item + nitems <= items_stride): every byte of those slots and no other byte, so ffgpu_outline_scene_dev may write the row first and the
+ *     trails the slots behind its markers.  THE ROW SHOWS THE STATE RIGHT AFTER RECORD t: several records of one stream in one call each get their
+ *     own trail.  With P = points: a slot is DRAWN when id != 0, n >= 1 and (last == frame or FFGPU_TRAILS_COAST is set).  The k-th drawn slot in slot
+ *     order owns the REGION first_item + k P .. first_item + k P + P - 1 while (k + 1) P <= nitems; further drawn slots get nothing and are counted in
+ *     `clipped`; `drawn` counts the slots that got a region (with NULL items every drawn slot is clipped).
+ *       Region item j < P - 1: the segment from live point j to live point j + 1 (0 = the oldest) when j + 1 < n, otherwise 32 zero bytes.
+ *       Region item P - 1, the TIP: the segment from the newest live point to (cx, cy).
+ *       Colour = palette entry id mod npalette (the non-negative remainder), or `color`; byte 3, `flags` and the reserved fields are 0.
+ *       dash = coast_dash when last != frame, otherwise 0.  thickness T = the spec's; with FFGPU_TRAILS_TAPER the tip keeps T and ring item j gets
+ *       1 + ((T - 1) * (j + 1)) / n, the division an integer one.
+ *     Every slot of the range outside a region is 32 zero bytes; for streams[t] == -1 all of them are.
+ * Redact, then draw, then outline, then trails, then caption. */
+#define FFGPU_TRAIL_POINTS   32   /* ring entries per slot */
+#define FFGPU_TRAILS_DETS    128  /* considered boxes per frame at most; also the largest capacity */
+#define FFGPU_TRAILS_ROW     16   /* header ints of a trail row in front of the boxes' motion rows */
+#define FFGPU_TRAILS_COAST   1    /* flags: a slot not seen in this frame is drawn too, dashed with coast_dash */
+#define FFGPU_TRAILS_TAPER   2    /* flags: the trail thins out toward its oldest point */
+typedef struct { int x, y, frame; } ffgpu_trail_point;   /* 12 bytes */
+typedef struct {
+    int id;                        /* 0: a free slot (all zero, all 416 bytes) */
+    int last;                      /* the stream's frame number when the object was last seen */
+    int n;                         /* live points, 0..points */
+    int head;                      /* ring index of the oldest live point */
+    int cx, cy;                    /* the anchor when last seen, converted */
+    int reserved[2];               /* 0 */
+    ffgpu_trail_point ring[FFGPU_TRAIL_POINTS];
+} ffgpu_trail_slot;                /* 416 bytes: id 0, last 4, n 8, head 12, cx 16, cy 20, reserved 24, ring 32; behind each stream's 16-byte header */
+typedef struct {
+    int   capacity;                /* 1..128: slots per stream (as the state was sized) */
+    int   max_missed;              /* 0..2^20: an object survives this many consecutive frames without being seen */
+    int   identity;                /* FFGPU_ZONES_TYPE | _IDS; _NONE is rejected: there is nobody to remember */
+    int   flags;                   /* 0 | FFGPU_TRAILS_COAST | FFGPU_TRAILS_TAPER; any other bit is rejected */
+    float min_score;               /* finite, in [0, 1]: a box is considered from this score on */
+    int   anchor;                  /* 0: the box's centre; 1: its bottom centre (the zones contract's anchor) */
+    int   points;                  /* 2..32: the history kept per object */
+    int   min_move;                /* 0..2^20: a point is appended from this Chebyshev distance to the newest one on */
+    int   thickness;               /* 1..8 */
+    int   coast_dash;              /* 0..6: the dash of a slot not seen in this frame */
+    unsigned char color[4];        /* the colour when palette is NULL */
+    int   reserved0;               /* 0 */
+    const unsigned char *palette;  /* HOST, npalette x 4 bytes, or NULL: exactly ffgpu_outline_spec's */
+    int   npalette;                /* 0 with a NULL palette, else 1..256 */
+    int   reserved;                /* 0 */
+} ffgpu_trails_spec;               /* 64 bytes: capacity 0, max_missed 4, identity 8, flags 12, min_score 16, anchor 20, points 24, min_move 28, */
+                                   /* thickness 32, coast_dash 36, color 40, reserved0 44, palette 48, npalette 56, reserved 60 */
+
+/* pure host code: the bytes of the state of nstreams (1..65536) streams of capacity (1..128) slots; 0 for arguments outside their ranges */
+size_t ffgpu_trails_state_bytes(int nstreams, int capacity);
+/* pure host code: 0, or -1 with the message in ffgpu_last_error */
+int ffgpu_trails_spec_check(const ffgpu_trails_spec *spec);
+/* zeroes the state of one stream, or of all with which_stream == -1, in stream order (a memset; no kernel) */
+int ffgpu_trails_reset_dev(void *d_state, int nstreams, int capacity, int which_stream, void *stream);
+
+/* The operator, on device records and lists with no executor.  d_records, d_lists, list_stride and the HOST array list_first are the draw operators'.
+ * One workgroup per video stream walks that stream's records of the call serially, the slots' 32-byte heads in LDS and the rings in global memory;
+ * streams, list_first and spec (with its palette) are HOST memory and free again on return; the tables and the palette travel as kernel arguments,
+ * 64 records per launch, the launches of one call in order on `stream`, the state passing through memory between them.  Enqueued without
+ * synchronising.  Rejected before anything is launched, with the entry's index in the message where there is one: the reasons of
+ * ffgpu_zones_boxes_dev that apply (NULL records, streams, spec, state or rows, ntargets < 1, nstreams outside 1..65536, a stream index outside
+ * -1..nstreams-1, a state that is not 16-byte aligned, a bad list_stride, a negative list start), a spec field outside its range, identity
+ * FFGPU_ZONES_NONE, unknown flag bits, a reserved field that is not 0, npalette not matching palette, d_ids (required exactly when identity ==
+ * FFGPU_ZONES_IDS: NULL then, or given otherwise, is rejected), and the items: NULL with items_stride, first_item or nitems not 0; otherwise not
+ * 4-byte aligned, items_stride outside 1..512, first_item < 0, nitems < 1, first_item + nitems > items_stride.  A rejected call leaves the state as
+ * it was. */
+int ffgpu_trails_boxes_dev(const void *d_records, const void *d_lists, int list_stride, const int *list_first, const int *streams, int ntargets,
+                           const ffgpu_trails_spec *spec, void *d_state, int nstreams, const void *d_ids, void *d_rows, void *d_items, int items_stride,
+                           int first_item, int nitems, void *stream);
+
+#define FFGPU_TRAILS_ENTRIES 0   /* entry n's full post-NMS list is record n; ntargets == batch; S as FFGPU_TRACK_ENTRIES                          */
+#define FFGPU_TRAILS_MERGED  1   /* picture g's merged list (last ffgpu_exec_merge_tiles) is record g; ntargets == its nimages; S as FFGPU_TRACK_MERGED */
+/* On an executor: a post-pass like ffgpu_exec_zones, with its stream, FFGPU_SPLIT2 and FFGPU_TRAILS_MERGED rules, enqueued on `stream` (NULL = the
+ * executor's own; it must be the stream of the forward or merge it follows) without synchronising.  The captured graph, the records, the full lists,
+ * the ring and the host mirror are untouched; state, rows and items are the caller's, and d_ids is what ffgpu_exec_track wrote for the same `which`.
+ * Rejected like the operator, and: ntargets not as stated, a `which` that is neither, FFGPU_TRAILS_MERGED when no merge has run, the wrong stream.  A
+ * rejected call leaves the state and the executor usable. */
+int ffgpu_exec_trails(ffgpu_exec *ex, int which, const int *streams, int ntargets, const ffgpu_trails_spec *spec, void *d_state, int nstreams,
+                      const void *d_ids, void *d_rows, void *d_items, int items_stride, int first_item, int nitems, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
