@@ -178,6 +178,23 @@ class TrailsSpec(C.Structure):       # ffgpu_trails_spec (64 bytes): the trails 
                 ("palette", C.c_void_p), ("npalette", C.c_int), ("reserved", C.c_int)]
 
 
+class HeatSpec(C.Structure):         # ffgpu_heat_spec (56 bytes): the heat accumulate pass's settings
+    _fields_ = [("gw", C.c_int), ("gh", C.c_int), ("cell_log2", C.c_int), ("mode", C.c_int), ("flags", C.c_int), ("anchor", C.c_int), ("spread", C.c_int),
+                ("gain", C.c_int), ("decay_shift", C.c_int), ("min_score", C.c_float), ("classes", C.c_void_p), ("nclasses", C.c_int), ("reserved", C.c_int)]
+
+
+class HeatBlendSpec(C.Structure):    # ffgpu_heat_blend_spec (48 bytes): how a stream's grid is shown in its frames
+    _fields_ = [("gw", C.c_int), ("gh", C.c_int), ("cell_log2", C.c_int), ("full_scale", C.c_int), ("floor", C.c_int), ("opacity", C.c_int),
+                ("sampling", C.c_int), ("flags", C.c_int), ("palette", C.c_void_p), ("reserved", C.c_int * 2)]
+
+
+HEAT_MAX, HEAT_DETS, HEAT_ROW = 2 ** 31 - 1, 128, 8                                    # FFGPU_HEAT_MAX, _DETS, _ROW
+HEAT_ANCHOR, HEAT_BOX = 0, 1                                                           # FFGPU_HEAT_* (ffgpu_heat_spec.mode)
+HEAT_NEAREST, HEAT_SMOOTH = 0, 1                                                       # FFGPU_HEAT_* (ffgpu_heat_blend_spec.sampling)
+HEAT_RAMP_ALPHA = 1                                                                    # FFGPU_HEAT_RAMP_ALPHA (ffgpu_heat_blend_spec.flags)
+HEAT_ENTRIES, HEAT_MERGED = 0, 1                                                       # FFGPU_HEAT_* (ffgpu_exec_heat: which)
+HEAT_ROW_HEADER = ("considered", "dropped", "outside", "frame", "peak", "saturated")
+HEAT_STATE_HEADER = 16                                                                 # bytes in front of a stream's cells
 TRAIL_POINTS, TRAILS_DETS, TRAILS_ROW = 32, 128, 16                                    # FFGPU_TRAIL_POINTS, FFGPU_TRAILS_DETS, _ROW
 TRAILS_COAST, TRAILS_TAPER = 1, 2                                                      # FFGPU_TRAILS_* (ffgpu_trails_spec.flags)
 TRAILS_ENTRIES, TRAILS_MERGED = 0, 1                                                   # FFGPU_TRAILS_* (ffgpu_exec_trails: which)
@@ -218,6 +235,7 @@ assert C.sizeof(Gallery) == 40 and C.sizeof(RedactSpec) == 40 and C.sizeof(BlurS
 assert C.sizeof(TextItem) == 64 and C.sizeof(CaptionSpec) == 48
 assert C.sizeof(SegItem) == 32 and C.sizeof(OutlineSpec) == 40
 assert C.sizeof(TrailPoint) == 12 and C.sizeof(TrailSlot) == 416 and C.sizeof(TrailsSpec) == 64
+assert C.sizeof(HeatSpec) == 56 and C.sizeof(HeatBlendSpec) == 48
 assert C.sizeof(Zone) == 96 and C.sizeof(Line) == 32 and C.sizeof(Scene) == 1040 and C.sizeof(ZonesSpec) == 32 and C.sizeof(ZoneSlot) == 64
 
 BOX_DTYPE = np.dtype([("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
@@ -264,7 +282,9 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_font_builtin", "ffgpu_draw_text_bgr_dev", "ffgpu_draw_text_nv12_dev", "ffgpu_caption_boxes_dev", "ffgpu_exec_caption_bgr", "ffgpu_exec_caption_nv12",
            "ffgpu_caption_scene_dev",
            "ffgpu_draw_segments_bgr_dev", "ffgpu_draw_segments_nv12_dev", "ffgpu_outline_spec_check", "ffgpu_outline_scene_dev",
-           "ffgpu_trails_state_bytes", "ffgpu_trails_spec_check", "ffgpu_trails_reset_dev", "ffgpu_trails_boxes_dev", "ffgpu_exec_trails"]
+           "ffgpu_trails_state_bytes", "ffgpu_trails_spec_check", "ffgpu_trails_reset_dev", "ffgpu_trails_boxes_dev", "ffgpu_exec_trails",
+           "ffgpu_heat_state_bytes", "ffgpu_heat_spec_check", "ffgpu_heat_blend_spec_check", "ffgpu_heat_palette", "ffgpu_heat_reset_dev", "ffgpu_heat_boxes_dev",
+           "ffgpu_exec_heat", "ffgpu_heat_blend_bgr_dev", "ffgpu_heat_blend_nv12_dev"]
 # include/ffcnn_hip_diag.h (libffcnn_hip_diag.so: lab equipment, its own library)
 DIAG_EXPORTS = ["ffgpu_membench", "ffgpu_pipe_probe", "ffgpu_pipe_probe2", "ffgpu_pipe_probe3", "ffgpu_mfma_floor", "ffgpu_diag_x3_term", "ffgpu_diag_xl_op", "ffgpu_clock_probe"]
 
@@ -435,6 +455,16 @@ def lib():
     L.ffgpu_trails_reset_dev.argtypes = [vp, i, i, i, vp]
     L.ffgpu_trails_boxes_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(i), i, C.POINTER(TrailsSpec), vp, i, vp, vp, vp, i, i, i, vp]
     L.ffgpu_exec_trails.argtypes = [vp, i, C.POINTER(i), i, C.POINTER(TrailsSpec), vp, i, vp, vp, vp, i, i, i, vp]
+    L.ffgpu_heat_state_bytes.restype = sz
+    L.ffgpu_heat_state_bytes.argtypes = [i, i, i]
+    L.ffgpu_heat_spec_check.argtypes = [C.POINTER(HeatSpec)]
+    L.ffgpu_heat_blend_spec_check.argtypes = [C.POINTER(HeatBlendSpec)]
+    L.ffgpu_heat_palette.argtypes = [i, vp]
+    L.ffgpu_heat_reset_dev.argtypes = [vp, i, i, i, i, vp]
+    L.ffgpu_heat_boxes_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(i), i, C.POINTER(HeatSpec), vp, i, vp, vp]
+    L.ffgpu_exec_heat.argtypes = [vp, i, C.POINTER(i), i, C.POINTER(HeatSpec), vp, i, vp, vp]
+    L.ffgpu_heat_blend_bgr_dev.argtypes = [vp, i, C.POINTER(i), C.POINTER(BgrFrame), i, C.POINTER(HeatBlendSpec), vp]
+    L.ffgpu_heat_blend_nv12_dev.argtypes = [vp, i, C.POINTER(i), C.POINTER(Nv12Frame), i, C.POINTER(HeatBlendSpec), vp]
     L.ffgpu_outline_scene_dev.argtypes = [vp, vp, i, i, vp, i, C.POINTER(i), i, C.POINTER(OutlineSpec), vp, i, vp]
     L.ffgpu_feature_dim.argtypes = [i, i, i, i]
     L.ffgpu_exec_feature_dim.argtypes = [vp, C.POINTER(FeatureSpec)]
@@ -819,6 +849,13 @@ class Executor:
         arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
         _check(lib().ffgpu_exec_zones(self.h, which, arr, len(streams), spec, d_scenes, d_state, nstreams, d_ids, d_events, d_out_records, d_out_lists, stream),
                "ffgpu_exec_zones")
+
+    def heat(self, streams, spec, d_state, nstreams, d_rows, which=0, stream=None):
+        """enqueue the heat accumulate pass on the last forward's boxes (which = HEAT_ENTRIES: entry n is record n of video stream streams[n], -1:
+        ignored) or on the last merge's (HEAT_MERGED: picture g) behind it (ffgpu_exec_heat): spec from heat_spec, d_state / d_rows the caller's device
+        buffers (heat_state_bytes; rows of HEAT_ROW ints).  heat_blend_bgr_dev / _nv12_dev show the state in the frames."""
+        arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+        _check(lib().ffgpu_exec_heat(self.h, which, arr, len(streams), spec, d_state, nstreams, d_rows, stream), "ffgpu_exec_heat")
 
     def trails(self, streams, spec, d_state, nstreams, d_rows, d_ids=None, d_items=None, items_stride=0, first_item=0, nitems=0, which=0, stream=None):
         """enqueue the trails pass on the last forward's boxes (which = TRAILS_ENTRIES: entry n is record n of video stream streams[n], -1: ignored) or
@@ -1402,6 +1439,90 @@ def trails_boxes_dev(d_records, d_lists, list_stride, streams, spec, d_state, ns
     first = None if list_first is None else (C.c_int * max(1, len(list_first)))(*[int(v) for v in list_first])
     _check(lib().ffgpu_trails_boxes_dev(d_records, d_lists, list_stride, first, arr, len(streams), spec, d_state, nstreams, d_ids, d_rows, d_items, items_stride,
                                         first_item, nitems, stream), "ffgpu_trails_boxes_dev")
+
+
+def heat_spec(gw, gh, cell_log2, mode=HEAT_ANCHOR, anchor=0, spread=0, gain=1, decay_shift=0, min_score=0.0, classes=None):
+    """a HeatSpec (ffgpu_heat_spec): the grid (gw x gh cells of 1 << cell_log2 pixels), the footprint of a box (HEAT_ANCHOR: the cells within `spread`
+    of the anchor's, 0: centre, 1: bottom centre; HEAT_BOX: every cell the box touches), what a box adds, the decay per frame (a shift, 0: none) and
+    which boxes qualify (min_score, classes as redact_spec).  The structure keeps its class bytes alive."""
+    sp = HeatSpec()
+    sp.gw, sp.gh, sp.cell_log2, sp.mode, sp.anchor, sp.spread, sp.gain, sp.decay_shift, sp.min_score = gw, gh, cell_log2, mode, anchor, spread, gain, decay_shift, min_score
+    if classes is not None:
+        cls = np.ascontiguousarray(np.asarray(classes) != 0, np.uint8) if len(classes) else np.zeros(1, np.uint8)
+        sp._cls = cls                                           # (owned by the structure: the C side reads it during the call)
+        sp.classes = cls.ctypes.data
+        sp.nclasses = len(classes)
+    return sp
+
+
+def heat_blend_spec(gw, gh, cell_log2, full_scale=0, floor=0, opacity=128, smooth=False, ramp_alpha=False, palette=None):
+    """a HeatBlendSpec (ffgpu_heat_blend_spec): the grid's geometry, the cell value shown as level 255 (0: the stream's peak), the level below which
+    a pixel stays, the opacity, the sampling and a palette of 256 colours (B G R for BGR targets, Y U V for NV12 ones; a (256, 3 | 4) uint8 array) or
+    None: the built-in one.  The structure keeps its palette bytes alive."""
+    sp = HeatBlendSpec()
+    sp.gw, sp.gh, sp.cell_log2, sp.full_scale, sp.floor, sp.opacity = gw, gh, cell_log2, full_scale, floor, opacity
+    sp.sampling, sp.flags = HEAT_SMOOTH if smooth else HEAT_NEAREST, HEAT_RAMP_ALPHA if ramp_alpha else 0
+    if palette is not None:
+        pal = np.zeros((256, 4), np.uint8)
+        pal[:, :3] = np.asarray(palette, np.uint8).reshape(256, -1)[:, :3]
+        sp._pal = pal
+        sp.palette = pal.ctypes.data
+    return sp
+
+
+def heat_spec_check(spec):
+    """ffgpu_heat_spec_check (pure host code): raises with what is wrong with the spec"""
+    _check(lib().ffgpu_heat_spec_check(spec), "ffgpu_heat_spec_check")
+
+
+def heat_blend_spec_check(spec):
+    """ffgpu_heat_blend_spec_check (pure host code): raises with what is wrong with the spec"""
+    _check(lib().ffgpu_heat_blend_spec_check(spec), "ffgpu_heat_blend_spec_check")
+
+
+def heat_palette(nv12=False):
+    """ffgpu_heat_palette (pure host code): the built-in palette as a (256, 4) uint8 array, B G R 0 or Y U V 0"""
+    out = np.zeros((256, 4), np.uint8)
+    _check(lib().ffgpu_heat_palette(1 if nv12 else 0, out.ctypes.data), "ffgpu_heat_palette")
+    return out
+
+
+def heat_state_bytes(nstreams, gw, gh):
+    return lib().ffgpu_heat_state_bytes(nstreams, gw, gh)
+
+
+def heat_state(raw, nstreams, gw, gh):
+    """(headers as a uint32 array of nstreams x 4: frames, peak, reserved x 2; cells as a uint32 array of nstreams x gh x gw) of a state's bytes"""
+    one = (HEAT_STATE_HEADER + 4 * gw * gh + 15) & ~15
+    raw = np.ascontiguousarray(raw, np.uint8).reshape(nstreams, one)
+    return (np.ascontiguousarray(raw[:, :HEAT_STATE_HEADER]).view("<u4"),
+            np.ascontiguousarray(raw[:, HEAT_STATE_HEADER:HEAT_STATE_HEADER + 4 * gw * gh]).view("<u4").reshape(nstreams, gh, gw))
+
+
+def heat_reset_dev(d_state, nstreams, gw, gh, which_stream=-1, stream=None):
+    """ffgpu_heat_reset_dev: zero the heat state of one video stream, or of all (-1), in stream order"""
+    _check(lib().ffgpu_heat_reset_dev(d_state, nstreams, gw, gh, which_stream, stream), "ffgpu_heat_reset_dev")
+
+
+def heat_boxes_dev(d_records, d_lists, list_stride, streams, spec, d_state, nstreams, d_rows, list_first=None, stream=None):
+    """ffgpu_heat_boxes_dev on device records / lists: record t is the next frame of video stream streams[t] (-1: ignored); d_lists None: the
+    records' own boxes; list_first as draw_boxes_bgr_dev; d_rows: rows of HEAT_ROW ints"""
+    arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+    first = None if list_first is None else (C.c_int * max(1, len(list_first)))(*[int(v) for v in list_first])
+    _check(lib().ffgpu_heat_boxes_dev(d_records, d_lists, list_stride, first, arr, len(streams), spec, d_state, nstreams, d_rows, stream), "ffgpu_heat_boxes_dev")
+
+
+def heat_blend_bgr_dev(d_state, nstreams, streams, frames, spec, stream=None):
+    """ffgpu_heat_blend_bgr_dev: the grid of video stream streams[t] (-1: untouched) blended into frames[t] (what bgr_frame_desc accepts, or None:
+    skipped) as it is when the launch runs"""
+    arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+    _check(lib().ffgpu_heat_blend_bgr_dev(d_state, nstreams, arr, bgr_frame_table(frames), len(frames), spec, stream), "ffgpu_heat_blend_bgr_dev")
+
+
+def heat_blend_nv12_dev(d_state, nstreams, streams, frames, spec, stream=None):
+    """ffgpu_heat_blend_nv12_dev: the same in NV12 frames (what nv12_frame_desc accepts, or None: skipped)"""
+    arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+    _check(lib().ffgpu_heat_blend_nv12_dev(d_state, nstreams, arr, nv12_frame_table(frames), len(frames), spec, stream), "ffgpu_heat_blend_nv12_dev")
 
 
 def feature_spec(layer=-1, pool=FFGPU.FEAT_MEAN, post=FFGPU.POST_NONE):

@@ -10,6 +10,7 @@
 #include "ffgpu_text_host.hpp"
 #include "ffgpu_lines_host.hpp"
 #include "ffgpu_trails_host.hpp"
+#include "ffgpu_heat_host.hpp"
 
 #define FFGPU_CHECK(expr)                                                                   \
     do {                                                                                    \
@@ -238,6 +239,9 @@ int ffgpu_launch_draw_segments(bool nv12, const void *d_items, int items_stride,
 // track trails (ffgpu_trails.inc): the launches; the checks both entry points share are host code with no HIP in it (ffgpu_trails_host.hpp)
 int ffgpu_launch_trails(const DetSource &src, const int *streams, int ntargets, const TrailsPlan &pl, void *d_state, const void *d_ids, void *d_rows, void *d_items,
                         int items_stride, int first_item, int nitems, hipStream_t s);
+
+// heat maps (ffgpu_heat.inc): the accumulate launches; the checks both entry points share are host code with no HIP in it (ffgpu_heat_host.hpp)
+int ffgpu_launch_heat(const DetSource &src, const int *streams, int ntargets, const HeatPlan &pl, void *d_state, void *d_rows, hipStream_t s);
 
 // the crops classified (ffgpu_feature.inc): the checks both entry points share, and the launches.  Features: frame n of the tensor is frame n % pn of
 // parts[n / pn], a CNHW tensor of pn frames (a split executor has one part per chain; at most 8).

@@ -1505,6 +1505,23 @@ extern "C" int ffgpu_exec_trails(ffgpu_exec *ex, int which, const int *streams, 
     return ffgpu_launch_trails(src, streams, ntargets, pl, d_state, d_ids, d_rows, d_items, items_stride, first_item, nitems, s);
 }
 
+// -------------------------------------------------------------------------- heat maps (include/ffcnn_hip.h; kernels: ffgpu_heat.inc)
+// A post-pass like the zones pass, on the stream of the forward or merge it follows: reads the records and full lists (per entry, or the merged ones),
+// writes the caller's state and rows and nothing of the executor's.  The blend has no executor form: it reads the state, not the records.
+extern "C" int ffgpu_exec_heat(ffgpu_exec *ex, int which, const int *streams, int ntargets, const ffgpu_heat_spec *spec, void *d_state, int nstreams,
+                               void *d_rows, void *stream)
+{
+    const char *const what = "exec_heat";
+    if (!exec_ok(ex, what)) return -1;
+    HeatPlan pl;
+    if (ffgpu_heat_args_check(what, streams, ntargets, spec, d_state, nstreams, d_rows, pl)) return -1;
+    DetSource src;
+    hipStream_t s;
+    if (exec_source(ex, what, "HEAT", "heat pass", which, ntargets, stream, src, &s)) return -1;
+    src.stride = (int)std::min(src.longest, (long long)0x7fffffff);  // a list too long for the kernel's int: clamped (no output is pitched by it)
+    return ffgpu_launch_heat(src, streams, ntargets, pl, d_state, d_rows, s);
+}
+
 // -------------------------------------------------------------------------- captions (include/ffcnn_hip.h; kernels: ffgpu_text.inc)
 // A post-pass like the draw, on the stream of the forward or merge it follows, in two launches: the items composed from the records and full lists (per
 // entry, or the merged ones) into the caller's d_items, then rasterised into the caller's frames.  Nothing of the executor's is written.

@@ -1419,6 +1419,141 @@ int ffgpu_trails_boxes_dev(const void *d_records, const void *d_lists, int list_
 int ffgpu_exec_trails(ffgpu_exec *ex, int which, const int *streams, int ntargets, const ffgpu_trails_spec *spec, void *d_state, int nstreams,
                       const void *d_ids, void *d_rows, void *d_items, int items_stride, int first_item, int nitems, void *stream);
 
+/* ---- heat maps: where the boxes have been, accumulated per stream on the device and blended into the frames -----------------------------------
+ * The zones state keeps one anchor per object and the trails state 32; nothing is kept per PLACE.  What follows keeps, per video stream, a grid of
+ * cells in the caller's device memory into which the considered boxes of any record (plain, merged, tracked, relabelled or gated) are accumulated
+ * with an integer decay -- a stateful per-stream pass in the shape of ffgpu_zones_boxes_dev / ffgpu_trails_boxes_dev -- and a per-pixel operator
+ * that colour-maps the grid and ALPHA-BLENDS it into u8 BGR and NV12 frames where they lie: the first frame writer that mixes a colour into the
+ * picture instead of replacing bytes.  Integers throughout, except the fp32 anchor; no atomics; one owner per written byte; the same bytes on every
+ * run (tests/heat/heatref.py restates both in numpy).
+ *
+ * State, in the caller's device memory (16-byte aligned, ffgpu_heat_state_bytes(nstreams, gw, gh) bytes; all-zero is the valid empty state, so
+ * hipMemsetAsync or ffgpu_heat_reset_dev initialises it): per stream a 16-byte header { int frames; unsigned peak; int reserved[2]; } then gw * gh
+ * cells of unsigned, row-major, the stream's block rounded up to 16 bytes.  The geometry comes from the spec, as capacity does for tracks: the cell
+ * side is c = 1 << cell_log2, the grid is anchored at picture pixel (0, 0), cell (i, j) covers x in [i c, (i + 1) c - 1] and y in [j c, (j + 1) c - 1],
+ * and the grid's EXTENT is gw c x gh c pixels; it need not match any frame's size.  The kernels are total over any state bytes: a cell is read as
+ * unsigned and clamped to FFGPU_HEAT_MAX where it is read, and so is peak where the blend reads it.  The grid is a documented, readable product: a
+ * dashboard copies it out as it is.  The reserved words of the header are never written.
+ *
+ * ACCUMULATE.  One frame of one stream, in this order (streams, ntargets, time order, -1 entries, list_first and the clamps of the counts: exactly
+ * as ffgpu_zones_boxes_dev):
+ *   1. Considered boxes.  The list is walked in list order.  A box QUALIFIES by the redact contract's rule: score >= min_score (a NaN score never
+ *      qualifies; with a NaN min_score nothing does) and its type allowed by the HOST array classes / nclasses (NULL allows every type).  Boxes are
+ *      considered until FFGPU_HEAT_DETS are; further qualifying boxes are counted in `dropped`.
+ *   2. Decay.  With decay_shift k in 1..16 every cell becomes v - ((v + (1 << k) - 1) >> k): the rounding is up, so a non-zero cell loses at least
+ *      1 per frame and old heat reaches exactly zero.  k = 0 means no decay.  Decay also runs for a frame without boxes.
+ *   3. Deposit.  Every considered box adds to the cells of its footprint; sums are taken in 64 bits and the cell is min(sum, FFGPU_HEAT_MAX) --
+ *      saturating sums of non-negative terms do not depend on order.
+ *      FFGPU_HEAT_ANCHOR: the anchor is computed and converted exactly as in step 2 of the trails contract (fp32, not contracted: px = (x1 + x2) *
+ *        0.5f; py = anchor ? y2 : (y1 + y2) * 0.5f; then the draw contract's conversion): A.  If A lies outside [0, gw c - 1] x [0, gh c - 1] the box
+ *        deposits nothing and is counted in `outside`.  Otherwise, with (i, j) = (A.x >> cell_log2, A.y >> cell_log2), every grid cell at Chebyshev
+ *        distance d <= spread from (i, j) receives gain >> d; cells beyond the grid are simply not there.
+ *      FFGPU_HEAT_BOX: the integer corners (a, b, c, d) of the draw contract, clipped to the extent: X0 = max(a, 0), Y0 = max(b, 0), X1 = min(c,
+ *        gw c - 1), Y1 = min(d, gh c - 1).  If a > c, b > d, or the clipped region is empty, the box is counted in `outside`.  Otherwise every cell
+ *        from (X0 >> k, Y0 >> k) to (X1 >> k, Y1 >> k) receives gain.  spread must be 0.
+ *   4. Finish.  peak = the largest cell; frames += 1 (modulo 2^32).
+ *   d_rows (required): row t of FFGPU_HEAT_ROW ints, every byte written, for streams[t] == -1 as zero: { considered, dropped, outside, frame, peak,
+ *     saturated, 0, 0 }; frame is `frames` before step 4 and saturated the number of cells at FFGPU_HEAT_MAX.
+ *
+ * BLEND.  Target t shows the grid of stream streams[t] AS IT IS WHEN THE LAUNCH RUNS IN STREAM ORDER: several frames of one stream in one call all
+ * show the same map.  streams[t] == -1 leaves the target untouched.  Targets are as the draw contract takes them (a NULL pixel address skips the
+ * target, the const pointers are written through, targets must not overlap).  For a pixel (x, y) inside the target's w x h, with k = cell_log2:
+ *   Outside the extent: a pixel with x >= gw c or y >= gh c is untouched.
+ *   Cell level: F = full_scale when full_scale >= 1; with full_scale == 0 F is the stream's peak, and a peak of 0 draws nothing in that target.
+ *     L(i, j) = min(255, (cell(i, j) * 255) / F), in 64-bit integers, rounded down.
+ *   Pixel level: FFGPU_HEAT_NEAREST: L(x >> k, y >> k).  FFGPU_HEAT_SMOOTH is bilinear between cell centres, in integers, with h = c / 2:
+ *     i0 = (x - h) >> k, an arithmetic shift, so i0 may be -1; fx = (x - h) & (c - 1); j0 and fy are formed likewise; the indices i0, i0 + 1, j0,
+ *     j0 + 1 are each clamped to the grid; level = (L00 (c - fx)(c - fy) + L10 fx (c - fy) + L01 (c - fx) fy + L11 fx fy + c c / 2) >> (2 k).
+ *   Alpha: a pixel with level < max(floor, 1) is not written.  Otherwise a = opacity; with FFGPU_HEAT_RAMP_ALPHA a = (level * opacity + 127) / 255,
+ *     and a == 0 is not written.
+ *   Byte: new = (old (255 - a) + pal[level][ch] a + 127) / 255.
+ *   NV12: luma is blended per pixel with pal[level][0].  Chroma sample (i, j) takes the level and alpha of luma pixel (2 i, 2 j), which is always
+ *     inside w x h; it blends U with pal[..][1] and V with pal[..][2] and is not written when that pixel is not.
+ *   Untouched bytes: every byte that is not written stays -- row padding, pixels below the floor or outside the extent, memory before and behind
+ *     the target.  The state is only read.
+ * The built-in palette (a NULL `palette`; ffgpu_heat_palette fills it) is a piecewise-linear ramp in integers through the (B, G, R) anchors
+ * (255, 0, 0) at level 0, (255, 255, 0) at 64, (0, 255, 0) at 128, (0, 255, 255) at 192 and (0, 0, 255) at 255; between anchors v0 < v1:
+ * ch = (c0 (v1 - v) + c1 (v - v0) + (v1 - v0) / 2) / (v1 - v0).  For NV12 each entry is converted, with >> arithmetic and a clamp to 0..255:
+ * Y = (29 B + 150 G + 77 R + 128) >> 8, U = ((128 B - 85 G - 43 R + 128) >> 8) + 128, V = ((-21 B - 107 G + 128 R + 128) >> 8) + 128.
+ * Redact and blur first, then the heat blend, then draw, outline, trails and caption: the overlays lie on top of the map. */
+#define FFGPU_HEAT_MAX        0x7fffffff  /* what a cell saturates at, and what a cell or peak above it reads as */
+#define FFGPU_HEAT_DETS       128  /* considered boxes per frame at most */
+#define FFGPU_HEAT_ROW        8    /* ints of a row */
+#define FFGPU_HEAT_ANCHOR     0    /* mode: a box deposits round its anchor's cell */
+#define FFGPU_HEAT_BOX        1    /* mode: a box deposits into every cell its clipped region touches */
+#define FFGPU_HEAT_NEAREST    0    /* sampling: a pixel takes its cell's level */
+#define FFGPU_HEAT_SMOOTH     1    /* sampling: bilinear between cell centres */
+#define FFGPU_HEAT_RAMP_ALPHA 1    /* blend flags: the alpha grows with the level */
+typedef struct {
+    int   gw, gh;                  /* 1..128 each: the grid, as the state was sized */
+    int   cell_log2;               /* 1..8: a cell is 1 << cell_log2 pixels wide and high */
+    int   mode;                    /* FFGPU_HEAT_ANCHOR | FFGPU_HEAT_BOX */
+    int   flags;                   /* 0: no flag is defined, any bit is rejected */
+    int   anchor;                  /* 0: the box's centre; 1: its bottom centre (the zones contract's anchor); read by FFGPU_HEAT_ANCHOR */
+    int   spread;                  /* 0..4: the Chebyshev radius, in cells, of an anchor's footprint; 0 with FFGPU_HEAT_BOX */
+    int   gain;                    /* 1..65536: what a box adds to a cell */
+    int   decay_shift;             /* 0..16: 0 = no decay */
+    float min_score;               /* any value: a box qualifies from this score on (NaN: none does) */
+    const unsigned char *classes;  /* HOST, nclasses bytes, non-zero = allowed; NULL: every type */
+    int   nclasses;                /* 0 with NULL classes, else 1..256 */
+    int   reserved;                /* 0 */
+} ffgpu_heat_spec;                 /* 56 bytes: gw 0, gh 4, cell_log2 8, mode 12, flags 16, anchor 20, spread 24, gain 28, decay_shift 32, */
+                                   /* min_score 36, classes 40, nclasses 48, reserved 52 */
+typedef struct {
+    int   gw, gh, cell_log2;       /* the grid's geometry, as ffgpu_heat_spec's */
+    int   full_scale;              /* >= 1: the cell value shown as level 255; 0: the stream's peak */
+    int   floor;                   /* 0..255: a pixel below max(floor, 1) is not written */
+    int   opacity;                 /* 1..255 */
+    int   sampling;                /* FFGPU_HEAT_NEAREST | FFGPU_HEAT_SMOOTH */
+    int   flags;                   /* 0 | FFGPU_HEAT_RAMP_ALPHA; any other bit is rejected */
+    const unsigned char *palette;  /* HOST, 256 x 4 bytes: B G R 0 (BGR targets) or Y U V 0 (NV12 targets), byte 3 ignored, nothing is converted; */
+                                   /* NULL: the built-in palette of the target's format */
+    int   reserved[2];             /* 0 */
+} ffgpu_heat_blend_spec;           /* 48 bytes: gw 0, gh 4, cell_log2 8, full_scale 12, floor 16, opacity 20, sampling 24, flags 28, palette 32, reserved 40 */
+
+/* pure host code: the bytes of the state of nstreams (1..65536) streams of gw x gh (1..128 each) cells; 0 for arguments outside their ranges */
+size_t ffgpu_heat_state_bytes(int nstreams, int gw, int gh);
+/* pure host code: 0, or -1 with the message in ffgpu_last_error */
+int ffgpu_heat_spec_check(const ffgpu_heat_spec *spec);
+int ffgpu_heat_blend_spec_check(const ffgpu_heat_blend_spec *spec);
+/* pure host code: the built-in palette, 256 x 4 bytes, B G R 0 (nv12 == 0) or Y U V 0 (nv12 != 0); -1 for a NULL out */
+int ffgpu_heat_palette(int nv12, unsigned char out[1024]);
+/* zeroes the state of one stream, or of all with which_stream == -1, in stream order (a memset; no kernel) */
+int ffgpu_heat_reset_dev(void *d_state, int nstreams, int gw, int gh, int which_stream, void *stream);
+
+/* The accumulate operator, on device records and lists with no executor.  d_records, d_lists, list_stride and the HOST array list_first are the draw
+ * operators'.  One workgroup per video stream walks that stream's records of the launch serially with the stream's grid in LDS, loaded once and
+ * stored once; streams, list_first and spec (with its classes) are HOST memory and free again on return; the tables travel as a kernel argument,
+ * 64 records per launch, the launches of one call in order on `stream`, the state passing through memory between them.  Enqueued without
+ * synchronising.  Rejected before anything is launched, with the entry's index in the message where there is one: the reasons of
+ * ffgpu_zones_boxes_dev that apply (NULL records, streams, spec, state or rows, ntargets < 1, nstreams outside 1..65536, a stream index outside
+ * -1..nstreams-1, a state that is not 16-byte aligned, a bad list_stride, a negative list start), every spec field outside its range, an unknown
+ * mode, any flag bit, a reserved field that is not 0, nclasses inconsistent with classes, a non-zero spread with FFGPU_HEAT_BOX.  A rejected call
+ * leaves the state as it was. */
+int ffgpu_heat_boxes_dev(const void *d_records, const void *d_lists, int list_stride, const int *list_first, const int *streams, int ntargets,
+                         const ffgpu_heat_spec *spec, void *d_state, int nstreams, void *d_rows, void *stream);
+
+#define FFGPU_HEAT_ENTRIES 0   /* entry n's full post-NMS list is record n; ntargets == batch                                          */
+#define FFGPU_HEAT_MERGED  1   /* picture g's merged list (last ffgpu_exec_merge_tiles) is record g; ntargets == its nimages            */
+/* On an executor: a post-pass like ffgpu_exec_zones, with its stream, FFGPU_SPLIT2 and FFGPU_HEAT_MERGED rules, enqueued on `stream` (NULL = the
+ * executor's own; it must be the stream of the forward or merge it follows) without synchronising.  The captured graph, the records, the full lists,
+ * the ring and the host mirror are untouched; state and rows are the caller's.  Rejected like the operator, and: ntargets not as stated, a `which`
+ * that is neither, FFGPU_HEAT_MERGED when no merge has run, the wrong stream.  A rejected call leaves the state and the executor usable. */
+int ffgpu_exec_heat(ffgpu_exec *ex, int which, const int *streams, int ntargets, const ffgpu_heat_spec *spec, void *d_state, int nstreams,
+                    void *d_rows, void *stream);
+
+/* The blend operators.  There is no executor form: the blend reads state, not records.  streams and spec (with its palette) are HOST memory and free
+ * again on return; the palette, the targets and their streams travel as ONE by-value kernel argument, 64 targets per launch (more targets: more
+ * launches, in order on `stream`).  A workgroup owns a 64 x 64 pixel block of its target anchored at (0, 0), computes the levels of the cells the
+ * block can reach first and leaves without loading a pixel when every one is below max(floor, 1).  Enqueued without synchronising.  Rejected before
+ * anything is launched, with the target's index where there is one: everything the draw operators reject about targets, NULL state, streams, spec or
+ * targets, ntargets < 1, nstreams outside 1..65536, a stream index outside -1..nstreams-1, a state that is not 16-byte aligned, a field outside its
+ * range, an unknown sampling, unknown flag bits, a reserved field that is not 0, a negative full_scale. */
+int ffgpu_heat_blend_bgr_dev(const void *d_state, int nstreams, const int *streams, const ffgpu_bgr_frame *targets, int ntargets,
+                             const ffgpu_heat_blend_spec *spec, void *stream);
+int ffgpu_heat_blend_nv12_dev(const void *d_state, int nstreams, const int *streams, const ffgpu_nv12_frame *targets, int ntargets,
+                              const ffgpu_heat_blend_spec *spec, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
