@@ -188,6 +188,18 @@ class HeatBlendSpec(C.Structure):    # ffgpu_heat_blend_spec (48 bytes): how a s
                 ("sampling", C.c_int), ("flags", C.c_int), ("palette", C.c_void_p), ("reserved", C.c_int * 2)]
 
 
+class MotionSpec(C.Structure):       # ffgpu_motion_spec (64 bytes): the motion maps' settings, read by the update and by the gate
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("cell_log2", C.c_int), ("threshold", C.c_int), ("learn_shift", C.c_int), ("learn_shift_changed", C.c_int),
+                ("min_pixels", C.c_int), ("cover", C.c_int), ("warmup", C.c_int), ("flags", C.c_int), ("min_score", C.c_float), ("nclasses", C.c_int),
+                ("classes", C.c_void_p), ("reserved", C.c_int * 2)]
+
+
+MOTION_DETS, MOTION_ROW, MOTION_WORDS, MOTION_MAX_SIDE = 128, 16, 8, 8192                # FFGPU_MOTION_DETS, _ROW, _WORDS, _MAX_SIDE
+MOTION_GATE_INVERT = 1                                                                 # FFGPU_MOTION_GATE_INVERT (ffgpu_motion_spec.flags)
+MOTION_ENTRIES, MOTION_MERGED = 0, 1                                                   # FFGPU_MOTION_* (ffgpu_exec_motion_gate: which)
+MOTION_ROW_HEADER = ("frame", "changed", "active", "x0", "y0", "x1", "y1", "warm")
+MOTION_WORDS_HEADER = ("considered", "dropped", "outside", "moving", "warm", "frames")
+MOTION_STATE_HEADER = 16                                                               # bytes in front of a stream's plane
 HEAT_MAX, HEAT_DETS, HEAT_ROW = 2 ** 31 - 1, 128, 8                                    # FFGPU_HEAT_MAX, _DETS, _ROW
 HEAT_ANCHOR, HEAT_BOX = 0, 1                                                           # FFGPU_HEAT_* (ffgpu_heat_spec.mode)
 HEAT_NEAREST, HEAT_SMOOTH = 0, 1                                                       # FFGPU_HEAT_* (ffgpu_heat_blend_spec.sampling)
@@ -236,6 +248,7 @@ assert C.sizeof(TextItem) == 64 and C.sizeof(CaptionSpec) == 48
 assert C.sizeof(SegItem) == 32 and C.sizeof(OutlineSpec) == 40
 assert C.sizeof(TrailPoint) == 12 and C.sizeof(TrailSlot) == 416 and C.sizeof(TrailsSpec) == 64
 assert C.sizeof(HeatSpec) == 56 and C.sizeof(HeatBlendSpec) == 48
+assert C.sizeof(MotionSpec) == 64
 assert C.sizeof(Zone) == 96 and C.sizeof(Line) == 32 and C.sizeof(Scene) == 1040 and C.sizeof(ZonesSpec) == 32 and C.sizeof(ZoneSlot) == 64
 
 BOX_DTYPE = np.dtype([("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
@@ -284,7 +297,9 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_draw_segments_bgr_dev", "ffgpu_draw_segments_nv12_dev", "ffgpu_outline_spec_check", "ffgpu_outline_scene_dev",
            "ffgpu_trails_state_bytes", "ffgpu_trails_spec_check", "ffgpu_trails_reset_dev", "ffgpu_trails_boxes_dev", "ffgpu_exec_trails",
            "ffgpu_heat_state_bytes", "ffgpu_heat_spec_check", "ffgpu_heat_blend_spec_check", "ffgpu_heat_palette", "ffgpu_heat_reset_dev", "ffgpu_heat_boxes_dev",
-           "ffgpu_exec_heat", "ffgpu_heat_blend_bgr_dev", "ffgpu_heat_blend_nv12_dev"]
+           "ffgpu_exec_heat", "ffgpu_heat_blend_bgr_dev", "ffgpu_heat_blend_nv12_dev",
+           "ffgpu_motion_state_bytes", "ffgpu_motion_spec_check", "ffgpu_motion_reset_dev", "ffgpu_motion_update_bgr_dev", "ffgpu_motion_update_nv12_dev",
+           "ffgpu_motion_gate_dev", "ffgpu_exec_motion_gate"]
 # include/ffcnn_hip_diag.h (libffcnn_hip_diag.so: lab equipment, its own library)
 DIAG_EXPORTS = ["ffgpu_membench", "ffgpu_pipe_probe", "ffgpu_pipe_probe2", "ffgpu_pipe_probe3", "ffgpu_mfma_floor", "ffgpu_diag_x3_term", "ffgpu_diag_xl_op", "ffgpu_clock_probe"]
 
@@ -465,6 +480,14 @@ def lib():
     L.ffgpu_exec_heat.argtypes = [vp, i, C.POINTER(i), i, C.POINTER(HeatSpec), vp, i, vp, vp]
     L.ffgpu_heat_blend_bgr_dev.argtypes = [vp, i, C.POINTER(i), C.POINTER(BgrFrame), i, C.POINTER(HeatBlendSpec), vp]
     L.ffgpu_heat_blend_nv12_dev.argtypes = [vp, i, C.POINTER(i), C.POINTER(Nv12Frame), i, C.POINTER(HeatBlendSpec), vp]
+    L.ffgpu_motion_state_bytes.restype = sz
+    L.ffgpu_motion_state_bytes.argtypes = [i, i, i, i]
+    L.ffgpu_motion_spec_check.argtypes = [C.POINTER(MotionSpec)]
+    L.ffgpu_motion_reset_dev.argtypes = [vp, i, i, i, i, i, vp]
+    L.ffgpu_motion_update_bgr_dev.argtypes = [C.POINTER(BgrFrame), i, C.POINTER(i), C.POINTER(MotionSpec), vp, i, vp, vp]
+    L.ffgpu_motion_update_nv12_dev.argtypes = [C.POINTER(Nv12Frame), i, C.POINTER(i), C.POINTER(MotionSpec), vp, i, vp, vp]
+    L.ffgpu_motion_gate_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(i), i, C.POINTER(MotionSpec), vp, i, vp, vp, vp, vp]
+    L.ffgpu_exec_motion_gate.argtypes = [vp, i, C.POINTER(i), i, C.POINTER(MotionSpec), vp, i, vp, vp, vp, vp]
     L.ffgpu_outline_scene_dev.argtypes = [vp, vp, i, i, vp, i, C.POINTER(i), i, C.POINTER(OutlineSpec), vp, i, vp]
     L.ffgpu_feature_dim.argtypes = [i, i, i, i]
     L.ffgpu_exec_feature_dim.argtypes = [vp, C.POINTER(FeatureSpec)]
@@ -856,6 +879,13 @@ class Executor:
         buffers (heat_state_bytes; rows of HEAT_ROW ints).  heat_blend_bgr_dev / _nv12_dev show the state in the frames."""
         arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
         _check(lib().ffgpu_exec_heat(self.h, which, arr, len(streams), spec, d_state, nstreams, d_rows, stream), "ffgpu_exec_heat")
+
+    def motion_gate(self, streams, spec, d_state, nstreams, d_words, d_out_records=None, d_out_lists=None, which=0, stream=None):
+        """enqueue the motion gate on the last forward's boxes (which = MOTION_ENTRIES: entry n is record n of video stream streams[n], -1: ignored) or
+        on the last merge's (MOTION_MERGED: picture g) behind it (ffgpu_exec_motion_gate): spec from motion_spec, d_state what motion_update_*_dev
+        keeps (only read), d_words rows of MOTION_WORDS + 2 S ints, the gated records and lists optional and the caller's."""
+        arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+        _check(lib().ffgpu_exec_motion_gate(self.h, which, arr, len(streams), spec, d_state, nstreams, d_words, d_out_records, d_out_lists, stream), "ffgpu_exec_motion_gate")
 
     def trails(self, streams, spec, d_state, nstreams, d_rows, d_ids=None, d_items=None, items_stride=0, first_item=0, nitems=0, which=0, stream=None):
         """enqueue the trails pass on the last forward's boxes (which = TRAILS_ENTRIES: entry n is record n of video stream streams[n], -1: ignored) or
@@ -1523,6 +1553,71 @@ def heat_blend_nv12_dev(d_state, nstreams, streams, frames, spec, stream=None):
     """ffgpu_heat_blend_nv12_dev: the same in NV12 frames (what nv12_frame_desc accepts, or None: skipped)"""
     arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
     _check(lib().ffgpu_heat_blend_nv12_dev(d_state, nstreams, arr, nv12_frame_table(frames), len(frames), spec, stream), "ffgpu_heat_blend_nv12_dev")
+
+
+def motion_spec(w, h, cell_log2, threshold=16, learn_shift=4, learn_shift_changed=8, min_pixels=1, cover=64, warmup=0, invert=False, min_score=0.0, classes=None):
+    """a MotionSpec (ffgpu_motion_spec): the model's size and its cells (1 << cell_log2 pixels), when a pixel counts as changed, how fast the model
+    follows an unchanged and a changed pixel (shifts; 0: take the frame, 16: keep the model), when a cell is active, the share of a box's cells
+    (of 256) that must be active for the box to move, the frames the gate fails open for, and which boxes qualify (min_score, classes as
+    redact_spec).  The structure keeps its class bytes alive."""
+    sp = MotionSpec()
+    sp.w, sp.h, sp.cell_log2, sp.threshold, sp.learn_shift, sp.learn_shift_changed, sp.min_pixels = w, h, cell_log2, threshold, learn_shift, learn_shift_changed, min_pixels
+    sp.cover, sp.warmup, sp.flags, sp.min_score = cover, warmup, MOTION_GATE_INVERT if invert else 0, min_score
+    if classes is not None:
+        cls = np.ascontiguousarray(np.asarray(classes) != 0, np.uint8) if len(classes) else np.zeros(1, np.uint8)
+        sp._cls = cls                                           # (owned by the structure: the C side reads it during the call)
+        sp.classes = cls.ctypes.data
+        sp.nclasses = len(classes)
+    return sp
+
+
+def motion_spec_check(spec):
+    """ffgpu_motion_spec_check (pure host code): raises with what is wrong with the spec"""
+    _check(lib().ffgpu_motion_spec_check(spec), "ffgpu_motion_spec_check")
+
+
+def motion_state_bytes(nstreams, w, h, cell_log2):
+    return lib().ffgpu_motion_state_bytes(nstreams, w, h, cell_log2)
+
+
+def motion_state(raw, nstreams, w, h, cell_log2):
+    """(headers as a uint32 array of nstreams x 4: frames, reserved x 3; the planes as a uint16 array of nstreams x h x w, luma in 8.8 fixed point;
+    the cells as a uint32 array of nstreams x gh x gw) of a state's bytes"""
+    c = 1 << cell_log2
+    gw, gh, pitch = (w + c - 1) // c, (h + c - 1) // c, (w + 7) & ~7
+    cells_off = MOTION_STATE_HEADER + 2 * pitch * h
+    one = cells_off + ((4 * gw * gh + 15) & ~15)
+    raw = np.ascontiguousarray(raw, np.uint8).reshape(nstreams, one)
+    return (np.ascontiguousarray(raw[:, :MOTION_STATE_HEADER]).view("<u4"),
+            np.ascontiguousarray(np.ascontiguousarray(raw[:, MOTION_STATE_HEADER:cells_off]).view("<u2").reshape(nstreams, h, pitch)[:, :, :w]),
+            np.ascontiguousarray(raw[:, cells_off:cells_off + 4 * gw * gh]).view("<u4").reshape(nstreams, gh, gw))
+
+
+def motion_reset_dev(d_state, nstreams, w, h, cell_log2, which_stream=-1, stream=None):
+    """ffgpu_motion_reset_dev: zero the motion state of one video stream, or of all (-1), in stream order"""
+    _check(lib().ffgpu_motion_reset_dev(d_state, nstreams, w, h, cell_log2, which_stream, stream), "ffgpu_motion_reset_dev")
+
+
+def motion_update_bgr_dev(frames, streams, spec, d_state, nstreams, d_rows, stream=None):
+    """ffgpu_motion_update_bgr_dev: frames[t] (what bgr_frame_desc accepts, or None: skipped) is the next frame of video stream streams[t] (-1:
+    ignored); a stream's frames are taken in the order given; d_rows: rows of MOTION_ROW ints"""
+    arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+    _check(lib().ffgpu_motion_update_bgr_dev(bgr_frame_table(frames), len(frames), arr, spec, d_state, nstreams, d_rows, stream), "ffgpu_motion_update_bgr_dev")
+
+
+def motion_update_nv12_dev(frames, streams, spec, d_state, nstreams, d_rows, stream=None):
+    """ffgpu_motion_update_nv12_dev: the same on NV12 frames (what nv12_frame_desc accepts, or None: skipped); only the Y plane is read"""
+    arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+    _check(lib().ffgpu_motion_update_nv12_dev(nv12_frame_table(frames), len(frames), arr, spec, d_state, nstreams, d_rows, stream), "ffgpu_motion_update_nv12_dev")
+
+
+def motion_gate_dev(d_records, d_lists, list_stride, streams, spec, d_state, nstreams, d_words, d_out_records=None, d_out_lists=None, list_first=None, stream=None):
+    """ffgpu_motion_gate_dev on device records / lists: record t belongs to video stream streams[t] (-1: ignored); d_lists None: the records' own
+    boxes; list_first as draw_boxes_bgr_dev; d_words: rows of MOTION_WORDS + 2 S ints; the gated records and lists are optional"""
+    arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+    first = None if list_first is None else (C.c_int * max(1, len(list_first)))(*[int(v) for v in list_first])
+    _check(lib().ffgpu_motion_gate_dev(d_records, d_lists, list_stride, first, arr, len(streams), spec, d_state, nstreams, d_words, d_out_records, d_out_lists, stream),
+           "ffgpu_motion_gate_dev")
 
 
 def feature_spec(layer=-1, pool=FFGPU.FEAT_MEAN, post=FFGPU.POST_NONE):

@@ -1,5 +1,5 @@
 // ffgpu_block.inc -- the workgroup primitives of the detection tail and the post-passes (k_nms, k_merge_tiles, k_track, k_feat_pool, k_feat_post,
-// k_topk, k_match, k_match_merge, k_enroll_decide, k_zones, k_trails, k_heat_accumulate).  Device code only.  Every one of those kernels is held byte for byte to a Python restatement, so
+// k_topk, k_match, k_match_merge, k_enroll_decide, k_zones, k_trails, k_heat_accumulate, k_motion_row, k_motion_gate).  Device code only.  Every one of those kernels is held byte for byte to a Python restatement, so
 // the ordering rule of a sort, the tie rule of a selection and the rounding of an overlap are part of a contract: each is written HERE, once, and what
 // differs between two kernels (array layouts, padding values, which slots start dead, how a record is written) stays at the call site.
 //

@@ -11,6 +11,7 @@
 #include "ffgpu_lines_host.hpp"
 #include "ffgpu_trails_host.hpp"
 #include "ffgpu_heat_host.hpp"
+#include "ffgpu_motion_host.hpp"
 
 #define FFGPU_CHECK(expr)                                                                   \
     do {                                                                                    \
@@ -242,6 +243,10 @@ int ffgpu_launch_trails(const DetSource &src, const int *streams, int ntargets, 
 
 // heat maps (ffgpu_heat.inc): the accumulate launches; the checks both entry points share are host code with no HIP in it (ffgpu_heat_host.hpp)
 int ffgpu_launch_heat(const DetSource &src, const int *streams, int ntargets, const HeatPlan &pl, void *d_state, void *d_rows, hipStream_t s);
+
+// motion maps (ffgpu_motion.inc): the gate launches; the checks both entry points share are host code with no HIP in it (ffgpu_motion_host.hpp)
+int ffgpu_launch_motion_gate(const DetSource &src, const int *streams, int ntargets, const MotionPlan &pl, const void *d_state, void *d_words, void *d_out_records,
+                             void *d_out_lists, hipStream_t s);
 
 // the crops classified (ffgpu_feature.inc): the checks both entry points share, and the launches.  Features: frame n of the tensor is frame n % pn of
 // parts[n / pn], a CNHW tensor of pn frames (a split executor has one part per chain; at most 8).

@@ -1522,6 +1522,26 @@ extern "C" int ffgpu_exec_heat(ffgpu_exec *ex, int which, const int *streams, in
     return ffgpu_launch_heat(src, streams, ntargets, pl, d_state, d_rows, s);
 }
 
+// -------------------------------------------------------------------------- motion maps (include/ffcnn_hip.h; kernels: ffgpu_motion.inc)
+// A post-pass like the zones pass, on the stream of the forward or merge it follows: reads the records and full lists (per entry, or the merged ones)
+// and the caller's motion state, writes the caller's words and gated records and nothing of the executor's.  The update has no executor form: it
+// reads frames, not records.
+extern "C" int ffgpu_exec_motion_gate(ffgpu_exec *ex, int which, const int *streams, int ntargets, const ffgpu_motion_spec *spec, const void *d_state, int nstreams,
+                                      void *d_words, void *d_out_records, void *d_out_lists, void *stream)
+{
+    const char *const what = "exec_motion_gate";
+    if (!exec_ok(ex, what)) return -1;
+    MotionPlan pl;
+    if (ffgpu_motion_gate_args_check(what, streams, ntargets, spec, d_state, nstreams, d_words, d_out_records, d_out_lists, pl)) return -1;
+    DetSource src;
+    hipStream_t s;
+    if (exec_source(ex, what, "MOTION", "motion gate", which, ntargets, stream, src, &s)) return -1;
+    // the stride is also the pitch of the words and the caller's output lists: a list too long is refused, not clamped (as the zones pass)
+    if (src.longest > (1 << 24)) { ffgpu_set_error("%s: lists of up to %lld boxes are too long", what, src.longest); return -1; }
+    src.stride = (int)src.longest;
+    return ffgpu_launch_motion_gate(src, streams, ntargets, pl, d_state, d_words, d_out_records, d_out_lists, s);
+}
+
 // -------------------------------------------------------------------------- captions (include/ffcnn_hip.h; kernels: ffgpu_text.inc)
 // A post-pass like the draw, on the stream of the forward or merge it follows, in two launches: the items composed from the records and full lists (per
 // entry, or the merged ones) into the caller's d_items, then rasterised into the caller's frames.  Nothing of the executor's is written.

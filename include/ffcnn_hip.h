@@ -1554,6 +1554,117 @@ int ffgpu_heat_blend_bgr_dev(const void *d_state, int nstreams, const int *strea
 int ffgpu_heat_blend_nv12_dev(const void *d_state, int nstreams, const int *streams, const ffgpu_nv12_frame *targets, int ntargets,
                               const ffgpu_heat_blend_spec *spec, void *stream);
 
+/* ---- motion maps: a per-stream background model of the frames' luma, the cells that changed, and a gate on the boxes that move ------------------
+ * Every pass above starts from the boxes.  This family is the first that reads WHOLE FRAMES over time: per video stream it keeps a background model
+ * of the luma in the caller's device memory, counts per cell the pixels of the stream's last frame that differ from it, and gates any record (plain,
+ * merged, tracked, relabelled) by whether a box lies on cells that move -- a poster, a parked car or a reflection the detector fires on in every
+ * frame does not.  (The trails family's "motion row" is a different thing: displacement of an identified anchor over its kept history.  The family
+ * here is named `motion`: pixels over time.)  Integers throughout; no atomics; one owner per written byte; the same bytes on every run; total over
+ * any state bytes (tests/motion/motionref.py restates it in numpy).
+ *
+ * Geometry, from the spec: frames and model are w x h pixels; a cell is c = 1 << cell_log2 pixels wide and high, anchored at pixel (0, 0); the grid
+ * is gw = ceil(w / c) by gh = ceil(h / c) cells, the last column and row partial where c does not divide w or h.
+ *
+ * State, in the caller's device memory (16-byte aligned, ffgpu_motion_state_bytes(nstreams, w, h, cell_log2) bytes; all-zero is the valid empty
+ * state, so hipMemsetAsync or ffgpu_motion_reset_dev initialises it).  Per stream, in this order:
+ *   1. a header { int frames; int reserved[3]; } (the reserved words are never written);
+ *   2. the background PLANE: h rows of ALIGN(w, 8) unsigned short, row-major, luma in 8.8 fixed point; the padding shorts of a row are never written;
+ *   3. gw * gh unsigned CELLS, row-major, rounded up to 16 bytes (the rounding bytes are never written): the number of changed pixels of the cell in
+ *      the stream's last frame.
+ * Plane and cells are documented, readable products.
+ *
+ * UPDATE.  One frame of one stream.  Luma y of a pixel: NV12: the Y byte (the UV plane is not read); BGR: y = (29 B + 150 G + 77 R + 128) >> 8.
+ * For every pixel, with cur = y << 8, bg the stored short (any value) and d = cur - bg as int:
+ *   If the header's `frames` is 0 the pixel is not changed and bg = cur.
+ *   Otherwise the pixel is CHANGED when |d| > threshold << 8; k = learn_shift_changed for a changed pixel, learn_shift for any other;
+ *     k == 0: bg = cur (plain frame differencing); k in 1..15: bg += sgn(d) * ((|d| + (1 << k) - 1) >> k) -- the rounding is up, so the model reaches
+ *     cur exactly; k == 16: bg stays.
+ *   cell(i, j) = the changed pixels with x >> cell_log2 == i and y >> cell_log2 == j.  Every cell of the stream is written.
+ * Then frames += 1 (modulo 2^32), and row t of FFGPU_MOTION_ROW ints, every byte written: { frame (frames before the increment), changed (pixels),
+ * active (cells with count >= min_pixels), x0, y0, x1, y1, warm, 0 x 8 }.  The bounding box of the active cells is in pixels: x0 = c * min i,
+ * x1 = min(c * (max i + 1), w) - 1, likewise y; with no active cell it is (0, 0, -1, -1).  warm = (frames after the increment) > warmup.
+ * Targets: streams[t] == -1 or a NULL pixel address leaves the state alone, and the row is zero (the size of such a target is not looked at).  Any
+ * other target whose w or h differ from the spec's is rejected.  A stream may appear several times in one call; its frames are then in time
+ * order, and the result is byte for byte what one call per frame leaves.
+ *
+ * GATE.  Only reads the state, AS IT IS WHEN THE LAUNCH RUNS IN STREAM ORDER.  Per record t of stream streams[t]:
+ *   Considered boxes: step 1 of the heat contract with the cap FFGPU_MOTION_DETS; further qualifying boxes are counted in `dropped`.
+ *   For a considered box, the integer corners (a, b, c, d) of the draw contract clipped to w x h: X0 = max(a, 0), Y0 = max(b, 0), X1 = min(c, w - 1),
+ *     Y1 = min(d, h - 1).  If a > c, b > d or the clip is empty the box is counted in `outside` and touched = active = 0.  Otherwise touched = the
+ *     cells from (X0 >> k, Y0 >> k) to (X1 >> k, Y1 >> k), k = cell_log2, and active = those among them with count >= min_pixels.
+ *   The stream is WARM when frames > warmup.  Warm: a box is MOVING when touched >= 1 and active * 256 >= cover * touched.  Not warm: every
+ *     considered box is MOVING -- the gate fails open, so no detection is lost while the model learns.
+ *   d_words (required): row t of 8 + 2 S ints (S = the list stride), every byte written: { considered, dropped, outside, moving, warm, frames, 0, 0 },
+ *     then { touched, active } per list box, zero for a box that was not considered.
+ *   d_out_records / d_out_lists (may be NULL): the considered boxes with MOVING != (flags & FFGPU_MOTION_GATE_INVERT), in list order and unchanged,
+ *     laid out by the zones gated record's rules word for word (count = min(n, FFGPU_MAX_DET), nfull = n, ncand and overflow bit 0 copied, bit 2 =
+ *     n > FFGPU_MAX_DET; unused box slots of the record and of the list are zero).  The outputs must not overlap the inputs.
+ *   streams[t] == -1: every output byte of the entry is written, as zero.
+ * The composition: update, forward, gate, then track, redact, draw or heat ON THE GATED RECORD.  FFGPU_MOTION_GATE_INVERT gives the boxes that
+ * stand still. */
+#define FFGPU_MOTION_DETS        128  /* considered boxes per record at most */
+#define FFGPU_MOTION_ROW         16   /* ints of an update row */
+#define FFGPU_MOTION_WORDS       8    /* ints in front of a gate row's { touched, active } pairs */
+#define FFGPU_MOTION_GATE_INVERT 1    /* flags bit 0: the gated record holds the considered boxes that are NOT moving */
+#define FFGPU_MOTION_MAX_SIDE    8192 /* w and h at most */
+typedef struct {
+    int   w, h;                    /* 1..8192: the size of the stream's frames and of the model */
+    int   cell_log2;               /* 2..6: a cell is c = 1 << cell_log2 pixels wide and high */
+    int   threshold;               /* 1..255: a pixel is changed when |luma - background| exceeds it */
+    int   learn_shift;             /* 0..16: the model's learning rate at an unchanged pixel (0: take the frame, 16: keep the model) */
+    int   learn_shift_changed;     /* 0..16: the same at a changed pixel */
+    int   min_pixels;              /* 1..c c: a cell is active from this many changed pixels on */
+    int   cover;                   /* 1..256: a box moves when active * 256 >= cover * touched */
+    int   warmup;                  /* 0..65535: the gate fails open until the stream has seen more frames than this */
+    int   flags;                   /* 0 | FFGPU_MOTION_GATE_INVERT; any other bit is rejected */
+    float min_score;               /* any value: a box qualifies from this score on (NaN: none does); read by the gate */
+    int   nclasses;                /* 0 with NULL classes, else 1..256 */
+    const unsigned char *classes;  /* HOST, nclasses bytes, non-zero = allowed; NULL: every type; read by the gate */
+    int   reserved[2];             /* 0 */
+} ffgpu_motion_spec;               /* 64 bytes: w 0, h 4, cell_log2 8, threshold 12, learn_shift 16, learn_shift_changed 20, min_pixels 24, cover 28, */
+                                   /* warmup 32, flags 36, min_score 40, nclasses 44, classes 48, reserved 56 */
+
+/* pure host code: the bytes of the state of nstreams (1..65536) streams of w x h (1..8192 each) pixels with cells of 1 << cell_log2 (2..6); 0 for
+ * arguments outside their ranges */
+size_t ffgpu_motion_state_bytes(int nstreams, int w, int h, int cell_log2);
+/* pure host code: 0, or -1 with the message in ffgpu_last_error */
+int ffgpu_motion_spec_check(const ffgpu_motion_spec *spec);
+/* zeroes the state of one stream, or of all with which_stream == -1, in stream order (a memset; no kernel) */
+int ffgpu_motion_reset_dev(void *d_state, int nstreams, int w, int h, int cell_log2, int which_stream, void *stream);
+
+/* The update operators.  targets (the frames, as the draw operators take them; only read), streams and spec are HOST memory and free again on
+ * return.  The host enqueues ROUND r -- the r-th occurrence of every stream in the call -- behind round r - 1: stream order is the barrier.  A round
+ * is two launches per 64 targets: k_motion_update, in which a workgroup owns a tile of 64 x 64 pixels -- whole cells at every legal cell size --
+ * reads the frame's bytes and the plane once, writes the plane once and stores each of its cells from one lane; then a small launch, one workgroup
+ * per target, that reduces the stream's cells to the row and writes `frames`.  The update launch only reads `frames`.  No atomics.  Enqueued
+ * without synchronising.  Rejected before anything is enqueued, with the target's index where there is one: everything the draw operators reject
+ * about targets, NULL targets, streams, spec, state or rows, ntargets < 1, nstreams outside 1..65536, a stream index outside -1..nstreams-1, a state
+ * that is not 16-byte aligned, every spec field outside its range, unknown flag bits, a reserved field that is not 0, nclasses inconsistent with
+ * classes, a target whose size is not the spec's.  A rejected call leaves the state as it was. */
+int ffgpu_motion_update_bgr_dev(const ffgpu_bgr_frame *targets, int ntargets, const int *streams, const ffgpu_motion_spec *spec, void *d_state,
+                                int nstreams, void *d_rows, void *stream);
+int ffgpu_motion_update_nv12_dev(const ffgpu_nv12_frame *targets, int ntargets, const int *streams, const ffgpu_motion_spec *spec, void *d_state,
+                                 int nstreams, void *d_rows, void *stream);
+
+/* The gate operator, on device records and lists with no executor.  d_records, d_lists, list_stride and the HOST array list_first are the draw
+ * operators'; streams and spec (with its classes) are HOST memory and free again on return.  One workgroup per record, 64 records per launch, the
+ * tables travelling as a kernel argument.  Enqueued without synchronising.  Rejected before anything is launched: the reasons of
+ * ffgpu_heat_boxes_dev that apply (with NULL words for NULL rows), the spec as above, d_out_lists without d_out_records, outputs that are the
+ * inputs. */
+int ffgpu_motion_gate_dev(const void *d_records, const void *d_lists, int list_stride, const int *list_first, const int *streams, int ntargets,
+                          const ffgpu_motion_spec *spec, const void *d_state, int nstreams, void *d_words, void *d_out_records, void *d_out_lists,
+                          void *stream);
+
+#define FFGPU_MOTION_ENTRIES 0   /* entry n's full post-NMS list is record n; ntargets == batch; S = ffgpu_exec_cand_capacity               */
+#define FFGPU_MOTION_MERGED  1   /* picture g's merged list (last ffgpu_exec_merge_tiles) is record g; ntargets == its nimages; S as FFGPU_ZONES_MERGED */
+/* On an executor: a post-pass like ffgpu_exec_heat, with its stream, FFGPU_SPLIT2 and FFGPU_MOTION_MERGED rules, enqueued on `stream` (NULL = the
+ * executor's own; it must be the stream of the forward or merge it follows) without synchronising.  The captured graph, the records, the full lists,
+ * the ring and the host mirror are untouched; the state is only read; words and the gated records are the caller's, pitched by S as the zones pass's.
+ * Rejected like the operator, and: ntargets not as stated, a `which` that is neither, FFGPU_MOTION_MERGED when no merge has run, the wrong stream,
+ * lists longer than 2^24 boxes.  A rejected call leaves the state and the executor usable. */
+int ffgpu_exec_motion_gate(ffgpu_exec *ex, int which, const int *streams, int ntargets, const ffgpu_motion_spec *spec, const void *d_state, int nstreams,
+                           void *d_words, void *d_out_records, void *d_out_lists, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
