@@ -276,7 +276,7 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_exec_kernel_count", "ffgpu_exec_work_model", "ffgpu_exec_set_scale", "ffgpu_exec_forward_dev", "ffgpu_exec_forward_host",
            "ffgpu_exec_forward_bgr_dev", "ffgpu_exec_forward_bgr_frames_dev", "ffgpu_exec_forward_nv12_frames_dev", "ffgpu_exec_dets_dev", "ffgpu_exec_dets_host", "ffgpu_exec_set_ring", "ffgpu_exec_set_ring_strided", "ffgpu_exec_read_dets", "ffgpu_exec_read_layer", "ffgpu_exec_hash_layers",
            "ffgpu_exec_read_boxes", "ffgpu_exec_cand_capacity", "ffgpu_exec_graph_captures",
-           "ffgpu_exec_profile", "ffgpu_exec_profile_steps", "ffgpu_exec_step_model", "ffgpu_groupconv_dev", "ffgpu_groupconv_kernel_name", "ffgpu_groupconv_time_dev", "ffgpu_irb_dev", "ffgpu_irb_plan_text", "ffgpu_irb_stage_plan_text", "ffgpu_irb_instantiations", "ffgpu_knobs_text", "ffgpu_dwpw_dev", "ffgpu_packed_records_bytes", "ffgpu_pack_records", "ffgpu_unpack_records",
+           "ffgpu_exec_profile", "ffgpu_exec_profile_steps", "ffgpu_exec_step_model", "ffgpu_groupconv_dev", "ffgpu_groupconv_kernel_name", "ffgpu_groupconv_time_dev", "ffgpu_irb_dev", "ffgpu_irb_plan_text", "ffgpu_irb_stage_plan_text", "ffgpu_front_plan_text", "ffgpu_irb_instantiations", "ffgpu_knobs_text", "ffgpu_dwpw_dev", "ffgpu_packed_records_bytes", "ffgpu_pack_records", "ffgpu_unpack_records",
            "ffgpu_shard_range", "ffgpu_node_create", "ffgpu_node_destroy", "ffgpu_node_ndev", "ffgpu_node_shard", "ffgpu_node_set_scale",
            "ffgpu_node_input_dev", "ffgpu_node_input_slot_dev", "ffgpu_node_depth", "ffgpu_node_rccl_ranks", "ffgpu_node_forward", "ffgpu_node_forward_host",
            "ffgpu_node_submit", "ffgpu_node_wait", "ffgpu_node_run",
@@ -380,6 +380,7 @@ def lib():
     L.ffgpu_irb_dev.argtypes = [vp] * 6 + [i] * 13 + [vp]
     L.ffgpu_irb_plan_text.argtypes = [i] * 12 + [C.c_char_p, i]
     L.ffgpu_irb_stage_plan_text.argtypes = [i] * 7 + [C.c_char_p, i]
+    L.ffgpu_front_plan_text.argtypes = [i] * 4 + [C.c_char_p, i]
     L.ffgpu_irb_instantiations.argtypes = [C.c_char_p, i]
     L.ffgpu_knobs_text.argtypes = [C.c_char_p, i]
     L.ffgpu_exec_read_boxes.argtypes = [vp, i, vp, i]
@@ -1853,6 +1854,18 @@ def irb_stage_plan_text(batch, iw, ih, blocks, act1=2, actd=2, flags=0):
     buf = C.create_string_buffer(1024)
     if lib().ffgpu_irb_stage_plan_text(batch, iw, ih, blocks, act1, actd, flags, buf, len(buf)) < 0:
         raise RuntimeError("ffgpu_irb_stage_plan_text failed: %s" % last_error())
+    return buf.value.decode()
+
+
+FRONT_FORMS = {"f32": 0, "u8": 1, "bgr_frames": 2, "nv12_frames": 3}
+
+
+def front_plan_text(batch, pw, ph, form="f32"):
+    """which instantiation of k_front a batch on a pw x ph plane (net input 2 pw x 2 ph) takes when it arrives in `form` (a key of FRONT_FORMS), and its launch
+    shape: "front<OC,U8,NC,RS,NV> W= H= N= band= nbands= ntasks= grid= block=", "staged" or "unsupported" (no GPU needed)"""
+    buf = C.create_string_buffer(256)
+    if lib().ffgpu_front_plan_text(batch, pw, ph, FRONT_FORMS[form], buf, len(buf)) < 0:
+        raise RuntimeError("ffgpu_front_plan_text failed: %s" % last_error())
     return buf.value.decode()
 
 

@@ -1356,6 +1356,30 @@ int ffgpu_front_nc(const IrbDesc &d)
 #define FFGPU_NV12_FRONT_DEFAULT 0
 bool ffgpu_front_nv12_fused() { return knob_or(K_NV12_FRONT, FFGPU_NV12_FRONT_DEFAULT) != 0; }
 
+// the launch shape of k_front for a planned thin block: rows per wave, bands per frame, waves, workgroups of four waves
+struct FrontGeom { int band, nbands, ntasks, grid; };
+static FrontGeom front_geom(const IrbDesc &d)
+{
+    FrontGeom g;
+    g.band = d.plan.front_band;
+    g.nbands = (d.H + g.band - 1) / g.band;
+    g.ntasks = d.N * g.nbands;
+    g.grid = (g.ntasks + 3) / 4;
+    return g;
+}
+
+// One line per launch of k_front (the probe behind ffgpu_front_plan_text): the instantiation ffgpu_launch_front dispatches to for `form` -- the template
+// arguments OC, U8, NC, RS, NV -- and the launch shape; "staged" where the form has no instantiation for the plane (the resizing forms at four columns per lane)
+int ffgpu_front_plan_line(const IrbDesc &d, InputForm form, char *buf, size_t cap)
+{
+    const bool resize = form == IN_BGR_FRAMES || form == IN_NV12_FRAMES;
+    const int nc = ffgpu_front_nc(d);
+    if (resize && nc != 3) return snprintf(buf, cap, "staged");
+    const FrontGeom g = front_geom(d);
+    return snprintf(buf, cap, "front<4,%d,%d,%d,%d> W=%d H=%d N=%d band=%d nbands=%d ntasks=%d grid=%d block=256",
+                    form != IN_F32, nc, resize, form == IN_NV12_FRAMES, d.W, d.H, d.N, g.band, g.nbands, g.ntasks, g.grid);
+}
+
 int ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, InputForm form, hipStream_t s)
 {
     const bool u8 = form == IN_U8, resize = form == IN_BGR_FRAMES || form == IN_NV12_FRAMES;
@@ -1367,11 +1391,10 @@ int ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, InputForm form, hipS
     p.in = c.in; p.in_ind = c.in_ind; p.prm = reinterpret_cast<const ExecParams *>(c.in_ind); p.out = d.out; p.f0 = c.filt; p.w1 = d.w1; p.wd = d.wd; p.w2 = d.w2;
     p.in_cs = c.in_cs; p.in_ns = c.in_ns;
     p.W = d.W; p.H = d.H; p.N = d.N;
-    p.band = d.plan.front_band;
-    p.nbands = (d.H + p.band - 1) / p.band;
-    p.ntasks = d.N * p.nbands;
+    const FrontGeom g = front_geom(d);
+    p.band = g.band; p.nbands = g.nbands; p.ntasks = g.ntasks;
     p.act0 = act_slope(c.act); p.act1 = act_slope(d.act1); p.actd = act_slope(d.actd); p.act2 = act_slope(d.act2);
-    const dim3 grid((unsigned)((p.ntasks + 3) / 4));
+    const dim3 grid((unsigned)g.grid);
     if (form == IN_NV12_FRAMES) {
         hipLaunchKernelGGL((k_front<4, true, 3, true, true>), grid, dim3(256), 0, s, p);
     } else if (resize) {

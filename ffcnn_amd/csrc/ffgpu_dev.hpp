@@ -99,6 +99,7 @@ bool   ffgpu_front_ok(const ConvDesc &c, const IrbDesc &d);      // first layer 
 enum InputForm { IN_F32, IN_U8, IN_BGR_FRAMES, IN_NV12_FRAMES, IN_FORMS };
 int    ffgpu_launch_front(const ConvDesc &c, const IrbDesc &d, InputForm form, hipStream_t s);
 bool   ffgpu_front_nv12_fused();                                 // NV12 frames go into the NV12 form of k_front where the plan has it (FFGPU_NV12_FRONT, else the measured default)
+int    ffgpu_front_plan_line(const IrbDesc &d, InputForm form, char *buf, size_t cap);   // the instantiation and launch shape for `form` as one line of text (ffgpu_front_plan_text)
 int    ffgpu_front_nc(const IrbDesc &d);                         // output columns per lane k_front uses for this block (3 or 4; the resizing form: 3 only)
 
 // depthwise K x K (stride 1, same padding) + pointwise 1 x 1 as one launch (ffgpu_dwpw.inc); dw.out == pw.in is never written

@@ -2009,6 +2009,17 @@ extern "C" int ffgpu_irb_plan_text(int batch, int iw, int ih, int ic, int ec, in
     return ffgpu_irb_plan_line(d, buf, (size_t)cap);
 }
 
+// pure host code: which instantiation of k_front a batch of `batch` frames on a plane of pw x ph takes (the net input is 2 pw x 2 ph) when it arrives in
+// `form` (0 fp32, 1 u8 frames of the net's size, 2 u8 BGR frames of any size, 3 NV12 frames), and the launch shape: the block's plan, then the launch's own arithmetic
+extern "C" int ffgpu_front_plan_text(int batch, int pw, int ph, int form, char *buf, int cap)
+{
+    if (!buf || cap < 1 || batch < 1 || pw < 1 || ph < 1 || form < 0 || form >= IN_FORMS) { ffgpu_set_error("front_plan_text: bad arguments"); return -1; }
+    IrbDesc d{};
+    irb_fill(d, batch, pw, ph, 8, 8, 4, 1, 0, 0, 0, 0);
+    if (!ffgpu_irb_plan(d) || d.plan.family != IRB_THIN) return snprintf(buf, (size_t)cap, "unsupported");
+    return ffgpu_front_plan_line(d, (InputForm)form, buf, (size_t)cap);
+}
+
 // pure host code: what an executor of `batch` frames made with `flags` does with a run of `blocks` blocks 48 -> 224 -> 48 on an iw x ih plane
 extern "C" int ffgpu_irb_stage_plan_text(int batch, int iw, int ih, int blocks, int act1, int actd, int flags, char *buf, int cap)
 {

@@ -342,6 +342,14 @@ int ffgpu_irb_plan_text(int batch, int iw, int ih, int ic, int ec, int oc, int s
  * block -- or "unsupported".  Pure host code (no device needed): for tests and logs. */
 int ffgpu_irb_stage_plan_text(int batch, int iw, int ih, int blocks, int act1, int actd, int flags, char *buf, int cap);
 
+/* Which instantiation of the first kernel (k_front: layers 0 - 3 of a net that starts like yolo-fastest) a batch takes and how it is
+ * launched, as one line of text in buf (at most cap bytes; returns snprintf's count).  pw x ph is the 8-channel plane (the net input is 2 pw x 2 ph);
+ * form: 0 fp32 frames, 1 u8 BGR frames of the net's size, 2 u8 BGR frames of any size, 3 NV12 frames.  The line reads
+ * "front<OC,U8,NC,RS,NV> W= H= N= band= nbands= ntasks= grid= block=" (the template arguments: NC = output columns per lane, RS / NV = the resizing
+ * BGR / NV12 gather), "staged" where the form has no instantiation for the plane, or "unsupported".  It describes the launch, not the planner's choice:
+ * whether a plan starts with k_front at all also depends on the batch (FFGPU_FRONT_MIN_PX) and FFGPU_NO_FRONT.  Pure host code (no device needed): for tests and logs. */
+int ffgpu_front_plan_text(int batch, int pw, int ph, int form, char *buf, int cap);
+
 /* The key of every instantiation the fused-block families have -- the first word of ffgpu_irb_plan_text's line -- one per line in buf
  * (at most cap bytes; returns snprintf's count): the thin ones, then the wave ones, then the workgroup ones for both wave counts, read
  * from the tables the planner dispatches through.  Pure host code: for tests that must reach every one of them. */

@@ -19,8 +19,8 @@ class _DevBuf:
         self.__cuda_array_interface__ = {"shape": (nbytes // 4,), "typestr": "<f4", "data": (ptr, False), "version": 2}
 
 
-def conv(filters, size, act, groups=1):
-    return "[convolutional]\n%sfilters=%d\nsize=%d\nstride=1\npad=%d\nactivation=%s\n\n" % ("groups=%d\n" % groups if groups > 1 else "", filters, size, 1 if size > 1 else 0, act)
+def conv(filters, size, act, groups=1, stride=1):
+    return "[convolutional]\n%sfilters=%d\nsize=%d\nstride=%d\npad=%d\nactivation=%s\n\n" % ("groups=%d\n" % groups if groups > 1 else "", filters, size, stride, 1 if size > 1 else 0, act)
 
 
 def block(act1, actd, ic=IC, ec=EC, oc=IC, frm=-5, dropout=True):
@@ -44,18 +44,8 @@ def rows(net, layer, fn, K):
     return net.weights_host()[off:off + fn * (k4 + 4)].reshape(fn, k4 + 4)
 
 
-def fill(net, filters):
-    """filters: [(f1, fd, f2)] per block"""
-    r0 = rows(net, 0, IC, 1)
-    r0[...] = 0
-    r0[:, 0] = 1.0
-    r0[:, 4] = 1.0
-    for b, (f1, fd, f2) in enumerate(filters):
-        p0 = first_layer(b)
-        rows(net, p0, EC, IC)[...] = f1
-        rows(net, p0 + 1, EC, 9)[...] = fd
-        rows(net, p0 + 2, IC, EC)[...] = f2
-    # the rows above are the host copy: write them over the device copy (the way a broadcast does), then refresh the packed images
+def commit(net):
+    """the rows written through rows() are the host copy: write them over the device copy (the way a broadcast does), then refresh the packed images"""
     import torch
     ptr, nbytes = net.weights_dev()
     host = net.weights_host()
@@ -63,6 +53,25 @@ def fill(net, filters):
     torch.as_tensor(_DevBuf(ptr, nbytes), device="cuda").copy_(torch.from_numpy(host.copy()))
     torch.cuda.synchronize()
     net.weights_commit()
+
+
+def put(net, layers):
+    """layers: [(layer index, K, filter rows (fn, k4 + 4))] of any cfg made of convolutions (tests/front uses it too); then commit"""
+    for layer, K, f in layers:
+        rows(net, layer, f.shape[0], K)[...] = f
+    commit(net)
+
+
+def fill(net, filters):
+    """filters: [(f1, fd, f2)] per block"""
+    ident = np.zeros((IC, 8), np.float32)
+    ident[:, 0] = 1.0
+    ident[:, 4] = 1.0
+    layers = [(0, 1, ident)]
+    for b, (f1, fd, f2) in enumerate(filters):
+        p0 = first_layer(b)
+        layers += [(p0, IC, f1), (p0 + 1, 9, fd), (p0 + 2, EC, f2)]
+    put(net, layers)
 
 
 def draw(seed, N, W, H, B):

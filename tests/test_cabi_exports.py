@@ -100,3 +100,16 @@ def test_irb_instantiations_lists_the_three_tables(capi):
     assert [k.split("<")[0] for k in keys] == ["thin"] * 4 + ["irbw2"] * 4 + ["irbw"] * 29 + ["irb"] * 24
     assert {"thin<8,8,4>", "irbw<6,2,1,2,big,x3>", "irbw2<2,3,x3>", "irb<2,3,1,1,8>", "irb<2,3,2,2,4>", "irbw<12,3,1,2,big,x3,xl>"} <= set(keys)
     assert capi.irb_plan_text((2, 16, 12, 8, 8, 4, 1, 2, 2, 0, 0)).split(" ")[0] in keys
+
+
+def test_front_plan_text_names_the_six_instantiations(capi, monkeypatch):
+    """ffgpu_front_plan_text: the template arguments ffgpu_launch_front dispatches on -- fp32 and u8 at three and four columns per lane, the resizing BGR form, the
+    NV12 form -- and the launch shape; the resizing forms are "staged" where the plane takes four columns"""
+    for v in ("FFGPU_FRONT_NC", "FFGPU_FRONT_BAND", "FFGPU_THIN_BAND", "FFGPU_NO_THIN"):
+        monkeypatch.delenv(v, raising=False)
+    heads = {(W, form): capi.front_plan_text(64, W, 160, form).split(" ")[0] for W in (160, 208) for form in capi.FRONT_FORMS}
+    assert heads == {(160, "f32"): "front<4,0,3,0,0>", (160, "u8"): "front<4,1,3,0,0>", (160, "bgr_frames"): "front<4,1,3,1,0>", (160, "nv12_frames"): "front<4,1,3,1,1>",
+                     (208, "f32"): "front<4,0,4,0,0>", (208, "u8"): "front<4,1,4,0,0>", (208, "bgr_frames"): "staged", (208, "nv12_frames"): "staged"}
+    assert capi.front_plan_text(64, 160, 160) == "front<4,0,3,0,0> W=160 H=160 N=64 band=16 nbands=10 ntasks=640 grid=160 block=256"
+    monkeypatch.setenv("FFGPU_FRONT_BAND", "3")
+    assert capi.front_plan_text(5, 16, 4).endswith(" band=3 nbands=2 ntasks=10 grid=3 block=256")
