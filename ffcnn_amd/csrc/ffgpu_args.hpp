@@ -116,6 +116,34 @@ int ffgpu_frame_table(const char *what, const FrameRole &role, const Frame *f, i
     return 0;
 }
 
+// -------------------------------------------------------------------------- colours and class tables
+// a colour of a spec (B G R or Y U V, a fourth byte ignored) as the kernels carry it: byte k in bits 8 k .. 8 k + 7
+inline unsigned ffgpu_pack_colour(const unsigned char *c) { return (unsigned)c[0] | (unsigned)c[1] << 8 | (unsigned)c[2] << 16; }
+
+// a spec's palette (npalette entries of 4 bytes), or without one its single `color`, packed into pal[256]: npal entries, the rest zero
+inline int ffgpu_palette_plan(const char *what, const unsigned char *palette, int npalette, const unsigned char *color, unsigned pal[256], int *npal)
+{
+    if (palette ? (npalette < 1 || npalette > 256) : npalette != 0) {
+        ffgpu_set_error("%s: npalette %d (0 with a NULL palette, else 1..256)", what, npalette);
+        return -1;
+    }
+    memset(pal, 0, sizeof(unsigned) * 256);
+    const unsigned char *src = palette ? palette : color;
+    *npal = palette ? npalette : 1;
+    for (int k = 0; k < *npal; k++) pal[k] = ffgpu_pack_colour(src + 4 * k);
+    return 0;
+}
+
+// a spec's class table: nclasses flags, or none
+inline int ffgpu_class_table_check(const char *what, const unsigned char *classes, int nclasses)
+{
+    if (classes ? (nclasses < 1 || nclasses > 256) : nclasses != 0) {
+        ffgpu_set_error("%s: nclasses %d (0 with NULL classes, else 1..256)", what, nclasses);
+        return -1;
+    }
+    return 0;
+}
+
 // -------------------------------------------------------------------------- where a post-pass finds its boxes
 // A post-pass runs behind a forward or a merge and reads one record per target, and either the record's own box[] or a full list.  Where those are is
 // this value: the operator forms build it from the caller's buffers (ffgpu_source_dev), the executor forms from the executor's (ffgpu_source_exec),

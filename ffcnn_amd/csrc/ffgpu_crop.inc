@@ -240,10 +240,7 @@ __global__ void __launch_bounds__(FFGPU_MAX_DET) k_crops_to_source(const int *ta
 // the selection's class table and margin, as the crop and the redact specs carry them
 int ffgpu_box_sel_check(const char *what, int nclasses, const unsigned char *classes, int margin_num, int margin_den)
 {
-    if (classes ? (nclasses < 1 || nclasses > 256) : nclasses != 0) {
-        ffgpu_set_error("%s: nclasses %d (0 with NULL classes, else 1..256)", what, nclasses);
-        return -1;
-    }
+    if (ffgpu_class_table_check(what, classes, nclasses)) return -1;
     if (margin_den < 1 || margin_den > 1024 || margin_num < 0 || margin_num > 4 * margin_den) {
         ffgpu_set_error("%s: margin %d / %d (den 1..1024, num 0..4 den)", what, margin_num, margin_den);
         return -1;

@@ -6,6 +6,8 @@
 #include <vector>
 #include "ffgpu_internal.h"
 #include "ffgpu_args.hpp"
+#include "ffgpu_streams_host.hpp"
+#include "ffgpu_track_host.hpp"
 #include "ffgpu_zones_host.hpp"
 #include "ffgpu_text_host.hpp"
 #include "ffgpu_lines_host.hpp"
@@ -221,9 +223,11 @@ int ffgpu_blur_spec_check(const char *what, const ffgpu_blur_spec *sp, BlurPlan 
 int ffgpu_launch_blur(const char *what, bool nv12, const DetSource &src, const std::vector<DrawTarget> &targets, const std::vector<DrawTarget> &scratch,
                       const BlurPlan &pl, hipStream_t s);
 
-// the detections tracked across a stream's frames (ffgpu_track.inc): the checks both entry points share, and the launches
-int ffgpu_track_args_check(const char *what, const int *streams, int ntargets, const ffgpu_track_spec *spec, const void *d_state, int nstreams,
-                           const void *d_ids, const void *d_out_records, const void *d_out_lists);
+// what the reset of every per-stream family ends in (ffgpu_kernels.hip): ffgpu_state_span's checks (ffgpu_streams_host.hpp), then the bytes cleared on `stream`
+int ffgpu_state_reset(const char *what, void *d_state, size_t all, int nstreams, int which_stream, void *stream);
+
+// the detections tracked across a stream's frames (ffgpu_track.inc): the launches; the checks both entry points share are host code with no HIP in it
+// (ffgpu_track_host.hpp)
 int ffgpu_launch_track(const DetSource &src, const int *streams, int ntargets, const ffgpu_track_spec &spec, void *d_state, void *d_ids, void *d_out_records, void *d_out_lists, hipStream_t s);
 
 // zones and lines (ffgpu_zones.inc): the launches; the checks both entry points share are host code with no HIP in it (ffgpu_zones_host.hpp)

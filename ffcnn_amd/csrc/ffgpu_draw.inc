@@ -126,15 +126,7 @@ int ffgpu_draw_style_check(const char *what, const ffgpu_draw_style *st, unsigne
 {
     if (!st) { ffgpu_set_error("%s: NULL style", what); return -1; }
     if (st->thickness < 1 || st->thickness > 8) { ffgpu_set_error("%s: thickness %d is outside 1..8", what, st->thickness); return -1; }
-    if (st->palette ? (st->npalette < 1 || st->npalette > 256) : st->npalette != 0) {
-        ffgpu_set_error("%s: npalette %d (0 with a NULL palette, else 1..256)", what, st->npalette);
-        return -1;
-    }
-    memset(pal, 0, sizeof(unsigned) * 256);
-    const unsigned char *src = st->palette ? st->palette : st->color;
-    *npal = st->palette ? st->npalette : 1;
-    for (int k = 0; k < *npal; k++) pal[k] = (unsigned)src[4 * k] | (unsigned)src[4 * k + 1] << 8 | (unsigned)src[4 * k + 2] << 16;
-    return 0;
+    return ffgpu_palette_plan(what, st->palette, st->npalette, st->color, pal, npal);
 }
 
 // targets[t] draws record t of `src`; DRAW_ARG_TARGETS targets per launch

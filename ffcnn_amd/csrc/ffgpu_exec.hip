@@ -1314,14 +1314,20 @@ extern "C" int ffgpu_exec_read_merged_boxes(ffgpu_exec *ex, int image, BBOX *hos
 
 // -------------------------------------------------------------------------- post-passes that read the boxes: draw, crop, track, relabel, redact
 // What the five post-passes that read boxes share: `which` as the executor's records and lists (ffgpu_source_exec) and the stream, which must be the
-// one the forward or merge ran on.  src.stride is the caller's to derive from src.longest.
-static int exec_source(ffgpu_exec *ex, const char *what, const char *family, const char *noun, int which, int ntargets, void *stream, DetSource &src, hipStream_t *s)
+// one the forward or merge ran on.  src.stride, the kernels' clamp of a list's length, comes from src.longest by the family's rule: where nothing is
+// pitched by it, a list too long for the kernel's int is clamped; where it is also the pitch of ids, rows or the caller's output lists, a list above 2^24
+// boxes is refused.
+enum StrideRule { STRIDE_CLAMPED, STRIDE_REFUSED };
+static int exec_source(ffgpu_exec *ex, const char *what, const char *family, const char *noun, StrideRule rule, int which, int ntargets, void *stream, DetSource &src,
+                       hipStream_t *s)
 {
     if (ffgpu_source_exec(what, family, which, ntargets, ex->N, ex->cand_cap, ex->d_merged ? &ex->mrg_off : nullptr, src)) return -1;
     *s = stream ? (hipStream_t)stream : ex->own_stream;
     if (*s != ex->last_stream) { ffgpu_set_error("%s: the %s must be enqueued on the stream of the forward or merge it follows", what, noun); return -1; }
     src.recs = which ? ex->d_merged : ex->d_dets;
     src.lists = which ? ex->d_merged_full : ex->d_full;
+    if (rule == STRIDE_REFUSED && src.longest > (1 << 24)) { ffgpu_set_error("%s: lists of up to %lld boxes are too long", what, src.longest); return -1; }
+    src.stride = (int)std::min(src.longest, (long long)0x7fffffff);
     return 0;
 }
 
@@ -1338,8 +1344,7 @@ static int exec_draw(ffgpu_exec *ex, const char *what, int which, const Frame *t
     if (ffgpu_draw_style_check(what, style, pal, &npal)) return -1;
     DetSource src;
     hipStream_t s;
-    if (exec_source(ex, what, "DRAW", "draw", which, ntargets, stream, src, &s)) return -1;
-    src.stride = (int)std::min(src.longest, (long long)0x7fffffff);  // a list too long for the kernel's int: clamped
+    if (exec_source(ex, what, "DRAW", "draw", STRIDE_CLAMPED, which, ntargets, stream, src, &s)) return -1;
     std::vector<DrawTarget> tab;
     if (ffgpu_frame_table(what, FRAME_DRAW, targets, ntargets, tab)) return -1;
     return ffgpu_launch_draw(std::is_same<Frame, ffgpu_nv12_frame>::value, src, tab, pal, npal, style->thickness, s);
@@ -1368,8 +1373,7 @@ static int exec_redact(ffgpu_exec *ex, const char *what, int which, const Frame 
     if (ffgpu_redact_spec_check(what, spec, nv12, pl)) return -1;
     DetSource src;
     hipStream_t s;
-    if (exec_source(ex, what, "REDACT", "redaction", which, ntargets, stream, src, &s)) return -1;
-    src.stride = (int)std::min(src.longest, (long long)0x7fffffff);  // (clamped, as the draw)
+    if (exec_source(ex, what, "REDACT", "redaction", STRIDE_CLAMPED, which, ntargets, stream, src, &s)) return -1;
     std::vector<DrawTarget> tab;
     if (ffgpu_frame_table(what, FRAME_DRAW, targets, ntargets, tab)) return -1;
     return ffgpu_launch_redact(what, nv12, src, tab, pl, s);
@@ -1399,8 +1403,7 @@ static int exec_blur(ffgpu_exec *ex, const char *what, int which, const Frame *t
     if (ffgpu_blur_spec_check(what, spec, pl)) return -1;
     DetSource src;
     hipStream_t s;
-    if (exec_source(ex, what, "BLUR", "blur", which, ntargets, stream, src, &s)) return -1;
-    src.stride = (int)std::min(src.longest, (long long)0x7fffffff);  // (clamped, as the draw)
+    if (exec_source(ex, what, "BLUR", "blur", STRIDE_CLAMPED, which, ntargets, stream, src, &s)) return -1;
     std::vector<DrawTarget> tab, stab;
     if (ffgpu_frame_table(what, FRAME_DRAW, targets, ntargets, tab) || ffgpu_frame_table(what, FRAME_SCRATCH, scratch, ntargets, stab)) return -1;
     return ffgpu_launch_blur(what, nv12, src, tab, stab, pl, s);
@@ -1431,8 +1434,7 @@ static int exec_crop(ffgpu_exec *ex, const char *what, int which, const Frame *s
     if (ffgpu_crop_spec_check(what, spec, pl) || ffgpu_crop_buffers_check(what, d_out, d_table, capacity)) return -1;
     DetSource src;
     hipStream_t s;
-    if (exec_source(ex, what, "CROP", "crop", which, ntargets, stream, src, &s)) return -1;
-    src.stride = (int)std::min(src.longest, (long long)0x7fffffff);  // (clamped, as the draw)
+    if (exec_source(ex, what, "CROP", "crop", STRIDE_CLAMPED, which, ntargets, stream, src, &s)) return -1;
     std::vector<CropSrc> tab;
     if (ffgpu_frame_table(what, FRAME_DRAW, sources, ntargets, tab)) return -1;
     return ffgpu_launch_crop(std::is_same<Frame, ffgpu_nv12_frame>::value, src, tab, pl, d_out, d_table, capacity, s);
@@ -1461,10 +1463,7 @@ extern "C" int ffgpu_exec_track(ffgpu_exec *ex, int which, const int *streams, i
     if (ffgpu_track_args_check(what, streams, ntargets, spec, d_state, nstreams, d_ids, d_out_records, d_out_lists)) return -1;
     DetSource src;
     hipStream_t s;
-    if (exec_source(ex, what, "TRACK", "tracker", which, ntargets, stream, src, &s)) return -1;
-    // the stride is also the pitch of the caller's output lists: a list too long is refused, not clamped
-    if (src.longest > (1 << 24)) { ffgpu_set_error("%s: lists of up to %lld boxes are too long", what, src.longest); return -1; }
-    src.stride = (int)src.longest;
+    if (exec_source(ex, what, "TRACK", "tracker", STRIDE_REFUSED, which, ntargets, stream, src, &s)) return -1;
     return ffgpu_launch_track(src, streams, ntargets, *spec, d_state, d_ids, d_out_records, d_out_lists, s);
 }
 
@@ -1479,10 +1478,7 @@ extern "C" int ffgpu_exec_zones(ffgpu_exec *ex, int which, const int *streams, i
     if (ffgpu_zones_args_check(what, streams, ntargets, spec, d_scenes, d_state, nstreams, d_ids, d_events, d_out_records, d_out_lists)) return -1;
     DetSource src;
     hipStream_t s;
-    if (exec_source(ex, what, "ZONES", "zones pass", which, ntargets, stream, src, &s)) return -1;
-    // the stride is also the pitch of the ids, the events and the caller's output lists: a list too long is refused, not clamped (as the tracker)
-    if (src.longest > (1 << 24)) { ffgpu_set_error("%s: lists of up to %lld boxes are too long", what, src.longest); return -1; }
-    src.stride = (int)src.longest;
+    if (exec_source(ex, what, "ZONES", "zones pass", STRIDE_REFUSED, which, ntargets, stream, src, &s)) return -1;
     return ffgpu_launch_zones(src, streams, ntargets, *spec, d_scenes, d_state, d_ids, d_events, d_out_records, d_out_lists, s);
 }
 
@@ -1498,10 +1494,7 @@ extern "C" int ffgpu_exec_trails(ffgpu_exec *ex, int which, const int *streams, 
     if (ffgpu_trails_args_check(what, streams, ntargets, spec, d_state, nstreams, d_ids, d_rows, d_items, items_stride, first_item, nitems, pl)) return -1;
     DetSource src;
     hipStream_t s;
-    if (exec_source(ex, what, "TRAILS", "trails pass", which, ntargets, stream, src, &s)) return -1;
-    // the stride is also the pitch of the ids and the rows: a list too long is refused, not clamped (as the tracker)
-    if (src.longest > (1 << 24)) { ffgpu_set_error("%s: lists of up to %lld boxes are too long", what, src.longest); return -1; }
-    src.stride = (int)src.longest;
+    if (exec_source(ex, what, "TRAILS", "trails pass", STRIDE_REFUSED, which, ntargets, stream, src, &s)) return -1;
     return ffgpu_launch_trails(src, streams, ntargets, pl, d_state, d_ids, d_rows, d_items, items_stride, first_item, nitems, s);
 }
 
@@ -1517,8 +1510,7 @@ extern "C" int ffgpu_exec_heat(ffgpu_exec *ex, int which, const int *streams, in
     if (ffgpu_heat_args_check(what, streams, ntargets, spec, d_state, nstreams, d_rows, pl)) return -1;
     DetSource src;
     hipStream_t s;
-    if (exec_source(ex, what, "HEAT", "heat pass", which, ntargets, stream, src, &s)) return -1;
-    src.stride = (int)std::min(src.longest, (long long)0x7fffffff);  // a list too long for the kernel's int: clamped (no output is pitched by it)
+    if (exec_source(ex, what, "HEAT", "heat pass", STRIDE_CLAMPED, which, ntargets, stream, src, &s)) return -1;
     return ffgpu_launch_heat(src, streams, ntargets, pl, d_state, d_rows, s);
 }
 
@@ -1535,10 +1527,7 @@ extern "C" int ffgpu_exec_motion_gate(ffgpu_exec *ex, int which, const int *stre
     if (ffgpu_motion_gate_args_check(what, streams, ntargets, spec, d_state, nstreams, d_words, d_out_records, d_out_lists, pl)) return -1;
     DetSource src;
     hipStream_t s;
-    if (exec_source(ex, what, "MOTION", "motion gate", which, ntargets, stream, src, &s)) return -1;
-    // the stride is also the pitch of the words and the caller's output lists: a list too long is refused, not clamped (as the zones pass)
-    if (src.longest > (1 << 24)) { ffgpu_set_error("%s: lists of up to %lld boxes are too long", what, src.longest); return -1; }
-    src.stride = (int)src.longest;
+    if (exec_source(ex, what, "MOTION", "motion gate", STRIDE_REFUSED, which, ntargets, stream, src, &s)) return -1;
     return ffgpu_launch_motion_gate(src, streams, ntargets, pl, d_state, d_words, d_out_records, d_out_lists, s);
 }
 
@@ -1555,10 +1544,7 @@ static int exec_caption(ffgpu_exec *ex, const char *what, int which, const Frame
     if (ffgpu_caption_boxes_args_check(what, spec, d_ids, d_items, items_stride, pl)) return -1;
     DetSource src;
     hipStream_t s;
-    if (exec_source(ex, what, "CAPTION", "caption", which, ntargets, stream, src, &s)) return -1;
-    // with ids the stride is also their pitch, the tracker's S: a list too long is refused as the tracker refuses it; without, clamped as the draw
-    if (d_ids && src.longest > (1 << 24)) { ffgpu_set_error("%s: lists of up to %lld boxes are too long", what, src.longest); return -1; }
-    src.stride = (int)std::min(src.longest, (long long)0x7fffffff);
+    if (exec_source(ex, what, "CAPTION", "caption", d_ids ? STRIDE_REFUSED : STRIDE_CLAMPED, which, ntargets, stream, src, &s)) return -1;
     std::vector<DrawTarget> tab;
     if (ffgpu_frame_table(what, FRAME_DRAW, targets, ntargets, tab)) return -1;
     if (ffgpu_launch_caption_boxes(src, ntargets, pl, d_ids, d_items, items_stride, s)) return -1;
@@ -1645,9 +1631,7 @@ extern "C" int ffgpu_exec_relabel(ffgpu_exec *ex, int which, const void *d_table
     if (ffgpu_relabel_args_check(what, d_table, capacity, d_labels, k, ntargets, spec, d_out_records)) return -1;
     DetSource src;
     hipStream_t s;
-    if (exec_source(ex, what, "RELABEL", "relabelling", which, ntargets, stream, src, &s)) return -1;
-    if (src.longest > (1 << 24)) { ffgpu_set_error("%s: lists of up to %lld boxes are too long", what, src.longest); return -1; }   // (refused, as the tracker)
-    src.stride = (int)src.longest;
+    if (exec_source(ex, what, "RELABEL", "relabelling", STRIDE_REFUSED, which, ntargets, stream, src, &s)) return -1;
     return ffgpu_launch_relabel(d_table, capacity, d_labels, k, src, ntargets, *spec, d_out_records, d_out_lists, s);
 }
 

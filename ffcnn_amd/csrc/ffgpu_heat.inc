@@ -17,10 +17,7 @@
 #define HEAT_BLOCK     64                             // the side of a blend block, in pixels
 #define HEAT_REACH     34                             // cells per side a block can reach: 64 / 2 + 2
 struct HeatArgs {
-    long long first[HEAT_ARG_ENTRIES];                // entry e: its list's first box in `lists`
-    int   rec[HEAT_ARG_ENTRIES];                      //          its record
-    int   gstream[HEAT_ARG_ENTRIES];                  // group g (= workgroup g): its video stream, or -1: the ignored entries
-    int   goff[HEAT_ARG_ENTRIES + 1];                 //          its entries goff[g] .. goff[g + 1] - 1
+    StreamEntries<HEAT_ARG_ENTRIES> en;               // the launch's records, grouped by video stream (ffgpu_streams_host.hpp)
     unsigned char classes[256];
     int   nclasses, gw, gh, cell_log2, mode, anchor, spread, gain, decay_shift, ngroups;
     float min_score;
@@ -52,10 +49,10 @@ __global__ void __launch_bounds__(256) k_heat_accumulate(HeatArgs a, const ffgpu
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) unsigned char s_heat[];
     const int tid = threadIdx.x, g = blockIdx.x;
-    const int e0 = a.goff[g], e1 = a.goff[g + 1], vs = a.gstream[g];
+    const int e0 = a.en.goff[g], e1 = a.en.goff[g + 1], vs = a.en.gstream[g];
     if (vs < 0) {                                                                     // the ignored entries: every output byte zero (uniform)
         for (int e = e0; e < e1; e++)
-            if (tid < FFGPU_HEAT_ROW) rows[(long)a.rec[e] * FFGPU_HEAT_ROW + tid] = 0;
+            if (tid < FFGPU_HEAT_ROW) rows[(long)a.en.rec[e] * FFGPU_HEAT_ROW + tid] = 0;
         return;
     }
     const int gw = a.gw, gh = a.gh, ncell = gw * gh, k = a.cell_log2;
@@ -76,10 +73,10 @@ __global__ void __launch_bounds__(256) k_heat_accumulate(HeatArgs a, const ffgpu
     const int dmask = by_box ? 0 : 31;                                                // FFGPU_HEAT_BOX: gain >> 0 whatever the distance
 
     for (int e = e0; e < e1; e++) {
-        const long t = a.rec[e];
+        const long t = a.en.rec[e];
         const ffgpu_frame_dets *rec = recs + t;
         const int n = max(0, min(lists ? rec->nfull : rec->count, stride));
-        const BBOX *list = lists ? lists + a.first[e] : rec->box;
+        const BBOX *list = lists ? lists + a.en.first[e] : rec->box;
 
         // 1. the considered boxes, in list order; each straight into its footprint
         const long nq = block_consider(n, FFGPU_HEAT_DETS, L.wsum,
@@ -332,8 +329,7 @@ int ffgpu_launch_heat(const DetSource &src, const int *streams, int ntargets, co
         memcpy(a.classes, pl.classes, sizeof a.classes);
         a.nclasses = pl.nclasses; a.gw = pl.gw; a.gh = pl.gh; a.cell_log2 = pl.cell_log2; a.mode = pl.mode; a.anchor = pl.anchor; a.spread = pl.spread;
         a.gain = pl.gain; a.decay_shift = pl.decay_shift; a.min_score = pl.min_score;
-        a.ngroups = ffgpu_group_by_stream(streams, t0, nt, a.rec, a.gstream, a.goff);
-        for (int i = 0; i < nt; i++) a.first[i] = src.first[a.rec[i]];
+        a.ngroups = ffgpu_stream_entries(src.first, streams, t0, nt, a.en);
         hipLaunchKernelGGL(k_heat_accumulate, dim3((unsigned)a.ngroups), dim3(256), lds, s, a, src.recs, src.lists, src.stride, (unsigned char *)d_state, (int *)d_rows);
         LAUNCH_OK("heat_boxes");
     }
@@ -344,19 +340,9 @@ extern "C" int ffgpu_heat_reset_dev(void *d_state, int nstreams, int gw, int gh,
 {
     const char *const what = "heat_reset_dev";
     if (ffgpu_no_device(what)) return -1;
-    if (!d_state) { ffgpu_set_error("%s: NULL state", what); return -1; }
     const size_t all = ffgpu_heat_state_bytes(nstreams, gw, gh);
-    if (!all) { ffgpu_set_error("%s: %d streams of %d x %d cells (nstreams 1..65536, gw and gh 1..%d)", what, nstreams, gw, gh, HEAT_GRID_MAX); return -1; }
-    if (reinterpret_cast<uintptr_t>(d_state) & 15) { ffgpu_set_error("%s: the state must be 16-byte aligned", what); return -1; }
-    if (which_stream < -1 || which_stream >= nstreams) { ffgpu_set_error("%s: stream %d is outside -1 .. %d", what, which_stream, nstreams - 1); return -1; }
-    const size_t one = all / (size_t)nstreams;
-    unsigned char *p = (unsigned char *)d_state + (which_stream < 0 ? 0 : one * (size_t)which_stream);
-    if (hipMemsetAsync(p, 0, which_stream < 0 ? all : one, (hipStream_t)stream) != hipSuccess) {
-        (void)hipGetLastError();
-        ffgpu_set_error("%s: hipMemsetAsync failed", what);
-        return -1;
-    }
-    return 0;
+    if (!all) ffgpu_set_error("%s: %d streams of %d x %d cells (nstreams 1..65536, gw and gh 1..%d)", what, nstreams, gw, gh, HEAT_GRID_MAX);   // (stands unless the state is NULL)
+    return ffgpu_state_reset(what, d_state, all, nstreams, which_stream, stream);
 }
 
 extern "C" int ffgpu_heat_boxes_dev(const void *d_records, const void *d_lists, int list_stride, const int *list_first, const int *streams, int ntargets,

@@ -2,9 +2,11 @@
 // ffgpu_heat_blend_spec_check, ffgpu_heat_palette, ffgpu_heat_boxes_dev, ffgpu_exec_heat, ffgpu_heat_blend_*_dev) before anything reaches the device:
 // the state's size, the two specs resolved into plans, the built-in palette, the argument checks.  Plain C++17 with no HIP in it: every function
 // reports through ffgpu_set_error and touches no device, so san/heat_driver.cc runs the same lines on the CPU under ASan + UBSan
-// (tests/test_heat_abi.py).  The grouping of a launch's records by stream is ffgpu_zones_host.hpp's; the targets are ffgpu_args.hpp's.
+// (tests/test_heat_abi.py).  The launch's entry table and the stream checks are ffgpu_streams_host.hpp's; the targets, the
+// palette's packing and the class table's check are ffgpu_args.hpp's.
 #pragma once
 #include "ffgpu_args.hpp"
+#include "ffgpu_streams_host.hpp"
 #include "ffgpu_zones_host.hpp"
 
 static_assert(sizeof(ffgpu_heat_spec) == 56 && sizeof(ffgpu_heat_blend_spec) == 48, "include/ffcnn_hip.h states these sizes");
@@ -48,10 +50,7 @@ inline int ffgpu_heat_spec_plan(const char *what, const ffgpu_heat_spec *sp, Hea
     if (sp->mode == FFGPU_HEAT_BOX && sp->spread != 0) { ffgpu_set_error("%s: spread %d with FFGPU_HEAT_BOX (0 then)", what, sp->spread); return -1; }
     if (sp->gain < 1 || sp->gain > 65536) { ffgpu_set_error("%s: gain %d is outside 1..65536", what, sp->gain); return -1; }
     if (sp->decay_shift < 0 || sp->decay_shift > 16) { ffgpu_set_error("%s: decay_shift %d is outside 0..16", what, sp->decay_shift); return -1; }
-    if (sp->classes ? (sp->nclasses < 1 || sp->nclasses > 256) : sp->nclasses != 0) {
-        ffgpu_set_error("%s: nclasses %d (0 with NULL classes, else 1..256)", what, sp->nclasses);
-        return -1;
-    }
+    if (ffgpu_class_table_check(what, sp->classes, sp->nclasses)) return -1;
     if (sp->reserved != 0) { ffgpu_set_error("%s: spec: reserved must be 0", what); return -1; }
     pl.gw = sp->gw; pl.gh = sp->gh; pl.cell_log2 = sp->cell_log2; pl.mode = sp->mode; pl.anchor = sp->anchor; pl.spread = sp->spread; pl.gain = sp->gain;
     pl.decay_shift = sp->decay_shift; pl.nclasses = sp->nclasses; pl.min_score = sp->min_score;
@@ -105,8 +104,8 @@ inline int ffgpu_heat_blend_spec_plan(const char *what, const ffgpu_heat_blend_s
     unsigned char own[1024];
     const unsigned char *src = sp->palette;
     if (!src) { ffgpu_heat_palette_host(nv12 ? 1 : 0, own); src = own; }
-    for (int k = 0; k < 256; k++) pl.pal[k] = (unsigned)src[4 * k] | (unsigned)src[4 * k + 1] << 8 | (unsigned)src[4 * k + 2] << 16;
-    return 0;
+    int npal;
+    return ffgpu_palette_plan(what, src, 256, nullptr, pl.pal, &npal);                  // (all 256 entries: the check inside cannot fail)
 }
 
 // what the accumulate operator and the executor form check alike, before either looks at its records
@@ -117,12 +116,8 @@ inline int ffgpu_heat_args_check(const char *what, const int *streams, int ntarg
     if (ffgpu_heat_spec_plan(what, spec, pl)) return -1;
     if (!d_state) { ffgpu_set_error("%s: NULL state", what); return -1; }
     if (!d_rows) { ffgpu_set_error("%s: NULL rows", what); return -1; }
-    if (ntargets < 1 || ntargets > (1 << 24)) { ffgpu_set_error("%s: %d targets (ntargets >= 1)", what, ntargets); return -1; }
-    if (nstreams < 1 || nstreams > 65536) { ffgpu_set_error("%s: nstreams %d is outside 1..65536", what, nstreams); return -1; }
-    if (reinterpret_cast<uintptr_t>(d_state) & 15) { ffgpu_set_error("%s: the state must be 16-byte aligned", what); return -1; }
-    for (int t = 0; t < ntargets; t++)
-        if (streams[t] < -1 || streams[t] >= nstreams) { ffgpu_set_error("%s: target %d: stream %d is outside -1 .. %d", what, t, streams[t], nstreams - 1); return -1; }
-    return 0;
+    if (ffgpu_streams_check(what, ntargets, nstreams, d_state)) return -1;
+    return ffgpu_stream_range_check(what, streams, ntargets, nstreams);
 }
 
 // the blend's arguments: the spec, the state, the streams and the descriptors into the table the launches take (a target of stream -1: skipped)
@@ -134,11 +129,8 @@ int ffgpu_heat_blend_args_check(const char *what, const void *d_state, int nstre
     if (!streams) { ffgpu_set_error("%s: NULL streams", what); return -1; }
     if (!targets) { ffgpu_set_error("%s: NULL targets", what); return -1; }
     if (ffgpu_heat_blend_spec_plan(what, spec, nv12, pl)) return -1;
-    if (ntargets < 1 || ntargets > (1 << 24)) { ffgpu_set_error("%s: %d targets (ntargets >= 1)", what, ntargets); return -1; }
-    if (nstreams < 1 || nstreams > 65536) { ffgpu_set_error("%s: nstreams %d is outside 1..65536", what, nstreams); return -1; }
-    if (reinterpret_cast<uintptr_t>(d_state) & 15) { ffgpu_set_error("%s: the state must be 16-byte aligned", what); return -1; }
-    for (int t = 0; t < ntargets; t++)
-        if (streams[t] < -1 || streams[t] >= nstreams) { ffgpu_set_error("%s: target %d: stream %d is outside -1 .. %d", what, t, streams[t], nstreams - 1); return -1; }
+    if (ffgpu_streams_check(what, ntargets, nstreams, d_state)) return -1;
+    if (ffgpu_stream_range_check(what, streams, ntargets, nstreams)) return -1;
     if (ffgpu_frame_table(what, FRAME_DRAW, targets, ntargets, tab)) return -1;
     for (int t = 0; t < ntargets; t++) {
         tab[t].first = streams[t];                                                // (the blend reads no list: the slot carries the stream)

@@ -469,6 +469,21 @@ static int lds_allow(const void *fn, size_t lds, const char *what)
     return 0;
 }
 
+// the reset of a per-stream family (ffgpu_<family>_reset_dev): one stream's block of the state, or all of it, zeroed on `stream`.  all == 0: the
+// family has set its message for that
+int ffgpu_state_reset(const char *what, void *d_state, size_t all, int nstreams, int which_stream, void *stream)
+{
+    size_t off, len;
+    if (ffgpu_state_span(what, d_state, all, nstreams, which_stream, off, len)) return -1;
+    unsigned char *p = (unsigned char *)d_state + off;
+    if (hipMemsetAsync(p, 0, len, (hipStream_t)stream) != hipSuccess) {
+        (void)hipGetLastError();
+        ffgpu_set_error("%s: hipMemsetAsync failed", what);
+        return -1;
+    }
+    return 0;
+}
+
 #include "ffgpu_input.inc"
 #include "ffgpu_conv_kernels.inc"
 

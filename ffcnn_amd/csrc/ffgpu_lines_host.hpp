@@ -31,16 +31,10 @@ inline int ffgpu_outline_spec_plan(const char *what, const ffgpu_outline_spec *s
     if (sp->line_dash < 0 || sp->line_dash > 6) { ffgpu_set_error("%s: line_dash %d is outside 0..6", what, sp->line_dash); return -1; }
     if (sp->marker < 0 || sp->marker > 32) { ffgpu_set_error("%s: marker %d is outside 0..32", what, sp->marker); return -1; }
     if ((sp->flags & FFGPU_OUTLINE_MARKERS) && sp->marker < 1) { ffgpu_set_error("%s: marker %d with FFGPU_OUTLINE_MARKERS (at least 1)", what, sp->marker); return -1; }
-    if (sp->palette ? (sp->npalette < 1 || sp->npalette > 256) : sp->npalette != 0) {
-        ffgpu_set_error("%s: npalette %d (0 with a NULL palette, else 1..256)", what, sp->npalette);
-        return -1;
-    }
+    if (ffgpu_palette_plan(what, sp->palette, sp->npalette, sp->color, pl.pal, &pl.npal)) return -1;
     if (sp->reserved != 0) { ffgpu_set_error("%s: reserved must be 0", what); return -1; }
     pl.flags = sp->flags; pl.thickness = sp->thickness; pl.line_dash = sp->line_dash; pl.marker = sp->marker;
-    pl.alarm = (unsigned)sp->alarm[0] | (unsigned)sp->alarm[1] << 8 | (unsigned)sp->alarm[2] << 16;
-    const unsigned char *src = sp->palette ? sp->palette : sp->color;
-    pl.npal = sp->palette ? sp->npalette : 1;
-    for (int k = 0; k < pl.npal; k++) pl.pal[k] = (unsigned)src[4 * k] | (unsigned)src[4 * k + 1] << 8 | (unsigned)src[4 * k + 2] << 16;
+    pl.alarm = ffgpu_pack_colour(sp->alarm);
     return 0;
 }
 

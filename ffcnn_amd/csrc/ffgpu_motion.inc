@@ -316,22 +316,9 @@ extern "C" int ffgpu_motion_reset_dev(void *d_state, int nstreams, int w, int h,
 {
     const char *const what = "motion_reset_dev";
     if (ffgpu_no_device(what)) return -1;
-    if (!d_state) { ffgpu_set_error("%s: NULL state", what); return -1; }
     const size_t all = ffgpu_motion_state_bytes(nstreams, w, h, cell_log2);
-    if (!all) {
-        ffgpu_set_error("%s: %d streams of %d x %d pixels, cell_log2 %d (nstreams 1..65536, w and h 1..%d, cell_log2 2..6)", what, nstreams, w, h, cell_log2, FFGPU_MOTION_MAX_SIDE);
-        return -1;
-    }
-    if (reinterpret_cast<uintptr_t>(d_state) & 15) { ffgpu_set_error("%s: the state must be 16-byte aligned", what); return -1; }
-    if (which_stream < -1 || which_stream >= nstreams) { ffgpu_set_error("%s: stream %d is outside -1 .. %d", what, which_stream, nstreams - 1); return -1; }
-    const size_t one = all / (size_t)nstreams;
-    unsigned char *p = (unsigned char *)d_state + (which_stream < 0 ? 0 : one * (size_t)which_stream);
-    if (hipMemsetAsync(p, 0, which_stream < 0 ? all : one, (hipStream_t)stream) != hipSuccess) {
-        (void)hipGetLastError();
-        ffgpu_set_error("%s: hipMemsetAsync failed", what);
-        return -1;
-    }
-    return 0;
+    if (!all) ffgpu_set_error("%s: %d streams of %d x %d pixels, cell_log2 %d (nstreams 1..65536, w and h 1..%d, cell_log2 2..6)", what, nstreams, w, h, cell_log2, FFGPU_MOTION_MAX_SIDE);   // (stands unless the state is NULL)
+    return ffgpu_state_reset(what, d_state, all, nstreams, which_stream, stream);
 }
 
 // Round r of a call -- the r-th frame of every stream in it -- behind round r - 1, MOTION_ARG_TARGETS targets per launch: the update, then the rows

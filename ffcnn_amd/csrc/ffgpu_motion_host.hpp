@@ -2,9 +2,11 @@
 // ffgpu_motion_update_*_dev, ffgpu_motion_gate_dev, ffgpu_exec_motion_gate) before anything reaches the device: the state's layout, the spec
 // resolved into a plan, the argument checks of the update and of the gate, and the rounds an update call is enqueued in.  Plain C++17 with no HIP in
 // it: every function reports through ffgpu_set_error and touches no device, so san/motion_driver.cc runs the same lines on the CPU under
-// ASan + UBSan (tests/test_motion_abi.py).  The targets are ffgpu_args.hpp's.
+// ASan + UBSan (tests/test_motion_abi.py).  The targets and the class table's check are ffgpu_args.hpp's, the stream checks
+// ffgpu_streams_host.hpp's.
 #pragma once
 #include "ffgpu_args.hpp"
+#include "ffgpu_streams_host.hpp"
 
 static_assert(sizeof(ffgpu_motion_spec) == 64, "include/ffcnn_hip.h states this size");
 static_assert(FFGPU_MOTION_ENTRIES == 0 && FFGPU_MOTION_MERGED == 1, "ffgpu_source_exec: one check of `which` serves every family");
@@ -58,10 +60,7 @@ inline int ffgpu_motion_spec_plan(const char *what, const ffgpu_motion_spec *sp,
     if (sp->cover < 1 || sp->cover > 256) { ffgpu_set_error("%s: cover %d is outside 1..256", what, sp->cover); return -1; }
     if (sp->warmup < 0 || sp->warmup > 65535) { ffgpu_set_error("%s: warmup %d is outside 0..65535", what, sp->warmup); return -1; }
     if (sp->flags & ~FFGPU_MOTION_GATE_INVERT) { ffgpu_set_error("%s: unknown flags 0x%x", what, (unsigned)sp->flags); return -1; }
-    if (sp->classes ? (sp->nclasses < 1 || sp->nclasses > 256) : sp->nclasses != 0) {
-        ffgpu_set_error("%s: nclasses %d (0 with NULL classes, else 1..256)", what, sp->nclasses);
-        return -1;
-    }
+    if (ffgpu_class_table_check(what, sp->classes, sp->nclasses)) return -1;
     if (sp->reserved[0] != 0 || sp->reserved[1] != 0) { ffgpu_set_error("%s: spec: reserved must be 0", what); return -1; }
     ffgpu_motion_layout(sp->w, sp->h, sp->cell_log2, pl.lay);
     pl.threshold = sp->threshold; pl.learn_shift = sp->learn_shift; pl.learn_shift_changed = sp->learn_shift_changed; pl.min_pixels = sp->min_pixels;
@@ -78,12 +77,8 @@ inline int ffgpu_motion_common_check(const char *what, const int *streams, int n
     if (ffgpu_motion_spec_plan(what, spec, pl)) return -1;
     if (!d_state) { ffgpu_set_error("%s: NULL state", what); return -1; }
     if (!d_out) { ffgpu_set_error("%s: NULL %s", what, out); return -1; }
-    if (ntargets < 1 || ntargets > (1 << 24)) { ffgpu_set_error("%s: %d targets (ntargets >= 1)", what, ntargets); return -1; }
-    if (nstreams < 1 || nstreams > 65536) { ffgpu_set_error("%s: nstreams %d is outside 1..65536", what, nstreams); return -1; }
-    if (reinterpret_cast<uintptr_t>(d_state) & 15) { ffgpu_set_error("%s: the state must be 16-byte aligned", what); return -1; }
-    for (int t = 0; t < ntargets; t++)
-        if (streams[t] < -1 || streams[t] >= nstreams) { ffgpu_set_error("%s: target %d: stream %d is outside -1 .. %d", what, t, streams[t], nstreams - 1); return -1; }
-    return 0;
+    if (ffgpu_streams_check(what, ntargets, nstreams, d_state)) return -1;
+    return ffgpu_stream_range_check(what, streams, ntargets, nstreams);
 }
 
 // The update's arguments: the spec, the state, the streams and the descriptors into the table the launches take.  tab[t].first carries the target's

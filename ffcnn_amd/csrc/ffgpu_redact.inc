@@ -208,7 +208,7 @@ int ffgpu_redact_spec_check(const char *what, const ffgpu_redact_spec *sp, bool 
     memset(&pl, 0, sizeof pl);
     pl.mode = sp->mode; pl.cell = sp->cell; pl.outside = sp->flags & FFGPU_REDACT_OUTSIDE; pl.min_score = sp->min_score;
     pl.nclasses = sp->nclasses; pl.num = sp->margin_num; pl.den = sp->margin_den;
-    pl.colour = (unsigned)sp->color[0] | (unsigned)sp->color[1] << 8 | (unsigned)sp->color[2] << 16;
+    pl.colour = ffgpu_pack_colour(sp->color);
     if (sp->classes) memcpy(pl.classes, sp->classes, (size_t)sp->nclasses);
     return 0;
 }

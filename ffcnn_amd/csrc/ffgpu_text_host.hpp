@@ -6,9 +6,8 @@
 #include <stdint.h>
 #include <string.h>
 #include <math.h>
-#include "ffcnn_hip.h"
-
-extern "C" void ffgpu_set_error(const char *fmt, ...);
+#include "ffgpu_args.hpp"
+#include "ffgpu_streams_host.hpp"
 
 static_assert(sizeof(ffgpu_text_item) == 64 && sizeof(ffgpu_caption_spec) == 48, "include/ffcnn_hip.h states these sizes");
 #define FONT8_GLYPHS          96                      // ffgpu_font8.inc: the ASCII glyphs 32..126, then the unknown glyph
@@ -57,15 +56,9 @@ inline int ffgpu_caption_spec_check(const char *what, const ffgpu_caption_spec *
         pl.min_score = sp->min_score; pl.identity = sp->identity; pl.nnames = sp->nnames; pl.d_names = sp->d_names;
     }
     if (sp->scale < 1 || sp->scale > 4) { ffgpu_set_error("%s: scale %d is outside 1..4", what, sp->scale); return -1; }
-    if (sp->palette ? (sp->npalette < 1 || sp->npalette > 256) : sp->npalette != 0) {
-        ffgpu_set_error("%s: npalette %d (0 with a NULL palette, else 1..256)", what, sp->npalette);
-        return -1;
-    }
+    if (ffgpu_palette_plan(what, sp->palette, sp->npalette, sp->color, pl.pal, &pl.npal)) return -1;
     pl.flags = sp->flags; pl.scale = sp->scale;
-    pl.fg = (unsigned)sp->fg[0] | (unsigned)sp->fg[1] << 8 | (unsigned)sp->fg[2] << 16;
-    const unsigned char *src = sp->palette ? sp->palette : sp->color;
-    pl.npal = sp->palette ? sp->npalette : 1;
-    for (int k = 0; k < pl.npal; k++) pl.pal[k] = (unsigned)src[4 * k] | (unsigned)src[4 * k + 1] << 8 | (unsigned)src[4 * k + 2] << 16;
+    pl.fg = ffgpu_pack_colour(sp->fg);
     return 0;
 }
 
@@ -123,9 +116,7 @@ inline int ffgpu_scene_source_ranges_check(const char *what, const void *d_scene
         ffgpu_set_error("%s: the scenes, the state and the events must be 4-byte aligned", what);
         return -1;
     }
-    for (int t = 0; t < ntargets; t++)
-        if (streams[t] < -1 || streams[t] >= nstreams) { ffgpu_set_error("%s: target %d: stream %d is outside -1 .. %d", what, t, streams[t], nstreams - 1); return -1; }
-    return 0;
+    return ffgpu_stream_range_check(what, streams, ntargets, nstreams);
 }
 
 inline int ffgpu_caption_scene_args_check(const char *what, const void *d_scenes, const void *d_state, int nstreams, int capacity, const void *d_events,

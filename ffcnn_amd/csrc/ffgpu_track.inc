@@ -1,6 +1,6 @@
 // ffgpu_track.inc -- the detections tracked across a stream's frames on the device (ffgpu_track_boxes_dev, ffgpu_exec_track, ffgpu_track_reset_dev,
 // ffgpu_track_state_bytes): a greedy, class-aware IoU tracker with "last box, no motion model", specified so that its result is a pure function of
-// its inputs.  The contract is in include/ffcnn_hip.h.
+// its inputs.  The contract is in include/ffcnn_hip.h; the host side (spec and argument checks) is ffgpu_track_host.hpp.
 //
 // One workgroup per video stream and launch: it loads the stream's state into LDS once, walks the stream's records of the launch serially and writes
 // the state back once.  Per frame: the considered detections are compacted into LDS by ballots (list order kept), the IoU of every (slot, detection)
@@ -15,15 +15,11 @@
 #define TRACK_ARG_ENTRIES 128
 #define TRACK_PITCH       (FFGPU_TRACK_DETS + 1)      // floats per matrix row: row a starts in bank a
 struct TrackArgs {
-    long long first[TRACK_ARG_ENTRIES];               // entry e: its list's first box in `lists`
-    int   rec[TRACK_ARG_ENTRIES];                     //          its record
-    int   gstream[TRACK_ARG_ENTRIES];                 // group g (= workgroup g): its video stream, or -1: the ignored entries
-    int   goff[TRACK_ARG_ENTRIES + 1];                //          its entries goff[g] .. goff[g + 1] - 1
+    StreamEntries<TRACK_ARG_ENTRIES> en;              // the launch's records, grouped by video stream (ffgpu_streams_host.hpp)
     ffgpu_track_spec spec;
     int   ngroups, pad_[3];
 };
 static_assert(sizeof(TrackArgs) + 7 * 8 <= 4096 - 256, "the tables travel as a kernel argument (4 KB at most, the hidden arguments included)");
-static_assert(sizeof(ffgpu_track) == 48 && sizeof(ffgpu_track_spec) == 32, "include/ffcnn_hip.h states these sizes");
 static_assert(FFGPU_TRACK_DETS == 128 && FFGPU_TRACK_DETS == 2 * WAVE, "k_track: waves 0 and 1 own the detections, waves 2 and 3 the slots");
 
 // the workgroup's LDS, all of it dynamic (above 64 KB: allowed per kernel and per device like k_spp's)
@@ -50,11 +46,11 @@ __global__ void __launch_bounds__(256) k_track(TrackArgs a, const ffgpu_frame_de
     extern __shared__ __attribute__((aligned(16))) unsigned char s_track[];
     TrackLds &L = *reinterpret_cast<TrackLds *>(s_track);
     const int tid = threadIdx.x, g = blockIdx.x;
-    const int e0 = a.goff[g], e1 = a.goff[g + 1], vs = a.gstream[g], C = a.spec.capacity;
+    const int e0 = a.en.goff[g], e1 = a.en.goff[g + 1], vs = a.en.gstream[g], C = a.spec.capacity;
     const long rowlen = 8 + (long)stride;
     if (vs < 0) {                                                                     // the ignored entries: every output byte zero (uniform)
         for (int e = e0; e < e1; e++) {
-            const long t = a.rec[e];
+            const long t = a.en.rec[e];
             for (long i = tid; i < rowlen; i += blockDim.x) ids[t * rowlen + i] = 0;
             if (out_recs) for (int i = tid; i < (int)(sizeof(ffgpu_frame_dets) / sizeof(int)); i += blockDim.x) reinterpret_cast<int *>(out_recs + t)[i] = 0;
             if (out_lists) for (long i = tid; i < stride; i += blockDim.x) track_zero(out_lists + t * stride + i);
@@ -70,10 +66,10 @@ __global__ void __launch_bounds__(256) k_track(TrackArgs a, const ffgpu_frame_de
     const float min_score = a.spec.min_score, birth_score = a.spec.birth_score, thr = a.spec.iou_thresh;
 
     for (int e = e0; e < e1; e++) {
-        const long t = a.rec[e];
+        const long t = a.en.rec[e];
         const ffgpu_frame_dets *rec = recs + t;
         const int n = max(0, min(lists ? rec->nfull : rec->count, stride)), ncand = rec->ncand, ovf = rec->overflow;
-        const BBOX *list = lists ? lists + a.first[e] : rec->box;
+        const BBOX *list = lists ? lists + a.en.first[e] : rec->box;
         int *const row = ids + t * rowlen;
         for (long i = tid; i < stride; i += blockDim.x) row[8 + i] = 0;
         if (tid < FFGPU_TRACK_DETS) { L.dmatch[tid] = -1; L.tmatch[tid] = -1; }
@@ -223,42 +219,7 @@ __global__ void __launch_bounds__(256) k_track(TrackArgs a, const ffgpu_frame_de
 static_assert(FFGPU_MAX_DET == FFGPU_TRACK_DETS, "k_track: a tracked record holds every considered box");
 
 // ---- host side
-extern "C" size_t ffgpu_track_state_bytes(int nstreams, int capacity)
-{
-    if (nstreams < 1 || nstreams > 65536 || capacity < 1 || capacity > FFGPU_TRACK_DETS) return 0;
-    return (size_t)nstreams * (16 + sizeof(ffgpu_track) * (size_t)capacity);
-}
-
-int ffgpu_track_spec_check(const char *what, const ffgpu_track_spec *sp)
-{
-    if (!sp) { ffgpu_set_error("%s: NULL spec", what); return -1; }
-    if (sp->capacity < 1 || sp->capacity > FFGPU_TRACK_DETS) { ffgpu_set_error("%s: capacity %d is outside 1..%d", what, sp->capacity, FFGPU_TRACK_DETS); return -1; }
-    if (sp->max_missed < 0 || sp->max_missed > (1 << 20)) { ffgpu_set_error("%s: max_missed %d is outside 0..2^20", what, sp->max_missed); return -1; }
-    if (sp->min_hits < 1 || sp->min_hits > (1 << 20)) { ffgpu_set_error("%s: min_hits %d is outside 1..2^20", what, sp->min_hits); return -1; }
-    if (!(sp->iou_thresh >= 0.f && sp->iou_thresh <= 1.f)) { ffgpu_set_error("%s: iou_thresh %g is not in [0, 1]", what, (double)sp->iou_thresh); return -1; }
-    if (!(sp->min_score >= 0.f && sp->min_score <= 1.f)) { ffgpu_set_error("%s: min_score %g is not in [0, 1]", what, (double)sp->min_score); return -1; }
-    if (!(sp->birth_score >= 0.f && sp->birth_score <= 1.f)) { ffgpu_set_error("%s: birth_score %g is not in [0, 1]", what, (double)sp->birth_score); return -1; }
-    if (sp->class_aware != 0 && sp->class_aware != 1) { ffgpu_set_error("%s: class_aware %d is neither 0 nor 1", what, sp->class_aware); return -1; }
-    if (sp->reserved != 0) { ffgpu_set_error("%s: spec: reserved must be 0", what); return -1; }
-    return 0;
-}
-
-// what the operator and the executor form check alike, before either looks at its records
-int ffgpu_track_args_check(const char *what, const int *streams, int ntargets, const ffgpu_track_spec *spec, const void *d_state, int nstreams,
-                           const void *d_ids, const void *d_out_records, const void *d_out_lists)
-{
-    if (!streams) { ffgpu_set_error("%s: NULL streams", what); return -1; }
-    if (ffgpu_track_spec_check(what, spec)) return -1;
-    if (!d_state) { ffgpu_set_error("%s: NULL state", what); return -1; }
-    if (!d_ids) { ffgpu_set_error("%s: NULL ids", what); return -1; }
-    if (ntargets < 1 || ntargets > (1 << 24)) { ffgpu_set_error("%s: %d targets (ntargets >= 1)", what, ntargets); return -1; }
-    if (nstreams < 1 || nstreams > 65536) { ffgpu_set_error("%s: nstreams %d is outside 1..65536", what, nstreams); return -1; }
-    if (reinterpret_cast<uintptr_t>(d_state) & 15) { ffgpu_set_error("%s: the state must be 16-byte aligned", what); return -1; }
-    if (d_out_lists && !d_out_records) { ffgpu_set_error("%s: d_out_lists without d_out_records", what); return -1; }
-    for (int t = 0; t < ntargets; t++)
-        if (streams[t] < -1 || streams[t] >= nstreams) { ffgpu_set_error("%s: target %d: stream %d is outside -1 .. %d", what, t, streams[t], nstreams - 1); return -1; }
-    return 0;
-}
+extern "C" size_t ffgpu_track_state_bytes(int nstreams, int capacity) { return ffgpu_track_state_bytes_host(nstreams, capacity); }
 
 // everything has been checked
 int ffgpu_launch_track(const DetSource &src, const int *streams, int ntargets, const ffgpu_track_spec &spec, void *d_state, void *d_ids, void *d_out_records, void *d_out_lists, hipStream_t s)
@@ -267,18 +228,10 @@ int ffgpu_launch_track(const DetSource &src, const int *streams, int ntargets, c
     if (lds_allow((const void *)k_track, lds, "track_boxes")) return -1;
     for (int t0 = 0; t0 < ntargets; t0 += TRACK_ARG_ENTRIES) {
         const int nt = std::min(TRACK_ARG_ENTRIES, ntargets - t0);
-        int order[TRACK_ARG_ENTRIES];
-        for (int i = 0; i < nt; i++) order[i] = t0 + i;
-        std::stable_sort(order, order + nt, [&](int x, int y) { return streams[x] < streams[y]; });
         TrackArgs a;
         memset(&a, 0, sizeof a);
         a.spec = spec;
-        for (int i = 0; i < nt; i++) {
-            const int t = order[i];
-            if (i == 0 || streams[t] != streams[order[i - 1]]) { a.gstream[a.ngroups] = streams[t]; a.goff[a.ngroups] = i; a.ngroups++; }
-            a.rec[i] = t; a.first[i] = src.first[t];
-        }
-        a.goff[a.ngroups] = nt;
+        a.ngroups = ffgpu_stream_entries(src.first, streams, t0, nt, a.en);
         hipLaunchKernelGGL(k_track, dim3((unsigned)a.ngroups), dim3(256), lds, s, a, src.recs, src.lists, src.stride, (unsigned char *)d_state, (int *)d_ids,
                            (ffgpu_frame_dets *)d_out_records, (BBOX *)d_out_lists);
         LAUNCH_OK("track_boxes");
@@ -290,19 +243,9 @@ extern "C" int ffgpu_track_reset_dev(void *d_state, int nstreams, int capacity, 
 {
     const char *const what = "track_reset_dev";
     if (ffgpu_no_device(what)) return -1;
-    if (!d_state) { ffgpu_set_error("%s: NULL state", what); return -1; }
     const size_t all = ffgpu_track_state_bytes(nstreams, capacity);
-    if (!all) { ffgpu_set_error("%s: %d streams of %d slots (nstreams 1..65536, capacity 1..%d)", what, nstreams, capacity, FFGPU_TRACK_DETS); return -1; }
-    if (reinterpret_cast<uintptr_t>(d_state) & 15) { ffgpu_set_error("%s: the state must be 16-byte aligned", what); return -1; }
-    if (which_stream < -1 || which_stream >= nstreams) { ffgpu_set_error("%s: stream %d is outside -1 .. %d", what, which_stream, nstreams - 1); return -1; }
-    const size_t one = all / (size_t)nstreams;
-    unsigned char *p = (unsigned char *)d_state + (which_stream < 0 ? 0 : one * (size_t)which_stream);
-    if (hipMemsetAsync(p, 0, which_stream < 0 ? all : one, (hipStream_t)stream) != hipSuccess) {
-        (void)hipGetLastError();
-        ffgpu_set_error("%s: hipMemsetAsync failed", what);
-        return -1;
-    }
-    return 0;
+    if (!all) ffgpu_set_error("%s: %d streams of %d slots (nstreams 1..65536, capacity 1..%d)", what, nstreams, capacity, FFGPU_TRACK_DETS);   // (stands unless the state is NULL)
+    return ffgpu_state_reset(what, d_state, all, nstreams, which_stream, stream);
 }
 
 extern "C" int ffgpu_track_boxes_dev(const void *d_records, const void *d_lists, int list_stride, const int *list_first, const int *streams, int ntargets,

@@ -10,10 +10,7 @@
 // written by all lanes too, a (region, item) pair each: the two ring points a lane reads may have been written by another lane of the workgroup in
 // this frame, in front of a barrier -- workgroup scope is all it takes; no device-scope fence, no atomic.  Integer arithmetic but the anchor.
 struct TrailsArgs {
-    long long first[TRAILS_ARG_ENTRIES];              // entry e: its list's first box in `lists`
-    int   rec[TRAILS_ARG_ENTRIES];                    //          its record
-    int   gstream[TRAILS_ARG_ENTRIES];                // group g (= workgroup g): its video stream, or -1: the ignored entries
-    int   goff[TRAILS_ARG_ENTRIES + 1];               //          its entries goff[g] .. goff[g + 1] - 1
+    StreamEntries<TRAILS_ARG_ENTRIES> en;             // the launch's records, grouped by video stream (ffgpu_streams_host.hpp)
     unsigned pal[256];
     int   capacity, max_missed, identity, flags, anchor, points, min_move, thickness, coast_dash, npal;
     float min_score;
@@ -54,12 +51,12 @@ __global__ void __launch_bounds__(256) k_trails(TrailsArgs a, const ffgpu_frame_
     __shared__ __attribute__((aligned(16))) unsigned char s_trails[sizeof(TrailsLds)];
     TrailsLds &L = *reinterpret_cast<TrailsLds *>(s_trails);
     const int tid = threadIdx.x, g = blockIdx.x;
-    const int e0 = a.goff[g], e1 = a.goff[g + 1], vs = a.gstream[g], C = a.capacity, P = a.points;
+    const int e0 = a.en.goff[g], e1 = a.en.goff[g + 1], vs = a.en.gstream[g], C = a.capacity, P = a.points;
     const long rowlen = FFGPU_TRAILS_ROW + 4 * (long)stride, idlen = 8 + (long)stride;
     const int nitems = items ? a.nitems : 0;
     if (vs < 0) {                                                                     // the ignored entries: every output byte zero (uniform)
         for (int e = e0; e < e1; e++) {
-            const long t = a.rec[e];
+            const long t = a.en.rec[e];
             for (long i = tid; i < rowlen; i += blockDim.x) rows[t * rowlen + i] = 0;
             unsigned *dst = items + ((size_t)t * (size_t)a.items_stride + (size_t)a.first_item) * 8u;
             for (int i = tid; i < nitems * 8; i += blockDim.x) dst[i] = 0;
@@ -79,10 +76,10 @@ __global__ void __launch_bounds__(256) k_trails(TrailsArgs a, const ffgpu_frame_
     const bool slane = sidx >= 0 && sidx < C;
 
     for (int e = e0; e < e1; e++) {
-        const long t = a.rec[e];
+        const long t = a.en.rec[e];
         const ffgpu_frame_dets *rec = recs + t;
         const int n = max(0, min(lists ? rec->nfull : rec->count, stride));
-        const BBOX *list = lists ? lists + a.first[e] : rec->box;
+        const BBOX *list = lists ? lists + a.en.first[e] : rec->box;
         int *const row = rows + t * rowlen;
         for (long i = tid; i < 4 * (long)stride; i += blockDim.x) row[FFGPU_TRAILS_ROW + i] = 0;
         if (tid < FFGPU_TRAILS_DETS) { L.named[tid] = 0; L.refill[tid] = 0; }
@@ -237,8 +234,7 @@ int ffgpu_launch_trails(const DetSource &src, const int *streams, int ntargets, 
         a.capacity = pl.capacity; a.max_missed = pl.max_missed; a.identity = pl.identity; a.flags = pl.flags; a.anchor = pl.anchor; a.points = pl.points;
         a.min_move = pl.min_move; a.thickness = pl.thickness; a.coast_dash = pl.coast_dash; a.npal = pl.npal; a.min_score = pl.min_score;
         a.items_stride = items_stride; a.first_item = first_item; a.nitems = nitems;
-        a.ngroups = ffgpu_group_by_stream(streams, t0, nt, a.rec, a.gstream, a.goff);
-        for (int i = 0; i < nt; i++) a.first[i] = src.first[a.rec[i]];
+        a.ngroups = ffgpu_stream_entries(src.first, streams, t0, nt, a.en);
         hipLaunchKernelGGL(k_trails, dim3((unsigned)a.ngroups), dim3(256), 0, s, a, src.recs, src.lists, src.stride, (unsigned char *)d_state, (const int *)d_ids,
                            (int *)d_rows, (unsigned *)d_items);
         LAUNCH_OK("trails_boxes");
@@ -250,19 +246,9 @@ extern "C" int ffgpu_trails_reset_dev(void *d_state, int nstreams, int capacity,
 {
     const char *const what = "trails_reset_dev";
     if (ffgpu_no_device(what)) return -1;
-    if (!d_state) { ffgpu_set_error("%s: NULL state", what); return -1; }
     const size_t all = ffgpu_trails_state_bytes(nstreams, capacity);
-    if (!all) { ffgpu_set_error("%s: %d streams of %d slots (nstreams 1..65536, capacity 1..%d)", what, nstreams, capacity, FFGPU_TRAILS_DETS); return -1; }
-    if (reinterpret_cast<uintptr_t>(d_state) & 15) { ffgpu_set_error("%s: the state must be 16-byte aligned", what); return -1; }
-    if (which_stream < -1 || which_stream >= nstreams) { ffgpu_set_error("%s: stream %d is outside -1 .. %d", what, which_stream, nstreams - 1); return -1; }
-    const size_t one = all / (size_t)nstreams;
-    unsigned char *p = (unsigned char *)d_state + (which_stream < 0 ? 0 : one * (size_t)which_stream);
-    if (hipMemsetAsync(p, 0, which_stream < 0 ? all : one, (hipStream_t)stream) != hipSuccess) {
-        (void)hipGetLastError();
-        ffgpu_set_error("%s: hipMemsetAsync failed", what);
-        return -1;
-    }
-    return 0;
+    if (!all) ffgpu_set_error("%s: %d streams of %d slots (nstreams 1..65536, capacity 1..%d)", what, nstreams, capacity, FFGPU_TRAILS_DETS);   // (stands unless the state is NULL)
+    return ffgpu_state_reset(what, d_state, all, nstreams, which_stream, stream);
 }
 
 extern "C" int ffgpu_trails_boxes_dev(const void *d_records, const void *d_lists, int list_stride, const int *list_first, const int *streams, int ntargets,

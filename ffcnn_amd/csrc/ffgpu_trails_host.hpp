@@ -1,8 +1,10 @@
 // ffgpu_trails_host.hpp -- the host side of the track trails (include/ffcnn_hip.h: ffgpu_trails_state_bytes, ffgpu_trails_spec_check,
 // ffgpu_trails_boxes_dev, ffgpu_exec_trails) before anything reaches the device: the state's size, the spec resolved into a plan, the argument checks.
 // Plain C++17 with no HIP in it: every function reports through ffgpu_set_error and touches no device, so san/trails_driver.cc runs the same lines on
-// the CPU under ASan + UBSan (tests/test_trails_abi.py).  The grouping of a launch's records by stream is ffgpu_zones_host.hpp's.
+// the CPU under ASan + UBSan (tests/test_trails_abi.py).  The launch's entry table and the stream checks are ffgpu_streams_host.hpp's,
+// the palette is ffgpu_args.hpp's.
 #pragma once
+#include "ffgpu_args.hpp"
 #include "ffgpu_zones_host.hpp"
 
 static_assert(sizeof(ffgpu_trail_point) == 12 && sizeof(ffgpu_trail_slot) == 416 && sizeof(ffgpu_trails_spec) == 64 && sizeof(ffgpu_seg_item) == 32,
@@ -42,16 +44,10 @@ inline int ffgpu_trails_spec_plan(const char *what, const ffgpu_trails_spec *sp,
     if (sp->min_move < 0 || sp->min_move > (1 << 20)) { ffgpu_set_error("%s: min_move %d is outside 0..2^20", what, sp->min_move); return -1; }
     if (sp->thickness < 1 || sp->thickness > 8) { ffgpu_set_error("%s: thickness %d is outside 1..8", what, sp->thickness); return -1; }
     if (sp->coast_dash < 0 || sp->coast_dash > 6) { ffgpu_set_error("%s: coast_dash %d is outside 0..6", what, sp->coast_dash); return -1; }
-    if (sp->palette ? (sp->npalette < 1 || sp->npalette > 256) : sp->npalette != 0) {
-        ffgpu_set_error("%s: npalette %d (0 with a NULL palette, else 1..256)", what, sp->npalette);
-        return -1;
-    }
+    if (ffgpu_palette_plan(what, sp->palette, sp->npalette, sp->color, pl.pal, &pl.npal)) return -1;
     if (sp->reserved0 != 0 || sp->reserved != 0) { ffgpu_set_error("%s: spec: reserved must be 0", what); return -1; }
     pl.capacity = sp->capacity; pl.max_missed = sp->max_missed; pl.identity = sp->identity; pl.flags = sp->flags; pl.anchor = sp->anchor;
     pl.points = sp->points; pl.min_move = sp->min_move; pl.thickness = sp->thickness; pl.coast_dash = sp->coast_dash; pl.min_score = sp->min_score;
-    const unsigned char *src = sp->palette ? sp->palette : sp->color;
-    pl.npal = sp->palette ? sp->npalette : 1;
-    for (int k = 0; k < pl.npal; k++) pl.pal[k] = (unsigned)src[4 * k] | (unsigned)src[4 * k + 1] << 8 | (unsigned)src[4 * k + 2] << 16;
     return 0;
 }
 
@@ -65,9 +61,7 @@ inline int ffgpu_trails_args_check(const char *what, const int *streams, int nta
     if (!d_rows) { ffgpu_set_error("%s: NULL rows", what); return -1; }
     if (spec->identity == FFGPU_ZONES_IDS && !d_ids) { ffgpu_set_error("%s: NULL ids with identity FFGPU_ZONES_IDS", what); return -1; }
     if (spec->identity != FFGPU_ZONES_IDS && d_ids) { ffgpu_set_error("%s: ids given without identity FFGPU_ZONES_IDS", what); return -1; }
-    if (ntargets < 1 || ntargets > (1 << 24)) { ffgpu_set_error("%s: %d targets (ntargets >= 1)", what, ntargets); return -1; }
-    if (nstreams < 1 || nstreams > 65536) { ffgpu_set_error("%s: nstreams %d is outside 1..65536", what, nstreams); return -1; }
-    if (reinterpret_cast<uintptr_t>(d_state) & 15) { ffgpu_set_error("%s: the state must be 16-byte aligned", what); return -1; }
+    if (ffgpu_streams_check(what, ntargets, nstreams, d_state)) return -1;
     if (!d_items) {
         if (items_stride != 0 || first_item != 0 || nitems != 0) {
             ffgpu_set_error("%s: NULL items with items_stride %d, first_item %d, nitems %d (all 0 then)", what, items_stride, first_item, nitems);
@@ -83,7 +77,5 @@ inline int ffgpu_trails_args_check(const char *what, const int *streams, int nta
             return -1;
         }
     }
-    for (int t = 0; t < ntargets; t++)
-        if (streams[t] < -1 || streams[t] >= nstreams) { ffgpu_set_error("%s: target %d: stream %d is outside -1 .. %d", what, t, streams[t], nstreams - 1); return -1; }
-    return 0;
+    return ffgpu_stream_range_check(what, streams, ntargets, nstreams);
 }

@@ -9,10 +9,7 @@
 // updates it in place.  Frees by the slot lanes, fresh owners by ranks (block_rank: the r-th fresh owner takes the r-th free slot), every count of the
 // event row by ballots folded in wave order.  No atomic, no arrival order.
 struct ZonesArgs {
-    long long first[ZONES_ARG_ENTRIES];               // entry e: its list's first box in `lists`
-    int   rec[ZONES_ARG_ENTRIES];                     //          its record
-    int   gstream[ZONES_ARG_ENTRIES];                 // group g (= workgroup g): its video stream, or -1: the ignored entries
-    int   goff[ZONES_ARG_ENTRIES + 1];                //          its entries goff[g] .. goff[g + 1] - 1
+    StreamEntries<ZONES_ARG_ENTRIES> en;              // the launch's records, grouped by video stream (ffgpu_streams_host.hpp)
     ffgpu_zones_spec spec;
     int   ngroups, pad_[3];
 };
@@ -83,11 +80,11 @@ __global__ void __launch_bounds__(256) k_zones(ZonesArgs a, const ffgpu_frame_de
     __shared__ __attribute__((aligned(16))) unsigned char s_zones[sizeof(ZonesLds)];
     ZonesLds &L = *reinterpret_cast<ZonesLds *>(s_zones);
     const int tid = threadIdx.x, g = blockIdx.x;
-    const int e0 = a.goff[g], e1 = a.goff[g + 1], vs = a.gstream[g], C = a.spec.capacity;
+    const int e0 = a.en.goff[g], e1 = a.en.goff[g + 1], vs = a.en.gstream[g], C = a.spec.capacity;
     const long rowlen = FFGPU_ZONES_ROW + 2 * (long)stride, idlen = 8 + (long)stride;
     if (vs < 0) {                                                                     // the ignored entries: every output byte zero (uniform)
         for (int e = e0; e < e1; e++) {
-            const long t = a.rec[e];
+            const long t = a.en.rec[e];
             for (long i = tid; i < rowlen; i += blockDim.x) events[t * rowlen + i] = 0;
             if (out_recs) for (int i = tid; i < (int)(sizeof(ffgpu_frame_dets) / sizeof(int)); i += blockDim.x) reinterpret_cast<int *>(out_recs + t)[i] = 0;
             if (out_lists) for (long i = tid; i < stride; i += blockDim.x) track_zero(out_lists + t * stride + i);
@@ -119,10 +116,10 @@ __global__ void __launch_bounds__(256) k_zones(ZonesArgs a, const ffgpu_frame_de
     const bool slane = sidx >= 0 && sidx < C;
 
     for (int e = e0; e < e1; e++) {
-        const long t = a.rec[e];
+        const long t = a.en.rec[e];
         const ffgpu_frame_dets *rec = recs + t;
         const int n = max(0, min(lists ? rec->nfull : rec->count, stride)), ncand = rec->ncand, ovf = rec->overflow;
-        const BBOX *list = lists ? lists + a.first[e] : rec->box;
+        const BBOX *list = lists ? lists + a.en.first[e] : rec->box;
         int *const row = events + t * rowlen;
         for (long i = tid; i < 2 * (long)stride; i += blockDim.x) row[FFGPU_ZONES_ROW + i] = 0;
         if (tid < FFGPU_ZONES_DETS) L.named[tid] = 0;
@@ -283,8 +280,7 @@ int ffgpu_launch_zones(const DetSource &src, const int *streams, int ntargets, c
         ZonesArgs a;
         memset(&a, 0, sizeof a);
         a.spec = spec;
-        a.ngroups = ffgpu_group_by_stream(streams, t0, nt, a.rec, a.gstream, a.goff);
-        for (int i = 0; i < nt; i++) a.first[i] = src.first[a.rec[i]];
+        a.ngroups = ffgpu_stream_entries(src.first, streams, t0, nt, a.en);
         hipLaunchKernelGGL(k_zones, dim3((unsigned)a.ngroups), dim3(256), 0, s, a, src.recs, src.lists, src.stride, (const unsigned char *)d_scenes,
                            (unsigned char *)d_state, (const int *)d_ids, (int *)d_events, (ffgpu_frame_dets *)d_out_records, (BBOX *)d_out_lists);
         LAUNCH_OK("zones_boxes");
@@ -296,19 +292,9 @@ extern "C" int ffgpu_zones_reset_dev(void *d_state, int nstreams, int capacity, 
 {
     const char *const what = "zones_reset_dev";
     if (ffgpu_no_device(what)) return -1;
-    if (!d_state) { ffgpu_set_error("%s: NULL state", what); return -1; }
     const size_t all = ffgpu_zones_state_bytes(nstreams, capacity);
-    if (!all) { ffgpu_set_error("%s: %d streams of %d slots (nstreams 1..65536, capacity 1..%d)", what, nstreams, capacity, FFGPU_ZONES_DETS); return -1; }
-    if (reinterpret_cast<uintptr_t>(d_state) & 15) { ffgpu_set_error("%s: the state must be 16-byte aligned", what); return -1; }
-    if (which_stream < -1 || which_stream >= nstreams) { ffgpu_set_error("%s: stream %d is outside -1 .. %d", what, which_stream, nstreams - 1); return -1; }
-    const size_t one = all / (size_t)nstreams;
-    unsigned char *p = (unsigned char *)d_state + (which_stream < 0 ? 0 : one * (size_t)which_stream);
-    if (hipMemsetAsync(p, 0, which_stream < 0 ? all : one, (hipStream_t)stream) != hipSuccess) {
-        (void)hipGetLastError();
-        ffgpu_set_error("%s: hipMemsetAsync failed", what);
-        return -1;
-    }
-    return 0;
+    if (!all) ffgpu_set_error("%s: %d streams of %d slots (nstreams 1..65536, capacity 1..%d)", what, nstreams, capacity, FFGPU_ZONES_DETS);   // (stands unless the state is NULL)
+    return ffgpu_state_reset(what, d_state, all, nstreams, which_stream, stream);
 }
 
 extern "C" int ffgpu_zones_boxes_dev(const void *d_records, const void *d_lists, int list_stride, const int *list_first, const int *streams, int ntargets,

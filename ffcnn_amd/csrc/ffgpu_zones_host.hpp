@@ -1,15 +1,13 @@
 // ffgpu_zones_host.hpp -- the host side of the zones family (include/ffcnn_hip.h: ffgpu_scene_check, ffgpu_zones_boxes_dev, ffgpu_exec_zones) before
-// anything reaches the device: the scene check, the spec and argument checks, and the grouping of a launch's records by video stream.  Plain C++17 with
-// no HIP in it: every function reports through ffgpu_set_error and touches no device, so san/zones_driver.cc runs the same lines on the CPU under
-// ASan + UBSan (tests/test_zones_abi.py).
+// anything reaches the device: the scene check and the spec and argument checks (the launch's entry table, its grouping by video stream and the stream
+// checks are ffgpu_streams_host.hpp's).  Plain C++17 with no HIP in it: every function reports through ffgpu_set_error and touches no device, so
+// san/zones_driver.cc runs the same lines on the CPU under ASan + UBSan (tests/test_zones_abi.py).
 #pragma once
 #include <stdint.h>
 #include <string.h>
 #include <math.h>
-#include <algorithm>
 #include "ffcnn_hip.h"
-
-extern "C" void ffgpu_set_error(const char *fmt, ...);
+#include "ffgpu_streams_host.hpp"
 
 static_assert(sizeof(ffgpu_zone) == 96 && sizeof(ffgpu_line) == 32 && sizeof(ffgpu_scene) == 1040 && sizeof(ffgpu_zones_spec) == 32 &&
               sizeof(ffgpu_zone_slot) == 64, "include/ffcnn_hip.h states these sizes");
@@ -77,26 +75,8 @@ inline int ffgpu_zones_args_check(const char *what, const int *streams, int ntar
     if (!d_events) { ffgpu_set_error("%s: NULL events", what); return -1; }
     if (spec->identity == FFGPU_ZONES_IDS && !d_ids) { ffgpu_set_error("%s: NULL ids with identity FFGPU_ZONES_IDS", what); return -1; }
     if (spec->identity != FFGPU_ZONES_IDS && d_ids) { ffgpu_set_error("%s: ids given without identity FFGPU_ZONES_IDS", what); return -1; }
-    if (ntargets < 1 || ntargets > (1 << 24)) { ffgpu_set_error("%s: %d targets (ntargets >= 1)", what, ntargets); return -1; }
-    if (nstreams < 1 || nstreams > 65536) { ffgpu_set_error("%s: nstreams %d is outside 1..65536", what, nstreams); return -1; }
-    if (reinterpret_cast<uintptr_t>(d_state) & 15) { ffgpu_set_error("%s: the state must be 16-byte aligned", what); return -1; }
+    if (ffgpu_streams_check(what, ntargets, nstreams, d_state)) return -1;
     if (reinterpret_cast<uintptr_t>(d_scenes) & 3) { ffgpu_set_error("%s: the scenes must be 4-byte aligned", what); return -1; }
     if (d_out_lists && !d_out_records) { ffgpu_set_error("%s: d_out_lists without d_out_records", what); return -1; }
-    for (int t = 0; t < ntargets; t++)
-        if (streams[t] < -1 || streams[t] >= nstreams) { ffgpu_set_error("%s: target %d: stream %d is outside -1 .. %d", what, t, streams[t], nstreams - 1); return -1; }
-    return 0;
-}
-
-// The records t0 .. t0 + nt - 1 of a call (nt <= ZONES_ARG_ENTRIES) grouped by video stream: order[i] = the i-th record in "stream ascending, record
-// order kept inside a stream"; group g (= workgroup g) serves stream gstream[g] (-1: the ignored entries) with order[goff[g] .. goff[g + 1] - 1].
-// Returns the number of groups.
-inline int ffgpu_group_by_stream(const int *streams, int t0, int nt, int *order, int *gstream, int *goff)
-{
-    for (int i = 0; i < nt; i++) order[i] = t0 + i;
-    std::stable_sort(order, order + nt, [&](int x, int y) { return streams[x] < streams[y]; });
-    int ng = 0;
-    for (int i = 0; i < nt; i++)
-        if (i == 0 || streams[order[i]] != streams[order[i - 1]]) { gstream[ng] = streams[order[i]]; goff[ng] = i; ng++; }
-    goff[ng] = nt;
-    return ng;
+    return ffgpu_stream_range_check(what, streams, ntargets, nstreams);
 }

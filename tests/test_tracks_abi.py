@@ -1,10 +1,11 @@
 """Tracking the detections across frames, without a GPU: the exported symbols, the layout of ffgpu_track_spec / ffgpu_track in the ctypes mirror and
 the constants in the header, ffgpu_track_state_bytes, tests/tracks/trackref.py (the numpy restatement of the contract the GPU tests compare with)
-pinned to a literal scalar loop on seeded cases and to hand-written cases, and the device entry points failing the way every entry point of the
-library does when no HIP device is visible."""
+pinned to a literal scalar loop on seeded cases and to hand-written cases, the host glue under ASan + UBSan (san/track_driver.cc, run as a child
+process), and the device entry points failing the way every entry point of the library does when no HIP device is visible."""
 import ctypes as C
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +17,7 @@ SYMBOLS = ["ffgpu_track_state_bytes", "ffgpu_track_reset_dev", "ffgpu_track_boxe
 NAN, INF = float("nan"), float("inf")
 F32 = np.float32
 S = trackref.Spec
+CSRC = os.path.join(ROOT, "ffcnn_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
@@ -325,3 +327,24 @@ def test_track_without_device(capi):
         errs.append(capi.last_error())
     want = "NULL" if torch.cuda.is_available() else "no HIP device"
     assert all(want in e for e in errs), errs
+
+
+def test_host_glue_under_the_sanitizers():
+    """san/track_driver.cc: the state's size, the spec and argument checks of ffgpu_track_host.hpp and a launch's entry table on the CPU under
+    ASan + UBSan, as a child process; the driver checks every case itself.  A sanitizer report aborts the child: the test fails with it."""
+    host = open(os.path.join(CSRC, "ffgpu_track_host.hpp")).read()
+    assert "hip/hip_runtime" not in host and "hipStream" not in host                    # plain C++: the sanitizer driver compiles it with no HIP
+    inc, drv = open(os.path.join(CSRC, "ffgpu_track.inc")).read(), open(os.path.join(CSRC, "san", "track_driver.cc")).read()
+    assert int(re.search(r"#define TRACK_ARG_ENTRIES\s+(\d+)", inc).group(1)) == 128 == int(re.search(r"#define ENTRIES\s+(\d+)", drv).group(1))
+    subprocess.check_call(["make", "-s", "-C", CSRC, "track"])
+    e = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([os.path.join(ROOT, "ffcnn_amd", "bin", "ffgpu_track_san")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e, timeout=120)
+    err, out = r.stderr.decode(errors="replace"), r.stdout.decode().split("\n")[:-1]
+    assert r.returncode == 0 and "Sanitizer" not in err and "runtime error" not in err, "rc %d\n%s" % (r.returncode, err[-3000:])
+    assert re.fullmatch(r"track_driver: (\d+) cases, 0 wrong", out[-1]) and int(out[-1].split()[1]) == len(out) - 1 >= 68, out[-1]
+    assert not any("WRONG" in ln for ln in out)
+    for ln in ("args.stream_high -1 op: target 1: stream 2 is outside -1 .. 1", "args.lists_without_records -1 op: d_out_lists without d_out_records",
+               "order.lists_before_streams -1 op: d_out_lists without d_out_records", "spec.min_hits_0 -1 op: min_hits 0 is outside 1..2^20",
+               "spec.class_aware_2 -1 op: class_aware 2 is neither 0 nor 1", "bytes.65536_128 %d" % (65536 * (16 + 48 * 128)), "bytes.1_129 0",
+               "entries.full_0 groups=54 ignored=31", "entries.tail groups=3 ignored=1", "entries.all_ignored groups=1 ignored=40", "entries.all_distinct groups=128 ignored=0"):
+        assert ln in out, ln

@@ -232,12 +232,19 @@ def cases():
     c["clamped lists"] = Case(5551, 2, S(16, max_missed=1, iou_thresh=0.25), [0, 0, 1, 0, 1, 1], lists, claimed=claimed, what="clamped nfull")
     lists = video(rng, 4, [128, 100], spread=2000)
     c["clamped records"] = Case(5552, 1, S(128, max_missed=1, iou_thresh=0.25), [0] * 4, lists, use_records=True, claimed={0: 129, 1: -7, 3: 2 ** 31 - 1}, what="clamped count")
+    # 131 records of 3 streams, lists of 0 to 5 boxes: two launches (128 records, then 3), ignored entries in both.  The second launch has room for three
+    # records: the last frames of streams 2 and 0 with an ignored entry between them, so two streams span the boundary
+    rng = np.random.default_rng(5580)
+    per = [video(rng, nf, [int(rng.integers(0, 6)) for _ in range(3)], spread=60) for nf in (40, 44, 41)]
+    streams, lists = interleave(rng, [per[0][:-1], per[1], per[2][:-1]], 5)
+    streams, lists = streams + [2, -1, 0], lists + [per[2][-1], video(rng, 1, [5])[0], per[0][-1]]
+    c["records 131"] = Case(5581, 3, S(6, max_missed=1, min_hits=2, iou_thresh=0.25, birth_score=0.25), streams, lists, what="131 records")
     _CASES.update(c)
     return _CASES
 
 
 NAMES = ["capacity 1", "capacity 2", "capacity 3", "capacity 127", "capacity 128", "counts", "all ties", "nstreams 1", "nstreams 3", "nstreams 65",
-         "list_first", "records", "ids only", "clamped lists", "clamped records"]
+         "list_first", "records", "ids only", "clamped lists", "clamped records", "records 131"]
 
 
 def test_seeded_set_covers_every_path():
@@ -265,6 +272,16 @@ def test_seeded_set_covers_every_path():
                 m = trackref.iou_matrix(b, b)
                 ties += int(((m[:, :, None] == m[:, None, :]) & (m[:, :, None] > 0)).sum() > (m > 0).sum())
     assert ties > 0
+    # "records 131": the first launch holds every stream and an ignored entry; the second (three records: no room for more) an ignored entry and two
+    # streams; a track issued before the boundary is matched again behind it (trackref alone: the state after the first 128 records)
+    c = cs["records 131"]
+    assert c.n == 131 and c.spec.capacity == 6 and {len(c.flat[t * c.stride:][:int(c.recs[t]["nfull"])]) for t in range(c.n)} == set(range(6))
+    assert set(c.streams[:128]) == {-1, 0, 1, 2} and c.streams[128:] == [2, -1, 0]
+    st = trackref.State(3, 6)
+    trackref.track(c.recs[:128], c.flat, c.stride, None, c.streams[:128], c.spec, st)
+    assert all(int(st.hdr[s][1]) > 0 for s in range(3))                             # (frames: every stream has a history at the boundary)
+    carried = [int(((np.abs(c.ids[t, 8:]) > 0) & (np.abs(c.ids[t, 8:]) <= int(st.hdr[c.streams[t]][0]))).sum()) for t in (128, 130)]
+    assert sum(carried) > 0 and not c.ids[129].any(), carried
 
 
 @pytest.mark.parametrize("name", NAMES)
