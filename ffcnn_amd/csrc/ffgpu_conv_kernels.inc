@@ -1008,7 +1008,8 @@ int ffgpu_launch_dwpw(const ConvDesc &dw, const ConvDesc &pw, const float *wpack
 // ffgpu_irb_plan picks the family -- thin (k_irb_thin), wave (k_irbw / k_irbw2) or workgroup (k_irb) --, the instantiation, the tile, the layout of the
 // packed image and the launch shape, and writes them into IrbDesc::plan.  It is the only function of this section that reads a choice or layout switch
 // of the FFGPU_* environment: ffgpu_irb_pack_floats, ffgpu_irb_pack, ffgpu_launch_irb and the front kernel follow the plan, so a switch changed after
-// planning cannot pair one kernel with another kernel's image.  (Read at launch: the diagnostics FFGPU_IRB_TRACE, FFGPU_VERBOSE_IRB, FFGPU_IRB_SKIP.)
+// planning cannot pair one kernel with another kernel's image.  (Read at launch: the diagnostics FFGPU_IRB_TRACE, FFGPU_VERBOSE_IRB, FFGPU_IRB_SKIP, and
+// -- a thin block has no image -- FFGPU_THIN_PAIR with the paired form's FFGPU_THIN_BAND: thin_form.)
 static float act_slope(int act) { return act == 2 ? 0.1f : (act == 1 ? 0.f : 1.f); }
 
 // tuning only (make TRACE=1 / -DIRB_TRACE=1, FFGPU_IRB_TRACE=1): in-kernel timeline of wave 0 of each workgroup of one k_irbw / k_irb launch, printed per
@@ -1107,17 +1108,75 @@ static int irb_thin_launch(const ThinP &p, const IrbPlan &c, hipStream_t s)
     return 0;
 }
 
+// The paired form (k_irb_thin_pair: two frames per wave) is the LAUNCH's choice, not the plan's: the planned line stays what it is, and a thin
+// block has no packed image that a later change of FFGPU_THIN_PAIR could mismatch.  Columns per lane: the fewest of 3, 4, 5 that divide the row
+// and put it into 32 lanes (160 pixels: 5); none: the single form.
+// (Five columns of 8 input channels do not fit the register file -- <8,8,4,5> and <8,8,8,5> spill even with the residual row read late --
+// so those two are not built: such a block keeps the single form.)
+static constexpr bool thin_pair_built(int ic, int ncp) { return !(ic == 8 && ncp == 5); }
+static int thin_pair_ncp(int W, int ic)
+{
+    for (int nc = 3; nc <= 5; nc++)
+        if (W % nc == 0 && W / nc <= 32) return thin_pair_built(ic, nc) ? nc : 0;
+    return 0;
+}
+
+// What launch_irb_thin launches for a planned thin block, pure host arithmetic (ffgpu_irb_thin_launch_line; tests/test_thin_pair_host.py enumerates it).
+// The paired form where a column count exists, the batch has a pair, the executor runs several chains (FFGPU_CONCURRENT: alone the single form's
+// twice as many waves fill the chip better) and FFGPU_THIN_PAIR is not 0.  Pairing halves the waves, so its band is thin_band's for ceil(N / 2)
+// pairs -- 8 rows at batch 64, the same 640 waves -- unless FFGPU_THIN_BAND says otherwise; the single form keeps the plan's band and grid.
+struct ThinForm { int ncp, band, nbands; long ntasks; int grid; };    // ncp 0: k_irb_thin
+static ThinForm thin_form(const IrbDesc &d)
+{
+    ThinForm f;
+    const int ncp = thin_pair_ncp(d.W, d.ic);
+    const bool pair = ncp && d.N >= 2 && (d.flags & FFGPU_CONCURRENT) && knob(K_THIN_PAIR) != 0;
+    const int units = pair ? (d.N + 1) / 2 : d.N;
+    f.ncp = pair ? ncp : 0;
+    f.band = pair ? knob_or(K_THIN_BAND, thin_band(units, d.H)) : d.plan.band;
+    f.nbands = (d.H + f.band - 1) / f.band;
+    f.ntasks = (long)units * f.nbands;
+    f.grid = pair ? (int)((f.ntasks + 3) / 4) : d.plan.grid;
+    return f;
+}
+
+template <int IC, int EC, int OC>
+static int irb_thin_pair_launch(const ThinP &p, const ThinForm &f, hipStream_t s)
+{
+    if (f.ncp == 3) hipLaunchKernelGGL((k_irb_thin_pair<IC, EC, OC, 3>), dim3((unsigned)f.grid), dim3(256), 0, s, p);
+    else if (f.ncp == 4) hipLaunchKernelGGL((k_irb_thin_pair<IC, EC, OC, 4>), dim3((unsigned)f.grid), dim3(256), 0, s, p);
+    else if constexpr (thin_pair_built(IC, 5)) hipLaunchKernelGGL((k_irb_thin_pair<IC, EC, OC, 5>), dim3((unsigned)f.grid), dim3(256), 0, s, p);
+    else { ffgpu_set_error("irb_thin_pair: no instantiation for %d columns per lane of %d channels", f.ncp, IC); return -1; }
+    LAUNCH_OK("irb_thin_pair");
+    return 0;
+}
+
 typedef int (*IrbThinLaunch)(const ThinP &, const IrbPlan &, hipStream_t);
-struct IrbThinKernel { int IC, OC; IrbThinLaunch launch; };
-static const IrbThinKernel irb_thin_kernels[] = { { 8, 4, irb_thin_launch<8, 8, 4> }, { 4, 4, irb_thin_launch<4, 8, 4> }, { 8, 8, irb_thin_launch<8, 8, 8> }, { 4, 8, irb_thin_launch<4, 8, 8> } };
+typedef int (*IrbThinPairLaunch)(const ThinP &, const ThinForm &, hipStream_t);
+struct IrbThinKernel { int IC, OC; IrbThinLaunch launch; IrbThinPairLaunch pair; };
+static const IrbThinKernel irb_thin_kernels[] = { { 8, 4, irb_thin_launch<8, 8, 4>, irb_thin_pair_launch<8, 8, 4> }, { 4, 4, irb_thin_launch<4, 8, 4>, irb_thin_pair_launch<4, 8, 4> },
+                                                  { 8, 8, irb_thin_launch<8, 8, 8>, irb_thin_pair_launch<8, 8, 8> }, { 4, 8, irb_thin_launch<4, 8, 8>, irb_thin_pair_launch<4, 8, 8> } };
 
 static int launch_irb_thin(const IrbDesc &d, hipStream_t s)
 {
-    const ThinP p = thin_params(d);
+    ThinP p = thin_params(d);
+    const ThinForm f = thin_form(d);
+    if (f.ncp) { p.band = f.band; p.nbands = f.nbands; p.ntasks = f.ntasks; }
     for (const IrbThinKernel &k : irb_thin_kernels)
-        if (k.IC == d.ic && k.OC == d.oc) return k.launch(p, d.plan, s);
+        if (k.IC == d.ic && k.OC == d.oc) return f.ncp ? k.pair(p, f, s) : k.launch(p, d.plan, s);
     ffgpu_set_error("irb_thin: no instantiation for %d -> 8 -> %d channels", d.ic, d.oc);
     return -1;
+}
+
+// one line per launch of a planned thin block: the form (thin<IC,8,OC> or thin_pair<IC,8,OC,NC>) and the launch's own shape
+int ffgpu_irb_thin_launch_line(const IrbDesc &d, char *buf, size_t cap)
+{
+    if (d.plan.family != IRB_THIN) return snprintf(buf, cap, "unsupported");
+    const ThinForm f = thin_form(d);
+    char key[48];
+    if (f.ncp) snprintf(key, sizeof key, "thin_pair<%d,8,%d,%d>", d.ic, d.oc, f.ncp);
+    else snprintf(key, sizeof key, "thin<%d,8,%d>", d.ic, d.oc);
+    return snprintf(buf, cap, "%s W=%d H=%d N=%d band=%d nbands=%d ntasks=%ld grid=%d block=256", key, d.W, d.H, d.N, f.band, f.nbands, f.ntasks, f.grid);
 }
 
 // ---- wave-autonomous form (ffgpu_irb_wave.inc, ffgpu_irb_wave2.inc): every instantiation that exists, shape test, tile / split choice, launch shape

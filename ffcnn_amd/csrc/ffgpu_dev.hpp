@@ -87,7 +87,8 @@ size_t ffgpu_irb_pack_floats(const IrbDesc &d);
 int    ffgpu_irb_pack(const IrbDesc &d, float *pk, hipStream_t s);
 int    ffgpu_launch_irb(const IrbDesc &d, hipStream_t s);
 int    ffgpu_irb_plan_line(const IrbDesc &d, char *buf, size_t cap);   // the plan as one canonical line of text (ffgpu_irb_plan_text)
-int    ffgpu_irb_keys(char *buf, size_t cap);                             // the key of every instantiation of the three families, one per line (ffgpu_irb_instantiations)
+int    ffgpu_irb_thin_launch_line(const IrbDesc &d, char *buf, size_t cap);   // a planned thin block's launch as one line: single or paired form, band, tasks, grid (ffgpu_irb_thin_launch_text)
+int    ffgpu_irb_keys(char *buf, size_t cap);                            // the key of every instantiation of the three families, one per line (ffgpu_irb_instantiations)
 // a run of B >= 2 blocks on one small plane (48 -> 224 -> 48, stride 1, linear project and shortcut) as one launch, one frame per workgroup
 // (ffgpu_irb_stage.inc): the blocks' own planned descriptors, whose packed images the kernel reads; in = blocks[0].in, out = blocks[B - 1].out
 #define IRBS_MAXB 8              /* blocks in a run */

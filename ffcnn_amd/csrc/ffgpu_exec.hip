@@ -2031,14 +2031,34 @@ extern "C" int ffgpu_knobs_text(char *buf, int cap)
     return ffgpu_knobs_lines(buf, (size_t)cap);
 }
 
+// pure host code: what the launch of a planned thin block does -- the single or the paired form of k_irb_thin, its band, tasks and grid
+extern "C" int ffgpu_irb_thin_launch_text(int batch, int iw, int ih, int ic, int ec, int oc, int stride, int act1, int actd, int act2, int res_act, int flags, char *buf, int cap)
+{
+    if (!buf || cap < 1 || batch < 1 || iw < 1 || ih < 1 || stride < 1) { ffgpu_set_error("irb_thin_launch_text: bad arguments"); return -1; }
+    IrbDesc d{};
+    irb_fill(d, batch, iw, ih, ic, ec, oc, stride, act1, actd, act2, res_act);
+    d.flags = flags & FFGPU_CONCURRENT;
+    (void)ffgpu_irb_plan(d);
+    return ffgpu_irb_thin_launch_line(d, buf, (size_t)cap);
+}
+
 extern "C" float ffgpu_irb_dev(const float *d_in, const float *d_w1, const float *d_wd, const float *d_w2,
                                const float *d_res, float *d_out, int batch, int iw, int ih, int ic, int ec, int oc,
                                int stride, int act1, int actd, int act2, int res_act, int warmup, int iters, void *stream)
+{
+    return ffgpu_irb_flags_dev(d_in, d_w1, d_wd, d_w2, d_res, d_out, batch, iw, ih, ic, ec, oc, stride, act1, actd, act2, res_act, 0, warmup, iters, stream);
+}
+
+// the same block as an executor created with `flags` (FFGPU_CONCURRENT or 0) plans and launches it
+extern "C" float ffgpu_irb_flags_dev(const float *d_in, const float *d_w1, const float *d_wd, const float *d_w2,
+                                     const float *d_res, float *d_out, int batch, int iw, int ih, int ic, int ec, int oc,
+                                     int stride, int act1, int actd, int act2, int res_act, int flags, int warmup, int iters, void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
     IrbDesc d{};
     d.in = d_in; d.out = d_out; d.residual = d_res; d.w1 = d_w1; d.wd = d_wd; d.w2 = d_w2;
     irb_fill(d, batch, iw, ih, ic, ec, oc, stride, act1, actd, act2, res_act);
+    d.flags = flags & FFGPU_CONCURRENT;
     if (!d_in || !d_out || !d_w1 || !d_wd || !d_w2 || !ffgpu_irb_plan(d)) { ffgpu_set_error("irb_dev: unsupported block shape"); return -1.f; }     // planned once per call
     float *pk = nullptr;
     if (hipMalloc(&pk, ffgpu_irb_pack_floats(d) * sizeof(float)) != hipSuccess) { ffgpu_set_error("irb_dev: hipMalloc failed"); return -1.f; }

@@ -329,6 +329,19 @@ float ffgpu_irb_dev(const float *d_in, const float *d_w1, const float *d_wd, con
                     const float *d_res, float *d_out, int batch, int iw, int ih, int ic, int ec, int oc,
                     int stride, int act1, int actd, int act2, int res_act, int warmup, int iters, void *stream);
 
+/* The same block as an executor created with `flags` (FFGPU_CONCURRENT or 0) plans and launches it: ffgpu_irb_dev is this call with flags 0. */
+float ffgpu_irb_flags_dev(const float *d_in, const float *d_w1, const float *d_wd, const float *d_w2,
+                          const float *d_res, float *d_out, int batch, int iw, int ih, int ic, int ec, int oc,
+                          int stride, int act1, int actd, int act2, int res_act, int flags, int warmup, int iters, void *stream);
+
+/* What the LAUNCH of a thin block (8 expanded channels, k_irb_thin) does, as one line of text in buf (at most cap bytes; returns snprintf's count):
+ * "thin<IC,8,OC> W= H= N= band= nbands= ntasks= grid= block=" -- one frame per wave, the planned band and grid -- or
+ * "thin_pair<IC,8,OC,NC> ..." -- two frames per wave, NC = 3, 4 or 5 columns per lane, the launch's own band and grid: taken where an NC divides
+ * the row into at most 32 lanes, the batch has two frames, flags has FFGPU_CONCURRENT and FFGPU_THIN_PAIR is not 0 --, or "unsupported" for a
+ * block the planner gives another family.  Arguments as ffgpu_irb_plan_text, whose line does not change with the form.  Pure host code. */
+int ffgpu_irb_thin_launch_text(int batch, int iw, int ih, int ic, int ec, int oc, int stride, int act1, int actd, int act2, int res_act,
+                               int flags, char *buf, int cap);
+
 /* What the planner decides for that block, as one line of text in buf (at most cap bytes; returns snprintf's count): the kernel
  * family and instantiation, every scalar of the parameter block the launch would pass, LDS bytes, grid, block, `half`, the floats
  * of the packed image -- or "unsupported".  flags: FFGPU_CONCURRENT or 0.  Pure host code (no device needed): for tests and logs. */

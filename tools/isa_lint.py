@@ -21,6 +21,8 @@ import sys
 CAP = 1.6       # a known form may grow to CAP x its recorded count (+ 16) before the lint asks for a fresh look
 # signature -> count at the time the form was last soaked (tools/isa_lint.py <listing> --census prints today's table)
 KNOWN_FORMS = {
+    # (six counts grew with k_irb_thin_pair: ten more instantiations of k_irb_thin's own arithmetic, no new form; the four-chain runs of
+    #  tests/test_gpu_round5.py take the paired form and soak it)
     # (operand kinds: v = VGPR pair, s = SGPR pair, c = constant / literal; counts of the round-5 tree incl. the three-column k_front, whose u8 conversion
     #  brought the two `vs ... op_sel:[0,1]` forms: mean / norm out of the high half of an SGPR pair -- soaked by the u8 mode of tests/test_gpu_round5.py)
     'v_pk_add_f32 vc op_sel_hi:[1,0]': 3,
@@ -31,18 +33,18 @@ KNOWN_FORMS = {
     'v_pk_fma_f32 vvc op_sel:[0,1,0] op_sel_hi:[1,1,0]': 8,
     'v_pk_fma_f32 vvc op_sel:[1,0,0] op_sel_hi:[1,1,0]': 72,
     'v_pk_fma_f32 vvc op_sel_hi:[0,1,0]': 48,
-    'v_pk_fma_f32 vvc op_sel_hi:[1,0,0]': 302,
+    'v_pk_fma_f32 vvc op_sel_hi:[1,0,0]': 704,      # (302 before k_irb_thin_pair)
     'v_pk_fma_f32 vvc op_sel_hi:[1,1,0]': 790,
     'v_pk_fma_f32 vvv op_sel:[0,1,0]': 212,
-    'v_pk_fma_f32 vvv op_sel:[1,0,0]': 1992,
+    'v_pk_fma_f32 vvv op_sel:[1,0,0]': 3384,      # (1992 before k_irb_thin_pair)
     'v_pk_fma_f32 vvv op_sel_hi:[0,1,1]': 4781,
-    'v_pk_fma_f32 vvv op_sel_hi:[1,0,1]': 2608,
+    'v_pk_fma_f32 vvv op_sel_hi:[1,0,1]': 5446,      # (2608 before k_irb_thin_pair)
     'v_pk_mul_f32 sv op_sel:[1,0]': 51,
-    'v_pk_mul_f32 sv op_sel_hi:[0,1]': 349,
+    'v_pk_mul_f32 sv op_sel_hi:[0,1]': 839,      # (349 before k_irb_thin_pair)
     'v_pk_mul_f32 vc op_sel_hi:[1,0]': 1,
     'v_pk_mul_f32 vs op_sel_hi:[1,0]': 143,
-    'v_pk_mul_f32 vv op_sel:[1,0]': 216,
-    'v_pk_mul_f32 vv op_sel_hi:[0,1]': 144,
+    'v_pk_mul_f32 vv op_sel:[1,0]': 408,      # (216 before k_irb_thin_pair)
+    'v_pk_mul_f32 vv op_sel_hi:[0,1]': 480,      # (144 before k_irb_thin_pair)
 }
 
 
