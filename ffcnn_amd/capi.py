@@ -194,6 +194,17 @@ class MotionSpec(C.Structure):       # ffgpu_motion_spec (64 bytes): the motion 
                 ("classes", C.c_void_p), ("reserved", C.c_int * 2)]
 
 
+class PreviewPane(C.Structure):      # ffgpu_preview_pane (32 bytes): a source region of a frame and the pane of a destination surface it is scaled into
+    _fields_ = [("sx", C.c_int), ("sy", C.c_int), ("sw", C.c_int), ("sh", C.c_int), ("dx", C.c_int), ("dy", C.c_int), ("dw", C.c_int), ("dh", C.c_int)]
+
+
+class PreviewSpec(C.Structure):      # ffgpu_preview_spec (16 bytes): how a pane is filled, and what its bars take
+    _fields_ = [("fit", C.c_int), ("flags", C.c_int), ("fill", C.c_ubyte * 4), ("reserved", C.c_int)]
+
+
+PREVIEW_STRETCH, PREVIEW_FIT = 0, 1                                                    # FFGPU_PREVIEW_* (ffgpu_preview_spec.fit)
+PREVIEW_KEEP_BARS = 1                                                                  # FFGPU_PREVIEW_KEEP_BARS (ffgpu_preview_spec.flags)
+PREVIEW_MAX_SIDE, PREVIEW_MAX_PANES = 8192, 4096                                       # FFGPU_PREVIEW_MAX_SIDE, _MAX_PANES
 MOTION_DETS, MOTION_ROW, MOTION_WORDS, MOTION_MAX_SIDE = 128, 16, 8, 8192                # FFGPU_MOTION_DETS, _ROW, _WORDS, _MAX_SIDE
 MOTION_GATE_INVERT = 1                                                                 # FFGPU_MOTION_GATE_INVERT (ffgpu_motion_spec.flags)
 MOTION_ENTRIES, MOTION_MERGED = 0, 1                                                   # FFGPU_MOTION_* (ffgpu_exec_motion_gate: which)
@@ -299,7 +310,8 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_heat_state_bytes", "ffgpu_heat_spec_check", "ffgpu_heat_blend_spec_check", "ffgpu_heat_palette", "ffgpu_heat_reset_dev", "ffgpu_heat_boxes_dev",
            "ffgpu_exec_heat", "ffgpu_heat_blend_bgr_dev", "ffgpu_heat_blend_nv12_dev",
            "ffgpu_motion_state_bytes", "ffgpu_motion_spec_check", "ffgpu_motion_reset_dev", "ffgpu_motion_update_bgr_dev", "ffgpu_motion_update_nv12_dev",
-           "ffgpu_motion_gate_dev", "ffgpu_exec_motion_gate"]
+           "ffgpu_motion_gate_dev", "ffgpu_exec_motion_gate",
+           "ffgpu_preview_spec_check", "ffgpu_preview_rect", "ffgpu_preview_grid", "ffgpu_preview_tile", "ffgpu_preview_bgr_dev", "ffgpu_preview_nv12_dev"]
 # include/ffcnn_hip_diag.h (libffcnn_hip_diag.so: lab equipment, its own library)
 DIAG_EXPORTS = ["ffgpu_membench", "ffgpu_pipe_probe", "ffgpu_pipe_probe2", "ffgpu_pipe_probe3", "ffgpu_mfma_floor", "ffgpu_diag_x3_term", "ffgpu_diag_xl_op", "ffgpu_clock_probe"]
 
@@ -492,6 +504,12 @@ def lib():
     L.ffgpu_motion_update_nv12_dev.argtypes = [C.POINTER(Nv12Frame), i, C.POINTER(i), C.POINTER(MotionSpec), vp, i, vp, vp]
     L.ffgpu_motion_gate_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(i), i, C.POINTER(MotionSpec), vp, i, vp, vp, vp, vp]
     L.ffgpu_exec_motion_gate.argtypes = [vp, i, C.POINTER(i), i, C.POINTER(MotionSpec), vp, i, vp, vp, vp, vp]
+    L.ffgpu_preview_spec_check.argtypes = [C.POINTER(PreviewSpec)]
+    L.ffgpu_preview_rect.argtypes = [i, i, i, i, C.POINTER(PreviewPane), C.POINTER(PreviewSpec), i, C.POINTER(i)]
+    L.ffgpu_preview_grid.argtypes = [i, i, i, i, i, i, C.POINTER(PreviewPane)]
+    L.ffgpu_preview_tile.argtypes = [C.POINTER(i)]
+    L.ffgpu_preview_bgr_dev.argtypes = [C.POINTER(BgrFrame), C.POINTER(BgrFrame), C.POINTER(PreviewPane), i, C.POINTER(PreviewSpec), vp]
+    L.ffgpu_preview_nv12_dev.argtypes = [C.POINTER(Nv12Frame), C.POINTER(Nv12Frame), C.POINTER(PreviewPane), i, C.POINTER(PreviewSpec), vp]
     L.ffgpu_outline_scene_dev.argtypes = [vp, vp, i, i, vp, i, C.POINTER(i), i, C.POINTER(OutlineSpec), vp, i, vp]
     L.ffgpu_feature_dim.argtypes = [i, i, i, i]
     L.ffgpu_exec_feature_dim.argtypes = [vp, C.POINTER(FeatureSpec)]
@@ -1920,3 +1938,73 @@ def irb_dev(d_in, d_w1, d_wd, d_w2, d_res, d_out, batch, iw, ih, ic, ec, oc, str
     if us < 0:
         raise RuntimeError("ffgpu_irb_dev failed: %s" % last_error())
     return us
+
+
+# ---------------------------------------------------------------------------------------------------------------- preview surfaces
+def preview_pane(src=None, dst=None):
+    """a PreviewPane (ffgpu_preview_pane): src = (sx, sy, sw, sh), the source region, or None for the whole frame; dst = (dx, dy, dw, dh), the pane
+    in the destination surface, or None for the whole surface"""
+    p = PreviewPane()
+    if src is not None:
+        p.sx, p.sy, p.sw, p.sh = (int(v) for v in src)
+    if dst is not None:
+        p.dx, p.dy, p.dw, p.dh = (int(v) for v in dst)
+    return p
+
+
+def preview_spec(fit=PREVIEW_STRETCH, fill=(0, 0, 0), keep_bars=False):
+    """a PreviewSpec (ffgpu_preview_spec): PREVIEW_STRETCH or PREVIEW_FIT; the bars' colour, B G R for BGR surfaces and Y U V for NV12 ones; keep_bars:
+    the bars are not written"""
+    sp = PreviewSpec()
+    sp.fit, sp.flags = fit, PREVIEW_KEEP_BARS if keep_bars else 0
+    sp.fill[:] = (int(fill[0]), int(fill[1]), int(fill[2]), 0)
+    return sp
+
+
+def preview_spec_check(spec):
+    """ffgpu_preview_spec_check (pure host code): raises with what is wrong with the spec"""
+    _check(lib().ffgpu_preview_spec_check(spec), "ffgpu_preview_spec_check")
+
+
+def preview_rect(src_w, src_h, dst_w, dst_h, pane, spec, nv12=False):
+    """ffgpu_preview_rect (pure host code): (sx, sy, sw, sh, X0, Y0, ow, oh) -- the pane's source region and its image in the destination surface"""
+    out = (C.c_int * 8)()
+    _check(lib().ffgpu_preview_rect(src_w, src_h, dst_w, dst_h, pane, spec, int(bool(nv12)), out), "ffgpu_preview_rect")
+    return tuple(out)
+
+
+def preview_grid(npanes, cols, dst_w, dst_h, gap=0, nv12=False):
+    """ffgpu_preview_grid (pure host code): the panes of a wall of `cols` columns in a dst_w x dst_h surface, as a list of PreviewPane whose source
+    fields are zero (the whole frame)"""
+    arr = (PreviewPane * max(1, npanes))()
+    _check(lib().ffgpu_preview_grid(npanes, cols, dst_w, dst_h, gap, int(bool(nv12)), arr), "ffgpu_preview_grid")
+    return [PreviewPane.from_buffer_copy(arr[k]) for k in range(npanes)]
+
+
+def preview_tile():
+    """ffgpu_preview_tile (pure host code): (the columns, the rows of a workgroup's tile of destination samples, the planes one launch takes)"""
+    out = (C.c_int * 3)()
+    _check(lib().ffgpu_preview_tile(out), "ffgpu_preview_tile")
+    return tuple(out)
+
+
+def _preview_panes(panes):
+    arr = (PreviewPane * max(1, len(panes)))()
+    for k, p in enumerate(panes):
+        arr[k] = p
+    return arr
+
+
+def preview_bgr_dev(srcs, dsts, panes, spec, stream=None):
+    """ffgpu_preview_bgr_dev: pane p scales srcs[p] into dsts[p] (what bgr_frame_desc accepts, or None: the pane is skipped); panes from preview_pane
+    or preview_grid, spec from preview_spec.  Enqueued on `stream` without synchronising."""
+    if not len(srcs) == len(dsts) == len(panes):
+        raise ValueError("%d sources, %d destinations and %d panes" % (len(srcs), len(dsts), len(panes)))
+    _check(lib().ffgpu_preview_bgr_dev(bgr_frame_table(srcs), bgr_frame_table(dsts), _preview_panes(panes), len(panes), spec, stream), "ffgpu_preview_bgr_dev")
+
+
+def preview_nv12_dev(srcs, dsts, panes, spec, stream=None):
+    """ffgpu_preview_nv12_dev: the same on NV12 frames (what nv12_frame_desc accepts, or None: skipped)"""
+    if not len(srcs) == len(dsts) == len(panes):
+        raise ValueError("%d sources, %d destinations and %d panes" % (len(srcs), len(dsts), len(panes)))
+    _check(lib().ffgpu_preview_nv12_dev(nv12_frame_table(srcs), nv12_frame_table(dsts), _preview_panes(panes), len(panes), spec, stream), "ffgpu_preview_nv12_dev")

@@ -14,6 +14,7 @@
 #include "ffgpu_trails_host.hpp"
 #include "ffgpu_heat_host.hpp"
 #include "ffgpu_motion_host.hpp"
+#include "ffgpu_preview_host.hpp"
 
 #define FFGPU_CHECK(expr)                                                                   \
     do {                                                                                    \

@@ -1686,6 +1686,81 @@ int ffgpu_motion_gate_dev(const void *d_records, const void *d_lists, int list_s
 int ffgpu_exec_motion_gate(ffgpu_exec *ex, int which, const int *streams, int ntargets, const ffgpu_motion_spec *spec, const void *d_state, int nstreams,
                            void *d_words, void *d_out_records, void *d_out_lists, void *stream);
 
+/* ---- preview surfaces: frames scaled by area averaging into panes, several streams composed into one wall on the device --------------------------
+ * Every operator above leaves a frame at its decoded size.  What a deployment shows is smaller: an operator's wall of 16 or 64 cameras, a thumbnail,
+ * a low-bitrate substream.  This family scales a source region of a frame into a PANE of a destination surface; a wall is several panes whose
+ * destinations name the same surface.  There is no format conversion: BGR to BGR, NV12 to NV12.  Integers throughout; no atomics; one owner per
+ * written byte; the same bytes on every run (tests/preview/previewref.py restates it in numpy).
+ *
+ * RESOLVE (ffgpu_preview_rect: out = { sx, sy, sw, sh, X0, Y0, ow, oh }).  The defaults first: sw == sh == 0 is the whole frame (sx, sy must be 0),
+ * dw == dh == 0 the whole surface (dx, dy must be 0).  Then the source region must lie inside the source frame and the pane inside the destination
+ * surface, every side 1..FFGPU_PREVIEW_MAX_SIDE; NV12 requires sx, sy, dx and dy even.  FFGPU_PREVIEW_STRETCH: ow = dw, oh = dh, ox = oy = 0.
+ * FFGPU_PREVIEW_FIT, in 64-bit integers: if sw dh >= sh dw then ow = dw and oh = clamp((2 sh dw + sw) / (2 sw), 1, dh), otherwise oh = dh and
+ * ow = clamp((2 sw dh + sh) / (2 sh), 1, dw); ox = (dw - ow) >> 1, oy = (dh - oh) >> 1, for NV12 both rounded down to even.  X0 = dx + ox,
+ * Y0 = dy + oy.  The IMAGE is the ow x oh rectangle at (X0, Y0); the BARS are the rest of the pane.
+ *
+ * RESAMPLE: one rule for every ratio, down or up.  A plane of sw x sh samples becomes ow x oh.  Destination sample (i, j) covers
+ * [i sw, (i + 1) sw) horizontally, in units of 1 / ow source samples; source sample x covers [x ow, (x + 1) ow); wx(i, x) is the length of their
+ * intersection, so the wx of a destination sample add up to sw; wy(j, y) likewise with sh and oh.  With D = sw sh:
+ *     out(i, j) = (sum_y wy(j, y) * sum_x wx(i, x) * v(x, y) + (D >> 1)) / D, rounded down.
+ * The inner sum fits 32 bits (255 * 8192 < 2^21); the outer sum is taken in 64 bits once 255 D >= 2^32; the division is exact, not a float
+ * reciprocal.  What follows from the rule: ow == sw and oh == sh gives a byte copy; integer ratios k x l give the rounded mean of each k x l block;
+ * a constant plane stays constant; mirroring the source mirrors the image.
+ *
+ * BGR: the three channels are resampled independently, as three interleaved planes.
+ * NV12: the Y plane is resampled as above.  The UV plane is resampled as two planes, U and V: the source region is ((sw + 1) / 2) x ((sh + 1) / 2) at
+ * (sx / 2, sy / 2), the destination region ((ow + 1) / 2) x ((oh + 1) / 2) at (X0 / 2, Y0 / 2), the same rule with those sizes.  Ownership of
+ * chroma: destination chroma sample (i, j) is written by the pane whose rectangle holds luma pixel (2 i, 2 j) -- as image when that pixel lies in
+ * the IMAGE, as bar otherwise.  `matrix` of the frames is not read.
+ *
+ * Bars take `fill`: B G R per pixel, or Y per luma pixel with U V per owned chroma sample.  With FFGPU_PREVIEW_KEEP_BARS they are not written.
+ * Untouched: every byte of a destination surface outside the panes, row padding, memory before and behind the surfaces, every source byte, kept
+ * bars.  A pane whose source or destination pixel address (bgr / y) is NULL is skipped; its sizes are not looked at.  The gaps of a wall are the
+ * caller's memset: the operator writes panes only.  One-pixel outlines survive area averaging only as faint lines: draw with a thickness near the
+ * ratio before scaling. */
+#define FFGPU_PREVIEW_STRETCH    0   /* fit: the source region fills the pane */
+#define FFGPU_PREVIEW_FIT        1   /* fit: aspect kept, the image centred in the pane, bars round it */
+#define FFGPU_PREVIEW_KEEP_BARS  1   /* flags bit 0: the bars' bytes are not written */
+#define FFGPU_PREVIEW_MAX_SIDE   8192
+#define FFGPU_PREVIEW_MAX_PANES  4096
+typedef struct {
+    int sx, sy, sw, sh;            /* source region; sw == sh == 0: the whole frame (sx, sy must be 0) */
+    int dx, dy, dw, dh;            /* pane in the destination surface; dw == dh == 0: the whole surface (dx, dy must be 0) */
+} ffgpu_preview_pane;              /* 32 bytes: sx 0, sy 4, sw 8, sh 12, dx 16, dy 20, dw 24, dh 28 */
+typedef struct {
+    int fit;                       /* FFGPU_PREVIEW_STRETCH or FFGPU_PREVIEW_FIT */
+    int flags;                     /* 0 | FFGPU_PREVIEW_KEEP_BARS; any other bit is rejected */
+    unsigned char fill[4];         /* B G R 0 or Y U V 0, byte 3 must be 0 */
+    int reserved;                  /* 0 */
+} ffgpu_preview_spec;              /* 16 bytes: fit 0, flags 4, fill 8, reserved 12 */
+
+/* pure host code: 0, or -1 with the message in ffgpu_last_error */
+int ffgpu_preview_spec_check(const ffgpu_preview_spec *spec);
+/* pure host code: RESOLVE for one pane of a src_w x src_h frame into a dst_w x dst_h surface */
+int ffgpu_preview_rect(int src_w, int src_h, int dst_w, int dst_h, const ffgpu_preview_pane *pane, const ffgpu_preview_spec *spec, int nv12, int out[8]);
+/* pure host code: lays out a wall and fills dx, dy, dw, dh of npanes panes, the source fields zero.  rows = ceil(npanes / cols);
+ * cw = (dst_w - (cols + 1) gap) / cols and ch = (dst_h - (rows + 1) gap) / rows; pane k lies at column k % cols and row k / cols:
+ * dx = gap + col (cw + gap), dy = gap + row (ch + gap).  For NV12 the gap must be even, and cw and ch are rounded down to even.  Rejected: npanes or
+ * cols below 1, cols above npanes, gap below 0, cw or ch below 1. */
+int ffgpu_preview_grid(int npanes, int cols, int dst_w, int dst_h, int gap, int nv12, ffgpu_preview_pane *out);
+/* pure host code: out = { the columns and the rows of a workgroup's tile of destination samples, the planes one launch takes } */
+int ffgpu_preview_tile(int out[3]);
+
+/* The operators.  srcs, dsts, panes and spec are HOST arrays, free again on return; pane p reads srcs[p] and writes into dsts[p] (the const pointers
+ * of the destinations are written through); frames are described exactly as the draw operators take them.  A workgroup owns a tile of destination
+ * samples of one pane, anchored at the pane's origin, image and bars alike, and is the only writer of those bytes; it reads the source bytes under
+ * its tile once with aligned loads, takes the horizontal sums once per source row into LDS and runs the vertical sums over them.  The planes
+ * travel as a kernel argument, 32 per launch; more panes are more launches, in order on `stream`.  Enqueued without synchronising; stream order is
+ * the only barrier.  There is no executor form: the operator reads frames, not records.  Rejected before anything is launched, with the pane's
+ * index: everything the draw operators reject about a frame description, for sources and destinations; NULL arrays or spec; npanes outside
+ * 1..FFGPU_PREVIEW_MAX_PANES; an unknown fit, unknown flag bits, fill[3] != 0, reserved != 0; a half-defaulted region; a region outside its frame
+ * or a side above 8192; odd sx, sy, dx or dy for NV12; a pane whose source and destination pixel addresses are equal; two panes with the same
+ * destination pixel address whose rectangles intersect (both indices).  Any other overlap of memory is the caller's responsibility. */
+int ffgpu_preview_bgr_dev(const ffgpu_bgr_frame *srcs, const ffgpu_bgr_frame *dsts, const ffgpu_preview_pane *panes, int npanes,
+                          const ffgpu_preview_spec *spec, void *stream);
+int ffgpu_preview_nv12_dev(const ffgpu_nv12_frame *srcs, const ffgpu_nv12_frame *dsts, const ffgpu_preview_pane *panes, int npanes,
+                           const ffgpu_preview_spec *spec, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
