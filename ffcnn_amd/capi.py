@@ -202,7 +202,24 @@ class PreviewSpec(C.Structure):      # ffgpu_preview_spec (16 bytes): how a pane
     _fields_ = [("fit", C.c_int), ("flags", C.c_int), ("fill", C.c_ubyte * 4), ("reserved", C.c_int)]
 
 
-PREVIEW_STRETCH, PREVIEW_FIT = 0, 1                                                    # FFGPU_PREVIEW_* (ffgpu_preview_spec.fit)
+class WarpMesh(C.Structure):         # ffgpu_warp_mesh (24 bytes): a mesh of source positions, mh rows of mw (x, y) pairs of int32 in 1 / 256 source pixel
+    _fields_ = [("xy", C.c_void_p), ("mw", C.c_int), ("mh", C.c_int), ("cell", C.c_int), ("reserved", C.c_int)]
+
+
+class WarpSpec(C.Structure):         # ffgpu_warp_spec (16 bytes): how a position is sampled, and what a tap outside the source frame is
+    _fields_ = [("filter", C.c_int), ("border", C.c_int), ("fill", C.c_ubyte * 4), ("reserved", C.c_int)]
+
+
+class WarpLens(C.Structure):         # ffgpu_warp_lens (120 bytes): a lens model for ffgpu_warp_mesh_lens
+    _fields_ = [("model", C.c_int), ("reserved", C.c_int), ("dst", C.c_double * 4), ("src", C.c_double * 4), ("k", C.c_double * 4), ("p", C.c_double * 2)]
+
+
+WARP_MESH_ONE, WARP_SUB = 256, 32                                                      # FFGPU_WARP_MESH_ONE, _SUB
+WARP_BILINEAR, WARP_NEAREST = 0, 1                                                     # FFGPU_WARP_* (ffgpu_warp_spec.filter)
+WARP_FILL, WARP_CLAMP = 0, 1                                                           # FFGPU_WARP_* (ffgpu_warp_spec.border)
+WARP_MAX_SIDE, WARP_MAX_JOBS = 8192, 4096                                              # FFGPU_WARP_MAX_SIDE, _MAX_JOBS
+WARP_LENS_BROWN, WARP_LENS_EQUIDISTANT = 0, 1                                          # FFGPU_WARP_LENS_* (ffgpu_warp_lens.model)
+PREVIEW_STRETCH, PREVIEW_FIT = 0, 1                                                 # FFGPU_PREVIEW_* (ffgpu_preview_spec.fit)
 PREVIEW_KEEP_BARS = 1                                                                  # FFGPU_PREVIEW_KEEP_BARS (ffgpu_preview_spec.flags)
 PREVIEW_MAX_SIDE, PREVIEW_MAX_PANES = 8192, 4096                                       # FFGPU_PREVIEW_MAX_SIDE, _MAX_PANES
 MOTION_DETS, MOTION_ROW, MOTION_WORDS, MOTION_MAX_SIDE = 128, 16, 8, 8192                # FFGPU_MOTION_DETS, _ROW, _WORDS, _MAX_SIDE
@@ -311,7 +328,9 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_exec_heat", "ffgpu_heat_blend_bgr_dev", "ffgpu_heat_blend_nv12_dev",
            "ffgpu_motion_state_bytes", "ffgpu_motion_spec_check", "ffgpu_motion_reset_dev", "ffgpu_motion_update_bgr_dev", "ffgpu_motion_update_nv12_dev",
            "ffgpu_motion_gate_dev", "ffgpu_exec_motion_gate",
-           "ffgpu_preview_spec_check", "ffgpu_preview_rect", "ffgpu_preview_grid", "ffgpu_preview_tile", "ffgpu_preview_bgr_dev", "ffgpu_preview_nv12_dev"]
+           "ffgpu_preview_spec_check", "ffgpu_preview_rect", "ffgpu_preview_grid", "ffgpu_preview_tile", "ffgpu_preview_bgr_dev", "ffgpu_preview_nv12_dev",
+           "ffgpu_warp_spec_check", "ffgpu_warp_mesh_size", "ffgpu_warp_mesh_orient", "ffgpu_warp_mesh_homography", "ffgpu_warp_mesh_lens", "ffgpu_warp_point",
+           "ffgpu_warp_tile", "ffgpu_warp_bgr_dev", "ffgpu_warp_nv12_dev"]
 # include/ffcnn_hip_diag.h (libffcnn_hip_diag.so: lab equipment, its own library)
 DIAG_EXPORTS = ["ffgpu_membench", "ffgpu_pipe_probe", "ffgpu_pipe_probe2", "ffgpu_pipe_probe3", "ffgpu_mfma_floor", "ffgpu_diag_x3_term", "ffgpu_diag_xl_op", "ffgpu_clock_probe"]
 
@@ -510,6 +529,15 @@ def lib():
     L.ffgpu_preview_tile.argtypes = [C.POINTER(i)]
     L.ffgpu_preview_bgr_dev.argtypes = [C.POINTER(BgrFrame), C.POINTER(BgrFrame), C.POINTER(PreviewPane), i, C.POINTER(PreviewSpec), vp]
     L.ffgpu_preview_nv12_dev.argtypes = [C.POINTER(Nv12Frame), C.POINTER(Nv12Frame), C.POINTER(PreviewPane), i, C.POINTER(PreviewSpec), vp]
+    L.ffgpu_warp_spec_check.argtypes = [C.POINTER(WarpSpec)]
+    L.ffgpu_warp_mesh_size.argtypes = [i, i, i, C.POINTER(i)]
+    L.ffgpu_warp_mesh_orient.argtypes = [i, i, i, i, C.POINTER(i), vp]
+    L.ffgpu_warp_mesh_homography.argtypes = [i, i, i, C.POINTER(C.c_double), vp]
+    L.ffgpu_warp_mesh_lens.argtypes = [i, i, i, C.POINTER(WarpLens), vp]
+    L.ffgpu_warp_point.argtypes = [C.POINTER(WarpMesh), i, i, i, i, C.POINTER(i)]
+    L.ffgpu_warp_tile.argtypes = [C.POINTER(i)]
+    L.ffgpu_warp_bgr_dev.argtypes = [C.POINTER(BgrFrame), C.POINTER(BgrFrame), C.POINTER(WarpMesh), i, C.POINTER(WarpSpec), vp]
+    L.ffgpu_warp_nv12_dev.argtypes = [C.POINTER(Nv12Frame), C.POINTER(Nv12Frame), C.POINTER(WarpMesh), i, C.POINTER(WarpSpec), vp]
     L.ffgpu_outline_scene_dev.argtypes = [vp, vp, i, i, vp, i, C.POINTER(i), i, C.POINTER(OutlineSpec), vp, i, vp]
     L.ffgpu_feature_dim.argtypes = [i, i, i, i]
     L.ffgpu_exec_feature_dim.argtypes = [vp, C.POINTER(FeatureSpec)]
@@ -2008,3 +2036,109 @@ def preview_nv12_dev(srcs, dsts, panes, spec, stream=None):
     if not len(srcs) == len(dsts) == len(panes):
         raise ValueError("%d sources, %d destinations and %d panes" % (len(srcs), len(dsts), len(panes)))
     _check(lib().ffgpu_preview_nv12_dev(nv12_frame_table(srcs), nv12_frame_table(dsts), _preview_panes(panes), len(panes), spec, stream), "ffgpu_preview_nv12_dev")
+
+
+# ---------------------------------------------------------------------------------------------------------------- warp surfaces
+def warp_spec(filter=WARP_BILINEAR, border=WARP_FILL, fill=(0, 0, 0)):
+    """a WarpSpec (ffgpu_warp_spec): WARP_BILINEAR or WARP_NEAREST; WARP_FILL or WARP_CLAMP; the colour of a tap outside the source frame, B G R for
+    BGR frames and Y U V for NV12 ones"""
+    sp = WarpSpec()
+    sp.filter, sp.border = filter, border
+    sp.fill[:] = (int(fill[0]), int(fill[1]), int(fill[2]), 0)
+    return sp
+
+
+def warp_spec_check(spec):
+    """ffgpu_warp_spec_check (pure host code): raises with what is wrong with the spec"""
+    _check(lib().ffgpu_warp_spec_check(spec), "ffgpu_warp_spec_check")
+
+
+def warp_mesh_size(dst_w, dst_h, cell):
+    """ffgpu_warp_mesh_size (pure host code): (mw, mh)"""
+    out = (C.c_int * 2)()
+    _check(lib().ffgpu_warp_mesh_size(dst_w, dst_h, cell, out), "ffgpu_warp_mesh_size")
+    return tuple(out)
+
+
+def warp_mesh_orient(src_w, src_h, orient, cell):
+    """ffgpu_warp_mesh_orient (pure host code): ((dw, dh), the mesh as an int32 array of shape (mh, mw, 2)) for orientation 0..7 of a src_w x src_h frame"""
+    wh = (C.c_int * 2)()
+    _check(lib().ffgpu_warp_mesh_orient(src_w, src_h, orient, cell, wh, None), "ffgpu_warp_mesh_orient")
+    mw, mh = warp_mesh_size(wh[0], wh[1], cell)
+    xy = np.empty((mh, mw, 2), np.int32)
+    _check(lib().ffgpu_warp_mesh_orient(src_w, src_h, orient, cell, wh, xy.ctypes.data), "ffgpu_warp_mesh_orient")
+    return (wh[0], wh[1]), xy
+
+
+def warp_mesh_homography(dst_w, dst_h, cell, h):
+    """ffgpu_warp_mesh_homography (pure host code): the mesh (mh, mw, 2) of the homography h (9 numbers, row-major, destination pixel to source position)"""
+    mw, mh = warp_mesh_size(dst_w, dst_h, cell)
+    xy = np.empty((mh, mw, 2), np.int32)
+    _check(lib().ffgpu_warp_mesh_homography(dst_w, dst_h, cell, (C.c_double * 9)(*[float(v) for v in h]), xy.ctypes.data), "ffgpu_warp_mesh_homography")
+    return xy
+
+
+def warp_lens(model, dst, src, k=(0, 0, 0, 0), p=(0, 0)):
+    """a WarpLens (ffgpu_warp_lens): WARP_LENS_BROWN or WARP_LENS_EQUIDISTANT; dst and src are (fx, fy, cx, cy) of the ideal pinhole image and of the camera"""
+    ln = WarpLens()
+    ln.model = model
+    ln.dst[:], ln.src[:] = [float(v) for v in dst], [float(v) for v in src]
+    ln.k[:], ln.p[:] = [float(v) for v in k], [float(v) for v in p]
+    return ln
+
+
+def warp_mesh_lens(dst_w, dst_h, cell, lens):
+    """ffgpu_warp_mesh_lens (pure host code): the mesh (mh, mw, 2) that undistorts the lens (from warp_lens) into a dst_w x dst_h pinhole image"""
+    mw, mh = warp_mesh_size(dst_w, dst_h, cell)
+    xy = np.empty((mh, mw, 2), np.int32)
+    _check(lib().ffgpu_warp_mesh_lens(dst_w, dst_h, cell, lens, xy.ctypes.data), "ffgpu_warp_mesh_lens")
+    return xy
+
+
+def warp_mesh(xy_ptr, dst_w, dst_h, cell):
+    """a WarpMesh (ffgpu_warp_mesh) for a destination of dst_w x dst_h: xy_ptr is the address of its (mh, mw, 2) int32 points -- device memory for the
+    operators, host memory for warp_point"""
+    m = WarpMesh()
+    m.xy, m.cell = xy_ptr, cell
+    m.mw, m.mh = (dst_w - 1) // cell + 2, (dst_h - 1) // cell + 2
+    return m
+
+
+def warp_point(xy, cell, dst_w, dst_h, i, j):
+    """ffgpu_warp_point (pure host code): (X8, Y8) of destination pixel (i, j) under the host mesh xy (an int32 array of shape (mh, mw, 2))"""
+    xy = np.ascontiguousarray(xy, np.int32)
+    m = WarpMesh(xy.ctypes.data, xy.shape[1], xy.shape[0], cell, 0)
+    out = (C.c_int * 2)()
+    _check(lib().ffgpu_warp_point(m, dst_w, dst_h, i, j, out), "ffgpu_warp_point")
+    return tuple(out)
+
+
+def warp_tile():
+    """ffgpu_warp_tile (pure host code): (the columns, the rows of a workgroup's tile of destination pixels, the bytes of LDS the staged form may fill,
+    the jobs one launch takes)"""
+    out = (C.c_int * 4)()
+    _check(lib().ffgpu_warp_tile(out), "ffgpu_warp_tile")
+    return tuple(out)
+
+
+def _warp_meshes(meshes):
+    arr = (WarpMesh * max(1, len(meshes)))()
+    for k, m in enumerate(meshes):
+        if m is not None:
+            arr[k] = m
+    return arr
+
+
+def warp_bgr_dev(srcs, dsts, meshes, spec, stream=None):
+    """ffgpu_warp_bgr_dev: job n maps srcs[n] through meshes[n] into the whole of dsts[n] (what bgr_frame_desc accepts, or None: the job is skipped);
+    meshes from warp_mesh, spec from warp_spec.  Enqueued on `stream` without synchronising."""
+    if not len(srcs) == len(dsts) == len(meshes):
+        raise ValueError("%d sources, %d destinations and %d meshes" % (len(srcs), len(dsts), len(meshes)))
+    _check(lib().ffgpu_warp_bgr_dev(bgr_frame_table(srcs), bgr_frame_table(dsts), _warp_meshes(meshes), len(meshes), spec, stream), "ffgpu_warp_bgr_dev")
+
+
+def warp_nv12_dev(srcs, dsts, meshes, spec, stream=None):
+    """ffgpu_warp_nv12_dev: the same on NV12 frames (what nv12_frame_desc accepts, or None: skipped)"""
+    if not len(srcs) == len(dsts) == len(meshes):
+        raise ValueError("%d sources, %d destinations and %d meshes" % (len(srcs), len(dsts), len(meshes)))
+    _check(lib().ffgpu_warp_nv12_dev(nv12_frame_table(srcs), nv12_frame_table(dsts), _warp_meshes(meshes), len(meshes), spec, stream), "ffgpu_warp_nv12_dev")

@@ -15,6 +15,7 @@
 #include "ffgpu_heat_host.hpp"
 #include "ffgpu_motion_host.hpp"
 #include "ffgpu_preview_host.hpp"
+#include "ffgpu_warp_host.hpp"
 
 #define FFGPU_CHECK(expr)                                                                   \
     do {                                                                                    \

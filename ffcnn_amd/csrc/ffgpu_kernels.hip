@@ -677,6 +677,7 @@ extern "C" int ffgpu_pack_records(const void *d_records, int nslots, long slot_s
 #include "ffgpu_heat.inc"
 #include "ffgpu_motion.inc"
 #include "ffgpu_preview.inc"
+#include "ffgpu_warp.inc"
 #include "ffgpu_feature.inc"
 #include "ffgpu_match.inc"
 

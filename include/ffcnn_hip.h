@@ -1761,6 +1761,126 @@ int ffgpu_preview_bgr_dev(const ffgpu_bgr_frame *srcs, const ffgpu_bgr_frame *ds
 int ffgpu_preview_nv12_dev(const ffgpu_nv12_frame *srcs, const ffgpu_nv12_frame *dsts, const ffgpu_preview_pane *panes, int npanes,
                            const ffgpu_preview_spec *spec, void *stream);
 
+/* ---- warp surfaces: frames dewarped, rotated and rectified through a mesh of source positions on the device --------------------------------------
+ * Every operator above keeps the camera's geometry.  This family maps a source frame through a coarse MESH of source positions into a destination
+ * frame: a lens undistorted, a camera mounted on its side turned upright, a floor plane rectified.  There is no format conversion: BGR to BGR,
+ * NV12 to NV12.  It sits in front of the motion update and the forward: decode, warp, motion update, forward, post-passes, preview.  Integers
+ * throughout on the device; no atomics; one owner per written byte; the same bytes on every run (tests/warp/warpref.py restates it in numpy).
+ *
+ * MESH.  A destination frame of dw x dh pixels and a cell of c = 1 << s pixels, c one of 8, 16, 32, 64, have a mesh of
+ * mw = (dw - 1) / c + 2 by mh = (dh - 1) / c + 2 points.  Point (ci, cj) is a pair of int32 (x, y): the source position of destination pixel
+ * (ci c, cj c) in units of 1 / 256 source pixel (FFGPU_WARP_MESH_ONE); an integer position is the centre of that source pixel.  The mesh lives
+ * in DEVICE memory, built once per camera, 8-byte aligned, rows of mw pairs.  Any int32 value is legal: the kernel never reads a byte outside
+ * the source frame, whatever the mesh holds.
+ *
+ * INTERPOLATION.  For destination pixel (i, j): ci = i >> s, a = i & (c - 1), cj = j >> s, b = j & (c - 1); P00, P10, P01, P11 are the points at
+ * (ci, cj), (ci + 1, cj), (ci, cj + 1), (ci + 1, cj + 1).  In 64-bit integers, for x and for y alike:
+ *     S  = (c - b) * ((c - a) * P00 + a * P10) + b * ((c - a) * P01 + a * P11)
+ *     X8 = (S + (1 << (2 s - 1))) >> (2 s)        (the shift is arithmetic)
+ *     x5 = (X8 + 4) >> 3                          (in 1 / 32 pixel, FFGPU_WARP_SUB)
+ * Neighbouring cells share points, so the map is continuous.
+ *
+ * SAMPLING.  FFGPU_WARP_BILINEAR: x0 = x5 >> 5, fx = x5 & 31, and likewise for y; the taps are (x0, y0), (x0 + 1, y0), (x0, y0 + 1),
+ * (x0 + 1, y0 + 1), and per channel
+ *     out = ((32 - fy) * ((32 - fx) * v00 + fx * v10) + fy * ((32 - fx) * v01 + fx * v11) + 512) >> 10.
+ * FFGPU_WARP_NEAREST: the one tap ((x5 + 16) >> 5, (y5 + 16) >> 5).  Border FFGPU_WARP_FILL: a tap outside the source frame has the fill
+ * colour's channel as its value, so an edge is a blend and a pixel whose taps are all outside is the fill.  Border FFGPU_WARP_CLAMP: each tap
+ * coordinate is clamped to 0 .. sw - 1 and 0 .. sh - 1.
+ *
+ * BGR: the three channels share the position.
+ * NV12: the Y plane is sampled as above.  Destination chroma sample (i, j) takes the mesh at luma pixel (2 i, 2 j), which is always inside the
+ * mesh; its position in the chroma plane is xc5 = (X8 + 8) >> 4, yc5 likewise; it samples U and V as two channels of a plane of
+ * ((sw + 1) / 2) x ((sh + 1) / 2) under the same filter and border.  The fill is Y U V.  `matrix` of the frames is not read; chroma is treated
+ * as co-sited, as the NV12 conversion above treats it.
+ *
+ * What follows from the rule: the identity mesh is a byte copy; the eight orientations permute bytes exactly; an integer translation shifts the
+ * frame and fills; a constant plane stays constant under CLAMP; NEAREST writes only source bytes or the fill.  The operator does no area
+ * averaging: strong minification aliases, so scale down with the preview operator afterwards.
+ * Untouched: row padding, memory round the destination, every source byte, the mesh. */
+#define FFGPU_WARP_MESH_ONE   256   /* mesh units per source pixel */
+#define FFGPU_WARP_SUB        32    /* sampling positions per source pixel */
+#define FFGPU_WARP_BILINEAR   0     /* filter */
+#define FFGPU_WARP_NEAREST    1
+#define FFGPU_WARP_FILL       0     /* border */
+#define FFGPU_WARP_CLAMP      1
+#define FFGPU_WARP_MAX_SIDE   8192
+#define FFGPU_WARP_MAX_JOBS   4096
+#define FFGPU_WARP_LENS_BROWN        0
+#define FFGPU_WARP_LENS_EQUIDISTANT  1
+typedef struct {
+    const int *xy;                 /* mh rows of mw (x, y) pairs, 8-byte aligned; device memory for the operators, host memory for ffgpu_warp_point */
+    int mw, mh;                    /* must equal the formula for the job's destination */
+    int cell;                      /* 8, 16, 32 or 64 */
+    int reserved;                  /* 0 */
+} ffgpu_warp_mesh;                 /* 24 bytes: xy 0, mw 8, mh 12, cell 16, reserved 20 */
+typedef struct {
+    int filter;                    /* FFGPU_WARP_BILINEAR or FFGPU_WARP_NEAREST */
+    int border;                    /* FFGPU_WARP_FILL or FFGPU_WARP_CLAMP */
+    unsigned char fill[4];         /* B G R 0 or Y U V 0, byte 3 must be 0 */
+    int reserved;                  /* 0 */
+} ffgpu_warp_spec;                 /* 16 bytes: filter 0, border 4, fill 8, reserved 12 */
+typedef struct {
+    int model;                     /* FFGPU_WARP_LENS_BROWN or FFGPU_WARP_LENS_EQUIDISTANT */
+    int reserved;                  /* 0 */
+    double dst[4];                 /* fx fy cx cy of the destination, the ideal pinhole image; fx and fy finite and above 0 */
+    double src[4];                 /* fx fy cx cy of the source, the camera as it is */
+    double k[4];                   /* radial coefficients k1 .. k4 (BROWN reads k1 .. k3) */
+    double p[2];                   /* tangential coefficients p1 p2 (BROWN only) */
+} ffgpu_warp_lens;                 /* 120 bytes: model 0, reserved 4, dst 8, src 40, k 72, p 104 */
+
+/* Pure host code, every function below: 0, or -1 with the message in ffgpu_last_error.  The builders write the mh x mw pairs of a mesh into HOST
+ * memory `xy` (the caller copies them to the device).  Doubles are evaluated in the order written, without contraction; each coordinate is
+ * floor(v * 256 + 0.5) saturated to int32; a non-finite value or a non-positive perspective denominator gives INT32_MIN, which lands outside
+ * the frame. */
+int ffgpu_warp_spec_check(const ffgpu_warp_spec *spec);
+/* out = { mw, mh } for a destination of dst_w x dst_h (1..FFGPU_WARP_MAX_SIDE each) and a cell of 8, 16, 32 or 64 */
+int ffgpu_warp_mesh_size(int dst_w, int dst_h, int cell, int out[2]);
+/* The eight orientations of a src_w x src_h frame.  orient 0..3 is a clockwise rotation by 0, 90, 180, 270 degrees; orient 4..7 mirrors the
+ * source left to right first and then rotates by orient - 4.  out_dst_wh = { dw, dh }: the source's sizes, exchanged for odd orient.  Destination
+ * pixel (i, j) is source pixel (x, y), with W = src_w and H = src_h:
+ *     0: (i, j)   1: (j, H - 1 - i)   2: (W - 1 - i, H - 1 - j)   3: (W - 1 - j, i)
+ *     4: (W - 1 - i, j)   5: (W - 1 - j, H - 1 - i)   6: (i, H - 1 - j)   7: (j, i)
+ * The points are exact integers (256 times the formula at (ci c, cj c)).  xy may be NULL to ask for the sizes only.  The inverse of orient 1 is
+ * 3 and of 3 is 1; every other orient is its own inverse. */
+int ffgpu_warp_mesh_orient(int src_w, int src_h, int orient, int cell, int out_dst_wh[2], int *xy);
+/* A homography h[9], row-major, from destination pixel (i, j) to the source position:
+ *     x = ((h0 i + h1 j) + h2) / ((h6 i + h7 j) + h8),  y = ((h3 i + h4 j) + h5) / ((h6 i + h7 j) + h8).
+ * An affine map is h6 = h7 = 0, h8 = 1.  A denominator that is not above 0 gives INT32_MIN for both coordinates of the point. */
+int ffgpu_warp_mesh_homography(int dst_w, int dst_h, int cell, const double h[9], int *xy);
+/* A lens: the destination is the ideal pinhole image, the source the camera's.  For the mesh point at destination pixel (i, j):
+ *     xn = (i - dst_cx) / dst_fx,  yn = (j - dst_cy) / dst_fy,  r2 = xn xn + yn yn
+ * FFGPU_WARP_LENS_BROWN, radial 1 + k1 r^2 + k2 r^4 + k3 r^6 plus tangential p1, p2:
+ *     rad = 1 + ((k3 r2 + k2) r2 + k1) r2
+ *     xd = xn rad + ((2 p1) (xn yn) + p2 (r2 + (2 xn) xn)),  yd = yn rad + (p1 (r2 + (2 yn) yn) + (2 p2) (xn yn))
+ * FFGPU_WARP_LENS_EQUIDISTANT, the fisheye:
+ *     r = sqrt(r2),  theta = atan(r),  t2 = theta theta,  theta_d = theta (1 + ((((k4 t2 + k3) t2 + k2) t2 + k1) t2))
+ *     scale = theta_d / r, or 1 where r is 0;  xd = xn scale,  yd = yn scale
+ * then x = src_fx xd + src_cx, y = src_fy yd + src_cy. */
+int ffgpu_warp_mesh_lens(int dst_w, int dst_h, int cell, const ffgpu_warp_lens *lens, int *xy);
+/* The interpolation rule for destination pixel (i, j) on a HOST copy of the mesh: out = { X8, Y8 }.  For hit-testing and the tests. */
+int ffgpu_warp_point(const ffgpu_warp_mesh *mesh_on_host, int dst_w, int dst_h, int i, int j, int out[2]);
+/* out = { the columns and the rows of a workgroup's tile of destination pixels, the bytes of LDS the staged form may fill, the jobs one launch takes } */
+int ffgpu_warp_tile(int out[4]);
+
+/* The operators.  srcs, dsts, meshes and spec are HOST arrays, free again on return; job n reads srcs[n] through meshes[n] into the WHOLE of
+ * dsts[n] (the const pointers of the destinations are written through); frames are described exactly as the draw operators take them; a pane of a
+ * larger surface is a frame descriptor into it, as with the tiles.  A workgroup owns a tile of destination pixels and is the only writer of those
+ * bytes.  The tile's taps lie inside the bounding box of the mesh points of the cells the tile touches, plus one pixel; where that box, clipped to
+ * the frame, fits the LDS budget, the workgroup loads it once with aligned loads and samples from LDS (staged); where not, every lane loads its taps'
+ * bytes from global memory (direct).  The choice is uniform per workgroup and both forms give the same bytes.  BGR frames have both forms; the planes
+ * of NV12 frames are always read directly (measured: DESIGN 5.33).  The jobs travel as a by-value table inside a kernel
+ * argument, 64 per launch; more jobs are more launches, in order on `stream`.  Enqueued without synchronising; stream order is the only barrier.
+ * There is no executor form: the operator reads frames, not records.  A job whose source or destination pixel address (bgr / y) is NULL is
+ * skipped; its sizes and its mesh are not looked at.  Rejected before anything is launched, with the job's index: everything the draw operators
+ * reject about a frame description, for sources and destinations; NULL arrays or spec; njobs outside 1..FFGPU_WARP_MAX_JOBS; a side above
+ * FFGPU_WARP_MAX_SIDE; an unknown filter or border, fill[3] != 0, reserved != 0; a NULL, misaligned or wrongly sized mesh, or a bad cell; a job
+ * whose source and destination pixel addresses are equal; two jobs with the same destination pixel address (both indices).  Any other overlap of
+ * memory is the caller's responsibility. */
+int ffgpu_warp_bgr_dev(const ffgpu_bgr_frame *srcs, const ffgpu_bgr_frame *dsts, const ffgpu_warp_mesh *meshes, int njobs,
+                       const ffgpu_warp_spec *spec, void *stream);
+int ffgpu_warp_nv12_dev(const ffgpu_nv12_frame *srcs, const ffgpu_nv12_frame *dsts, const ffgpu_warp_mesh *meshes, int njobs,
+                        const ffgpu_warp_spec *spec, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
