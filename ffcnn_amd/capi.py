@@ -304,7 +304,7 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_exec_kernel_count", "ffgpu_exec_work_model", "ffgpu_exec_set_scale", "ffgpu_exec_forward_dev", "ffgpu_exec_forward_host",
            "ffgpu_exec_forward_bgr_dev", "ffgpu_exec_forward_bgr_frames_dev", "ffgpu_exec_forward_nv12_frames_dev", "ffgpu_exec_dets_dev", "ffgpu_exec_dets_host", "ffgpu_exec_set_ring", "ffgpu_exec_set_ring_strided", "ffgpu_exec_read_dets", "ffgpu_exec_read_layer", "ffgpu_exec_hash_layers",
            "ffgpu_exec_read_boxes", "ffgpu_exec_cand_capacity", "ffgpu_exec_graph_captures",
-           "ffgpu_exec_profile", "ffgpu_exec_profile_steps", "ffgpu_exec_step_model", "ffgpu_groupconv_dev", "ffgpu_groupconv_kernel_name", "ffgpu_groupconv_time_dev", "ffgpu_irb_dev", "ffgpu_irb_flags_dev", "ffgpu_irb_plan_text", "ffgpu_irb_thin_launch_text", "ffgpu_irb_stage_plan_text", "ffgpu_front_plan_text", "ffgpu_irb_instantiations", "ffgpu_knobs_text", "ffgpu_dwpw_dev", "ffgpu_packed_records_bytes", "ffgpu_pack_records", "ffgpu_unpack_records",
+           "ffgpu_exec_profile", "ffgpu_exec_profile_steps", "ffgpu_exec_step_model", "ffgpu_groupconv_dev", "ffgpu_groupconv_kernel_name", "ffgpu_groupconv_time_dev", "ffgpu_irb_dev", "ffgpu_irb_flags_dev", "ffgpu_irb_plan_text", "ffgpu_irb_thin_launch_text", "ffgpu_irb_s2_launch_text", "ffgpu_irb_stage_plan_text", "ffgpu_front_plan_text", "ffgpu_irb_instantiations", "ffgpu_knobs_text", "ffgpu_dwpw_dev", "ffgpu_packed_records_bytes", "ffgpu_pack_records", "ffgpu_unpack_records",
            "ffgpu_shard_range", "ffgpu_node_create", "ffgpu_node_destroy", "ffgpu_node_ndev", "ffgpu_node_shard", "ffgpu_node_set_scale",
            "ffgpu_node_input_dev", "ffgpu_node_input_slot_dev", "ffgpu_node_depth", "ffgpu_node_rccl_ranks", "ffgpu_node_forward", "ffgpu_node_forward_host",
            "ffgpu_node_submit", "ffgpu_node_wait", "ffgpu_node_run",
@@ -412,6 +412,7 @@ def lib():
     L.ffgpu_irb_flags_dev.restype = C.c_float
     L.ffgpu_irb_flags_dev.argtypes = [vp] * 6 + [i] * 14 + [vp]
     L.ffgpu_irb_thin_launch_text.argtypes = [i] * 12 + [C.c_char_p, i]
+    L.ffgpu_irb_s2_launch_text.argtypes = [i] * 12 + [C.c_char_p, i]
     L.ffgpu_irb_plan_text.argtypes = [i] * 12 + [C.c_char_p, i]
     L.ffgpu_irb_stage_plan_text.argtypes = [i] * 7 + [C.c_char_p, i]
     L.ffgpu_front_plan_text.argtypes = [i] * 4 + [C.c_char_p, i]
@@ -1955,6 +1956,16 @@ def irb_thin_launch_text(shape, flags=0):
     buf = C.create_string_buffer(256)
     if lib().ffgpu_irb_thin_launch_text(*shape, flags, buf, len(buf)) < 0:
         raise RuntimeError("ffgpu_irb_thin_launch_text failed: %s" % last_error())
+    return buf.value.decode()
+
+
+def irb_s2_launch_text(shape, flags=0):
+    """what the launch of the block shape = (batch, iw, ih, ic, ec, oc, stride, act1, actd, act2, res_act) does in an executor made with `flags`:
+    "thin_s2<4,24,8,3> frames= band= tasks= grid= ..." (the streaming stride-2 form), "<planned key> frames= band= tasks= grid= block=" or
+    "unsupported" (no GPU needed)"""
+    buf = C.create_string_buffer(256)
+    if lib().ffgpu_irb_s2_launch_text(*shape, flags, buf, len(buf)) < 0:
+        raise RuntimeError("ffgpu_irb_s2_launch_text failed: %s" % last_error())
     return buf.value.decode()
 
 

@@ -8,6 +8,7 @@
 #include "ffgpu_conv_dense.inc"
 #include "ffgpu_irb.inc"
 #include "ffgpu_irb_thin.inc"
+#include "ffgpu_irb_thin_s2.inc"
 #include "ffgpu_front.inc"
 #include "ffgpu_irb_wave.inc"
 #include "ffgpu_irb_wave2.inc"
@@ -1179,6 +1180,53 @@ int ffgpu_irb_thin_launch_line(const IrbDesc &d, char *buf, size_t cap)
     return snprintf(buf, cap, "%s W=%d H=%d N=%d band=%d nbands=%d ntasks=%ld grid=%d block=256", key, d.W, d.H, d.N, f.band, f.nbands, f.ntasks, f.grid);
 }
 
+// ---- streaming stride-2 form (ffgpu_irb_thin_s2.inc): the 4 -> 24 -> 8 block of a 160-pixel plane on the vector ALU.  Like the paired thin form it is the
+// LAUNCH's choice, not the plan's: the block stays planned as the wave form (plan line, packed image and instantiation list are what they were), and the
+// streaming kernel reads the filter rows, not the image, so a later change of FFGPU_THIN_S2 cannot mismatch anything.
+// Taken where the block is stride 2 with (ic, ec, oc) = (4, 24, 8) on an even-width plane, a row of the output fits 32 lanes at NC = 3 columns per lane
+// (and has three columns), the batch has at least two frames, the block has no residual, the executor runs several chains (FFGPU_CONCURRENT), the activations are the thin family's and
+// FFGPU_THIN_S2 is not 0.  (NC = 4 -- 20 lanes, three frames -- needs 90 registers more than the file has and is not built.)
+// Band: output rows per wave; the longest of 2, 4, 8, 16 that leaves the launch THIN_S2_WAVES waves (4 rows at batch 64, 640 waves: 213.9 k frames/s against 212.3 k at 8 rows and 202.5 k
+// at 16, profiles/thin_s2_ab.txt), unless FFGPU_THIN_S2_BAND names one.  The rule is fitted to that one batch: smaller batches get 2 rows by it (a halo row per four expanded rows
+// instead of one per eight), and neither 2 rows nor any other batch has been measured.
+#define THIN_S2_NC 3
+#define THIN_S2_WAVES 640
+struct ThinS2Form { bool on; int lpr, F, band, nbands; long ntasks; int grid; };
+static ThinS2Form thin_s2_form(const IrbDesc &d)
+{
+    ThinS2Form f{};
+    const int lpr = (d.OW + THIN_S2_NC - 1) / THIN_S2_NC;
+    f.on = d.stride == 2 && d.ic == 4 && d.ec == 24 && d.oc == 8 && d.W % 2 == 0 && d.OW == d.W / 2 && d.OH == (d.H + 1) / 2 && d.OW >= THIN_S2_NC && lpr <= 32 &&
+           d.N >= 2 && (d.flags & FFGPU_CONCURRENT) && !d.residual &&
+           (size_t)d.ic * d.N * d.H * d.W < (1u << 30) &&                    // 32-bit offsets (the wave plan's own condition)
+           d.act1 != 3 && d.actd != 3 && d.act2 != 3 && knob(K_THIN_S2) != 0;
+    if (!f.on) return f;
+    f.lpr = lpr; f.F = 64 / lpr;
+    const int groups = (d.N + f.F - 1) / f.F;
+    int band = 2;
+    while (band < 16 && (long)groups * d.OH >= (long)THIN_S2_WAVES * band * 2) band *= 2;
+    if (const int kb = knob(K_THIN_S2_BAND); kb > 0) band = kb;
+    f.band = band;
+    f.nbands = (d.OH + f.band - 1) / f.band;
+    f.ntasks = (long)groups * f.nbands;
+    f.grid = (int)((f.ntasks + 3) / 4);
+    return f;
+}
+
+static int launch_irb_thin_s2(const IrbDesc &d, const ThinS2Form &f, hipStream_t s)
+{
+    ThinS2P p;
+    p.in = d.in; p.out = d.out; p.w1 = d.w1; p.wd = d.wd; p.w2 = d.w2;
+    p.W = d.W; p.H = d.H; p.N = d.N; p.OW = d.OW; p.OH = d.OH;
+    p.lpr = f.lpr; p.F = f.F; p.band = f.band; p.nbands = f.nbands;
+    p.act1 = act_slope(d.act1); p.actd = act_slope(d.actd); p.act2 = act_slope(d.act2);
+    p.ntasks = f.ntasks;
+    if (!p.in || !p.out || !p.w1 || !p.wd || !p.w2) { ffgpu_set_error("irb_thin_s2: no tensors or filter rows"); return -1; }
+    hipLaunchKernelGGL((k_irb_thin_s2<4, 24, 8, THIN_S2_NC>), dim3((unsigned)f.grid), dim3(256), 0, s, p);
+    LAUNCH_OK("irb_thin_s2");
+    return 0;
+}
+
 // ---- wave-autonomous form (ffgpu_irb_wave.inc, ffgpu_irb_wave2.inc): every instantiation that exists, shape test, tile / split choice, launch shape
 typedef int (*IrbwLaunch)(const IrbwP &, const IrbPlan &, hipStream_t);
 // S: stride; NSI: input strips per wave; NSO: output strips per wave (2: k_irbw2); big: the 256-register budget; x3: expand GEMM as split-bf16 products;
@@ -1745,12 +1793,34 @@ int ffgpu_irb_plan_line(const IrbDesc &d, char *buf, size_t cap)
     return snprintf(buf, cap, "unsupported");
 }
 
+// one line per launch of a planned block that the streaming stride-2 form may take: the form (thin_s2<4,24,8,3>, or the planned key where the launch
+// follows the plan), frames per wave, band (rows per task), tasks and grid -- pure host arithmetic (ffgpu_irb_s2_launch_text; tests/test_thin_s2_host.py)
+int ffgpu_irb_s2_launch_line(const IrbDesc &d, char *buf, size_t cap)
+{
+    const IrbPlan &c = d.plan;
+    char key[48];
+    if (c.family == IRB_NONE) return snprintf(buf, cap, "unsupported");
+    if (c.family == IRB_THIN) {
+        const ThinP p = thin_params(d);
+        irb_thin_key(d.ic, d.oc, key, sizeof key);
+        return snprintf(buf, cap, "%s frames=1 band=%d tasks=%ld grid=%d block=%d", key, p.band, p.ntasks, c.grid, c.block);
+    }
+    if (const ThinS2Form f = thin_s2_form(d); f.on)
+        return snprintf(buf, cap, "thin_s2<%d,%d,%d,%d> frames=%d band=%d tasks=%ld grid=%d block=256 W=%d H=%d N=%d lanes=%d nbands=%d",
+                        d.ic, d.ec, d.oc, THIN_S2_NC, f.F, f.band, f.ntasks, f.grid, d.W, d.H, d.N, f.lpr, f.nbands);
+    long tiles;
+    if (c.family == IRB_WAVE) { irbw_key(irbw_kernels[c.inst], key, sizeof key); tiles = irbw_params(d).ntiles; }
+    else { irb_key(irb_kernels[c.inst], key, sizeof key); tiles = irb_params(d).ntiles; }
+    return snprintf(buf, cap, "%s frames=%d band=%d tasks=%ld grid=%d block=%d", key, c.family == IRB_WG ? c.NF : 1, c.TH, tiles, c.grid, c.block);
+}
+
 int ffgpu_launch_irb(const IrbDesc &d, hipStream_t s)
 {
     const IrbPlan &c = d.plan;
     if (!irb_planned(d, "irb")) return -1;
     if (knob(K_VERBOSE_IRB)) { char line[1024]; ffgpu_irb_plan_line(d, line, sizeof line); fprintf(stderr, "%s\n", line); }
     if (c.family == IRB_THIN) return launch_irb_thin(d, s);
+    if (const ThinS2Form f = thin_s2_form(d); f.on) return launch_irb_thin_s2(d, f, s);      // the launch's choice; the plan and its image stay the wave form's
     if (!d.pk) { ffgpu_set_error("irb: constants not packed"); return -1; }
     return c.family == IRB_WAVE ? irbw_kernels[c.inst].launch(irbw_params(d), c, s) : irb_kernels[c.inst].launch(irb_params(d), c, s);
 }

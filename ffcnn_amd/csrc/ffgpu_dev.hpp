@@ -90,6 +90,7 @@ int    ffgpu_irb_pack(const IrbDesc &d, float *pk, hipStream_t s);
 int    ffgpu_launch_irb(const IrbDesc &d, hipStream_t s);
 int    ffgpu_irb_plan_line(const IrbDesc &d, char *buf, size_t cap);   // the plan as one canonical line of text (ffgpu_irb_plan_text)
 int    ffgpu_irb_thin_launch_line(const IrbDesc &d, char *buf, size_t cap);   // a planned thin block's launch as one line: single or paired form, band, tasks, grid (ffgpu_irb_thin_launch_text)
+int    ffgpu_irb_s2_launch_line(const IrbDesc &d, char *buf, size_t cap);     // a planned block's launch as one line: the streaming stride-2 form (k_irb_thin_s2) or the planned key, frames per wave, band, tasks, grid (ffgpu_irb_s2_launch_text)
 int    ffgpu_irb_keys(char *buf, size_t cap);                            // the key of every instantiation of the three families, one per line (ffgpu_irb_instantiations)
 // a run of B >= 2 blocks on one small plane (48 -> 224 -> 48, stride 1, linear project and shortcut) as one launch, one frame per workgroup
 // (ffgpu_irb_stage.inc): the blocks' own planned descriptors, whose packed images the kernel reads; in = blocks[0].in, out = blocks[B - 1].out

@@ -2042,6 +2042,18 @@ extern "C" int ffgpu_irb_thin_launch_text(int batch, int iw, int ih, int ic, int
     return ffgpu_irb_thin_launch_line(d, buf, (size_t)cap);
 }
 
+// pure host code: what the launch of a planned block does where the streaming stride-2 form may take it -- thin_s2<4,24,8,3> or the planned key, frames
+// per wave, band, tasks and grid
+extern "C" int ffgpu_irb_s2_launch_text(int batch, int iw, int ih, int ic, int ec, int oc, int stride, int act1, int actd, int act2, int res_act, int flags, char *buf, int cap)
+{
+    if (!buf || cap < 1 || batch < 1 || iw < 1 || ih < 1 || stride < 1) { ffgpu_set_error("irb_s2_launch_text: bad arguments"); return -1; }
+    IrbDesc d{};
+    irb_fill(d, batch, iw, ih, ic, ec, oc, stride, act1, actd, act2, res_act);
+    d.flags = flags & FFGPU_CONCURRENT;
+    (void)ffgpu_irb_plan(d);
+    return ffgpu_irb_s2_launch_line(d, buf, (size_t)cap);
+}
+
 extern "C" float ffgpu_irb_dev(const float *d_in, const float *d_w1, const float *d_wd, const float *d_w2,
                                const float *d_res, float *d_out, int batch, int iw, int ih, int ic, int ec, int oc,
                                int stride, int act1, int actd, int act2, int res_act, int warmup, int iters, void *stream)

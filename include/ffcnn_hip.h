@@ -342,6 +342,16 @@ float ffgpu_irb_flags_dev(const float *d_in, const float *d_w1, const float *d_w
 int ffgpu_irb_thin_launch_text(int batch, int iw, int ih, int ic, int ec, int oc, int stride, int act1, int actd, int act2, int res_act,
                                int flags, char *buf, int cap);
 
+/* What the LAUNCH of a planned block does where the streaming stride-2 form (k_irb_thin_s2) may take it, as one line of text in buf (at most cap bytes;
+ * returns snprintf's count): "thin_s2<4,24,8,3> frames= band= tasks= grid= block= W= H= N= lanes= nbands=" -- frames per wave, output rows per
+ * task, the launch's own tasks and grid: taken where the block is stride 2 with 4 -> 24 -> 8 channels on an even-width plane, a row of the output
+ * fits 32 lanes at three columns per lane and has at least three, the batch has at least two frames, the block has no residual, its input tensor fits
+ * 32-bit offsets (under 2^30 floats), the activations are linear, relu or leaky, flags has FFGPU_CONCURRENT and FFGPU_THIN_S2 is not 0 --, or
+ * "<planned key> frames= band= tasks= grid= block=" where the launch follows the plan, or "unsupported".  Arguments as ffgpu_irb_plan_text, whose
+ * line does not change with the form.  Pure host code. */
+int ffgpu_irb_s2_launch_text(int batch, int iw, int ih, int ic, int ec, int oc, int stride, int act1, int actd, int act2, int res_act,
+                             int flags, char *buf, int cap);
+
 /* What the planner decides for that block, as one line of text in buf (at most cap bytes; returns snprintf's count): the kernel
  * family and instantiation, every scalar of the parameter block the launch would pass, LDS bytes, grid, block, `half`, the floats
  * of the packed image -- or "unsupported".  flags: FFGPU_CONCURRENT or 0.  Pure host code (no device needed): for tests and logs. */

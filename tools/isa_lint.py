@@ -37,7 +37,9 @@ KNOWN_FORMS = {
     'v_pk_fma_f32 vvc op_sel_hi:[1,1,0]': 790,
     'v_pk_fma_f32 vvv op_sel:[0,1,0]': 212,
     'v_pk_fma_f32 vvv op_sel:[1,0,0]': 3384,      # (1992 before k_irb_thin_pair)
-    'v_pk_fma_f32 vvv op_sel_hi:[0,1,1]': 4781,
+    'v_pk_fma_f32 vvv op_sel_hi:[0,1,1]': 8117,      # (7613 before k_irb_thin_s2, recorded as 4781 when the form was last soaked; the new kernel's 504 are the thin kernels' own arithmetic -- a tap
+                                                     #  pair times one pixel plus a sum; the four-chain runs of tests/test_gpu_round5.py take the streaming stride-2 form and soak it next to the
+                                                     #  bf16 MFMAs of the other chains)
     'v_pk_fma_f32 vvv op_sel_hi:[1,0,1]': 5446,      # (2608 before k_irb_thin_pair)
     'v_pk_mul_f32 sv op_sel:[1,0]': 51,
     'v_pk_mul_f32 sv op_sel_hi:[0,1]': 839,      # (349 before k_irb_thin_pair)
