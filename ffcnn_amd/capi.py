@@ -304,7 +304,7 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_exec_kernel_count", "ffgpu_exec_work_model", "ffgpu_exec_set_scale", "ffgpu_exec_forward_dev", "ffgpu_exec_forward_host",
            "ffgpu_exec_forward_bgr_dev", "ffgpu_exec_forward_bgr_frames_dev", "ffgpu_exec_forward_nv12_frames_dev", "ffgpu_exec_dets_dev", "ffgpu_exec_dets_host", "ffgpu_exec_set_ring", "ffgpu_exec_set_ring_strided", "ffgpu_exec_read_dets", "ffgpu_exec_read_layer", "ffgpu_exec_hash_layers",
            "ffgpu_exec_read_boxes", "ffgpu_exec_cand_capacity", "ffgpu_exec_graph_captures",
-           "ffgpu_exec_profile", "ffgpu_exec_profile_steps", "ffgpu_exec_step_model", "ffgpu_groupconv_dev", "ffgpu_groupconv_kernel_name", "ffgpu_groupconv_time_dev", "ffgpu_irb_dev", "ffgpu_irb_flags_dev", "ffgpu_irb_plan_text", "ffgpu_irb_thin_launch_text", "ffgpu_irb_s2_launch_text", "ffgpu_irb_stage_plan_text", "ffgpu_front_plan_text", "ffgpu_irb_instantiations", "ffgpu_knobs_text", "ffgpu_dwpw_dev", "ffgpu_packed_records_bytes", "ffgpu_pack_records", "ffgpu_unpack_records",
+           "ffgpu_exec_profile", "ffgpu_exec_profile_steps", "ffgpu_exec_step_model", "ffgpu_groupconv_dev", "ffgpu_groupconv_kernel_name", "ffgpu_groupconv_time_dev", "ffgpu_irb_dev", "ffgpu_irb_flags_dev", "ffgpu_irb_plan_text", "ffgpu_irb_thin_launch_text", "ffgpu_irb_s2_launch_text", "ffgpu_sparse_head_dev", "ffgpu_sparse_head_launch_text", "ffgpu_irb_stage_plan_text", "ffgpu_front_plan_text", "ffgpu_irb_instantiations", "ffgpu_knobs_text", "ffgpu_dwpw_dev", "ffgpu_packed_records_bytes", "ffgpu_pack_records", "ffgpu_unpack_records",
            "ffgpu_shard_range", "ffgpu_node_create", "ffgpu_node_destroy", "ffgpu_node_ndev", "ffgpu_node_shard", "ffgpu_node_set_scale",
            "ffgpu_node_input_dev", "ffgpu_node_input_slot_dev", "ffgpu_node_depth", "ffgpu_node_rccl_ranks", "ffgpu_node_forward", "ffgpu_node_forward_host",
            "ffgpu_node_submit", "ffgpu_node_wait", "ffgpu_node_run",
@@ -413,6 +413,8 @@ def lib():
     L.ffgpu_irb_flags_dev.argtypes = [vp] * 6 + [i] * 14 + [vp]
     L.ffgpu_irb_thin_launch_text.argtypes = [i] * 12 + [C.c_char_p, i]
     L.ffgpu_irb_s2_launch_text.argtypes = [i] * 12 + [C.c_char_p, i]
+    L.ffgpu_sparse_head_dev.argtypes = [vp, vp, vp] + [i] * 6 + [C.c_float, vp, vp, vp]
+    L.ffgpu_sparse_head_launch_text.argtypes = [i] * 6 + [C.c_char_p, i]
     L.ffgpu_irb_plan_text.argtypes = [i] * 12 + [C.c_char_p, i]
     L.ffgpu_irb_stage_plan_text.argtypes = [i] * 7 + [C.c_char_p, i]
     L.ffgpu_front_plan_text.argtypes = [i] * 4 + [C.c_char_p, i]
@@ -1966,6 +1968,21 @@ def irb_s2_launch_text(shape, flags=0):
     buf = C.create_string_buffer(256)
     if lib().ffgpu_irb_s2_launch_text(*shape, flags, buf, len(buf)) < 0:
         raise RuntimeError("ffgpu_irb_s2_launch_text failed: %s" % last_error())
+    return buf.value.decode()
+
+
+def sparse_head_dev(d_in, d_filt, d_out, batch, iw, ih, ic, classes, thresh, d_list, d_count, act=0, stream=None):
+    """the pointwise layer ic -> 3 (5 + classes) in front of a yolo head as the sparse pair of k_conv_x3 launches (box pass, class pass) on caller-owned
+    device tensors; d_list (batch ih iw / 4 int32) and d_count (one int32, the caller zeroes it) receive the listed quads and their number"""
+    _check(lib().ffgpu_sparse_head_dev(d_in, d_filt, d_out, batch, iw, ih, ic, classes, act, thresh, d_list, d_count, stream), "ffgpu_sparse_head_dev")
+
+
+def sparse_head_launch_text(batch, iw, ih, ic, classes, flags=0):
+    """what an executor made with `flags` launches for that layer: "sparse box<1,NW> rows=15 grid= class<MT,NW> rows= grid= quads= image=" or
+    "dense <kernel>" (no GPU needed)"""
+    buf = C.create_string_buffer(256)
+    if lib().ffgpu_sparse_head_launch_text(batch, iw, ih, ic, classes, flags, buf, len(buf)) < 0:
+        raise RuntimeError("ffgpu_sparse_head_launch_text failed: %s" % last_error())
     return buf.value.decode()
 
 

@@ -285,7 +285,19 @@ static int ig_x3_mt_plan(const ConvDesc &d)
 }
 static int ig_x3_mt(const ConvDesc &d) { const int m = d.x3_mt == 4 || d.x3_mt == 2 || d.x3_mt == 1 ? d.x3_mt : ig_x3_mt_plan(d); return d.stride == 2 && m > 2 ? 2 : m; }
 static void ig_x3_dims(const ConvDesc &d, int &MT, int &ngr, int &nrb, int &ntm) { MT = ig_x3_mt(d); ngr = (d.fs * (d.ic / 8) + 3) / 4; nrb = (d.oc + 15) / 16; ntm = (nrb + MT - 1) / MT; }
-static size_t ig_x3_img_dwords(const ConvDesc &d) { int MT, ngr, nrb, ntm; ig_x3_dims(d, MT, ngr, nrb, ntm); return (size_t)ntm * ngr * 3 * d.fs * MT * 256; }
+// The sparse form of a yolo head's input layer (ConvDesc::sp_classes; ffgpu_conv_x3.inc "SPARSE HEAD"): form sp = 1 (box pass: one 16-row block at MT = 1) and
+// sp = 2 (class pass: 3 x classes rows at the layer's own MT) read row-permuted images that lie BEHIND the regular one in the layer's packed image -- sized,
+// filled and refreshed with it by this table's one rule (conv_image, ffgpu_pw_pack_floats, ffgpu_pw_pack).
+static bool ig_x3_sparse(const ConvDesc &d) { return d.sp_classes > 0 && d.fs == 1 && d.oc == 3 * (5 + d.sp_classes); }
+static void ig_x3_sp_dims(const ConvDesc &d, int sp, int &MT, int &ngr, int &nrb, int &ntm)
+{
+    ig_x3_dims(d, MT, ngr, nrb, ntm);
+    if (sp == 1) { MT = 1; nrb = 1; }
+    if (sp == 2) nrb = (3 * d.sp_classes + 15) / 16;
+    ntm = (nrb + MT - 1) / MT;
+}
+static size_t ig_x3_sp_dwords(const ConvDesc &d, int sp) { int MT, ngr, nrb, ntm; ig_x3_sp_dims(d, sp, MT, ngr, nrb, ntm); return (size_t)ntm * ngr * 3 * d.fs * MT * 256; }
+static size_t ig_x3_img_dwords(const ConvDesc &d) { return ig_x3_sp_dwords(d, 0) + (ig_x3_sparse(d) ? ig_x3_sp_dwords(d, 1) + ig_x3_sp_dwords(d, 2) : 0); }
 // AUTO takes it where it wins over k_conv_igemm (tools/igemm_bench.py): enough (channel tile, pixel range) workgroups to fill the chip -- the
 // fp32 kernel has split-K for the small planes, this one has not.  FFGPU_IG_X3=0: never.
 static bool ig_x3_auto(const ConvDesc &d)
@@ -302,14 +314,18 @@ static bool ig_x3_auto(const ConvDesc &d)
 }
 static int ig_x3_pack(const ConvDesc &d, float *pk, hipStream_t s)
 {
-    IgX3PackP q;
-    int nrb;
-    q.filt = d.filt; q.pk = reinterpret_cast<unsigned *>(pk); q.ic = d.ic; q.oc = d.oc; q.k4 = conv_k4(d); q.fs = d.fs;
-    ig_x3_dims(d, q.MT, q.ngr, nrb, q.ntm);
-    q.nunits = d.fs * (d.ic / 8);
-    const long total = (long)ig_x3_img_dwords(d);
-    hipLaunchKernelGGL(k_conv_x3_pack, dim3((unsigned)std::min((total + 255) / 256, 8192L)), dim3(256), 0, s, q);
-    LAUNCH_OK("conv_x3_pack");
+    unsigned *img = reinterpret_cast<unsigned *>(pk);
+    for (int sp = 0; sp <= (ig_x3_sparse(d) ? 2 : 0); sp++) {         // the regular image, then a sparse head's two
+        IgX3PackP q;
+        int nrb;
+        q.filt = d.filt; q.pk = img; q.ic = d.ic; q.oc = d.oc; q.k4 = conv_k4(d); q.fs = d.fs; q.sp = sp; q.classes = d.sp_classes;
+        ig_x3_sp_dims(d, sp, q.MT, q.ngr, nrb, q.ntm);
+        q.nunits = d.fs * (d.ic / 8);
+        const long total = (long)ig_x3_sp_dwords(d, sp);
+        hipLaunchKernelGGL(k_conv_x3_pack, dim3((unsigned)std::min((total + 255) / 256, 8192L)), dim3(256), 0, s, q);
+        LAUNCH_OK("conv_x3_pack");
+        img += total;
+    }
     return 0;
 }
 
@@ -672,16 +688,19 @@ static int launch_pw_bf16(const ConvDesc &d, const float *image, hipStream_t s)
     return 0;
 }
 
-static int launch_conv_x3(const ConvDesc &d, const float *image, hipStream_t s)
+// the launch of one form: sp = 0 the layer as planned, sp = 1 / 2 the box and the class pass of a sparse head on their images behind the regular one
+static int launch_conv_x3_form(const ConvDesc &d, const float *image, int sp, hipStream_t s)
 {
     IgX3P p;
     int MT;
     p.in = d.in; p.out = d.out; p.residual = d.residual; p.filt = d.filt;
     p.iw = d.iw; p.ih = d.ih; p.ow = d.ow; p.oh = d.oh; p.ic = d.ic; p.oc = d.oc; p.k4 = conv_k4(d); p.act = d.act; p.res_act = d.res_act;
     p.in_cs = (unsigned)d.in_cs; p.in_ns = (unsigned)d.in_ns;
-    ig_x3_dims(d, MT, p.ngr, p.nrb, p.ntm);
+    ig_x3_sp_dims(d, sp, MT, p.ngr, p.nrb, p.ntm);
     p.nunits = d.fs * (d.ic / 8);
-    p.wpack = reinterpret_cast<const unsigned *>(image);
+    p.wpack = reinterpret_cast<const unsigned *>(image) + (sp >= 1 ? ig_x3_sp_dwords(d, 0) : 0) + (sp == 2 ? ig_x3_sp_dwords(d, 1) : 0);
+    p.sp_list = d.sp_list; p.sp_ctr = d.sp_ctr; p.sp_classes = d.sp_classes; p.sp_thresh = d.sp_thresh;
+    p.sp_cap = (int)((long)d.N * d.oh * d.ow / 4);
     const int NW = ig_x3_nw(d);
     p.owp = d.fs == 1 ? d.ow : (d.ow + 3) & ~3; p.P = (long)d.N * d.oh * d.ow; p.Pp = (long)d.N * d.oh * p.owp;
     p.ntn = (p.Pp + 63) / 64; p.npg = (p.ntn + NW - 1) / NW;
@@ -689,6 +708,15 @@ static int launch_conv_x3(const ConvDesc &d, const float *image, hipStream_t s)
     if (nblk > (1L << 30)) { ffgpu_set_error("conv_x3: too many tiles"); return -1; }
     const size_t lds = (size_t)2 * 3 * d.fs * MT * 1024 + (size_t)MT * 128;
     const dim3 grid((unsigned)nblk);
+    if (sp) {
+#define IGX3_LAUNCH_SP(mt, nw, spv) do { if (lds_allow((const void *)k_conv_x3<mt, nw, 1, 1, spv>, lds, "conv_x3")) return -1; hipLaunchKernelGGL((k_conv_x3<mt, nw, 1, 1, spv>), grid, dim3(64 * nw), lds, s, p); } while (0)
+        if (sp == 1) { if (NW == 8) IGX3_LAUNCH_SP(1, 8, 1); else IGX3_LAUNCH_SP(1, 4, 1); }
+        else if (NW == 8) { if (MT == 4) IGX3_LAUNCH_SP(4, 8, 2); else if (MT == 2) IGX3_LAUNCH_SP(2, 8, 2); else IGX3_LAUNCH_SP(1, 8, 2); }
+        else              { if (MT == 4) IGX3_LAUNCH_SP(4, 4, 2); else if (MT == 2) IGX3_LAUNCH_SP(2, 4, 2); else IGX3_LAUNCH_SP(1, 4, 2); }
+#undef IGX3_LAUNCH_SP
+        LAUNCH_OK(sp == 1 ? "conv_x3 (box pass)" : "conv_x3 (class pass)");
+        return 0;
+    }
 #define IGX3_LAUNCH(mt, nw, fs) do { if (lds_allow((const void *)k_conv_x3<mt, nw, fs>, lds, "conv_x3")) return -1; hipLaunchKernelGGL((k_conv_x3<mt, nw, fs>), grid, dim3(64 * nw), lds, s, p); } while (0)
 #define IGX3_LAUNCH2(mt, nw) do { if (d.fs == 1) IGX3_LAUNCH(mt, nw, 1); else IGX3_LAUNCH(mt, nw, 3); } while (0)
     if (d.stride == 2) {
@@ -703,6 +731,33 @@ static int launch_conv_x3(const ConvDesc &d, const float *image, hipStream_t s)
 #undef IGX3_LAUNCH
     LAUNCH_OK("conv_x3");
     return 0;
+}
+
+// a layer marked as a sparse head's (with its list and counter): the box pass, then the class pass over what the box pass listed; every other layer as planned
+static int launch_conv_x3(const ConvDesc &d, const float *image, hipStream_t s)
+{
+    if (!(ig_x3_sparse(d) && d.sp_list && d.sp_ctr && !d.residual)) return launch_conv_x3_form(d, image, 0, s);
+    return launch_conv_x3_form(d, image, 1, s) || launch_conv_x3_form(d, image, 2, s) ? -1 : 0;
+}
+
+// what the launch of the layer in front of a yolo head does, as one line: the sparse pair with its grids and the list's capacity, or the kernel's name
+int ffgpu_conv_sparse_head_line(const ConvDesc &d0, int classes, bool wanted, char *buf, size_t cap)
+{
+    ConvDesc d = d0;
+    ffgpu_conv_plan(d);
+    if (!wanted || !ffgpu_conv_sparse_head_ok(d, classes)) return snprintf(buf, cap, "dense %s", ffgpu_conv_kernel_name(d, FFGPU_K_AUTO));
+    d.sp_classes = classes;
+    int MT, ngr, nrb, ntm1, ntm2;
+    ig_x3_sp_dims(d, 1, MT, ngr, nrb, ntm1);
+    ig_x3_sp_dims(d, 2, MT, ngr, nrb, ntm2);
+    const long slots = (ig_x3_npg(d) + 7) / 8 * 8;
+    return snprintf(buf, cap, "sparse box<1,%d> rows=15 grid=%ld class<%d,%d> rows=%d grid=%ld quads=%ld image=%zu", ig_x3_nw(d), slots * ntm1, MT, ig_x3_nw(d),
+                    3 * classes, slots * ntm2, (long)d.N * d.oh * d.ow / 4, ig_x3_img_dwords(d));
+}
+
+bool ffgpu_conv_sparse_head_ok(const ConvDesc &d, int classes)
+{
+    return classes >= 1 && d.fs == 1 && d.oc == 3 * (5 + classes) && !d.residual && conv_pick(d, FFGPU_K_AUTO) == FFGPU_K_CONV_X3 && ig_x3_ok(d);
 }
 
 static int launch_igemm(const ConvDesc &d, const float *image, hipStream_t s)

@@ -35,9 +35,29 @@ struct IgX3P {
     int  nunits, ngr;            // k-units (8 input channels x one tap row) = 3 ic / 8 (ic % 8 == 0); groups of four units (one per lane quarter) = ceil(nunits / 4)
     int  nrb, ntm;               // 16-row blocks, channel tiles of MT blocks
     int  act, res_act;
+    // the sparse forms of a yolo head's pointwise layer (SP = 1, 2; below): the head's list of pixel quads, its counter, the list's capacity in quads
+    // (P / 4), the head's class count and objectness threshold
+    int *sp_list, *sp_ctr;
+    int  sp_cap, sp_classes;
+    float sp_thresh;
 };
 
-struct IgX3PackP { const float *filt; unsigned *pk; int ic, oc, k4, nunits, ngr, ntm, MT, fs; };
+// SPARSE HEAD (FS = 1; DESIGN.md 5.11): the layer in front of a yolo head (3 anchors, 5 + classes channels each) as two launches of this kernel, each on
+// a row-permuted image of its own.  Row r of a form's image is the layer's output channel x3_sp_chan(r) (-1: a padding row):
+//   SP = 1, the BOX pass: the 15 rows r = 5 a + v (v = tx, ty, tw, th, objectness) of anchor a, all pixels; a wave then puts the quads that hold a
+//           (pixel, anchor) whose objectness passes k_yolo's own test (yolo_obj_pass) on the head's list;
+//   SP = 2, the CLASS pass: the 3 x classes rows r = a classes + c, the listed quads only, sixteen list slots per wave.
+// An output value depends on its filter row, its pixel and the K order alone -- not on the row block or the pixel slot that computes it -- so both passes
+// write the dense launch's bits.
+template <int SP>
+__host__ __device__ static inline int x3_sp_chan(int classes, int r)
+{
+    if (SP == 1) return r < 15 ? (r / 5) * (5 + classes) + r % 5 : -1;
+    if (SP == 2) return r < 3 * classes ? (r / classes) * (5 + classes) + 5 + r % classes : -1;
+    return r;
+}
+
+struct IgX3PackP { const float *filt; unsigned *pk; int ic, oc, k4, nunits, ngr, ntm, MT, fs, sp, classes; };
 __global__ void k_conv_x3_pack(IgX3PackP p)
 {
     const int nkx = p.fs;                                             // k-steps per group: the tap columns (3), or one (pointwise form)
@@ -51,9 +71,10 @@ __global__ void k_conv_x3_pack(IgX3PackP p)
         const int kx = (int)(t % nkx); t /= nkx;
         const int gr = (int)(t % p.ngr), mt = (int)(t / p.ngr);
         const int u = 4 * gr + (l >> 4), cb8 = u / nkx, ky = u - nkx * cb8;                // this lane quarter's k-unit (zero beyond the last one)
-        const int o = 16 * (mt * p.MT + rb) + (l & 15), c = u < p.nunits ? 8 * cb8 + 2 * d : p.ic;
-        const float w0 = (o < p.oc && c < p.ic) ? p.filt[(long)o * rl + (c * nkx + ky) * nkx + kx] : 0.f;
-        const float w1 = (o < p.oc && c + 1 < p.ic) ? p.filt[(long)o * rl + ((c + 1) * nkx + ky) * nkx + kx] : 0.f;
+        const int r = 16 * (mt * p.MT + rb) + (l & 15), c = u < p.nunits ? 8 * cb8 + 2 * d : p.ic;
+        const int o = p.sp == 1 ? x3_sp_chan<1>(p.classes, r) : (p.sp == 2 ? x3_sp_chan<2>(p.classes, r) : r);      // (the sparse forms' row maps; -1: a padding row)
+        const float w0 = (o >= 0 && o < p.oc && c < p.ic) ? p.filt[(long)o * rl + (c * nkx + ky) * nkx + kx] : 0.f;
+        const float w1 = (o >= 0 && o < p.oc && c + 1 < p.ic) ? p.filt[(long)o * rl + ((c + 1) * nkx + ky) * nkx + kx] : 0.f;
         p.pk[i] = irbw_x3_part(w0, part) | (irbw_x3_part(w1, part) << 16);
     }
 }
@@ -64,9 +85,11 @@ __global__ void k_conv_x3_pack(IgX3PackP p)
 // ST = 2 (FS = 3 only; even planes, iw = 2 ow): the downsampling 3x3 layers of yolov3 / yolov4-tiny.  A quad of four output pixels reads the NINE input columns
 // 2 x - 1 .. 2 x + 7 (left neighbour + two quads, all inside the row), the operand of pixel q at tap column kx is pk[2 q + kx]; 108 + 72 registers of packed / raw
 // values leave room for two 16-row blocks per wave at most.
-template <int MT, int NW, int FS, int ST = 1>
+// SP (FS = 1 only): 0 the dense form, 1 / 2 the box and the class pass of a sparse head (above).
+template <int MT, int NW, int FS, int ST = 1, int SP = 0>
 __global__ void __launch_bounds__(64 * NW, 8 / NW) __attribute__((amdgpu_waves_per_eu(2))) k_conv_x3(IgX3P p)
 {
+    static_assert(SP == 0 || (FS == 1 && ST == 1), "the sparse forms are pointwise");
     constexpr int NKX = FS, NCOL = FS == 1 ? 4 : (ST == 2 ? 9 : 6);   // k-steps per group; input columns per lane
     constexpr int CH = 3 * NKX * MT * 256;                            // dwords per weight chunk (one group)
     typedef v4f_x3 v4a4 __attribute__((aligned(4)));                  // (a row starts at any dword)
@@ -80,20 +103,35 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) __attribute__((amdgpu_waves_p
     const int mtile = (int)(rr_ % p.ntm);
     const long pg = (rr_ / p.ntm) * 8 + xcd;                          // pixel range: all its channel tiles on XCD blockIdx % 8
     if (pg >= p.npg) return;
+    // class pass: the list's length (a count above the capacity comes from a forward that died midway: ALL quads then, by arithmetic index); a workgroup
+    // whose first slot lies behind it has nothing to do.  The grid is the dense launch's (sixteen slots per wave cover P / 4 quads): it does not depend on data.
+    unsigned sp_cnt = 0; bool sp_all = false;
+    if (SP == 2) {
+        const unsigned c = (unsigned)*p.sp_ctr;
+        sp_all = c > (unsigned)p.sp_cap;
+        sp_cnt = sp_all ? (unsigned)p.sp_cap : c;
+        if ((unsigned long)pg * (16 * NW) >= sp_cnt) return;
+    }
     const int rb0 = mtile * MT;
     float *sb = reinterpret_cast<float *>(igx_lds + 2 * CH);
     {
         const int rl = p.k4 + 4;
         for (int i = tid; i < MT * 32; i += 64 * NW) {
-            const int o = 16 * rb0 + (i >> 1);
-            sb[i] = o < p.oc ? p.filt[(long)o * rl + p.k4 + (i & 1)] : 0.f;
+            const int o = x3_sp_chan<SP>(p.sp_classes, 16 * rb0 + (i >> 1));
+            sb[i] = (o >= 0 && o < p.oc) ? p.filt[(long)o * rl + p.k4 + (i & 1)] : 0.f;
         }
     }
 
     // ---- this lane's quad: frame, row, first column in the row-padded pixel space
     const long pxt = pg * NW + wid;
-    const long pq = pxt * 64 + 4 * n;
-    const bool qvalid = pq < p.Pp;
+    long pq = pxt * 64 + 4 * n;
+    bool qvalid = pq < p.Pp;
+    if (SP == 2) {                                                    // list slot 16 pxt + n: the quad's index (clamped: a lane never leaves the tensor)
+        const unsigned slot = (unsigned)pxt * 16u + (unsigned)n;
+        qvalid = slot < sp_cnt;
+        const unsigned quad = !qvalid ? 0u : (sp_all ? slot : min((unsigned)p.sp_list[slot], (unsigned)p.sp_cap - 1u));
+        pq = 4L * quad;
+    }
     const unsigned pqu = (unsigned)(qvalid ? pq : 0);
     unsigned qn = 0; int qy = 0, qa = 0, qskip = 0;
     unsigned base_pix = pqu;                                          // FS = 1: contiguous CNHW, the flat pixel index itself
@@ -290,6 +328,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) __attribute__((amdgpu_waves_p
 
     // ---- epilogue: acc[t][q][r] = Out[16 (rb0 + t) + 4 kq + r][quad pixel q]
     if (!qvalid) return;
+    bool sp_hit = false;
     const float slope = p.act == 2 ? 0.1f : (p.act == 1 ? 0.f : 1.f), rslope = p.res_act == 2 ? 0.1f : (p.res_act == 1 ? 0.f : 1.f);
     const long px = FS == 3 ? ((long)qn * p.oh + qy) * p.ow + qa : pq;    // real pixel index of the quad's first pixel
     const bool vec = FS == 1 || (p.owp == p.ow && (p.P & 3) == 0);    // 16-byte stores: every quad 16-byte aligned (uniform)
@@ -297,8 +336,8 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) __attribute__((amdgpu_waves_p
     for (int t = 0; t < MT; t++)
 #pragma unroll
         for (int r = 0; r < 4; r++) {
-            const int o = 16 * (rb0 + t) + 4 * kq + r;
-            if (o < p.oc) {
+            const int o = x3_sp_chan<SP>(p.sp_classes, 16 * (rb0 + t) + 4 * kq + r);
+            if (o >= 0 && o < p.oc) {
                 const float sc = sb[2 * (16 * t + 4 * kq + r)], bi = sb[2 * (16 * t + 4 * kq + r) + 1];
                 // (four plain v_fma_f32, kept apart: see k_pw_x3)
                 v4f_pw v = pw_fma4_apart(acc[t][0][r], acc[t][1][r], acc[t][2][r], acc[t][3][r], sc, bi);
@@ -320,6 +359,22 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) __attribute__((amdgpu_waves_p
 #pragma unroll
                     for (int q = 0; q < 4; q++) if (q >= qskip) p.out[off + q] = v[q];
                 }
+                // box pass: rows 4, 9, 14 are the anchors' objectness -- k_yolo's test on the values just stored
+                if (SP == 1 && (4 * kq + r) % 5 == 4)
+                    sp_hit = sp_hit || yolo_obj_pass(v[0], p.sp_thresh) || yolo_obj_pass(v[1], p.sp_thresh) || yolo_obj_pass(v[2], p.sp_thresh) || yolo_obj_pass(v[3], p.sp_thresh);
             }
         }
+    if (SP == 1) {
+        // lane (kq, n) holds rows 4 kq .. 4 kq + 3 of quad n: the quad is listed when any of its lanes hit.  One ballot and one integer atomic per wave; the
+        // append is guarded by the capacity (the counter may run past it: the class pass then takes every quad).  A wave with a live lane has lane 0 live.
+        const unsigned long long hit = __ballot(sp_hit);
+        const unsigned m16 = (unsigned)((hit | (hit >> 16) | (hit >> 32) | (hit >> 48)) & 0xffffu);
+        if (m16) {
+            int base = 0;
+            if (lane == 0) base = atomicAdd(p.sp_ctr, __popc(m16));
+            base = __builtin_amdgcn_readfirstlane(base);
+            const int slot = base + __popc(m16 & ((1u << n) - 1u));
+            if (kq == 0 && ((m16 >> n) & 1u) && (unsigned)slot < (unsigned)p.sp_cap) p.sp_list[slot] = (int)(pq >> 2);
+        }
+    }
 }

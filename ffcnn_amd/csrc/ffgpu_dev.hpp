@@ -51,6 +51,11 @@ struct ConvDesc {
     int   kernel;         // FFGPU_K_* frozen at plan time (ffgpu_conv_plan): ffgpu_launch_conv(AUTO), the pack size and the pack kernel all follow it,
                           // so a later change of the FFGPU_* tuning environment cannot pair one kernel with another kernel's weight image; 0 = pick at launch
     int   x3_mt;          // k_conv_x3's MT (16-row blocks per wave) / k_pw_x3t's RB (32-row blocks per wave): the layout of the packed image, frozen with the plan; 0 = decided at launch
+    // the SPARSE form of a yolo head's input layer (ffgpu_conv_x3.inc; sp_classes == 0: none): the head's classes and objectness threshold, its list of
+    // pixel quads (N ih iw / 4 ints) and the list's counter.  The packed image then holds the form's two row-permuted images behind the regular one.
+    int   sp_classes;
+    float sp_thresh;
+    int  *sp_list, *sp_ctr;
 };
 // internal bit of ConvDesc::flags (never part of the public flag set): the step reads the executor's BATCH INPUT (frame-major, possibly through the
 // parameter block) -- kernels that cannot read through ConvDesc::in_ind are not picked for it, so the one-graph-for-every-input property survives
@@ -170,7 +175,10 @@ struct YoloHead {
 };
 // cand / cand_key: `cap` slots per frame (cap = 3 * cells summed over the heads: every anchor of every cell has a slot, so
 // the decode never drops a candidate -- the reference's buffer holds bbox_max = 51 200 of them, ffcnn.c:243,463)
-int ffgpu_launch_yolo(const YoloHead &hd, int N, int netw, int neth, BBOX *cand, int *cand_key, int *ncand, int cap, int *ring_ctr, hipStream_t s);
+int ffgpu_launch_yolo(const YoloHead &hd, int N, int netw, int neth, BBOX *cand, int *cand_key, int *ncand, int cap, int *ring_ctr, int *sp_ctr, hipStream_t s);
+// may the pointwise layer d in front of a yolo head of `classes` classes run in the sparse form (shape and kernel; the knob and the executor's flags are the caller's)
+bool ffgpu_conv_sparse_head_ok(const ConvDesc &d, int classes);
+int  ffgpu_conv_sparse_head_line(const ConvDesc &d, int classes, bool wanted, char *buf, size_t cap);   // that layer's launch as one line of text (ffgpu_sparse_head_launch_text)
 // full (may be NULL): cap boxes per frame, ALL survivors in score order (the fixed-size record keeps the first FFGPU_MAX_DET)
 // bbox_max: the reference stops appending candidates at net->bbox_max in emission order (ffcnn.c:463); same here
 // scratch (cap_pow2 > FFGPU_NMS_LDS_CAP only): 12 bytes x cap_pow2 per frame of global memory instead of LDS

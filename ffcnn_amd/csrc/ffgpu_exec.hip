@@ -171,6 +171,7 @@ struct Step {
     float   *out2[2];        // S_POOL: further stride-1 max pools of the same tensor merged into this launch (fs2[k] != 0)
     int      fs2[2];
     int      lane;           // 0: main stream, 1: side stream (a detection head that runs beside the rest of the net)
+    int     *sp_ctr;         // S_YOLO: the counter of the head's quad list where its input layer runs in the sparse form (sparse_heads), else NULL -- k_yolo zeroes it
 };
 
 struct ffgpu_netdev {
@@ -223,6 +224,7 @@ struct ffgpu_exec {
     float *arena = nullptr;            // layout.arena_floats floats
     float *d_input = nullptr;          // own staging buffer for host / bgr entry points
     float *d_pack = nullptr;           // packed constants of the fused blocks (derived from the weights)
+    int   *d_sparse = nullptr;         // sparse heads (sparse_heads): per head 64 ints with the counter in front (zero between forwards), then the list of P / 4 quads
     BBOX  *d_cand = nullptr;           // cand_cap candidate slots per frame: one per anchor of every head cell
     int   *d_cand_key = nullptr, *d_ncand = nullptr;
     int    cand_cap = 1, bbox_max = 1;
@@ -518,6 +520,48 @@ static void merge_spp(std::vector<Step> &S)
     }
 }
 
+// The pointwise layer in front of a yolo head computes 3 (5 + classes) channels for every cell and k_yolo reads the class scores of the few (cell, anchor)
+// whose objectness can pass.  Where that layer runs on k_conv_x3's pointwise form and the head is its only reader, its launch becomes the SPARSE form
+// (ffgpu_conv_x3.inc): box rows everywhere, class rows on the listed quads.  The layer stays planned as it was (kernel, MT, the regular image); its tensor
+// is no longer whole, so read_layer and hash_layers refuse it like the inside of a fused block.  Same rule as k_irb_stage: FFGPU_CONCURRENT executors only (a single chain
+// measured 0.8 % slower with the form: the second launch costs it more than the class rows did, profiles/sparse_head_ab.txt), never under FFGPU_KEEP_ALL /
+// FFGPU_NO_FUSE; FFGPU_SPARSE_HEAD=0: never.  Every head of every executor (each half of a split one) has its own list and counter.
+static bool sparse_head_wanted(int flags) { return (flags & FFGPU_CONCURRENT) && !(flags & (FFGPU_KEEP_ALL | FFGPU_NO_FUSE)) && knob(K_SPARSE_HEAD) != 0; }
+
+static void sparse_heads(ffgpu_exec *ex)
+{
+    if (!sparse_head_wanted(ex->flags)) return;
+    std::vector<Step> &S = ex->steps;
+    for (Step &y : S) {
+        if (y.kind != S_YOLO) continue;
+        for (Step &c : S) {
+            // the layer straight in front of the head, its own tensor, the head its only reader
+            if (c.kind != S_CONV || c.layer < 0 || c.layer != y.layer - 1 || ex->layout.canon[c.layer] != c.layer || ex->layout.nuses[c.layer] != 1 ||
+                c.in_is_input || c.conv.out != y.head.in) continue;
+            if (!ffgpu_conv_sparse_head_ok(c.conv, y.head.classes)) continue;
+            c.conv.sp_classes = y.head.classes; c.conv.sp_thresh = y.head.thresh;
+            ex->layout.readable[c.layer] = 0;
+        }
+    }
+}
+
+// the lists and counters of the steps sparse_heads marked (zeroed once: k_yolo leaves every counter at zero behind a forward)
+static int place_sparse(ffgpu_exec *ex)
+{
+    size_t tot = 0;
+    for (const Step &st : ex->steps) if (st.kind == S_CONV && st.conv.sp_classes) tot += 64 + (size_t)st.conv.N * st.conv.oh * st.conv.ow / 4;
+    if (!tot) return 0;
+    if (hipMalloc(&ex->d_sparse, tot * sizeof(int)) != hipSuccess || hipMemsetAsync(ex->d_sparse, 0, tot * sizeof(int), ex->own_stream) != hipSuccess) { ffgpu_set_error("hipMalloc(sparse heads) failed"); return -1; }
+    size_t off = 0;
+    for (Step &st : ex->steps) {
+        if (st.kind != S_CONV || !st.conv.sp_classes) continue;
+        st.conv.sp_ctr = ex->d_sparse + off; st.conv.sp_list = ex->d_sparse + off + 64;
+        for (Step &y : ex->steps) if (y.kind == S_YOLO && y.layer - 1 == st.layer) y.sp_ctr = st.conv.sp_ctr;
+        off += 64 + (size_t)st.conv.N * st.conv.oh * st.conv.ow / 4;
+    }
+    return 0;
+}
+
 static void rewrite_steps(ffgpu_exec *ex)
 {
     std::vector<Step> &S = ex->steps;
@@ -531,6 +575,7 @@ static void rewrite_steps(ffgpu_exec *ex)
         S.erase(std::remove_if(S.begin(), S.end(), [](const Step &t) { return t.kind == S_CLEAR; }), S.end());
     }
     { Step nm{}; nm.kind = S_NMS; nm.layer = -1; nm.ltype = LAYER_TYPE_YOLO; S.push_back(nm); }
+    sparse_heads(ex);
     const NetLayout &nl = ex->layout;
     for (Step &st : S) st.lane = (nl.side_lo >= 0 && st.layer >= nl.side_lo && st.layer <= nl.side_hi) ? 1 : 0;
 }
@@ -585,9 +630,10 @@ static int plan(ffgpu_exec *ex)
     std::vector<IrbDesc> irb_planned;
     if (plan_layout(ex, irb_planned) || plan_arena(ex) || plan_steps(ex, irb_planned)) return -1;
     rewrite_steps(ex);
-    if (place_constants(ex)) return -1;
+    if (place_constants(ex) || place_sparse(ex)) return -1;
     decide_indirect(ex);
     ex->kernel_count = (int)ex->steps.size();
+    for (const Step &st : ex->steps) if (st.kind == S_CONV && st.conv.sp_list) ex->kernel_count++;      // (a sparse head's step is two launches)
     return 0;
 }
 
@@ -663,7 +709,7 @@ static int issue_step(ffgpu_exec *ex, const Step &st, const InputSrc &in, hipStr
         return ffgpu_launch_front(d, st.irb, in.form, s); }
     case S_YOLO:
         return ffgpu_launch_yolo(st.head, ex->N, ex->in_w, ex->in_h, ex->d_cand, ex->d_cand_key, ex->d_ncand, ex->cand_cap,
-                                 st.flag ? ex->d_ringctr : nullptr, s);          // forwards are counted whether or not a ring is attached
+                                 st.flag ? ex->d_ringctr : nullptr, st.sp_ctr, s);          // forwards are counted whether or not a ring is attached
     case S_NMS:
         return ffgpu_launch_nms(ex->d_cand, ex->d_cand_key, ex->d_ncand, ex->cand_cap, ex->d_full, ex->d_nms_scratch,
                                 ex->d_dets, ex->h_dets_dev, ex->d_ringctr, ex->N, 0.5f, 1, ex->d_prm, s);
@@ -960,7 +1006,7 @@ extern "C" void ffgpu_exec_destroy(ffgpu_exec *ex)
     }
     drop_graphs(ex);
     for (const Step &st : ex->steps) if (st.kind == S_TOCNHW) (void)hipFree(st.out);
-    (void)hipFree(ex->arena); (void)hipFree(ex->d_input); (void)hipFree(ex->d_pack); (void)hipFree(ex->d_cand);
+    (void)hipFree(ex->arena); (void)hipFree(ex->d_input); (void)hipFree(ex->d_pack); (void)hipFree(ex->d_sparse); (void)hipFree(ex->d_cand);
     (void)hipFree(ex->d_cand_key); (void)hipFree(ex->d_ncand); (void)hipFree(ex->d_dets);
     (void)hipFree(ex->d_full); (void)hipFree(ex->d_prm); (void)hipFree(ex->d_nms_scratch); (void)hipFree(ex->d_ftab);
     (void)hipFree(ex->d_merged); (void)hipFree(ex->d_merged_full); (void)hipFree(ex->d_merge_scratch); (void)hipFree(ex->d_mtab);
@@ -1693,6 +1739,11 @@ extern "C" int ffgpu_exec_read_layer(ffgpu_exec *ex, int layer, int frame, float
         if (copy_d2h(host_out, ex->last.frames + (size_t)frame * fl, fl * sizeof(float))) return -1;
         return (int)fl;
     }
+    // (a layer with a tensor of its own that a launch leaves unwritten or partly written -- the front kernel's inside, a sparse head's input -- says so on every plan)
+    if (layer >= 0 && layer < ex->net->layer_num && ex->layout.canon[layer] == layer && !ex->layout.readable[layer]) {
+        ffgpu_set_error("read_layer: layer %d is not materialised by this executor (fused away or no tensor)", layer);
+        return -1;
+    }
     if (!(ex->flags & FFGPU_KEEP_ALL)) { ffgpu_set_error("read_layer needs an FFGPU_KEEP_ALL executor"); return -1; }
     if (layer < 0 || layer >= ex->net->layer_num || ex->layout.canon[layer] < 0 || !ex->layout.readable[layer]) {
         ffgpu_set_error("read_layer: layer %d is not materialised by this executor (fused away or no tensor)", layer);
@@ -1936,6 +1987,28 @@ extern "C" int ffgpu_groupconv_dev(const float *d_in, const float *d_filt, float
     ConvDesc d;
     fill_desc(d, d_in, d_filt, d_out, batch, iw, ih, ic, groups, pad, stride, fs, ow, oh, oc, act, flags);
     return ffgpu_launch_conv(d, variant, (hipStream_t)stream);
+}
+
+// The sparse form of a yolo head's input layer on caller-owned tensors (tests): the pointwise layer ic -> 3 (5 + classes) on batch x ih x iw pixels as the box
+// pass and the class pass of k_conv_x3, whatever AUTO would pick for the shape.  d_list (batch ih iw / 4 ints) and d_count (one int) are the caller's: the
+// count is NOT reset here -- a caller zeroes it (or leaves it as the case under test wants it) and reads list and count back after the call.
+extern "C" int ffgpu_sparse_head_dev(const float *d_in, const float *d_filt, float *d_out, int batch, int iw, int ih, int ic, int classes, int act,
+                                     float thresh, int *d_list, int *d_count, void *stream)
+{
+    if (!d_in || !d_filt || !d_out || !d_list || !d_count || batch < 1 || iw < 1 || ih < 1 || classes < 1 || classes > 4096) { ffgpu_set_error("sparse_head_dev: bad arguments"); return -1; }
+    ConvDesc d;
+    fill_desc(d, d_in, d_filt, d_out, batch, iw, ih, ic, 1, 0, 1, 1, iw, ih, 3 * (5 + classes), act, 0);
+    d.sp_classes = classes; d.sp_thresh = thresh; d.sp_list = d_list; d.sp_ctr = d_count;
+    return ffgpu_launch_conv(d, FFGPU_K_CONV_X3, (hipStream_t)stream);
+}
+
+// pure host code: what an executor made with `flags` launches for the pointwise layer ic -> 3 (5 + classes) in front of a yolo head
+extern "C" int ffgpu_sparse_head_launch_text(int batch, int iw, int ih, int ic, int classes, int flags, char *buf, int cap)
+{
+    if (!buf || cap < 1 || batch < 1 || iw < 1 || ih < 1 || ic < 1 || classes < 1) { ffgpu_set_error("sparse_head_launch_text: bad arguments"); return -1; }
+    ConvDesc d;
+    fill_desc(d, nullptr, nullptr, nullptr, batch, iw, ih, ic, 1, 0, 1, 1, iw, ih, 3 * (5 + classes), 0, 0);
+    return ffgpu_conv_sparse_head_line(d, classes, sparse_head_wanted(flags | (knob(K_NO_FUSE) ? FFGPU_NO_FUSE : 0)), buf, (size_t)cap);
 }
 
 extern "C" const char *ffgpu_groupconv_kernel_name(int batch, int iw, int ih, int ic, int groups, int pad,

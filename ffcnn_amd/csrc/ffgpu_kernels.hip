@@ -256,10 +256,23 @@ __global__ void k_copy(const float *src, float *dst, long n)
 // evaluated in double and narrowed exactly where the reference does, and FMA
 // contraction is off so the confidence/box arithmetic rounds like the C code.
 // ring_ctr (one head of a forward only, may be NULL): this forward's number for the record ring -- counted here, consumed by k_nms
-__global__ void k_yolo(YoloHead hd, int N, int netw, int neth, BBOX *cand, int *cand_key, int *ncand, int cap, int *ring_ctr)
+// sp_ctr (a head whose input layer ran in the sparse form, else NULL): the counter of that head's quad list, consumed by the class pass in front of this
+// launch -- zeroed here for the next forward, as k_nms zeroes ncand
+//
+// conf = 1 / (1 + e^-bs (1 + e^-cs)) <= 1 / (1 + e^-bs): a (cell, anchor) whose objectness bs alone cannot reach the threshold (almost all of them)
+// has no candidate, and nothing reads its class scores.  0.1 % slack keeps the shortcut rounding-proof.  ONE function for k_yolo's class scan and for the
+// box pass of a sparse head (ffgpu_conv_x3.inc), which computes the class scores only where it holds.
+__device__ __forceinline__ bool yolo_obj_pass(float bs, float thresh)
+{
+#pragma clang fp contract(off)
+    return !(1.0f / (1.0f + __expf(-bs)) < thresh * 0.999f);
+}
+
+__global__ void k_yolo(YoloHead hd, int N, int netw, int neth, BBOX *cand, int *cand_key, int *ncand, int cap, int *ring_ctr, int *sp_ctr)
 {
 #pragma clang fp contract(off)
     if (ring_ctr && blockIdx.x == 0 && threadIdx.x == 0) *ring_ctr += 1;
+    if (sp_ctr && blockIdx.x == 0 && threadIdx.x == 0) *sp_ctr = 0;
     const int cells = hd.w * hd.h;
     const long total = (long)N * 3 * cells;
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -272,9 +285,8 @@ __global__ void k_yolo(YoloHead hd, int N, int netw, int neth, BBOX *cand, int *
     const long cs = (long)N * cells;                                  // CNHW channel stride
     const float *p = hd.in + (long)k * (5 + hd.classes) * cs + (long)n * cells + cell;
     const float bs = p[4 * cs];
-    // conf = 1 / (1 + e^-bs (1 + e^-cs)) <= 1 / (1 + e^-bs): cells whose objectness alone cannot reach the
-    // threshold (almost all of them) skip the 80-class scan.  0.1 % slack keeps the shortcut rounding-proof.
-    const bool pass = gid < total && !(1.0f / (1.0f + __expf(-bs)) < hd.thresh * 0.999f);
+    // cells whose objectness alone cannot reach the threshold skip the 80-class scan (yolo_obj_pass)
+    const bool pass = gid < total && yolo_obj_pass(bs, hd.thresh);
     // class scan of a passing cell: the WAVE reads its scores (lane l -> classes l, l + 64, ...) and reduces to the
     // first maximum (the reference's `if (cs < val)` scan from class 0, ffcnn.c:446-450) -- one lane walking 80 strided
     // loads alone set the run time of the whole kernel
@@ -568,10 +580,10 @@ int ffgpu_launch_copy(const float *src, float *dst, long n, hipStream_t s)
     return 0;
 }
 
-int ffgpu_launch_yolo(const YoloHead &hd, int N, int netw, int neth, BBOX *cand, int *cand_key, int *ncand, int cap, int *ring_ctr, hipStream_t s)
+int ffgpu_launch_yolo(const YoloHead &hd, int N, int netw, int neth, BBOX *cand, int *cand_key, int *ncand, int cap, int *ring_ctr, int *sp_ctr, hipStream_t s)
 {
     const long total = (long)N * 3 * hd.w * hd.h;
-    hipLaunchKernelGGL(k_yolo, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, hd, N, netw, neth, cand, cand_key, ncand, cap, ring_ctr);
+    hipLaunchKernelGGL(k_yolo, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, hd, N, netw, neth, cand, cand_key, ncand, cap, ring_ctr, sp_ctr);
     LAUNCH_OK("yolo");
     return 0;
 }

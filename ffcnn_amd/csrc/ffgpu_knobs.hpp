@@ -96,6 +96,7 @@ enum KnobClass { KNOB_PRODUCT, KNOB_TUNING, KNOB_TEST, KNOB_LAB };
     X(THIN_PAIR,         "FFGPU_THIN_PAIR",         INT,  1,             TUNING,  "k_irb_thin: 0 keeps FFGPU_CONCURRENT executors off the paired form (two frames per wave, 3 / 4 / 5 columns per lane); read at launch") \
     X(THIN_S2,           "FFGPU_THIN_S2",           INT,  1,             TUNING,  "k_irb_thin_s2: 0 keeps FFGPU_CONCURRENT executors off the streaming form of the stride-2 block 4 -> 24 -> 8 (the planned wave kernel instead); read at launch") \
     X(THIN_S2_BAND,      "FFGPU_THIN_S2_BAND",      INT,  0,             TUNING,  "k_irb_thin_s2: output rows per wave (0: by batch and height, thin_s2_form); read at launch") \
+    X(SPARSE_HEAD,       "FFGPU_SPARSE_HEAD",       INT,  1,             TUNING,  "k_conv_x3: 0 keeps FFGPU_CONCURRENT executors off the sparse form of the pointwise layer in front of a yolo head (a box pass over all pixels, then the class rows of the quads whose objectness can pass; the dense launch instead); read when an executor is created") \
     X(FRONT_BAND,        "FFGPU_FRONT_BAND",       INT,  KNOB_COMPUTED, TUNING,  "k_front: rows per wave; default as FFGPU_THIN_BAND") \
     X(NO_FRONT,          "FFGPU_NO_FRONT",          INT,  0,             PRODUCT, "layers 0-3 as k_conv_first + k_irb_thin instead of k_front") \
     X(FRONT_MIN_PX,      "FFGPU_FRONT_MIN_PX",      INT,  262144,        TUNING,  "k_front: fewest output pixels of the batch") \

@@ -352,6 +352,21 @@ int ffgpu_irb_thin_launch_text(int batch, int iw, int ih, int ic, int ec, int oc
 int ffgpu_irb_s2_launch_text(int batch, int iw, int ih, int ic, int ec, int oc, int stride, int act1, int actd, int act2, int res_act,
                              int flags, char *buf, int cap);
 
+/* The SPARSE form of the pointwise layer in front of a yolo head (3 anchors: ic -> 3 (5 + classes) channels, CNHW, batch ih iw a multiple of 4) on
+ * caller-owned device tensors, as an FFGPU_CONCURRENT executor without FFGPU_KEEP_ALL / FFGPU_NO_FUSE runs it unless FFGPU_SPARSE_HEAD=0: a box pass writes the 15 box and
+ * objectness channels of every pixel and appends to d_list (batch ih iw / 4 ints) the index of every quad of four consecutive pixels that holds a
+ * (pixel, anchor) whose objectness can reach `thresh` (k_yolo's own test), counting them in *d_count; a class pass then writes the 3 x classes class
+ * channels of the listed quads and of no other pixel.  Every value written has the bits of the dense launch (ffgpu_groupconv_dev, variant
+ * FFGPU_K_CONV_X3).  *d_count is the caller's to zero before the call; a count above batch ih iw / 4 on entry makes the class pass take every quad.
+ * List order is unspecified.  Returns 0, or -1 with ffgpu_last_error(). */
+int ffgpu_sparse_head_dev(const float *d_in, const float *d_filt, float *d_out, int batch, int iw, int ih, int ic, int classes, int act,
+                          float thresh, int *d_list, int *d_count, void *stream);
+
+/* What an executor made with `flags` launches for that layer, as one line of text in buf (at most cap bytes; returns snprintf's count):
+ * "sparse box<1,NW> rows=15 grid= class<MT,NW> rows= grid= quads= image=" -- the two passes' instantiations and workgroups, the list's capacity, the
+ * dwords of the packed image (the regular one and the two row-permuted ones behind it) -- or "dense <kernel>".  Pure host code. */
+int ffgpu_sparse_head_launch_text(int batch, int iw, int ih, int ic, int classes, int flags, char *buf, int cap);
+
 /* What the planner decides for that block, as one line of text in buf (at most cap bytes; returns snprintf's count): the kernel
  * family and instantiation, every scalar of the parameter block the launch would pass, LDS bytes, grid, block, `half`, the floats
  * of the packed image -- or "unsupported".  flags: FFGPU_CONCURRENT or 0.  Pure host code (no device needed): for tests and logs. */
