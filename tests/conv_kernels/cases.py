@@ -24,6 +24,14 @@ Where plant() puts the values (each on a position of its own; a frame or channel
   frame-seam     the last pixel of the last frame of channel ic / 2 - 1 and the first pixel of frame 0 of the next channel's plane run: ragged pixel tiles, clamped quads
   strip-seam     flat pixels 63 and 64 of a channel's run of N H W pixels (both sides of pw_mfma's 64-pixel strip boundary), and 127 / 128 (the tiles of pw_gemm)
   stride         under stride 2 (or 3) an odd row and an odd column: only some outputs read them
+and for the split-bf16 kernels (X3: they choose the Inf form of the split per wave, over a group's raw values) on top:
+  range-seam     flat pixels 255 / 256 and 511 / 512 of a channel's run: the pixel ranges of four and eight waves of 64 pixels
+  unit-edge      +Inf in channel ic - 8: with last-channel the first and last channel of the k-unit that the padded k-units of the last group re-read
+  last-quad      (3x3) a value in each of the last four columns of one row: the quad that slides left to end with a row whose width is no multiple of 4
+  row-wrap       (3x3) column W - 1 of one row and column 0 of the next: neighbours in memory that are not neighbours in the plane
+  last-column, last-row   (3x3, stride 2) the last input column and the last input row: a border tap (kx = 2, ky = 2) alone reads them
+  filter rows 3, 4, 5: a row of bf16 numbers (two empty parts), a row with an empty third part, a zero weight on the last channel's +Inf
+The split kernels' cases run a second time without the planted values (`x0` of nf_reference): every untouched output must keep its bits.
 The touched set -- outputs whose window holds a planted value of their own group -- follows from the geometry alone (touched()); under a linear activation it must
 equal the set of non-finite outputs of conv64, and {NaN, +Inf, -Inf} must all occur there."""
 import collections
@@ -123,6 +131,41 @@ TABLE += [("conv_thin", "conv_thin", "K_GROUP_THIN", 0, {}, _cv(gic * g, goc * g
     (7, 3, 1, 2, 5, 7, 1, 3, 0, "1x1 filter, stride 3"), (2, 1, 7, 1, 40, 70, 3, 1, 2, "padding 2 on a 3x3"), (5, 2, 2, 1, 5, 7, 7, 3, 5, "7x7, stride 3, padding 5"),
     (7, 3, 3, 1, 40, 70, 3, 1, 1, "three groups of seven on the large plane"))]
 
+# the split-bf16 ("X3") kernels: k_pw_x3 (k-steps of 32 channels), k_pw_x3t (chunks of 16 in pairs, 128-pixel and 256-channel tiles), k_conv_x3 as the dense 3x3
+# kernel conv_x3 (stride 1 and 2: k-units of 8 channels x one tap row, groups of four units, quads of pixels that never leave their row) and as the pointwise
+# form pw_x3s (groups of four 8-channel units, quads of the flat pixel space).  Held to convref.bound_x3.
+X3 = ("pw_x3", "pw_x3s", "pw_x3t", "conv_x3")
+X3_VARIANT = {"pw_x3": "K_PW_X3", "pw_x3s": "K_CONV_X3", "pw_x3t": "K_PW_X3T", "conv_x3": "K_CONV_X3"}
+
+
+def _x3sw(mt, nw):
+    return {"FFGPU_IGX3_MT": str(mt), "FFGPU_IGX3_NW": str(nw)} if mt else {}
+
+
+for mt in (0, 1, 2, 4):
+    sw = {"FFGPU_PWX3_MT": str(mt)} if mt else {}
+    TABLE += [("pw_x3", "pw_x3", "K_PW_X3", 0, sw, shape, why) for shape, why in (
+        (_pw(8, 16, 2, 2, 2), "a quarter k-step, under one pixel tile"), (_pw(33, 21, 1, 6, 6), "one channel into the second k-step, ragged row block"),
+        (_pw(72, 130, 3, 10, 10), "several 64-channel workgroups, 300 pixels"), (_pw(100, 200, 1, 12, 12), "3.125 k-steps"))]
+for mt, nw in ((0, 0), (1, 4), (2, 4), (4, 8)):
+    TABLE += [("pw_x3s", "pw_x3s", "K_CONV_X3", 0, _x3sw(mt, nw), shape, why) for shape, why in (
+        (_pw(8, 16, 1, 2, 2), "one k-unit, three padded"), (_pw(40, 33, 5, 4, 13), "a ragged last group; 52-pixel frames: quads and tiles straddle frames"),
+        (_pw(120, 255, 2, 10, 10), "the heads' 120 -> 255"), (_pw(16, 70, 7, 9, 4), "two units, 252 pixels: a ragged last tile"))]
+for sw in ({}, {"FFGPU_PWXT_NARROW": "0"}, {"FFGPU_PWXT_NT": "1"}, {"FFGPU_PWXT_TM": "128"}):
+    TABLE += [("pw_x3t", "pw_x3t", "K_PW_X3T", 0, sw, shape, why) for shape, why in (
+        (_pw(8, 16, 2, 4, 4), "half a chunk, under one tile"), (_pw(33, 21, 1, 6, 6), "one channel into the third chunk"),
+        (_pw(72, 300, 3, 10, 10), "two channel tiles, the second ragged, a ragged last pixel tile"), (_pw(16, 130, 5, 12, 7), "420 pixels: 3.3 tiles"))]
+for mt, nw in ((0, 0), (1, 4), (2, 8), (4, 4)):
+    TABLE += [("conv_x3", "conv_x3", "K_CONV_X3", 0, _x3sw(mt, nw), shape, why) for shape, why in (
+        (_cv(8, 20, 1, 1, 4, 3, 1, 1), "one row, one quad that touches both borders"), (_cv(16, 16, 2, 5, 5, 3, 1, 1), "width 5: the last quad overlaps three pixels (qskip = 3)"),
+        (_cv(40, 48, 2, 7, 31, 3, 1, 1), "width 31: the last quad overlaps one pixel (qskip = 1); 15 k-units = 3.75 groups"),
+        (_cv(8, 16, 1, 3, 6, 3, 1, 1), "width 6: overlap of two"), (_cv(24, 100, 1, 5, 13, 3, 1, 1), "width 13, several channel tiles"),
+        (_cv(8, 130, 4, 4, 4, 3, 1, 1), "one quad per row, 130 channels"))]
+for mt, nw in ((0, 0), (1, 4), (2, 8), (4, 4)):             # (stride 2 caps MT at 2)
+    TABLE += [("conv_x3", "conv_x3", "K_CONV_X3", 0, _x3sw(mt, nw), shape, why) for shape, why in (
+        (_cv(8, 16, 1, 8, 8, 3, 2, 1), "stride 2, one quad per row"), (_cv(24, 40, 2, 8, 10, 3, 2, 1), "stride 2, output width 5"),
+        (_cv(32, 130, 3, 10, 12, 3, 2, 1), "stride 2, output width 6 (32 channels, not 64: at K = 576 the ORACLE misses 8e-7 max |y| on one seed in four)"), (_cv(40, 24, 5, 12, 26, 3, 2, 1), "stride 2, output width 13"))]
+
 PAIR_TABLE = [((1, 4, 4, 8, 8), 3, 0, 0), ((1, 6, 6, 12, 20), 3, 2, 0), ((2, 7, 13, 16, 24), 3, 2, 2), ((1, 5, 17, 30, 128), 5, 2, 0)]
 PAIRS = [Pair("dwpw-C%d-OC%d-N%d-%dx%d-fs%d-act%d%d" % (s[3], s[4], s[0], s[2], s[1], fs, ad, ap), s, fs, ad, ap) for s, fs, ad, ap in PAIR_TABLE]
 NF_PAIRS = [PAIRS[1]._replace(id=PAIRS[1].id + "-nf"), PAIRS[3]._replace(id=PAIRS[3].id + "-nf"), PAIRS[2]._replace(id=PAIRS[2].id + "-relu-nf", actd=1, actp=1)]
@@ -192,6 +235,17 @@ NF_TABLE = [
     ("conv_thin", "conv_thin", "K_GROUP_THIN", 0, {}, _cv(4, 10, 1, 9, 13, 3, 1, 3, 2)),
     ("conv_thin", "conv_thin", "K_GROUP_THIN", 0, {}, _cv(7, 4, 1, 19, 17, 7, 1, 3)),
     ("conv_thin", "conv_thin", "K_GROUP_THIN", 0, {}, _cv(6, 6, 2, 5, 7, 1, 1, 0, 3)),
+    # the split kernels: 600 pixels (the range seams of four and eight waves), ic = 40 ragged for every k-step size (16, 32; 5 units = 1.25 groups); the 3x3 forms on
+    # widths 13 (the overlapping last quad) and 12, ic = 40 (15 units = 3.75 groups), 16 (1.5) and 24 (2.25)
+    ("pw_x3", "pw_x3", "K_PW_X3", 0, {}, _pw(40, 24, 3, 10, 20)),
+    ("pw_x3", "pw_x3", "K_PW_X3", 0, {"FFGPU_PWX3_MT": "1"}, _pw(40, 33, 3, 10, 20)),
+    ("pw_x3s", "pw_x3s", "K_CONV_X3", 0, {}, _pw(40, 24, 3, 10, 20)),
+    ("pw_x3s", "pw_x3s", "K_CONV_X3", 0, _x3sw(1, 8), _pw(40, 33, 3, 10, 20)),
+    ("pw_x3t", "pw_x3t", "K_PW_X3T", 0, {}, _pw(40, 33, 3, 10, 20)),
+    ("pw_x3t", "pw_x3t", "K_PW_X3T", 0, {"FFGPU_PWXT_TM": "128"}, _pw(40, 24, 3, 10, 20)),
+    ("conv_x3", "conv_x3", "K_CONV_X3", 0, {}, _cv(40, 24, 2, 9, 13, 3, 1, 1)),
+    ("conv_x3", "conv_x3", "K_CONV_X3", 0, _x3sw(1, 8), _cv(16, 33, 2, 12, 12, 3, 1, 1)),
+    ("conv_x3", "conv_x3", "K_CONV_X3", 0, {}, _cv(24, 24, 2, 10, 26, 3, 2, 1)),
 ]
 
 
@@ -208,7 +262,11 @@ NF_CASES = _nf_cases()
 NF_IDS = [c.id for c in NF_CASES]
 
 SWITCHES = ("FFGPU_DW_U", "FFGPU_DW_NT", "FFGPU_NO_DW_PAIR", "FFGPU_PWG_WM", "FFGPU_CONV_FIRST_MIN_PX", "FFGPU_NO_CONV_FIRST", "FFGPU_IGEMM_SPLIT",
-            "FFGPU_PW_X3T", "FFGPU_PW_X3S", "FFGPU_BF16_PW", "FFGPU_COMPAT_V6", "FFGPU_DWL_BH", "FFGPU_DWL_NPL", "FFGPU_DWP_NI")
+            "FFGPU_PW_X3T", "FFGPU_PW_X3S", "FFGPU_BF16_PW", "FFGPU_COMPAT_V6", "FFGPU_DWL_BH", "FFGPU_DWL_NPL", "FFGPU_DWP_NI",
+            # the split kernels: tile forms (parts A and B) and what steers AUTO to them on small tensors (part C)
+            "FFGPU_PWX3_MT", "FFGPU_IGX3_MT", "FFGPU_IGX3_NW", "FFGPU_PWXT_NARROW", "FFGPU_PWXT_NT", "FFGPU_PWXT_TM", "FFGPU_PWXT_PERSIST", "FFGPU_PW_X3", "FFGPU_IG_X3",
+            "FFGPU_IGX3_S2", "FFGPU_IGX3_MT4_WGS", "FFGPU_PWX3_MIN_IC", "FFGPU_PWX3_MIN_OC", "FFGPU_PWX3_MIN_P", "FFGPU_PWX3T_MIN_IC", "FFGPU_PWX3T_MIN_OC", "FFGPU_PWX3T_MIN_P",
+            "FFGPU_PWX3S_MIN_IC", "FFGPU_PWX3S_MIN_OC", "FFGPU_PWX3S_MIN_WGS", "FFGPU_IGX3_MIN_IC", "FFGPU_IGX3_MIN_WGS")
 
 
 def set_switches(monkeypatch, case):
@@ -241,8 +299,9 @@ def make_inputs(seed, c):
 INF, NAN = np.float32(np.inf), np.float32(np.nan)
 
 
-def placements(N, W, H, ic, groups, stride):
-    """[(channel, frame, row, column, value, what)], each position once"""
+def placements(N, W, H, ic, groups, stride, x3=0, dropped=None):
+    """[(channel, frame, row, column, value, what)], each position once.  x3 = the filter size of a split-bf16 kernel's case (0: any other kernel): the
+    placements of those kernels on top.  dropped (a list): the placements that fell on a position already taken, for the CPU test that none of the new ones does"""
     gic = ic // groups
     out, used = [], set()
 
@@ -251,6 +310,8 @@ def placements(N, W, H, ic, groups, stride):
         if pos not in used:
             used.add(pos)
             out.append(pos + (v, what))
+        elif dropped is not None:
+            dropped.append(pos + (v, what))
 
     def flat(ch, p, v, what):                                      # pixel p of channel ch's run of N H W pixels
         if p < N * H * W:
@@ -279,6 +340,20 @@ def placements(N, W, H, ic, groups, stride):
     if stride > 1:
         put(ic - 1, N - 1, 1, W // 2 + (W // 2 + 1) % 2, INF, "stride")
         put(0, N - 1, H // 2 + (H // 2 + 1) % 2, 1, -INF, "stride")
+    if x3:
+        # the split kernels choose the Inf form of the split per WAVE (x3_wave_has_inf over a group's raw values, clamped re-reads and neighbours included):
+        # values where that choice, a row mask or a clamp can go wrong
+        for p, v in ((255, INF), (256, -INF), (511, NAN), (512, INF)):
+            flat(ic // 4, p, v, "range-seam")                     # the pixel ranges of four and eight waves of 64 pixels
+        put(ic - 8, 1, H // 2, W // 2, INF, "unit-edge")          # the first channel of the k-unit that the padded units of the last group re-read (last-channel: its last)
+        if x3 == 3:
+            for k, v in enumerate((INF, -INF, NAN, INF)):
+                put(ic // 4 + 1, 0, H // 2, W - 4 + k, v, "last-quad")        # the quad that slides left to end with the row (qa = min(qx, ow - 4), qskip)
+            put(2, N - 1, 1, W - 1, INF, "row-wrap")              # column iw - 1 and column 0 of the next row: neighbours in memory, not in the plane
+            put(2, N - 1, 2, 0, -INF, "row-wrap")
+            if stride == 2:
+                put(3, 0, (H // 2) & ~1, W - 1, INF, "last-column")           # the last input column and row: read by a border tap (kx = 2, ky = 2) alone
+                put(4, N - 1, H - 1, W // 2, -INF, "last-row")
     return out
 
 
@@ -286,9 +361,15 @@ def plant(c, x, f):
     """in place; returns the placements"""
     N, W, H, ic, groups, pad, stride, fs, oc, OH, OW, K = dims(c)
     xf = x.reshape(ic, N, H, W)
-    P = placements(N, W, H, ic, groups, stride)
+    P = placements(N, W, H, ic, groups, stride, fs if c.kernel in X3 else 0)
     for ch, n, y, xx, v, _ in P:
         xf[ch, n, y, xx] = v
+    if c.kernel in X3:
+        # the filter rows of tests/test_gpu_round5.py::test_x3_non_finite_lanes, on every channel (the Inf channels among them): the weight side of the Inf path
+        K_ = fs * fs * ic
+        f[3, :K_] = np.round(f[3, :K_] * 64) / 64                                       # bf16 numbers: parts 1 and 2 are empty (packed as sign(w) 2^(e-40))
+        f[4, :K_] = (f[4, :K_].view(np.uint32) & np.uint32(0xffffff00)).view(np.float32)  # an empty third part
+        f[5, (ic - 1) * fs * fs:ic * fs * fs] = 0.0                                     # a ZERO weight on the last channel's +Inf: NaN, as in the reference
     gic, goc, t = ic // groups, oc // groups, fs * fs
     if gic >= 2:
         f[0, 0:2 * t] = np.abs(f[0, 0:2 * t]) + np.float32(0.01)                    # +Inf w - Inf w': NaN
@@ -327,7 +408,7 @@ def _refs(orc, c, x, f, compat):
     N, W, H, ic, groups, pad, stride, fs, oc, OH, OW, K = dims(c)
     y64, sabs = convref.conv64(x, f, N, W, H, ic, groups, pad, stride, fs, c.act, compat_v6=compat)
     y32 = convref.oracle32(orc, x, f, N, W, H, ic, groups, pad, stride, fs, c.act, compat_v6=compat)
-    return y64, sabs, y32, convref.bound(f, K, sabs, c.act)
+    return y64, sabs, y32, (convref.bound_x3 if c.kernel in X3 else convref.bound)(f, K, sabs, c.act)
 
 
 @functools.lru_cache(maxsize=None)
@@ -350,6 +431,7 @@ def nf_reference(i):
     orc.build()
     c = NF_CASES[i]
     x, f = make_inputs(c.seed, c)
+    x0 = x.copy()                                                      # the case without the planted values (the filter rows stay as plant() leaves them)
     P = plant(c, x, f)
     y64, sabs, y32, b = _refs(orc, c, x, f, 0)
     N, W, H, ic, groups, pad, stride, fs, oc, OH, OW, K = dims(c)
@@ -357,8 +439,19 @@ def nf_reference(i):
     t = touched(c, P)
     ok = ~t
     d = np.abs(np.where(ok, y32, 0) - np.where(ok, y64, 0))
-    return _freeze(dict(x=x, f=f, P=P, y64=y64, y32=y32, bound=b, sabs=sabs, lin64=lin64, touched=t, ok=ok, E_ref=float(d.max()) if ok.any() else 0.0,
+    return _freeze(dict(x=x, x0=x0, f=f, P=P, y64=y64, y32=y32, bound=b, sabs=sabs, lin64=lin64, touched=t, ok=ok, E_ref=float(d.max()) if ok.any() else 0.0,
                         ymax=float(np.abs(y64[ok]).max()) if ok.any() else 0.0))
+
+
+@functools.lru_cache(maxsize=None)
+def x3_models(i):
+    """CASES[i] of a split kernel through convref.model_x3: (the model, the model with each of the three 2^-16-sized terms left out), read only"""
+    c, r = CASES[i], reference(i)
+    N, W, H, ic, groups, pad, stride, fs, oc, OH, OW, K = dims(c)
+    out = tuple(convref.model_x3(c.kernel, r["x"], r["f"], N, W, H, ic, pad, stride, fs, c.act, drop) for drop in (None,) + convref.X3_SMALL)
+    for a in out:
+        a.setflags(write=False)
+    return out
 
 
 def classes(v):
@@ -416,7 +509,7 @@ FACTOR = {}
 # ---- part C: the fused residual epilogue act2(act(conv) + residual), reached through an executor
 # (id, the kernel AUTO must pick for the conv under the switches, switches, batch, w, h, ic, oc, filter size, groups, the shortcut's activation)
 #   cfg: L0 = 1x1 conv 3 -> oc (the residual), L1 = leaky 1x1 conv oc -> ic, L2 = the LINEAR conv under test ic -> oc, L3 = shortcut(from L0): a fused plan
-#   absorbs L3 into L2's launch.  pw_gemm and the split kernel need 16384 pixels before AUTO picks them: one 128 x 128 frame.
+#   absorbs L3 into L2's launch.  pw_gemm and pw_x3s need 16384 pixels before AUTO picks them: one 128 x 128 frame.
 RES_TABLE = [
     ("pw_mfma", "pw_mfma", {}, 2, 10, 6, 13, 10, 1, 1, "leaky"),
     ("pw_gemm", "pw_gemm", {"FFGPU_PW_X3T": "0", "FFGPU_PW_X3S": "0"}, 1, 128, 128, 136, 128, 1, 1, "linear"),
@@ -424,9 +517,20 @@ RES_TABLE = [
     ("conv_igemm", "conv_igemm", {}, 2, 11, 7, 9, 12, 3, 1, "relu"),
     ("conv_dense8", "conv_dense8", {}, 2, 9, 7, 5, 11, 3, 1, "leaky"),
     ("conv_thin", "conv_thin", {}, 2, 9, 7, 10, 6, 3, 2, "linear"),
+    # every residual epilogue of the split kernels (pw_x3s: above).  AUTO is steered to the kernel on a small tensor by the kernel's own thresholds, set before the
+    # executor exists (the choice is frozen with the plan); the thresholds sit at the conv's own channel counts, so the cfg's other layers stay where they were
+    ("pw_x3", "pw_x3", {"FFGPU_PWX3_MIN_IC": "40", "FFGPU_PWX3_MIN_OC": "24", "FFGPU_PWX3_MIN_P": "1"}, 2, 10, 6, 40, 24, 1, 1, "leaky"),
+    ("pw_x3t-full", "pw_x3t", {"FFGPU_PWX3T_MIN_IC": "24", "FFGPU_PWX3T_MIN_OC": "130", "FFGPU_PWX3T_MIN_P": "1"}, 2, 10, 10, 24, 256, 1, 1, "relu"),     # whole 256-channel tile
+    ("pw_x3t-ragged", "pw_x3t", {"FFGPU_PWX3T_MIN_IC": "24", "FFGPU_PWX3T_MIN_OC": "130", "FFGPU_PWX3T_MIN_P": "1"}, 2, 10, 10, 24, 130, 1, 1, "linear"),
+    ("conv_x3-vec", "conv_x3", {"FFGPU_IGX3_MIN_WGS": "1"}, 2, 8, 8, 16, 24, 3, 1, "relu"),               # 16-byte residual loads
+    ("conv_x3-qskip", "conv_x3", {"FFGPU_IGX3_MIN_WGS": "1"}, 2, 13, 7, 16, 24, 3, 1, "linear"),          # width 13: the scalar loads of the overlapping quad
+    ("conv_x3-s2", "conv_x3", {"FFGPU_IGX3_MIN_WGS": "1"}, 2, 12, 10, 16, 24, 3, 1, "leaky"),             # stride 2 (RES_STRIDE): 10 x 12 -> 5 x 6
 ]
 RES_IDS = [r[0] for r in RES_TABLE]
+RES_STRIDE = {"conv_x3-s2": 2}                                             # the conv under test and the 1x1 conv that makes its residual both halve the plane
 RES_NF = ("pw_mfma-nf", "pw_mfma", {}, 1, 10, 6, 6, 12, 1, 1, "relu")      # the conv reads the net input (planted there), the residual is a 1x1 conv of it
+# k_conv_x3 does not read the net input (ig_x3_ok: no FFGPU_F_BATCH_INPUT): the conv reads a 1 x 1 average pool of it -- a copy -- and so does the residual's conv
+RES_NF_X3 = ("conv_x3-nf", "conv_x3", {"FFGPU_IGX3_MIN_WGS": "1"}, 1, 13, 7, 16, 24, 3, 1, "relu")
 
 
 def res_cfg(row):
@@ -434,6 +538,12 @@ def res_cfg(row):
     from layer_ops import cfgs
     name, _, _, batch, w, h, ic, oc, size, groups, act = row
     g = cfgs.Cfg("res_" + name.replace("-", "_"), w, h, 3, batch)
+    if name in RES_STRIDE:                         # L0 = leaky 1x1 conv 3 -> ic, L1 = 1x1 stride-2 conv ic -> oc (the residual), L2 = route(L0), L3 = the conv under test, L4 = shortcut(from L1)
+        b = g.conv(ic, act="leaky")
+        a = g.conv(oc, stride=RES_STRIDE[name])
+        c = g.conv(oc, size=size, groups=groups, stride=RES_STRIDE[name], src=b)
+        s = g.absorbed_shortcut(a, act)
+        return g.tail(), a, b, c, s
     a = g.conv(oc)
     b = g.conv(ic, act="leaky")
     c = g.conv(oc, size=size, groups=groups)
@@ -448,7 +558,8 @@ def res_nf_cfg(row=RES_NF):
     name, _, _, batch, w, h, ic, oc, size, groups, act = row
     g = cfgs.Cfg("res_" + name.replace("-", "_"), w, h, ic, batch)
     g.dropout()
+    src = g.pool("avg", 1, 1) if row is RES_NF_X3 else -1
     a = g.conv(oc)
-    c = g.conv(oc, size=size, groups=groups, src=-1)
+    c = g.conv(oc, size=size, groups=groups, src=src)
     s = g.absorbed_shortcut(a, act)
-    return g.tail(), a, -1, c, s
+    return g.tail(), a, src, c, s

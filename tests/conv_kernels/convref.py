@@ -5,7 +5,8 @@
             activation of the reference (utils.h:15-23: x > 0 ? x : 0, x > 0 ? x : 0.1f x, sigmoid, linear), then the optional residual add with its own
             activation (ffcnn.c:418-423).  It also returns sabs = sum |w x| over the same taps, per output.
   oracle32  the fp32 reference: orc.groupconv (and orc.shortcut) frame by frame.
-  bound     the hard bound below.
+  bound     the hard bound below; bound_x3: the same for the split-bf16 kernels (its derivation stands in front of it).
+  model_x3  a numpy model of the split kernels' arithmetic: what tests/test_conv_kernels_ref.py shows the criterion to tell from a kernel that forgets a term.
 
 Tensors are CNHW as the kernels take them, (channels * N, H, W); filters are conv.h rows (blockref.make_filter).
 
@@ -90,6 +91,108 @@ def bound(f, K, sabs, act, pre=None, res=None, res_act=0):
         if res_act == 3:
             b = b / 4 + 4 * U
     return b
+
+
+# ---- the split-bf16 ("X3") kernels: k_pw_x3, k_pw_x3t, k_conv_x3 (conv_x3 and its pointwise form pw_x3s)
+# THE SPLIT BOUND.  Every operand is cut by truncation into three bf16 parts, v = v0 + v1 + v2 exactly, all with the sign of v.  For 2^e <= |v| < 2^(e+1) a bf16
+# keeps 8 significand bits, so |v1| <= |v - v0| < 2^(e-7) <= 2^-7 |v| and |v2| < 2^-15 |v|.  The kernels keep the six partial products w_i x_j with i + j <= 2 and
+# drop D = w1 x2 + w2 x1 + w2 x2:
+#     |D| < (2^-7 2^-15 + 2^-15 2^-7 + 2^-15 2^-15) |w x| = (2^-21 + 2^-30) |w x|        (X3_DROPPED; reached to within 3 %: w = x = 1 + 2^-7 - 2^-23 drops 2^-21.03 |w x|)
+# A zero part of a non-zero weight is packed as sign(w) 2^(e-40) (so that an Inf input meets no 0 x Inf): at most two parts, 2^-39 |w x| together, on both the
+# value of the sum of the kept terms and its sum of magnitudes.  Every bf16 x bf16 product is exact in fp32 (8 x 8 significand bits), the kept terms of one product
+# have one sign and add up to at most (1 + 2^-39) |w x|, and the matrix cores add the 6 K exact terms in fp32 in SOME order (padded k-slots add exact zeros):
+#     |sum_kernel - sum_kept| <= gamma(6 K) (1 + 2^-39) sum |w x|
+# With the affine step, the leaky product and the spare of the fp32 bound, and 2^-38 for the perturbation and every cross term (gamma x 2^-39, gamma(3) x 2^-21):
+#     |got - ref64| <= (gamma(6 K + 3) + 2^-21 + 2^-30 + 2^-38) (|scale'| sabs + |bias'|)
+# and from there on (sigmoid, residual) as the fp32 bound.  That is (6 K + 11) / (K + 3) times the fp32 bound -- 5.4 times at K = 8, six times for a long K: the
+# dropped terms are worth eight roundings (2^-21 = 8 u) whatever K is.  Derived, not measured; the oracle and the numpy model below are held to it on the CPU.
+# It grows like K sum |w x| and a forgotten 2^-16-sized term hides under it from K of about 16 up: what tells a subtly wrong kernel from a right one is the
+# criterion against E_ref (tests/test_conv_kernels_ref.py holds the model with one such term left out to FAIL it on every case).
+X3_DROPPED = 2.0 ** -21 + 2.0 ** -30
+X3_SLACK = 2.0 ** -38
+
+
+def bound_x3(f, K, sabs, act, pre=None, res=None, res_act=0):
+    """the hard bound of a split-bf16 kernel, per output (bound() with the split form's constant)"""
+    k4 = (K + 3) & ~3
+    sc, bi = np.abs(f[:, k4].astype(np.float64))[:, None, None, None], np.abs(f[:, k4 + 1].astype(np.float64))[:, None, None, None]
+    b = (gamma(6 * K + 3) + X3_DROPPED + X3_SLACK) * (sc * sabs + bi)
+    if act == 3:
+        b = b / 4 + 4 * U
+    if res is not None:
+        b = b + gamma(2) * (np.abs(pre) + np.abs(res.reshape(pre.shape).astype(np.float64)))
+        if res_act == 3:
+            b = b / 4 + 4 * U
+    return b
+
+
+def _trunc16(v):
+    return (np.ascontiguousarray(v, np.float32).view(np.uint32) & np.uint32(0xffff0000)).view(np.float32)
+
+
+def split3(v, weights=False):
+    """the truncation split of the kernels (tools/sim_split_bf16.py has the same one): three float32 arrays, each a bf16 number, v0 + v1 + v2 == v exactly.
+    weights: a zero part of a non-zero weight of exponent e >= 41 (biased) becomes sign(w) 2^(e-40), as irbw_x3_part packs it"""
+    v = np.ascontiguousarray(v, np.float32)
+    p0 = _trunc16(v)
+    with np.errstate(invalid="ignore"):
+        r = (v - p0).astype(np.float32)
+        p1 = _trunc16(r)
+        p2 = (r - p1).astype(np.float32)
+    if weights:
+        u = v.view(np.uint32)
+        ex = (u >> np.uint32(23)) & np.uint32(0xff)
+        tiny = (((u >> np.uint32(16)) & np.uint32(0x8000)) | ((ex.astype(np.int64) - 40).clip(0).astype(np.uint32) << np.uint32(7))) << np.uint32(16)
+        for p in (p1, p2):
+            z = ((p.view(np.uint32) & np.uint32(0x7fff0000)) == 0) & (ex >= 41) & (ex != 255)
+            p.view(np.uint32)[z] = tiny[z]
+    return p0, p1, p2
+
+
+X3_TERMS = ((0, 2), (1, 1), (2, 0), (0, 1), (1, 0), (0, 0))            # (weight part, input part) in the kernels' order: the small terms first
+X3_SMALL = ((2, 0), (1, 1), (0, 2))                                    # the three 2^-16-sized ones
+
+
+def x3_steps(kernel, ic, fs):
+    """the k-steps of a split kernel as lists of (channel, ky, kx): what one MFMA chain link adds at once.  k_pw_x3: 32 channels; k_pw_x3t: 16; k_conv_x3: a group
+    is four k-units (8 channels, tap row ky) in a row and one k-step per tap column kx"""
+    if kernel == "pw_x3":
+        return [[(c, 0, 0) for c in range(s, min(s + 32, ic))] for s in range(0, ic, 32)]
+    if kernel == "pw_x3t":
+        return [[(c, 0, 0) for c in range(s, min(s + 16, ic))] for s in range(0, ic, 16)]
+    assert kernel in ("pw_x3s", "conv_x3") and ic % 8 == 0
+    units = [(cb, ky) for cb in range(ic // 8) for ky in range(fs)]
+    return [[(8 * cb + j, ky, kx) for cb, ky in units[g:g + 4] for j in range(8)] for g in range(0, len(units), 4) for kx in range(fs)]
+
+
+def model_x3(kernel, x, f, N, W, H, ic, pad, stride, fs, act, drop=None):
+    """a numpy model of the split kernels' arithmetic, (oc, N, OH, OW) float32: truncation split of both operands, the six kept terms in the kernels' order,
+    every k-step's 32 (16) exact products added exactly and the accumulator rounded to fp32 once per (k-step, term) -- the matrix cores' own order inside
+    a k-step is not modelled -- then fp32 scale' * sum + bias' and the activation.  drop = (weight part, input part): the model of a kernel that forgets that term."""
+    oc = f.shape[0]
+    K = fs * fs * ic
+    k4 = (K + 3) & ~3
+    OH, OW = out_dims(H, W, pad, stride, fs)
+    xp = np.zeros((ic, N, H + 2 * pad, W + 2 * pad), np.float32)
+    xp[:, :, pad:pad + H, pad:pad + W] = x.reshape(ic, N, H, W)
+    xs = [p.astype(np.float64) for p in split3(xp)]
+    ws = [p.astype(np.float64).reshape(oc, ic, fs, fs) for p in split3(f[:, :K], weights=True)]
+    acc = np.zeros((oc, N * OH * OW), np.float32)
+    for step in x3_steps(kernel, ic, fs):
+        ci, ky, kx = (np.array(v) for v in zip(*step))
+        cols = [p[ci[:, None, None, None], np.arange(N)[None, :, None, None], (np.arange(OH) * stride)[None, None, :, None] + ky[:, None, None, None],
+                  (np.arange(OW) * stride)[None, None, None, :] + kx[:, None, None, None]].reshape(len(step), -1) for p in xs]
+        rows = [p[:, ci, ky, kx] for p in ws]
+        for wp, xq in X3_TERMS:
+            if (wp, xq) != drop:
+                acc = (acc.astype(np.float64) + rows[wp] @ cols[xq]).astype(np.float32)
+    sc, bi = f[:, k4][:, None], f[:, k4 + 1][:, None]
+    v = (acc.astype(np.float64) * sc.astype(np.float64) + bi.astype(np.float64)).astype(np.float32)      # one fused multiply-add
+    if act == 3:
+        v = (1.0 / (1.0 + np.exp(-v.astype(np.float64)))).astype(np.float32)
+    elif act:
+        v = np.where(v > 0, v, (np.float32(0.1) * v if act == 2 else np.float32(0.0))).astype(np.float32)
+    return v.reshape(oc, N, OH, OW)
 
 
 def pair64(x, fd, fp, N, W, H, C, fs, actd, actp):

@@ -2,8 +2,9 @@
 kernel is forced by its FFGPU_K_* id and ffgpu_groupconv_kernel_name must answer the declared name first.  tests/test_conv_kernels_ref.py holds the table, the
 bound and the oracle to their purpose on the CPU.
 
-Part A (test_error_bound, test_pair_error_bound), every fp32 kernel.  Both must hold:
+Part A (test_error_bound, test_pair_error_bound), every fp32 kernel and the four split-bf16 kernels (pw_x3, pw_x3t, conv_x3, pw_x3s).  Both must hold:
     per output   |got - ref64| <= gamma(K + 3) (|scale'| sum |w x| + |bias'|)     the hard bound of convref: no correct fp32 evaluation can exceed it
+                 split kernels: (gamma(6 K + 3) + 2^-21 + 2^-30 + 2^-38) (...)    convref.bound_x3: six exact partial products per product, three dropped
     per case     E_k <= 2 E_ref + 1e-6  and  E_k <= 8e-7 max |y| + 1e-6            blockref.criterion, E_ref = max |oracle - ref64| the yardstick (cases.FACTOR holds
                                                                                   the kernels that need more than 2, if any, with the measured ratio)
 The output lies between guard words in one allocation and starts as NaN: the guards are unchanged, no output is unwritten, inputs and weights are unchanged.  The
@@ -12,9 +13,10 @@ two forms of the first layer (k_conv_dense8, k_conv_first) are compared bit for 
 Part B (test_non_finite_inputs, test_pair_non_finite_inputs), every conv kernel including pw_bf16: +Inf, -Inf and NaN among the inputs where each kernel's
 addressing can go wrong (cases.placements), under every activation the kernel takes.  The NaN pattern equals conv64's, every other touched output -- +-Inf, or the
 exact 0 / 1 that relu and the sigmoid make of -Inf, NaN and +-Inf (utils.h:15-23) -- is EQUAL to it, and every untouched output is finite and within the part A
-bound (pw_bf16: its own 2^-7 bound): nothing leaks into a neighbour's sum, a zero-weight padded k-slot included.
+bound (pw_bf16: its own 2^-7 bound): nothing leaks into a neighbour's sum, a zero-weight padded k-slot included.  A split kernel's case runs once more without
+the planted values: every untouched output keeps its bits (the Inf form of the split is chosen per wave and must not show in a neighbour's finite values).
 
-Part C (test_fused_residual): the epilogue act2(act(conv) + residual), reached through an executor whose fused plan absorbs the shortcut into the conv in front of it.
+Part C (test_fused_residual, test_fused_residual_non_finite*): the epilogue act2(act(conv) + residual), reached through an executor whose fused plan absorbs the shortcut into the conv in front of it.
 
 (File name: the suite orders GPU test files by their base name (tests/conftest.py); this one runs with the kernel tests.)"""
 import numpy as np
@@ -138,6 +140,13 @@ def test_non_finite_inputs(env, i, monkeypatch):
         assert (np.abs(got[ok].astype(np.float64) - r["y64"][ok]) <= b[ok]).all(), c.id
     else:
         assert_error(c.id, c.kernel, got, r, ok)
+    if c.kernel in cases.X3:
+        # the split kernels take the Inf form of the split per WAVE; for a finite value it computes the same three parts, so the same case WITHOUT the planted
+        # values must give every untouched output the same bits: a wave-level choice that leaks into its neighbours shows here
+        clean = launch(capi, torch, c, r["x0"], r["f"])
+        assert np.isfinite(clean).all(), c.id
+        diff = ok & (clean.view(np.uint32) != got.view(np.uint32))
+        assert not diff.any(), "%s: %d untouched outputs change their bits with the planted values, first at %r" % (c.id, int(diff.sum()), np.argwhere(diff)[:4].tolist())
 
 
 @pytest.mark.parametrize("i", range(len(NF_PAIRS)), ids=[p.id for p in NF_PAIRS])
@@ -157,9 +166,13 @@ def _run_res(capi, orc, tmp_path, monkeypatch, row, made, frames):
     from test_gpu_parity import _write_random_weights
     name, kernel, env, batch, w, h, ic, oc, size, groups, act = row
     g, a, b, c, s = made
+    stride = cases.RES_STRIDE.get(name, 1)
+    for k in cases.SWITCHES:
+        monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
+        assert k in cases.SWITCHES, k
         monkeypatch.setenv(k, v)
-    assert capi.kernel_name(batch, w, h, ic, groups, size // 2, 1, size, oc) == kernel
+    assert capi.kernel_name(batch, w, h, ic, groups, size // 2, stride, size, oc) == kernel
     cfg, wts = str(tmp_path / (g.name + ".cfg")), str(tmp_path / (g.name + ".weights"))
     with open(cfg, "w") as fp:
         fp.write(g.cfg_text())
@@ -179,7 +192,7 @@ def _run_res(capi, orc, tmp_path, monkeypatch, row, made, frames):
         with net.executor(batch, capi.FFGPU.KEEP_ALL | capi.FFGPU.NO_FUSE) as ex:
             model = [lay for lay, _ in ex.step_model()]
             assert s in model and [lay for lay in model if lay >= 0] == g.steps[False], (name, model)
-    return x.reshape(ic * batch, h, w), f, res.reshape(oc * batch, h, w), got
+    return x.reshape(ic * batch, h, w), f, res.reshape(oc * batch, h // stride, w // stride), got
 
 
 @pytest.mark.parametrize("row", cases.RES_TABLE, ids=cases.RES_IDS)
@@ -191,40 +204,56 @@ def test_fused_residual(env, orc, tmp_path, monkeypatch, row):
     rng = np.random.default_rng(len(name))
     frames = rng.uniform(-1, 1, (batch, 3, h, w)).astype(np.float32)
     x, f, res, got = _run_res(capi, orc, tmp_path, monkeypatch, row, made, frames)
-    ra, K = {"linear": 0, "relu": 1, "leaky": 2}[act], size * size * ic // groups
-    y64, sabs = convref.conv64(x, f, batch, w, h, ic, groups, size // 2, 1, size, 0, res, ra)
-    pre, _ = convref.conv64(x, f, batch, w, h, ic, groups, size // 2, 1, size, 0)
-    y32 = convref.oracle32(orc, x, f, batch, w, h, ic, groups, size // 2, 1, size, 0, res, ra)
-    r = dict(y64=y64, bound=convref.bound(f, K, sabs, 0, pre, res, ra), E_ref=float(np.abs(y32 - y64).max()), ymax=float(np.abs(y64).max()))
+    ra, K, stride = {"linear": 0, "relu": 1, "leaky": 2}[act], size * size * ic // groups, cases.RES_STRIDE.get(name, 1)
+    y64, sabs = convref.conv64(x, f, batch, w, h, ic, groups, size // 2, stride, size, 0, res, ra)
+    pre, _ = convref.conv64(x, f, batch, w, h, ic, groups, size // 2, stride, size, 0)
+    y32 = convref.oracle32(orc, x, f, batch, w, h, ic, groups, size // 2, stride, size, 0, res, ra)
+    bound = convref.bound_x3 if kernel in cases.X3 else convref.bound
+    r = dict(y64=y64, bound=bound(f, K, sabs, 0, pre, res, ra), E_ref=float(np.abs(y32 - y64).max()), ymax=float(np.abs(y64).max()))
     assert (np.abs(y32 - y64) <= r["bound"]).all(), "%s: the oracle misses the bound" % name
     assert_error("residual-" + name, kernel, got, r)
 
 
-def test_fused_residual_non_finite(env, orc, tmp_path, monkeypatch):
-    """+Inf, -Inf and NaN in the frame reach both sides of the add: +Inf + -Inf = NaN where the residual and the conv disagree in sign, and the relu shortcut makes
-    0 of it, of every NaN and of every -Inf (utils.h:18) -- NaN pattern (none is left), +Inf and the exact zeros equal to conv64's, the untouched pixels within the bound"""
-    capi, torch = env
-    row = cases.RES_NF
+def _residual_non_finite(capi, orc, tmp_path, monkeypatch, row, planted):
+    """+Inf, -Inf and NaN in the frame (planted: the three pixels) reach both sides of the add: +Inf + -Inf = NaN where the residual and the conv disagree in sign, and
+    the relu shortcut makes 0 of it, of every NaN and of every -Inf (utils.h:18) -- NaN pattern (none is left), +Inf and the exact zeros equal to conv64's, the
+    untouched pixels within the bound"""
     name, kernel, _, batch, w, h, ic, oc, size, groups, act = row
     rng = np.random.default_rng(11)
     frames = rng.uniform(-1, 1, (batch, ic, h, w)).astype(np.float32)
-    frames[0, 0, 2, 3], frames[0, ic - 1, 4, 7], frames[0, ic // 2, 5, 9] = np.inf, -np.inf, np.nan
-    x, f, res, got = _run_res(capi, orc, tmp_path, monkeypatch, row, cases.res_nf_cfg(), frames)
-    assert x.tobytes() == frames[0].tobytes()
-    y64, sabs = convref.conv64(x, f, batch, w, h, ic, 1, 0, 1, 1, 0, res, 1)
-    pre, _ = convref.conv64(x, f, batch, w, h, ic, 1, 0, 1, 1, 0)
+    (y0, x0), (y1, x1), (y2, x2) = planted
+    frames[0, 0, y0, x0], frames[0, ic - 1, y1, x1], frames[0, ic // 2, y2, x2] = np.inf, -np.inf, np.nan
+    x, f, res, got = _run_res(capi, orc, tmp_path, monkeypatch, row, cases.res_nf_cfg(row), frames)
+    # (the net input itself: its bytes; the average pool's copy of it: its values, a NaN for the NaN)
+    assert x.tobytes() == frames[0].tobytes() if row is cases.RES_NF else np.array_equal(x, frames[0], equal_nan=True), "%s: the conv does not read the planted frame" % name
+    pad, K = size // 2, size * size * ic
+    y64, sabs = convref.conv64(x, f, batch, w, h, ic, 1, pad, 1, size, 0, res, 1)
+    pre, _ = convref.conv64(x, f, batch, w, h, ic, 1, pad, 1, size, 0)
     r64 = res.reshape(pre.shape).astype(np.float64)
     t = np.zeros(y64.shape, bool)
-    t[:, 0, 2, 3] = t[:, 0, 4, 7] = t[:, 0, 5, 9] = True
+    for y, xx in planted:
+        t[:, 0, max(0, y - pad):y + pad + 1, max(0, xx - pad):xx + pad + 1] = True
     with np.errstate(invalid="ignore"):
         lin = pre + r64
     # set-up: the residual holds +Inf where the conv holds -Inf (and the other way round), both hold NaN at the third pixel; every touched sum is non-finite, all three kinds
     assert (np.isposinf(r64) & np.isneginf(pre)).any() and (np.isneginf(r64) & np.isposinf(pre)).any() and (np.isnan(r64) & np.isnan(pre)).any()
     assert not np.isfinite(lin[t]).any() and np.isfinite(lin[~t]).all() and cases.classes(lin) == {"nan", "+inf", "-inf"}
     assert not np.isnan(y64).any() and (y64[t] == 0).any() and np.isposinf(y64[t]).any() and np.isin(y64[t], (0.0, np.inf)).all()
-    r = dict(y64=y64, touched=t, bound=convref.bound(f, ic, sabs, 0, pre, res, 1), E_ref=0.0, ymax=0.0)
+    bound = convref.bound_x3 if kernel in cases.X3 else convref.bound
+    r = dict(y64=y64, touched=t, bound=bound(f, K, sabs, 0, pre, res, 1), E_ref=0.0, ymax=0.0)
     assert_non_finite(name, got, r)
     ok = ~t
-    y32 = convref.oracle32(orc, x, f, batch, w, h, ic, 1, 0, 1, 1, 0, res, 1)
+    y32 = convref.oracle32(orc, x, f, batch, w, h, ic, 1, pad, 1, size, 0, res, 1)
     r["E_ref"], r["ymax"] = float(np.abs(y32[ok] - y64[ok]).max()), float(np.abs(y64[ok]).max())
     assert_error("residual-" + name, kernel, got, r, ok)
+
+
+def test_fused_residual_non_finite(env, orc, tmp_path, monkeypatch):
+    """k_pw_mfma's epilogue: the conv reads the net input, the residual is a 1x1 conv of it"""
+    _residual_non_finite(env[0], orc, tmp_path, monkeypatch, cases.RES_NF, ((2, 3), (4, 7), (5, 9)))
+
+
+def test_fused_residual_non_finite_conv_x3(env, orc, tmp_path, monkeypatch):
+    """k_conv_x3's scalar epilogue at width 13: three 3x3 windows apart from each other, the last one in the overlapping last quad of its rows.  The residual is
+    non-finite in the middle of a window only: around it a finite residual meets +-Inf or NaN from the conv"""
+    _residual_non_finite(env[0], orc, tmp_path, monkeypatch, cases.RES_NF_X3, ((2, 3), (4, 7), (5, 11)))

@@ -80,13 +80,13 @@ class Cfg:
     def dropout(self):
         return self._add("dropout", "[dropout]\nprobability=.5\n", self.out_shape(self.n - 1), self.tip())
 
-    def conv(self, filters, act="linear", src=None, size=1, groups=1):
-        """1x1 by default; size > 1: stride 1 with "same" padding (pad=1 in a cfg: size / 2), so the plane keeps its shape"""
+    def conv(self, filters, act="linear", src=None, size=1, groups=1, stride=1):
+        """1x1 by default; size > 1: "same" padding (pad=1 in a cfg: size / 2), so that at stride 1 the plane keeps its shape; stride 2 halves an even plane"""
         self._goto(src)
         c, h, w = self.out_shape(self.n - 1)
-        assert size % 2 == 1 and c % groups == 0 and filters % groups == 0
-        i = self._add("conv", "[convolutional]\nfilters=%d\nsize=%d\nstride=1\npad=%d\n%sactivation=%s\n" % (
-            filters, size, 1 if size > 1 else 0, "groups=%d\n" % groups if groups > 1 else "", act), (filters, h, w))
+        assert size % 2 == 1 and c % groups == 0 and filters % groups == 0 and (stride == 1 or (h % stride == 0 and w % stride == 0))
+        i = self._add("conv", "[convolutional]\nfilters=%d\nsize=%d\nstride=%d\npad=%d\n%sactivation=%s\n" % (
+            filters, size, stride, 1 if size > 1 else 0, "groups=%d\n" % groups if groups > 1 else "", act), (filters, (h - 1) // stride + 1, (w - 1) // stride + 1))
         self._step(i)
         return i
 
