@@ -306,6 +306,7 @@ def test_exec_heat_then_blend_draw_caption_bgr(F, net, picture, flags):
         stride = 8
         d_items = torch.full((2 * stride * 64,), 0xA5, dtype=torch.uint8, device="cuda")
         F.heat_blend_bgr_dev(d_state.data_ptr(), 2, [1, 0], frames, c_blend(F, bs))
+        torch.cuda.synchronize()                                                       # (the blend ran on the default stream, the draw runs on the executor's)
         ex.draw_bgr(frames, F.DRAW_ENTRIES, color=(0, 255, 0), thickness=2)
         ex.caption_bgr(frames, F.caption_spec(True, True, False, True, 0.25, F.ZONES_NONE, 1, ts.fg, ts.color, ts.palette, d_names.data_ptr(), len(names)), d_items.data_ptr(), stride)
         torch.cuda.synchronize()
@@ -360,6 +361,7 @@ def test_exec_heat_nv12(F, net, picture):
         d_rows = torch.full((4 * heatref.ROW,), 0xA5, dtype=torch.uint8, device="cuda")
         ex.heat([0], c_spec(F, hs), d_state.data_ptr(), 1, d_rows.data_ptr())
         ex.heat([0], c_spec(F, hs), d_state.data_ptr(), 1, d_rows.data_ptr())
+        torch.cuda.synchronize()                                                       # (the passes ran on the executor's stream, the blend runs on the default one)
         F.heat_blend_nv12_dev(d_state.data_ptr(), 1, [0], [frame], c_blend(F, bs))
         torch.cuda.synchronize()
         state = heatref.State(1, 20, 14)

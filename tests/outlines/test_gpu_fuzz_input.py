@@ -240,6 +240,7 @@ def test_outlines_behind_the_tracker_and_the_zones(F, net, picture):
         stride = 96
         ospec = lineref.Spec(fuzzcases.ALL, 2, 2, 5, alarm=(0, 0, 255), palette=[(255, 0, 0), (0, 255, 0), (0, 160, 255), (255, 255, 0)])
         d_items = torch.full((2 * stride * 32,), 0xA5, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()                                                       # (the zones pass ran on the executor's stream, the operators run on the default one)
         F.outline_scene_dev(d_scene.data_ptr(), z_state.data_ptr(), 1, 16, z_ev.data_ptr(), zoneref.ROW + 2 * S, [0, 0], c_spec(F, ospec), d_items.data_ptr(), stride)
         F.draw_segments_bgr_dev(d_items.data_ptr(), stride, frames)
         nw, nh = 333, 201                                                               # the same items into NV12 surfaces of another size: clipped at their edges

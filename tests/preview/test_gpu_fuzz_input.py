@@ -189,18 +189,21 @@ def test_forward_draw_preview(F, net, picture, fmt):
 
     def at(d):
         return (base + d[0],) + tuple(d[1:]) if fmt == "bgr" else (base + d[0], base + d[1]) + tuple(d[2:])
+    torch.cuda.synchronize()
+    st = torch.cuda.Stream()                                                           # forward, draw and preview on ONE stream: stream order is the only barrier
+    s = st.cuda_stream
     with net.executor(1) as ex:
         if fmt == "bgr":
-            ex.forward_bgr_frames_dev([at(src)])
+            ex.forward_bgr_frames_dev([at(src)], stream=s)
             boxes = ex.read_boxes(0)
-            ex.draw_bgr([at(src)], F.DRAW_ENTRIES, color=(0, 255, 0), thickness=4)
-            F.preview_bgr_dev([at(src)], [at(dst)], [F.preview_pane(region, pane)], F.preview_spec())
+            ex.draw_bgr([at(src)], F.DRAW_ENTRIES, color=(0, 255, 0), thickness=4, stream=s)
+            F.preview_bgr_dev([at(src)], [at(dst)], [F.preview_pane(region, pane)], F.preview_spec(), stream=s)
         else:
-            ex.forward_nv12_frames_dev([at(src)])
+            ex.forward_nv12_frames_dev([at(src)], stream=s)
             boxes = ex.read_boxes(0)
-            ex.draw_nv12([at(src)], F.DRAW_ENTRIES, color=(81, 90, 240), thickness=4)
-            F.preview_nv12_dev([at(src)], [at(dst)], [F.preview_pane(region, pane)], F.preview_spec())
-        torch.cuda.synchronize()
+            ex.draw_nv12([at(src)], F.DRAW_ENTRIES, color=(81, 90, 240), thickness=4, stream=s)
+            F.preview_nv12_dev([at(src)], [at(dst)], [F.preview_pane(region, pane)], F.preview_spec(), stream=s)
+        st.synchronize()
     assert len(boxes) > 0
     want = arena.copy()
     if fmt == "bgr":

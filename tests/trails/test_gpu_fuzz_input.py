@@ -226,8 +226,10 @@ def test_trails_behind_the_tracker_drawn_into_the_frames(F, net, picture, behind
             ex.track([0, 1], F.track_spec(16, 1, 1, 0.2), t_state.data_ptr(), 2, t_ids.data_ptr())
             if behind_outline:
                 ex.zones([0, 1], F.zones_spec(CAP, 1, F.ZONES_IDS), d_scene.data_ptr(), z_state.data_ptr(), 2, z_ev.data_ptr(), t_ids.data_ptr())
+                torch.cuda.synchronize()                                               # (the outline operator runs on the default stream, between two passes on the executor's)
                 F.outline_scene_dev(d_scene.data_ptr(), z_state.data_ptr(), 2, CAP, z_ev.data_ptr(), zoneref.ROW + 2 * S, [0, 1],
                                     F.outline_spec(True, True, False, True, False, 2, 2, 5, palette=ospec.palette), d_items.data_ptr(), stride)
+                torch.cuda.synchronize()
             ex.trails([0, 1], c_spec(F, tspec), r_state.data_ptr(), 2, r_rows.data_ptr(), t_ids.data_ptr(), d_items.data_ptr(), stride, first_item, nitems)
             torch.cuda.synchronize()
             ids = t_ids.cpu().numpy().view("<i4").reshape(2, 8 + S)
