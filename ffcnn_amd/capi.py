@@ -214,6 +214,13 @@ class WarpLens(C.Structure):         # ffgpu_warp_lens (120 bytes): a lens model
     _fields_ = [("model", C.c_int), ("reserved", C.c_int), ("dst", C.c_double * 4), ("src", C.c_double * 4), ("k", C.c_double * 4), ("p", C.c_double * 2)]
 
 
+class Surface(C.Structure):          # ffgpu_surface (56 bytes): a source frame of the convert surfaces in any of the FFGPU_PIX_* layouts
+    _fields_ = [("p", C.c_void_p * 3), ("pitch", C.c_int * 3), ("w", C.c_int), ("h", C.c_int), ("format", C.c_int), ("matrix", C.c_int), ("reserved", C.c_int)]
+
+
+PIX_NAMES = ("BGR24", "RGB24", "BGRA32", "RGBA32", "GRAY8", "NV12", "NV21", "I420", "YV12", "YUY2", "UYVY", "P010")       # FFGPU_PIX_*, by value
+(PIX_BGR24, PIX_RGB24, PIX_BGRA32, PIX_RGBA32, PIX_GRAY8, PIX_NV12, PIX_NV21, PIX_I420, PIX_YV12, PIX_YUY2, PIX_UYVY, PIX_P010) = range(12)
+CONVERT_MAX_SIDE, CONVERT_MAX_JOBS = 8192, 4096                                        # FFGPU_CONVERT_MAX_SIDE, _MAX_JOBS
 WARP_MESH_ONE, WARP_SUB = 256, 32                                                      # FFGPU_WARP_MESH_ONE, _SUB
 WARP_BILINEAR, WARP_NEAREST = 0, 1                                                     # FFGPU_WARP_* (ffgpu_warp_spec.filter)
 WARP_FILL, WARP_CLAMP = 0, 1                                                           # FFGPU_WARP_* (ffgpu_warp_spec.border)
@@ -330,7 +337,8 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_motion_gate_dev", "ffgpu_exec_motion_gate",
            "ffgpu_preview_spec_check", "ffgpu_preview_rect", "ffgpu_preview_grid", "ffgpu_preview_tile", "ffgpu_preview_bgr_dev", "ffgpu_preview_nv12_dev",
            "ffgpu_warp_spec_check", "ffgpu_warp_mesh_size", "ffgpu_warp_mesh_orient", "ffgpu_warp_mesh_homography", "ffgpu_warp_mesh_lens", "ffgpu_warp_point",
-           "ffgpu_warp_tile", "ffgpu_warp_bgr_dev", "ffgpu_warp_nv12_dev"]
+           "ffgpu_warp_tile", "ffgpu_warp_bgr_dev", "ffgpu_warp_nv12_dev",
+           "ffgpu_convert_check", "ffgpu_convert_tile", "ffgpu_convert_bgr_dev", "ffgpu_convert_nv12_dev"]
 # include/ffcnn_hip_diag.h (libffcnn_hip_diag.so: lab equipment, its own library)
 DIAG_EXPORTS = ["ffgpu_membench", "ffgpu_pipe_probe", "ffgpu_pipe_probe2", "ffgpu_pipe_probe3", "ffgpu_mfma_floor", "ffgpu_diag_x3_term", "ffgpu_diag_xl_op", "ffgpu_clock_probe"]
 
@@ -541,6 +549,10 @@ def lib():
     L.ffgpu_warp_tile.argtypes = [C.POINTER(i)]
     L.ffgpu_warp_bgr_dev.argtypes = [C.POINTER(BgrFrame), C.POINTER(BgrFrame), C.POINTER(WarpMesh), i, C.POINTER(WarpSpec), vp]
     L.ffgpu_warp_nv12_dev.argtypes = [C.POINTER(Nv12Frame), C.POINTER(Nv12Frame), C.POINTER(WarpMesh), i, C.POINTER(WarpSpec), vp]
+    L.ffgpu_convert_check.argtypes = [C.POINTER(Surface), i, i, i]
+    L.ffgpu_convert_tile.argtypes = [C.POINTER(i)]
+    L.ffgpu_convert_bgr_dev.argtypes = [C.POINTER(Surface), C.POINTER(BgrFrame), i, vp]
+    L.ffgpu_convert_nv12_dev.argtypes = [C.POINTER(Surface), C.POINTER(Nv12Frame), i, vp]
     L.ffgpu_outline_scene_dev.argtypes = [vp, vp, i, i, vp, i, C.POINTER(i), i, C.POINTER(OutlineSpec), vp, i, vp]
     L.ffgpu_feature_dim.argtypes = [i, i, i, i]
     L.ffgpu_exec_feature_dim.argtypes = [vp, C.POINTER(FeatureSpec)]
@@ -2170,3 +2182,52 @@ def warp_nv12_dev(srcs, dsts, meshes, spec, stream=None):
     if not len(srcs) == len(dsts) == len(meshes):
         raise ValueError("%d sources, %d destinations and %d meshes" % (len(srcs), len(dsts), len(meshes)))
     _check(lib().ffgpu_warp_nv12_dev(nv12_frame_table(srcs), nv12_frame_table(dsts), _warp_meshes(meshes), len(meshes), spec, stream), "ffgpu_warp_nv12_dev")
+
+
+# ---------------------------------------------------------------------------------------------------------------- convert surfaces
+def surface(format, w, h, planes, pitches=(0, 0, 0), matrix=0):
+    """a Surface (ffgpu_surface): PIX_*; `planes` the device addresses of its one to three planes (0 or None behind the first: directly behind the
+    previous plane); pitches 0 = the minimum for w; matrix YUV_* (read for YUV sources into BGR and RGB sources into NV12)"""
+    s = Surface()
+    for k, p in enumerate(planes):
+        s.p[k] = p or None
+    for k, p in enumerate(pitches):
+        s.pitch[k] = p
+    s.w, s.h, s.format, s.matrix = w, h, format, matrix
+    return s
+
+
+def _surfaces(srcs):
+    arr = (Surface * max(1, len(srcs)))()
+    for k, s in enumerate(srcs):
+        if s is not None:                                       # (None: p[0] stays NULL, the job is skipped)
+            arr[k] = s
+    return arr
+
+
+def convert_check(src, dst_nv12, dst_w, dst_h):
+    """ffgpu_convert_check (pure host code): raises with what the operators reject about the surface for a destination of dst_w x dst_h"""
+    _check(lib().ffgpu_convert_check(src, int(bool(dst_nv12)), dst_w, dst_h), "ffgpu_convert_check")
+    return True
+
+
+def convert_tile():
+    """ffgpu_convert_tile (pure host code): (the columns, the rows of a workgroup's tile of destination pixels, the jobs one launch takes)"""
+    out = (C.c_int * 3)()
+    _check(lib().ffgpu_convert_tile(out), "ffgpu_convert_tile")
+    return tuple(out)
+
+
+def convert_bgr_dev(srcs, dsts, stream=None):
+    """ffgpu_convert_bgr_dev: job n converts srcs[n] (from surface, or None: skipped) into the whole of dsts[n] (what bgr_frame_desc accepts, or
+    None: skipped).  Enqueued on `stream` without synchronising."""
+    if len(srcs) != len(dsts):
+        raise ValueError("%d sources and %d destinations" % (len(srcs), len(dsts)))
+    _check(lib().ffgpu_convert_bgr_dev(_surfaces(srcs), bgr_frame_table(dsts), len(srcs), stream), "ffgpu_convert_bgr_dev")
+
+
+def convert_nv12_dev(srcs, dsts, stream=None):
+    """ffgpu_convert_nv12_dev: the same into NV12 frames (what nv12_frame_desc accepts, or None: skipped)"""
+    if len(srcs) != len(dsts):
+        raise ValueError("%d sources and %d destinations" % (len(srcs), len(dsts)))
+    _check(lib().ffgpu_convert_nv12_dev(_surfaces(srcs), nv12_frame_table(dsts), len(srcs), stream), "ffgpu_convert_nv12_dev")

@@ -16,6 +16,7 @@
 #include "ffgpu_motion_host.hpp"
 #include "ffgpu_preview_host.hpp"
 #include "ffgpu_warp_host.hpp"
+#include "ffgpu_convert_host.hpp"
 
 #define FFGPU_CHECK(expr)                                                                   \
     do {                                                                                    \

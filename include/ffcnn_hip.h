@@ -1906,6 +1906,87 @@ int ffgpu_warp_bgr_dev(const ffgpu_bgr_frame *srcs, const ffgpu_bgr_frame *dsts,
 int ffgpu_warp_nv12_dev(const ffgpu_nv12_frame *srcs, const ffgpu_nv12_frame *dsts, const ffgpu_warp_mesh *meshes, int njobs,
                         const ffgpu_warp_spec *spec, void *stream);
 
+/* ---- convert surfaces: I420, YV12, NV21, YUY2, UYVY, P010, RGB, BGRA, RGBA and GRAY8 frames into BGR and NV12 frames on the device ----------------
+ * Every operator above takes ffgpu_bgr_frame or ffgpu_nv12_frame and nothing else.  This family turns what decoders, cameras, capture cards and
+ * desktop capture write into one of the two, and the BGR a pipeline composed into the NV12 an encoder takes: decode, CONVERT, warp, motion update,
+ * forward, post-passes, preview, CONVERT (BGR to NV12), encode.  Source and destination have the same size; nothing is scaled.  Integers
+ * throughout, >> is arithmetic, clamps come last; no atomics; one owner per written byte; the same bytes on every run
+ * (tests/convert/convertref.py restates it in numpy).
+ *
+ * SURFACES.  Chroma planes have (w + 1) / 2 columns; 4:2:0 chroma has (h + 1) / 2 rows; a 4:2:2 row holds (w + 1) / 2 four-byte groups.  8-bit
+ * planes may have any byte alignment; the pair plane of NV12 / NV21 is 2-byte aligned with an even pitch, as ffgpu_nv12_frame states; both P010
+ * planes are 2-byte aligned with even pitches.  Odd sizes are legal in every format.
+ *
+ * REDUCTION OF P010.  A sample s becomes min(((s >> 6) + 2) >> 2, 255) before anything else; the low six bits are ignored.
+ *
+ * INTO BGR.  RGB family: a byte permutation, alpha dropped; BGR24 to BGR is a copy.  GRAY8: B = G = R = v.  YUV families: pixel (x, y) is the
+ * NV12 formula above (FFGPU_YUV_*, the source's `matrix`) of Y[y][x] and the NEAREST chroma sample, [y >> 1][x >> 1] for 4:2:0 and [y][x >> 1]
+ * for 4:2:2.  For NV12 that is the very image ffgpu_exec_forward_nv12_frames_dev is defined on.
+ *
+ * INTO NV12.  Neither frame's `matrix` is converted between: YUV to NV12 does no range or matrix change, and the source's `matrix` is read for
+ * RGB sources only.  Luma: YUV sources, Y copied (P010 reduced); GRAY8, Y = v; RGB sources,
+ *     Y = clamp(((yr R + yg G + yb B + 128) >> 8) + yoff, 0, 255).
+ * Chroma sample (i, j) owns luma pixels (2i..2i+1, 2j..2j+1) clipped to the frame.  4:2:0 sources: the source's sample (i, j) copied, U before V
+ * whatever the source's order.  4:2:2 sources: (C[2j][i] + C[2j+1][i] + 1) >> 1 per component, or C[2j][i] alone where 2j + 1 == h.  GRAY8: 128,
+ * 128.  RGB sources: the n pixels of the block (n = 1, 2 or 4) summed per channel, the mean (sum + (n >> 1)) >> log2 n, then
+ *     U = clamp(((ur R + ug G + ub B + 128) >> 8) + 128, 0, 255),  V = clamp(((vr R + vg G + vb B + 128) >> 8) + 128, 0, 255).
+ * RGB to YUV coefficients by FFGPU_YUV_*:         yoff   yr  yg  yb    ur  ug  ub    vr   vg  vb
+ *     FFGPU_YUV_BT601_LIMITED                       16   66 129  25   -38 -74 112   112  -94 -18
+ *     FFGPU_YUV_BT601_FULL                           0   77 150  29   -43 -85 128   128 -107 -21
+ *     FFGPU_YUV_BT709_LIMITED                       16   47 157  16   -26 -86 112   112 -102 -10
+ *     FFGPU_YUV_BT709_FULL                           0   54 183  19   -29 -99 128   128 -116 -12
+ * Every chroma row sums to 0, so a grey picture gives U = V = 128 exactly; luma rows sum to 220 or 256, so white gives 235 or 255; the clamp is
+ * needed: full-range pure blue reaches 256 before it.
+ *
+ * What follows from the rule: NV12 to NV12 and BGR to BGR are byte copies; I420, YV12 and NV21 into NV12 permute bytes; a constant surface stays
+ * constant.  Untouched: row padding, memory round the destination, every source byte. */
+#define FFGPU_PIX_BGR24 0   /* p[0]: B G R                                  */
+#define FFGPU_PIX_RGB24 1   /* p[0]: R G B                                  */
+#define FFGPU_PIX_BGRA32 2  /* p[0]: B G R A, A dropped                     */
+#define FFGPU_PIX_RGBA32 3  /* p[0]: R G B A, A dropped                     */
+#define FFGPU_PIX_GRAY8 4   /* p[0]: one byte per pixel                     */
+#define FFGPU_PIX_NV12  5   /* p[0]: Y, p[1]: U V pairs at half size        */
+#define FFGPU_PIX_NV21  6   /* p[0]: Y, p[1]: V U pairs                     */
+#define FFGPU_PIX_I420  7   /* p[0]: Y, p[1]: U, p[2]: V, chroma half size  */
+#define FFGPU_PIX_YV12  8   /* p[0]: Y, p[1]: V, p[2]: U                    */
+#define FFGPU_PIX_YUY2  9   /* p[0]: Y0 U Y1 V per pixel pair               */
+#define FFGPU_PIX_UYVY 10   /* p[0]: U Y0 V Y1                              */
+#define FFGPU_PIX_P010 11   /* as NV12, 16-bit little-endian samples, value in the top 10 bits */
+#define FFGPU_CONVERT_MAX_SIDE 8192
+#define FFGPU_CONVERT_MAX_JOBS 4096
+typedef struct {
+    const unsigned char *p[3];  /* planes; unused ones NULL.  A NULL used plane after p[0] = directly behind the previous plane */
+    int pitch[3];               /* bytes per row of each plane; 0 = the minimum for w */
+    int w, h;                   /* pixels, 1..FFGPU_CONVERT_MAX_SIDE (8192); odd sizes legal in every format */
+    int format;                 /* FFGPU_PIX_*   */
+    int matrix;                 /* FFGPU_YUV_*   */
+    int reserved;               /* 0 */
+} ffgpu_surface;                /* 56 bytes: p 0, pitch 24, w 36, h 40, format 44, matrix 48, reserved 52 */
+
+/* Pure host code, both: 0, or -1 with the message in ffgpu_last_error.  ffgpu_convert_check: what the operators below reject about ONE source
+ * surface (as job 0) for a destination of dst_w x dst_h, BGR or (dst_nv12 != 0) NV12; with a NULL p[0] the checks of addresses are left out. */
+int ffgpu_convert_check(const ffgpu_surface *src, int dst_nv12, int dst_w, int dst_h);
+/* out = { the columns and the rows of a workgroup's tile of destination pixels, the jobs one launch takes } */
+int ffgpu_convert_tile(int out[3]);
+
+/* The operators.  srcs and dsts are HOST arrays, free again on return; job n converts srcs[n] into the WHOLE of dsts[n] (the const pointers of
+ * the destinations are written through); destinations are described exactly as the draw operators take them.  One kernel template, instantiated per
+ * source class (packed RGB, gray, planar 4:2:0, pair-plane 4:2:0, 16-bit pair-plane 4:2:0, packed 4:2:2) and destination.  A lane owns a block of
+ * 4 destination pixels by 2 rows anchored at the frame's origin and reads or produces the block's two chroma samples per plane once; a workgroup
+ * owns a tile of 256 x 8 pixels and is the only writer of those bytes.  A job whose every plane address and pitch, source and destination, is a
+ * multiple of 4 runs in the ALIGNED form: whole dwords loaded and stored, the stores streamed past the caches, the ragged last block of a row and
+ * the odd last row byte by byte; every other job runs in the GENERAL form, bytes and aligned 16-bit pairs.  The choice is the host's, per job, and
+ * both forms give the same bytes.  The jobs travel as a by-value table inside a kernel argument, 48 per launch and source class; more jobs are
+ * more launches, in order on `stream`.  Enqueued without synchronising; stream order is the only barrier.  There is no executor form: the operator
+ * reads frames, not records.  A job whose p[0] or whose destination pixel address (bgr / y) is NULL is skipped; its surface is not looked at.
+ * Rejected before anything is launched, with the job's index: everything the draw operators reject about the destination frame; NULL arrays; njobs
+ * outside 1..FFGPU_CONVERT_MAX_JOBS; an unknown format, or matrix outside 0..3; reserved != 0; a side outside 1..8192; a pitch below its minimum,
+ * or an odd pitch where pairs are read; a misaligned pair or 16-bit plane; a non-NULL pointer in a plane the format does not use; a size that
+ * differs from the destination's; a source plane address equal to a destination plane address; two jobs with the same destination pixel address
+ * (both indices).  Any other overlap of memory is the caller's responsibility. */
+int ffgpu_convert_bgr_dev (const ffgpu_surface *srcs, const ffgpu_bgr_frame  *dsts, int njobs, void *stream);
+int ffgpu_convert_nv12_dev(const ffgpu_surface *srcs, const ffgpu_nv12_frame *dsts, int njobs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
