@@ -116,6 +116,15 @@ int ffgpu_frame_table(const char *what, const FrameRole &role, const Frame *f, i
     return 0;
 }
 
+// the grid of a surface pass's launch: the tiles (tw x th) of the job with the most of them among n jobs, whose extent is the members w x h
+template <class Job>
+inline unsigned ffgpu_most_tiles(const Job *j, int n, int tw, int th, int Job::*w, int Job::*h)
+{
+    unsigned most = 1;
+    for (int i = 0; i < n; i++) most = std::max(most, (unsigned)(((j[i].*w + tw - 1) / tw) * ((j[i].*h + th - 1) / th)));
+    return most;
+}
+
 // -------------------------------------------------------------------------- colours and class tables
 // a colour of a spec (B G R or Y U V, a fourth byte ignored) as the kernels carry it: byte k in bits 8 k .. 8 k + 7
 inline unsigned ffgpu_pack_colour(const unsigned char *c) { return (unsigned)c[0] | (unsigned)c[1] << 8 | (unsigned)c[2] << 16; }

@@ -239,15 +239,7 @@ extern "C" int ffgpu_convert_tile(int out[3])
 template <int SRC, int DST>
 static int convert_launch(const std::vector<ConvertJob> &jobs, hipStream_t s)
 {
-    for (size_t i0 = 0; i0 < jobs.size(); i0 += CONVERT_ARG_JOBS) {
-        const int n = (int)std::min((size_t)CONVERT_ARG_JOBS, jobs.size() - i0);
-        ConvertArgs a;
-        memset(&a, 0, sizeof a);
-        memcpy(a.j, jobs.data() + i0, sizeof(ConvertJob) * (size_t)n);
-        hipLaunchKernelGGL((k_convert<SRC, DST>), dim3(ffgpu_convert_tiles(a.j, n), (unsigned)n), dim3(256), 0, s, a);
-        LAUNCH_OK("convert");
-    }
-    return 0;
+    return launch_jobs<ConvertArgs, CONVERT_ARG_JOBS>("convert", jobs, ffgpu_convert_tiles, [](ConvertArgs &) {}, k_convert<SRC, DST>, s);
 }
 
 template <int DST, class Frame>

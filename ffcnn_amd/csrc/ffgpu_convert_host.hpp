@@ -135,9 +135,4 @@ int ffgpu_convert_args_check(const char *what, const ffgpu_surface *srcs, const 
 }
 
 // the tiles of the job with the most of them: the launch's grid
-inline unsigned ffgpu_convert_tiles(const ConvertJob *j, int n)
-{
-    unsigned most = 1;
-    for (int i = 0; i < n; i++) most = std::max(most, (unsigned)(((j[i].w + CONVERT_TW - 1) / CONVERT_TW) * ((j[i].h + CONVERT_TH - 1) / CONVERT_TH)));
-    return most;
-}
+inline unsigned ffgpu_convert_tiles(const ConvertJob *j, int n) { return ffgpu_most_tiles(j, n, CONVERT_TW, CONVERT_TH, &ConvertJob::w, &ConvertJob::h); }

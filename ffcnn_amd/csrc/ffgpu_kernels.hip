@@ -459,6 +459,23 @@ static inline int grid_for(long total, int block, int cap = 256 * 16)
         if (e_ != hipSuccess) { ffgpu_set_error("%s launch failed: %s", what, hipGetErrorString(e_)); return -1; } \
     } while (0)
 
+// A surface pass's jobs of one kind (preview, warp, convert), PER per launch, in order on the stream: the jobs travel by value in Args::j, every other
+// byte of Args zero but for what `rest` sets; the grid is (tiles(the launch's jobs, their number), jobs) of 256 threads.
+template <class Args, int PER, class Job, class Tiles, class Rest, class Kernel>
+static int launch_jobs(const char *what, const std::vector<Job> &jobs, Tiles tiles, Rest rest, Kernel kernel, hipStream_t s)
+{
+    for (size_t i0 = 0; i0 < jobs.size(); i0 += PER) {
+        const int n = (int)std::min((size_t)PER, jobs.size() - i0);
+        Args a;
+        memset(&a, 0, sizeof a);
+        memcpy(a.j, jobs.data() + i0, sizeof(Job) * (size_t)n);
+        rest(a);
+        hipLaunchKernelGGL(kernel, dim3(tiles(a.j, n), (unsigned)n), dim3(256), 0, s, a);
+        LAUNCH_OK(what);
+    }
+    return 0;
+}
+
 // Dynamic LDS above 64 KB has to be allowed per kernel AND per device: a node (ffgpu_node.inc) plans the same kernels on every
 // GPU of the box from one process, so "raised once per process" is not enough.
 static int lds_allow(const void *fn, size_t lds, const char *what)

@@ -182,15 +182,7 @@ extern "C" int ffgpu_preview_tile(int out[3])
 template <int CH>
 static int preview_launch(const std::vector<PreviewJob> &jobs, hipStream_t s)
 {
-    for (size_t i0 = 0; i0 < jobs.size(); i0 += PREVIEW_ARG_JOBS) {
-        const int n = (int)std::min((size_t)PREVIEW_ARG_JOBS, jobs.size() - i0);
-        PreviewArgs a;
-        memset(&a, 0, sizeof a);
-        memcpy(a.j, jobs.data() + i0, sizeof(PreviewJob) * (size_t)n);
-        hipLaunchKernelGGL(k_preview<CH>, dim3(ffgpu_preview_tiles(a.j, n), (unsigned)n), dim3(256), 0, s, a);
-        LAUNCH_OK("preview");
-    }
-    return 0;
+    return launch_jobs<PreviewArgs, PREVIEW_ARG_JOBS>("preview", jobs, ffgpu_preview_tiles, [](PreviewArgs &) {}, k_preview<CH>, s);
 }
 
 template <class Frame>

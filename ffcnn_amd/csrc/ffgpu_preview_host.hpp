@@ -164,9 +164,4 @@ int ffgpu_preview_args_check(const char *what, const Frame *srcs, const Frame *d
 }
 
 // the tiles of the job with the most of them: the launch's grid
-inline unsigned ffgpu_preview_tiles(const PreviewJob *j, int n)
-{
-    unsigned most = 1;
-    for (int i = 0; i < n; i++) most = std::max(most, (unsigned)(((j[i].pw + PREVIEW_TW - 1) / PREVIEW_TW) * ((j[i].ph + PREVIEW_TH - 1) / PREVIEW_TH)));
-    return most;
-}
+inline unsigned ffgpu_preview_tiles(const PreviewJob *j, int n) { return ffgpu_most_tiles(j, n, PREVIEW_TW, PREVIEW_TH, &PreviewJob::pw, &PreviewJob::ph); }

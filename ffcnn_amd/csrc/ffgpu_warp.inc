@@ -205,16 +205,8 @@ extern "C" int ffgpu_warp_tile(int out[4])
 template <int CH>
 static int warp_launch(const std::vector<WarpJob> &jobs, const ffgpu_warp_spec *spec, unsigned fill, hipStream_t s)
 {
-    for (size_t i0 = 0; i0 < jobs.size(); i0 += WARP_ARG_JOBS) {
-        const int n = (int)std::min((size_t)WARP_ARG_JOBS, jobs.size() - i0);
-        WarpArgs a;
-        memset(&a, 0, sizeof a);
-        memcpy(a.j, jobs.data() + i0, sizeof(WarpJob) * (size_t)n);
-        a.fill = fill; a.nearest = spec->filter == FFGPU_WARP_NEAREST; a.clamp = spec->border == FFGPU_WARP_CLAMP;
-        hipLaunchKernelGGL(k_warp<CH>, dim3(ffgpu_warp_tiles(a.j, n), (unsigned)n), dim3(256), 0, s, a);
-        LAUNCH_OK("warp");
-    }
-    return 0;
+    const auto rest = [=](WarpArgs &a) { a.fill = fill; a.nearest = spec->filter == FFGPU_WARP_NEAREST; a.clamp = spec->border == FFGPU_WARP_CLAMP; };
+    return launch_jobs<WarpArgs, WARP_ARG_JOBS>("warp", jobs, ffgpu_warp_tiles, rest, k_warp<CH>, s);
 }
 
 template <class Frame>

@@ -245,9 +245,4 @@ int ffgpu_warp_args_check(const char *what, const Frame *srcs, const Frame *dsts
 }
 
 // the tiles of the job with the most of them: the launch's grid
-inline unsigned ffgpu_warp_tiles(const WarpJob *j, int n)
-{
-    unsigned most = 1;
-    for (int i = 0; i < n; i++) most = std::max(most, (unsigned)(((j[i].dw + WARP_TW - 1) / WARP_TW) * ((j[i].dh + WARP_TH - 1) / WARP_TH)));
-    return most;
-}
+inline unsigned ffgpu_warp_tiles(const WarpJob *j, int n) { return ffgpu_most_tiles(j, n, WARP_TW, WARP_TH, &WarpJob::dw, &WarpJob::dh); }

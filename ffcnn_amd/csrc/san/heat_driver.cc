@@ -2,38 +2,12 @@
 // specs resolved into their plans, the built-in palette, and the argument checks of the accumulate operator and of the blend, on good and hostile
 // arguments.  One line per case: id, return value, message.  The last line is "heat_driver: N cases, 0 wrong".  Nothing of HIP: the addresses are
 // made up and never followed.  `heat_driver palette` prints the two built-in palettes as hex instead (2 x 1024 bytes).
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include <limits>
 #include "../ffgpu_heat_host.hpp"
+#include "driver.hpp"
 
-static char g_err[512];
-extern "C" void ffgpu_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-
-static int g_cases, g_wrong;
-static void line(const char *id, int rc, int want_rc, const char *want_msg)
-{
-    const bool ok = rc == want_rc && (rc == 0 || strstr(g_err, want_msg));
-    g_cases++;
-    g_wrong += !ok;
-    printf("%s %d %s%s\n", id, rc, rc ? g_err : "", ok ? "" : "   <-- WRONG");
-}
-static void fact(const char *id, bool ok)
-{
-    g_cases++;
-    g_wrong += !ok;
-    printf("%s %s\n", id, ok ? "holds" : "fails   <-- WRONG");
-}
-
-static const void *at(uintptr_t a) { return reinterpret_cast<const void *>(a); }
 static const unsigned char g_classes[3] = { 1, 0, 1 };
 static unsigned char g_palette[1024];
 
@@ -58,7 +32,7 @@ template <class Fn> static void spec(const char *id, int want_rc, const char *wa
     change(sp);
     g_err[0] = 0;
     HeatPlan pl;
-    line(id, ffgpu_heat_spec_plan("op", &sp, pl), want_rc, want_msg);
+    line_exact(id, ffgpu_heat_spec_plan("op", &sp, pl), want_rc, want_msg);
 }
 template <class Fn> static void blend(const char *id, int want_rc, const char *want_msg, Fn change)
 {
@@ -66,7 +40,7 @@ template <class Fn> static void blend(const char *id, int want_rc, const char *w
     change(sp);
     g_err[0] = 0;
     HeatBlendPlan pl;
-    line(id, ffgpu_heat_blend_spec_plan("op", &sp, false, pl), want_rc, want_msg);
+    line_exact(id, ffgpu_heat_blend_spec_plan("op", &sp, false, pl), want_rc, want_msg);
 }
 
 struct Args {
@@ -82,8 +56,8 @@ template <class Fn> static void args(const char *id, int want_rc, const char *wa
     change(a);
     g_err[0] = 0;
     HeatPlan pl;
-    line(id, ffgpu_heat_args_check("op", a.have_streams ? a.streams.data() : nullptr, a.ntargets, a.have_spec ? &a.spec : nullptr, at(a.state), a.nstreams, at(a.rows), pl),
-         want_rc, want_msg);
+    line_exact(id, ffgpu_heat_args_check("op", a.have_streams ? a.streams.data() : nullptr, a.ntargets, a.have_spec ? &a.spec : nullptr, at(a.state), a.nstreams, at(a.rows), pl),
+               want_rc, want_msg);
 }
 
 struct BArgs {
@@ -117,7 +91,7 @@ template <class Fn> static void bargs(const char *id, bool nv12, int want_rc, co
     const ffgpu_heat_blend_spec *sp = a.have_spec ? &a.spec : nullptr;
     if (nv12) rc = ffgpu_heat_blend_args_check("op", at(a.state), a.nstreams, st, a.have_targets ? a.nv.data() : nullptr, a.ntargets, sp, true, pl, tab);
     else      rc = ffgpu_heat_blend_args_check("op", at(a.state), a.nstreams, st, a.have_targets ? a.bgr.data() : nullptr, a.ntargets, sp, false, pl, tab);
-    line(id, rc, want_rc, want_msg);
+    line_exact(id, rc, want_rc, want_msg);
     if (rc == 0 && want_rc == 0)
         fact(id, tab.size() == 3 && tab[0].p0 && tab[0].first == 0 && !tab[1].p0 && tab[1].first == -1 && !tab[2].p0 && tab[2].first == 1 && tab[0].w == 65 && tab[0].h == 33 &&
                  tab[0].pitch == (nv12 ? 65 : 200) && (nv12 ? tab[0].p1 != nullptr && tab[0].pitch_uv == 66 : tab[0].p1 == nullptr));
@@ -163,25 +137,25 @@ int main(int argc, char **argv)
         ffgpu_heat_spec sp = good_spec();
         HeatPlan pl;
         g_err[0] = 0;
-        line("plan.spec", ffgpu_heat_spec_plan("op", &sp, pl), 0, "");
+        line_exact("plan.spec", ffgpu_heat_spec_plan("op", &sp, pl), 0, "");
         fact("plan.spec_values", pl.gw == 40 && pl.gh == 23 && pl.cell_log2 == 4 && pl.mode == 0 && pl.anchor == 1 && pl.spread == 2 && pl.gain == 64 && pl.decay_shift == 5 &&
                                  pl.min_score == 0.25f && pl.nclasses == 0);
         sp.classes = g_classes; sp.nclasses = 3;
-        line("plan.classes", ffgpu_heat_spec_plan("op", &sp, pl), 0, "");
+        line_exact("plan.classes", ffgpu_heat_spec_plan("op", &sp, pl), 0, "");
         fact("plan.classes_values", pl.nclasses == 3 && pl.classes[0] == 1 && pl.classes[1] == 0 && pl.classes[2] == 1 && pl.classes[3] == 0);
-        line("plan.null_spec", ffgpu_heat_spec_plan("op", nullptr, pl), -1, "NULL spec");
+        line_exact("plan.null_spec", ffgpu_heat_spec_plan("op", nullptr, pl), -1, "NULL spec");
         ffgpu_heat_blend_spec bs = good_blend();
         HeatBlendPlan bp;
-        line("plan.blend", ffgpu_heat_blend_spec_plan("op", &bs, false, bp), 0, "");
+        line_exact("plan.blend", ffgpu_heat_blend_spec_plan("op", &bs, false, bp), 0, "");
         fact("plan.blend_values", bp.gw == 40 && bp.gh == 23 && bp.cell_log2 == 4 && bp.full_scale == 1000 && bp.floor == 8 && bp.opacity == 160 && bp.smooth == 1 && bp.ramp == 1 &&
                                   bp.pal[0] == 0x0000ffu && bp.pal[64] == 0x00ffffu && bp.pal[255] == 0xff0000u);
-        line("plan.blend_nv12", ffgpu_heat_blend_spec_plan("op", &bs, true, bp), 0, "");
+        line_exact("plan.blend_nv12", ffgpu_heat_blend_spec_plan("op", &bs, true, bp), 0, "");
         fact("plan.blend_nv12_values", bp.pal[0] == (29u | 255u << 8 | 107u << 16));
         for (int i = 0; i < 1024; i++) g_palette[i] = (unsigned char)(i * 7);
         bs.palette = g_palette;
-        line("plan.blend_palette", ffgpu_heat_blend_spec_plan("op", &bs, true, bp), 0, "");
+        line_exact("plan.blend_palette", ffgpu_heat_blend_spec_plan("op", &bs, true, bp), 0, "");
         fact("plan.blend_palette_values", bp.pal[1] == ((4u * 7u) | (5u * 7u) << 8 | (6u * 7u) << 16) && bp.pal[255] == ((1020u * 7u & 255u) | (1021u * 7u & 255u) << 8 | (1022u * 7u & 255u) << 16));
-        line("plan.null_blend", ffgpu_heat_blend_spec_plan("op", nullptr, false, bp), -1, "NULL spec");
+        line_exact("plan.null_blend", ffgpu_heat_blend_spec_plan("op", nullptr, false, bp), -1, "NULL spec");
     }
 
     spec("spec.good", 0, "", [](ffgpu_heat_spec &) {});
@@ -275,6 +249,5 @@ int main(int argc, char **argv)
     bargs("nv12.uv_odd", true, -1, "is odd (U V pairs are written", [](BArgs &a) { a.nv[0].uv = (const unsigned char *)at(0x18001); });
     bargs("nv12.matrix", true, -1, "target 1: matrix 4", [](BArgs &a) { a.nv[1].matrix = 4; });
 
-    printf("heat_driver: %d cases, %d wrong\n", g_cases, g_wrong);
-    return g_wrong ? 1 : 0;
+    return finish("heat_driver");
 }

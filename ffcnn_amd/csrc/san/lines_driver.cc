@@ -1,38 +1,12 @@
 // lines_driver.cc -- ffgpu_lines_host.hpp on the CPU under AddressSanitizer + UBSan (`make lines`; tests/test_outlines_abi.py): the outline spec
 // resolved into its plan, and the argument checks of the segment rasteriser and the scene composer on good and hostile arguments.  One line per
 // case: id, return value, message.  The last line is "lines_driver: N cases, 0 wrong".  Nothing of HIP: the addresses are made up and never followed.
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include <limits>
 #include "../ffgpu_lines_host.hpp"
+#include "driver.hpp"
 
-static char g_err[512];
-extern "C" void ffgpu_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-
-static int g_cases, g_wrong;
-static void line(const char *id, int rc, int want_rc, const char *want_msg)
-{
-    const bool ok = rc == want_rc && (rc == 0 || strstr(g_err, want_msg));
-    g_cases++;
-    g_wrong += !ok;
-    printf("%s %d %s%s\n", id, rc, rc ? g_err : "", ok ? "" : "   <-- WRONG");
-}
-static void fact(const char *id, bool ok)
-{
-    g_cases++;
-    g_wrong += !ok;
-    printf("%s %s\n", id, ok ? "holds" : "fails   <-- WRONG");
-}
-
-static const void *at(uintptr_t a) { return reinterpret_cast<const void *>(a); }
 static const unsigned char g_palette[3 * 4] = { 1, 2, 3, 9, 4, 5, 6, 9, 7, 8, 9, 9 };
 static const int ALL = FFGPU_OUTLINE_ZONES | FFGPU_OUTLINE_LINES | FFGPU_OUTLINE_TICKS | FFGPU_OUTLINE_MARKERS | FFGPU_OUTLINE_ALARM;
 
@@ -52,7 +26,7 @@ template <class Fn> static void spec(const char *id, int want_rc, const char *wa
     change(sp);
     g_err[0] = 0;
     OutlinePlan pl;
-    line(id, ffgpu_outline_spec_plan("op", &sp, pl), want_rc, want_msg);
+    line_exact(id, ffgpu_outline_spec_plan("op", &sp, pl), want_rc, want_msg);
 }
 
 struct Scene {
@@ -68,9 +42,9 @@ template <class Fn> static void scene(const char *id, int want_rc, const char *w
     change(a);
     g_err[0] = 0;
     OutlinePlan pl;
-    line(id, ffgpu_outline_scene_args_check("op", at(a.scenes), at(a.state), a.nstreams, a.capacity, at(a.events), a.events_stride,
-                                            a.have_streams ? a.streams.data() : nullptr, a.ntargets, a.have_spec ? &a.spec : nullptr, at(a.items), a.items_stride, pl),
-         want_rc, want_msg);
+    line_exact(id, ffgpu_outline_scene_args_check("op", at(a.scenes), at(a.state), a.nstreams, a.capacity, at(a.events), a.events_stride,
+                                                  a.have_streams ? a.streams.data() : nullptr, a.ntargets, a.have_spec ? &a.spec : nullptr, at(a.items), a.items_stride, pl),
+               want_rc, want_msg);
 }
 
 struct Segs { uintptr_t items = 0x4000, targets = 0x5000; int items_stride = 512, ntargets = 3; };
@@ -79,7 +53,7 @@ template <class Fn> static void segs(const char *id, int want_rc, const char *wa
     Segs a;
     change(a);
     g_err[0] = 0;
-    line(id, ffgpu_draw_segments_args_check("op", at(a.items), a.items_stride, at(a.targets), a.ntargets), want_rc, want_msg);
+    line_exact(id, ffgpu_draw_segments_args_check("op", at(a.items), a.items_stride, at(a.targets), a.ntargets), want_rc, want_msg);
 }
 
 int main()
@@ -91,13 +65,13 @@ int main()
         ffgpu_outline_spec sp = good_spec();
         OutlinePlan pl;
         g_err[0] = 0;
-        line("plan.color", ffgpu_outline_spec_plan("op", &sp, pl), 0, "");
+        line_exact("plan.color", ffgpu_outline_spec_plan("op", &sp, pl), 0, "");
         fact("plan.color_values", pl.npal == 1 && pl.pal[0] == 0x1e140au && pl.pal[1] == 0 && pl.alarm == 0xfcfbfau && pl.flags == ALL && pl.thickness == 2 &&
                                   pl.line_dash == 3 && pl.marker == 4);
         sp.palette = g_palette; sp.npalette = 3;
-        line("plan.palette", ffgpu_outline_spec_plan("op", &sp, pl), 0, "");
+        line_exact("plan.palette", ffgpu_outline_spec_plan("op", &sp, pl), 0, "");
         fact("plan.palette_values", pl.npal == 3 && pl.pal[0] == 0x030201u && pl.pal[1] == 0x060504u && pl.pal[2] == 0x090807u && pl.pal[3] == 0);
-        line("plan.null_spec", ffgpu_outline_spec_plan("op", nullptr, pl), -1, "NULL spec");
+        line_exact("plan.null_spec", ffgpu_outline_spec_plan("op", nullptr, pl), -1, "NULL spec");
     }
 
     // every combination of the five flags: legal exactly when a part is named, TICKS has LINES and ALARM has ZONES
@@ -176,6 +150,5 @@ int main()
     segs("segments.ntargets_0", -1, "0 targets", [](Segs &a) { a.ntargets = 0; });
     segs("segments.ntargets_neg", -1, "-5 targets", [](Segs &a) { a.ntargets = -5; });
 
-    printf("lines_driver: %d cases, %d wrong\n", g_cases, g_wrong);
-    return g_wrong ? 1 : 0;
+    return finish("lines_driver");
 }

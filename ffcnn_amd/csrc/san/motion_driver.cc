@@ -2,38 +2,12 @@
 // size, the motion spec resolved into its plan, the argument checks of the update and of the gate, and the rounds of an update call, on good and
 // hostile arguments.  One line per case: id, return value, message.  The last line is "motion_driver: N cases, 0 wrong".  Nothing of HIP: the
 // addresses are made up and never followed.
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include <limits>
 #include "../ffgpu_motion_host.hpp"
+#include "driver.hpp"
 
-static char g_err[512];
-extern "C" void ffgpu_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-
-static int g_cases, g_wrong;
-static void line(const char *id, int rc, int want_rc, const char *want_msg)
-{
-    const bool ok = (want_rc < 0 ? rc == want_rc : rc >= 0) && (rc >= 0 || strstr(g_err, want_msg));
-    g_cases++;
-    g_wrong += !ok;
-    printf("%s %d %s%s\n", id, rc, rc < 0 ? g_err : "", ok ? "" : "   <-- WRONG");
-}
-static void fact(const char *id, bool ok)
-{
-    g_cases++;
-    g_wrong += !ok;
-    printf("%s %s\n", id, ok ? "holds" : "fails   <-- WRONG");
-}
-
-static const void *at(uintptr_t a) { return reinterpret_cast<const void *>(a); }
 static const unsigned char g_classes[3] = { 1, 0, 1 };
 
 static ffgpu_motion_spec good_spec()
@@ -51,7 +25,7 @@ template <class Fn> static void spec(const char *id, int want_rc, const char *wa
     change(sp);
     g_err[0] = 0;
     MotionPlan pl;
-    line(id, ffgpu_motion_spec_plan("op", &sp, pl), want_rc, want_msg);
+    line_nonneg(id, ffgpu_motion_spec_plan("op", &sp, pl), want_rc, want_msg);
 }
 
 struct UArgs {
@@ -86,7 +60,7 @@ template <class Fn> static void uargs(const char *id, bool nv12, int want_rc, co
     const ffgpu_motion_spec *sp = a.have_spec ? &a.spec : nullptr;
     if (nv12) rc = ffgpu_motion_update_args_check("op", a.have_targets ? a.nv.data() : nullptr, a.ntargets, st, sp, at(a.state), a.nstreams, at(a.rows), pl, tab, round);
     else      rc = ffgpu_motion_update_args_check("op", a.have_targets ? a.bgr.data() : nullptr, a.ntargets, st, sp, at(a.state), a.nstreams, at(a.rows), pl, tab, round);
-    line(id, rc, want_rc, want_msg);
+    line_nonneg(id, rc, want_rc, want_msg);
     if (rc >= 0 && want_rc >= 0)                                                   // streams 0 2 -1 0 (1, skipped) 0: three rounds, the skipped ones in round 0
         fact(id, rc == 3 && tab.size() == 6 && round == std::vector<int>({ 0, 0, 0, 1, 0, 2 }) && tab[0].p0 && tab[0].first == 0 && !tab[2].p0 && tab[2].first == -1 &&
                  !tab[4].p0 && tab[4].first == 1 && tab[5].first == 0 && tab[0].w == 65 && tab[0].h == 33 && tab[5].w == 65 && tab[0].pitch == (nv12 ? 65 : 200));
@@ -105,8 +79,8 @@ template <class Fn> static void gargs(const char *id, int want_rc, const char *w
     change(a);
     g_err[0] = 0;
     MotionPlan pl;
-    line(id, ffgpu_motion_gate_args_check("op", a.have_streams ? a.streams.data() : nullptr, a.ntargets, a.have_spec ? &a.spec : nullptr, at(a.state), a.nstreams, at(a.words),
-                                          at(a.out_recs), at(a.out_lists), pl), want_rc, want_msg);
+    line_nonneg(id, ffgpu_motion_gate_args_check("op", a.have_streams ? a.streams.data() : nullptr, a.ntargets, a.have_spec ? &a.spec : nullptr, at(a.state), a.nstreams, at(a.words),
+                                                 at(a.out_recs), at(a.out_lists), pl), want_rc, want_msg);
 }
 
 int main()
@@ -135,14 +109,14 @@ int main()
         ffgpu_motion_spec sp = good_spec();
         MotionPlan pl;
         g_err[0] = 0;
-        line("plan.spec", ffgpu_motion_spec_plan("op", &sp, pl), 0, "");
+        line_nonneg("plan.spec", ffgpu_motion_spec_plan("op", &sp, pl), 0, "");
         fact("plan.spec_values", pl.lay.w == 65 && pl.lay.h == 33 && pl.lay.cell_log2 == 4 && pl.lay.gw == 5 && pl.lay.gh == 3 && pl.lay.pitch == 72 && pl.threshold == 20 &&
                                  pl.learn_shift == 4 && pl.learn_shift_changed == 8 && pl.min_pixels == 16 && pl.cover == 64 && pl.warmup == 30 && pl.invert == 1 &&
                                  pl.min_score == 0.25f && pl.nclasses == 0);
         sp.classes = g_classes; sp.nclasses = 3;
-        line("plan.classes", ffgpu_motion_spec_plan("op", &sp, pl), 0, "");
+        line_nonneg("plan.classes", ffgpu_motion_spec_plan("op", &sp, pl), 0, "");
         fact("plan.classes_values", pl.nclasses == 3 && pl.classes[0] == 1 && pl.classes[1] == 0 && pl.classes[2] == 1 && pl.classes[3] == 0);
-        line("plan.null_spec", ffgpu_motion_spec_plan("op", nullptr, pl), -1, "NULL spec");
+        line_nonneg("plan.null_spec", ffgpu_motion_spec_plan("op", nullptr, pl), -1, "NULL spec");
     }
 
     spec("spec.good", 0, "", [](ffgpu_motion_spec &) {});
@@ -224,6 +198,5 @@ int main()
     gargs("gate.stream_low", -1, "target 3: stream -2", [](GArgs &a) { a.streams[3] = -2; });
     gargs("gate.lists_without_records", -1, "d_out_lists without d_out_records", [](GArgs &a) { a.out_recs = 0; });
 
-    printf("motion_driver: %d cases, %d wrong\n", g_cases, g_wrong);
-    return g_wrong ? 1 : 0;
+    return finish("motion_driver");
 }

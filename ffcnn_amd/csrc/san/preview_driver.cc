@@ -2,38 +2,11 @@
 // a pane resolved into its region, image and bars, the wall's layout, the argument checks with the overlap test and the planes of a call, on good and
 // hostile arguments.  One line per case: id, return value, message.  The last line is "preview_driver: N cases, 0 wrong".  Nothing of HIP: the
 // addresses are made up and never followed.
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include <limits>
 #include "../ffgpu_preview_host.hpp"
-
-static char g_err[512];
-extern "C" void ffgpu_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-
-static int g_cases, g_wrong;
-static void line(const char *id, int rc, int want_rc, const char *want_msg)
-{
-    const bool ok = (want_rc < 0 ? rc == want_rc : rc >= 0) && (rc >= 0 || strstr(g_err, want_msg));
-    g_cases++;
-    g_wrong += !ok;
-    printf("%s %d %s%s\n", id, rc, rc < 0 ? g_err : "", ok ? "" : "   <-- WRONG");
-}
-static void fact(const char *id, bool ok)
-{
-    g_cases++;
-    g_wrong += !ok;
-    printf("%s %s\n", id, ok ? "holds" : "fails   <-- WRONG");
-}
-
-static const unsigned char *at(uintptr_t a) { return reinterpret_cast<const unsigned char *>(a); }
+#include "driver.hpp"
 
 static ffgpu_preview_spec good_spec()
 {
@@ -47,7 +20,7 @@ template <class Fn> static void spec(const char *id, int want_rc, const char *wa
     ffgpu_preview_spec sp = good_spec();
     change(sp);
     g_err[0] = 0;
-    line(id, ffgpu_preview_spec_check_host("op", &sp), want_rc, want_msg);
+    line_nonneg(id, ffgpu_preview_spec_check_host("op", &sp), want_rc, want_msg);
 }
 
 // resolve of one pane of a 100 x 60 frame into a 50 x 40 surface
@@ -58,7 +31,7 @@ static bool rect(const char *id, int fit, bool nv12, ffgpu_preview_pane p, int w
     int out[8] = { 0 };
     g_err[0] = 0;
     const int rc = ffgpu_preview_rect_host("op", 100, 60, 50, 40, &p, &sp, nv12, out);
-    line(id, rc, want_rc, want_msg);
+    line_nonneg(id, rc, want_rc, want_msg);
     if (rc == 0 && !want.empty()) fact(id, std::vector<int>(out, out + 8) == want);
     return rc == 0;
 }
@@ -77,10 +50,10 @@ struct Call {
         for (int k = 0; k < 4; k++) {
             memset(&sb[k], 0, sizeof sb[k]); memset(&db[k], 0, sizeof db[k]); memset(&sn[k], 0, sizeof sn[k]); memset(&dn[k], 0, sizeof dn[k]);
             memset(&panes[k], 0, sizeof panes[k]);
-            sb[k].bgr = at(0x10001 + 0x10000 * k); sb[k].w = 64 + k; sb[k].h = 48; sb[k].pitch = 3 * (64 + k) + 5;
-            sn[k].y = at(0x10001 + 0x10000 * k); sn[k].uv = at(0x18000 + 0x10000 * k); sn[k].w = 64 + k; sn[k].h = 48;
-            db[k].bgr = at(0x90003); db[k].w = 40; db[k].h = 30;
-            dn[k].y = at(0x90003); dn[k].uv = at(0x98000); dn[k].w = 40; dn[k].h = 30;
+            sb[k].bgr = bytes_at(0x10001 + 0x10000 * k); sb[k].w = 64 + k; sb[k].h = 48; sb[k].pitch = 3 * (64 + k) + 5;
+            sn[k].y = bytes_at(0x10001 + 0x10000 * k); sn[k].uv = bytes_at(0x18000 + 0x10000 * k); sn[k].w = 64 + k; sn[k].h = 48;
+            db[k].bgr = bytes_at(0x90003); db[k].w = 40; db[k].h = 30;
+            dn[k].y = bytes_at(0x90003); dn[k].uv = bytes_at(0x98000); dn[k].w = 40; dn[k].h = 30;
             panes[k].dx = 20 * (k & 1); panes[k].dy = 16 * (k >> 1); panes[k].dw = 18; panes[k].dh = 14;
         }
         sb[2].bgr = nullptr; sn[2].y = nullptr;                                      // a skipped pane
@@ -98,7 +71,7 @@ template <class Fn> static void call(const char *id, bool nv12, int want_rc, con
     const ffgpu_preview_spec *sp = c.have_spec ? &c.spec : nullptr;
     if (nv12) rc = ffgpu_preview_args_check("op", c.have_srcs ? c.sn.data() : nullptr, c.have_dsts ? c.dn.data() : nullptr, pp, c.npanes, sp, jobs);
     else      rc = ffgpu_preview_args_check("op", c.have_srcs ? c.sb.data() : nullptr, c.have_dsts ? c.db.data() : nullptr, pp, c.npanes, sp, jobs);
-    line(id, rc, want_rc, want_msg);
+    line_nonneg(id, rc, want_rc, want_msg);
     if (rc == 0 && want_rc == 0 && c.npanes == 4) {                                  // three live panes; NV12: a U V plane of half the size for each
         bool ok = jobs[0].size() == 3 && jobs[1].size() == (nv12 ? 3u : 0u) && jobs[0][0].pane == 0 && jobs[0][1].pane == 1 && jobs[0][2].pane == 3;
         if (ok) {
@@ -130,7 +103,7 @@ int main()
     spec("spec.fill3", -1, "fill[3] must be 0", [](ffgpu_preview_spec &s) { s.fill[3] = 1; });
     spec("spec.reserved", -1, "reserved must be 0", [](ffgpu_preview_spec &s) { s.reserved = 1; });
     g_err[0] = 0;
-    line("spec.null", ffgpu_preview_spec_check_host("op", nullptr), -1, "NULL spec");
+    line_nonneg("spec.null", ffgpu_preview_spec_check_host("op", nullptr), -1, "NULL spec");
 
     // resolve: 100 x 60 into 50 x 40
     rect("rect.default_stretch", 0, false, { 0, 0, 0, 0, 0, 0, 0, 0 }, 0, "", { 0, 0, 100, 60, 0, 0, 50, 40 });
@@ -157,17 +130,17 @@ int main()
         memset(&p, 0, sizeof p);
         int out[8];
         g_err[0] = 0;
-        line("rect.side_8193", ffgpu_preview_rect_host("op", 8193, 10, 50, 40, &p, &sp, 0, out), -1, "a source region of 8193 x 10 (1..8192 each)");
-        line("rect.side_8192", ffgpu_preview_rect_host("op", 8192, 8192, 8192, 8192, &p, &sp, 0, out), 0, "");
+        line_nonneg("rect.side_8193", ffgpu_preview_rect_host("op", 8193, 10, 50, 40, &p, &sp, 0, out), -1, "a source region of 8193 x 10 (1..8192 each)");
+        line_nonneg("rect.side_8192", ffgpu_preview_rect_host("op", 8192, 8192, 8192, 8192, &p, &sp, 0, out), 0, "");
         fact("rect.side_8192", out[2] == 8192 && out[6] == 8192 && out[7] == 8192);
-        line("rect.one", ffgpu_preview_rect_host("op", 1, 1, 1, 1, &p, &sp, 1, out), 0, "");
+        line_nonneg("rect.one", ffgpu_preview_rect_host("op", 1, 1, 1, 1, &p, &sp, 1, out), 0, "");
         fact("rect.one", out[2] == 1 && out[3] == 1 && out[4] == 0 && out[5] == 0 && out[6] == 1 && out[7] == 1);
-        line("rect.null_pane", ffgpu_preview_rect_host("op", 1, 1, 1, 1, nullptr, &sp, 0, out), -1, "NULL pane");
-        line("rect.null_out", ffgpu_preview_rect_host("op", 1, 1, 1, 1, &p, &sp, 0, nullptr), -1, "NULL out");
-        line("rect.null_spec", ffgpu_preview_rect_host("op", 1, 1, 1, 1, &p, nullptr, 0, out), -1, "NULL spec");
-        line("rect.no_frame", ffgpu_preview_rect_host("op", 0, 1, 1, 1, &p, &sp, 0, out), -1, "a frame of 0 x 1 into a surface of 1 x 1");
+        line_nonneg("rect.null_pane", ffgpu_preview_rect_host("op", 1, 1, 1, 1, nullptr, &sp, 0, out), -1, "NULL pane");
+        line_nonneg("rect.null_out", ffgpu_preview_rect_host("op", 1, 1, 1, 1, &p, &sp, 0, nullptr), -1, "NULL out");
+        line_nonneg("rect.null_spec", ffgpu_preview_rect_host("op", 1, 1, 1, 1, &p, nullptr, 0, out), -1, "NULL spec");
+        line_nonneg("rect.no_frame", ffgpu_preview_rect_host("op", 0, 1, 1, 1, &p, &sp, 0, out), -1, "a frame of 0 x 1 into a surface of 1 x 1");
         sp.fit = 7;
-        line("rect.bad_fit", ffgpu_preview_rect_host("op", 1, 1, 1, 1, &p, &sp, 0, out), -1, "fit 7 is neither");
+        line_nonneg("rect.bad_fit", ffgpu_preview_rect_host("op", 1, 1, 1, 1, &p, &sp, 0, out), -1, "fit 7 is neither");
     }
 
     // the grid
@@ -175,20 +148,20 @@ int main()
         ffgpu_preview_pane g[8];
         memset(g, 0xff, sizeof g);
         g_err[0] = 0;
-        line("grid.2x3", ffgpu_preview_grid_host("op", 6, 2, 97, 61, 2, 0, g), 0, "");
+        line_nonneg("grid.2x3", ffgpu_preview_grid_host("op", 6, 2, 97, 61, 2, 0, g), 0, "");
         fact("grid.2x3", g[0].dx == 2 && g[0].dy == 2 && g[0].dw == 45 && g[0].dh == 17 && g[5].dx == 49 && g[5].dy == 40 && g[5].sx == 0 && g[5].sw == 0 && g[5].sh == 0);
-        line("grid.nv12", ffgpu_preview_grid_host("op", 5, 3, 97, 61, 2, 1, g), 0, "");
+        line_nonneg("grid.nv12", ffgpu_preview_grid_host("op", 5, 3, 97, 61, 2, 1, g), 0, "");
         fact("grid.nv12", g[4].dx == 32 && g[4].dy == 30 && g[4].dw == 28 && g[4].dh == 26);                                      // cw 29 -> 28, ch 27 -> 26
-        line("grid.one", ffgpu_preview_grid_host("op", 1, 1, 1, 1, 0, 0, g), 0, "");
-        line("grid.npanes_0", ffgpu_preview_grid_host("op", 0, 1, 10, 10, 0, 0, g), -1, "0 panes in 1 columns");
-        line("grid.cols_0", ffgpu_preview_grid_host("op", 4, 0, 10, 10, 0, 0, g), -1, "4 panes in 0 columns");
-        line("grid.cols_above", ffgpu_preview_grid_host("op", 4, 5, 10, 10, 0, 0, g), -1, "4 panes in 5 columns");
-        line("grid.gap_neg", ffgpu_preview_grid_host("op", 4, 2, 10, 10, -1, 0, g), -1, "gap -1 (from 0)");
-        line("grid.gap_odd_nv12", ffgpu_preview_grid_host("op", 4, 2, 10, 10, 1, 1, g), -1, "gap 1 (from 0, even for NV12)");
-        line("grid.no_room", ffgpu_preview_grid_host("op", 4, 2, 10, 10, 4, 0, g), -1, "2 x 2 panes with gap 4 leave no room in 10 x 10");
-        line("grid.no_room_nv12", ffgpu_preview_grid_host("op", 4, 2, 3, 10, 0, 1, g), -1, "leave no room in 3 x 10");
-        line("grid.gap_max", ffgpu_preview_grid_host("op", 4, 2, 10, 10, imax, 0, g), -1, "leave no room");
-        line("grid.null_out", ffgpu_preview_grid_host("op", 4, 2, 10, 10, 0, 0, nullptr), -1, "NULL out");
+        line_nonneg("grid.one", ffgpu_preview_grid_host("op", 1, 1, 1, 1, 0, 0, g), 0, "");
+        line_nonneg("grid.npanes_0", ffgpu_preview_grid_host("op", 0, 1, 10, 10, 0, 0, g), -1, "0 panes in 1 columns");
+        line_nonneg("grid.cols_0", ffgpu_preview_grid_host("op", 4, 0, 10, 10, 0, 0, g), -1, "4 panes in 0 columns");
+        line_nonneg("grid.cols_above", ffgpu_preview_grid_host("op", 4, 5, 10, 10, 0, 0, g), -1, "4 panes in 5 columns");
+        line_nonneg("grid.gap_neg", ffgpu_preview_grid_host("op", 4, 2, 10, 10, -1, 0, g), -1, "gap -1 (from 0)");
+        line_nonneg("grid.gap_odd_nv12", ffgpu_preview_grid_host("op", 4, 2, 10, 10, 1, 1, g), -1, "gap 1 (from 0, even for NV12)");
+        line_nonneg("grid.no_room", ffgpu_preview_grid_host("op", 4, 2, 10, 10, 4, 0, g), -1, "2 x 2 panes with gap 4 leave no room in 10 x 10");
+        line_nonneg("grid.no_room_nv12", ffgpu_preview_grid_host("op", 4, 2, 3, 10, 0, 1, g), -1, "leave no room in 3 x 10");
+        line_nonneg("grid.gap_max", ffgpu_preview_grid_host("op", 4, 2, 10, 10, imax, 0, g), -1, "leave no room");
+        line_nonneg("grid.null_out", ffgpu_preview_grid_host("op", 4, 2, 10, 10, 0, 0, nullptr), -1, "NULL out");
     }
 
     for (int nv12 = 0; nv12 < 2; nv12++) {
@@ -218,14 +191,14 @@ int main()
         call(n ? "nv12.overlap" : "bgr.overlap", n, -1, "panes 0 and 3 overlap in one destination surface", [](Call &c) { c.panes[3].dx = 16; c.panes[3].dy = 12; });
         call(n ? "nv12.touching" : "bgr.touching", n, 0, "", [](Call &c) { c.panes[3].dx = 18; c.panes[3].dy = 14; });
         call(n ? "nv12.skipped_sizes" : "bgr.skipped_sizes", n, 0, "", [](Call &c) { c.panes[2].sw = -7; c.panes[2].dw = 9000; c.panes[2].dx = 1; });
-        call(n ? "nv12.other_surface" : "bgr.other_surface", n, 0, "", [](Call &c) { c.db[3].bgr = at(0xa0000); c.dn[3].y = at(0xa0000); c.dn[3].uv = at(0xa8000); c.panes[3].dx = 0; c.panes[3].dy = 0; });
+        call(n ? "nv12.other_surface" : "bgr.other_surface", n, 0, "", [](Call &c) { c.db[3].bgr = bytes_at(0xa0000); c.dn[3].y = bytes_at(0xa0000); c.dn[3].uv = bytes_at(0xa8000); c.panes[3].dx = 0; c.panes[3].dy = 0; });
     }
     call("bgr.src_pitch", false, -1, "source 0: pitch 100 is below 3 w = 192", [](Call &c) { c.sb[0].pitch = 100; });
     call("bgr.dst_pitch", false, -1, "destination 0: pitch 100 is below 3 w = 120", [](Call &c) { c.db[0].pitch = 100; });
     call("bgr.odd_sx_is_fine", false, 0, "", [](Call &c) { c.panes[0].sx = 3; c.panes[0].sy = 1; c.panes[0].sw = 11; c.panes[0].sh = 9; c.panes[0].dx = 1; });
     call("nv12.pitch_y", true, -1, "source 0: pitch_y 10 is below w = 64", [](Call &c) { c.sn[0].pitch_y = 10; });
-    call("nv12.uv_odd_src", true, -1, "is odd (U V pairs are read", [](Call &c) { c.sn[0].uv = at(0x18001); });
-    call("nv12.uv_odd_dst", true, -1, "is odd (U V pairs are written", [](Call &c) { c.dn[1].uv = at(0x98001); });
+    call("nv12.uv_odd_src", true, -1, "is odd (U V pairs are read", [](Call &c) { c.sn[0].uv = bytes_at(0x18001); });
+    call("nv12.uv_odd_dst", true, -1, "is odd (U V pairs are written", [](Call &c) { c.dn[1].uv = bytes_at(0x98001); });
     call("nv12.matrix", true, -1, "destination 1: matrix 4", [](Call &c) { c.dn[1].matrix = 4; });
     call("nv12.odd_sx", true, -1, "pane 1: NV12 wants even sx, sy, dx, dy, not (3, 4) and (20, 0)", [](Call &c) { c.panes[1].sx = 3; });
     call("nv12.odd_dy", true, -1, "pane 3: NV12 wants even sx, sy, dx, dy, not (0, 0) and (20, 17)", [](Call &c) { c.panes[3].dy = 17; c.panes[3].dh = 13; });
@@ -238,6 +211,5 @@ int main()
         fact("tiles", ffgpu_preview_tiles(j, 1) == 1 && ffgpu_preview_tiles(j, 2) == 9 && PREVIEW_TW == 64 && PREVIEW_TH == 16 && PREVIEW_ARG_JOBS == 32);
     }
 
-    printf("preview_driver: %d cases, %d wrong\n", g_cases, g_wrong);
-    return g_wrong ? 1 : 0;
+    return finish("preview_driver");
 }

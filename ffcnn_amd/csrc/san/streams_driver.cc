@@ -2,31 +2,11 @@
 // ffgpu_streams_host.hpp's stream checks and the bytes a reset clears, and ffgpu_args.hpp's colours, palettes and class tables, each rejection with
 // its message.  (The grouping's cases are san/zones_driver.cc's, the entry table's san/track_driver.cc's.)  One line per case: id, return value, message
 // or result.  The last line is "streams_driver: N cases, 0 wrong".  Nothing of HIP: the addresses are made up and never followed.
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <limits>
 #include "../ffgpu_streams_host.hpp"
 #include "../ffgpu_args.hpp"
-
-static char g_err[512];
-extern "C" void ffgpu_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-
-static int g_cases, g_wrong;
-static void line(const char *id, int rc, int want_rc, const char *want_msg, bool also = true)
-{
-    const bool ok = rc == want_rc && (rc == 0 || strstr(g_err, want_msg)) && also;
-    g_cases++;
-    g_wrong += !ok;
-    printf("%s %d %s%s\n", id, rc, rc ? g_err : "", ok ? "" : "   <-- WRONG");
-}
-static const void *at(uintptr_t a) { return reinterpret_cast<const void *>(a); }
+#include "driver.hpp"
 
 static void span(const char *id, uintptr_t state, size_t all, int nstreams, int which, int want_rc, const char *want_msg, size_t want_off = 0, size_t want_len = 0)
 {
@@ -53,7 +33,7 @@ int main()
         { "three.state_8", 5, 3, 0x2008, -1, "16-byte aligned" }, { "three.ntargets_first", 0, 0, 0x2001, -1, "0 targets" },
         { "three.nstreams_second", 5, 0, 0x2001, -1, "nstreams 0" },
     };
-    for (const auto &c : three) { g_err[0] = 0; line(c.id, ffgpu_streams_check("op", c.nt, c.ns, at(c.st)), c.rc, c.msg); }
+    for (const auto &c : three) { g_err[0] = 0; line_exact(c.id, ffgpu_streams_check("op", c.nt, c.ns, at(c.st)), c.rc, c.msg); }
 
     // every target's stream
     struct { const char *id; int s[5]; int ns, rc; const char *msg; } range[] = {
@@ -63,9 +43,9 @@ int main()
         { "range.min", { 0, std::numeric_limits<int>::min(), 0, 0, 0 }, 3, -1, "target 1: stream -2147483648" },
         { "range.max", { 0, 0, std::numeric_limits<int>::max(), 0, 0 }, 65536, -1, "target 2: stream 2147483647" },
     };
-    for (const auto &c : range) { g_err[0] = 0; line(c.id, ffgpu_stream_range_check("op", c.s, 5, c.ns), c.rc, c.msg); }
+    for (const auto &c : range) { g_err[0] = 0; line_exact(c.id, ffgpu_stream_range_check("op", c.s, 5, c.ns), c.rc, c.msg); }
     g_err[0] = 0;
-    line("range.none", ffgpu_stream_range_check("op", nullptr, 0, 3), 0, "");                                       // (no target: nothing is read)
+    line_exact("range.none", ffgpu_stream_range_check("op", nullptr, 0, 3), 0, "");                                       // (no target: nothing is read)
 
     // the bytes a reset clears
     span("span.all", 0x2000, 3 * 256, 3, -1, 0, "", 0, 768);
@@ -113,15 +93,15 @@ int main()
         auto rest_zero = [&](int from) { for (int k = from; k < 256; k++) if (pal[k]) return false; return true; };
         memset(pal, 0xee, sizeof pal); g_err[0] = 0;
         int rc = ffgpu_palette_plan("op", nullptr, 0, color, pal, &npal);
-        line("palette.single_colour", rc, 0, "", npal == 1 && pal[0] == 0x030201u && rest_zero(1));
+        line_exact("palette.single_colour", rc, 0, "", npal == 1 && pal[0] == 0x030201u && rest_zero(1));
         memset(pal, 0xee, sizeof pal); g_err[0] = 0;
         rc = ffgpu_palette_plan("op", p3, 3, color, pal, &npal);
-        line("palette.three", rc, 0, "", npal == 3 && pal[0] == 0xf2f1f0u && pal[2] == 0xfaf9f8u && rest_zero(3));
+        line_exact("palette.three", rc, 0, "", npal == 3 && pal[0] == 0xf2f1f0u && pal[2] == 0xfaf9f8u && rest_zero(3));
         memset(pal, 0xee, sizeof pal); g_err[0] = 0;
         rc = ffgpu_palette_plan("op", p256, 256, nullptr, pal, &npal);
         bool all = npal == 256;
         for (int k = 0; k < 256; k++) all = all && pal[k] == ((unsigned)p256[4 * k] | (unsigned)p256[4 * k + 1] << 8 | (unsigned)p256[4 * k + 2] << 16);
-        line("palette.256_no_colour", rc, 0, "", all);
+        line_exact("palette.256_no_colour", rc, 0, "", all);
         struct { const char *id; const unsigned char *p; int n; const char *msg; } bad[] = {
             { "palette.null_with_count", nullptr, 3, "op: npalette 3 (0 with a NULL palette, else 1..256)" }, { "palette.null_with_neg", nullptr, -1, "npalette -1" },
             { "palette.count_0", p3, 0, "npalette 0 (0 with a NULL palette, else 1..256)" }, { "palette.count_neg", p3, -2, "npalette -2" },
@@ -130,7 +110,7 @@ int main()
         for (const auto &c : bad) {
             memset(pal, 0xee, sizeof pal); npal = -7; g_err[0] = 0;
             rc = ffgpu_palette_plan("op", c.p, c.n, color, pal, &npal);
-            line(c.id, rc, -1, c.msg, npal == -7 && pal[0] == 0xeeeeeeeeu && pal[255] == 0xeeeeeeeeu);              // a rejected palette writes nothing
+            line_exact(c.id, rc, -1, c.msg, npal == -7 && pal[0] == 0xeeeeeeeeu && pal[255] == 0xeeeeeeeeu);              // a rejected palette writes nothing
         }
         free(p256); free(p3);
     }
@@ -144,9 +124,8 @@ int main()
             { "classes.count_0", c1, 0, -1, "nclasses 0 (0 with NULL classes, else 1..256)" }, { "classes.count_neg", c1, -5, -1, "nclasses -5" },
             { "classes.count_257", c1, 257, -1, "nclasses 257" }, { "classes.count_min", c1, std::numeric_limits<int>::min(), -1, "nclasses -2147483648" },
         };
-        for (const auto &c : tab) { g_err[0] = 0; line(c.id, ffgpu_class_table_check("op", c.p, c.n), c.rc, c.msg); }
+        for (const auto &c : tab) { g_err[0] = 0; line_exact(c.id, ffgpu_class_table_check("op", c.p, c.n), c.rc, c.msg); }
         free(c1);
     }
-    printf("streams_driver: %d cases, %d wrong\n", g_cases, g_wrong);
-    return g_wrong ? 1 : 0;
+    return finish("streams_driver");
 }

@@ -2,38 +2,12 @@
 // against the properties include/ffcnn_hip.h states, the caption spec resolved into its plan, and the argument checks of the rasteriser and the two
 // composers on good and hostile arguments.  One line per case: id, return value, message.  The last line is "text_driver: N cases, 0 wrong".  Nothing of
 // HIP: the addresses are made up and never followed.
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include <limits>
 #include "../ffgpu_text_host.hpp"
+#include "driver.hpp"
 
-static char g_err[512];
-extern "C" void ffgpu_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-
-static int g_cases, g_wrong;
-static void line(const char *id, int rc, int want_rc, const char *want_msg)
-{
-    const bool ok = rc == want_rc && (rc == 0 || strstr(g_err, want_msg));
-    g_cases++;
-    g_wrong += !ok;
-    printf("%s %d %s%s\n", id, rc, rc ? g_err : "", ok ? "" : "   <-- WRONG");
-}
-static void fact(const char *id, bool ok)
-{
-    g_cases++;
-    g_wrong += !ok;
-    printf("%s %s\n", id, ok ? "holds" : "fails   <-- WRONG");
-}
-
-static const void *at(uintptr_t a) { return reinterpret_cast<const void *>(a); }
 static const unsigned char g_palette[3 * 4] = { 1, 2, 3, 9, 4, 5, 6, 9, 7, 8, 9, 9 };
 
 static ffgpu_caption_spec good_spec()
@@ -59,7 +33,7 @@ template <class Fn> static void boxes(const char *id, int want_rc, const char *w
     change(a);
     g_err[0] = 0;
     CaptionPlan pl;
-    line(id, ffgpu_caption_boxes_args_check("op", a.have_spec ? &a.spec : nullptr, at(a.ids), at(a.items), a.items_stride, pl), want_rc, want_msg);
+    line_exact(id, ffgpu_caption_boxes_args_check("op", a.have_spec ? &a.spec : nullptr, at(a.ids), at(a.items), a.items_stride, pl), want_rc, want_msg);
 }
 
 struct Scene {
@@ -75,9 +49,9 @@ template <class Fn> static void scene(const char *id, int want_rc, const char *w
     change(a);
     g_err[0] = 0;
     CaptionPlan pl;
-    line(id, ffgpu_caption_scene_args_check("op", at(a.scenes), at(a.state), a.nstreams, a.capacity, at(a.events), a.events_stride,
-                                            a.have_streams ? a.streams.data() : nullptr, a.ntargets, a.have_spec ? &a.spec : nullptr, at(a.items), a.items_stride, pl),
-         want_rc, want_msg);
+    line_exact(id, ffgpu_caption_scene_args_check("op", at(a.scenes), at(a.state), a.nstreams, a.capacity, at(a.events), a.events_stride,
+                                                  a.have_streams ? a.streams.data() : nullptr, a.ntargets, a.have_spec ? &a.spec : nullptr, at(a.items), a.items_stride, pl),
+               want_rc, want_msg);
 }
 
 struct Text { uintptr_t items = 0x4000, targets = 0x5000; int items_stride = 256, ntargets = 3; };
@@ -86,7 +60,7 @@ template <class Fn> static void text(const char *id, int want_rc, const char *wa
     Text a;
     change(a);
     g_err[0] = 0;
-    line(id, ffgpu_draw_text_args_check("op", at(a.items), a.items_stride, at(a.targets), a.ntargets), want_rc, want_msg);
+    line_exact(id, ffgpu_draw_text_args_check("op", at(a.items), a.items_stride, at(a.targets), a.ntargets), want_rc, want_msg);
 }
 
 int main()
@@ -122,14 +96,14 @@ int main()
         ffgpu_caption_spec sp = good_spec();
         CaptionPlan pl;
         g_err[0] = 0;
-        line("plan.color", ffgpu_caption_spec_check("op", &sp, true, pl), 0, "");
+        line_exact("plan.color", ffgpu_caption_spec_check("op", &sp, true, pl), 0, "");
         fact("plan.color_values", pl.npal == 1 && pl.pal[0] == 0x1e140au && pl.pal[1] == 0 && pl.fg == 0xfcfbfau && pl.scale == 2 && pl.nnames == 80 &&
                                   pl.identity == FFGPU_ZONES_IDS && pl.min_score == 0.25f && pl.flags == 15 && pl.d_names == at(0x7000));
         sp.palette = g_palette; sp.npalette = 3;
-        line("plan.palette", ffgpu_caption_spec_check("op", &sp, true, pl), 0, "");
+        line_exact("plan.palette", ffgpu_caption_spec_check("op", &sp, true, pl), 0, "");
         fact("plan.palette_values", pl.npal == 3 && pl.pal[0] == 0x030201u && pl.pal[1] == 0x060504u && pl.pal[2] == 0x090807u && pl.pal[3] == 0);
         sp.min_score = nan; sp.flags = 0; sp.identity = 7; sp.nnames = -1;              // what the scene composer ignores
-        line("plan.scene_ignores", ffgpu_caption_spec_check("op", &sp, false, pl), 0, "");
+        line_exact("plan.scene_ignores", ffgpu_caption_spec_check("op", &sp, false, pl), 0, "");
         fact("plan.scene_values", pl.npal == 3 && pl.flags == 0 && pl.nnames == 0 && pl.d_names == nullptr && pl.identity == 0);
     }
 
@@ -207,6 +181,5 @@ int main()
     text("text.ntargets_0", -1, "0 targets", [](Text &a) { a.ntargets = 0; });
     text("text.ntargets_neg", -1, "-5 targets", [](Text &a) { a.ntargets = -5; });
 
-    printf("text_driver: %d cases, %d wrong\n", g_cases, g_wrong);
-    return g_wrong ? 1 : 0;
+    return finish("text_driver");
 }

@@ -2,30 +2,11 @@
 // tracker's spec and arguments, the state's size at its limits and outside them, and a launch's entry table (ffgpu_streams_host.hpp, at the tracker's
 // 128 records per launch) against its definition.  One line per case: id, return value, message.  The last line is "track_driver: N cases, 0 wrong".
 // Nothing of HIP: the addresses are made up and never followed.
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include <limits>
 #include "../ffgpu_track_host.hpp"
-
-static char g_err[512];
-extern "C" void ffgpu_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-
-static int g_cases, g_wrong;
-static void line(const char *id, int rc, int want_rc, const char *want_msg)
-{
-    const bool ok = rc == want_rc && (rc == 0 || strstr(g_err, want_msg));
-    g_cases++;
-    g_wrong += !ok;
-    printf("%s %d %s%s\n", id, rc, rc ? g_err : "", ok ? "" : "   <-- WRONG");
-}
+#include "driver.hpp"
 
 static ffgpu_track_spec good_spec()
 {
@@ -34,7 +15,6 @@ static ffgpu_track_spec good_spec()
     sp.capacity = 16; sp.max_missed = 2; sp.min_hits = 2; sp.iou_thresh = 0.25f; sp.min_score = 0.125f; sp.birth_score = 0.25f; sp.class_aware = 1;
     return sp;
 }
-static const void *at(uintptr_t a) { return reinterpret_cast<const void *>(a); }
 struct Args {
     std::vector<int> streams{ 0, 2, -1, 1, 0 };
     bool have_streams = true, have_spec = true;
@@ -47,8 +27,8 @@ template <class Fn> static void args(const char *id, int want_rc, const char *wa
     Args a;
     change(a);
     g_err[0] = 0;
-    line(id, ffgpu_track_args_check("op", a.have_streams ? a.streams.data() : nullptr, a.ntargets, a.have_spec ? &a.spec : nullptr, at(a.state), a.nstreams,
-                                    at(a.ids), at(a.orecs), at(a.olists)), want_rc, want_msg);
+    line_exact(id, ffgpu_track_args_check("op", a.have_streams ? a.streams.data() : nullptr, a.ntargets, a.have_spec ? &a.spec : nullptr, at(a.state), a.nstreams,
+                                          at(a.ids), at(a.orecs), at(a.olists)), want_rc, want_msg);
 }
 
 // a launch's table against its definition: the groups ascend by stream, a group's entries are its stream's records of the window in record order, every
@@ -162,6 +142,5 @@ int main()
         for (size_t i = 0; i < s.size(); i++) s[i] = (int)i;                          // every record its own stream: as many groups as entries
         entries("entries.all_distinct", s, 1, ENTRIES);
     }
-    printf("track_driver: %d cases, %d wrong\n", g_cases, g_wrong);
-    return g_wrong ? 1 : 0;
+    return finish("track_driver");
 }

@@ -1,38 +1,12 @@
 // trails_driver.cc -- ffgpu_trails_host.hpp on the CPU under AddressSanitizer + UBSan (`make trails`; tests/test_trails_abi.py): the state's size, the
 // trails spec resolved into its plan, and the argument checks the operator and the executor form share, on good and hostile arguments.  One line per
 // case: id, return value, message.  The last line is "trails_driver: N cases, 0 wrong".  Nothing of HIP: the addresses are made up and never followed.
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include <limits>
 #include "../ffgpu_trails_host.hpp"
+#include "driver.hpp"
 
-static char g_err[512];
-extern "C" void ffgpu_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-
-static int g_cases, g_wrong;
-static void line(const char *id, int rc, int want_rc, const char *want_msg)
-{
-    const bool ok = rc == want_rc && (rc == 0 || strstr(g_err, want_msg));
-    g_cases++;
-    g_wrong += !ok;
-    printf("%s %d %s%s\n", id, rc, rc ? g_err : "", ok ? "" : "   <-- WRONG");
-}
-static void fact(const char *id, bool ok)
-{
-    g_cases++;
-    g_wrong += !ok;
-    printf("%s %s\n", id, ok ? "holds" : "fails   <-- WRONG");
-}
-
-static const void *at(uintptr_t a) { return reinterpret_cast<const void *>(a); }
 static const unsigned char g_palette[3 * 4] = { 1, 2, 3, 9, 4, 5, 6, 9, 7, 8, 9, 9 };
 
 static ffgpu_trails_spec good_spec()
@@ -51,7 +25,7 @@ template <class Fn> static void spec(const char *id, int want_rc, const char *wa
     change(sp);
     g_err[0] = 0;
     TrailsPlan pl;
-    line(id, ffgpu_trails_spec_plan("op", &sp, pl), want_rc, want_msg);
+    line_exact(id, ffgpu_trails_spec_plan("op", &sp, pl), want_rc, want_msg);
 }
 
 struct Args {
@@ -67,9 +41,9 @@ template <class Fn> static void args(const char *id, int want_rc, const char *wa
     change(a);
     g_err[0] = 0;
     TrailsPlan pl;
-    line(id, ffgpu_trails_args_check("op", a.have_streams ? a.streams.data() : nullptr, a.ntargets, a.have_spec ? &a.spec : nullptr, at(a.state), a.nstreams, at(a.ids),
-                                     at(a.rows), at(a.items), a.items_stride, a.first_item, a.nitems, pl),
-         want_rc, want_msg);
+    line_exact(id, ffgpu_trails_args_check("op", a.have_streams ? a.streams.data() : nullptr, a.ntargets, a.have_spec ? &a.spec : nullptr, at(a.state), a.nstreams, at(a.ids),
+                                           at(a.rows), at(a.items), a.items_stride, a.first_item, a.nitems, pl),
+               want_rc, want_msg);
 }
 
 int main()
@@ -90,13 +64,13 @@ int main()
         ffgpu_trails_spec sp = good_spec();
         TrailsPlan pl;
         g_err[0] = 0;
-        line("plan.color", ffgpu_trails_spec_plan("op", &sp, pl), 0, "");
+        line_exact("plan.color", ffgpu_trails_spec_plan("op", &sp, pl), 0, "");
         fact("plan.color_values", pl.npal == 1 && pl.pal[0] == 0x1e140au && pl.pal[1] == 0 && pl.capacity == 16 && pl.max_missed == 2 && pl.identity == FFGPU_ZONES_IDS &&
                                   pl.flags == 3 && pl.min_score == 0.25f && pl.anchor == 1 && pl.points == 8 && pl.min_move == 3 && pl.thickness == 4 && pl.coast_dash == 2);
         sp.palette = g_palette; sp.npalette = 3;
-        line("plan.palette", ffgpu_trails_spec_plan("op", &sp, pl), 0, "");
+        line_exact("plan.palette", ffgpu_trails_spec_plan("op", &sp, pl), 0, "");
         fact("plan.palette_values", pl.npal == 3 && pl.pal[0] == 0x030201u && pl.pal[1] == 0x060504u && pl.pal[2] == 0x090807u && pl.pal[3] == 0);
-        line("plan.null_spec", ffgpu_trails_spec_plan("op", nullptr, pl), -1, "NULL spec");
+        line_exact("plan.null_spec", ffgpu_trails_spec_plan("op", nullptr, pl), -1, "NULL spec");
     }
 
     spec("spec.good", 0, "", [](ffgpu_trails_spec &) {});
@@ -167,6 +141,5 @@ int main()
     args("args.range_over", -1, "items 80 .. 512 lie outside a row of items_stride 512", [](Args &a) { a.nitems = 433; });
     args("args.range_overflow", -1, "lie outside a row", [&](Args &a) { a.first_item = imax; a.nitems = imax; });
 
-    printf("trails_driver: %d cases, %d wrong\n", g_cases, g_wrong);
-    return g_wrong ? 1 : 0;
+    return finish("trails_driver");
 }

@@ -1,30 +1,11 @@
 // zones_driver.cc -- ffgpu_zones_host.hpp on the CPU under AddressSanitizer + UBSan (`make zones`; tests/test_zones_abi.py): the scene check on good and
 // hostile scenes, the spec and argument checks, and the grouping of a launch's records by stream against its definition.  One line per case: id, return
 // value, message.  The last line is "zones_driver: N cases, 0 wrong".  Nothing of HIP: the addresses are made up and never followed.
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include <limits>
 #include "../ffgpu_zones_host.hpp"
-
-static char g_err[512];
-extern "C" void ffgpu_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-
-static int g_cases, g_wrong;
-static void line(const char *id, int rc, int want_rc, const char *want_msg)
-{
-    const bool ok = rc == want_rc && (rc == 0 || strstr(g_err, want_msg));
-    g_cases++;
-    g_wrong += !ok;
-    printf("%s %d %s%s\n", id, rc, rc ? g_err : "", ok ? "" : "   <-- WRONG");
-}
+#include "driver.hpp"
 
 static ffgpu_scene good_scene()
 {
@@ -45,7 +26,7 @@ template <class Fn> static void scene(const char *id, int want_rc, const char *w
     std::vector<ffgpu_scene> v(3, good_scene());
     change(v[1]);
     g_err[0] = 0;
-    line(id, ffgpu_scene_check_host(v.data(), 3), want_rc, want_msg);
+    line_exact(id, ffgpu_scene_check_host(v.data(), 3), want_rc, want_msg);
 }
 
 static ffgpu_zones_spec good_spec()
@@ -55,7 +36,6 @@ static ffgpu_zones_spec good_spec()
     sp.capacity = 16; sp.max_missed = 2; sp.identity = FFGPU_ZONES_IDS; sp.min_score = 0.25f; sp.gate_zone = 0xff;
     return sp;
 }
-static const void *at(uintptr_t a) { return reinterpret_cast<const void *>(a); }
 struct Args {
     std::vector<int> streams{ 0, 2, -1, 1, 0 };
     bool have_streams = true, have_spec = true;
@@ -68,8 +48,8 @@ template <class Fn> static void args(const char *id, int want_rc, const char *wa
     Args a;
     change(a);
     g_err[0] = 0;
-    line(id, ffgpu_zones_args_check("op", a.have_streams ? a.streams.data() : nullptr, a.ntargets, a.have_spec ? &a.spec : nullptr, at(a.scenes), at(a.state),
-                                    a.nstreams, at(a.ids), at(a.events), at(a.orecs), at(a.olists)), want_rc, want_msg);
+    line_exact(id, ffgpu_zones_args_check("op", a.have_streams ? a.streams.data() : nullptr, a.ntargets, a.have_spec ? &a.spec : nullptr, at(a.scenes), at(a.state),
+                                          a.nstreams, at(a.ids), at(a.events), at(a.orecs), at(a.olists)), want_rc, want_msg);
 }
 
 // the grouping against its definition: a stable sort by stream, groups of equal streams
@@ -118,8 +98,8 @@ int main()
     scene("scene.anchor_1", 0, "", [](ffgpu_scene &s) { s.anchor = 1; });
     scene("scene.reserved", -1, "scene 1: reserved", [](ffgpu_scene &s) { s.reserved = 1; });
     g_err[0] = 0;
-    line("scene.null", ffgpu_scene_check_host(nullptr, 1), -1, "NULL scenes");
-    { ffgpu_scene s = good_scene(); g_err[0] = 0; line("scene.n0", ffgpu_scene_check_host(&s, 0), -1, "0 scenes"); }
+    line_exact("scene.null", ffgpu_scene_check_host(nullptr, 1), -1, "NULL scenes");
+    { ffgpu_scene s = good_scene(); g_err[0] = 0; line_exact("scene.n0", ffgpu_scene_check_host(&s, 0), -1, "0 scenes"); }
 
     args("args.good", 0, "", [](Args &) {});
     args("args.no_outputs", 0, "", [](Args &a) { a.orecs = a.olists = 0; });
@@ -182,6 +162,5 @@ int main()
         for (size_t i = 0; i < s.size(); i++) s[i] = (int)i;                          // every record its own stream: as many groups as entries
         grouping("group.all_distinct", s, 1, ZONES_ARG_ENTRIES);
     }
-    printf("zones_driver: %d cases, %d wrong\n", g_cases, g_wrong);
-    return g_wrong ? 1 : 0;
+    return finish("zones_driver");
 }

@@ -4,15 +4,9 @@ and executor builders) -- on the CPU under AddressSanitizer + UndefinedBehaviorS
 to.  Every line is compared with a literal here.  The message formats below are the strings of the entry points as they stood before the checks were
 gathered in one header (ffgpu_exec.hip, ffgpu_draw.inc, ffgpu_crop.inc, ffgpu_track.inc, ffgpu_feature.inc of that commit), copied: a call with one
 bad argument reports what it always did, byte for byte.  A sanitizer report aborts the child: the test fails with it."""
-import os
-import subprocess
-
 import pytest
 
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "ffcnn_amd", "csrc")
-BIN = os.path.join(ROOT, "ffcnn_amd", "bin", "ffgpu_args_san")
+from sanrun import run_driver
 
 # the C format strings, `what` = "op"; NOUN is "frame" in the forward's messages and "target" in the draw's and the crop's
 NULL_BGR = "op: frame %d: NULL bgr"
@@ -115,12 +109,7 @@ WANT = _frames("fwd") + _frames("draw") + [
 
 @pytest.fixture(scope="module")
 def lines():
-    subprocess.check_call(["make", "-s", "-C", CSRC, "args"])
-    e = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([BIN], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e, timeout=120)
-    err = r.stderr.decode(errors="replace")
-    assert r.returncode == 0 and "Sanitizer" not in err and "runtime error" not in err, "rc %d\n%s" % (r.returncode, err[-3000:])
-    return r.stdout.decode().split("\n")[:-1]
+    return run_driver("args", "args")
 
 
 def test_every_case_line_for_line(lines):

@@ -11,12 +11,12 @@ import ctypes as C
 import hashlib
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from sanrun import check_summary, run_driver
 from captions import fuzzcases, textref
 
 SYMBOLS = ["ffgpu_font_builtin", "ffgpu_draw_text_bgr_dev", "ffgpu_draw_text_nv12_dev", "ffgpu_caption_boxes_dev", "ffgpu_exec_caption_bgr",
@@ -332,13 +332,8 @@ def test_captions_without_device(capi):
 def test_host_glue_under_the_sanitizers():
     """san/text_driver.cc: the built-in font's table, the caption spec's plan and every argument check of ffgpu_text_host.hpp on the CPU under
     ASan + UBSan, as a child process; the driver checks every case itself.  A sanitizer report aborts the child: the test fails with it."""
-    subprocess.check_call(["make", "-s", "-C", CSRC, "text"])
-    e = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([os.path.join(ROOT, "ffcnn_amd", "bin", "ffgpu_text_san")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e, timeout=120)
-    err, out = r.stderr.decode(errors="replace"), r.stdout.decode().split("\n")[:-1]
-    assert r.returncode == 0 and "Sanitizer" not in err and "runtime error" not in err, "rc %d\n%s" % (r.returncode, err[-3000:])
-    assert re.fullmatch(r"text_driver: (\d+) cases, 0 wrong", out[-1]) and int(out[-1].split()[1]) == len(out) - 1 >= 80, out[-1]
-    assert not any("WRONG" in ln for ln in out)
+    out = run_driver("text", "text")
+    check_summary(out, "text", 80)
     for ln in ("font.margins_empty holds", "font.space_is_the_only_empty_glyph holds", "font.ascii_pairwise_different holds", "font.other_codes_are_the_unknown_glyph holds",
                "boxes.null_spec -1 op: NULL spec", "boxes.null_items -1 op: NULL items", "boxes.stride_0 -1 op: items_stride 0 is outside 1..256",
                "boxes.stride_257 -1 op: items_stride 257 is outside 1..256", "boxes.min_score_nan -1 op: min_score nan is not in [0, 1]",

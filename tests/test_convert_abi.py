@@ -5,12 +5,12 @@ failing the way every entry point of the library does when no HIP device is visi
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from sanrun import check_summary, run_driver
 from convert import convertref as R
 
 SYMBOLS = ["ffgpu_convert_check", "ffgpu_convert_tile", "ffgpu_convert_bgr_dev", "ffgpu_convert_nv12_dev"]
@@ -57,13 +57,8 @@ def test_convert_check(capi):
 
 
 def test_host_glue_under_the_sanitizers():
-    csrc = os.path.join(ROOT, "ffcnn_amd", "csrc")
-    subprocess.check_call(["make", "-s", "-C", csrc, "convert"])
-    e = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([os.path.join(ROOT, "ffcnn_amd", "bin", "ffgpu_convert_san")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e, timeout=120)
-    err, out = r.stderr.decode(errors="replace"), r.stdout.decode().split("\n")[:-1]
-    assert r.returncode == 0 and "Sanitizer" not in err and "runtime error" not in err, "rc %d\n%s" % (r.returncode, err[-3000:])
-    assert re.fullmatch(r"convert_driver: (\d+) cases, 0 wrong", out[-1]) and int(out[-1].split()[1]) == len(out) - 1 >= 100, out[-1]
+    out = run_driver("convert", "convert")
+    check_summary(out, "convert", 100)
     text = "\n".join(out)
     for msg in ("NULL srcs", "NULL dsts", "0 jobs (1..4096)", "target 3: bad size", "is none of FFGPU_PIX_*", "matrix 4 is none of", "surface: reserved must be 0", "(1..8192 each)",
                 "for a destination of 70 x 35", "pitch[0] 69 is below 70", "pitch[1] 71 is odd", "plane 1's address 0x200001 is odd", "p[2] must be NULL",

@@ -7,12 +7,12 @@ does when no HIP device is visible."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from sanrun import check_summary, run_driver
 from heat import fuzzcases, heatref
 
 SYMBOLS = ["ffgpu_heat_state_bytes", "ffgpu_heat_spec_check", "ffgpu_heat_blend_spec_check", "ffgpu_heat_palette", "ffgpu_heat_reset_dev",
@@ -137,13 +137,8 @@ def test_palette_equals_heatref(capi):
 def test_host_glue_under_the_sanitizers():
     """san/heat_driver.cc: the state's size, the plans of the two specs, the palette and every argument check of ffgpu_heat_host.hpp on the CPU under
     ASan + UBSan, as a child process; the driver checks every case itself.  A sanitizer report aborts the child: the test fails with it."""
-    subprocess.check_call(["make", "-s", "-C", CSRC, "heat"])
-    e = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    exe = os.path.join(ROOT, "ffcnn_amd", "bin", "ffgpu_heat_san")
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e, timeout=120)
-    err, out = r.stderr.decode(errors="replace"), r.stdout.decode().split("\n")[:-1]
-    assert r.returncode == 0 and "Sanitizer" not in err and "runtime error" not in err, "rc %d\n%s" % (r.returncode, err[-3000:])
-    assert re.fullmatch(r"heat_driver: (\d+) cases, 0 wrong", out[-1]) and int(out[-1].split()[1]) == len(out) - 1 >= 120, out[-1]
+    out = run_driver("heat", "heat")
+    check_summary(out, "heat", 120)
     text = "\n".join(out)
     for msg in ("a grid of 0 x 23 cells (1..128 each)", "cell_log2 9 is outside 1..8", "mode 2 is neither FFGPU_HEAT_ANCHOR nor FFGPU_HEAT_BOX", "unknown flags 0x1",
                 "anchor 2 is neither 0 nor 1", "spread 5 is outside 0..4", "spread 2 with FFGPU_HEAT_BOX (0 then)", "gain 65537 is outside 1..65536",
@@ -152,8 +147,7 @@ def test_host_glue_under_the_sanitizers():
                 "NULL rows", "NULL targets", "0 targets", "nstreams 65537", "the state must be 16-byte aligned", "target 1: stream 2 is outside -1 .. 1", "target 3: stream -2",
                 "target 1: bad size 0 x 33", "target 0: pitch 100 is below 3 w = 195", "is odd (U V pairs are written"):
         assert msg in text, msg
-    r = subprocess.run([exe, "palette"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e, timeout=120)
-    assert r.returncode == 0 and r.stdout.decode().split() == [heatref.palette(False).tobytes().hex(), heatref.palette(True).tobytes().hex()]
+    assert run_driver("heat", "heat", "palette") == [heatref.palette(False).tobytes().hex(), heatref.palette(True).tobytes().hex()]
 
 
 def test_heat_without_device(capi):

@@ -6,12 +6,12 @@ vacuously, and the device entry points failing the way every entry point of the 
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from sanrun import check_summary, run_driver
 from motion import fuzzcases, motionref
 
 SYMBOLS = ["ffgpu_motion_state_bytes", "ffgpu_motion_spec_check", "ffgpu_motion_reset_dev", "ffgpu_motion_update_bgr_dev", "ffgpu_motion_update_nv12_dev",
@@ -118,13 +118,8 @@ def test_header_states_the_contract():
 def test_host_glue_under_the_sanitizers():
     """san/motion_driver.cc: the state's layout, the spec's plan, every argument check of ffgpu_motion_host.hpp and the rounds of an update call on the
     CPU under ASan + UBSan, as a child process; the driver checks every case itself.  A sanitizer report aborts the child: the test fails with it."""
-    subprocess.check_call(["make", "-s", "-C", CSRC, "motion"])
-    e = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    exe = os.path.join(ROOT, "ffcnn_amd", "bin", "ffgpu_motion_san")
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e, timeout=120)
-    err, out = r.stderr.decode(errors="replace"), r.stdout.decode().split("\n")[:-1]
-    assert r.returncode == 0 and "Sanitizer" not in err and "runtime error" not in err, "rc %d\n%s" % (r.returncode, err[-3000:])
-    assert re.fullmatch(r"motion_driver: (\d+) cases, 0 wrong", out[-1]) and int(out[-1].split()[1]) == len(out) - 1 >= 100, out[-1]
+    out = run_driver("motion", "motion")
+    check_summary(out, "motion", 100)
     text = "\n".join(out)
     for msg in ("a model of 0 x 33 pixels (1..8192 each)", "a model of 65 x 8193 pixels", "cell_log2 1 is outside 2..6", "cell_log2 7 is outside 2..6", "threshold 0 is outside 1..255",
                 "threshold 256 is outside 1..255", "learn_shift -1 is outside 0..16", "learn_shift 17 is outside 0..16", "learn_shift_changed 17 is outside 0..16",

@@ -7,12 +7,12 @@ device entry points failing the way every entry point of the library does when n
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from sanrun import check_summary, run_driver
 from outlines import fuzzcases, lineref
 from zones import zoneref
 
@@ -476,13 +476,8 @@ def test_outlines_without_device(capi):
 def test_host_glue_under_the_sanitizers():
     """san/lines_driver.cc: the outline spec's plan and every argument check of ffgpu_lines_host.hpp on the CPU under ASan + UBSan, as a child process;
     the driver checks every case itself.  A sanitizer report aborts the child: the test fails with it."""
-    subprocess.check_call(["make", "-s", "-C", CSRC, "lines"])
-    e = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([os.path.join(ROOT, "ffcnn_amd", "bin", "ffgpu_lines_san")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e, timeout=120)
-    err, out = r.stderr.decode(errors="replace"), r.stdout.decode().split("\n")[:-1]
-    assert r.returncode == 0 and "Sanitizer" not in err and "runtime error" not in err, "rc %d\n%s" % (r.returncode, err[-3000:])
-    assert re.fullmatch(r"lines_driver: (\d+) cases, 0 wrong", out[-1]) and int(out[-1].split()[1]) == len(out) - 1 >= 60, out[-1]
-    assert not any("WRONG" in ln for ln in out)
+    out = run_driver("lines", "lines")
+    check_summary(out, "lines", 60)
     for ln in ("plan.color_values holds", "plan.palette_values holds", "spec.every_flag_combination holds", "plan.null_spec -1 op: NULL spec",
                "spec.flags_0 -1 op: flags 0x0 name no part (FFGPU_OUTLINE_ZONES | _LINES | _MARKERS)", "spec.flags_32 -1 op: unknown flags 0x21",
                "spec.ticks_without_lines -1 op: FFGPU_OUTLINE_TICKS without FFGPU_OUTLINE_LINES", "spec.alarm_without_zones -1 op: FFGPU_OUTLINE_ALARM without FFGPU_OUTLINE_ZONES",

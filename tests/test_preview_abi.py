@@ -7,12 +7,12 @@ the device entry points failing the way every entry point of the library does wh
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from sanrun import check_summary, run_driver
 from preview import fuzzcases, previewref
 
 SYMBOLS = ["ffgpu_preview_spec_check", "ffgpu_preview_rect", "ffgpu_preview_grid", "ffgpu_preview_tile", "ffgpu_preview_bgr_dev", "ffgpu_preview_nv12_dev"]
@@ -98,7 +98,7 @@ def test_header_states_the_contract():
     assert kern.count("__global__") == 1 and "template <int CH>\n__global__" in kern    # one kernel template
     assert "static_assert(sizeof(PreviewArgs)" in kern and "4096 - 256" in kern
     mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert mk.count("ffgpu_motion_host.hpp ffgpu_preview_host.hpp") == 2 and "san/preview_driver.cc" in mk
+    assert mk.count("ffgpu_motion_host.hpp ffgpu_preview_host.hpp") == 2 and "preview" in re.search(r"^DRIVERS := (.*)$", mk, re.M).group(1).split()
 
 
 # ------------------------------------------------------------------------------------------------- the host functions against previewref
@@ -162,13 +162,8 @@ def test_preview_grid_equals_previewref(capi):
 def test_host_glue_under_the_sanitizers():
     """san/preview_driver.cc: the spec, resolve, the grid and every argument check of ffgpu_preview_host.hpp on the CPU under ASan + UBSan, as a child
     process; the driver checks every case itself.  A sanitizer report aborts the child: the test fails with it."""
-    subprocess.check_call(["make", "-s", "-C", CSRC, "preview"])
-    e = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    exe = os.path.join(ROOT, "ffcnn_amd", "bin", "ffgpu_preview_san")
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e, timeout=120)
-    err, out = r.stderr.decode(errors="replace"), r.stdout.decode().split("\n")[:-1]
-    assert r.returncode == 0 and "Sanitizer" not in err and "runtime error" not in err, "rc %d\n%s" % (r.returncode, err[-3000:])
-    assert re.fullmatch(r"preview_driver: (\d+) cases, 0 wrong", out[-1]) and int(out[-1].split()[1]) >= len(out) - 1 >= 100, out[-1]
+    out = run_driver("preview", "preview")
+    check_summary(out, "preview", 100, exact=False)
     text = "\n".join(out)
     for msg in ("NULL srcs", "NULL dsts", "NULL panes", "NULL spec", "0 panes (1..4096)", "4097 panes (1..4096)", "fit 3 is neither FFGPU_PREVIEW_STRETCH nor FFGPU_PREVIEW_FIT",
                 "unknown flags 0x4", "unknown flags 0x80000000", "fill[3] must be 0", "spec: reserved must be 0", "source 1: bad size 0 x 48", "destination 3: bad size 40 x -1",

@@ -2,11 +2,8 @@
 bytes a reset clears, and ffgpu_args.hpp's colours, palettes and class tables, under ASan + UBSan (san/streams_driver.cc, run as a child process)."""
 import os
 import re
-import subprocess
 
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "ffcnn_amd", "csrc")
+from sanrun import CSRC, check_summary, run_driver
 
 
 def test_shared_host_pieces_are_plain_cpp_and_written_once():
@@ -28,13 +25,8 @@ def test_shared_host_pieces_are_plain_cpp_and_written_once():
 def test_shared_host_pieces_under_the_sanitizers():
     """san/streams_driver.cc on the CPU under ASan + UBSan, as a child process; the driver checks every case itself.  A sanitizer report aborts the
     child: the test fails with it."""
-    subprocess.check_call(["make", "-s", "-C", CSRC, "streams"])
-    e = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([os.path.join(ROOT, "ffcnn_amd", "bin", "ffgpu_streams_san")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e, timeout=120)
-    err, out = r.stderr.decode(errors="replace"), r.stdout.decode().split("\n")[:-1]
-    assert r.returncode == 0 and "Sanitizer" not in err and "runtime error" not in err, "rc %d\n%s" % (r.returncode, err[-3000:])
-    assert re.fullmatch(r"streams_driver: (\d+) cases, 0 wrong", out[-1]) and int(out[-1].split()[1]) == len(out) - 1 >= 65, out[-1]
-    assert not any("WRONG" in ln for ln in out)
+    out = run_driver("streams", "streams")
+    check_summary(out, "streams", 65)
     for ln in ("three.ntargets_first -1 op: 0 targets (ntargets >= 1)", "three.state_odd -1 op: the state must be 16-byte aligned",
                "range.high -1 op: target 1: stream 2 is outside -1 .. 1", "span.all 0 off=0 len=768", "span.first 0 off=0 len=256", "span.last 0 off=512 len=256",
                "span.which_nstreams -1 reset: stream 3 is outside -1 .. 2", "span.which_m2 -1 reset: stream -2 is outside -1 .. 2",

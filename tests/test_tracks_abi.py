@@ -5,12 +5,12 @@ process), and the device entry points failing the way every entry point of the l
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from sanrun import check_summary, run_driver
 from tracks import trackref
 
 SYMBOLS = ["ffgpu_track_state_bytes", "ffgpu_track_reset_dev", "ffgpu_track_boxes_dev", "ffgpu_exec_track"]
@@ -336,13 +336,8 @@ def test_host_glue_under_the_sanitizers():
     assert "hip/hip_runtime" not in host and "hipStream" not in host                    # plain C++: the sanitizer driver compiles it with no HIP
     inc, drv = open(os.path.join(CSRC, "ffgpu_track.inc")).read(), open(os.path.join(CSRC, "san", "track_driver.cc")).read()
     assert int(re.search(r"#define TRACK_ARG_ENTRIES\s+(\d+)", inc).group(1)) == 128 == int(re.search(r"#define ENTRIES\s+(\d+)", drv).group(1))
-    subprocess.check_call(["make", "-s", "-C", CSRC, "track"])
-    e = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([os.path.join(ROOT, "ffcnn_amd", "bin", "ffgpu_track_san")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e, timeout=120)
-    err, out = r.stderr.decode(errors="replace"), r.stdout.decode().split("\n")[:-1]
-    assert r.returncode == 0 and "Sanitizer" not in err and "runtime error" not in err, "rc %d\n%s" % (r.returncode, err[-3000:])
-    assert re.fullmatch(r"track_driver: (\d+) cases, 0 wrong", out[-1]) and int(out[-1].split()[1]) == len(out) - 1 >= 68, out[-1]
-    assert not any("WRONG" in ln for ln in out)
+    out = run_driver("track", "track")
+    check_summary(out, "track", 68)
     for ln in ("args.stream_high -1 op: target 1: stream 2 is outside -1 .. 1", "args.lists_without_records -1 op: d_out_lists without d_out_records",
                "order.lists_before_streams -1 op: d_out_lists without d_out_records", "spec.min_hits_0 -1 op: min_hits 0 is outside 1..2^20",
                "spec.class_aware_2 -1 op: class_aware 2 is neither 0 nor 1", "bytes.65536_128 %d" % (65536 * (16 + 48 * 128)), "bytes.1_129 0",

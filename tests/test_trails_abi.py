@@ -6,12 +6,12 @@ vacuously, and the device entry points failing the way every entry point of the 
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from sanrun import check_summary, run_driver
 from trails import fuzzcases, trailref
 
 SYMBOLS = ["ffgpu_trails_state_bytes", "ffgpu_trails_spec_check", "ffgpu_trails_reset_dev", "ffgpu_trails_boxes_dev", "ffgpu_exec_trails"]
@@ -335,9 +335,4 @@ def test_trails_without_device(capi):
 def test_host_glue_under_the_sanitizers():
     """san/trails_driver.cc: the state's size, the trails spec's plan and every argument check of ffgpu_trails_host.hpp on the CPU under ASan + UBSan, as
     a child process; the driver checks every case itself.  A sanitizer report aborts the child: the test fails with it."""
-    subprocess.check_call(["make", "-s", "-C", CSRC, "trails"])
-    e = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([os.path.join(ROOT, "ffcnn_amd", "bin", "ffgpu_trails_san")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e, timeout=120)
-    err, out = r.stderr.decode(errors="replace"), r.stdout.decode().split("\n")[:-1]
-    assert r.returncode == 0 and "Sanitizer" not in err and "runtime error" not in err, "rc %d\n%s" % (r.returncode, err[-3000:])
-    assert re.fullmatch(r"trails_driver: (\d+) cases, 0 wrong", out[-1]) and int(out[-1].split()[1]) == len(out) - 1 >= 60, out[-1]
+    check_summary(run_driver("trails", "trails"), "trails", 60)

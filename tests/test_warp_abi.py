@@ -9,12 +9,12 @@ import ctypes as C
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from sanrun import check_summary, run_driver
 from warp import fuzzcases, warpref
 
 SYMBOLS = ["ffgpu_warp_spec_check", "ffgpu_warp_mesh_size", "ffgpu_warp_mesh_orient", "ffgpu_warp_mesh_homography", "ffgpu_warp_mesh_lens", "ffgpu_warp_point",
@@ -119,7 +119,7 @@ def test_header_states_the_contract():
     assert kern.count("__global__") == 1 and "template <int CH>\n__global__" in kern    # one kernel template
     assert "static_assert(sizeof(WarpArgs)" in kern and "4096 - 256" in kern
     mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert mk.count("ffgpu_preview_host.hpp ffgpu_warp_host.hpp") == 2 and "san/warp_driver.cc" in mk
+    assert mk.count("ffgpu_preview_host.hpp ffgpu_warp_host.hpp") == 2 and "warp" in re.search(r"^DRIVERS := (.*)$", mk, re.M).group(1).split()
 
 
 # ------------------------------------------------------------------------------------------------- the exact builders against warpref
@@ -250,13 +250,8 @@ def test_host_glue_under_the_sanitizers():
     """san/warp_driver.cc: the spec, the builders into buffers of exactly the mesh's size, the interpolation rule and every argument check of
     ffgpu_warp_host.hpp on the CPU under ASan + UBSan, as a child process; the driver checks every case itself.  A sanitizer report aborts the child:
     the test fails with it."""
-    subprocess.check_call(["make", "-s", "-C", CSRC, "warp"])
-    e = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    exe = os.path.join(ROOT, "ffcnn_amd", "bin", "ffgpu_warp_san")
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e, timeout=120)
-    err, out = r.stderr.decode(errors="replace"), r.stdout.decode().split("\n")[:-1]
-    assert r.returncode == 0 and "Sanitizer" not in err and "runtime error" not in err, "rc %d\n%s" % (r.returncode, err[-3000:])
-    assert re.fullmatch(r"warp_driver: (\d+) cases, 0 wrong", out[-1]) and int(out[-1].split()[1]) >= len(out) - 1 >= 150, out[-1]
+    out = run_driver("warp", "warp")
+    check_summary(out, "warp", 150, exact=False)
     text = "\n".join(out)
     for msg in ("NULL srcs", "NULL dsts", "NULL meshes", "NULL spec", "0 jobs (1..4096)", "4097 jobs (1..4096)", "filter 3 is neither FFGPU_WARP_BILINEAR nor FFGPU_WARP_NEAREST",
                 "border 4 is neither FFGPU_WARP_FILL nor FFGPU_WARP_CLAMP", "fill[3] must be 0", "spec: reserved must be 0", "source 1: bad size 0 x 48",
