@@ -194,6 +194,11 @@ class MotionSpec(C.Structure):       # ffgpu_motion_spec (64 bytes): the motion 
                 ("classes", C.c_void_p), ("reserved", C.c_int * 2)]
 
 
+class FlowSpec(C.Structure):         # ffgpu_flow_spec (64 bytes): the flow maps' settings, read by the update and by the box operator
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("block_log2", C.c_int), ("range", C.c_int), ("min_spread", C.c_int), ("flags", C.c_int), ("min_score", C.c_float),
+                ("nclasses", C.c_int), ("classes", C.c_void_p), ("reserved", C.c_int * 6)]
+
+
 class PreviewPane(C.Structure):      # ffgpu_preview_pane (32 bytes): a source region of a frame and the pane of a destination surface it is scaled into
     _fields_ = [("sx", C.c_int), ("sy", C.c_int), ("sw", C.c_int), ("sh", C.c_int), ("dx", C.c_int), ("dy", C.c_int), ("dw", C.c_int), ("dh", C.c_int)]
 
@@ -235,6 +240,12 @@ MOTION_ENTRIES, MOTION_MERGED = 0, 1                                            
 MOTION_ROW_HEADER = ("frame", "changed", "active", "x0", "y0", "x1", "y1", "warm")
 MOTION_WORDS_HEADER = ("considered", "dropped", "outside", "moving", "warm", "frames")
 MOTION_STATE_HEADER = 16                                                               # bytes in front of a stream's plane
+FLOW_DETS, FLOW_ROW, FLOW_WORDS, FLOW_MAX_SIDE = 128, 16, 8, 8192                        # FFGPU_FLOW_DETS, _ROW, _WORDS, _MAX_SIDE
+FLOW_ENTRIES, FLOW_MERGED = 0, 1                                                       # FFGPU_FLOW_* (ffgpu_exec_flow_boxes: which)
+FLOW_ROW_HEADER = ("frame", "blocks", "reliable", "moving", "gdx", "gdy", "support")
+FLOW_WORDS_HEADER = ("considered", "dropped", "outside", "frames", "gdx", "gdy", "support")
+FLOW_STATE_HEADER = 16                                                                 # bytes in front of a stream's planes: frames, gdx, gdy, support
+FLOW_RECORD_DTYPE = np.dtype([("dx", "<i2"), ("dy", "<i2"), ("cost", "<u2"), ("spread", "<u2")])
 HEAT_MAX, HEAT_DETS, HEAT_ROW = 2 ** 31 - 1, 128, 8                                    # FFGPU_HEAT_MAX, _DETS, _ROW
 HEAT_ANCHOR, HEAT_BOX = 0, 1                                                           # FFGPU_HEAT_* (ffgpu_heat_spec.mode)
 HEAT_NEAREST, HEAT_SMOOTH = 0, 1                                                       # FFGPU_HEAT_* (ffgpu_heat_blend_spec.sampling)
@@ -283,7 +294,7 @@ assert C.sizeof(TextItem) == 64 and C.sizeof(CaptionSpec) == 48
 assert C.sizeof(SegItem) == 32 and C.sizeof(OutlineSpec) == 40
 assert C.sizeof(TrailPoint) == 12 and C.sizeof(TrailSlot) == 416 and C.sizeof(TrailsSpec) == 64
 assert C.sizeof(HeatSpec) == 56 and C.sizeof(HeatBlendSpec) == 48
-assert C.sizeof(MotionSpec) == 64
+assert C.sizeof(MotionSpec) == 64 and C.sizeof(FlowSpec) == 64
 assert C.sizeof(Zone) == 96 and C.sizeof(Line) == 32 and C.sizeof(Scene) == 1040 and C.sizeof(ZonesSpec) == 32 and C.sizeof(ZoneSlot) == 64
 
 BOX_DTYPE = np.dtype([("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
@@ -338,7 +349,9 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_preview_spec_check", "ffgpu_preview_rect", "ffgpu_preview_grid", "ffgpu_preview_tile", "ffgpu_preview_bgr_dev", "ffgpu_preview_nv12_dev",
            "ffgpu_warp_spec_check", "ffgpu_warp_mesh_size", "ffgpu_warp_mesh_orient", "ffgpu_warp_mesh_homography", "ffgpu_warp_mesh_lens", "ffgpu_warp_point",
            "ffgpu_warp_tile", "ffgpu_warp_bgr_dev", "ffgpu_warp_nv12_dev",
-           "ffgpu_convert_check", "ffgpu_convert_tile", "ffgpu_convert_bgr_dev", "ffgpu_convert_nv12_dev"]
+           "ffgpu_convert_check", "ffgpu_convert_tile", "ffgpu_convert_bgr_dev", "ffgpu_convert_nv12_dev",
+           "ffgpu_flow_state_bytes", "ffgpu_flow_spec_check", "ffgpu_flow_reset_dev", "ffgpu_flow_update_bgr_dev", "ffgpu_flow_update_nv12_dev",
+           "ffgpu_flow_boxes_dev", "ffgpu_exec_flow_boxes"]
 # include/ffcnn_hip_diag.h (libffcnn_hip_diag.so: lab equipment, its own library)
 DIAG_EXPORTS = ["ffgpu_membench", "ffgpu_pipe_probe", "ffgpu_pipe_probe2", "ffgpu_pipe_probe3", "ffgpu_mfma_floor", "ffgpu_diag_x3_term", "ffgpu_diag_xl_op", "ffgpu_clock_probe"]
 
@@ -526,6 +539,14 @@ def lib():
     L.ffgpu_exec_heat.argtypes = [vp, i, C.POINTER(i), i, C.POINTER(HeatSpec), vp, i, vp, vp]
     L.ffgpu_heat_blend_bgr_dev.argtypes = [vp, i, C.POINTER(i), C.POINTER(BgrFrame), i, C.POINTER(HeatBlendSpec), vp]
     L.ffgpu_heat_blend_nv12_dev.argtypes = [vp, i, C.POINTER(i), C.POINTER(Nv12Frame), i, C.POINTER(HeatBlendSpec), vp]
+    L.ffgpu_flow_state_bytes.restype = sz
+    L.ffgpu_flow_state_bytes.argtypes = [i, i, i, i]
+    L.ffgpu_flow_spec_check.argtypes = [C.POINTER(FlowSpec)]
+    L.ffgpu_flow_reset_dev.argtypes = [vp, i, i, i, i, i, vp]
+    L.ffgpu_flow_update_bgr_dev.argtypes = [C.POINTER(BgrFrame), i, C.POINTER(i), C.POINTER(FlowSpec), vp, i, vp, vp]
+    L.ffgpu_flow_update_nv12_dev.argtypes = [C.POINTER(Nv12Frame), i, C.POINTER(i), C.POINTER(FlowSpec), vp, i, vp, vp]
+    L.ffgpu_flow_boxes_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(i), i, C.POINTER(FlowSpec), vp, i, vp, vp]
+    L.ffgpu_exec_flow_boxes.argtypes = [vp, i, C.POINTER(i), i, C.POINTER(FlowSpec), vp, i, vp, vp]
     L.ffgpu_motion_state_bytes.restype = sz
     L.ffgpu_motion_state_bytes.argtypes = [i, i, i, i]
     L.ffgpu_motion_spec_check.argtypes = [C.POINTER(MotionSpec)]
@@ -944,6 +965,13 @@ class Executor:
         buffers (heat_state_bytes; rows of HEAT_ROW ints).  heat_blend_bgr_dev / _nv12_dev show the state in the frames."""
         arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
         _check(lib().ffgpu_exec_heat(self.h, which, arr, len(streams), spec, d_state, nstreams, d_rows, stream), "ffgpu_exec_heat")
+
+    def flow_boxes(self, streams, spec, d_state, nstreams, d_words, which=0, stream=None):
+        """enqueue the flow box operator on the last forward's boxes (which = FLOW_ENTRIES: entry n is record n of video stream streams[n], -1: ignored)
+        or on the last merge's (FLOW_MERGED: picture g) behind it (ffgpu_exec_flow_boxes): spec from flow_spec, d_state what flow_update_*_dev keeps
+        (only read), d_words rows of FLOW_WORDS + 4 S ints."""
+        arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+        _check(lib().ffgpu_exec_flow_boxes(self.h, which, arr, len(streams), spec, d_state, nstreams, d_words, stream), "ffgpu_exec_flow_boxes")
 
     def motion_gate(self, streams, spec, d_state, nstreams, d_words, d_out_records=None, d_out_lists=None, which=0, stream=None):
         """enqueue the motion gate on the last forward's boxes (which = MOTION_ENTRIES: entry n is record n of video stream streams[n], -1: ignored) or
@@ -1683,6 +1711,67 @@ def motion_gate_dev(d_records, d_lists, list_stride, streams, spec, d_state, nst
     first = None if list_first is None else (C.c_int * max(1, len(list_first)))(*[int(v) for v in list_first])
     _check(lib().ffgpu_motion_gate_dev(d_records, d_lists, list_stride, first, arr, len(streams), spec, d_state, nstreams, d_words, d_out_records, d_out_lists, stream),
            "ffgpu_motion_gate_dev")
+
+
+def flow_spec(w, h, block_log2, range_, min_spread=0, min_score=0.0, classes=None):
+    """a FlowSpec (ffgpu_flow_spec): the frames' size, the blocks (1 << block_log2 pixels, 8 or 16), the search range in pixels (1..16), the spread a
+    block is reliable from, and which boxes qualify (min_score, classes as redact_spec).  The structure keeps its class bytes alive."""
+    sp = FlowSpec()
+    sp.w, sp.h, sp.block_log2, sp.range, sp.min_spread, sp.min_score = w, h, block_log2, range_, min_spread, min_score
+    if classes is not None:
+        cls = np.ascontiguousarray(np.asarray(classes) != 0, np.uint8) if len(classes) else np.zeros(1, np.uint8)
+        sp._cls = cls                                           # (owned by the structure: the C side reads it during the call)
+        sp.classes = cls.ctypes.data
+        sp.nclasses = len(classes)
+    return sp
+
+
+def flow_spec_check(spec):
+    """ffgpu_flow_spec_check (pure host code): raises with what is wrong with the spec"""
+    _check(lib().ffgpu_flow_spec_check(spec), "ffgpu_flow_spec_check")
+
+
+def flow_state_bytes(nstreams, w, h, block_log2):
+    return lib().ffgpu_flow_state_bytes(nstreams, w, h, block_log2)
+
+
+def flow_state(raw, nstreams, w, h, block_log2):
+    """(headers as an int32 array of nstreams x 4: frames, gdx, gdy, support; the two luma planes as a uint8 array of nstreams x 2 x h x w; the block
+    records as a FLOW_RECORD_DTYPE array of nstreams x gh x gw) of a state's bytes"""
+    b = 1 << block_log2
+    gw, gh, pitch = (w + b - 1) // b, (h + b - 1) // b, (w + 15) & ~15
+    recs_off = FLOW_STATE_HEADER + 2 * pitch * h
+    one = recs_off + ((8 * gw * gh + 15) & ~15)
+    raw = np.ascontiguousarray(raw, np.uint8).reshape(nstreams, one)
+    return (np.ascontiguousarray(raw[:, :FLOW_STATE_HEADER]).view("<i4"),
+            np.ascontiguousarray(raw[:, FLOW_STATE_HEADER:recs_off].reshape(nstreams, 2, h, pitch)[:, :, :, :w]),
+            np.ascontiguousarray(raw[:, recs_off:recs_off + 8 * gw * gh]).view(FLOW_RECORD_DTYPE).reshape(nstreams, gh, gw))
+
+
+def flow_reset_dev(d_state, nstreams, w, h, block_log2, which_stream=-1, stream=None):
+    """ffgpu_flow_reset_dev: zero the flow state of one video stream, or of all (-1), in stream order"""
+    _check(lib().ffgpu_flow_reset_dev(d_state, nstreams, w, h, block_log2, which_stream, stream), "ffgpu_flow_reset_dev")
+
+
+def flow_update_bgr_dev(frames, streams, spec, d_state, nstreams, d_rows, stream=None):
+    """ffgpu_flow_update_bgr_dev: frames[t] (what bgr_frame_desc accepts, or None: skipped) is the next frame of video stream streams[t] (-1:
+    ignored); a stream's frames are taken in the order given; d_rows: rows of FLOW_ROW ints"""
+    arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+    _check(lib().ffgpu_flow_update_bgr_dev(bgr_frame_table(frames), len(frames), arr, spec, d_state, nstreams, d_rows, stream), "ffgpu_flow_update_bgr_dev")
+
+
+def flow_update_nv12_dev(frames, streams, spec, d_state, nstreams, d_rows, stream=None):
+    """ffgpu_flow_update_nv12_dev: the same on NV12 frames (what nv12_frame_desc accepts, or None: skipped); only the Y plane is read"""
+    arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+    _check(lib().ffgpu_flow_update_nv12_dev(nv12_frame_table(frames), len(frames), arr, spec, d_state, nstreams, d_rows, stream), "ffgpu_flow_update_nv12_dev")
+
+
+def flow_boxes_dev(d_records, d_lists, list_stride, streams, spec, d_state, nstreams, d_words, list_first=None, stream=None):
+    """ffgpu_flow_boxes_dev on device records / lists: record t belongs to video stream streams[t] (-1: ignored); d_lists None: the records' own
+    boxes; list_first as draw_boxes_bgr_dev; d_words: rows of FLOW_WORDS + 4 S ints"""
+    arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+    first = None if list_first is None else (C.c_int * max(1, len(list_first)))(*[int(v) for v in list_first])
+    _check(lib().ffgpu_flow_boxes_dev(d_records, d_lists, list_stride, first, arr, len(streams), spec, d_state, nstreams, d_words, stream), "ffgpu_flow_boxes_dev")
 
 
 def feature_spec(layer=-1, pool=FFGPU.FEAT_MEAN, post=FFGPU.POST_NONE):

@@ -17,6 +17,7 @@
 #include "ffgpu_preview_host.hpp"
 #include "ffgpu_warp_host.hpp"
 #include "ffgpu_convert_host.hpp"
+#include "ffgpu_flow_host.hpp"
 
 #define FFGPU_CHECK(expr)                                                                   \
     do {                                                                                    \
@@ -265,6 +266,9 @@ int ffgpu_launch_heat(const DetSource &src, const int *streams, int ntargets, co
 // motion maps (ffgpu_motion.inc): the gate launches; the checks both entry points share are host code with no HIP in it (ffgpu_motion_host.hpp)
 int ffgpu_launch_motion_gate(const DetSource &src, const int *streams, int ntargets, const MotionPlan &pl, const void *d_state, void *d_words, void *d_out_records,
                              void *d_out_lists, hipStream_t s);
+
+// flow maps (ffgpu_flow.inc): the box launches; the checks both entry points share are host code with no HIP in it (ffgpu_flow_host.hpp)
+int ffgpu_launch_flow_boxes(const DetSource &src, const int *streams, int ntargets, const FlowPlan &pl, const void *d_state, void *d_words, hipStream_t s);
 
 // the crops classified (ffgpu_feature.inc): the checks both entry points share, and the launches.  Features: frame n of the tensor is frame n % pn of
 // parts[n / pn], a CNHW tensor of pn frames (a split executor has one part per chain; at most 8).

@@ -1577,6 +1577,22 @@ extern "C" int ffgpu_exec_motion_gate(ffgpu_exec *ex, int which, const int *stre
     return ffgpu_launch_motion_gate(src, streams, ntargets, pl, d_state, d_words, d_out_records, d_out_lists, s);
 }
 
+// -------------------------------------------------------------------------- flow maps (include/ffcnn_hip.h; kernels: ffgpu_flow.inc)
+// A post-pass like the motion gate, on the stream of the forward or merge it follows: reads the records and full lists (per entry, or the merged ones)
+// and the caller's flow state, writes the caller's words and nothing of the executor's.  The update has no executor form: it reads frames, not records.
+extern "C" int ffgpu_exec_flow_boxes(ffgpu_exec *ex, int which, const int *streams, int ntargets, const ffgpu_flow_spec *spec, const void *d_state, int nstreams,
+                                     void *d_words, void *stream)
+{
+    const char *const what = "exec_flow_boxes";
+    if (!exec_ok(ex, what)) return -1;
+    FlowPlan pl;
+    if (ffgpu_flow_boxes_args_check(what, streams, ntargets, spec, d_state, nstreams, d_words, pl)) return -1;
+    DetSource src;
+    hipStream_t s;
+    if (exec_source(ex, what, "FLOW", "flow boxes", STRIDE_REFUSED, which, ntargets, stream, src, &s)) return -1;
+    return ffgpu_launch_flow_boxes(src, streams, ntargets, pl, d_state, d_words, s);
+}
+
 // -------------------------------------------------------------------------- captions (include/ffcnn_hip.h; kernels: ffgpu_text.inc)
 // A post-pass like the draw, on the stream of the forward or merge it follows, in two launches: the items composed from the records and full lists (per
 // entry, or the merged ones) into the caller's d_items, then rasterised into the caller's frames.  Nothing of the executor's is written.

@@ -1987,6 +1987,109 @@ int ffgpu_convert_tile(int out[3]);
 int ffgpu_convert_bgr_dev (const ffgpu_surface *srcs, const ffgpu_bgr_frame  *dsts, int njobs, void *stream);
 int ffgpu_convert_nv12_dev(const ffgpu_surface *srcs, const ffgpu_nv12_frame *dsts, int njobs, void *stream);
 
+/* ---- flow maps: block-matching vectors per stream, the camera's shift, the boxes' motion relative to it ---------------------------------------------
+ * The motion maps answer "did these pixels change"; this family answers "where did they go".  Per video stream it keeps the luma of the last two
+ * frames in the caller's device memory and, per block of 8 x 8 or 16 x 16 pixels, the integer vector that carries the previous frame's content into
+ * the block -- an exhaustive search of every vector within +-range, by the sum of absolute differences --, the vector most blocks agree on (a
+ * panning camera: the GLOBAL vector) and, for the boxes of any record, the motion of the blocks under a box relative to it: a velocity for a box
+ * seen for the first time.  Integers throughout; no global atomics; one owner per written byte; the same bytes on every run; total over any state
+ * bytes (tests/flow/flowref.py restates it in numpy).
+ *
+ * Geometry, from the spec: frames are w x h pixels; a block is b = 1 << block_log2 pixels wide and high, anchored at pixel (0, 0); the grid is
+ * gw = ceil(w / b) by gh = ceil(h / b) blocks, the last column and row partial where b does not divide w or h.  A partial block is the set of its
+ * pixels inside the frame.
+ *
+ * State, in the caller's device memory (16-byte aligned, ffgpu_flow_state_bytes(nstreams, w, h, block_log2) bytes; all-zero is the valid empty
+ * state, so hipMemsetAsync or ffgpu_flow_reset_dev initialises it).  Per stream, in this order:
+ *   1. a header { int frames; int gdx; int gdy; int support; };
+ *   2. two luma PLANES P0 and P1: each h rows of ALIGN(w, 16) bytes, row-major; the padding bytes of a row are never written;
+ *   3. gw * gh block RECORDS { short dx; short dy; unsigned short cost; unsigned short spread; }, row-major, rounded up to 16 bytes (the rounding
+ *      bytes are never written).
+ * Planes and records are documented, readable products.
+ *
+ * UPDATE.  One frame of one stream; f = the header's `frames` before it.  Luma as the motion maps take it: NV12: the Y byte (the UV plane is not
+ * read); BGR: y = (29 B + 150 G + 77 R + 128) >> 8.  The frame's luma `cur` is written into P[f & 1]; `prev` is P[(f & 1) ^ 1].
+ *   If f == 0 every record is { 0, 0, 0, 0 } and gdx = gdy = support = 0.
+ *   Otherwise, for every block B: the CANDIDATES are the vectors v = (vx, vy) with |vx|, |vy| <= range such that p - v lies inside the frame for
+ *     every pixel p of B (the zero vector always is one); cost(v) = the sum over p in B of |cur(p) - prev(p - v)|, at most 256 * 255 = 65280;
+ *     (dx, dy) = the candidate that is least under the total order (cost, vx vx + vy vy, vy, vx); `cost` its cost; spread = min(the largest cost
+ *     over the candidates - cost, 65535).  So v is the motion of the content from the previous frame to this one; a flat block has spread 0; a
+ *     periodic texture resolves to its shortest vector.
+ *   A block is RELIABLE when spread >= max(min_spread, 1).  The GLOBAL vector (gdx, gdy) is the vector held by the most reliable blocks, ties to the
+ *     least under (vx vx + vy vy, vy, vx); `support` is that number of blocks; with no reliable block it is (0, 0) with support 0.  A block is MOVING
+ *     when it is reliable and its vector is not the global one.
+ * Then frames += 1 (modulo 2^32), the header is written, and row t of FFGPU_FLOW_ROW ints, every byte written: { frame (f), blocks (gw gh),
+ * reliable, moving, gdx, gdy, support, 0 x 9 }.
+ * Targets: streams[t] == -1 or a NULL pixel address leaves the state alone, and the row is zero (the size of such a target is not looked at).  Any
+ * other target whose w or h differ from the spec's is rejected.  A stream may appear several times in one call; its frames are then in time
+ * order, and the result is byte for byte what one call per frame leaves.
+ *
+ * BOXES.  Only reads the state, AS IT IS WHEN THE LAUNCH RUNS IN STREAM ORDER.  Per record t of stream streams[t]:
+ *   Considered boxes: step 1 of the heat contract with the cap FFGPU_FLOW_DETS; further qualifying boxes are counted in `dropped`.
+ *   A considered box is clipped to w x h as the motion gate clips it; an inverted box or an empty clip is counted in `outside`, with touched = 0.
+ *     Otherwise touched = the blocks from (X0 >> k, Y0 >> k) to (X1 >> k, Y1 >> k), k = block_log2; reliable = those among them with
+ *     spread >= max(min_spread, 1); sum_dx, sum_dy = the sums over those reliable blocks of dx - gdx and dy - gdy, in 32-bit wrapping arithmetic
+ *     (exact for every state an update leaves; any order gives the same bits): the object's motion relative to the camera, times `reliable`.
+ *   d_words (required): row t of 8 + 4 S ints (S = the list stride), every byte written: { considered, dropped, outside, frames, gdx, gdy, support,
+ *     0 }, then { touched, reliable, sum_dx, sum_dy } per list box, zero for a box that was not considered.
+ *   streams[t] == -1: every int of the row is zero.
+ * The composition: decode, convert, warp, motion update and flow update, forward, flow boxes and motion gate, then the other passes.
+ * Deliberately not built: sub-pixel vectors, a pyramid, a motion update compensated by the global vector, a tracker that predicts from the box
+ * flow. */
+#define FFGPU_FLOW_DETS     128  /* considered boxes per record at most */
+#define FFGPU_FLOW_ROW      16   /* ints of an update row */
+#define FFGPU_FLOW_WORDS    8    /* ints in front of a box row's { touched, reliable, sum_dx, sum_dy } */
+#define FFGPU_FLOW_MAX_SIDE 8192 /* w and h at most */
+typedef struct {
+    int   w, h;                    /* 1..8192: the size of the stream's frames */
+    int   block_log2;              /* 3..4: a block is b = 1 << block_log2 pixels wide and high */
+    int   range;                   /* 1..16: the search range in pixels, either way, in x and in y */
+    int   min_spread;              /* 0..65535: a block is reliable from this spread on (0 behaves as 1) */
+    int   flags;                   /* 0; any set bit is rejected */
+    float min_score;               /* any value: a box qualifies from this score on (NaN: none does); read by the box operator */
+    int   nclasses;                /* 0 with NULL classes, else 1..256 */
+    const unsigned char *classes;  /* HOST, nclasses bytes, non-zero = allowed; NULL: every type; read by the box operator */
+    int   reserved[6];             /* 0 */
+} ffgpu_flow_spec;                 /* 64 bytes: w 0, h 4, block_log2 8, range 12, min_spread 16, flags 20, min_score 24, nclasses 28, classes 32, */
+                                   /* reserved 40 */
+
+/* pure host code: the bytes of the state of nstreams (1..65536) streams of w x h (1..8192 each) pixels with blocks of 1 << block_log2 (3..4); 0 for
+ * arguments outside their ranges */
+size_t ffgpu_flow_state_bytes(int nstreams, int w, int h, int block_log2);
+/* pure host code: 0, or -1 with the message in ffgpu_last_error */
+int ffgpu_flow_spec_check(const ffgpu_flow_spec *spec);
+/* zeroes the state of one stream, or of all with which_stream == -1, in stream order (a memset; no kernel) */
+int ffgpu_flow_reset_dev(void *d_state, int nstreams, int w, int h, int block_log2, int which_stream, void *stream);
+
+/* The update operators.  targets (the frames, as the draw operators take them; only read), streams and spec are HOST memory and free again on
+ * return.  The host enqueues ROUND r -- the r-th occurrence of every stream in the call -- behind round r - 1: stream order is the barrier.  A round
+ * is two launches per 64 targets.  k_flow_match: a workgroup owns a tile of 64 x 32 pixels -- 32 blocks of 8 x 8 or 8 of 16 x 16 --, reads the
+ * frame's bytes once, writes the luma into the current plane with 16-byte stores, stages it and the previous plane's window with its halo in LDS,
+ * and spreads (block, vy, four consecutive vx) over its lanes: four costs a lane in one packed 16-bit accumulator (v_qsad_pk_u16_u8), misaligned
+ * windows built from aligned LDS dwords, the winner and every tie settled by one min over a key, one lane storing each record.  Then a small launch,
+ * one workgroup per target, that votes the reliable blocks' vectors in LDS and writes the header and the row.  The match launch only reads `frames`.
+ * No global atomics.  Enqueued without synchronising.  Rejected before anything is enqueued, with the target's index where there is one: everything
+ * the motion update rejects that applies here, in its words; every spec field outside its range, set flag bits, a reserved field that is not 0, a
+ * state that is not 16-byte aligned.  A rejected call leaves the state as it was. */
+int ffgpu_flow_update_bgr_dev(const ffgpu_bgr_frame *targets, int ntargets, const int *streams, const ffgpu_flow_spec *spec, void *d_state,
+                              int nstreams, void *d_rows, void *stream);
+int ffgpu_flow_update_nv12_dev(const ffgpu_nv12_frame *targets, int ntargets, const int *streams, const ffgpu_flow_spec *spec, void *d_state,
+                               int nstreams, void *d_rows, void *stream);
+
+/* The box operator, on device records and lists with no executor.  d_records, d_lists, list_stride and the HOST array list_first are the draw
+ * operators'; streams and spec (with its classes) are HOST memory and free again on return.  One workgroup per record, 64 records per launch, the
+ * tables travelling as a kernel argument.  Enqueued without synchronising.  Rejected before anything is launched: the reasons of
+ * ffgpu_motion_gate_dev that apply, and the spec as above. */
+int ffgpu_flow_boxes_dev(const void *d_records, const void *d_lists, int list_stride, const int *list_first, const int *streams, int ntargets,
+                         const ffgpu_flow_spec *spec, const void *d_state, int nstreams, void *d_words, void *stream);
+
+#define FFGPU_FLOW_ENTRIES 0   /* entry n's full post-NMS list is record n; ntargets == batch; S = ffgpu_exec_cand_capacity               */
+#define FFGPU_FLOW_MERGED  1   /* picture g's merged list (last ffgpu_exec_merge_tiles) is record g; ntargets == its nimages; S as FFGPU_ZONES_MERGED */
+/* On an executor: a post-pass exactly like ffgpu_exec_motion_gate, with its stream, FFGPU_SPLIT2 and MERGED rules and its rejections, and no gated
+ * record.  The captured graph, the records, the full lists, the ring and the host mirror are untouched; the state is only read. */
+int ffgpu_exec_flow_boxes(ffgpu_exec *ex, int which, const int *streams, int ntargets, const ffgpu_flow_spec *spec, const void *d_state, int nstreams,
+                          void *d_words, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
