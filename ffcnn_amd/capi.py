@@ -199,6 +199,11 @@ class FlowSpec(C.Structure):         # ffgpu_flow_spec (64 bytes): the flow maps
                 ("nclasses", C.c_int), ("classes", C.c_void_p), ("reserved", C.c_int * 6)]
 
 
+class BlobsSpec(C.Structure):        # ffgpu_blobs_spec (64 bytes): the motion blobs' settings
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("cell_log2", C.c_int), ("min_pixels", C.c_int), ("warmup", C.c_int), ("connect", C.c_int), ("min_cells", C.c_int),
+                ("max_cells", C.c_int), ("max_boxes", C.c_int), ("pad", C.c_int), ("type", C.c_int), ("flags", C.c_int), ("reserved", C.c_int * 4)]
+
+
 class PreviewPane(C.Structure):      # ffgpu_preview_pane (32 bytes): a source region of a frame and the pane of a destination surface it is scaled into
     _fields_ = [("sx", C.c_int), ("sy", C.c_int), ("sw", C.c_int), ("sh", C.c_int), ("dx", C.c_int), ("dy", C.c_int), ("dw", C.c_int), ("dh", C.c_int)]
 
@@ -246,6 +251,8 @@ FLOW_ROW_HEADER = ("frame", "blocks", "reliable", "moving", "gdx", "gdy", "suppo
 FLOW_WORDS_HEADER = ("considered", "dropped", "outside", "frames", "gdx", "gdy", "support")
 FLOW_STATE_HEADER = 16                                                                 # bytes in front of a stream's planes: frames, gdx, gdy, support
 FLOW_RECORD_DTYPE = np.dtype([("dx", "<i2"), ("dy", "<i2"), ("cost", "<u2"), ("spread", "<u2")])
+BLOBS_WORDS, BLOBS_MAX_CELLS, BLOBS_COMPONENTS = 8, 32768, 2048                        # FFGPU_BLOBS_WORDS, _MAX_CELLS, _COMPONENTS
+BLOBS_WORDS_HEADER = ("active", "components", "kept", "written", "untabled", "warm", "frames")
 HEAT_MAX, HEAT_DETS, HEAT_ROW = 2 ** 31 - 1, 128, 8                                    # FFGPU_HEAT_MAX, _DETS, _ROW
 HEAT_ANCHOR, HEAT_BOX = 0, 1                                                           # FFGPU_HEAT_* (ffgpu_heat_spec.mode)
 HEAT_NEAREST, HEAT_SMOOTH = 0, 1                                                       # FFGPU_HEAT_* (ffgpu_heat_blend_spec.sampling)
@@ -294,7 +301,7 @@ assert C.sizeof(TextItem) == 64 and C.sizeof(CaptionSpec) == 48
 assert C.sizeof(SegItem) == 32 and C.sizeof(OutlineSpec) == 40
 assert C.sizeof(TrailPoint) == 12 and C.sizeof(TrailSlot) == 416 and C.sizeof(TrailsSpec) == 64
 assert C.sizeof(HeatSpec) == 56 and C.sizeof(HeatBlendSpec) == 48
-assert C.sizeof(MotionSpec) == 64 and C.sizeof(FlowSpec) == 64
+assert C.sizeof(MotionSpec) == 64 and C.sizeof(FlowSpec) == 64 and C.sizeof(BlobsSpec) == 64
 assert C.sizeof(Zone) == 96 and C.sizeof(Line) == 32 and C.sizeof(Scene) == 1040 and C.sizeof(ZonesSpec) == 32 and C.sizeof(ZoneSlot) == 64
 
 BOX_DTYPE = np.dtype([("type", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
@@ -351,7 +358,7 @@ EXPORTS = ["net_load", "net_free", "net_input", "net_forward", "net_dump", "net_
            "ffgpu_warp_tile", "ffgpu_warp_bgr_dev", "ffgpu_warp_nv12_dev",
            "ffgpu_convert_check", "ffgpu_convert_tile", "ffgpu_convert_bgr_dev", "ffgpu_convert_nv12_dev",
            "ffgpu_flow_state_bytes", "ffgpu_flow_spec_check", "ffgpu_flow_reset_dev", "ffgpu_flow_update_bgr_dev", "ffgpu_flow_update_nv12_dev",
-           "ffgpu_flow_boxes_dev", "ffgpu_exec_flow_boxes"]
+           "ffgpu_flow_boxes_dev", "ffgpu_exec_flow_boxes", "ffgpu_blobs_spec_check", "ffgpu_blobs_dev"]
 # include/ffcnn_hip_diag.h (libffcnn_hip_diag.so: lab equipment, its own library)
 DIAG_EXPORTS = ["ffgpu_membench", "ffgpu_pipe_probe", "ffgpu_pipe_probe2", "ffgpu_pipe_probe3", "ffgpu_mfma_floor", "ffgpu_diag_x3_term", "ffgpu_diag_xl_op", "ffgpu_clock_probe"]
 
@@ -547,6 +554,8 @@ def lib():
     L.ffgpu_flow_update_nv12_dev.argtypes = [C.POINTER(Nv12Frame), i, C.POINTER(i), C.POINTER(FlowSpec), vp, i, vp, vp]
     L.ffgpu_flow_boxes_dev.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(i), i, C.POINTER(FlowSpec), vp, i, vp, vp]
     L.ffgpu_exec_flow_boxes.argtypes = [vp, i, C.POINTER(i), i, C.POINTER(FlowSpec), vp, i, vp, vp]
+    L.ffgpu_blobs_spec_check.argtypes = [C.POINTER(BlobsSpec)]
+    L.ffgpu_blobs_dev.argtypes = [C.POINTER(i), i, C.POINTER(BlobsSpec), vp, i, vp, vp, vp, vp]
     L.ffgpu_motion_state_bytes.restype = sz
     L.ffgpu_motion_state_bytes.argtypes = [i, i, i, i]
     L.ffgpu_motion_spec_check.argtypes = [C.POINTER(MotionSpec)]
@@ -1772,6 +1781,27 @@ def flow_boxes_dev(d_records, d_lists, list_stride, streams, spec, d_state, nstr
     arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
     first = None if list_first is None else (C.c_int * max(1, len(list_first)))(*[int(v) for v in list_first])
     _check(lib().ffgpu_flow_boxes_dev(d_records, d_lists, list_stride, first, arr, len(streams), spec, d_state, nstreams, d_words, stream), "ffgpu_flow_boxes_dev")
+
+
+def blobs_spec(w, h, cell_log2, min_pixels, warmup=0, connect=8, min_cells=1, max_cells=0, max_boxes=FFGPU.MAX_DET, pad=0, type_=0):
+    """a BlobsSpec (ffgpu_blobs_spec): the motion state's geometry and min_pixels, the frames a stream stays silent for, the neighbourhood (4 or
+    8), which components are kept (min_cells <= cells <= max_cells, 0: no upper limit), how many boxes are written, their margin in pixels and type"""
+    sp = BlobsSpec()
+    sp.w, sp.h, sp.cell_log2, sp.min_pixels, sp.warmup, sp.connect, sp.min_cells, sp.max_cells = w, h, cell_log2, min_pixels, warmup, connect, min_cells, max_cells
+    sp.max_boxes, sp.pad, sp.type = max_boxes, pad, type_
+    return sp
+
+
+def blobs_spec_check(spec):
+    """ffgpu_blobs_spec_check (pure host code): raises with what is wrong with the spec"""
+    _check(lib().ffgpu_blobs_spec_check(spec), "ffgpu_blobs_spec_check")
+
+
+def blobs_dev(streams, spec, d_state, nstreams, d_words, d_out_records, d_labels=None, stream=None):
+    """ffgpu_blobs_dev: target t is video stream streams[t] (-1: ignored) of the state motion_update_*_dev keeps (only read); d_words: rows of
+    BLOBS_WORDS ints; d_out_records: an ffgpu_frame_dets per target; d_labels (optional): gw * gh uint16 per target, pitched by ALIGN(gw * gh, 8)"""
+    arr = (C.c_int * max(1, len(streams)))(*[int(v) for v in streams])
+    _check(lib().ffgpu_blobs_dev(arr, len(streams), spec, d_state, nstreams, d_words, d_out_records, d_labels, stream), "ffgpu_blobs_dev")
 
 
 def feature_spec(layer=-1, pool=FFGPU.FEAT_MEAN, post=FFGPU.POST_NONE):

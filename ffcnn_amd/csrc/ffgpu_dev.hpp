@@ -18,6 +18,7 @@
 #include "ffgpu_warp_host.hpp"
 #include "ffgpu_convert_host.hpp"
 #include "ffgpu_flow_host.hpp"
+#include "ffgpu_blobs_host.hpp"
 
 #define FFGPU_CHECK(expr)                                                                   \
     do {                                                                                    \

@@ -709,6 +709,7 @@ extern "C" int ffgpu_pack_records(const void *d_records, int nslots, long slot_s
 #include "ffgpu_warp.inc"
 #include "ffgpu_convert.inc"
 #include "ffgpu_flow.inc"
+#include "ffgpu_blobs.inc"
 #include "ffgpu_feature.inc"
 #include "ffgpu_match.inc"
 

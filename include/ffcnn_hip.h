@@ -2090,6 +2090,75 @@ int ffgpu_flow_boxes_dev(const void *d_records, const void *d_lists, int list_st
 int ffgpu_exec_flow_boxes(ffgpu_exec *ex, int which, const int *streams, int ntargets, const ffgpu_flow_spec *spec, const void *d_state, int nstreams,
                           void *d_words, void *stream);
 
+/* ---- motion blobs: the active cells of a stream's motion state labelled into connected components, the components written as boxes ----------------
+ * The motion gate takes boxes a detector produced and says whether they move.  This family is the PRODUCER: "something moved there", whatever it is
+ * -- a dropped bag, an animal, smoke, a person too small for the net.  It only reads the state ffgpu_motion_update_*_dev keeps and writes a record
+ * per target in the layout every consumer takes (d_lists == NULL): track, zones, trails, heat, draw, caption, crop, redact.  "Track and count
+ * everything that moves" is three calls: update, blobs, track.  Integers throughout; integer LDS atomics only (sums, minima, maxima: any order gives
+ * the same bits), no global atomics; one owner per written byte; the same bytes on every run; total over any state bytes
+ * (tests/blobs/blobref.py restates it in numpy with a flood fill).
+ *
+ * Geometry is the motion state's (w, h, cell_log2 as ffgpu_motion_spec; c = 1 << cell_log2; gw x gh cells), with gw * gh <= FFGPU_BLOBS_MAX_CELLS:
+ * 1920 x 1080 at cells of 8, 3840 x 2160 at cells of 16.  A cell is ACTIVE when its stored count is >= min_pixels, compared unsigned, as in the gate.
+ *
+ * Per target t of stream streams[t], reading the state AS IT IS WHEN THE LAUNCH RUNS IN STREAM ORDER:
+ *   1. Warm-up.  A stream with frames <= warmup (compared modulo 2^32, as in the gate) reports NOTHING: the record and the labels are zero and the
+ *      words are { 0, 0, 0, 0, 0, 0, frames, 0 }.  The gate fails OPEN while the model learns, so that no detection is lost; a motion detector
+ *      must not fire on a model that knows nothing yet, so this operator fails CLOSED.
+ *   2. Components: those of the active cells under 4-connectivity (left, right, up, down) or 8-connectivity (and the diagonals), by `connect`.  A
+ *      component's ROOT is the smallest raster index y * gw + x among its cells; components are numbered by ascending root.  The first
+ *      FFGPU_BLOBS_COMPONENTS are TABLED; any further ones are counted in `untabled` and never reported.
+ *   3. Per tabled component: cells = the number of its cells; area = the sum over its cells of the cell's pixel area clipped to w x h
+ *      ((min(c (x + 1), w) - c x) (min(c (y + 1), h) - c y)); pixels = the sum over its cells of min(count, that cell's clipped area), so at most
+ *      2^27 whatever the counts are; the cell bounding box i0..i1, j0..j1.
+ *   4. KEPT are the tabled components with min_cells <= cells and, where max_cells != 0, cells <= max_cells, ordered by pixels descending, then cells
+ *      descending, then root ascending.  WRITTEN are the first max_boxes of them.
+ *   5. The box of a written component: X0 = max(c i0 - pad, 0), Y0 = max(c j0 - pad, 0), X1 = min(min(c (i1 + 1), w) - 1 + pad, w - 1), Y1 likewise;
+ *      { type, score, (float)X0, (float)Y0, (float)X1, (float)Y1 }.  The coordinates are INCLUSIVE pixels: the draw contract's truncated corners land
+ *      on the blob's outermost pixels, and with pad == 0 the gate's `touched` is exactly the component's cell bounding box.  score = q / 256.0f with
+ *      q = min(256, pixels * 256 / area), an integer division: exact, no float division.
+ *   6. Outputs; every byte is written, for streams[t] == -1 as zero.
+ *      d_words (required): row t of FFGPU_BLOBS_WORDS ints { active, components, kept, written, untabled, warm (1), frames, 0 }.
+ *      d_out_records (required): ffgpu_frame_dets t: count = nfull = written, ncand = kept, overflow bit 0 = kept > written or untabled > 0 and no
+ *        other bit, the boxes in the order of step 4, unused box slots zero.
+ *      d_labels (may be NULL): for target t, gw * gh unsigned shorts at t x ALIGN(gw * gh, 8) shorts, row-major: 0 an inactive cell, r + 1 a cell of
+ *        the component written as box r, 0xFFFF an active cell of any other component.  The padding shorts are not written.
+ * A stream may appear several times in one call; every occurrence reads the same state and gives the same bytes.
+ *
+ * k_blobs: one workgroup of 1024 lanes per target, 64 targets per launch, the table of streams travelling as a kernel argument; the whole grid
+ * lives in LDS (136 KB at 240 x 135 cells, 148 KB at most, raised above the 64 KB default per kernel and device).  The cells are read coalesced, a wave's ballot is
+ * one 64-bit word of a row's mask; runs and their overlaps with the row above are bit arithmetic on the masks; a lock-free union-find over the
+ * runs (roots hooked toward the smaller index by an atomic min, paths compressed) makes the time independent of a component's shape; the roots are
+ * ranked in raster order, the table is accumulated per run segment, the kept entries are sorted by a bitonic network over one 64-bit key.
+ * Enqueued without synchronising.  streams and spec are HOST memory and free again on return.  Rejected before anything is enqueued, with the
+ * target's index where there is one: NULL streams, spec, state, words or records, ntargets < 1, nstreams outside 1..65536, a state that is not
+ * 16-byte aligned, a stream index outside -1..nstreams-1, every spec field outside its range, a grid of more than FFGPU_BLOBS_MAX_CELLS cells,
+ * flags or reserved words that are not 0.
+ * Deliberately not built: morphological closing or joining of nearby components, larger grids, an executor form, per-pixel masks. */
+#define FFGPU_BLOBS_WORDS      8     /* ints of a words row */
+#define FFGPU_BLOBS_MAX_CELLS  32768 /* gw * gh at most */
+#define FFGPU_BLOBS_COMPONENTS 2048  /* tabled components per target at most */
+typedef struct {
+    int   w, h;                    /* 1..8192: the motion state's geometry */
+    int   cell_log2;               /* 2..6: the motion state's geometry */
+    int   min_pixels;              /* 1..c c: a cell is active from this count on */
+    int   warmup;                  /* 0..65535: a stream with frames <= warmup reports nothing */
+    int   connect;                 /* 4 or 8: the neighbourhood */
+    int   min_cells;               /* 1..32768: the smallest component kept */
+    int   max_cells;               /* 0: no limit, else min_cells..32768: the largest component kept */
+    int   max_boxes;               /* 1..FFGPU_MAX_DET: boxes written per target */
+    int   pad;                     /* 0..256: pixels added round each box, clipped to the frame */
+    int   type;                    /* any value: the `type` of every box written */
+    int   flags;                   /* 0 */
+    int   reserved[4];             /* 0 */
+} ffgpu_blobs_spec;                /* 64 bytes: w 0, h 4, cell_log2 8, min_pixels 12, warmup 16, connect 20, min_cells 24, max_cells 28, max_boxes 32, */
+                                   /* pad 36, type 40, flags 44, reserved 48 */
+
+/* pure host code: 0, or -1 with the message in ffgpu_last_error */
+int ffgpu_blobs_spec_check(const ffgpu_blobs_spec *spec);
+int ffgpu_blobs_dev(const int *streams, int ntargets, const ffgpu_blobs_spec *spec, const void *d_state, int nstreams, void *d_words, void *d_out_records,
+                    void *d_labels, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
